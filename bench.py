@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Mrays/s (primary, closest-hit) on BASELINE.json's configs.
 
-    python bench.py --gpus N --steps K --warmup W [--config C3|C2|C5]
+    python bench.py --gpus N --steps K --warmup W [--config C3|C2|C5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch.
@@ -45,6 +45,9 @@ import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
 N_SIMD = 256 * 4       # 256 CUs x 4 SIMD-32 (same guide)
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: records written at most (48 B each with their index: about 50 MB)
+DUMP_SEED = 0xD0D0     # --dump-outputs: stream of synth.splitmix64 that picks the sample
+DUMP_MAX_BYTES = 64 * 1000 * 1000
 
 
 def parse():
@@ -68,7 +71,13 @@ def parse():
     ap.add_argument("--gather", default="tokens", choices=["tokens", "records"],
                     help="what travels to rank 0 at N > 1: 4-byte hit tokens (records rebuilt on rank 0, bit-identical) or the records")
     ap.add_argument("--grid-tile", type=int, default=0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the hit records of the last one as DIR/<field>.npy (float32 / float64; "
+                         f"a fixed sample of {DUMP_SAMPLE} records when there are more, DIR/index.npy says which)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def one_socket_cpus():
@@ -181,6 +190,30 @@ def digest_of(hits_u8: torch.Tensor, first_index: int = 0) -> dict:
     prim = rec[:, 1].contiguous().cpu().numpy()
     t = rec[:, 0].contiguous().cpu().numpy().view(np.float32)
     return digests.digest_columns(prim, t, first_index)
+
+
+def dump_outputs(image: torch.Tensor, directory: str) -> dict:
+    """--dump-outputs: the 32-byte hit records the last timed step left (rank 0: every view, or the whole grid, in order)
+    as one .npy per field of mrt_hit32, float32 where the field is, float64 for the integer fields.  More than
+    DUMP_SAMPLE records: the same seeded sample every run (index.npy = the record numbers, ascending), so two builds
+    given the same arguments can be compared array for array."""
+    from messyerraytracer_amd import synth, types as T
+    rec = image.reshape(-1).view(torch.int32).view(-1, 8)
+    n = rec.shape[0]
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(synth.splitmix64(DUMP_SEED, 0, DUMP_SAMPLE) % np.uint64(n)).astype(np.int64)
+    rows = np.ascontiguousarray(rec[torch.from_numpy(idx).to(rec.device)].cpu().numpy()).view(T.HIT32).reshape(-1)
+    arrays = {"index": idx.astype(np.float64), "t": rows["t"], "prim_id": rows["prim_id"].astype(np.float64),
+              "bary_u": rows["bary_u"], "bary_v": rows["bary_v"], "normal": rows["normal"],
+              "hit_layers": rows["hit_layers"].astype(np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr))
+    return dict(dir=directory, records=int(n), written=int(idx.size), bytes=int(total), files=sorted(k + ".npy" for k in arrays))
 
 
 def main():
@@ -377,6 +410,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = dump_outputs(last, a.dump_outputs) if a.dump_outputs and rank == 0 and last is not None else None
 
     # ---- what the timed launches wrote: digest of the last frame against the oracle's digest of the whole batch ----
     verified = None
@@ -439,6 +473,8 @@ def main():
         out["source_sha16"] = source_sha16()   # of messyerraytracer_amd/csrc: what committed counter passes are keyed on
         if verified is not None:
             out["verified"] = verified
+        if dumped is not None:
+            out["outputs"] = dumped
         # ---- roofline of the dominant kernel --------------------------------------------------------------------
         if events:  # queued casts: detection kernel + trace kernel between the two events
             trace_ms.extend(e0.elapsed_time(e1) for (e0, e1) in events)

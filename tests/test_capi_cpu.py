@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, gpu_present
 from messyerraytracer_amd import capi, synth, types as T
 from oracle import pyoracle as po
 
@@ -63,8 +63,7 @@ def test_null_arguments_are_rejected_not_crashed(built):
 
 def test_create_without_gpu_fails_loudly(built):
     """No silent CPU fallback: without a device mrt_create reports MRT_ERR_NO_DEVICE."""
-    import torch
-    if torch.cuda.is_available():
+    if gpu_present():
         pytest.skip("a GPU is present")
     with pytest.raises(capi.MrtError) as e:
         capi.Context(0)
@@ -79,8 +78,7 @@ def test_options_are_validated_before_a_device_is_asked_for(built):
             capi.Context(0, **kw)
         assert e.value.status == capi.ERR_INVALID, kw
     assert capi.kernel_name(capi.KERNEL_PACKET_QUAD) == "trace_packet_quad_kernel"
-    import torch
-    if not torch.cuda.is_available():
+    if not gpu_present():
         for kw in (dict(kernel=capi.KERNEL_PACKET_DUAL), dict(packet_wg=64, packet_cull=2, tile_schedule=1)):
             with pytest.raises(capi.MrtError) as e:
                 capi.Context(0, **kw)

@@ -3,6 +3,7 @@ import ctypes as C
 
 import pytest
 
+from conftest import gpu_present
 from messyerraytracer_amd import capi, sharded
 from oracle import digests
 import numpy as np
@@ -19,7 +20,6 @@ def test_row_blocks_tile_the_grid_and_match_the_torch_path(built, rows, n):
 
 
 def test_group_without_a_device_fails_loudly(built):
-    import torch
     L = capi.load()
     h = C.c_void_p()
     assert L.mrt_group_create(0, None, None, C.byref(h)) == capi.ERR_INVALID
@@ -27,7 +27,7 @@ def test_group_without_a_device_fails_loudly(built):
     assert L.mrt_group_size(None) == 0 and L.mrt_group_context(None, 0) is None
     assert L.mrt_group_cast_grid(None, None, 0, 0, None, 0, 0, 0) == capi.ERR_INVALID
     L.mrt_group_destroy(None)
-    if not torch.cuda.is_available():
+    if not gpu_present():
         assert L.mrt_group_create(2, None, None, C.byref(h)) == capi.ERR_NO_DEVICE   # never a CPU fallback
         with pytest.raises(capi.MrtError):
             capi.Group([0])

@@ -15,7 +15,15 @@ MAIN = os.path.join(ROOT, "tests", "san", "host_san_test.cpp")
 OUT = os.path.join(ROOT, "tests", "san", "_build")
 
 
-def _build_and_run(name, flags, env):
+def _without_aslr():
+    """`setarch -R` where it is allowed: ThreadSanitizer's runtime rejects the layout of hosts whose kernel randomises
+    addresses with more bits than it knows ("unexpected memory mapping"); one process without randomisation runs anywhere."""
+    if shutil.which("setarch") is None or subprocess.run(["setarch", "-R", "true"], capture_output=True).returncode != 0:
+        return []
+    return ["setarch", "-R"]
+
+
+def _build_and_run(name, flags, env, launcher=()):
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     os.makedirs(OUT, exist_ok=True)
@@ -26,7 +34,7 @@ def _build_and_run(name, flags, env):
         cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-mfma", "-Wall"] + flags + SRC + [MAIN, "-o", exe, "-pthread"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe, os.path.join(OUT, name + "_cache.bin")], capture_output=True, text=True, timeout=900,
+    r = subprocess.run(list(launcher) + [exe, os.path.join(OUT, name + "_cache.bin")], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, **env))
     report = r.stdout[-2000:] + r.stderr[-6000:]
     assert r.returncode == 0, report
@@ -42,4 +50,4 @@ def test_host_code_under_asan_and_ubsan():
 
 def test_host_threads_under_tsan():
     """The builder's worker threads (>= 50 000 triangles) and the CPU backend's pool."""
-    _build_and_run("host_san_tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1"})
+    _build_and_run("host_san_tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1"}, _without_aslr())
