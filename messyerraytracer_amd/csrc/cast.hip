@@ -1,0 +1,403 @@
+// cast.hip — the casts of the C-ABI: mrt_cast / mrt_submit / mrt_collect (rays from arrays), mrt_cast_grid (rays made in the
+// kernel), mrt_cast_tiled.  launch_policy.cpp plans every cast (which kernel, how launched); launch_planned runs the plan.
+#include <cstdio>
+#include <cstring>
+#include <atomic>
+#include <thread>
+#include <utility>
+#include <vector>
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
+#include "mrt_context.h"
+
+namespace {
+
+// Sorts ray indices by direction Morton key on the device; returns the permutation in idx_out.
+int device_sort(mrt_ctx *ctx, const void *d_rays, uint32_t in_fmt, uint64_t count, const uint32_t **perm)
+{
+	if (count > 0xFFFFFFFFull) return fail(ctx, MRT_ERR_UNSUPPORTED, "sorted batches are limited to 2^32-1 rays");
+	int rc;
+	if ((rc = ensure(ctx, ctx->keys_in, count * 4)) || (rc = ensure(ctx, ctx->keys_out, count * 4)) ||
+			(rc = ensure(ctx, ctx->idx_in, count * 4)) || (rc = ensure(ctx, ctx->idx_out, count * 4))) return rc;
+	uint32_t *ki = (uint32_t *)ctx->keys_in.ptr, *ko = (uint32_t *)ctx->keys_out.ptr;
+	uint32_t *ii = (uint32_t *)ctx->idx_in.ptr, *io = (uint32_t *)ctx->idx_out.ptr;
+	if (ctx->opts.sort_key == 1) // the reference's direction-only key (ray_sort.h:64-76)
+		HIP_TRY(ctx, mrt::launch_morton_keys(d_rays, in_fmt, count, ki, ii, ctx->stream));
+	else // origin cell first, then direction: groups rays whose origins are scattered too
+		HIP_TRY(ctx, mrt::launch_origin_dir_keys(d_rays, in_fmt, count, ctx->bounds_lo, ctx->bounds_hi, ki, ii, ctx->stream));
+	size_t tmp_bytes = 0;
+	HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, ki, ko, ii, io, (size_t)count, 0, 30, ctx->stream));
+	if ((rc = ensure(ctx, ctx->sort_tmp, tmp_bytes ? tmp_bytes : 16))) return rc;
+	HIP_TRY(ctx, rocprim::radix_sort_pairs(ctx->sort_tmp.ptr, tmp_bytes, ki, ko, ii, io, (size_t)count, 0, 30, ctx->stream));
+	*perm = io;
+	return MRT_OK;
+}
+
+mrt::SceneFacts scene_facts(const mrt_ctx *ctx)
+{
+	mrt::SceneFacts s;
+	s.two_level = ctx->two_level != nullptr; s.rows = ctx->d_rows != nullptr; s.rows4 = ctx->d_rows4 != nullptr;
+	s.nodes4 = ctx->d_nodes4 != nullptr; s.nodes8 = ctx->d_nodes8 != nullptr;
+	s.n_nodes = ctx->n_nodes; s.depth = ctx->depth; s.stack4 = ctx->stack4; s.stack8 = ctx->stack8;
+	s.cu_count = (uint32_t)ctx->cu_count;
+	return s;
+}
+
+mrt::CastPlan plan(mrt_ctx *ctx, const mrt::CastRequest &r)
+{
+	const mrt::PrevDetect prev{ctx->pending, ctx->last_detect_count, {ctx->h_auto[0], ctx->h_auto[1], ctx->h_auto[2], ctx->h_auto[3]}};
+	return mrt::plan_cast(ctx->opts, scene_facts(ctx), r, prev, ctx->knobs, ctx->grids);
+}
+
+void note_queued(mrt_ctx *ctx, uint32_t kernel)
+{
+	ctx->queued_kernel = kernel;
+	std::snprintf(ctx->queued_variant, sizeof(ctx->queued_variant), "%s", mrt::last_trace_variant());
+}
+
+int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uint64_t count, bool any_hit)
+{
+	int rc;
+	p.kernel = l.kernel;
+	if (!l.persistent) {
+		p.sparse_lanes = l.sparse_lanes;
+		HIP_TRY(ctx, mrt::launch_trace(p, any_hit, l.count, ctx->stream));
+		note_queued(ctx, p.kernel);
+		return MRT_OK;
+	}
+	uint32_t *ovf = nullptr;
+	if (l.spill) { // deeper entries spill to [depth - lds_depth][thread] in HBM
+		if ((rc = ensure(ctx, ctx->overflow, (size_t)l.spill * l.blocks * 256u * 4u))) return rc;
+		ovf = (uint32_t *)ctx->overflow.ptr;
+	}
+	// eight ray counters (one per region of the batch), 128 bytes apart
+	unsigned long long *next_ray = ctx->d_counters + mrt::kNextRayOff;
+	HIP_TRY(ctx, hipMemsetAsync(next_ray, 0, 128 * sizeof(unsigned long long), ctx->stream));
+	HIP_TRY(ctx, mrt::launch_trace_persistent(p, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, any_hit, l.count, ctx->stream));
+	note_queued(ctx, p.kernel);
+	return MRT_OK;
+}
+
+// Runs a plan on the context's stream: pre-processing of rays from an array (sort, detect) from ev[2] to ev[3] (last_sort_ms), the
+// trace launches from ev[3] to ev[4] (last_trace_ms), then the sort of a measuring frame's tile costs on the side stream.  p holds
+// the batch (rays, hits, formats, grid); the plan decides the rest.
+int launch_planned(mrt_ctx *ctx, const mrt::CastPlan &c, const mrt::CastRequest &r, mrt::TraceParams &p)
+{
+	int rc;
+	const bool rays = mrt::ray_entry(r.entry), any = r.mode == MRT_MODE_ANY_HIT;
+	const auto zero_counters = [&] { return hipMemsetAsync(ctx->d_counters, 0, mrt::kNumCounters * sizeof(unsigned long long), ctx->stream); };
+	p.kernel = c.kernel; p.lane_map = c.lane_map; p.quarter_all = c.quarter_all;
+	if (rays) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+	if (c.sort) {
+		const uint32_t *perm = nullptr;
+		if ((rc = device_sort(ctx, p.rays, p.in_fmt, r.count, &perm))) return rc;
+		p.perm = perm;
+	}
+	if (c.detect) {
+		uint32_t *d_auto = reinterpret_cast<uint32_t *>(ctx->d_counters + mrt::kAutoGridOff);
+		HIP_TRY(ctx, mrt::launch_detect_grid(p.rays, p.in_fmt, r.count, p.tile_w_log2, ctx->d_counters + mrt::kDetectScratchOff, d_auto, ctx->d_auto_host, ctx->stream));
+		p.auto_grid = d_auto;
+	}
+	if (rays && ctx->opts.count_visits) HIP_TRY(ctx, zero_counters());
+	if (c.scheduled && (rc = schedule_grid(ctx, c, p))) return rc;
+	if (rays) ctx->last_detect_count = c.detect ? r.count : 0;
+	HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+	if (!rays && ctx->opts.count_visits) HIP_TRY(ctx, zero_counters());
+	ctx->queued_detect = c.detect; ctx->queued_alt_kernel = 0;
+	if (c.launch == mrt::CastPlan::DUAL) {
+		p.skip_flag = p.auto_grid + 3; p.skip_when = 1u;
+		HIP_TRY(ctx, mrt::launch_trace(p, any, c.count, ctx->stream));
+		note_queued(ctx, p.kernel);
+		mrt::TraceParams lp = p;
+		lp.lane_map = mrt::MAP_LINEAR; lp.auto_grid = nullptr; lp.skip_when = 0u; lp.quarter_all = 0u;
+		std::swap(ctx->queued_kernel, ctx->queued_alt_kernel); std::swap(ctx->queued_variant, ctx->queued_alt_variant);
+		if ((rc = launch_lane(ctx, c.lane, lp, r.count, any))) return rc; // runs if the batch is judged incoherent
+		std::swap(ctx->queued_kernel, ctx->queued_alt_kernel); std::swap(ctx->queued_variant, ctx->queued_alt_variant);
+	} else if (c.launch == mrt::CastPlan::LANE) {
+		if ((rc = launch_lane(ctx, c.lane, p, r.count, any))) return rc;
+	} else {
+		HIP_TRY(ctx, mrt::launch_trace(p, any, c.count, ctx->stream));
+		note_queued(ctx, p.kernel);
+	}
+	HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+	if (c.scheduled && (rc = schedule_sort(ctx))) return rc;
+	if (c.launches) ctx->stats.last_kernel_launches = c.launches;
+	ctx->stats.rays_cast += r.count;
+	return MRT_OK;
+}
+
+// Enqueue H2D (if needed) + optional sort + trace.  On return the kernels are queued on ctx->stream.
+int enqueue_cast(mrt_ctx *ctx, mrt::Entry entry, const void *rays, void *hits_dev_or_null, uint64_t count, uint32_t query_mask,
+		int mode, uint32_t flags, void **d_hits_out)
+{
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded (is_available() == false)");
+	if (mode != MRT_MODE_NEAREST && mode != MRT_MODE_ANY_HIT) return fail(ctx, MRT_ERR_INVALID, "bad mode");
+	if ((flags & MRT_FLAG_BOOL_OUT) && mode != MRT_MODE_ANY_HIT) return fail(ctx, MRT_ERR_INVALID, "BOOL_OUT needs any-hit mode");
+	if ((flags & MRT_FLAG_BOOL_OUT) && (flags & MRT_FLAG_TOKEN_OUT)) return fail(ctx, MRT_ERR_INVALID, "BOOL_OUT and TOKEN_OUT exclude each other");
+	const size_t rs = ray_stride(flags), hs = hit_stride(ctx, flags, mode);
+	int rc;
+	const void *d_rays = rays;
+	ctx->stats.last_h2d_ms = ctx->stats.last_d2h_ms = ctx->stats.last_sort_ms = 0.0f;
+	if (!(flags & MRT_FLAG_RAYS_ON_DEVICE)) {
+		if ((rc = ensure(ctx, ctx->rays, count * rs))) return rc;
+		HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->rays.ptr, rays, count * rs, hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+		d_rays = ctx->rays.ptr;
+	}
+	void *d_hits = hits_dev_or_null;
+	if (!d_hits) {
+		if ((rc = ensure(ctx, ctx->hits, count * hs))) return rc;
+		d_hits = ctx->hits.ptr;
+	}
+	mrt::TraceParams p;
+	base_params(ctx, p);
+	p.rays = d_rays; p.hits = d_hits; p.count = count; p.query_mask = query_mask;
+	p.in_fmt = (flags & MRT_FLAG_HOST_LAYOUT) ? mrt::IN_HOST60 : mrt::IN_RAY32;
+	p.out_fmt = out_format(ctx, flags, mode);
+	const mrt::CastRequest r{entry, count, flags, mode};
+	if ((rc = launch_planned(ctx, plan(ctx, r), r, p))) return rc;
+	*d_hits_out = d_hits;
+	return MRT_OK;
+}
+
+constexpr uint64_t kSmallCast = 1024; // rays: host-array casts up to this size take the mapped-memory path of mrt_cast
+
+int finish_timing(mrt_ctx *ctx, bool h2d, bool sorted, bool d2h)
+{
+	float ms = 0.0f;
+	if (h2d) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); ctx->stats.last_h2d_ms = ms; }
+	if (sorted) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3])); ctx->stats.last_sort_ms = ms; }
+	HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4])); ctx->stats.last_trace_ms = ms;
+	if (d2h) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5])); ctx->stats.last_d2h_ms = ms; }
+	// which kernel did the work: the stream has been waited for, so detect_grid_kernel's words are in h_auto
+	ctx->stats.detected_grid_w = ctx->queued_detect ? ctx->h_auto[0] : 0u;
+	ctx->stats.reserved = ctx->queued_detect ? ctx->h_auto[3] : 0u; // 1: the "coherent" batch was judged incoherent
+	const bool alt_ran = ctx->queued_detect && ctx->queued_alt_kernel && ctx->h_auto[3];
+	ctx->stats.last_kernel = alt_ran ? ctx->queued_alt_kernel : ctx->queued_kernel;
+	std::snprintf(ctx->last_variant, sizeof(ctx->last_variant), "%s", alt_ran ? ctx->queued_alt_variant : ctx->queued_variant);
+	if (ctx->opts.count_visits) {
+		unsigned long long c[mrt::kNumCounters];
+		HIP_TRY(ctx, hipMemcpy(c, ctx->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+		ctx->stats.tri_tests += c[mrt::kCntTris]; ctx->stats.bvh_nodes_visited += c[mrt::kCntNodes]; ctx->stats.hits += c[mrt::kCntHits];
+		if ((uint32_t)c[mrt::kCntMaxStack] > ctx->stats.max_stack_depth) ctx->stats.max_stack_depth = (uint32_t)c[mrt::kCntMaxStack];
+		ctx->stats.dead_pops += c[mrt::kCntDeadPops];
+		ctx->stats.wave_node_fetches += c[mrt::kCntWaveNodeFetch]; ctx->stats.wave_tri_fetches += c[mrt::kCntWaveTriFetch];
+		ctx->stats.leaf_box_checks += c[mrt::kCntLeafBoxChecks];
+		ctx->stats.fetch_wait_cycles += c[mrt::kCntFetchWaitCycles]; ctx->stats.wave_cycles += c[mrt::kCntWaveCycles];
+		ctx->stats.waves += c[mrt::kCntWaves];
+	}
+	return MRT_OK;
+}
+
+// Host arrays in, host arrays out (the reference's cast_rays contract), large batch: upload, trace and
+// download run as a pipeline over 2^20-ray chunks.  A pageable copy occupies the host thread that
+// issues it, so uploads are issued from the calling thread and downloads from a helper thread: both
+// PCIe directions then move data at once, and the trace of a chunk hides between them.
+constexpr uint64_t kPipeChunk = 1ull << 20;
+
+int cast_host_pipelined(mrt_ctx *ctx, const void *rays, void *hits, uint64_t count, uint32_t query_mask, int mode, uint32_t flags)
+{
+	const size_t rs = ray_stride(flags), hs = hit_stride(ctx, flags, mode);
+	const uint32_t n_chunks = (uint32_t)((count + kPipeChunk - 1) / kPipeChunk);
+	int rc;
+	if ((rc = ensure(ctx, ctx->rays, count * rs)) || (rc = ensure(ctx, ctx->hits, count * hs))) return rc;
+	if (!ctx->up_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
+	if (!ctx->dn_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->dn_stream, hipStreamNonBlocking));
+	while (ctx->pipe_ev.size() < 2u * n_chunks) {
+		hipEvent_t e;
+		HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		ctx->pipe_ev.push_back(e);
+	}
+	char *d_rays = (char *)ctx->rays.ptr, *d_hits = (char *)ctx->hits.ptr;
+	std::atomic<uint32_t> traced{0};      // chunks whose trace has been queued (their event is recorded)
+	std::atomic<int> stop{0}, down_err{0};
+	std::thread down([&] {
+		if (hipSetDevice(ctx->device) != hipSuccess) { down_err = (int)hipErrorInvalidDevice; return; }
+		for (uint32_t k = 0; k < n_chunks; k++) {
+			while (traced.load(std::memory_order_acquire) <= k) { if (stop.load()) return; std::this_thread::yield(); }
+			const uint64_t off = (uint64_t)k * kPipeChunk, n = count - off < kPipeChunk ? count - off : kPipeChunk;
+			hipError_t e = hipEventSynchronize(ctx->pipe_ev[2 * k + 1]);
+			if (e == hipSuccess) e = hipMemcpyAsync((char *)hits + off * hs, d_hits + off * hs, n * hs, hipMemcpyDeviceToHost, ctx->dn_stream);
+			if (e == hipSuccess) e = hipStreamSynchronize(ctx->dn_stream);
+			if (e != hipSuccess) { down_err = (int)e; return; }
+		}
+	});
+	const uint32_t dev_flags = flags | MRT_FLAG_RAYS_ON_DEVICE | MRT_FLAG_HITS_ON_DEVICE;
+	hipError_t e = hipSuccess;
+	uint32_t launches = 0;
+	for (uint32_t k = 0; k < n_chunks && e == hipSuccess && rc == MRT_OK && !down_err.load(); k++) {
+		const uint64_t off = (uint64_t)k * kPipeChunk, n = count - off < kPipeChunk ? count - off : kPipeChunk;
+		e = hipMemcpyAsync(d_rays + off * rs, (const char *)rays + off * rs, n * rs, hipMemcpyHostToDevice, ctx->up_stream);
+		if (e == hipSuccess) e = hipEventRecord(ctx->pipe_ev[2 * k], ctx->up_stream);
+		if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->pipe_ev[2 * k], 0);
+		if (e != hipSuccess) break;
+		void *unused = nullptr;
+		rc = enqueue_cast(ctx, mrt::ENTRY_CHUNK, d_rays + off * rs, d_hits + off * hs, n, query_mask, mode, dev_flags, &unused);
+		if (rc) break;
+		if (ctx->stats.last_kernel_launches > launches) launches = ctx->stats.last_kernel_launches;
+		e = hipEventRecord(ctx->pipe_ev[2 * k + 1], ctx->stream);
+		if (e == hipSuccess) traced.store(k + 1, std::memory_order_release);
+	}
+	if (e != hipSuccess || rc != MRT_OK) stop = 1;
+	down.join();
+	(void)hipStreamSynchronize(ctx->stream);
+	if (rc) return rc;
+	if (e != hipSuccess || down_err.load()) {
+		std::snprintf(ctx->err, sizeof(ctx->err), "pipelined cast failed: %s", hipGetErrorString(e != hipSuccess ? e : (hipError_t)down_err.load()));
+		return MRT_ERR_HIP;
+	}
+	ctx->stats.last_kernel_launches = launches;
+	ctx->stats.last_h2d_ms = ctx->stats.last_d2h_ms = 0.0f; // overlapped: not separable (last_trace_ms is the last chunk's)
+	return finish_timing(ctx, false, launches >= 2, false);
+}
+
+} // namespace
+
+extern "C" {
+
+int mrt_cast(mrt_ctx *ctx, const void *rays, void *hits, uint64_t count, uint32_t query_mask, int mode, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (count == 0) return ctx->scene ? MRT_OK : fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded"); // cpp:419: silent no-op
+	if (!rays || !hits) return fail(ctx, MRT_ERR_INVALID, "null rays / hits");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	void *d_hits = nullptr;
+	const bool hits_dev = (flags & MRT_FLAG_HITS_ON_DEVICE) != 0;
+	if ((flags & MRT_FLAG_ASYNC) && !(hits_dev && (flags & MRT_FLAG_RAYS_ON_DEVICE)))
+		return fail(ctx, MRT_ERR_INVALID, "ASYNC needs device-resident rays and hits");
+	if (!hits_dev && !(flags & MRT_FLAG_RAYS_ON_DEVICE) && count >= 2 * kPipeChunk && !ctx->opts.count_visits) {
+		if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded (is_available() == false)");
+		return cast_host_pipelined(ctx, rays, hits, count, query_mask, mode, flags);
+	}
+	// Latency path: host arrays of at most kSmallCast rays skip both DMA copies: the kernel reads the rays from, and
+	// writes the records to, pinned host memory mapped into the device (one ray: 85 -> 55 us per blocking call,
+	// tools/bench_latency.py).  The same kernels, the same records.
+	if (!hits_dev && !(flags & (MRT_FLAG_RAYS_ON_DEVICE | MRT_FLAG_ASYNC)) && count <= kSmallCast && !ctx->opts.count_visits) {
+		const size_t rs_ = ray_stride(flags), hs_ = hit_stride(ctx, flags, mode);
+		if (!ctx->h_small_in) {
+			if (hipHostMalloc(&ctx->h_small_in, kSmallCast * 64, hipHostMallocMapped) != hipSuccess ||
+					hipHostMalloc(&ctx->h_small_out, kSmallCast * 64, hipHostMallocMapped) != hipSuccess ||
+					hipHostGetDevicePointer(&ctx->d_small_in, ctx->h_small_in, 0) != hipSuccess ||
+					hipHostGetDevicePointer(&ctx->d_small_out, ctx->h_small_out, 0) != hipSuccess) {
+				if (ctx->h_small_in) (void)hipHostFree(ctx->h_small_in);
+				if (ctx->h_small_out) (void)hipHostFree(ctx->h_small_out);
+				ctx->h_small_in = ctx->h_small_out = ctx->d_small_in = ctx->d_small_out = nullptr;
+				(void)hipGetLastError();
+			}
+		}
+		if (ctx->h_small_in) {
+			std::memcpy(ctx->h_small_in, rays, count * rs_);
+			int rc2 = enqueue_cast(ctx, mrt::ENTRY_CAST, ctx->d_small_in, ctx->d_small_out, count, query_mask, mode, flags | MRT_FLAG_RAYS_ON_DEVICE, &d_hits);
+			if (rc2) return rc2;
+			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			std::memcpy(hits, ctx->h_small_out, count * hs_);
+			return finish_timing(ctx, false, ctx->stats.last_kernel_launches >= 2, false);
+		}
+	}
+	int rc = enqueue_cast(ctx, mrt::ENTRY_CAST, rays, hits_dev ? hits : nullptr, count, query_mask, mode, flags, &d_hits);
+	if (rc) return rc;
+	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; } // queued on the context's stream; no timing
+	if (!hits_dev) {
+		HIP_TRY(ctx, hipMemcpyAsync(hits, d_hits, count * hit_stride(ctx, flags, mode), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+	}
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	rc = finish_timing(ctx, !(flags & MRT_FLAG_RAYS_ON_DEVICE), ctx->stats.last_kernel_launches >= 2, !hits_dev);
+	if (rc == MRT_OK) mrt::tune_record(ctx->grids.tune(), ctx->stats.last_trace_ms);
+	return rc;
+}
+
+int mrt_submit(mrt_ctx *ctx, const void *rays, uint64_t count, uint32_t query_mask, int mode, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "submit while a dispatch is pending (gpu_ray_caster.cpp:538)");
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
+	if (count == 0) return MRT_OK;
+	if (!rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
+	if (flags & (MRT_FLAG_HITS_ON_DEVICE | MRT_FLAG_ASYNC)) return fail(ctx, MRT_ERR_INVALID, "submit keeps results in the context; use mrt_cast for device outputs");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	void *d_hits = nullptr;
+	int rc = enqueue_cast(ctx, mrt::ENTRY_SUBMIT, rays, nullptr, count, query_mask, mode, flags, &d_hits);
+	if (rc) return rc;
+	ctx->pending = true; ctx->pending_count = count; ctx->pending_flags = flags; ctx->pending_mode = mode;
+	ctx->pending_dev_hits = d_hits;
+	return MRT_OK;
+}
+
+int mrt_collect(mrt_ctx *ctx, void *hits, uint64_t count)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (!ctx->pending) return fail(ctx, MRT_ERR_NOT_PENDING, "collect without a pending dispatch");
+	if (!hits) return fail(ctx, MRT_ERR_INVALID, "null hits");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const uint64_t n = count < ctx->pending_count ? count : ctx->pending_count; // cpp:573
+	HIP_TRY(ctx, hipMemcpyAsync(hits, ctx->pending_dev_hits, n * hit_stride(ctx, ctx->pending_flags, ctx->pending_mode),
+			hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->pending = false;
+	return finish_timing(ctx, !(ctx->pending_flags & MRT_FLAG_RAYS_ON_DEVICE), ctx->stats.last_kernel_launches >= 2, true);
+}
+
+int mrt_has_pending(const mrt_ctx *ctx) { return ctx && ctx->pending ? 1 : 0; }
+
+int mrt_cast_grid(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h,
+		uint32_t y0, uint32_t y1, void *hits, uint32_t query_mask, int mode, uint32_t flags)
+{
+	if (!ctx || !hits) return MRT_ERR_INVALID;
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (flags & MRT_FLAG_HOST_LAYOUT) return fail(ctx, MRT_ERR_UNSUPPORTED, "grid casts write packed hits");
+	if ((flags & MRT_FLAG_BOOL_OUT) && (flags & MRT_FLAG_TOKEN_OUT)) return fail(ctx, MRT_ERR_INVALID, "BOOL_OUT and TOKEN_OUT exclude each other");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	mrt::TraceParams p;
+	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
+	if (rc) return rc;
+	if (p.count == 0) return MRT_OK;
+	const size_t hs = hit_stride(ctx, flags, mode);
+	const bool hits_dev = (flags & MRT_FLAG_HITS_ON_DEVICE) != 0;
+	if ((flags & MRT_FLAG_ASYNC) && !hits_dev) return fail(ctx, MRT_ERR_INVALID, "ASYNC needs device-resident hits");
+	void *d_hits = hits;
+	if (!hits_dev) { if ((rc = ensure(ctx, ctx->hits, p.count * hs))) return rc; d_hits = ctx->hits.ptr; }
+	p.hits = d_hits; p.query_mask = query_mask;
+	p.out_fmt = out_format(ctx, flags, mode);
+	const mrt::CastRequest r{mrt::ENTRY_GRID, p.count, flags, mode, grid_w, grid_h, y0, p.rows};
+	if ((rc = launch_planned(ctx, plan(ctx, r), r, p))) return rc;
+	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
+	if (!hits_dev) {
+		HIP_TRY(ctx, hipMemcpyAsync(hits, d_hits, p.count * hs, hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+	}
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
+	rc = finish_timing(ctx, false, false, !hits_dev);
+	if (rc == MRT_OK) mrt::tune_record(ctx->grids.tune(), ctx->stats.last_trace_ms);
+	return rc;
+}
+
+int mrt_cast_tiled(mrt_ctx *ctx, const mrt_ray32 *d_rays, mrt_hit32 *d_hits,
+		uint32_t grid_w, uint32_t rows, uint32_t query_mask, int mode)
+{
+	if (!ctx || !d_rays || !d_hits || grid_w == 0) return MRT_ERR_INVALID;
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (rows == 0) return MRT_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	mrt::TraceParams p;
+	base_params(ctx, p);
+	p.rays = d_rays; p.hits = d_hits; p.count = (uint64_t)grid_w * rows; p.query_mask = query_mask;
+	p.in_fmt = mrt::IN_RAY32; p.out_fmt = mrt::OUT_HIT32;
+	p.grid_w = grid_w; p.grid_h = rows; p.y0 = 0; p.rows = rows;
+	const mrt::CastRequest r{mrt::ENTRY_TILED, p.count, 0u, mode, grid_w, rows, 0u, rows};
+	const mrt::CastPlan c = plan(ctx, r);
+	p.tiles_x = c.tiles_x;
+	int rc = launch_planned(ctx, c, r, p);
+	if (rc) return rc;
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
+	return finish_timing(ctx, false, false, false);
+}
+
+} // extern "C"

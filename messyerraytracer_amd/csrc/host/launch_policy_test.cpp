@@ -1,0 +1,332 @@
+// launch_policy_test.cpp — pins the cast launch policy (launch_policy.cpp) without a device: a table of casts and the plan
+// each one must get, then the grid kernel tuner over fifteen frames with fake timings and the per-grid state LRU.
+// Exit status 0 iff every check holds; one line per failure.
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include "../launch_policy.h"
+
+using namespace mrt;
+
+namespace {
+
+int failures = 0, checks = 0;
+void expect(bool ok, const std::string &what)
+{
+	checks++;
+	if (!ok) { failures++; std::printf("FAIL %s\n", what.c_str()); }
+}
+
+const char *kname(uint32_t k)
+{
+	switch (k) {
+		case MRT_KERNEL_LANE: return "lane";
+		case MRT_KERNEL_PACKET_ASM: return "asm";
+		case MRT_KERNEL_LANE_PERSISTENT: return "lp";
+		case MRT_KERNEL_LANE4_PERSISTENT: return "l4p";
+		case MRT_KERNEL_LANE8_PERSISTENT: return "l8p";
+		case MRT_KERNEL_PACKET_DUAL: return "dual";
+		case MRT_KERNEL_PACKET_ROWS: return "rows";
+		case MRT_KERNEL_PACKET_QUAD: return "quad";
+		case MRT_KERNEL_TWO_LEVEL: return "tl";
+		case MRT_KERNEL_TWO_LEVEL_PACKET: return "tlpkt";
+		case MRT_KERNEL_TWO_LEVEL_PERSISTENT: return "tlp";
+		case MRT_KERNEL_TWO_LEVEL_PERSISTENT8: return "tlp8";
+		default: return "?";
+	}
+}
+
+// one line per plan: k=<kernel> map=<lanes> q=<quarter_all> <launch>(<lane launch>) [sort] [detect] [sched=WxR/tiles_x[+pieces][+wait]] [arms] n=<launches> [cnt]
+std::string describe(const CastPlan &c)
+{
+	static const char *maps[] = {"lin", "tile", "auto"};
+	char b[256];
+	int n = std::snprintf(b, sizeof(b), "k=%s map=%s q=%u ", kname(c.kernel), maps[c.lane_map], c.quarter_all);
+	if (c.launch == CastPlan::PLAIN) n += std::snprintf(b + n, sizeof(b) - n, "plain");
+	else {
+		const LaneLaunch &l = c.lane;
+		n += std::snprintf(b + n, sizeof(b) - n, "%s(%s ", c.launch == CastPlan::DUAL ? "dual" : "lane", kname(l.kernel));
+		if (l.persistent) n += std::snprintf(b + n, sizeof(b) - n, "pers blocks=%u lds=%u spill=%u wait=%u", l.blocks, l.lds_depth, l.spill, l.leaf_wait);
+		else n += std::snprintf(b + n, sizeof(b) - n, "sparse=%u", l.sparse_lanes);
+		n += std::snprintf(b + n, sizeof(b) - n, "%s)", l.count ? " cnt" : "");
+	}
+	if (c.sort) n += std::snprintf(b + n, sizeof(b) - n, " sort");
+	if (c.detect) n += std::snprintf(b + n, sizeof(b) - n, " detect");
+	if (c.scheduled) n += std::snprintf(b + n, sizeof(b) - n, " sched=%ux%u/%u%s%s", c.grid_w, c.rows, c.tiles_x, c.pieces ? "+pieces" : "", c.wait_sorts ? "+wait" : "");
+	if (c.arms_tuner) n += std::snprintf(b + n, sizeof(b) - n, " arms");
+	n += std::snprintf(b + n, sizeof(b) - n, " n=%u%s", c.launches, c.count ? " cnt" : "");
+	return b;
+}
+
+// scenes: a flat one with every layout, without the row array, with nothing but the 2-wide nodes, with 2-wide nodes only
+// and no 8-wide ones, past the 32-bit node offsets of the hand-written loop; two-level with and without 8-wide BLASes
+enum { FLAT, NO_ROWS, BARE, NO8, BIG, TL, TL_NO8 };
+SceneFacts scene(int k)
+{
+	SceneFacts s;
+	s.rows = s.nodes4 = s.nodes8 = true; s.n_nodes = 40000; s.depth = 20; s.stack4 = 12; s.stack8 = 10;
+	if (k == NO_ROWS) s.rows = false;
+	if (k == BARE) s.rows = s.nodes4 = s.nodes8 = false;
+	if (k == NO8) s.nodes8 = false;
+	if (k == BIG) { s.rows = false; s.n_nodes = kAsmNodeLimit; }
+	if (k == TL || k == TL_NO8) { s.two_level = true; s.rows = s.nodes4 = false; s.nodes8 = k == TL; s.depth = 30; s.stack8 = 14; }
+	return s;
+}
+
+struct Opt { uint32_t kernel = MRT_KERNEL_AUTO, count_visits = 0, grid_tile = 0, tile_schedule = 0, tile_w_log2 = 0, stack_override = 0; };
+mrt_options options(const Opt &x)
+{
+	mrt_options o;
+	std::memset(&o, 0, sizeof(o));
+	o.struct_size = sizeof(o);
+	o.kernel = x.kernel; o.count_visits = x.count_visits; o.grid_tile = x.grid_tile; o.tile_schedule = x.tile_schedule;
+	o.tile_w_log2 = x.tile_w_log2; o.stack_override = x.stack_override;
+	return o;
+}
+
+enum { NONE, SAME, OTHER_COUNT, INCOHERENT, PENDING, NO_WIDTH }; // the previous detect
+struct Case {
+	const char *name;
+	Opt opt;
+	int scene;
+	Entry entry;
+	uint64_t count;   // rays of an array cast; ignored for grids (w x rows)
+	uint32_t flags;
+	uint32_t w, h, y0, rows; // grids; for a previous detect (array casts): what it found, {w, h, w / 8}
+	int prev;
+	const char *want;
+};
+
+constexpr uint32_t COH = MRT_FLAG_COHERENT, FORCE = MRT_FLAG_FORCE_SORT, ASYNC = MRT_FLAG_ASYNC | MRT_FLAG_RAYS_ON_DEVICE | MRT_FLAG_HITS_ON_DEVICE;
+constexpr uint32_t HOST = MRT_FLAG_HOST_LAYOUT, TOKEN = MRT_FLAG_TOKEN_OUT, BOOL = MRT_FLAG_BOOL_OUT;
+const Opt AUTO{};
+Opt kernel(uint32_t k) { Opt o; o.kernel = k; return o; }
+Opt with(Opt o, uint32_t Opt::*f, uint32_t v) { o.*f = v; return o; }
+
+const Case kCases[] = {
+	// ---- rays from an array, not declared coherent: the lane kernels; a sort from 256 rays unless one ray per wave (<= 8 192 rays)
+	{"incoherent 1", AUTO, FLAT, ENTRY_CAST, 1, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"incoherent 63", AUTO, FLAT, ENTRY_CAST, 63, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"incoherent 255", AUTO, FLAT, ENTRY_CAST, 255, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"incoherent 256", AUTO, FLAT, ENTRY_CAST, 256, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"incoherent 8192", AUTO, FLAT, ENTRY_CAST, 8192, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"incoherent 8193", AUTO, FLAT, ENTRY_CAST, 8193, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=2) sort n=3"},
+	{"incoherent 2^15-1", AUTO, FLAT, ENTRY_CAST, 32767, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=4) sort n=3"},
+	{"incoherent 2^15", AUTO, FLAT, ENTRY_CAST, 32768, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=4) sort n=3"},
+	{"incoherent 2^15+1", AUTO, FLAT, ENTRY_CAST, 32769, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=0) sort n=3"},
+	{"incoherent 65535", AUTO, FLAT, ENTRY_CAST, 65535, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=0) sort n=3"},
+	{"incoherent 65536", AUTO, FLAT, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=16 spill=0 wait=8) sort n=3"},
+	{"incoherent 2^17", AUTO, FLAT, ENTRY_CAST, 1u << 17, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=512 lds=16 spill=0 wait=8) sort n=3"},
+	{"incoherent 2^22", AUTO, FLAT, ENTRY_CAST, 1u << 22, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3"},
+	{"incoherent 2^24", AUTO, FLAT, ENTRY_CAST, 1u << 24, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3"},
+	{"FORCE_SORT 1", AUTO, FLAT, ENTRY_CAST, 1, FORCE, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3"},
+	{"TOKEN_OUT 100000", AUTO, FLAT, ENTRY_CAST, 100000, TOKEN, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=391 lds=16 spill=0 wait=8) sort n=3"},
+	{"BOOL_OUT 10", AUTO, FLAT, ENTRY_CAST, 10, BOOL, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"ASYNC 65536", AUTO, FLAT, ENTRY_CAST, 65536, ASYNC, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=16 spill=0 wait=8) sort n=3"},
+	{"no 8-wide 65536", AUTO, NO8, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l4p map=lin q=0 lane(l4p pers blocks=256 lds=16 spill=0 wait=16) sort n=3"},
+	{"2-wide only 65536", AUTO, BARE, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=256 lds=16 spill=4 wait=16) sort n=3"},
+	{"stack_override 8", with(AUTO, &Opt::stack_override, 8), FLAT, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=8 spill=2 wait=8) sort n=3"},
+	{"stack_override 32", with(AUTO, &Opt::stack_override, 32), FLAT, ENTRY_CAST, 1u << 22, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=1280 lds=32 spill=0 wait=8) sort n=3"},
+	{"pipelined chunk 2^20", AUTO, FLAT, ENTRY_CHUNK, 1u << 20, MRT_FLAG_RAYS_ON_DEVICE | MRT_FLAG_HITS_ON_DEVICE, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3"},
+	// ---- declared coherent: the width is looked for on the device from 256 rays; packets with the lane launch queued behind
+	{"coherent 63", AUTO, FLAT, ENTRY_CAST, 63, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"coherent 64", AUTO, FLAT, ENTRY_CAST, 64, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"coherent 255", AUTO, FLAT, ENTRY_CAST, 255, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"coherent 256", AUTO, FLAT, ENTRY_CAST, 256, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2"},
+	{"coherent 2^15", AUTO, FLAT, ENTRY_CAST, 32768, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=4) detect n=2"},
+	{"coherent 2^15+1", AUTO, FLAT, ENTRY_CAST, 32769, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(lane sparse=0) detect n=2"},
+	{"coherent 65535", AUTO, FLAT, ENTRY_CAST, 65535, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(lane sparse=0) detect n=2"},
+	{"coherent 65536", AUTO, FLAT, ENTRY_CAST, 65536, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(l8p pers blocks=256 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent 3600 tiles of rays", AUTO, FLAT, ENTRY_CAST, 230400, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent 3600 tiles + 1 ray", AUTO, FLAT, ENTRY_CAST, 230401, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=901 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent 2^19", AUTO, FLAT, ENTRY_CAST, 1u << 19, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent 2^22-1", AUTO, FLAT, ENTRY_CAST, (1u << 22) - 1, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent 2^22", AUTO, FLAT, ENTRY_CAST, 1u << 22, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent 2^22+1", AUTO, FLAT, ENTRY_CAST, (1u << 22) + 1, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent 2^24", AUTO, FLAT, ENTRY_CAST, 1u << 24, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent + FORCE_SORT 300", AUTO, FLAT, ENTRY_CAST, 300, COH | FORCE, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2"},
+	{"coherent HOST_LAYOUT 1024", AUTO, FLAT, ENTRY_CAST, 1024, COH | HOST, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2"},
+	{"coherent submit 4096", AUTO, FLAT, ENTRY_SUBMIT, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2"},
+	{"coherent grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"coherent count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0 cnt) detect n=2 cnt"},
+	{"coherent tile_w_log2 2", with(AUTO, &Opt::tile_w_log2, 2), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2"},
+	{"coherent 2^22 no rows", AUTO, BARE, ENTRY_CAST, 1u << 22, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(lp pers blocks=2048 lds=16 spill=4 wait=16) detect n=2"},
+	{"coherent 4096 past kAsmNodeLimit", AUTO, BIG, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2"},
+	{"coherent 65536 past kAsmNodeLimit", AUTO, BIG, ENTRY_CAST, 65536, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=256 lds=16 spill=0 wait=8) detect n=2"},
+	// ---- two-level scenes
+	{"two-level incoherent 1", AUTO, TL, ENTRY_CAST, 1, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=1) n=1"},
+	{"two-level incoherent 65536", AUTO, TL, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tlp8 map=lin q=0 lane(tlp8 pers blocks=256 lds=16 spill=0 wait=8) sort n=3"},
+	{"two-level no 8-wide 65536", AUTO, TL_NO8, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tlp map=lin q=0 lane(tlp pers blocks=256 lds=16 spill=14 wait=16) sort n=3"},
+	{"two-level count_visits 65536", with(AUTO, &Opt::count_visits, 1), TL, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=0 cnt) sort n=3 cnt"},
+	{"two-level coherent 4096", AUTO, TL, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=2 dual(tl sparse=1) detect n=2"},
+	{"two-level coherent 2^17", AUTO, TL, ENTRY_CAST, 1u << 17, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=1 dual(tlp8 pers blocks=512 lds=16 spill=0 wait=8) detect n=2"},
+	{"two-level coherent 2^19", AUTO, TL, ENTRY_CAST, 1u << 19, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=0 dual(tlp8 pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
+	// ---- explicit kernels
+	{"ASM coherent", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2"},
+	{"ASM incoherent", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_CAST, 4096, 0, 0, 0, 0, 0, NONE, "k=asm map=lin q=0 plain sort n=3"},
+	{"LANE 255", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 255, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
+	{"LANE 256", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 256, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3"},
+	{"LANE coherent", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2"},
+	{"LANE_PERSISTENT incoherent", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=4 lds=16 spill=4 wait=16) sort n=3"},
+	{"LANE_PERSISTENT coherent", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_CAST, 1000, COH, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=4 lds=16 spill=4 wait=16) n=1"},
+	{"LANE4_PERSISTENT", kernel(MRT_KERNEL_LANE4_PERSISTENT), FLAT, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=l4p map=lin q=0 lane(l4p pers blocks=1 lds=16 spill=0 wait=16) n=1"},
+	{"LANE8_PERSISTENT", kernel(MRT_KERNEL_LANE8_PERSISTENT), FLAT, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=1 lds=16 spill=0 wait=8) n=1"},
+	{"LANE8_PERSISTENT without 8-wide", kernel(MRT_KERNEL_LANE8_PERSISTENT), BARE, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=1 lds=16 spill=4 wait=16) n=1"},
+	{"PACKET_DUAL coherent", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 plain detect n=2"},
+	{"PACKET_DUAL coherent no rows", kernel(MRT_KERNEL_PACKET_DUAL), NO_ROWS, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2"},
+	{"PACKET_DUAL incoherent", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_CAST, 4096, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3"},
+	{"PACKET_ROWS coherent", kernel(MRT_KERNEL_PACKET_ROWS), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=rows map=auto q=0 plain detect n=2"},
+	{"PACKET_QUAD coherent no 4-wide rows", kernel(MRT_KERNEL_PACKET_QUAD), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2"},
+	{"LANE two-level coherent", kernel(MRT_KERNEL_LANE), TL, ENTRY_CAST, 1u << 17, COH, 0, 0, 0, 0, NONE, "k=tl map=auto q=0 lane(tl sparse=0) detect n=2"},
+	{"LANE_PERSISTENT two-level", kernel(MRT_KERNEL_LANE_PERSISTENT), TL, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=1) sort n=3"},
+	{"LANE8_PERSISTENT two-level", kernel(MRT_KERNEL_LANE8_PERSISTENT), TL, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=tlp8 map=lin q=0 lane(tlp8 pers blocks=4 lds=16 spill=0 wait=8) sort n=3"},
+	// ---- the width found by the previous cast of as many rays: a tile schedule (and the tuner) as for a grid of that width
+	{"prev detect 640x360", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect sched=640x360/80+pieces n=2"},
+	{"prev detect other count", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, OTHER_COUNT, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
+	{"prev detect incoherent", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, INCOHERENT, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
+	{"prev detect pending", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, PENDING, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
+	{"prev detect no width", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, NO_WIDTH, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
+	{"prev detect 512x256 (all in quarters)", AUTO, FLAT, ENTRY_CAST, 131072, COH, 512, 256, 0, 0, SAME, "k=asm map=auto q=1 dual(l8p pers blocks=512 lds=16 spill=0 wait=8) detect n=2"},
+	{"prev detect 1280x960", AUTO, FLAT, ENTRY_CAST, 1228800, COH, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces arms n=2"},
+	{"prev detect 1280x960 submit", AUTO, FLAT, ENTRY_SUBMIT, 1228800, COH, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces n=2"},
+	{"prev detect 1280x960 ASYNC", AUTO, FLAT, ENTRY_CAST, 1228800, COH | ASYNC, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces n=2"},
+	{"prev detect count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, SAME, "k=asm map=auto q=0 plain detect n=2 cnt"},
+	// ---- grids of known width (mrt_cast_grid): quarter / sixteenth tiles up to 3 600 / 512 tiles, the schedule from 2^17 rays
+	{"grid 7x5", AUTO, FLAT, ENTRY_GRID, 0, 0, 7, 5, 0, 5, NONE, "k=lane map=tile q=0 plain n=1"},
+	{"grid 8x8", AUTO, FLAT, ENTRY_GRID, 0, 0, 8, 8, 0, 8, NONE, "k=asm map=tile q=2 plain n=1"},
+	{"grid 16x12", AUTO, FLAT, ENTRY_GRID, 0, 0, 16, 12, 0, 12, NONE, "k=asm map=tile q=2 plain n=1"},
+	{"grid 184x176 (506 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 184, 176, 0, 176, NONE, "k=asm map=tile q=2 plain n=1"},
+	{"grid 192x176 (528 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 192, 176, 0, 176, NONE, "k=asm map=tile q=1 plain n=1"},
+	{"grid 512x255", AUTO, FLAT, ENTRY_GRID, 0, 0, 512, 255, 0, 255, NONE, "k=asm map=tile q=1 plain n=1"},
+	{"grid 512x256 (2^17, all in quarters)", AUTO, FLAT, ENTRY_GRID, 0, 0, 512, 256, 0, 256, NONE, "k=asm map=tile q=1 plain n=1"},
+	{"grid 640x360 (3600 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=640x360/80+pieces n=1"},
+	{"grid 648x360 (3645 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1"},
+	{"grid 1280x960", AUTO, FLAT, ENTRY_GRID, 0, 0, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain sched=1280x960/160+pieces arms n=1"},
+	{"grid 1280x960 ASYNC", AUTO, FLAT, ENTRY_GRID, 0, ASYNC, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain sched=1280x960/160+pieces n=0"},
+	{"grid row block 1280x[100,300)", AUTO, FLAT, ENTRY_GRID, 0, 0, 1280, 960, 100, 200, NONE, "k=asm map=tile q=0 plain sched=1280x200/160+pieces n=1"},
+	{"grid 2048x2048 (2^22)", AUTO, FLAT, ENTRY_GRID, 0, 0, 2048, 2048, 0, 2048, NONE, "k=dual map=tile q=0 plain sched=2048x2048/256+pieces n=1"},
+	{"grid 4096x4096 (2^24)", AUTO, FLAT, ENTRY_GRID, 0, 0, 4096, 4096, 0, 4096, NONE, "k=dual map=tile q=0 plain n=1"},
+	{"grid grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=lin q=0 plain n=1"},
+	{"grid tile_schedule 1", with(AUTO, &Opt::tile_schedule, 1), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1"},
+	{"grid tile_schedule 2", with(AUTO, &Opt::tile_schedule, 2), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81 n=1"},
+	{"grid count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1 cnt"},
+	{"grid count_visits 64x64", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=lane map=tile q=0 plain n=1 cnt"},
+	{"grid tile_w_log2 4", with(AUTO, &Opt::tile_w_log2, 4), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/41 n=1"},
+	{"grid past kAsmNodeLimit", AUTO, BIG, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=640x360/80+pieces n=1"},
+	{"grid two-level 64x64", AUTO, TL, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=tlpkt map=tile q=2 plain n=1"},
+	{"grid two-level 1280x960", AUTO, TL, ENTRY_GRID, 0, 0, 1280, 960, 0, 960, NONE, "k=tlpkt map=tile q=0 plain n=1"},
+	{"grid ASM 648x360", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1"},
+	{"grid ASM 64x64", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=asm map=tile q=0 plain n=1"},
+	{"grid PACKET_DUAL 648x360", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=dual map=tile q=0 plain sched=648x360/81+pieces n=1"},
+	{"grid PACKET_DUAL no rows", kernel(MRT_KERNEL_PACKET_DUAL), NO_ROWS, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1"},
+	{"grid LANE 648x360", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=lane map=tile q=0 plain n=1"},
+	{"grid LANE_PERSISTENT 648x360", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=lp map=tile q=0 plain n=1"},
+	// ---- tiled casts (mrt_cast_tiled): the grid rules without schedule or tuner
+	{"tiled 64x64", AUTO, FLAT, ENTRY_TILED, 0, 0, 64, 64, 0, 64, NONE, "k=asm map=tile q=2 plain n=1"},
+	{"tiled 648x360", AUTO, FLAT, ENTRY_TILED, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1"},
+	{"tiled 1280x960", AUTO, FLAT, ENTRY_TILED, 0, 0, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain n=1"},
+	{"tiled 2048x2048", AUTO, FLAT, ENTRY_TILED, 0, 0, 2048, 2048, 0, 2048, NONE, "k=dual map=tile q=0 plain n=1"},
+	{"tiled grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_TILED, 0, 0, 64, 64, 0, 64, NONE, "k=lane map=lin q=0 plain n=1"},
+};
+
+CastPlan plan(const Case &t, GridStates &gs, const Knobs &k = Knobs())
+{
+	CastRequest r;
+	r.entry = t.entry; r.flags = t.flags; r.mode = MRT_MODE_NEAREST;
+	PrevDetect prev;
+	if (ray_entry(t.entry)) {
+		r.count = t.count;
+		if (t.prev != NONE) {
+			prev.count = t.prev == OTHER_COUNT ? t.count + 64 : t.count;
+			prev.pending = t.prev == PENDING;
+			prev.word[0] = t.prev == NO_WIDTH ? 0u : t.w; prev.word[1] = t.h; prev.word[2] = (t.w + 7u) / 8u;
+			prev.word[3] = t.prev == INCOHERENT ? 1u : 0u;
+		}
+	} else {
+		r.count = (uint64_t)t.w * t.rows; r.grid_w = t.w; r.grid_h = t.h; r.y0 = t.y0; r.rows = t.rows;
+	}
+	return plan_cast(options(t.opt), scene(t.scene), r, prev, k, gs);
+}
+
+void table()
+{
+	for (const Case &t : kCases) {
+		GridStates gs;
+		const std::string got = describe(plan(t, gs));
+		expect(got == t.want, std::string(t.name) + ": got \"" + got + "\", want \"" + t.want + "\"");
+	}
+	// the schedule's bound from the environment (MRT_SCHEDULE_MIN_LOG2 = 15) moves the tuner's with it
+	Knobs k; k.schedule_min_rays = k.tune_min_rays = 1ull << 15;
+	GridStates gs;
+	const Case t{"grid ASM 256x128 with the bound at 2^15", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_GRID, 0, 0, 256, 128, 0, 128, NONE, ""};
+	expect(describe(plan(t, gs, k)) == "k=asm map=tile q=0 plain sched=256x128/32+pieces n=1", "schedule bound 2^15: " + describe(plan(t, gs, k)));
+	expect(describe(plan(t, gs)) == "k=asm map=tile q=0 plain n=1", "schedule bound 2^17: " + describe(plan(t, gs)));
+}
+
+// 15 frames of one 1280x960 grid: frames 0-3 the 64-ray kernel, 4-7 the 128-ray walk in pieces, 8-11 whole; the last two of every
+// candidate are timed, waiting for the sorts; from frame 12 the fastest (the faster of its two timed frames)
+void tuner(const char *name, const float ms[12], const char *final_want)
+{
+	GridStates gs;
+	const Case grid{name, AUTO, FLAT, ENTRY_GRID, 0, 0, 1280, 960, 0, 960, NONE, ""};
+	static const char *want[12] = {"asm+pieces", "asm+pieces", "asm+pieces+wait", "asm+pieces+wait", "dual+pieces", "dual+pieces",
+		"dual+pieces+wait", "dual+pieces+wait", "dual", "dual", "dual+wait", "dual+wait"};
+	for (int f = 0; f < 15; f++) {
+		const CastPlan c = plan(grid, gs);
+		char got[64];
+		std::snprintf(got, sizeof(got), "%s%s%s", kname(c.kernel), c.pieces ? "+pieces" : "", c.wait_sorts ? "+wait" : "");
+		const std::string w = f < 12 ? want[f] : final_want;
+		expect(got == w && c.arms_tuner == (f < 12) && c.scheduled, std::string(name) + " frame " + std::to_string(f) + ": got " + got + ", want " + w);
+		tune_record(gs.tune(), f < 12 ? ms[f] : 0.1f);
+		if (f == 5) { // an ASYNC frame has no timing: it takes the phase's kernel and leaves the phase where it is
+			Case a = grid; a.flags = ASYNC;
+			const CastPlan ca = plan(a, gs);
+			expect(!ca.arms_tuner && ca.kernel == MRT_KERNEL_PACKET_DUAL && gs.tune().phase == 6, std::string(name) + ": ASYNC frame");
+			tune_record(gs.tune(), 9.0f);
+			expect(gs.tune().phase == 6, std::string(name) + ": ASYNC frame advanced the phase");
+		}
+	}
+}
+
+// per grid and mode: eight states, the least recently used one goes
+void lru()
+{
+	GridStates gs;
+	const Case a{"lru", AUTO, FLAT, ENTRY_GRID, 0, 0, 1280, 960, 0, 960, NONE, ""};
+	auto other = [&](uint32_t k) { Case c = a; c.w = 1280 + 8 * k; return c; };
+	for (int f = 0; f < 5; f++) { plan(a, gs); tune_record(gs.tune(), 1.0f); } // phase 5
+	for (uint32_t k = 1; k <= 7; k++) plan(other(k), gs);                      // seven more grids: a is still held
+	CastPlan c = plan(a, gs);
+	expect(c.kernel == MRT_KERNEL_PACKET_DUAL && c.pieces && gs.tune().phase == 5, "lru: grid a kept among eight");
+	Case any = a; // the same grid in any-hit mode is a state of its own
+	CastRequest r; r.entry = ENTRY_GRID; r.count = 1280u * 960u; r.grid_w = 1280; r.grid_h = 960; r.rows = 960; r.mode = MRT_MODE_ANY_HIT;
+	c = plan_cast(options(any.opt), scene(FLAT), r, PrevDetect(), Knobs(), gs);
+	expect(c.kernel == MRT_KERNEL_PACKET_ASM && gs.tune().phase == 0 && gs.e[gs.cur].key.mode == MRT_MODE_ANY_HIT, "lru: any-hit mode has its own state");
+	const int slot_of_other1 = [&] { for (int i = 0; i < GridStates::kCount; i++) if (gs.e[i].key.w == 1288) return i; return -1; }();
+	expect(slot_of_other1 < 0, "lru: the any-hit state evicted the oldest (grid 1)");
+	plan(a, gs); // a: most recent again
+	for (uint32_t k = 10; k <= 17; k++) plan(other(k), gs); // eight new grids: a is the oldest by the eighth
+	c = plan(a, gs);
+	expect(c.kernel == MRT_KERNEL_PACKET_ASM && gs.tune().phase == 0, "lru: grid a evicted after eight others");
+	GridStates g2;
+	for (uint32_t k = 0; k < 8; k++) select_grid_state(g2, GridKey{100 + k, 1, 0, 1, 0});
+	select_grid_state(g2, GridKey{100, 1, 0, 1, 0});
+	const int at = select_grid_state(g2, GridKey{200, 1, 0, 1, 0});
+	expect(at == 1 && g2.e[0].key.w == 100, "lru: select_grid_state evicts the least recently used");
+}
+
+} // namespace
+
+int main()
+{
+	table();
+	const float pieces_win[12] = {0, 0, 0.40f, 0.38f, 0, 0, 0.35f, 0.36f, 0, 0, 0.37f, 0.38f};   // whole 0.37 > 1.03 x 0.35
+	const float whole_wins[12] = {0, 0, 0.40f, 0.38f, 0, 0, 0.35f, 0.36f, 0, 0, 0.36f, 0.361f};  // whole 0.36 <= 1.03 x 0.35
+	const float asm_wins[12] = {0, 0, 0.30f, 0.31f, 0, 0, 0.35f, 0.36f, 0, 0, 0.36f, 0.37f};
+	tuner("tuner, pieces win", pieces_win, "dual+pieces");
+	tuner("tuner, whole wins", whole_wins, "dual");
+	tuner("tuner, 64-ray kernel wins", asm_wins, "asm+pieces");
+	lru();
+	std::printf("%d of %d checks hold (%zu table cases)\n", checks - failures, checks, sizeof(kCases) / sizeof(kCases[0]));
+	return failures ? 1 : 0;
+}

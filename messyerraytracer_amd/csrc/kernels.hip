@@ -711,7 +711,7 @@ __global__ __launch_bounds__(MRT_DETECT_THREADS) void detect_grid_kernel(const v
 		// somewhere else, the batch goes to the lane kernel (out[3] = 1) instead of packets
 		const unsigned long long n_wide = __hip_atomic_load(&scratch[1025], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		// ... and so does a small batch in which no row width was found: packets of 64 consecutive rays are no match for one lane
-		// per ray there (with a width, small batches go in pieces of 4 or 16 rays: api.hip quarter_small_grid)
+		// per ray there (with a width, small batches go in pieces of 4 or 16 rays: launch_policy.cpp quarter_rule)
 		out[3] = (n_wide * 8ull > (unsigned long long)m || (!ok && count < 32768ull)) ? 1u : 0u;
 		// the same four words to host-mapped memory: read by the host after it has waited for the stream
 		if (host_out) { host_out[0] = out[0]; host_out[1] = out[1]; host_out[2] = out[2]; host_out[3] = out[3]; }
@@ -804,7 +804,7 @@ hipError_t launch_origin_dir_keys(const void *rays, uint32_t in_fmt, uint64_t co
 	return hipGetLastError();
 }
 
-// ---- launch wrappers (called from api.hip) -------------------------------------------
+// ---- launch wrappers (called from api.hip / cast.hip) -------------------------------------------
 bool quad_kernel_built()
 {
 #ifdef MRT_WITH_QUAD
@@ -826,7 +826,7 @@ static void note_variant(const char *fmt, ...)
 #ifndef MRT_ROWS_WG_LARGE
 #define MRT_ROWS_WG_LARGE MRT_WG // threads per workgroup of the rows kernel on large scenes
 #endif
-constexpr uint32_t kPrefetchMaxWaves = 10240u; // 1.25 rounds of the device's 8 192 wave slots
+constexpr uint32_t kPrefetchMaxWaves = kWaveSlots + kWaveSlots / 4u; // 1.25 rounds of the device's wave slots
 hipError_t launch_trace(const TraceParams &p_in, bool any_hit, bool count, hipStream_t stream)
 {
 	TraceParams p = p_in;
@@ -900,7 +900,7 @@ hipError_t launch_trace(const TraceParams &p_in, bool any_hit, bool count, hipSt
 		} else {
 			// the scalar-cache prefetch of both children: where the launch is about one round of waves (packet_asm_kernel.h)
 			// (a scheduled launch covers the slots the list MAY use: what counts is the units, or the one round the fill rule makes of fewer)
-			const uint64_t waves = p.tile_sched != nullptr && p.n_slots_max != 0u ? (p.n_units > 8192u ? p.n_units : (p.n_slots_max < 8192u ? p.n_slots_max : 8192u)) : threads / MRT_WAVE;
+			const uint64_t waves = p.tile_sched != nullptr && p.n_slots_max != 0u ? (p.n_units > kWaveSlots ? p.n_units : (p.n_slots_max < kWaveSlots ? p.n_slots_max : kWaveSlots)) : threads / MRT_WAVE;
 			const bool kpf = waves <= kPrefetchMaxWaves;
 			if (kpf) { if (any_hit) hipLaunchKernelGGL((trace_packet_asm_kernel<true, false, true>), grid, wg, p.extra_lds, stream, p);
 				else hipLaunchKernelGGL((trace_packet_asm_kernel<false, false, true>), grid, wg, p.extra_lds, stream, p); }

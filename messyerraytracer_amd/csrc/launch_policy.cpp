@@ -1,0 +1,252 @@
+// launch_policy.cpp — the cast launch policy (launch_policy.h): plain host code, no HIP.
+#include <cstdint>
+#include "../../include/mrt_hip.h"
+#include "mrt_internal.h"
+#include "launch_policy.h"
+
+namespace mrt {
+namespace {
+
+bool persistent_lane_kernel(uint32_t k)
+{
+	return k == MRT_KERNEL_LANE_PERSISTENT || k == MRT_KERNEL_LANE4_PERSISTENT || k == MRT_KERNEL_LANE8_PERSISTENT;
+}
+bool lane_kernel(uint32_t k) { return k == MRT_KERNEL_LANE || k == MRT_KERNEL_TWO_LEVEL; }
+
+// MRT_KERNEL_AUTO: packets for batches the caller declares coherent (RayQuery::coherent,
+// primary-ray grids), one lane per ray for everything else (sorted / incoherent batches).
+uint32_t pick_kernel(const mrt_options &o, const SceneFacts &s, bool coherent, uint64_t count)
+{
+	// a two-level scene has its own pair of kernels (two_level_kernel.h)
+	// Packets pay once there are enough of them: a wave that walks for 64 rays is a long serial chain (0.3 - 0.7 ms on a
+	// 1 M-triangle scene, the longer the wider its 8x8 tile opens), and a small batch is over when its slowest wave is.
+	// Coherent grids on the C3 scene (tools/bench_small_batches.py, profiles/r02d_small_batches.txt): 64^2 rays 0.69 ms by
+	// packets, 0.32 ms one lane per ray; 128^2 0.56 / 0.40; 256^2 0.40 / 0.43; 512^2 0.35 / 0.59 (C2 scene: even at 128^2).
+	// (Batches whose tiling is known or found -- grids, tiled casts, mrt_cast(COHERENT) -- leave this rule from 2^11 rays on:
+	// the quarter rule of plan_cast runs them by packets of 16 rays, faster than either.)
+	const bool few = o.kernel == MRT_KERNEL_AUTO && count < (1ull << 15);
+	if (s.two_level) return coherent && !few && o.kernel != MRT_KERNEL_LANE ? MRT_KERNEL_TWO_LEVEL_PACKET : MRT_KERNEL_TWO_LEVEL;
+	if (o.kernel == MRT_KERNEL_PACKET_DUAL || o.kernel == MRT_KERNEL_PACKET_ROWS)
+		return !coherent ? MRT_KERNEL_LANE : (s.rows ? o.kernel : MRT_KERNEL_PACKET_ASM);
+	if (o.kernel == MRT_KERNEL_PACKET_QUAD)
+		return !coherent ? MRT_KERNEL_LANE : (s.rows4 ? MRT_KERNEL_PACKET_QUAD : MRT_KERNEL_PACKET_ASM);
+	if (o.kernel >= MRT_KERNEL_LANE && o.kernel <= MRT_KERNEL_LANE8_PERSISTENT) return o.kernel;
+	if (!coherent || few) return MRT_KERNEL_LANE;
+	// Coherent batches: the 128-ray shared walk over the row array (packet_rows_kernel.h) once the batch is large
+	// enough to fill the chip with half as many waves (C3 2.16 -> 2.06 ms, C5 23.2 -> 21.2 ms; C2's 2^20 rays are
+	// 7 % faster with one packet per wave: 0.188 against 0.202 ms), else the 64-ray packet kernel with the
+	// hand-written node loop.
+	return (s.rows && count >= (1ull << 22)) ? MRT_KERNEL_PACKET_DUAL : MRT_KERNEL_PACKET_ASM;
+}
+
+bool schedule_applies(const mrt_options &o, const SceneFacts &s, const Knobs &k, uint32_t lane_map, uint64_t count, uint32_t kernel)
+{
+	if (o.tile_schedule == 1u || o.count_visits) return false;
+	if ((lane_map != MAP_TILE8X8 && lane_map != MAP_AUTO) || count < k.schedule_min_rays || count >= kScheduleMaxRays) return false;
+	return kernel == MRT_KERNEL_PACKET_ASM || (kernel == MRT_KERNEL_PACKET_DUAL && s.rows);
+}
+
+// The kernel of a mid-size grid cast, by measurement (GridTune).  Only for MRT_KERNEL_AUTO on flat scenes, blocking
+// casts (a timing is needed), grids the schedule applies to.
+uint32_t tune_grid_kernel(GridTune &t, const mrt_options &o, const SceneFacts &s, const Knobs &k, const GridKey &g, uint64_t count,
+		uint32_t lane_map, uint32_t quarter_all, uint32_t kernel, uint32_t flags)
+{
+	t.armed = false; t.no_pieces = false;
+	if (o.kernel != MRT_KERNEL_AUTO || s.two_level || !s.rows || o.count_visits || o.tile_schedule == 1u) return kernel;
+	// (from 2^22 rays on the 128-ray walk won every measurement -- 2560x1440 .. 7680x4320, C5's row blocks --: no frames are spent on the other one)
+	if (lane_map != MAP_TILE8X8 || quarter_all || count < k.schedule_min_rays || count < k.tune_min_rays || count >= kScheduleMaxRays || count >= (1ull << 22)) return kernel;
+	if (kernel != MRT_KERNEL_PACKET_ASM && kernel != MRT_KERNEL_PACKET_DUAL) return kernel;
+	const bool same = t.grid_w == g.w && t.grid_h == g.h && t.y0 == g.y0 && t.rows == g.rows && t.mode == g.mode;
+	if (!same) { t.grid_w = g.w; t.grid_h = g.h; t.y0 = g.y0; t.rows = g.rows; t.mode = g.mode; t.phase = 0; t.t_asm = t.t_dual = t.t_whole = 0.0f; }
+	// frames 0-3: the 64-ray kernel; 4-7: the 128-ray walk, its most expensive units in pieces (schedule_plan_kernel); 8-11: the
+	// same with every unit whole; then the fastest of the three (each by the faster of its last two frames)
+	if (t.phase < kTuneFrames) kernel = MRT_KERNEL_PACKET_ASM;
+	else if (t.phase < 2 * kTuneFrames) kernel = MRT_KERNEL_PACKET_DUAL;
+	else if (t.phase < 3 * kTuneFrames) { kernel = MRT_KERNEL_PACKET_DUAL; t.no_pieces = true; }
+	else {
+		const bool whole = t.t_whole <= t.t_dual * 1.03f; // (pieces must win by more than the noise of two timings)
+		const float best_dual = whole ? t.t_whole : t.t_dual;
+		kernel = best_dual < t.t_asm ? MRT_KERNEL_PACKET_DUAL : MRT_KERNEL_PACKET_ASM;
+		t.no_pieces = kernel == MRT_KERNEL_PACKET_DUAL && whole;
+	}
+	t.armed = t.phase < 3 * kTuneFrames && !(flags & MRT_FLAG_ASYNC);   // an ASYNC cast has no timing: the phase waits for a blocking one
+	return kernel;
+}
+
+// Lane kernel launch: plain (one fixed ray per lane) or persistent (resident waves pulling rays
+// from a counter, short LDS stack with HBM spill).
+LaneLaunch lane_launch(const mrt_options &o, const SceneFacts &s, uint64_t count, uint32_t lane_map, bool persistent)
+{
+	LaneLaunch l;
+	// The wide walks exist in persistent form only.  For large incoherent batches MRT_KERNEL_AUTO takes the
+	// 8-wide compressed layout when the scene has it (6.1 ms at C4), else the 4-wide one (7.7 ms), else the
+	// 2-wide persistent kernel (11.0 ms).
+	const bool wide4 = s.nodes4 && (o.kernel == MRT_KERNEL_LANE4_PERSISTENT || (o.kernel == MRT_KERNEL_AUTO && persistent));
+	const bool wide8 = s.nodes8 && (o.kernel == MRT_KERNEL_LANE8_PERSISTENT || (o.kernel == MRT_KERNEL_AUTO && persistent));
+	// counting builds: the persistent kernels count for flat scenes; two-level scenes take the plain lane kernel
+	const bool can_count = !o.count_visits || !s.two_level;
+	if ((wide4 || wide8) && can_count) persistent = true;
+	if (!persistent || !can_count) {
+		l.kernel = s.two_level ? MRT_KERNEL_TWO_LEVEL : MRT_KERNEL_LANE;
+		// A small batch on more, emptier waves: with fewer rays than the device has wave slots (8 192) every ray gets a wave of its
+		// own, up to 2^15 rays two or four share one.  A wave's walk is as long as its longest ray's and every step costs as many
+		// memory requests as it has rays; a batch this small ends with its longest wave (blocking mrt_cast of incoherent rays in
+		// host arrays: 256 rays 190 -> 97 us, 1 024 rays 247 -> 125, 4 096 rays 317 -> 210; 2^14 device-resident rays 503 -> 338;
+		// on the C5 two-level scene 256 rays 1 649 -> 319 us, 4 096 rays 2 272 -> 646; profiles/r03_latency.txt)
+		if (lane_map == MAP_LINEAR && count <= (kWaveSlots << 2)) {
+			l.sparse_lanes = 1u;
+			while ((count + l.sparse_lanes - 1u) / l.sparse_lanes > kWaveSlots) l.sparse_lanes <<= 1;
+		}
+		l.count = o.count_visits != 0;
+		return l;
+	}
+	l.persistent = true;
+	l.lds_depth = o.stack_override >= 4 && o.stack_override <= 64 ? o.stack_override : 16u;
+	const uint32_t lds_bytes = 4u * l.lds_depth * 64u * 4u; // per 256-thread workgroup
+	uint32_t wg_per_cu = (160u * 1024u) / lds_bytes; if (wg_per_cu > 8u) wg_per_cu = 8u;
+	const uint64_t blocks = (uint64_t)s.cu_count * wg_per_cu, needed = (count + 255u) / 256u;
+	l.blocks = (uint32_t)(blocks > needed ? needed : blocks);
+	const uint32_t need = wide8 ? s.stack8 : (wide4 ? s.stack4 : s.depth); // entries one ray can have pending
+	l.spill = need > l.lds_depth ? need - l.lds_depth : 0u; // deeper entries spill to [depth - lds_depth][thread] in HBM
+	l.kernel = wide8 ? MRT_KERNEL_LANE8_PERSISTENT : (wide4 ? MRT_KERNEL_LANE4_PERSISTENT : MRT_KERNEL_LANE_PERSISTENT);
+	if (s.two_level) l.kernel = wide8 ? MRT_KERNEL_TWO_LEVEL_PERSISTENT8 : MRT_KERNEL_TWO_LEVEL_PERSISTENT; // need = stack8 (= depth8) / depth
+	l.refill = o.refill ? o.refill : 16u;
+	l.leaf_wait = o.leaf_wait ? o.leaf_wait : (wide8 ? 8u : 16u);
+	l.count = o.count_visits != 0 && !s.two_level;
+	return l;
+}
+
+// Small grids of known width (mrt_cast_grid, mrt_cast_tiled; flat scenes, MRT_KERNEL_AUTO; mrt_cast(COHERENT) does the same for a
+// width found on the device): the 64-ray packet kernel with EVERY tile launched in pieces (TraceParams::quarter_all) -- up to 512
+// tiles as its sixteen 2x2-pixel sixteenths (4 rays in lanes 0..3 of a wave), up to 3 600 tiles as its four 4x4-pixel quarters (16
+// rays).  Such a grid has fewer tiles than the device has wave slots (8 192), so it lasts as long as its longest walk whatever the
+// order, and a walk for 16 rays is about half as long as its tile's, one for 4 rays a third.  C3 scene, kernel time in ms (whole
+// tiles by packets / one lane per ray / quarters / sixteenths): 16x12 - / 0.23 / - / 0.15, 32^2 1.22 / 0.34 / 0.36 / 0.15, 64^2 0.67 /
+// 0.31 / 0.26 / 0.12, 128^2 0.53 / 0.37 / 0.20 / 0.18, 192^2 0.46 / 0.45 / 0.25 / 0.22, 256^2 0.37 / 0.40 / 0.24 / 0.25, 384^2 0.34 / 0.47 /
+// 0.25, 640x360 0.38 / 0.55 / 0.29; sixteen times as many waves are two rounds of them from 1 024 tiles on, four times as many from
+// 4 096 (512^2: 0.32 / 0.55 / 0.32), and nothing is gained.  The C2 scene draws the same lines (64^2 0.38 / 0.27 / 0.18 / 0.09;
+// 192^2 - / - / 0.10 / 0.10; 256^2 - / - / 0.09 / 0.15).  Between 2 048 and 8 192 tiles the cost history picks the tiles (schedule_plan_kernel).
+// Two-level scenes go the same way with their own packet kernel (whose walks are longer still: a ray crosses several instances):
+// C5 as a two-level scene, 64^2 2.56 -> 0.95 ms, 128^2 2.78 -> 0.83, 256^2 4.14 -> 1.73, 640x360 2.10 -> 1.79.
+// Two rules that look alike: `units` are the tiles of a grid of known width, but rays / 64 (rounded up) for a width found on the
+// device, whose grid is not known when the kernel is chosen -- a grid with clipped tiles has more tiles than that.
+void quarter_rule(const mrt_options &o, const SceneFacts &s, uint64_t count, uint64_t units, CastPlan &c)
+{
+	if (o.kernel != MRT_KERNEL_AUTO || o.count_visits || tile_w_log2(o) != 3u || s.n_nodes >= kAsmNodeLimit) return;
+	if (count < kQuarterMinRays || units > kQuarterMaxTiles) return;
+	c.kernel = s.two_level ? MRT_KERNEL_TWO_LEVEL_PACKET : MRT_KERNEL_PACKET_ASM; // (a two-level scene: its packet kernel maps lanes the same way)
+	c.quarter_all = units <= kSixteenthMaxTiles ? 2u : 1u;
+}
+
+} // namespace
+
+uint32_t tile_w_log2(const mrt_options &o) { return o.tile_w_log2 >= 1 && o.tile_w_log2 <= 6 ? o.tile_w_log2 : 3u; }
+
+int select_grid_state(GridStates &g, const GridKey &k)
+{
+	int pick = -1, oldest = 0;
+	for (int i = 0; i < GridStates::kCount; i++) {
+		const GridKey &q = g.e[i].key;
+		if (q.mode == k.mode && q.w == k.w && q.h == k.h && q.y0 == k.y0 && q.rows == k.rows) { pick = i; break; }
+		if (g.e[i].stamp < g.e[oldest].stamp) oldest = i;
+	}
+	if (pick < 0) { pick = oldest; g.e[pick].key = k; }
+	g.e[pick].stamp = ++g.clock;
+	return g.cur = pick;
+}
+
+void tune_record(GridTune &t, float trace_ms)
+{
+	if (!t.armed) return;
+	// the faster of a candidate's last two frames (both launched in a measured order: schedule_grid waits for the sorts behind them)
+	const int cand = t.phase / kTuneFrames, at = t.phase % kTuneFrames;
+	float &slot = cand == 0 ? t.t_asm : (cand == 1 ? t.t_dual : t.t_whole);
+	if (at == kTuneFrames - 2) slot = trace_ms;
+	if (at == kTuneFrames - 1 && trace_ms < slot) slot = trace_ms;
+	t.phase++;
+	t.armed = false;
+}
+
+CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest &r, const PrevDetect &prev, const Knobs &k, GridStates &gs)
+{
+	CastPlan c;
+	const uint64_t n = r.count;
+	const bool auto_k = o.kernel == MRT_KERNEL_AUTO, coherent = (r.flags & MRT_FLAG_COHERENT) != 0;
+	const uint32_t tw = tile_w_log2(o), th = 64u >> tw;
+	gs.tune().armed = false; // (the grid tuner times a cast only if THIS cast asks it to)
+	if (ray_entry(r.entry)) {
+		const uint32_t thr = o.sort_threshold ? o.sort_threshold : 256u; // MIN_BATCH_FOR_SORTING
+		// (a batch of at most 8 192 rays runs one ray per wave in the lane kernel, lane_launch: there is no wave whose rays a sort could
+		// bring together, and its three launches are a third of such a cast's time)
+		const bool one_ray_waves = auto_k && n <= kWaveSlots && !(r.flags & MRT_FLAG_FORCE_SORT);
+		c.sort = !coherent && !one_ray_waves && (n >= thr || (r.flags & MRT_FLAG_FORCE_SORT));
+		c.kernel = pick_kernel(o, s, !c.sort && coherent, n);
+		const bool persistent_kind = persistent_lane_kernel(c.kernel);
+		// Coherent batch without a declared width: look for the row width on the device and let the
+		// trace kernel tile its lanes (no host round trip: the kernel reads the answer from HBM).
+		// Timed with the sort as pre-processing (last_sort_ms); last_trace_ms is the trace kernel alone.
+		c.detect = !c.sort && coherent && n >= 256 && o.grid_tile != 1 && !persistent_kind;
+		c.lane_map = c.detect ? MAP_AUTO : MAP_LINEAR;
+		// a small batch whose width the device finds: sixteenth or quarter tiles (if no width is found the lanes stay linear and the
+		// waves past the batch have nothing to do)
+		if (c.detect && (c.kernel == MRT_KERNEL_PACKET_ASM || lane_kernel(c.kernel) || c.kernel == MRT_KERNEL_TWO_LEVEL_PACKET))
+			quarter_rule(o, s, n, n / 64u + (n % 64u != 0u), c);
+		// the tile schedule for a batch whose width the device finds: sized from what the previous cast of as many rays found ...
+		if (c.detect && !prev.pending && prev.count == n && prev.word[0] != 0u && prev.word[3] == 0u &&
+				schedule_applies(o, s, k, c.lane_map, n, c.kernel) && !(c.quarter_all && n <= kQuarterAllRays)) {
+			c.scheduled = true; c.quarter_all = 0u;
+			c.grid_w = prev.word[0]; c.rows = c.grid_h = prev.word[1]; c.tiles_x = prev.word[2];
+			// ... and so is the way it is cast: the grid tuner's candidates, as for a grid cast of that width (mrt_cast records the timing)
+			const GridKey key{c.grid_w, c.grid_h, 0u, c.rows, r.mode};
+			select_grid_state(gs, key);
+			c.kernel = tune_grid_kernel(gs.tune(), o, s, k, key, n, MAP_TILE8X8, 0u, c.kernel, r.flags);
+		}
+		c.launches = c.sort ? 3 : (c.detect ? 2 : 1);
+		if (c.detect && auto_k && !o.count_visits && !lane_kernel(c.kernel)) {
+			// The caller said "coherent"; the device checks.  Packet launch first, lane launch behind it:
+			// detect_grid_kernel's verdict (auto_grid[3]) makes exactly one of them do the work.  The lane launch is
+			// persistent from 2^16 rays, the bound below, but its lanes are linear whatever the device finds (a two-level
+			// scene: its own lane kernels).
+			c.launch = CastPlan::DUAL;
+			c.lane = lane_launch(o, s, n, MAP_LINEAR, n >= 65536);
+		} else if (persistent_kind || lane_kernel(c.kernel)) {
+			// large incoherent batches: resident waves that pull rays from a counter (no counting variant)
+			const bool persistent = c.lane_map == MAP_LINEAR && (persistent_kind || (auto_k && n >= 65536));
+			c.launch = CastPlan::LANE;
+			c.lane = lane_launch(o, s, n, c.lane_map, persistent);
+			c.kernel = c.lane.kernel;
+		}
+	} else {
+		// a grid of known width: mrt_cast_grid, mrt_cast_tiled
+		c.grid_w = r.grid_w; c.grid_h = r.grid_h; c.y0 = r.y0; c.rows = r.rows;
+		c.tiles_x = (r.grid_w + (1u << tw) - 1u) >> tw;
+		c.lane_map = o.grid_tile == 1 ? MAP_LINEAR : MAP_TILE8X8;
+		c.kernel = pick_kernel(o, s, true, n);
+		if (c.lane_map == MAP_TILE8X8) quarter_rule(o, s, n, (uint64_t)c.tiles_x * ((r.rows + 7u) / 8u), c);
+		if (r.entry == ENTRY_GRID) {
+			const GridKey key{r.grid_w, r.grid_h, r.y0, r.rows, r.mode};
+			if (n >= k.schedule_min_rays) select_grid_state(gs, key);
+			c.kernel = tune_grid_kernel(gs.tune(), o, s, k, key, n, c.lane_map, c.quarter_all, c.kernel, r.flags);
+			// (from 2 048 tiles on the cost history says WHICH tiles go in quarters)
+			c.scheduled = schedule_applies(o, s, k, c.lane_map, n, c.kernel) && !(c.quarter_all && n <= kQuarterAllRays);
+			if (c.scheduled) c.quarter_all = 0u;
+		}
+		c.launches = r.entry == ENTRY_GRID && (r.flags & MRT_FLAG_ASYNC) ? 0 : 1; // (an ASYNC grid cast leaves the count as it was)
+	}
+	c.count = o.count_visits != 0;
+	const GridTune &t = gs.tune();
+	if (c.scheduled) {
+		// pieces: 8x8 tiles only, ids within the entry's 28 bits, not while the kernel tuner tries (or has chosen) the frames without
+		const uint64_t tiles = (uint64_t)c.tiles_x * ((c.rows + th - 1u) / th);
+		c.pieces = tw == 3u && o.tile_schedule != 2u && tiles < (1ull << 28) && !t.no_pieces;
+		// the frame the kernel tuner times (the third of a kernel) waits for the sorts behind it: it is launched the way later frames will be
+		c.wait_sorts = t.armed && t.phase % kTuneFrames >= kTuneFrames - 2;
+	}
+	// only a blocking mrt_cast / mrt_cast_grid records its time (a submitted cast is collected later, pipeline chunks are not timed
+	// one by one)
+	c.arms_tuner = t.armed && (r.entry == ENTRY_CAST || r.entry == ENTRY_GRID);
+	gs.tune().armed = c.arms_tuner;
+	return c;
+}
+
+} // namespace mrt

@@ -1,0 +1,108 @@
+// launch_policy.h — which kernel a cast gets and how it is launched, as plain host code (no HIP calls, no allocation).
+// The HIP side (cast.hip launch_planned) executes a CastPlan; csrc/host/launch_policy_test.cpp pins the plans on the CPU.
+#pragma once
+#include <cstdint>
+#include "../../include/mrt_hip.h"
+#include "mrt_internal.h"
+
+namespace mrt {
+
+// Grid casts of 2^19 .. 2^24 rays are scheduled (schedule.hip): see the comment there.
+#ifndef MRT_SCHEDULE_MAX_LOG2
+#define MRT_SCHEDULE_MAX_LOG2 24
+#endif
+constexpr uint64_t kScheduleMaxRays = 1ull << MRT_SCHEDULE_MAX_LOG2;
+constexpr uint64_t kQuarterMinRays = 64, kQuarterMaxTiles = 3600, kSixteenthMaxTiles = 512; // small grids in quarter / sixteenth tiles
+constexpr uint64_t kQuarterAllRays = 2048ull * 64ull; // up to here four quarters per tile still fit one round of waves: no schedule needed
+constexpr int kTuneFrames = 4; // frames per candidate of the grid kernel tuner (tune_grid_kernel): the last two are timed
+
+// Settings read from the environment once, when the context is created (mrt_create).
+struct Knobs {
+	// From 2^17 rays (2 048 tiles: below, all tiles go in quarter tiles anyway, quarter rule).  With the order alone 640x360
+	// measured 7 % slower scheduled than not; with the most expensive tiles in quarter tiles until the chip is full
+	// (schedule_plan_kernel) it is 20 % faster.  MRT_SCHEDULE_MIN_LOG2 moves the bound (the tests schedule smaller grids)
+	uint64_t schedule_min_rays = 1ull << 17;
+	// the grid tuner: from 2^19 rays on the 128-ray walk is a candidate (below, the 64-ray kernel won every measurement); a test that
+	// moves the schedule's bound moves this one with it
+	uint64_t tune_min_rays = 1ull << 19;
+	uint32_t split_pct = 1;  // MRT_SCHED_SPLIT_PCT: the rank, in percent, above which a unit goes in pieces (schedule_plan_kernel)
+	bool dump = false;       // MRT_SCHED_DUMP: print what every schedule was made of (tools/bench_resolutions.py)
+};
+
+// What the cast path needs to know about the scene (and the device).
+struct SceneFacts {
+	bool two_level = false, rows = false, rows4 = false, nodes4 = false, nodes8 = false; // which layouts are resident
+	uint32_t n_nodes = 0, depth = 0, stack4 = 0, stack8 = 0; // stack entries one ray can need in the 2-, 4- and 8-wide walks
+	uint32_t cu_count = 256;
+};
+
+enum Entry : uint32_t { ENTRY_CAST, ENTRY_SUBMIT, ENTRY_CHUNK, ENTRY_GRID, ENTRY_TILED }; // ENTRY_CHUNK: a chunk of cast_host_pipelined
+inline bool ray_entry(Entry e) { return e <= ENTRY_CHUNK; } // rays from an array, through enqueue_cast
+
+struct CastRequest {
+	Entry entry = ENTRY_CAST;
+	uint64_t count = 0;
+	uint32_t flags = 0;
+	int mode = MRT_MODE_NEAREST;
+	uint32_t grid_w = 0, grid_h = 0, y0 = 0, rows = 0; // grid / tiled casts
+};
+
+// What detect_grid_kernel found for the previous cast ({row width, rows, tiles_x, verdict}), and for how many rays.
+struct PrevDetect {
+	bool pending = false;  // an ASYNC / submitted cast may not have written the words yet
+	uint64_t count = 0;    // rays of the last cast that ran detect_grid_kernel (0: none)
+	uint32_t word[4] = {0, 0, 0, 0};
+};
+
+// How a mid-size grid is cast is MEASURED per grid (tune_grid_kernel): four frames with the 64-ray kernel, four with the 128-ray
+// walk and its most expensive units launched in pieces, four with the 128-ray walk and every unit whole; from frame 12 on the
+// fastest of the three, each judged by the faster of its last two frames.  What wins flips with the number of rounds a grid
+// makes on the chip (C3 scene: 1280x720 the 64-ray kernel, 1280x960 the 128-ray walk whole, 1920x1080 the 128-ray walk in pieces).
+struct GridTune { uint32_t grid_w = 0, grid_h = 0, y0 = 0, rows = 0; int mode = -1; int phase = 0; float t_asm = 0.0f, t_dual = 0.0f, t_whole = 0.0f; bool armed = false, no_pieces = false; };
+// What has been learnt about a grid (its tile schedule, how it is cast fastest) is kept per grid AND cast mode, for the last few
+// of them: a renderer that casts two views, or closest-hit and any-hit rays of one view, or the row-block chunks of a sharded
+// frame, in turn, keeps every one's state (with one state each change of grid threw the other's away, and cost a stream
+// synchronisation and an upload to start over).  select_grid_state() picks the entry of a cast; the least recently used one goes.
+// The context keeps the tile schedule of entry k in its own array at k.
+struct GridKey { uint32_t w = 0, h = 0, y0 = 0, rows = 0; int mode = -1; };
+struct GridStates {
+	static constexpr int kCount = 8;
+	struct Entry { GridKey key; GridTune tune; uint64_t stamp = 0; } e[kCount];
+	uint64_t clock = 0;
+	int cur = 0;
+	GridTune &tune() { return e[cur].tune; }
+};
+int select_grid_state(GridStates &g, const GridKey &k); // returns (and makes current) the entry of k
+void tune_record(GridTune &t, float trace_ms);          // after a blocking cast the tuner armed: note its time, next phase
+
+// One launch of the lane kernels (launch_lane): plain, one fixed ray per lane, or persistent, resident waves pulling rays from
+// a counter with a short LDS stack that spills to HBM.
+struct LaneLaunch {
+	bool persistent = false;
+	uint32_t kernel = MRT_KERNEL_LANE;
+	uint32_t sparse_lanes = 0;              // plain: rays per wave (0 = 64)
+	uint32_t lds_depth = 0, blocks = 0;     // persistent: LDS stack entries per lane, workgroups
+	uint32_t spill = 0;                     // persistent: stack entries per lane past lds_depth (in HBM)
+	uint32_t refill = 0, leaf_wait = 0;
+	bool count = false;                     // the counting variant
+};
+
+struct CastPlan {
+	bool sort = false, detect = false;
+	uint32_t kernel = MRT_KERNEL_LANE, lane_map = MAP_LINEAR, quarter_all = 0;
+	enum Launch : uint32_t { PLAIN, LANE, DUAL } launch = PLAIN; // DUAL: the packet kernel, then `lane` queued behind it
+	bool count = false;                     // PLAIN / DUAL packet launch: the counting variant
+	LaneLaunch lane;                        // LANE, DUAL
+	bool scheduled = false;                 // a frame-coherent tile schedule (schedule_grid / schedule_sort) ...
+	uint32_t grid_w = 0, grid_h = 0, y0 = 0, rows = 0, tiles_x = 0; // ... of this grid (mrt_cast(COHERENT): the detected one)
+	bool pieces = false;                    // ... with its most expensive units in pieces
+	bool wait_sorts = false;                // ... launched in a measured order (the tuner times this frame)
+	bool arms_tuner = false;                // the cast's timing goes to tune_record
+	uint32_t launches = 0;                  // mrt_stats.last_kernel_launches (0: left as it is)
+};
+
+uint32_t tile_w_log2(const mrt_options &o);
+// Plans a cast.  May select (and reset) the grid state of the cast in `gs`.
+CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest &r, const PrevDetect &prev, const Knobs &k, GridStates &gs);
+
+} // namespace mrt

@@ -1,0 +1,140 @@
+// mrt_context.h — the context behind the C-ABI (mrt_ctx) and what api.hip, cast.hip and schedule.hip share: the kernel
+// launchers of kernels.hip / device_build.hip, the error and buffer helpers.
+#pragma once
+#include <cstdio>
+#include <vector>
+#include <hip/hip_runtime.h>
+#include "mrt_internal.h"
+#include "launch_policy.h"
+
+namespace mrt {
+hipError_t launch_trace(const TraceParams &p, bool any_hit, bool count, hipStream_t stream);
+const char *last_trace_variant();
+bool quad_kernel_built();
+hipError_t launch_grid_rays(const TraceParams &p, mrt_ray32 *out, hipStream_t stream);
+hipError_t launch_build_rows4(const Dev4Node *nodes4, const TriHot *hot, const TriCold *cold, uint32_t n_nodes4, uint32_t n_tris,
+		void *rows, hipStream_t stream);
+hipError_t launch_build_rows(const DevNode *nodes, const TriHot *hot, const TriCold *cold, uint32_t n_nodes, uint32_t n_tris,
+		void *rows, hipStream_t stream);
+hipError_t launch_expand_tokens(const TraceParams &p, const uint32_t *tokens, hipStream_t stream);
+hipError_t launch_offset_refs(DevNode *dst, const DevNode *src, uint32_t n, uint32_t node_base, uint32_t tri_base, void *stream);
+hipError_t launch_offset_refs8(Dev8Node *dst, const Dev8Node *src, uint32_t n, uint32_t node_base, uint32_t tri_base, void *stream);
+hipError_t launch_flatten_instances(const float *d_verts9, const mrt_instance *d_instances, const uint32_t *d_first_out,
+		uint32_t n_instances, uint32_t max_tris_per_instance, mrt_tri64 *d_out, void *stream);
+hipError_t launch_morton_keys(const void *rays, uint32_t in_fmt, uint64_t count, uint32_t *keys, uint32_t *index, hipStream_t stream);
+hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream);
+hipError_t launch_origin_dir_keys(const void *rays, uint32_t in_fmt, uint64_t count, const float lo[3], const float hi[3],
+		uint32_t *keys, uint32_t *index, hipStream_t stream);
+hipError_t launch_detect_grid(const void *rays, uint32_t in_fmt, uint64_t count, uint32_t tile_w_log2,
+		unsigned long long *scratch, uint32_t *out, uint32_t *host_out, hipStream_t stream);
+}
+
+struct DevBuf {
+	void *ptr = nullptr;
+	size_t cap = 0;
+};
+
+struct mrt_ctx {
+	int device = 0;
+	mrt_options opts{};
+	mrt::Knobs knobs;            // read from the environment by mrt_create
+	hipStream_t own_stream = nullptr;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev[6] = {};
+	char err[512] = {0};
+	// scene
+	mrt::DevNode *d_nodes = nullptr; mrt::TriHot *d_hot = nullptr; mrt::TriCold *d_cold = nullptr;
+	mrt::Dev4Node *d_nodes4 = nullptr; uint32_t n_nodes4 = 0;
+	mrt::Dev8Node *d_nodes8 = nullptr; uint32_t n_nodes8 = 0, stack8 = 0;
+	float *d_leaf_box = nullptr; // exact leaf boxes that go with d_nodes8
+	mrt::BuildArena build_arena; // temporaries of the device builder, kept between builds
+	void *d_rows4 = nullptr;     // flat scenes with the 4-wide layout: 128-byte node rows + triangle rows (packet_quad_kernel.h)
+	void *d_rows = nullptr;      // flat scenes: nodes + triangles as one array of 64-byte rows (packet_rows_kernel.h)
+	// two-level scene: d_nodes = TLAS + every BLAS, d_hot / d_cold = mesh-space triangles, d_instances in TLAS leaf order
+	mrt::DevInstance *d_instances = nullptr;
+	mrt::TwoLevelHost *two_level = nullptr; // host copy kept for mrt_update_instances
+	float bounds_lo[3] = {0, 0, 0}, bounds_hi[3] = {0, 0, 0};
+	uint32_t n_nodes = 0, n_tris = 0, depth = 0, stack_depth = 0, stack4 = 0;
+	bool scene = false;
+	// per-dispatch buffers (grow only, x1.5: gpu_ray_caster.cpp:776-817)
+	DevBuf rays, hits, keys_in, keys_out, idx_in, idx_out, sort_tmp, overflow;
+	int cu_count = 256;
+	unsigned long long *d_counters = nullptr;
+	// what detect_grid_kernel decided, also written to this host-mapped word block {row width, rows, tiles_x, verdict}
+	// so that the host knows after the stream sync which of the two queued kernels did the work (no extra copy)
+	uint32_t *h_auto = nullptr, *d_auto_host = nullptr;
+	// small host-array casts (RayDispatcher::cast_ray / any_hit: one ray; tiles of a few hundred rays): rays and hits go
+	// through two pinned, device-mapped buffers instead of two DMA copies (mrt_cast)
+	void *h_small_in = nullptr, *d_small_in = nullptr, *h_small_out = nullptr, *d_small_out = nullptr;
+	// Frame-coherent tile schedule of grid casts: what every schedule unit (one 8x8 tile, or the two of a 128-ray wave)
+	// cost in the last cast of this grid, and the launch order made of it (longest first); see schedule_grid().
+	struct TileSchedule {
+		uint32_t grid_w = 0, grid_h = 0, y0 = 0, rows = 0, unit = 0, n_units = 0, tile_w_log2 = 0; bool pieces = false;
+		// two generations: frame f notes its costs in cost[f & 1] and the side stream sorts them into order[f & 1] while frame
+		// f + 1 (launched in the order of frame f - 1) already runs: back-to-back frames never wait for a sort
+		uint32_t frame = 0, gen = 0;       // frames of this grid, sorts issued for it
+		bool measuring = false;            // this frame notes its costs (and is sorted afterwards)
+		bool have_order[2] = {false, false};
+		DevBuf cost[2], order[2], cost_sorted, iota, tmp;
+		DevBuf slots[2], hdr[2];           // what is launched: the order with its most expensive units in pieces (schedule_split)
+		uint32_t n_slots_max = 0;
+		hipStream_t side = nullptr;
+		hipEvent_t traced = nullptr, ready[2] = {nullptr, nullptr};
+		void forget() { have_order[0] = have_order[1] = false; }
+	};
+	uint64_t last_detect_count = 0;   // rays of the last cast whose row width was looked for on the device (h_auto holds what it found)
+	// per grid and cast mode, for the last few of them (mrt::GridStates): how it is cast, and its tile schedule in sched[same index]
+	mrt::GridStates grids;
+	TileSchedule sched[mrt::GridStates::kCount];
+	char queued_variant[96] = "", queued_alt_variant[96] = "", last_variant[96] = ""; // instantiation names (mrt_last_kernel_variant)
+	uint32_t queued_kernel = 0, queued_alt_kernel = 0; bool queued_detect = false; // what the last cast put on the stream
+	// host-array pipeline (cast_host_pipelined): copy streams and per-chunk events, created on first use
+	hipStream_t up_stream = nullptr, dn_stream = nullptr;
+	std::vector<hipEvent_t> pipe_ev;
+	// async state
+	bool pending = false;
+	uint64_t pending_count = 0; uint32_t pending_flags = 0; int pending_mode = 0;
+	const void *pending_dev_hits = nullptr;
+	mrt_stats stats{};
+};
+
+#define HIP_TRY(ctx, call)                                                                          \
+	do {                                                                                            \
+		hipError_t e_ = (call);                                                                     \
+		if (e_ != hipSuccess) {                                                                     \
+			std::snprintf((ctx)->err, sizeof((ctx)->err), "%s failed: %s (%s:%d)", #call,           \
+					hipGetErrorString(e_), __FILE__, __LINE__);                                      \
+			return MRT_ERR_HIP;                                                                     \
+		}                                                                                           \
+	} while (0)
+
+inline int fail(mrt_ctx *ctx, int code, const char *msg)
+{
+	if (ctx) std::snprintf(ctx->err, sizeof(ctx->err), "%s", msg);
+	return code;
+}
+
+inline int ensure(mrt_ctx *ctx, DevBuf &b, size_t bytes)
+{
+	if (b.cap >= bytes) return MRT_OK;
+	size_t want = bytes + bytes / 2; // grow x1.5
+	if (b.ptr) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); HIP_TRY(ctx, hipFree(b.ptr)); b.ptr = nullptr; b.cap = 0; }
+	hipError_t e = hipMalloc(&b.ptr, want);
+	if (e != hipSuccess) { want = bytes; e = hipMalloc(&b.ptr, want); }
+	if (e != hipSuccess) { b.ptr = nullptr; return fail(ctx, MRT_ERR_OOM, "device allocation failed"); }
+	b.cap = want;
+	return MRT_OK;
+}
+
+inline void release(DevBuf &b) { if (b.ptr) (void)hipFree(b.ptr); b.ptr = nullptr; b.cap = 0; }
+
+// api.hip
+size_t ray_stride(uint32_t flags);
+size_t hit_stride(const mrt_ctx *ctx, uint32_t flags, int mode);
+uint32_t out_format(const mrt_ctx *ctx, uint32_t flags, int mode);
+void base_params(mrt_ctx *ctx, mrt::TraceParams &p);
+int grid_params(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1, mrt::TraceParams &p);
+// schedule.hip: before the launch of a scheduled cast (fills p's schedule fields), after it (ev[4] recorded)
+int schedule_grid(mrt_ctx *ctx, const mrt::CastPlan &c, mrt::TraceParams &p);
+int schedule_sort(mrt_ctx *ctx);

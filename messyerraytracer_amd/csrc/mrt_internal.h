@@ -89,6 +89,9 @@ constexpr int kDetectScratchOff = kAutoGridOff + 8; // 1026 words: jump masks + 
 constexpr int kNextRayOff = kDetectScratchOff + 1026; // 128 words: 8 ray counters of the persistent kernels, 16 words apart
 constexpr int kCounterWords = kNextRayOff + 128;
 
+// wave slots of the device (256 CUs x 4 SIMDs x 8 waves): what a launch's work is spread over in one round
+constexpr uint32_t kWaveSlots = 8192u;
+
 constexpr uint32_t kSentinel = 0x7FFFFFFFu;
 constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kLastInLeaf = 1u;
@@ -131,12 +134,12 @@ struct TraceParams {
 	uint32_t tile_w_log2;      // lane tile: 2^k wide, 64 / 2^k high
 	uint32_t tile_order;       // 0: tiles row-major, 1: Z-order inside 16x16-tile super-tiles, 2: 32x32, 3: column strips per XCD
 	uint32_t tile_group;       // tile_order 3: consecutive tiles per workgroup (set by launch_trace)
-	// Frame-coherent tile schedule of grid casts (api.hip, TileSchedule): launch slot u runs schedule unit tile_sched[u]
+	// Frame-coherent tile schedule of grid casts (schedule.hip; mrt_ctx::TileSchedule): launch slot u runs schedule unit tile_sched[u]
 	// (a unit = tile_unit consecutive tiles: 1, or 2 for the 128-ray walk) and leaves the shader cycles it took in
 	// tile_cost[unit]; the next cast of the same grid launches the units longest first.  Both may be null.
 	// An entry of tile_sched: bits 0-27 an id, bits 28-31 what the slot's wave works on -- 0: schedule unit `id`; 1: the one tile
 	// `id` (in the wave's first group; a second group stays empty); 2 + q: quarter q of tile `id`, 4x4 pixels in lanes 0..15.
-	// The most expensive units of the last measured frame are launched in such pieces (api.hip schedule_split): a frame of a
+	// The most expensive units of the last measured frame are launched in such pieces (schedule.hip schedule_plan_kernel): a frame of a
 	// million rays ends with its longest walk, and the longest one is 2-3 x the 99th percentile.  sched_hdr[2] = slots in use
 	// (the launch covers n_slots_max); a piece parks its start time in tile_cost[n_units + slot] and ADDS its share to its unit.
 	const uint32_t *tile_sched;
@@ -144,11 +147,11 @@ struct TraceParams {
 	uint32_t tile_unit, n_units;
 	const uint32_t *sched_hdr;
 	uint32_t n_slots_max;
-	// Small grids (api.hip quarter_small_grid): EVERY tile is launched as its four quarter tiles (launch slot s = quarter s & 3 of
+	// Small grids (launch_policy.cpp quarter_rule): EVERY tile is launched as its four quarter tiles (launch slot s = quarter s & 3 of
 	// tile s >> 2, 16 rays in lanes 0..15) -- a grid of fewer tiles than the device has wave slots lasts as long as its longest
 	// walk, and a quarter tile's walk is about half as long as its tile's.
 	uint32_t quarter_all;
-	uint32_t sparse_lanes;     // linear lane map of the lane kernel: rays per wave, in lanes 0 .. sparse_lanes - 1 (0 = 64): a small batch on more, emptier waves (api.hip launch_lane)
+	uint32_t sparse_lanes;     // linear lane map of the lane kernel: rays per wave, in lanes 0 .. sparse_lanes - 1 (0 = 64): a small batch on more, emptier waves (launch_policy.cpp lane_launch)
 	uint32_t kernel;           // MRT_KERNEL_LANE / MRT_KERNEL_PACKET
 	uint32_t stack_depth;      // LDS stack entries per lane
 	uint32_t xcd_swizzle;      // 1: remap blockIdx so each XCD owns a contiguous band
