@@ -271,7 +271,8 @@ const char *mrt_last_error(const mrt_ctx *ctx);
 const char *mrt_status_string(int status);
 uint32_t mrt_version(void);
 /* sizeof() of the boundary's structs as this library was compiled, for bindings in other languages to check
- * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance (0 for anything else). */
+ * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light (0 for anything
+ * else). */
 uint32_t mrt_struct_size(uint32_t which);
 /* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream). */
 int mrt_set_stream(mrt_ctx *ctx, void *hip_stream);
@@ -443,6 +444,36 @@ int mrt_cast_grid(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t
  * grid_w-wide grid (lets the kernel tile lanes 8x8 instead of 64x1). */
 int mrt_cast_tiled(mrt_ctx *ctx, const mrt_ray32 *d_rays, mrt_hit32 *d_hits,
 		uint32_t grid_w, uint32_t rows, uint32_t query_mask, int mode);
+
+/* ---- shadow rays from resident hit records: the second batch of RayRenderer's frame
+ * (src/modules/graphics/ray_renderer.cpp:540-620, cpu_path_tracer.h:250-328), made in the trace kernel.
+ * For every (pixel, light) pair whose primary record is a hit: p = the hit position (mrt_host_hit44:
+ * its `position`; mrt_hit32: origin + direction * t of the primary ray), org = p + normal * 1e-3
+ * (SHADOW_BIAS), t_min = 0; DIRECTIONAL: dir = light.direction as given, t_max = 1000
+ * (DIR_LIGHT_MAX_DIST); POINT / SPOT: to = position - org, dist = |to|, dir = to / dist, t_max = dist,
+ * and no ray if dist < 1e-6.  Plain fp32 operations in that order.  Pairs without a ray (a primary miss,
+ * cast_shadows == 0, the degenerate point-light ray) are lit.  Any-hit under query_mask. */
+enum { MRT_LIGHT_DIRECTIONAL = 0, MRT_LIGHT_POINT = 1, MRT_LIGHT_SPOT = 2 };   /* LightData::Type */
+typedef struct mrt_light {   /* the fields of LightData (src/api/light_data.h) that shadow rays use; 32 bytes */
+	uint32_t type;           /* MRT_LIGHT_*                                                           */
+	uint32_t cast_shadows;   /* 0: every pixel is lit for this light and no ray is traced             */
+	float position[3];       /* POINT / SPOT                                                          */
+	float direction[3];      /* DIRECTIONAL: towards the light, used as given (not normalised)        */
+} mrt_light;
+#define MRT_MAX_LIGHTS 16    /* MAX_SCENE_LIGHTS */
+
+/* Shadow rays for the hit records of a cast (what mrt_cast wrote): d_rays mrt_ray32 and d_hits mrt_hit32,
+ * or with MRT_FLAG_HOST_LAYOUT mrt_host_ray60 / mrt_host_hit44 (the rays are then not read -- the record
+ * has the position -- but d_rays must still be non-null).  Output: d_mask[l * count + i] = 1 lit, 0 shadowed.  d_rays, d_hits, d_mask are
+ * device pointers, `lights` a host array.  Flags: MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC (queue on the
+ * context's stream without waiting).  n_lights == 0: MRT_OK, nothing written.  MRT_ERR_INVALID for
+ * n_lights > MRT_MAX_LIGHTS, a null pointer, count * n_lights overflowing, an unknown light type or flag. */
+int mrt_cast_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count,
+		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_hits as it wrote them, mrt_hit32):
+ * the primary rays are regenerated in the kernel.  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_cast_grid_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const mrt_hit32 *d_hits, const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags);
 
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to

@@ -13,10 +13,11 @@ HOST_TEST = os.path.join(HERE, "host_mirror_test")
 HOST_CPU_TEST = os.path.join(HERE, "host_cpu_test")
 HOST_TLAS_TEST = os.path.join(HERE, "host_tlas_test")
 POLICY_TEST = os.path.join(HERE, "launch_policy_test")
+SHADOW_POLICY_TEST = os.path.join(HERE, "shadow_policy_test")
 
 SOURCES = ["kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip", "device_build.hip",
            "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
-HEADERS = ["mrt_internal.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
+HEADERS = ["mrt_internal.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "shadow_kernel.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
            "host/host_types.hpp", "host/cpu_backend.hpp", "host/ray_tracer_server.hpp"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
@@ -121,9 +122,22 @@ def build_policy_test(force: bool = False) -> str:
     return POLICY_TEST
 
 
+def build_shadow_policy_test(force: bool = False) -> str:
+    """C++ test driver for the plans of shadow casts (launch_policy.cpp alone: host code, no device, no library)."""
+    srcs = [os.path.join(CSRC, "host", "shadow_policy_test.cpp"), os.path.join(CSRC, "launch_policy.cpp")]
+    deps = srcs + [os.path.join(CSRC, h) for h in HEADERS]
+    if force or _stale(SHADOW_POLICY_TEST, deps):
+        cmd = [_hipcc(), "-O2", "-std=c++17", "-Wall"] + srcs + ["-o", SHADOW_POLICY_TEST]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
+        if r.returncode != 0:
+            raise RuntimeError("shadow policy test build failed:\n" + r.stdout + r.stderr)
+    return SHADOW_POLICY_TEST
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_host_test(force=True))
     print(build_host_cpu_test(force=True))
     print(build_host_tlas_test(force=True))
     print(build_policy_test(force=True))
+    print(build_shadow_policy_test(force=True))

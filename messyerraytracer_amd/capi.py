@@ -29,7 +29,8 @@ SYMBOLS = [
     "mrt_create", "mrt_destroy", "mrt_last_error", "mrt_status_string", "mrt_version", "mrt_set_stream",
     "mrt_synchronize", "mrt_make_triangles", "mrt_pack_host_triangles", "mrt_bvh2_build", "mrt_bvh2_save", "mrt_bvh2_load", "mrt_upload_scene",
     "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_upload_two_level_scene", "mrt_update_instances", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
-    "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled", "mrt_expand_tokens",
+    "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
+    "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
     "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
     "mrt_group_create", "mrt_group_destroy", "mrt_group_size", "mrt_group_context", "mrt_group_last_error", "mrt_group_row_block",
@@ -120,6 +121,10 @@ def load():
     L.mrt_generate_grid.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.mrt_cast_grid.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                 C.c_void_p, C.c_uint32, C.c_int, C.c_uint32]
+    L.mrt_cast_shadows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                   C.c_uint32, C.c_uint32]
+    L.mrt_cast_grid_shadows.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_cast_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mrt_expand_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
     L.mrt_expand_grid_tokens.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -408,6 +413,25 @@ class Context:
 
     def cast_tiled(self, d_rays, d_hits, grid_w, rows, query_mask=0xFFFFFFFF, mode=MODE_NEAREST):
         self._chk(self.L.mrt_cast_tiled(self.h, _ptr(d_rays), _ptr(d_hits), grid_w, rows, query_mask, mode))
+
+    @staticmethod
+    def _lights(lights):
+        lights = np.ascontiguousarray(lights, dtype=T.LIGHT)
+        return lights, (_np(lights) if lights.shape[0] else None)
+
+    def cast_shadows(self, d_rays, d_hits, count, lights, d_mask, query_mask=0xFFFFFFFF, flags=0):
+        """Shadow rays for the hit records of a cast (device pointers / tensors: mrt_ray32 + mrt_hit32, or mrt_host_ray60 +
+        mrt_host_hit44 with FLAG_HOST_LAYOUT); lights: types.LIGHT array on the host.  d_mask[l * count + i] = 1 lit, 0 shadowed."""
+        lights, lp = self._lights(lights)
+        self._chk(self.L.mrt_cast_shadows(self.h, _ptr(d_rays), _ptr(d_hits), count, lp, lights.shape[0], _ptr(d_mask),
+                                          query_mask, flags))
+
+    def cast_grid_shadows(self, cam, grid_w, grid_h, d_hits, lights, d_mask, y0=0, y1=None, query_mask=0xFFFFFFFF, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (d_hits: its mrt_hit32 records on the device)."""
+        y1 = grid_h if y1 is None else y1
+        lights, lp = self._lights(lights)
+        self._chk(self.L.mrt_cast_grid_shadows(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), lp, lights.shape[0],
+                                               _ptr(d_mask), query_mask, flags))
 
     def expand_tokens(self, d_rays, d_tokens, d_hits, count, flags=0, stream=None):
         """Device pointers; enqueued on `stream` (raw hipStream_t) or the context's stream, not waited for."""

@@ -147,6 +147,7 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 1: return (uint32_t)sizeof(mrt_camera);
 		case 2: return (uint32_t)sizeof(mrt_stats);
 		case 3: return (uint32_t)sizeof(mrt_instance);
+		case 4: return (uint32_t)sizeof(mrt_light);
 		default: return 0u;
 	}
 }

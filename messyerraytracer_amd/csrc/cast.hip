@@ -55,13 +55,17 @@ void note_queued(mrt_ctx *ctx, uint32_t kernel)
 	std::snprintf(ctx->queued_variant, sizeof(ctx->queued_variant), "%s", mrt::last_trace_variant());
 }
 
-int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uint64_t count, bool any_hit)
+// A shadow cast (sh: its lights and records, src its SRC_SHADOW_* source) launches the shadow instantiation of the same kernel.
+struct ShadowLaunch { const mrt::ShadowParams *params; int src; };
+
+int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uint64_t count, bool any_hit, const ShadowLaunch *sh = nullptr)
 {
 	int rc;
 	p.kernel = l.kernel;
 	if (!l.persistent) {
 		p.sparse_lanes = l.sparse_lanes;
-		HIP_TRY(ctx, mrt::launch_trace(p, any_hit, l.count, ctx->stream));
+		if (sh) HIP_TRY(ctx, mrt::launch_shadow(p, *sh->params, sh->src, nullptr, nullptr, 0, 0, 0, 0, ctx->stream));
+		else HIP_TRY(ctx, mrt::launch_trace(p, any_hit, l.count, ctx->stream));
 		note_queued(ctx, p.kernel);
 		return MRT_OK;
 	}
@@ -73,7 +77,8 @@ int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uin
 	// eight ray counters (one per region of the batch), 128 bytes apart
 	unsigned long long *next_ray = ctx->d_counters + mrt::kNextRayOff;
 	HIP_TRY(ctx, hipMemsetAsync(next_ray, 0, 128 * sizeof(unsigned long long), ctx->stream));
-	HIP_TRY(ctx, mrt::launch_trace_persistent(p, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, any_hit, l.count, ctx->stream));
+	if (sh) HIP_TRY(ctx, mrt::launch_shadow(p, *sh->params, sh->src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, ctx->stream));
+	else HIP_TRY(ctx, mrt::launch_trace_persistent(p, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, any_hit, l.count, ctx->stream));
 	note_queued(ctx, p.kernel);
 	return MRT_OK;
 }
@@ -81,7 +86,7 @@ int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uin
 // Runs a plan on the context's stream: pre-processing of rays from an array (sort, detect) from ev[2] to ev[3] (last_sort_ms), the
 // trace launches from ev[3] to ev[4] (last_trace_ms), then the sort of a measuring frame's tile costs on the side stream.  p holds
 // the batch (rays, hits, formats, grid); the plan decides the rest.
-int launch_planned(mrt_ctx *ctx, const mrt::CastPlan &c, const mrt::CastRequest &r, mrt::TraceParams &p)
+int launch_planned(mrt_ctx *ctx, const mrt::CastPlan &c, const mrt::CastRequest &r, mrt::TraceParams &p, const ShadowLaunch *sh = nullptr)
 {
 	int rc;
 	const bool rays = mrt::ray_entry(r.entry), any = r.mode == MRT_MODE_ANY_HIT;
@@ -114,7 +119,7 @@ int launch_planned(mrt_ctx *ctx, const mrt::CastPlan &c, const mrt::CastRequest 
 		if ((rc = launch_lane(ctx, c.lane, lp, r.count, any))) return rc; // runs if the batch is judged incoherent
 		std::swap(ctx->queued_kernel, ctx->queued_alt_kernel); std::swap(ctx->queued_variant, ctx->queued_alt_variant);
 	} else if (c.launch == mrt::CastPlan::LANE) {
-		if ((rc = launch_lane(ctx, c.lane, p, r.count, any))) return rc;
+		if ((rc = launch_lane(ctx, c.lane, p, r.count, any, sh))) return rc;
 	} else {
 		HIP_TRY(ctx, mrt::launch_trace(p, any, c.count, ctx->stream));
 		note_queued(ctx, p.kernel);
@@ -250,6 +255,45 @@ int cast_host_pipelined(mrt_ctx *ctx, const void *rays, void *hits, uint64_t cou
 	ctx->stats.last_kernel_launches = launches;
 	ctx->stats.last_h2d_ms = ctx->stats.last_d2h_ms = 0.0f; // overlapped: not separable (last_trace_ms is the last chunk's)
 	return finish_timing(ctx, false, launches >= 2, false);
+}
+
+// The shadow casts (mrt_cast_shadows, mrt_cast_grid_shadows) after their own checks: p holds the scene, the grid (grid source) and
+// the primary rays (SRC_SHADOW_RAY32); count = records.
+int cast_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
+		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	const uint32_t known = (entry == mrt::ENTRY_SHADOW ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
+	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a shadow cast");
+	if (n_lights > MRT_MAX_LIGHTS) return fail(ctx, MRT_ERR_INVALID, "more than MRT_MAX_LIGHTS lights");
+	if (!d_hits || !d_mask || (n_lights && !lights)) return fail(ctx, MRT_ERR_INVALID, "null hits / lights / mask");
+	if (n_lights && count > ~0ull / n_lights) return fail(ctx, MRT_ERR_INVALID, "count * n_lights overflows");
+	mrt::ShadowParams s;
+	std::memset(&s, 0, sizeof(s));
+	s.records = d_hits; s.pixels = count;
+	for (uint32_t l = 0; l < n_lights; l++) {
+		const mrt_light &L = lights[l];
+		if (L.type > MRT_LIGHT_SPOT) return fail(ctx, MRT_ERR_INVALID, "unknown light type");
+		mrt::ShadowLight &d = s.light[l];
+		d.kind = !L.cast_shadows ? mrt::SHADOW_OFF : (L.type == MRT_LIGHT_DIRECTIONAL ? mrt::SHADOW_DIRECTIONAL : mrt::SHADOW_POINT);
+		const float *v = L.type == MRT_LIGHT_DIRECTIONAL ? L.direction : L.position;
+		d.v[0] = v[0]; d.v[1] = v[1]; d.v[2] = v[2];
+	}
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (count == 0 || n_lights == 0) return MRT_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	p.hits = d_mask; p.count = count * n_lights; p.query_mask = query_mask;
+	p.out_fmt = mrt::OUT_BOOL8;
+	// (the plan reads neither the detected grid nor the grid states: an empty PrevDetect)
+	const mrt::CastRequest r{entry, p.count, flags, MRT_MODE_ANY_HIT};
+	const mrt::CastPlan c = mrt::plan_cast(ctx->opts, scene_facts(ctx), r, mrt::PrevDetect{}, ctx->knobs, ctx->grids);
+	const ShadowLaunch sh{&s, src};
+	int rc = launch_planned(ctx, c, r, p, &sh);
+	if (rc) return rc;
+	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
+	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
 }
 
 } // namespace
@@ -398,6 +442,29 @@ int mrt_cast_tiled(mrt_ctx *ctx, const mrt_ray32 *d_rays, mrt_hit32 *d_hits,
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
 	return finish_timing(ctx, false, false, false);
+}
+
+int mrt_cast_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count,
+		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
+	mrt::TraceParams p;
+	base_params(ctx, p);
+	p.rays = d_rays; // (SRC_SHADOW_HOST44: not read, the record has the position)
+	const int src = (flags & MRT_FLAG_HOST_LAYOUT) ? mrt::SRC_SHADOW_HOST44 : mrt::SRC_SHADOW_RAY32;
+	return cast_shadows(ctx, mrt::ENTRY_SHADOW, src, p, d_hits, count, lights, n_lights, d_mask, query_mask, flags);
+}
+
+int mrt_cast_grid_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const mrt_hit32 *d_hits, const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	mrt::TraceParams p;
+	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
+	if (rc) return rc;
+	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the pairs; the kernel regenerates the primary ray from p.cam itself)
+	return cast_shadows(ctx, mrt::ENTRY_GRID_SHADOW, mrt::SRC_SHADOW_GRID, p, d_hits, p.count, lights, n_lights, d_mask, query_mask, flags);
 }
 
 } // extern "C"

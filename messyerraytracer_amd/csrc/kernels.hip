@@ -14,6 +14,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include "mrt_internal.h"
 
 namespace mrt {
@@ -328,125 +329,17 @@ __device__ __forceinline__ void finish_two_level_ray(const TraceParams &p, uint6
 	store_hit(p, ray_idx, r, best_t, prim, best_u, best_v, nx, ny, nz, layers, best_slot);
 }
 
+#include "shadow_kernel.h"
+
 // ---- the traversal kernel: one lane = one ray -------------------------------------
 // LDS: per-lane stack, entry d of lane l at dword d*64 + l of the wave's region
 // (conflict-free: the 64 lanes of a push/pop hit 64 consecutive dwords).
 template <bool ANY_HIT, bool COUNT>
 __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 {
-	extern __shared__ uint32_t lds_stack[];
-	if (skip_launch(p)) return;
-	uint32_t block = blockIdx.x;
-	if (p.xcd_swizzle) { // contiguous band of the batch per XCD (blocks are dealt round-robin over 8 XCDs)
-		const uint32_t per = gridDim.x >> 3;
-		if (block < (per << 3)) block = (block & 7u) * per + (block >> 3);
-	}
-	uint64_t ray_idx = 0; uint32_t px = 0, py = 0;
-	if (!lane_ray_index(p, block, ray_idx, px, py)) return;
-	RayRegs r;
-	load_ray(p, ray_idx, px, py, r);
-
-	float best_t = r.t_max, best_u = 0.0f, best_v = 0.0f;
-	uint32_t best_slot = 0xFFFFFFFFu, best_id = 0xFFFFFFFFu;
-	uint32_t n_nodes = 0, n_tris = 0, max_sp = 0;
-
-	if (!(r.t_min >= r.t_max)) { // degenerate rays are misses, glsl:214-222
-		const float ix = safe_inv(r.dx), iy = safe_inv(r.dy), iz = safe_inv(r.dz);
-		const float nrx = -(r.ox * ix), nry = -(r.oy * iy), nrz = -(r.oz * iz);
-		const uint32_t lane = threadIdx.x & (MRT_WAVE - 1);
-		const uint32_t wave = threadIdx.x / MRT_WAVE;
-		uint32_t sp = wave * (p.stack_depth * MRT_WAVE) + lane; // dword index of this lane's stack bottom
-		lds_stack[sp] = kSentinel; sp += MRT_WAVE;
-		uint32_t cur = 0; // the root is always a wide node (root leaves are wrapped on the host)
-		const float4 *nodes = reinterpret_cast<const float4 *>(p.nodes);
-		const float4 *hot = reinterpret_cast<const float4 *>(p.tri_hot);
-
-		while (cur != kSentinel) {
-			// ---- inner nodes: glsl:243-318 ----
-			while (cur < kSentinel) {
-				const float4 *n = nodes + (size_t)cur * 4u;
-				const float4 a = n[0], b = n[1], c = n[2], d = n[3];
-				if (COUNT) n_nodes++;
-				// ray_aabb (glsl:84-99) for both children, clamped to [t_min, best_t]
-				const float l0x = fma_(a.x, ix, nrx), l1x = fma_(b.x, ix, nrx);
-				const float l0y = fma_(a.y, iy, nry), l1y = fma_(b.y, iy, nry);
-				const float l0z = fma_(a.z, iz, nrz), l1z = fma_(b.z, iz, nrz);
-				const float r0x = fma_(c.x, ix, nrx), r1x = fma_(d.x, ix, nrx);
-				const float r0y = fma_(c.y, iy, nry), r1y = fma_(d.y, iy, nry);
-				const float r0z = fma_(c.z, iz, nrz), r1z = fma_(d.z, iz, nrz);
-				const float tl = fmaxf(fmaxf(fminf(l0x, l1x), fminf(l0y, l1y)), fmaxf(fminf(l0z, l1z), r.t_min));
-				const float tlx = fminf(fminf(fmaxf(l0x, l1x), fmaxf(l0y, l1y)), fminf(fmaxf(l0z, l1z), best_t));
-				const float tr = fmaxf(fmaxf(fminf(r0x, r1x), fminf(r0y, r1y)), fmaxf(fminf(r0z, r1z), r.t_min));
-				const float trx = fminf(fminf(fmaxf(r0x, r1x), fmaxf(r0y, r1y)), fminf(fmaxf(r0z, r1z), best_t));
-				const bool hl = tl <= tlx, hr = tr <= trx;
-				const uint32_t lref = __float_as_uint(a.w), rref = __float_as_uint(b.w);
-				if (hl && hr) { // near child first, far child pushed (glsl:290-305)
-					const bool left_near = tl < tr;
-					cur = left_near ? lref : rref;
-					lds_stack[sp] = left_near ? rref : lref; sp += MRT_WAVE;
-					if (COUNT) { const uint32_t dpt = (sp - lane) / MRT_WAVE - wave * p.stack_depth; max_sp = dpt > max_sp ? dpt : max_sp; }
-				} else if (hl) cur = lref;
-				else if (hr) cur = rref;
-				else { sp -= MRT_WAVE; cur = lds_stack[sp]; }
-			}
-			// ---- leaves: INTERSECT_LEAF, glsl:166-192 ----
-			while (cur >= kLeafBit) {
-				uint32_t slot = cur & 0x7FFFFFFFu;
-				bool last;
-				do {
-					const float4 *t3 = hot + (size_t)slot * 3u;
-					const float4 q0 = t3[0], q1 = t3[1], q2 = t3[2];
-					last = (__float_as_uint(q2.w) & kLastInLeaf) != 0u;
-					if ((__float_as_uint(q1.w) & p.query_mask) != 0u) {
-						if (COUNT) n_tris++;
-						// ray_triangle, glsl:105-131 == Triangle::intersect, src/core/triangle.h:56-105
-						const float pvx = fma_(r.dy, q2.z, -(r.dz * q2.y));
-						const float pvy = fma_(r.dz, q2.x, -(r.dx * q2.z));
-						const float pvz = fma_(r.dx, q2.y, -(r.dy * q2.x));
-						const float det = dot3(q1.x, q1.y, q1.z, pvx, pvy, pvz);
-						if (!(__builtin_fabsf(det) < 1e-8f)) {
-							const float inv_det = 1.0f / det;
-							const float tvx = r.ox - q0.x, tvy = r.oy - q0.y, tvz = r.oz - q0.z;
-							const float u = dot3(tvx, tvy, tvz, pvx, pvy, pvz) * inv_det;
-							if (!(u < 0.0f || u > 1.0f)) {
-								const float qvx = fma_(tvy, q1.z, -(tvz * q1.y));
-								const float qvy = fma_(tvz, q1.x, -(tvx * q1.z));
-								const float qvz = fma_(tvx, q1.y, -(tvy * q1.x));
-								const float v = dot3(r.dx, r.dy, r.dz, qvx, qvy, qvz) * inv_det;
-								if (!(v < 0.0f || u + v > 1.0f)) {
-									const float t = dot3(q2.x, q2.y, q2.z, qvx, qvy, qvz) * inv_det;
-									// glsl:124 accepts t_min <= t < best_t; an exact tie goes to the lower
-									// triangle id so the answer does not depend on the visiting order
-									const uint32_t id = __float_as_uint(q0.w);
-									if (!(t < r.t_min) && (t < best_t || (t == best_t && best_slot != 0xFFFFFFFFu && id < best_id))) {
-										best_t = t; best_u = u; best_v = v; best_slot = slot; best_id = id;
-										if (ANY_HIT) last = true;
-									}
-								}
-							}
-						}
-					}
-					slot++;
-				} while (!last);
-				if (ANY_HIT && best_slot != 0xFFFFFFFFu) { cur = kSentinel; break; }
-				sp -= MRT_WAVE; cur = lds_stack[sp];
-			}
-		}
-	}
-
-	// ---- result: glsl:322-327 ----
-	finish_ray(p, ray_idx, r, best_t, best_u, best_v, best_slot);
-
-	if (COUNT) {
-		atomicAdd(&p.counters[kCntRays], 1ull);
-		atomicAdd(&p.counters[kCntTris], (unsigned long long)n_tris);
-		atomicAdd(&p.counters[kCntNodes], (unsigned long long)n_nodes);
-		if (best_slot != 0xFFFFFFFFu) atomicAdd(&p.counters[kCntHits], 1ull);
-		atomicMax(&p.counters[kCntMaxStack], (unsigned long long)max_sp);
-		// one lane = one ray: every node step is a (divergent) node fetch, every test a triangle row
-		atomicAdd(&p.counters[kCntWaveNodeFetch], (unsigned long long)n_nodes);
-		atomicAdd(&p.counters[kCntWaveTriFetch], (unsigned long long)n_tris);
-	}
+	constexpr int SRC = SRC_CAST;
+	const ShadowParams *sh = nullptr;
+#include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 
 #include "lane_persistent_kernel.h"
@@ -457,6 +350,30 @@ __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 #include "packet_quad_kernel.h"
 #endif
 #include "two_level_kernel.h"
+
+// ---- shadow casts (shadow_kernel.h): the lane kernels a non-coherent any-hit batch can get, with a shadow ray source -------
+// (the bodies are the ones of trace_lane_kernel, trace_two_level_kernel and trace_lane_persistent_kernel, included with SRC set)
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void trace_shadow_lane_kernel(const TraceParams p, const ShadowParams s)
+{
+	constexpr bool ANY_HIT = true, COUNT = false;
+	const ShadowParams *sh = &s;
+#include "lane_walk.inc" // (in scope: the names its first lines check)
+}
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void trace_shadow_two_level_kernel(const TraceParams p, const ShadowParams s)
+{
+	constexpr bool ANY_HIT = true;
+	const ShadowParams *sh = &s;
+#include "two_level_walk.inc" // (in scope: the names its first lines check)
+}
+template <int SRC, int WIDTH, bool TL>
+__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_shadow_persistent_kernel(const TraceParams p, const PersistParams q, const ShadowParams s)
+{
+	constexpr bool ANY_HIT = true, COUNT = false;
+	const ShadowParams *sh = &s;
+#include "persistent_walk.inc" // (in scope: the names its first lines check)
+}
 
 // ---- the unified row array of packet_rows_kernel.h ------------------------------------------------------------
 // rows[0, n_nodes) = the wide nodes with leaf refs rebased to row indices (0x80000000 | (n_nodes + first slot));
@@ -934,17 +851,24 @@ hipError_t launch_trace(const TraceParams &p_in, bool any_hit, bool count, hipSt
 	return hipGetLastError();
 }
 
-// Persistent lane kernel: `blocks` workgroups stay resident and pull rays from *next_ray.
-hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream)
+static PersistParams persist_params(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks)
 {
-	if (p.count == 0 || blocks == 0) return hipSuccess;
 	PersistParams q;
 	q.next_ray = next_ray; q.overflow = overflow; q.overflow_stride = blocks * MRT_WG;
 	q.lds_depth = lds_depth; q.refill = refill; q.leaf_wait = leaf_wait ? leaf_wait : 1u;
 	// about 32 chunks per wave, between one wave's worth of rays and MRT_RAY_CHUNK
 	const uint64_t per_wave = p.count / ((uint64_t)blocks * (MRT_WG / MRT_WAVE)) / 32u;
 	q.chunk = per_wave >= MRT_RAY_CHUNK ? MRT_RAY_CHUNK : (per_wave <= MRT_WAVE ? MRT_WAVE : (uint32_t)(per_wave & ~63ull));
+	return q;
+}
+
+// Persistent lane kernel: `blocks` workgroups stay resident and pull rays from *next_ray.
+hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream)
+{
+	if (p.count == 0 || blocks == 0) return hipSuccess;
+	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
 	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * lds_depth * MRT_WAVE * sizeof(uint32_t);
 	const bool wide8 = p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr;
 	const bool wide4 = p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr;
@@ -975,6 +899,48 @@ hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *nex
 		const int width = tl ? ((p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) ? 8 : 2) : (wide8 ? 8 : (wide4 ? 4 : 2));
 		note_variant("trace_lane_persistent_kernel<%s, %d, %s, %s>", MRT_B(any_hit), width, MRT_B(tl), MRT_B(count && !tl));
 	}
+	return hipGetLastError();
+}
+
+// Shadow casts: p.kernel is the lane kernel the plan chose (launch_policy.cpp, ENTRY_SHADOW / ENTRY_GRID_SHADOW); p.count = pairs.
+// persistent: blocks != 0 (as launch_trace_persistent), else the plain kernel with p.sparse_lanes.
+template <int SRC>
+static void launch_shadow_src(const TraceParams &p, const ShadowParams &s, const PersistParams &q, uint32_t blocks, hipStream_t stream)
+{
+	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
+	if (blocks == 0) {
+		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
+		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
+		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
+		if (tl) hipLaunchKernelGGL((trace_shadow_two_level_kernel<SRC>), grid, wg, lds, stream, p, s);
+		else hipLaunchKernelGGL((trace_shadow_lane_kernel<SRC>), grid, wg, lds, stream, p, s);
+		note_variant("trace_shadow_%s_kernel<%d>", tl ? "two_level" : "lane", SRC);
+		return;
+	}
+	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
+	int width = 2;
+	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
+		width = 8; hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else if (tl) hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) {
+		width = 8; hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 8, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) {
+		width = 4; hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 4, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 2, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	note_variant("trace_shadow_persistent_kernel<%d, %d, %s>", SRC, width, MRT_B(tl));
+}
+
+hipError_t launch_shadow(const TraceParams &p, const ShadowParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
+{
+	if (p.count == 0) return hipSuccess;
+	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
+	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
+	if (src == SRC_SHADOW_RAY32) launch_shadow_src<SRC_SHADOW_RAY32>(p, s, q, blocks, stream);
+	else if (src == SRC_SHADOW_HOST44) launch_shadow_src<SRC_SHADOW_HOST44>(p, s, q, blocks, stream);
+	else if (src == SRC_SHADOW_GRID) launch_shadow_src<SRC_SHADOW_GRID>(p, s, q, blocks, stream);
+	else return hipErrorInvalidValue;
 	return hipGetLastError();
 }
 

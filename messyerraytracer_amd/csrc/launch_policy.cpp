@@ -167,8 +167,30 @@ void tune_record(GridTune &t, float trace_ms)
 	t.armed = false;
 }
 
+// Shadow casts: count = pixels * lights any-hit rays made in the kernel, in pixel order (which already groups nearby origins), never
+// sorted (the rays never exist in memory) and never tiled.  The lane kernels as for any incoherent batch: the plain one (small batches on
+// emptier waves), from 2^16 rays the persistent ones (8-, 4- or 2-wide, two-level scenes their own).  The packet kernels have no shadow
+// source: a forced one means the policy's own lane kernel.  Shadow kernels have no counting variant.  Nothing of the grid state
+// (detected widths, the grid tuner, tile schedules) is read or changed: a renderer that alternates primary and shadow casts keeps its
+// primary grid's plan exactly as it is without them.
+static CastPlan plan_shadow(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
+{
+	CastPlan c;
+	mrt_options so = o;
+	so.count_visits = 0;
+	if (so.kernel != MRT_KERNEL_LANE && !persistent_lane_kernel(so.kernel)) so.kernel = MRT_KERNEL_AUTO;
+	const uint32_t kernel = pick_kernel(so, s, false, r.count);
+	const bool persistent = persistent_lane_kernel(kernel) || (so.kernel == MRT_KERNEL_AUTO && r.count >= 65536);
+	c.launch = CastPlan::LANE;
+	c.lane = lane_launch(so, s, r.count, MAP_LINEAR, persistent);
+	c.kernel = c.lane.kernel;
+	c.launches = (r.flags & MRT_FLAG_ASYNC) ? 0 : 1;
+	return c;
+}
+
 CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest &r, const PrevDetect &prev, const Knobs &k, GridStates &gs)
 {
+	if (shadow_entry(r.entry)) return plan_shadow(o, s, r);
 	CastPlan c;
 	const uint64_t n = r.count;
 	const bool auto_k = o.kernel == MRT_KERNEL_AUTO, coherent = (r.flags & MRT_FLAG_COHERENT) != 0;

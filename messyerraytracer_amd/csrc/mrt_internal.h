@@ -12,6 +12,7 @@ static_assert(sizeof(mrt_bvh_node_wide64) == 64, "GPUBVHNodeWide must be 64 byte
 static_assert(sizeof(mrt_host_ray60) == 60, "Ray must be 60 bytes (src/core/ray.h:25-51, precision=single)");
 static_assert(sizeof(mrt_host_hit44) == 44, "Intersection must be 44 bytes (src/core/intersection.h:16-40)");
 static_assert(sizeof(mrt_host_tri80) == 80, "Triangle must be 80 bytes (src/core/triangle.h:22-39)");
+static_assert(sizeof(mrt_light) == 32, "mrt_light must be 32 bytes");
 
 namespace mrt {
 
@@ -161,6 +162,19 @@ struct TraceParams {
 	uint32_t count_mode;       // COUNT variants: mrt_options.count_visits (1: visit counters, 2: only the sampled clock of the rows kernel)
 	uint32_t extra_lds;        // experiments: dynamic LDS bytes added per workgroup of the packet kernels (occupancy sweeps)
 	mrt_camera cam;
+};
+
+// ---- shadow rays (shadow_kernel.h): made in the trace kernel from the hit records of a cast -----------------------------
+// Entry g of a shadow cast is the pair (light g / pixels, pixel g % pixels); TraceParams::count = pixels * lights, hits = the
+// lit mask (one byte per entry), rays = the primary rays (SRC_SHADOW_RAY32).  The ray source is a template parameter of the
+// kernels (SRC_CAST: the rays of an ordinary cast, the instantiations that existed before).
+enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, SRC_SHADOW_GRID = 3 };
+enum ShadowKind : uint32_t { SHADOW_OFF = 0, SHADOW_DIRECTIONAL = 1, SHADOW_POINT = 2 }; // OFF: cast_shadows == 0 (lit)
+struct ShadowLight { uint32_t kind; float v[3]; }; // DIRECTIONAL: direction towards the light; POINT (point and spot): position
+struct ShadowParams {
+	const void *records;       // mrt_hit32 (SRC_SHADOW_RAY32, SRC_SHADOW_GRID) or mrt_host_hit44 (SRC_SHADOW_HOST44), `pixels` of them
+	uint64_t pixels;
+	ShadowLight light[MRT_MAX_LIGHTS];
 };
 
 // host-side preparation (scene_prep.cpp)

@@ -216,6 +216,71 @@ def flatten_instances(local: np.ndarray, inst: np.ndarray) -> np.ndarray:
     return np.concatenate(out).astype(np.float32)
 
 
+
+def _facing(tris: np.ndarray, point, towards: bool) -> np.ndarray:
+    """Winds every triangle so that its normal cross(v1 - v0, v2 - v0) points towards `point` (or away from it)."""
+    e1, e2 = tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]
+    side = np.einsum("ij,ij->i", np.cross(e1, e2), np.asarray(point, np.float32) - tris.mean(axis=1))
+    flip = (side < 0) if towards else (side > 0)
+    out = tris.copy()
+    out[flip, 1], out[flip, 2] = tris[flip, 2], tris[flip, 1]
+    return out
+
+
+def room(subdiv: int = 29, size: float = 10.0, height: float = 6.0):
+    """A shadow test scene in the shapes of the reference's demo scene (tools/generate_demo_assets.py): a closed room of
+    subdivided wall quads (floor, ceiling and four walls, one mesh each, normals facing into the room), a 32 x 16 UV sphere and
+    two boxes (one mesh, two instances).  Returns mesh-space vertices (n,3,3) float32 and one types.INSTANCE per placed mesh:
+    the walls on layer 2, the sphere and the boxes on layer 1.  flatten_instances(*room()) is the same scene flat (11 076
+    triangles with the default subdivision).  The sphere's vertices come from float64 sin / cos rounded to float32."""
+    from . import types as T
+    f = np.float32
+    n, hs, hh = subdiv, f(size / 2), f(height)
+    walls = [  # corner, u, v: the cells are corner + u * i / n + v * j / n
+        ((-hs, f(0), -hs), (0, 0, size), (size, 0, 0)),     # floor
+        ((-hs, hh, -hs), (size, 0, 0), (0, 0, size)),       # ceiling
+        ((-hs, f(0), -hs), (0, height, 0), (0, 0, size)),   # x = -size / 2
+        ((hs, f(0), -hs), (0, 0, size), (0, height, 0)),    # x = +size / 2
+        ((-hs, f(0), -hs), (size, 0, 0), (0, height, 0)),   # z = -size / 2
+        ((-hs, f(0), hs), (0, height, 0), (size, 0, 0)),    # z = +size / 2
+    ]
+    centre = (f(0), hh / f(2), f(0))
+    meshes = []
+    for corner, u, v in walls:
+        c, u, v = np.asarray(corner, f), np.asarray(u, f), np.asarray(v, f)
+        k = np.arange(n + 1, dtype=f) / f(n)
+        grid = c[None, None, :] + u[None, None, :] * k[:, None, None] + v[None, None, :] * k[None, :, None]
+        p00, p10, p11, p01 = grid[:-1, :-1], grid[1:, :-1], grid[1:, 1:], grid[:-1, 1:]
+        quads = np.stack([np.stack([p00, p10, p11], axis=2), np.stack([p00, p11, p01], axis=2)], axis=2)
+        meshes.append(_facing(quads.reshape(-1, 3, 3), centre, towards=True))
+    # UV sphere, unit radius: 32 segments, 16 rings (one triangle per cell at the poles)
+    th = (np.arange(17, dtype=np.float64) * np.pi / 16)[:, None]
+    ph = (np.arange(33, dtype=np.float64) * 2 * np.pi / 32)[None, :]
+    sp = np.stack([np.sin(th) * np.cos(ph), np.cos(th) * np.ones_like(ph), np.sin(th) * np.sin(ph)], axis=-1).astype(f)
+    sphere = []
+    for r in range(16):
+        for q in range(32):
+            a, b, c, d = sp[r, q], sp[r + 1, q], sp[r + 1, q + 1], sp[r, q + 1]
+            if r != 0:
+                sphere.append((a, c, d))
+            if r != 15:
+                sphere.append((a, b, c))
+    meshes.append(_facing(np.asarray(sphere, f), (0, 0, 0), towards=False))
+    meshes.append(cube())  # unit box centred on the origin (outward already)
+    local = np.concatenate(meshes).astype(f)
+    inst = np.zeros(9, dtype=T.INSTANCE)
+    first = np.cumsum([0] + [m.shape[0] for m in meshes])
+    place = [(k, 2, np.eye(3), (0, 0, 0)) for k in range(6)]
+    rot = np.array([[0.8, 0.0, 0.6], [0.0, 1.0, 0.0], [-0.6, 0.0, 0.8]])  # about y, a 3-4-5 triangle
+    place += [(6, 1, 1.25 * np.eye(3), (0.5, 1.25, -0.5)),            # the sphere, resting on the floor
+              (7, 1, 1.5 * rot, (-2.25, 0.75, 1.25)),                 # a box of side 1.5, turned
+              (7, 1, np.diag([1.0, 2.5, 1.0]), (2.5, 1.25, -2.0))]    # a pillar
+    for i, (m, layers, basis, origin) in enumerate(place):
+        inst[i]["first_tri"], inst[i]["n_tris"], inst[i]["layers"] = first[m], meshes[m].shape[0], layers
+        inst[i]["basis"] = np.asarray(basis, f).reshape(9)
+        inst[i]["origin"] = np.asarray(origin, f)
+    return local, inst
+
 # Named workloads of BASELINE.json `configs`.
 CONFIGS = {
     "C1": dict(scene="cube", grid=(16, 12), origin=(0.0, 0.0, 3.0), forward=(0.0, 0.0, -1.0), fov=60.0),

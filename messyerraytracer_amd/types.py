@@ -25,7 +25,11 @@ HOST_TRI80 = np.dtype([("v0", "<f4", 3), ("v1", "<f4", 3), ("v2", "<f4", 3), ("e
 INSTANCE = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("layers", "<u4"), ("reserved", "<u4"),
                      ("basis", "<f4", 9), ("origin", "<f4", 3)])  # mrt_instance
 
-assert INSTANCE.itemsize == 64
+LIGHT = np.dtype([("type", "<u4"), ("cast_shadows", "<u4"), ("position", "<f4", 3), ("direction", "<f4", 3)])  # mrt_light
+LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2
+MAX_LIGHTS = 16
+
+assert INSTANCE.itemsize == 64 and LIGHT.itemsize == 32
 assert RAY32.itemsize == 32 and HIT32.itemsize == 32 and TRI64.itemsize == 64
 assert NODE32.itemsize == 32 and WIDE64.itemsize == 64
 assert HOST_RAY60.itemsize == 60 and HOST_HIT44.itemsize == 44 and HOST_TRI80.itemsize == 80
