@@ -153,7 +153,7 @@ typedef struct mrt_stats {
 	uint32_t detected_grid_w;    /* count_visits: row width found for the last coherent mrt_cast (0 = none) */
 	uint32_t reserved;           /* 1 if the last batch declared coherent went to the one-lane-per-ray kernel by the device's verdict:
 	                                judged incoherent, or fewer than 2^15 rays in which no row width was found */
-	float last_build_ms;         /* device time of the last mrt_build_scene_device */
+	float last_build_ms;         /* device time of the last mrt_build_scene_device (or mrt_refit_scene / mrt_refit_instanced_scene) */
 	uint32_t last_kernel;        /* MRT_KERNEL_* that did the work of the last blocking cast (a batch declared coherent is
 	                                checked on the device: this is the kernel the device chose); 0 after an ASYNC cast */
 	/* count_visits, memory-side view of the walk (what the roofline of bench.py prices): */
@@ -360,6 +360,24 @@ int mrt_flatten_instances(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh_tri
 		const mrt_instance *instances, uint32_t n_instances, uint32_t flags, mrt_tri64 *d_out);
 /* mrt_flatten_instances into a scratch buffer + mrt_build_scene_device over it. */
 int mrt_build_instanced_scene_device(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh_tris,
+		const mrt_instance *instances, uint32_t n_instances, uint32_t flags);
+
+/* ---- refit: new vertices for the resident flat scene's tree ----
+ * tris: as many triangles as the scene has, in the order of the array it came from (mrt_upload_scene, every form of
+ * mrt_build_scene_device, the flattened array of mrt_build_instanced_scene_device); triangle i of the new array takes the
+ * place of triangle i of the old one, whole row (vertices, normal, id, layers).  The tree keeps its shape and gets new boxes
+ * (the wide layouts and row arrays are re-derived from them), so casts return what they return against a fresh build of the
+ * new triangles; the tree walks worse as the motion grows (rebuild then).  flags: 0 or MRT_BUILD_TRIS_ON_DEVICE.  Blocks until
+ * done; ordered on the context's stream (a cast queued before with MRT_FLAG_ASYNC sees the old triangles).  Unlike a new scene,
+ * what the context learnt about its grids (tuner, tile schedules, detected widths) is kept.  mrt_stats.last_build_ms = device time
+ * of the refit.  Returns MRT_ERR_INVALID (null argument, unknown flag, a count other than the scene's, a non-finite coordinate),
+ * MRT_ERR_NO_SCENE, MRT_ERR_UNSUPPORTED (a two-level scene: mrt_update_instances), MRT_ERR_PENDING (collect first): the scene is
+ * then unchanged.  MRT_ERR_HIP if the refit tree fails its check pass: the scene is then released. */
+int mrt_refit_scene(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris, uint32_t flags);
+/* mrt_flatten_instances (verts9 on the host, or on the device with MRT_BUILD_TRIS_ON_DEVICE) + mrt_refit_scene over the result:
+ * the same meshes and instances as the scene's mrt_build_instanced_scene_device, with new vertices or transforms (the flattened
+ * count must be the scene's). */
+int mrt_refit_instanced_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh_tris,
 		const mrt_instance *instances, uint32_t n_instances, uint32_t flags);
 
 /* ---- two-level scene: SceneTLAS + MeshBLAS + BLASInstance (src/accel/scene_tlas.h:140-251,

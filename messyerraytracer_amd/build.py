@@ -15,7 +15,7 @@ HOST_TLAS_TEST = os.path.join(HERE, "host_tlas_test")
 POLICY_TEST = os.path.join(HERE, "launch_policy_test")
 SHADOW_POLICY_TEST = os.path.join(HERE, "shadow_policy_test")
 
-SOURCES = ["kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip", "device_build.hip",
+SOURCES = ["kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip", "device_build.hip", "refit.hip",
            "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
 HEADERS = ["mrt_internal.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "shadow_kernel.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
            "host/host_types.hpp", "host/cpu_backend.hpp", "host/ray_tracer_server.hpp"]

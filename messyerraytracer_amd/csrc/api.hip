@@ -78,8 +78,6 @@ int grid_params(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t g
 	return MRT_OK;
 }
 
-namespace {
-
 void free_scene(mrt_ctx *ctx)
 {
 	if (ctx->d_nodes) (void)hipFree(ctx->d_nodes);
@@ -96,6 +94,9 @@ void free_scene(mrt_ctx *ctx)
 	if (ctx->d_instances) (void)hipFree(ctx->d_instances);
 	ctx->d_instances = nullptr;
 	if (ctx->two_level) { mrt::free_two_level(ctx->two_level); delete ctx->two_level; ctx->two_level = nullptr; }
+	if (ctx->d_slot_src) (void)hipFree(ctx->d_slot_src);
+	if (ctx->d_parent) (void)hipFree(ctx->d_parent);
+	ctx->d_slot_src = nullptr; ctx->d_parent = nullptr;
 	ctx->d_nodes = nullptr; ctx->d_hot = nullptr; ctx->d_cold = nullptr; ctx->d_nodes4 = nullptr; ctx->d_nodes8 = nullptr;
 	ctx->n_nodes8 = ctx->stack8 = 0;
 	ctx->scene = false; ctx->n_nodes = ctx->n_tris = 0;
@@ -103,6 +104,8 @@ void free_scene(mrt_ctx *ctx)
 		ctx->sched[k].forget(); ctx->grids.e[k].tune.phase = 0; ctx->grids.e[k].tune.mode = -1;
 	}
 }
+
+namespace {
 
 // Flat scenes: the unified row array of the assembly packet walk, built on the device from the arrays just
 // uploaded / built.  Optional: a scene too large for its 26-bit row index, or a device short of memory, goes
@@ -246,7 +249,7 @@ void mrt_destroy(mrt_ctx *ctx)
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
 	free_scene(ctx);
 	release(ctx->rays); release(ctx->hits); release(ctx->keys_in); release(ctx->keys_out);
-	release(ctx->idx_in); release(ctx->idx_out); release(ctx->sort_tmp); release(ctx->overflow);
+	release(ctx->idx_in); release(ctx->idx_out); release(ctx->sort_tmp); release(ctx->overflow); release(ctx->refit_in);
 	for (auto &sc : ctx->sched) {
 		if (sc.side) { (void)hipStreamSynchronize(sc.side); (void)hipStreamDestroy(sc.side); }
 		if (sc.traced) (void)hipEventDestroy(sc.traced);
@@ -307,7 +310,8 @@ int mrt_upload_scene(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris,
 			(e = hipMalloc(&ctx->d_cold, (size_t)h.n_tris * sizeof(mrt::TriCold))) != hipSuccess ||
 			(want4 && (e = hipMalloc(&ctx->d_nodes4, (size_t)h.n_nodes4 * sizeof(mrt::Dev4Node))) != hipSuccess) ||
 			(h.nodes8 && ((e = hipMalloc(&ctx->d_nodes8, (size_t)h.n_nodes8 * sizeof(mrt::Dev8Node))) != hipSuccess ||
-					(e = hipMalloc(&ctx->d_leaf_box, (size_t)h.n_tris * 32)) != hipSuccess))) {
+					(e = hipMalloc(&ctx->d_leaf_box, (size_t)h.n_tris * 32)) != hipSuccess)) ||
+			(e = hipMalloc(&ctx->d_slot_src, (size_t)h.n_tris * 4)) != hipSuccess) {
 		cleanup(); free_scene(ctx);
 		return fail(ctx, MRT_ERR_OOM, "scene does not fit in device memory");
 	}
@@ -317,6 +321,7 @@ int mrt_upload_scene(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris,
 	if (e == hipSuccess && want4) e = hipMemcpy(ctx->d_nodes4, h.nodes4, (size_t)h.n_nodes4 * sizeof(mrt::Dev4Node), hipMemcpyHostToDevice);
 	if (e == hipSuccess && h.nodes8) e = hipMemcpy(ctx->d_nodes8, h.nodes8, (size_t)h.n_nodes8 * sizeof(mrt::Dev8Node), hipMemcpyHostToDevice);
 	if (e == hipSuccess && h.nodes8) e = hipMemcpy(ctx->d_leaf_box, h.leaf_box, (size_t)h.n_tris * 32, hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = hipMemcpy(ctx->d_slot_src, prim_idx, (size_t)h.n_tris * 4, hipMemcpyHostToDevice); // slot k holds triangle prim_idx[k]
 	ctx->n_nodes4 = want4 ? h.n_nodes4 : 0;
 	ctx->n_nodes8 = h.nodes8 ? h.n_nodes8 : 0; ctx->stack8 = h.stack8;
 	for (int c = 0; c < 3; c++) { ctx->bounds_lo[c] = h.bounds_lo[c]; ctx->bounds_hi[c] = h.bounds_hi[c]; }
@@ -361,14 +366,18 @@ int mrt_build_scene_device(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris,
 		d_tris = (const mrt_tri64 *)staged;
 	}
 	mrt::DeviceBuildResult b;
+	if (hipMalloc(&b.slot_src, (size_t)n_tris * 4) != hipSuccess) {
+		if (staged) (void)hipFree(staged);
+		return fail(ctx, MRT_ERR_OOM, "scene does not fit in device memory");
+	}
 	const bool want4 = ctx->opts.kernel == MRT_KERNEL_LANE4_PERSISTENT || ctx->opts.kernel == MRT_KERNEL_PACKET_QUAD || ctx->opts.kernel == MRT_KERNEL_AUTO;
 	const bool want8 = ctx->opts.kernel == MRT_KERNEL_LANE8_PERSISTENT || ctx->opts.kernel == MRT_KERNEL_AUTO;
 	rc = mrt::device_build_lbvh(d_tris, n_tris, want4, want8, (flags & MRT_BUILD_SAFE_HANDOFF) != 0, (flags & MRT_BUILD_SAH) ? 2 : (flags & MRT_BUILD_PLOC) ? 1 : 0, &ctx->build_arena, (void *)ctx->stream, &b,
 			ctx->err, sizeof(ctx->err));
 	if (staged) (void)hipFree(staged);
-	if (rc) return rc;
+	if (rc) { (void)hipFree(b.slot_src); return rc; }
 	auto drop_build = [&] { // the build's arrays are ours until the context takes them over below
-		(void)hipFree(b.nodes); (void)hipFree(b.hot); (void)hipFree(b.cold);
+		(void)hipFree(b.nodes); (void)hipFree(b.hot); (void)hipFree(b.cold); (void)hipFree(b.slot_src);
 		if (b.nodes4) (void)hipFree(b.nodes4);
 		if (b.nodes8) (void)hipFree(b.nodes8);
 		if (b.leaf_box) (void)hipFree(b.leaf_box);
@@ -383,7 +392,7 @@ int mrt_build_scene_device(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris,
 	if (te == hipSuccess) te = hipEventElapsedTime(&ms, e0, e1);
 	if (te != hipSuccess) { drop_build(); return fail(ctx, MRT_ERR_HIP, hipGetErrorString(te)); }
 	free_scene(ctx);
-	ctx->d_nodes = b.nodes; ctx->d_hot = b.hot; ctx->d_cold = b.cold;
+	ctx->d_nodes = b.nodes; ctx->d_hot = b.hot; ctx->d_cold = b.cold; ctx->d_slot_src = b.slot_src;
 	ctx->d_nodes4 = b.nodes4; ctx->n_nodes4 = b.nodes4 ? b.n_nodes : 0; ctx->stack4 = b.stack4;
 	ctx->d_nodes8 = b.nodes8; ctx->d_leaf_box = b.leaf_box; ctx->n_nodes8 = b.nodes8 ? b.n_nodes : 0; ctx->stack8 = b.stack8;
 	ctx->n_nodes = b.n_nodes; ctx->n_tris = b.n_tris; ctx->depth = b.depth;

@@ -847,6 +847,20 @@ hipError_t launch_offset_refs8(Dev8Node *dst, const Dev8Node *src, uint32_t n, u
 	return hipGetLastError();
 }
 
+// the wide layouts of a refit tree (refit.hip), re-derived at binary-node indices as a device build lays them out
+hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream)
+{
+	if (n_nodes == 0) return hipSuccess;
+	hipLaunchKernelGGL(lbvh_collapse4_kernel, dim3((n_nodes + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, nodes, n_nodes, nodes4);
+	return hipGetLastError();
+}
+hipError_t launch_collapse8(const DevNode *nodes, uint32_t n_nodes, Dev8Node *nodes8, float *leaf_box, uint32_t *bad, hipStream_t stream)
+{
+	if (n_nodes == 0) return hipSuccess;
+	hipLaunchKernelGGL(lbvh_collapse8_kernel, dim3((n_nodes + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, nodes, n_nodes, nodes8, leaf_box, bad);
+	return hipGetLastError();
+}
+
 hipError_t launch_offset_refs(DevNode *dst, const DevNode *src, uint32_t n, uint32_t node_base, uint32_t tri_base, void *stream)
 {
 	if (n == 0) return hipSuccess;
@@ -1090,6 +1104,7 @@ int device_build_lbvh(const mrt_tri64 *d_tris, uint32_t n, bool want4, bool want
 			if (attempt >= 1) { std::snprintf(err, err_len, "device build: the tree failed its verification pass (%u nodes)", h[8]); cleanup(); return MRT_ERR_HIP; }
 		}
 	}
+	if (out->slot_src) DB_TRY(hipMemcpyAsync(out->slot_src, idx_b, nn * 4, hipMemcpyDeviceToDevice, stream)); // (before the arena is reused)
 	out->nodes = nodes; out->hot = hot; out->cold = cold;
 	out->n_nodes = n_rows; out->n_tris = n;
 	out->depth = h[6] + 1u; // pending entries on the deepest path + the sentinel

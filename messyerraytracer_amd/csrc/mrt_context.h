@@ -20,6 +20,8 @@ hipError_t launch_build_rows4(const Dev4Node *nodes4, const TriHot *hot, const T
 hipError_t launch_build_rows(const DevNode *nodes, const TriHot *hot, const TriCold *cold, uint32_t n_nodes, uint32_t n_tris,
 		void *rows, hipStream_t stream);
 hipError_t launch_expand_tokens(const TraceParams &p, const uint32_t *tokens, hipStream_t stream);
+hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);
+hipError_t launch_collapse8(const DevNode *nodes, uint32_t n_nodes, Dev8Node *nodes8, float *leaf_box, uint32_t *bad, hipStream_t stream);
 hipError_t launch_offset_refs(DevNode *dst, const DevNode *src, uint32_t n, uint32_t node_base, uint32_t tri_base, void *stream);
 hipError_t launch_offset_refs8(Dev8Node *dst, const Dev8Node *src, uint32_t n, uint32_t node_base, uint32_t tri_base, void *stream);
 hipError_t launch_flatten_instances(const float *d_verts9, const mrt_instance *d_instances, const uint32_t *d_first_out,
@@ -51,7 +53,10 @@ struct mrt_ctx {
 	mrt::Dev4Node *d_nodes4 = nullptr; uint32_t n_nodes4 = 0;
 	mrt::Dev8Node *d_nodes8 = nullptr; uint32_t n_nodes8 = 0, stack8 = 0;
 	float *d_leaf_box = nullptr; // exact leaf boxes that go with d_nodes8
-	mrt::BuildArena build_arena; // temporaries of the device builder, kept between builds
+	mrt::BuildArena build_arena; // temporaries of the device builder, kept between builds (and of the refit)
+	// flat scenes, for mrt_refit_scene (refit.hip): slot k of d_hot / d_cold holds input triangle d_slot_src[k] (every flat-scene path
+	// writes it); d_parent, made by the first refit and kept: every node's parent, | 1 << 31 for a right child, 0xFFFFFFFF for the root
+	uint32_t *d_slot_src = nullptr, *d_parent = nullptr;
 	void *d_rows4 = nullptr;     // flat scenes with the 4-wide layout: 128-byte node rows + triangle rows (packet_quad_kernel.h)
 	void *d_rows = nullptr;      // flat scenes: nodes + triangles as one array of 64-byte rows (packet_rows_kernel.h)
 	// two-level scene: d_nodes = TLAS + every BLAS, d_hot / d_cold = mesh-space triangles, d_instances in TLAS leaf order
@@ -62,6 +67,7 @@ struct mrt_ctx {
 	bool scene = false;
 	// per-dispatch buffers (grow only, x1.5: gpu_ray_caster.cpp:776-817)
 	DevBuf rays, hits, keys_in, keys_out, idx_in, idx_out, sort_tmp, overflow;
+	DevBuf refit_in;               // a refit's triangles, staged from the host or flattened from instances
 	int cu_count = 256;
 	unsigned long long *d_counters = nullptr;
 	// what detect_grid_kernel decided, also written to this host-mapped word block {row width, rows, tiles_x, verdict}
@@ -133,6 +139,7 @@ inline int ensure(mrt_ctx *ctx, DevBuf &b, size_t bytes)
 inline void release(DevBuf &b) { if (b.ptr) (void)hipFree(b.ptr); b.ptr = nullptr; b.cap = 0; }
 
 // api.hip
+void free_scene(mrt_ctx *ctx);
 size_t ray_stride(uint32_t flags);
 size_t hit_stride(const mrt_ctx *ctx, uint32_t flags, int mode);
 uint32_t out_format(const mrt_ctx *ctx, uint32_t flags, int mode);

@@ -202,6 +202,7 @@ struct DeviceBuildResult {
 	float *leaf_box = nullptr;   // with nodes8: exact leaf boxes, 8 floats per slot
 	uint32_t n_nodes = 0, n_tris = 0, depth = 0, stack4 = 0, stack8 = 0;
 	float bounds_lo[3] = {0, 0, 0}, bounds_hi[3] = {0, 0, 0};
+	uint32_t *slot_src = nullptr; // in, optional: n device words, filled with the input triangle of every slot (what a refit rewrites slot k from)
 };
 struct BuildArena { void *ptr = nullptr; size_t cap = 0; uint32_t *pinned = nullptr; }; // the builder's temporaries: owned by the context, grown on demand (pinned: 64 host bytes the per-level counters are read back into)
 // form: 0 the radix tree over the Morton keys (fastest build), 1 PLOC, 2 binned SAH (the host builder's tree; leaves of several triangles)

@@ -1,0 +1,390 @@
+// refit.hip — new triangles for the resident tree of a flat scene (mrt_refit_scene, mrt_refit_instanced_scene).
+//
+// A refit keeps the tree's topology -- every node's refs and counts, every leaf's slot range -- and recomputes the boxes
+// from the new triangles.  Casts return what they return against a fresh build of the new triangles, because results do
+// not depend on which valid BVH is walked; the tree only walks worse as the motion grows.  On the
+// context's stream, in order:
+//   1. the box of every slot's new triangle, the scene bounds and a non-finite flag  (refit_boxes_kernel; read back:
+//      a refused refit has written nothing of the scene)
+//   2. the triangle rows: slot k <- input triangle slot_src[k], leaf-end flags kept    (refit_rows_kernel)
+//   3. every node's parent, once per scene                                              (refit_parents_kernel)
+//   4. the boxes bottom-up                                                              (refit_climb_kernel)
+//   5. a check that every box a node holds is its child's own union                     (refit_verify_kernel)
+//   6. the 4- and 8-wide layouts and the row arrays, as a build derives them            (device_build.hip, kernels.hip)
+// DESIGN.md 4.8 has the measurements.
+#include <cfloat>
+#include <cstdio>
+#include <cstring>
+#include <hip/hip_runtime.h>
+#include "mrt_context.h"
+
+namespace mrt {
+
+namespace {
+
+#define REFIT_WG 256
+#define REFIT_BOXES_BLOCKS 1024u
+
+struct Box { float mn[3], mx[3]; };
+
+// The box rule of lbvh_bounds_kernel (device_build.hip): the vertices v0, v0 + e1, v0 + e2 as the intersection test
+// sees them, one ulp outwards (a rounded sum may lie half an ulp inside the true vertex).
+__device__ __forceinline__ float ulp_down(float f) { return f == 0.0f ? -FLT_MIN : __uint_as_float(__float_as_uint(f) + (f > 0.0f ? -1 : 1)); }
+__device__ __forceinline__ float ulp_up(float f) { return f == 0.0f ? FLT_MIN : __uint_as_float(__float_as_uint(f) + (f > 0.0f ? 1 : -1)); }
+__device__ __forceinline__ uint32_t f2ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+
+// left then right: every union of the refit is taken in this order, so the climb and the check agree bit for bit
+__device__ __forceinline__ Box unite(const Box &l, const Box &r)
+{
+	Box u;
+	for (int k = 0; k < 3; k++) { u.mn[k] = fminf(l.mn[k], r.mn[k]); u.mx[k] = fmaxf(l.mx[k], r.mx[k]); }
+	return u;
+}
+
+// the union of the slots [first, first + count) (a host SAH leaf holds several; the root leaf of a tiny scene is wrapped
+// as two children over the halves of one range)
+__device__ __forceinline__ Box leaf_union(const Box *boxes, uint32_t first, uint32_t count)
+{
+	Box u = boxes[first];
+	for (uint32_t j = 1; j < count; j++) u = unite(u, boxes[first + j]);
+	return u;
+}
+
+__device__ __forceinline__ void put_side(DevNode *row, int side, const Box &b)
+{
+	float *mn = side ? row->rmin : row->lmin, *mx = side ? row->rmax : row->lmax;
+	for (int k = 0; k < 3; k++) { mn[k] = b.mn[k]; mx[k] = b.mx[k]; }
+}
+// the same, write-through (sc1: agent-scope relaxed atomic stores, 8 + 4 bytes per corner), for a box another thread reads in the launch
+typedef __attribute__((address_space(1))) unsigned long long refit_gu64;
+typedef __attribute__((address_space(1))) unsigned int refit_gu32;
+#define REFIT_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+__device__ __forceinline__ void put_side_sc1(DevNode *row, int side, const Box &b)
+{
+	float *mn = side ? row->rmin : row->lmin, *mx = side ? row->rmax : row->lmax;
+	__hip_atomic_store((refit_gu64 *)mn, (unsigned long long)__float_as_uint(b.mn[0]) | ((unsigned long long)__float_as_uint(b.mn[1]) << 32), REFIT_RLX);
+	__hip_atomic_store((refit_gu32 *)(mn + 2), __float_as_uint(b.mn[2]), REFIT_RLX);
+	__hip_atomic_store((refit_gu64 *)mx, (unsigned long long)__float_as_uint(b.mx[0]) | ((unsigned long long)__float_as_uint(b.mx[1]) << 32), REFIT_RLX);
+	__hip_atomic_store((refit_gu32 *)(mx + 2), __float_as_uint(b.mx[2]), REFIT_RLX);
+}
+__device__ __forceinline__ Box get_side(const DevNode *row, int side)
+{
+	const float *mn = side ? row->rmin : row->lmin, *mx = side ? row->rmax : row->lmax;
+	Box b;
+	for (int k = 0; k < 3; k++) { b.mn[k] = mn[k]; b.mx[k] = mx[k]; }
+	return b;
+}
+
+// 1. boxes[k] = box of input triangle slot_src[k] (slot order: a leaf's boxes are contiguous); scal[0..5] = the bounds
+//    (ordered uint: min, max), scal[6] != 0 if any coordinate is not finite.  Grid-stride, one atomic per block and component.
+__global__ __launch_bounds__(REFIT_WG) void refit_boxes_kernel(const mrt_tri64 *tris, const uint32_t *slot_src, uint32_t n, Box *boxes, uint32_t *scal)
+{
+	__shared__ float part[REFIT_WG / 64][6];
+	float mn[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, mx[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
+	bool finite = true;
+	for (uint32_t k = blockIdx.x * REFIT_WG + threadIdx.x; k < n; k += gridDim.x * REFIT_WG) {
+		const float4 *t = reinterpret_cast<const float4 *>(tris + slot_src[k]);
+		const float4 a = t[0], b = t[1], c = t[2];
+		const float v0[3] = { a.x, a.y, a.z }, e1[3] = { b.x, b.y, b.z }, e2[3] = { c.x, c.y, c.z };
+		Box bx;
+		for (int i = 0; i < 3; i++) {
+			const float p1 = v0[i] + e1[i], p2 = v0[i] + e2[i];
+			finite = finite && __builtin_isfinite(v0[i]) && __builtin_isfinite(e1[i]) && __builtin_isfinite(e2[i]) &&
+					__builtin_isfinite(p1) && __builtin_isfinite(p2);
+			bx.mn[i] = ulp_down(fminf(v0[i], fminf(p1, p2)));
+			bx.mx[i] = ulp_up(fmaxf(v0[i], fmaxf(p1, p2)));
+			mn[i] = fminf(mn[i], bx.mn[i]); mx[i] = fmaxf(mx[i], bx.mx[i]);
+		}
+		boxes[k] = bx;
+	}
+	if (!finite) atomicOr(&scal[6], 1u);
+	for (int i = 0; i < 3; i++) {
+		float lo = mn[i], hi = mx[i];
+		for (int off = 32; off > 0; off >>= 1) { lo = fminf(lo, __shfl_xor(lo, off)); hi = fmaxf(hi, __shfl_xor(hi, off)); }
+		if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][i] = lo; part[threadIdx.x >> 6][3 + i] = hi; }
+	}
+	__syncthreads();
+	if (threadIdx.x < 6u) {
+		const bool is_min = threadIdx.x < 3u;
+		float v = part[0][threadIdx.x];
+		for (uint32_t w = 1; w < REFIT_WG / 64; w++) v = is_min ? fminf(v, part[w][threadIdx.x]) : fmaxf(v, part[w][threadIdx.x]);
+		if (is_min) atomicMin(&scal[threadIdx.x], f2ord(v)); else atomicMax(&scal[threadIdx.x], f2ord(v));
+	}
+}
+
+// 2. slot k <- input triangle slot_src[k]: the whole row (v0, edges, id, layers, normal) but the leaf-end flag, which is the tree's
+__global__ __launch_bounds__(REFIT_WG) void refit_rows_kernel(const mrt_tri64 *tris, const uint32_t *slot_src, uint32_t n, TriHot *hot, TriCold *cold)
+{
+	const uint32_t k = blockIdx.x * REFIT_WG + threadIdx.x;
+	if (k >= n) return;
+	const float4 *t = reinterpret_cast<const float4 *>(tris + slot_src[k]);
+	const float4 a = t[0], b = t[1], d = t[3];
+	float4 c = t[2];
+	c.w = __uint_as_float(hot[k].flags & kLastInLeaf);
+	float4 *h = reinterpret_cast<float4 *>(hot + k);
+	h[0] = a; h[1] = b; h[2] = c;
+	float4 nn = d; nn.w = 0.0f;
+	reinterpret_cast<float4 *>(cold)[k] = nn;
+}
+
+// 3. parent[c] = b for the left child c of node b, b | 1 << 31 for the right one; the root's is 0xFFFFFFFF
+__global__ __launch_bounds__(REFIT_WG) void refit_parents_kernel(const DevNode *nodes, uint32_t n_nodes, uint32_t *parent)
+{
+	const uint32_t b = blockIdx.x * REFIT_WG + threadIdx.x;
+	if (b >= n_nodes) return;
+	const uint32_t l = nodes[b].left_ref, r = nodes[b].right_ref;
+	if (b == 0u) parent[0] = 0xFFFFFFFFu;
+	if (l < n_nodes && l != 0u) parent[l] = b;
+	if (r < n_nodes && r != 0u) parent[r] = b | 0x80000000u;
+}
+
+// 4. The climb.  A node whose children are both leaves boxes them and owns itself; a node with one leaf child boxes it and
+//    arrives at itself with it, as a finished child would.  A thread that finishes a node writes the node's box into its
+//    parent's row (its own side only: refs and counts stay) and adds one to the parent's arrival counter; the second to
+//    arrive owns the parent, reads the other side and climbs on.  The hand-off crosses CUs and XCDs (per-XCD L2s are not
+//    coherent with each other, a CU's L1 is never refreshed by another CU's stores), so it is the write-through form with
+//    an acquire (MI355X guide, inter-workgroup visibility; the R1 recipe): the box is stored sc1, the storing thread drains
+//    its stores (s_waitcnt vmcnt(0)) before its agent-scope add to the counter, and the owner takes an agent acquire
+//    (buffer_inv sc1: its CU's L1) before its plain loads of the other side.  No release fence: an agent release writes back
+//    the XCD's whole L2, and one per wave and level made this pass 4x slower.
+__global__ __launch_bounds__(REFIT_WG) void refit_climb_kernel(DevNode *nodes, uint32_t n_nodes, const Box *boxes, uint32_t n_tris,
+		const uint32_t *parent, uint32_t *arrivals)
+{
+	const uint32_t b = blockIdx.x * REFIT_WG + threadIdx.x;
+	if (b >= n_nodes) return;
+	const DevNode g = nodes[b];
+	const bool ll = (g.left_ref & kLeafBit) != 0u, rl = (g.right_ref & kLeafBit) != 0u;
+	if (!ll && !rl) return;
+	// (a leaf range outside the triangle arrays cannot come from a builder of this library; the check pass reports it)
+	auto leaf = [&](uint32_t ref, uint32_t count) {
+		const uint32_t first = (ref & 0x7FFFFFFFu) < n_tris ? (ref & 0x7FFFFFFFu) : n_tris - 1u;
+		return leaf_union(boxes, first, count == 0u ? 1u : (count <= n_tris - first ? count : n_tris - first));
+	};
+	Box have;
+	uint32_t node = b;
+	int side = ll ? 0 : 1;
+	bool owned = ll && rl;
+	if (owned) {
+		const Box lb = leaf(g.left_ref, g.left_count), rb = leaf(g.right_ref, g.right_count);
+		put_side(nodes + b, 0, lb); put_side(nodes + b, 1, rb);
+		have = unite(lb, rb);
+	} else have = ll ? leaf(g.left_ref, g.left_count) : leaf(g.right_ref, g.right_count);
+	for (;;) {
+		if (!owned) {
+			put_side_sc1(nodes + node, side, have);
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the box is out before the counter moves
+			const uint32_t before = __hip_atomic_fetch_add(&arrivals[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (before == 0u) return; // the other side is not finished: its thread climbs on
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+			const Box other = get_side(nodes + node, side ^ 1);
+			have = side ? unite(other, have) : unite(have, other);
+		}
+		owned = false;
+		const uint32_t p = parent[node];
+		if (p == 0xFFFFFFFFu) return;
+		node = p & 0x7FFFFFFFu; side = (int)(p >> 31);
+		if (node >= n_nodes) return;
+	}
+}
+
+// 5. After the kernel boundary: every box a node holds must be what its child says -- the union of a leaf's slot boxes, the union
+//    of an inner child's two boxes.  A stale hand-off (or a broken tree) shows as a count in *bad.
+__global__ __launch_bounds__(REFIT_WG) void refit_verify_kernel(const DevNode *nodes, uint32_t n_nodes, const Box *boxes, uint32_t n_tris, uint32_t *bad)
+{
+	const uint32_t b = blockIdx.x * REFIT_WG + threadIdx.x;
+	if (b >= n_nodes) return;
+	const DevNode g = nodes[b];
+	bool ok = true;
+	for (int side = 0; side < 2; side++) {
+		const uint32_t ref = side ? g.right_ref : g.left_ref;
+		Box want;
+		if (ref & kLeafBit) {
+			const uint32_t first = ref & 0x7FFFFFFFu, cnt = side ? g.right_count : g.left_count;
+			if (cnt == 0u || first >= n_tris || cnt > n_tris - first) { ok = false; continue; }
+			want = leaf_union(boxes, first, cnt);
+		} else {
+			if (ref >= n_nodes) { ok = false; continue; }
+			want = unite(get_side(nodes + ref, 0), get_side(nodes + ref, 1));
+		}
+		const Box have = get_side(&g, side);
+		for (int k = 0; k < 3; k++)
+			ok = ok && __float_as_uint(have.mn[k]) == __float_as_uint(want.mn[k]) && __float_as_uint(have.mx[k]) == __float_as_uint(want.mx[k]);
+	}
+	if (!ok) atomicAdd(bad, 1u);
+}
+
+} // namespace
+
+} // namespace mrt
+
+namespace {
+
+inline float ord2f(uint32_t o)
+{
+	const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
+	float f; std::memcpy(&f, &u, 4); return f;
+}
+
+// The refit of the resident flat scene from n_tris = ctx->n_tris device triangles (checked by the callers).  Blocks until it is
+// done.  Everything that can fail before the scene is written (allocation, a non-finite coordinate) fails with the scene as it was.
+int refit_flat_scene(mrt_ctx *ctx, const mrt_tri64 *d_tris)
+{
+	using namespace mrt;
+	const uint32_t n = ctx->n_tris, nn = ctx->n_nodes;
+	const size_t box_bytes = ((size_t)n * sizeof(Box) + 255u) & ~(size_t)255u, arr_bytes = ((size_t)nn * 4u + 255u) & ~(size_t)255u;
+	const size_t need = box_bytes + arr_bytes + 256u;
+	if (ctx->build_arena.cap < need) {
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		if (ctx->build_arena.ptr) (void)hipFree(ctx->build_arena.ptr);
+		ctx->build_arena.ptr = nullptr; ctx->build_arena.cap = 0;
+		if (hipMalloc(&ctx->build_arena.ptr, need) != hipSuccess) { ctx->build_arena.ptr = nullptr; return fail(ctx, MRT_ERR_OOM, "refit: out of device memory"); }
+		ctx->build_arena.cap = need;
+	}
+	char *A = (char *)ctx->build_arena.ptr;
+	Box *boxes = (Box *)A;
+	uint32_t *arrivals = (uint32_t *)(A + box_bytes);
+	uint32_t *scal = (uint32_t *)(A + box_bytes + arr_bytes); // bounds[6], non-finite, verification failures, collapse8 "bad"
+	// what the first refit of a scene allocates: the parent array; a host-uploaded scene's wide layouts at binary-node indices
+	// (its compact host collapse has no map from binary nodes to wide nodes)
+	uint32_t *parent = ctx->d_parent;
+	Dev4Node *nodes4 = ctx->d_nodes4; Dev8Node *nodes8 = ctx->d_nodes8;
+	auto drop_new = [&] {
+		if (parent != ctx->d_parent) (void)hipFree(parent);
+		if (nodes4 != ctx->d_nodes4) (void)hipFree(nodes4);
+		if (nodes8 != ctx->d_nodes8) (void)hipFree(nodes8);
+	};
+	auto alloc = [](auto **p, size_t bytes) { if (hipMalloc((void **)p, bytes) == hipSuccess) return true; *p = nullptr; return false; };
+	bool ok = true;
+	if (!parent) ok = alloc(&parent, (size_t)nn * 4u);
+	if (ok && nodes4 && ctx->n_nodes4 != nn) ok = alloc(&nodes4, (size_t)nn * sizeof(Dev4Node));
+	if (ok && nodes8 && ctx->n_nodes8 != nn) ok = alloc(&nodes8, (size_t)nn * sizeof(Dev8Node));
+	if (!ok) { drop_new(); return fail(ctx, MRT_ERR_OOM, "refit: out of device memory"); }
+	// (hipMalloc leaves a failed pointer null: drop_new frees nothing that is the scene's)
+	auto bail = [&](hipError_t e, const char *what, bool written) {
+		drop_new();
+		if (written) free_scene(ctx); // part of the scene may be new, part old: released rather than kept wrong
+		std::snprintf(ctx->err, sizeof(ctx->err), "refit: %s failed: %s%s", what, hipGetErrorString(e), written ? "; the scene was released" : "");
+		return MRT_ERR_HIP;
+	};
+
+	// 1. boxes, bounds and the non-finite flag; read back before anything of the scene is written
+	hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1], e2 = ctx->ev[2], e3 = ctx->ev[3];
+	const uint32_t blocks = (n + REFIT_WG - 1u) / REFIT_WG, node_blocks = (nn + REFIT_WG - 1u) / REFIT_WG;
+	const uint32_t init[10] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+	uint32_t h[10];
+	hipError_t e = hipEventRecord(e0, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(scal, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(refit_boxes_kernel, dim3(blocks < REFIT_BOXES_BLOCKS ? blocks : REFIT_BOXES_BLOCKS), dim3(REFIT_WG), 0, ctx->stream, d_tris, ctx->d_slot_src, n, boxes, scal);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e != hipSuccess) return bail(e, "the box pass", false);
+	if (h[6] != 0u) { drop_new(); return fail(ctx, MRT_ERR_INVALID, "refit: a triangle has a non-finite coordinate (the scene is unchanged)"); }
+
+	// 2-6. rows, parents (first refit), climb, check, wide layouts, row arrays
+	e = hipEventRecord(e2, ctx->stream);
+	if (e == hipSuccess) { hipLaunchKernelGGL(refit_rows_kernel, dim3(blocks), dim3(REFIT_WG), 0, ctx->stream, d_tris, ctx->d_slot_src, n, ctx->d_hot, ctx->d_cold); e = hipGetLastError(); }
+	if (e == hipSuccess && parent != ctx->d_parent) { hipLaunchKernelGGL(refit_parents_kernel, dim3(node_blocks), dim3(REFIT_WG), 0, ctx->stream, ctx->d_nodes, nn, parent); e = hipGetLastError(); }
+	if (e == hipSuccess) e = hipMemsetAsync(arrivals, 0, (size_t)nn * 4u, ctx->stream);
+	if (e == hipSuccess) { hipLaunchKernelGGL(refit_climb_kernel, dim3(node_blocks), dim3(REFIT_WG), 0, ctx->stream, ctx->d_nodes, nn, boxes, n, parent, arrivals); e = hipGetLastError(); }
+	if (e == hipSuccess) { hipLaunchKernelGGL(refit_verify_kernel, dim3(node_blocks), dim3(REFIT_WG), 0, ctx->stream, ctx->d_nodes, nn, boxes, n, scal + 7); e = hipGetLastError(); }
+	if (e == hipSuccess && nodes4) e = launch_collapse4(ctx->d_nodes, nn, nodes4, ctx->stream);
+	if (e == hipSuccess && nodes8) e = launch_collapse8(ctx->d_nodes, nn, nodes8, ctx->d_leaf_box, scal + 8, ctx->stream);
+	if (e == hipSuccess && ctx->d_rows) e = launch_build_rows(ctx->d_nodes, ctx->d_hot, ctx->d_cold, nn, n, ctx->d_rows, ctx->stream);
+	if (e == hipSuccess && ctx->d_rows4 && nodes4 == ctx->d_nodes4) e = launch_build_rows4(nodes4, ctx->d_hot, ctx->d_cold, ctx->n_nodes4, n, ctx->d_rows4, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipEventRecord(e3, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e != hipSuccess) return bail(e, "the refit", true);
+
+	// the new arrays are the scene's now
+	ctx->d_parent = parent;
+	const bool new4 = nodes4 != ctx->d_nodes4;
+	if (new4) { (void)hipFree(ctx->d_nodes4); ctx->d_nodes4 = nodes4; ctx->n_nodes4 = nn; }
+	if (nodes8 != ctx->d_nodes8) { (void)hipFree(ctx->d_nodes8); ctx->d_nodes8 = nodes8; ctx->n_nodes8 = nn; }
+	if (h[7] != 0u) {
+		// boxes that are not what the tree needs could make casts miss: the scene is released rather than kept wrong
+		free_scene(ctx);
+		std::snprintf(ctx->err, sizeof(ctx->err), "refit: the tree failed its verification pass (%u nodes); the scene was released", h[7]);
+		return MRT_ERR_HIP;
+	}
+	// the walks' stack bounds by the builder's rule (device_build.hip): every 4-wide node on a path leaves at most 3 entries pending
+	// and descends at least one binary level, every 8-wide node at most 7
+	const uint32_t levels = ctx->depth - 1u;
+	if (ctx->d_nodes4) ctx->stack4 = 3u * levels + 1u;
+	if (ctx->d_nodes8) ctx->stack8 = 7u * levels + 1u;
+	if (ctx->d_nodes8 && h[8] != 0u) { // a box that fits no grid: the scene goes without the 8-wide layout, as a build does
+		(void)hipFree(ctx->d_nodes8); (void)hipFree(ctx->d_leaf_box);
+		ctx->d_nodes8 = nullptr; ctx->d_leaf_box = nullptr; ctx->n_nodes8 = ctx->stack8 = 0;
+	}
+	if (new4 && ctx->d_rows4) {
+		// the 4-wide rows (builds with the four-wide packet walk) of a host-uploaded scene's first refit: sized by the new layout,
+		// under build_rows' conditions (api.hip), else the scene goes without them as an upload would
+		(void)hipFree(ctx->d_rows4); ctx->d_rows4 = nullptr;
+		const uint64_t n_units4 = (uint64_t)2u * nn + n;
+		if (ctx->stack4 <= 64u && n_units4 < kAsmNodeLimit) {
+			if (hipMalloc(&ctx->d_rows4, (size_t)n_units4 * 64u) != hipSuccess) { ctx->d_rows4 = nullptr; (void)hipGetLastError(); }
+			else {
+				e = launch_build_rows4(ctx->d_nodes4, ctx->d_hot, ctx->d_cold, nn, n, ctx->d_rows4, ctx->stream);
+				if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+				if (e != hipSuccess) return bail(e, "the 4-wide rows", true);
+			}
+		}
+	}
+	float ms0 = 0.0f, ms1 = 0.0f;
+	if (hipEventElapsedTime(&ms0, e0, e1) == hipSuccess && hipEventElapsedTime(&ms1, e2, e3) == hipSuccess) ctx->stats.last_build_ms = ms0 + ms1;
+	for (int c = 0; c < 3; c++) { ctx->bounds_lo[c] = ord2f(h[c]); ctx->bounds_hi[c] = ord2f(h[3 + c]); }
+	return MRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// refusals that leave the scene as it is, in the order the header lists them
+static int refit_precheck(mrt_ctx *ctx, uint32_t flags)
+{
+	if (flags & ~(uint32_t)MRT_BUILD_TRIS_ON_DEVICE) return fail(ctx, MRT_ERR_INVALID, "refit: unknown flag");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "refit: collect the pending dispatch first");
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "refit: no scene uploaded");
+	if (ctx->two_level) return fail(ctx, MRT_ERR_UNSUPPORTED, "refit: a two-level scene (mrt_update_instances moves its instances)");
+	if (!ctx->d_slot_src) return fail(ctx, MRT_ERR_UNSUPPORTED, "refit: the scene has no slot map");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	return MRT_OK;
+}
+
+int mrt_refit_scene(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (!tris) return fail(ctx, MRT_ERR_INVALID, "refit: null triangles");
+	int rc = refit_precheck(ctx, flags);
+	if (rc) return rc;
+	if (n_tris != ctx->n_tris) return fail(ctx, MRT_ERR_INVALID, "refit: the triangle count differs from the scene's");
+	const mrt_tri64 *d_tris = tris;
+	if (!(flags & MRT_BUILD_TRIS_ON_DEVICE)) {
+		if ((rc = ensure(ctx, ctx->refit_in, (size_t)n_tris * sizeof(mrt_tri64)))) return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->refit_in.ptr, tris, (size_t)n_tris * sizeof(mrt_tri64), hipMemcpyHostToDevice, ctx->stream));
+		d_tris = (const mrt_tri64 *)ctx->refit_in.ptr;
+	}
+	return refit_flat_scene(ctx, d_tris);
+}
+
+int mrt_refit_instanced_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh_tris, const mrt_instance *instances,
+		uint32_t n_instances, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (!verts9 || !instances || n_instances == 0) return fail(ctx, MRT_ERR_INVALID, "refit: no instances");
+	int rc = refit_precheck(ctx, flags);
+	if (rc) return rc;
+	uint64_t total = 0;
+	for (uint32_t i = 0; i < n_instances; i++) total += instances[i].n_tris;
+	if (total != ctx->n_tris) return fail(ctx, MRT_ERR_INVALID, "refit: the instances' triangle count differs from the scene's");
+	if ((rc = ensure(ctx, ctx->refit_in, (size_t)total * sizeof(mrt_tri64)))) return rc;
+	if ((rc = mrt_flatten_instances(ctx, verts9, n_mesh_tris, instances, n_instances, flags, (mrt_tri64 *)ctx->refit_in.ptr))) return rc;
+	return refit_flat_scene(ctx, (const mrt_tri64 *)ctx->refit_in.ptr);
+}
+
+} // extern "C"

@@ -281,6 +281,23 @@ def room(subdiv: int = 29, size: float = 10.0, height: float = 6.0):
         inst[i]["origin"] = np.asarray(origin, f)
     return local, inst
 
+def deform(verts: np.ndarray, amplitude: float, phase: float, seed: int = 0) -> np.ndarray:
+    """A frame of a smooth, seeded animation of a mesh: every vertex moves by a displacement field of three sine waves
+    (direction, wave vector and offset drawn from the seed), scaled by `amplitude`, travelling with `phase`.  Vertices a
+    triangle shares move alike, so a closed mesh stays closed.  Evaluated in float64 and rounded once to float32: the same
+    frame for the same arguments (tests and tools/bench_refit.py share the frames).  amplitude 0 returns a copy."""
+    v = np.asarray(verts, dtype=np.float32)
+    p = v.reshape(-1, 3).astype(np.float64)
+    u = uniform01(seed ^ 0xDEF0, 0, 27).reshape(3, 9).astype(np.float64)
+    d = np.zeros_like(p)
+    for k in range(3):
+        direction = u[k, 0:3] - 0.5
+        direction /= np.linalg.norm(direction) + 1e-12
+        wave = (u[k, 3:6] - 0.5) * 2.0 * np.pi * (0.5 + u[k, 6])
+        d += np.sin(p @ wave + phase * (1.0 + u[k, 7]) + 2.0 * np.pi * u[k, 8])[:, None] * direction[None, :]
+    return (p + (amplitude / 3.0) * d).astype(np.float32).reshape(v.shape)
+
+
 # Named workloads of BASELINE.json `configs`.
 CONFIGS = {
     "C1": dict(scene="cube", grid=(16, 12), origin=(0.0, 0.0, 3.0), forward=(0.0, 0.0, -1.0), fov=60.0),
