@@ -153,7 +153,7 @@ typedef struct mrt_stats {
 	uint32_t detected_grid_w;    /* count_visits: row width found for the last coherent mrt_cast (0 = none) */
 	uint32_t reserved;           /* 1 if the last batch declared coherent went to the one-lane-per-ray kernel by the device's verdict:
 	                                judged incoherent, or fewer than 2^15 rays in which no row width was found */
-	float last_build_ms;         /* device time of the last mrt_build_scene_device (or mrt_refit_scene / mrt_refit_instanced_scene) */
+	float last_build_ms;         /* device time of the last mrt_build_scene_device (or mrt_refit_scene / mrt_refit_instanced_scene / mrt_refit_two_level_scene) */
 	uint32_t last_kernel;        /* MRT_KERNEL_* that did the work of the last blocking cast (a batch declared coherent is
 	                                checked on the device: this is the kernel the device chose); 0 after an ASYNC cast */
 	/* count_visits, memory-side view of the walk (what the roofline of bench.py prices): */
@@ -401,6 +401,19 @@ int mrt_upload_two_level_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mes
  * instances (same meshes, same order) with new transforms / masks.  Only the top level is rebuilt
  * and re-uploaded (n_instances rows + fewer than 2 n_instances nodes). */
 int mrt_update_instances(mrt_ctx *ctx, const mrt_instance *instances, uint32_t n_instances);
+
+/* New vertices for the resident two-level scene's meshes: the arguments of mrt_upload_two_level_scene, every
+ * instance naming the mesh it named at upload (same first_tri, n_tris; same count).  Every BLAS keeps its shape and gets new boxes
+ * and triangle rows from verts9 -- the rows an upload of the same vertices writes -- and the TLAS is rebuilt from the instances as
+ * given: transforms and layers may change in the same call, so one call a frame covers deformation and motion.  flags: 0, or
+ * MRT_BUILD_TRIS_ON_DEVICE (verts9 is a device pointer).  Blocks until done; ordered on the context's stream (a cast queued before
+ * with MRT_FLAG_ASYNC sees the old meshes).  The grid tuner, tile schedules and detected widths are kept; mrt_stats.last_build_ms =
+ * device time of the refit.  Returns MRT_ERR_INVALID (null or empty argument, unknown flag, another instance count or mesh range,
+ * a range outside n_mesh_tris, a singular transform, a non-finite coordinate), MRT_ERR_NO_SCENE, MRT_ERR_UNSUPPORTED (a flat
+ * scene: mrt_refit_scene), MRT_ERR_PENDING (collect first): the scene is then unchanged.  MRT_ERR_HIP if a tree fails its check
+ * pass: the scene is then released. */
+int mrt_refit_two_level_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh_tris,
+		const mrt_instance *instances, uint32_t n_instances, uint32_t flags);
 
 /* The prepared two-level scene ON THE HOST: exactly the arrays mrt_upload_two_level_scene uploads, for a host whose
  * router also has a CPU backend (RayDispatcher::_cpu_cast_rays routes to the TLAS when there is one,

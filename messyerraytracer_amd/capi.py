@@ -28,7 +28,7 @@ KERNEL_TWO_LEVEL, KERNEL_TWO_LEVEL_PACKET, KERNEL_TWO_LEVEL_PERSISTENT, KERNEL_T
 SYMBOLS = [
     "mrt_create", "mrt_destroy", "mrt_last_error", "mrt_status_string", "mrt_version", "mrt_set_stream",
     "mrt_synchronize", "mrt_make_triangles", "mrt_pack_host_triangles", "mrt_bvh2_build", "mrt_bvh2_save", "mrt_bvh2_load", "mrt_upload_scene",
-    "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_update_instances", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
+    "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
     "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
@@ -109,6 +109,7 @@ def load():
     L.mrt_build_instanced_scene_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_refit_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_refit_instanced_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.mrt_refit_two_level_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_upload_two_level_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_update_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.mrt_is_available.argtypes = [C.c_void_p]
@@ -355,6 +356,17 @@ class Context:
         assert instances.dtype == T.INSTANCE
         self._chk(self.L.mrt_upload_two_level_scene(self.h, _np(verts9), verts9.size // 9, _np(instances), instances.shape[0],
                                                     (BUILD_BLAS_ON_DEVICE if blas_on_device else 0) | (BUILD_SAH if sah else 0)))
+
+    def refit_two_level_scene(self, verts9, instances, n_mesh_tris=None, on_device=False):
+        """The two-level scene of upload_two_level_scene with new mesh vertices (numpy array, or a device pointer with on_device)
+        and the instances as given (same meshes and count; transforms and layers may change): every BLAS is refit, the TLAS rebuilt."""
+        if isinstance(verts9, np.ndarray):
+            verts9 = np.ascontiguousarray(verts9, dtype=np.float32)
+            n_mesh_tris = verts9.size // 9
+        instances = np.ascontiguousarray(instances)
+        assert instances.dtype == T.INSTANCE
+        self._chk(self.L.mrt_refit_two_level_scene(self.h, _ptr(verts9), n_mesh_tris, _np(instances), instances.shape[0],
+                                                   BUILD_TRIS_ON_DEVICE if on_device else 0))
 
     def update_instances(self, instances):
         """SceneTLAS::refit_tlas: the same instances with new transforms."""

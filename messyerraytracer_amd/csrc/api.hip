@@ -507,7 +507,7 @@ static int build_blases_on_device(mrt_ctx *ctx, mrt::TwoLevelHost *h, const floa
 		if (e != hipSuccess) { rc = fail(ctx, MRT_ERR_HIP, hipGetErrorString(e)); break; }
 		// (the scene's node array holds n_tris - 1 rows per mesh: what the radix tree fills; the SAH form, with leaves of several triangles, fewer)
 		if (b.n_nodes == 0u || b.n_nodes > bl.n_tris - 1u) { rc = fail(ctx, MRT_ERR_BAD_BVH, "two-level scene: unexpected BLAS size"); break; }
-		bl.depth = b.depth;
+		bl.depth = b.depth; bl.n_nodes = b.n_nodes;
 		for (int c = 0; c < 3; c++) { bl.lo[c] = b.bounds_lo[c]; bl.hi[c] = b.bounds_hi[c]; }
 		tri_base += bl.n_tris;
 	}

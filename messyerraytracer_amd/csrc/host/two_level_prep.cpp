@@ -147,6 +147,22 @@ int refit_two_level(TwoLevelHost *h, const mrt_instance *instances, uint32_t n, 
 	return MRT_OK;
 }
 
+int check_two_level_refit(const TwoLevelHost *h, const mrt_instance *instances, uint32_t n, uint32_t n_mesh_tris, char *err, size_t err_len)
+{
+	if (!h || !instances || n != h->n_inst) return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: the instance count of a refit must match the upload");
+	for (uint32_t i = 0; i < n; i++) {
+		const TwoLevelBlas &b = h->blas[h->inst_blas[i]];
+		if (instances[i].first_tri != b.first_tri || instances[i].n_tris != b.n_tris) return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: a refit may move instances, not change their meshes");
+	}
+	for (uint32_t k = 0; k < h->n_blas; k++)
+		if (h->blas[k].first_tri >= n_mesh_tris || h->blas[k].n_tris > n_mesh_tris - h->blas[k].first_tri)
+			return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: a mesh's triangle range lies outside the mesh array");
+	float inv[12];
+	for (uint32_t i = 0; i < n; i++)
+		if (!invert_affine(instances[i].basis, instances[i].origin, inv)) return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: singular instance transform");
+	return MRT_OK;
+}
+
 int prepare_two_level(const float *verts9, uint32_t n_mesh_tris, const mrt_instance *instances, uint32_t n,
 		uint32_t n_threads, bool build_blas, TwoLevelHost *out, char *err, size_t err_len)
 {
@@ -261,7 +277,7 @@ int prepare_two_level(const float *verts9, uint32_t n_mesh_tris, const mrt_insta
 			blas[k].root8 = base8; blas[k].stack8 = s.stack8;
 			base8 += s.n_nodes8;
 		}
-		blas[k].root = node_base;
+		blas[k].root = node_base; blas[k].n_nodes = s.n_nodes;
 		node_base += s.n_nodes; tri_base += s.n_tris;
 	}
 	cleanup();

@@ -234,7 +234,8 @@ struct alignas(16) DevInstance {
 };
 static_assert(sizeof(DevInstance) == 128, "DevInstance must be 128 bytes");
 
-struct TwoLevelBlas { uint32_t first_tri, n_tris, root, depth; float lo[3], hi[3]; uint32_t root8, stack8; };
+// n_nodes: the rows the BLAS fills from root (a device SAH tree leaves the rest of its n_tris - 1 rows unused)
+struct TwoLevelBlas { uint32_t first_tri, n_tris, root, depth; float lo[3], hi[3]; uint32_t root8, stack8, n_nodes; };
 struct TwoLevelHost {
 	DevNode *nodes = nullptr; uint32_t n_nodes = 0, tlas_cap = 0, n_tlas_nodes = 0;
 	TriHot *hot = nullptr; TriCold *cold = nullptr; uint32_t n_tris = 0;   // all BLAS triangles, mesh-space
@@ -256,5 +257,9 @@ int prepare_two_level(const float *verts9, uint32_t n_mesh_tris, const mrt_insta
 
 // New transforms for the same instances: inverse, world box, TLAS rebuilt into nodes[0, tlas_cap) and inst[].
 int refit_two_level(TwoLevelHost *h, const mrt_instance *instances, uint32_t n_instances, char *err, size_t err_len);
+// What refit_two_level would refuse (instance count, mesh ranges, singular transforms) and a mesh range outside n_mesh_tris,
+// checked without touching h: mrt_refit_two_level_scene refuses before any device write.
+int check_two_level_refit(const TwoLevelHost *h, const mrt_instance *instances, uint32_t n_instances, uint32_t n_mesh_tris,
+		char *err, size_t err_len);
 
 } // namespace mrt

@@ -1,4 +1,5 @@
-// refit.hip — new triangles for the resident tree of a flat scene (mrt_refit_scene, mrt_refit_instanced_scene).
+// refit.hip — new triangles for the resident tree of a flat scene (mrt_refit_scene, mrt_refit_instanced_scene) and for the
+// BLASes of a two-level scene (mrt_refit_two_level_scene).
 //
 // A refit keeps the tree's topology -- every node's refs and counts, every leaf's slot range -- and recomputes the boxes
 // from the new triangles.  Casts return what they return against a fresh build of the new triangles, because results do
@@ -11,10 +12,13 @@
 //   4. the boxes bottom-up                                                              (refit_climb_kernel)
 //   5. a check that every box a node holds is its child's own union                     (refit_verify_kernel)
 //   6. the 4- and 8-wide layouts and the row arrays, as a build derives them            (device_build.hip, kernels.hip)
-// DESIGN.md 4.8 has the measurements.
+// DESIGN.md 4.8 has the measurements.  A two-level scene (mrt_refit_two_level_scene) runs the same passes over
+// its BLAS rows, with kernels of its own where a pass needs the BLAS table or global refs (refit2_*), then rebuilds its TLAS.
 #include <cfloat>
 #include <cstdio>
+#include <cmath>
 #include <cstring>
+#include <vector>
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
 
@@ -213,6 +217,115 @@ __global__ __launch_bounds__(REFIT_WG) void refit_verify_kernel(const DevNode *n
 	if (!ok) atomicAdd(bad, 1u);
 }
 
+// ---- two-level scenes (mrt_refit_two_level_scene).  The node array holds the TLAS in [0, tlas_cap) and every BLAS behind it,
+// with global refs: inner refs are node indices, leaf refs slots of d_hot / d_cold, whose ids are mesh-local.  The passes above run
+// over the BLAS rows [lo, hi) = [tlas_cap, n_nodes) only (TLAS leaves hold instance slots, not triangles); the TLAS is rebuilt on
+// the host from the new mesh boxes, as mrt_update_instances rebuilds it.
+
+// One row per BLAS, in blas[] order: its node rows [root, root + n_nodes), its slots [slot_base, slot_base + n_tris), its triangles
+// [first_tri, first_tri + n_tris) of the mesh array.  Roots and slot bases grow with the index.
+struct RefitBlas { uint32_t root, n_nodes, slot_base, n_tris, first_tri; };
+
+// the last BLAS whose first node (by_node) or first slot starts at or before key
+__device__ __forceinline__ RefitBlas blas_of(const RefitBlas *blas, uint32_t n_blas, uint32_t key, bool by_node)
+{
+	uint32_t lo = 0u, hi = n_blas;
+	while (hi - lo > 1u) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if ((by_node ? blas[mid].root : blas[mid].slot_base) <= key) lo = mid; else hi = mid;
+	}
+	return blas[lo];
+}
+
+// 0. the triangles of every BLAS as mrt_make_triangles (scene_prep.cpp) makes them for an upload -- v0, edges, cross product,
+//    normalised; mesh-local id, all layers -- BLAS after BLAS: row slot_base + j is triangle first_tri + j of the mesh array.
+//    The same fp32 operations in the same order (nothing is contracted: -ffp-contract=off), so the rows are the upload's bit for bit.
+__global__ __launch_bounds__(REFIT_WG) void refit2_tris_kernel(const float *verts9, const RefitBlas *blas, uint32_t n_blas, uint32_t n, mrt_tri64 *out)
+{
+	const uint32_t s = blockIdx.x * REFIT_WG + threadIdx.x;
+	if (s >= n) return;
+	const RefitBlas bl = blas_of(blas, n_blas, s, false);
+	const uint32_t j = s - bl.slot_base;
+	const float *a = verts9 + 9u * (size_t)(bl.first_tri + j), *b = a + 3, *c = a + 6;
+	float e1[3], e2[3], nn[3];
+	for (int k = 0; k < 3; k++) { e1[k] = b[k] - a[k]; e2[k] = c[k] - a[k]; }
+	nn[0] = e1[1] * e2[2] - e1[2] * e2[1];
+	nn[1] = e1[2] * e2[0] - e1[0] * e2[2];
+	nn[2] = e1[0] * e2[1] - e1[1] * e2[0];
+	const float l2 = nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2];
+	if (l2 == 0.0f) { nn[0] = nn[1] = nn[2] = 0.0f; }
+	else { const float l = __builtin_sqrtf(l2); nn[0] /= l; nn[1] /= l; nn[2] /= l; }
+	float4 *dst = reinterpret_cast<float4 *>(out + s);
+	dst[0] = make_float4(a[0], a[1], a[2], __uint_as_float(j));
+	dst[1] = make_float4(e1[0], e1[1], e1[2], __uint_as_float(0xFFFFFFFFu));
+	dst[2] = make_float4(e2[0], e2[1], e2[2], 0.0f);
+	dst[3] = make_float4(nn[0], nn[1], nn[2], 0.0f);
+}
+
+// the slot map, once per scene: slot k holds triangle hot[k].id of its BLAS, staged at slot_base + id.  (An id beyond its mesh
+// cannot come from a builder of this library; it is held inside the BLAS's rows.)
+__global__ __launch_bounds__(REFIT_WG) void refit2_slots_kernel(const TriHot *hot, const RefitBlas *blas, uint32_t n_blas, uint32_t n, uint32_t *slot_src)
+{
+	const uint32_t k = blockIdx.x * REFIT_WG + threadIdx.x;
+	if (k >= n) return;
+	const RefitBlas bl = blas_of(blas, n_blas, k, false);
+	const uint32_t id = hot[k].id;
+	slot_src[k] = bl.slot_base + (id < bl.n_tris ? id : 0u);
+}
+
+// 3. parents, once per scene, numbered from lo as refit_climb_kernel sees the BLAS rows (it runs on nodes + lo): parent[c - lo] =
+//    b - lo for the left child c of node b, | 1 << 31 for the right one.  Every BLAS root keeps the 0xFFFFFFFF of the memset before,
+//    so each climb ends at its mesh's root.  The rows a BLAS leaves unused (a device SAH tree fills fewer than n_tris - 1) are
+//    zeroed: without leaf refs, the climb starts nothing there and the check pass skips them.
+__global__ __launch_bounds__(REFIT_WG) void refit2_parents_kernel(DevNode *nodes, uint32_t lo, uint32_t hi, const RefitBlas *blas, uint32_t n_blas,
+		uint32_t *parent)
+{
+	const uint32_t b = lo + blockIdx.x * REFIT_WG + threadIdx.x;
+	if (b >= hi) return;
+	const RefitBlas bl = blas_of(blas, n_blas, b, true);
+	const uint32_t end = bl.root + bl.n_nodes;
+	if (b >= end) { DevNode z; memset(&z, 0, sizeof(z)); nodes[b] = z; return; }
+	const uint32_t l = nodes[b].left_ref, r = nodes[b].right_ref;
+	if (l > bl.root && l < end) parent[l - lo] = b - lo;
+	if (r > bl.root && r < end) parent[r - lo] = (b - lo) | 0x80000000u;
+}
+
+// 5. the check pass of refit_verify_kernel over the BLAS rows, with global refs: inner refs must lie in [lo, hi).  A zeroed, unused
+//    row has nothing to check.  (A kernel of its own: the flat check keeps its code as it is.)
+__global__ __launch_bounds__(REFIT_WG) void refit2_verify_kernel(const DevNode *nodes, uint32_t lo, uint32_t hi, const Box *boxes, uint32_t n_tris, uint32_t *bad)
+{
+	const uint32_t b = lo + blockIdx.x * REFIT_WG + threadIdx.x;
+	if (b >= hi) return;
+	const DevNode g = nodes[b];
+	if (g.left_ref == 0u && g.right_ref == 0u) return;
+	bool ok = true;
+	for (int side = 0; side < 2; side++) {
+		const uint32_t ref = side ? g.right_ref : g.left_ref;
+		Box want;
+		if (ref & kLeafBit) {
+			const uint32_t first = ref & 0x7FFFFFFFu, cnt = side ? g.right_count : g.left_count;
+			if (cnt == 0u || first >= n_tris || cnt > n_tris - first) { ok = false; continue; }
+			want = leaf_union(boxes, first, cnt);
+		} else {
+			if (ref < lo || ref >= hi) { ok = false; continue; }
+			want = unite(get_side(nodes + ref, 0), get_side(nodes + ref, 1));
+		}
+		const Box have = get_side(&g, side);
+		for (int k = 0; k < 3; k++)
+			ok = ok && __float_as_uint(have.mn[k]) == __float_as_uint(want.mn[k]) && __float_as_uint(have.mx[k]) == __float_as_uint(want.mx[k]);
+	}
+	if (!ok) atomicAdd(bad, 1u);
+}
+
+// 6. every mesh's new box: the union of its root's two sides (what the TLAS rebuild and later mrt_update_instances calls box)
+__global__ __launch_bounds__(REFIT_WG) void refit2_roots_kernel(const DevNode *nodes, const RefitBlas *blas, uint32_t n_blas, Box *out)
+{
+	const uint32_t k = blockIdx.x * REFIT_WG + threadIdx.x;
+	if (k >= n_blas) return;
+	const DevNode *g = nodes + blas[k].root;
+	out[k] = unite(get_side(g, 0), get_side(g, 1));
+}
+
 } // namespace
 
 } // namespace mrt
@@ -340,6 +453,156 @@ int refit_flat_scene(mrt_ctx *ctx, const mrt_tri64 *d_tris)
 	return MRT_OK;
 }
 
+// The refit of the resident two-level scene from the mesh array d_verts9 (on the device), for instances checked by
+// check_two_level_refit.  Blocks until it is done.  Everything that can fail before the scene is written (allocation, a non-finite
+// coordinate) fails with the scene as it was; a failure after that releases the scene.
+int refit_two_level_scene(mrt_ctx *ctx, const float *d_verts9, const mrt_instance *instances, uint32_t n_instances)
+{
+	using namespace mrt;
+	TwoLevelHost *tl = ctx->two_level;
+	const uint32_t n = ctx->n_tris, lo = tl->tlas_cap, hi = ctx->n_nodes, nb = hi - lo, n_blas = tl->n_blas;
+	std::vector<RefitBlas> table(n_blas);
+	uint32_t slot_base = 0, max_nodes = 0;
+	bool binary8 = ctx->n_nodes8 == nb; // the 8-wide layout sits at binary-node indices (device-built BLASes, or refit before)
+	for (uint32_t k = 0; k < n_blas; k++) {
+		const TwoLevelBlas &b = tl->blas[k];
+		table[k] = RefitBlas{ b.root, b.n_nodes, slot_base, b.n_tris, b.first_tri };
+		slot_base += b.n_tris;
+		if (b.n_nodes > max_nodes) max_nodes = b.n_nodes;
+		binary8 = binary8 && b.root8 == b.root - lo;
+	}
+	const bool wide8 = tl->wide8 && ctx->d_nodes8 && ctx->d_leaf_box;
+	auto al = [](size_t bytes) { return (bytes + 255u) & ~(size_t)255u; };
+	const size_t box_bytes = al((size_t)n * sizeof(Box)), arr_bytes = al((size_t)nb * 4u), tab_bytes = al((size_t)n_blas * sizeof(RefitBlas)),
+			root_bytes = al((size_t)n_blas * sizeof(Box)), scr_bytes = wide8 ? al((size_t)max_nodes * sizeof(DevNode)) : 0u,
+			scr8_bytes = wide8 ? al((size_t)max_nodes * sizeof(Dev8Node)) : 0u;
+	const size_t need = box_bytes + arr_bytes + 256u + tab_bytes + root_bytes + scr_bytes + scr8_bytes;
+	if (ctx->build_arena.cap < need) {
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		if (ctx->build_arena.ptr) (void)hipFree(ctx->build_arena.ptr);
+		ctx->build_arena.ptr = nullptr; ctx->build_arena.cap = 0;
+		if (hipMalloc(&ctx->build_arena.ptr, need) != hipSuccess) { ctx->build_arena.ptr = nullptr; return fail(ctx, MRT_ERR_OOM, "refit: out of device memory"); }
+		ctx->build_arena.cap = need;
+	}
+	char *A = (char *)ctx->build_arena.ptr;
+	Box *boxes = (Box *)A; A += box_bytes;
+	uint32_t *arrivals = (uint32_t *)A; A += arr_bytes;
+	uint32_t *scal = (uint32_t *)A; A += 256u; // [0, 6) unused bounds of the mesh-space boxes, non-finite, verification failures, collapse8 "bad"
+	RefitBlas *d_table = (RefitBlas *)A; A += tab_bytes;
+	Box *d_roots = (Box *)A; A += root_bytes;
+	DevNode *scr = (DevNode *)A; A += scr_bytes;
+	Dev8Node *scr8 = (Dev8Node *)A;
+	mrt_tri64 *staged = (mrt_tri64 *)ctx->refit_in.ptr; // (sized by the caller)
+	// what the first refit of a scene allocates: the slot map and the parents (kept); a host-built scene's 8-wide layout at
+	// binary-node indices (its compact host collapse has no map from binary nodes to 8-wide nodes)
+	uint32_t *slot_src = ctx->d_slot_src, *parent = ctx->d_parent;
+	Dev8Node *nodes8 = ctx->d_nodes8;
+	auto drop_new = [&] {
+		if (slot_src != ctx->d_slot_src) (void)hipFree(slot_src);
+		if (parent != ctx->d_parent) (void)hipFree(parent);
+		if (nodes8 != ctx->d_nodes8) (void)hipFree(nodes8);
+	};
+	auto alloc = [](auto **p, size_t bytes) { if (hipMalloc((void **)p, bytes) == hipSuccess) return true; *p = nullptr; return false; };
+	bool ok = true;
+	if (!slot_src) ok = alloc(&slot_src, (size_t)n * 4u);
+	if (ok && !parent) ok = alloc(&parent, (size_t)nb * 4u);
+	if (ok && wide8 && !binary8) ok = alloc(&nodes8, (size_t)nb * sizeof(Dev8Node));
+	if (!ok) { drop_new(); return fail(ctx, MRT_ERR_OOM, "refit: out of device memory"); }
+	auto bail = [&](hipError_t e, const char *what, bool written) {
+		drop_new();
+		if (written) free_scene(ctx); // part of the scene may be new, part old: released rather than kept wrong
+		std::snprintf(ctx->err, sizeof(ctx->err), "refit: %s failed: %s%s", what, hipGetErrorString(e), written ? "; the scene was released" : "");
+		return MRT_ERR_HIP;
+	};
+
+	// 0-1. the new triangle rows staged, the slot map (first refit), boxes and the non-finite flag; read back before anything of the
+	//      scene is written
+	hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1], e2 = ctx->ev[2], e3 = ctx->ev[3];
+	const uint32_t blocks = (n + REFIT_WG - 1u) / REFIT_WG, node_blocks = (nb + REFIT_WG - 1u) / REFIT_WG, blas_blocks = (n_blas + REFIT_WG - 1u) / REFIT_WG;
+	const uint32_t init[10] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+	uint32_t h[10];
+	hipError_t e = hipEventRecord(e0, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(scal, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_table, table.data(), (size_t)n_blas * sizeof(RefitBlas), hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess) { hipLaunchKernelGGL(refit2_tris_kernel, dim3(blocks), dim3(REFIT_WG), 0, ctx->stream, d_verts9, d_table, n_blas, n, staged); e = hipGetLastError(); }
+	if (e == hipSuccess && slot_src != ctx->d_slot_src) { hipLaunchKernelGGL(refit2_slots_kernel, dim3(blocks), dim3(REFIT_WG), 0, ctx->stream, ctx->d_hot, d_table, n_blas, n, slot_src); e = hipGetLastError(); }
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(refit_boxes_kernel, dim3(blocks < REFIT_BOXES_BLOCKS ? blocks : REFIT_BOXES_BLOCKS), dim3(REFIT_WG), 0, ctx->stream, staged, slot_src, n, boxes, scal);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e != hipSuccess) return bail(e, "the box pass", false);
+	if (h[6] != 0u) { drop_new(); return fail(ctx, MRT_ERR_INVALID, "refit: a mesh triangle has a non-finite coordinate (the scene is unchanged)"); }
+
+	// 2-6. rows, parents (first refit), the climb over the BLAS rows, check, mesh boxes, 8-wide layout per BLAS
+	std::vector<Box> roots(n_blas);
+	e = hipEventRecord(e2, ctx->stream);
+	if (e == hipSuccess) { hipLaunchKernelGGL(refit_rows_kernel, dim3(blocks), dim3(REFIT_WG), 0, ctx->stream, staged, slot_src, n, ctx->d_hot, ctx->d_cold); e = hipGetLastError(); }
+	if (e == hipSuccess && parent != ctx->d_parent) {
+		e = hipMemsetAsync(parent, 0xFF, (size_t)nb * 4u, ctx->stream);
+		if (e == hipSuccess) { hipLaunchKernelGGL(refit2_parents_kernel, dim3(node_blocks), dim3(REFIT_WG), 0, ctx->stream, ctx->d_nodes, lo, hi, d_table, n_blas, parent); e = hipGetLastError(); }
+	}
+	if (e == hipSuccess) e = hipMemsetAsync(arrivals, 0, (size_t)nb * 4u, ctx->stream);
+	if (e == hipSuccess) { hipLaunchKernelGGL(refit_climb_kernel, dim3(node_blocks), dim3(REFIT_WG), 0, ctx->stream, ctx->d_nodes + lo, nb, boxes, n, parent, arrivals); e = hipGetLastError(); }
+	if (e == hipSuccess) { hipLaunchKernelGGL(refit2_verify_kernel, dim3(node_blocks), dim3(REFIT_WG), 0, ctx->stream, ctx->d_nodes, lo, hi, boxes, n, scal + 7); e = hipGetLastError(); }
+	if (e == hipSuccess) { hipLaunchKernelGGL(refit2_roots_kernel, dim3(blas_blocks), dim3(REFIT_WG), 0, ctx->stream, ctx->d_nodes, d_table, n_blas, d_roots); e = hipGetLastError(); }
+	// the builder's collapse wants a tree from node 0 with local refs: each BLAS is localised into scratch (offset_refs adds modulo
+	// 2^32), collapsed with its exact leaf boxes, and put back at root - tlas_cap with global refs, as build_blases_on_device places it
+	for (uint32_t k = 0; wide8 && k < n_blas && e == hipSuccess; k++) {
+		const RefitBlas &b = table[k];
+		const uint32_t root8 = b.root - lo;
+		e = launch_offset_refs(scr, ctx->d_nodes + b.root, b.n_nodes, 0u - b.root, 0u - b.slot_base, (void *)ctx->stream);
+		if (e == hipSuccess) e = launch_collapse8(scr, b.n_nodes, scr8, ctx->d_leaf_box + (size_t)b.slot_base * 8u, scal + 8, ctx->stream);
+		if (e == hipSuccess) e = launch_offset_refs8(nodes8 + root8, scr8, b.n_nodes, root8, b.slot_base, (void *)ctx->stream);
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(roots.data(), d_roots, (size_t)n_blas * sizeof(Box), hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipEventRecord(e3, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e != hipSuccess) return bail(e, "the refit", true);
+
+	// the new arrays are the scene's now
+	ctx->d_slot_src = slot_src; ctx->d_parent = parent;
+	if (nodes8 != ctx->d_nodes8) { (void)hipFree(ctx->d_nodes8); ctx->d_nodes8 = nodes8; ctx->n_nodes8 = tl->n_nodes8 = nb; }
+	if (h[7] != 0u) {
+		free_scene(ctx);
+		std::snprintf(ctx->err, sizeof(ctx->err), "refit: the tree failed its verification pass (%u nodes); the scene was released", h[7]);
+		return MRT_ERR_HIP;
+	}
+	// the mesh boxes every TLAS build (here and in later mrt_update_instances calls) boxes the instances by; the 8-wide roots and
+	// stack bounds by the builder's rule (device_build.hip: 7 entries per binary level) where the layout moved to binary indices
+	for (uint32_t k = 0; k < n_blas; k++) {
+		TwoLevelBlas &b = tl->blas[k];
+		for (int c = 0; c < 3; c++) { b.lo[c] = roots[k].mn[c]; b.hi[c] = roots[k].mx[c]; }
+		if (wide8 && !binary8) { b.root8 = b.root - lo; b.stack8 = 7u * (b.depth - 1u) + 1u; }
+	}
+	if (wide8 && h[8] != 0u) { // a box that fits no grid: the scene goes without the 8-wide layout, as upload and build do
+		(void)hipFree(ctx->d_nodes8); (void)hipFree(ctx->d_leaf_box);
+		ctx->d_nodes8 = nullptr; ctx->d_leaf_box = nullptr; ctx->n_nodes8 = ctx->stack8 = 0;
+		tl->wide8 = false; tl->n_nodes8 = 0;
+	}
+	// the TLAS over the new world boxes, uploaded as mrt_update_instances does.  (The host's copy of the BLAS rows, tl->nodes beyond
+	// the TLAS range of a host-built scene, is stale from here on: nothing reads it after the upload.)
+	int rc = refit_two_level(tl, instances, n_instances, ctx->err, sizeof(ctx->err));
+	if (!rc && tl->depth > 64u) rc = fail(ctx, MRT_ERR_UNSUPPORTED, "refit: the new top level is too deep for the per-lane stack");
+	if (rc) { free_scene(ctx); return rc; } // (checked before; a new TLAS that cannot be used leaves new meshes behind an old one)
+	e = hipMemcpy(ctx->d_nodes, tl->nodes, (size_t)tl->n_tlas_nodes * sizeof(DevNode), hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = hipMemcpy(ctx->d_instances, tl->inst, (size_t)tl->n_inst * sizeof(DevInstance), hipMemcpyHostToDevice);
+	if (e != hipSuccess) return bail(e, "the top-level upload", true);
+	ctx->depth = tl->depth; ctx->stack8 = tl->wide8 ? tl->depth8 : 0;
+	ctx->stack_depth = ((tl->depth + 7u) / 8u) * 8u;
+	if (ctx->stack_depth < 8) ctx->stack_depth = 8;
+	for (int c = 0; c < 3; c++) {
+		ctx->bounds_lo[c] = std::fmin(tl->nodes[0].lmin[c], tl->nodes[0].rmin[c]);
+		ctx->bounds_hi[c] = std::fmax(tl->nodes[0].lmax[c], tl->nodes[0].rmax[c]);
+	}
+	float ms0 = 0.0f, ms1 = 0.0f;
+	if (hipEventElapsedTime(&ms0, e0, e1) == hipSuccess && hipEventElapsedTime(&ms1, e2, e3) == hipSuccess) ctx->stats.last_build_ms = ms0 + ms1;
+	return MRT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -385,6 +648,31 @@ int mrt_refit_instanced_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh
 	if ((rc = ensure(ctx, ctx->refit_in, (size_t)total * sizeof(mrt_tri64)))) return rc;
 	if ((rc = mrt_flatten_instances(ctx, verts9, n_mesh_tris, instances, n_instances, flags, (mrt_tri64 *)ctx->refit_in.ptr))) return rc;
 	return refit_flat_scene(ctx, (const mrt_tri64 *)ctx->refit_in.ptr);
+}
+
+int mrt_refit_two_level_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh_tris, const mrt_instance *instances,
+		uint32_t n_instances, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (!verts9 || !instances || n_instances == 0 || n_mesh_tris == 0) return fail(ctx, MRT_ERR_INVALID, "refit: null or empty argument");
+	if (flags & ~(uint32_t)MRT_BUILD_TRIS_ON_DEVICE) return fail(ctx, MRT_ERR_INVALID, "refit: unknown flag");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "refit: collect the pending dispatch first");
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "refit: no scene uploaded");
+	if (!ctx->two_level) return fail(ctx, MRT_ERR_UNSUPPORTED, "refit: a flat scene (mrt_refit_scene / mrt_refit_instanced_scene refit it)");
+	int rc = mrt::check_two_level_refit(ctx->two_level, instances, n_instances, n_mesh_tris, ctx->err, sizeof(ctx->err));
+	if (rc) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// the staged triangle rows, then (host vertices) a copy of the mesh array behind them
+	const size_t tri_bytes = (size_t)ctx->n_tris * sizeof(mrt_tri64), vert_bytes = (size_t)n_mesh_tris * 9u * sizeof(float);
+	const bool on_device = (flags & MRT_BUILD_TRIS_ON_DEVICE) != 0;
+	if ((rc = ensure(ctx, ctx->refit_in, tri_bytes + (on_device ? 0u : vert_bytes)))) return rc;
+	const float *d_verts9 = verts9;
+	if (!on_device) {
+		float *dst = (float *)((char *)ctx->refit_in.ptr + tri_bytes);
+		HIP_TRY(ctx, hipMemcpyAsync(dst, verts9, vert_bytes, hipMemcpyHostToDevice, ctx->stream));
+		d_verts9 = dst;
+	}
+	return refit_two_level_scene(ctx, d_verts9, instances, n_instances);
 }
 
 } // extern "C"
