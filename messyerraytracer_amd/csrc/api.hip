@@ -223,6 +223,7 @@ int mrt_create(int device_ordinal, const mrt_options *opts, mrt_ctx **out)
 	}
 	if (const char *e = std::getenv("MRT_SCHED_SPLIT_PCT")) { const int v = std::atoi(e); if (v >= 0 && v <= 50) ctx->knobs.split_pct = (uint32_t)v; }
 	ctx->knobs.dump = std::getenv("MRT_SCHED_DUMP") != nullptr;
+	ctx->knobs.poison = std::getenv("MRT_POISON_OUTPUT") != nullptr;
 	auto bail = [&](int code) { mrt_destroy(ctx); return code; };
 	if (hipSetDevice(device_ordinal) != hipSuccess) return bail(MRT_ERR_NO_DEVICE);
 	if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(MRT_ERR_HIP);
@@ -283,6 +284,7 @@ int mrt_synchronize(mrt_ctx *ctx)
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->detect.waited(ctx->h_auto);
 	return MRT_OK;
 }
 

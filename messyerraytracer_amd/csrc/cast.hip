@@ -33,6 +33,18 @@ int device_sort(mrt_ctx *ctx, const void *d_rays, uint32_t in_fmt, uint64_t coun
 	return MRT_OK;
 }
 
+// bytes of one output record (mrt::OutFmt)
+size_t out_bytes(uint32_t out_fmt)
+{
+	switch (out_fmt) {
+		case mrt::OUT_HOST44: return sizeof(mrt_host_hit44);
+		case mrt::OUT_BOOL8: return 1;
+		case mrt::OUT_TOKEN4: return 4;
+		case mrt::OUT_TOKEN8: return 8;
+		default: return sizeof(mrt_hit32);
+	}
+}
+
 mrt::SceneFacts scene_facts(const mrt_ctx *ctx)
 {
 	mrt::SceneFacts s;
@@ -45,8 +57,8 @@ mrt::SceneFacts scene_facts(const mrt_ctx *ctx)
 
 mrt::CastPlan plan(mrt_ctx *ctx, const mrt::CastRequest &r)
 {
-	const mrt::PrevDetect prev{ctx->pending, ctx->last_detect_count, {ctx->h_auto[0], ctx->h_auto[1], ctx->h_auto[2], ctx->h_auto[3]}};
-	return mrt::plan_cast(ctx->opts, scene_facts(ctx), r, prev, ctx->knobs, ctx->grids);
+	// (never h_auto itself: a detect queued before this cast may not have run yet; the memo's pair is the one of the last wait)
+	return mrt::plan_cast(ctx->opts, scene_facts(ctx), r, ctx->detect.prev(), ctx->knobs, ctx->grids);
 }
 
 void note_queued(mrt_ctx *ctx, uint32_t kernel)
@@ -92,6 +104,9 @@ int launch_planned(mrt_ctx *ctx, const mrt::CastPlan &c, const mrt::CastRequest 
 	const bool rays = mrt::ray_entry(r.entry), any = r.mode == MRT_MODE_ANY_HIT;
 	const auto zero_counters = [&] { return hipMemsetAsync(ctx->d_counters, 0, mrt::kNumCounters * sizeof(unsigned long long), ctx->stream); };
 	p.kernel = c.kernel; p.lane_map = c.lane_map; p.quarter_all = c.quarter_all;
+	// (tests: a record no launch writes keeps the pattern; the mapped small-cast buffer is filled on the host, mrt_cast)
+	if (ctx->knobs.poison && p.hits != ctx->d_small_out)
+		HIP_TRY(ctx, hipMemsetAsync(p.hits, mrt::kPoisonByte, p.count * out_bytes(p.out_fmt), ctx->stream));
 	if (rays) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
 	if (c.sort) {
 		const uint32_t *perm = nullptr;
@@ -103,9 +118,9 @@ int launch_planned(mrt_ctx *ctx, const mrt::CastPlan &c, const mrt::CastRequest 
 		HIP_TRY(ctx, mrt::launch_detect_grid(p.rays, p.in_fmt, r.count, p.tile_w_log2, ctx->d_counters + mrt::kDetectScratchOff, d_auto, ctx->d_auto_host, ctx->stream));
 		p.auto_grid = d_auto;
 	}
+	if (rays) ctx->detect.queued(c.detect, r.count);
 	if (rays && ctx->opts.count_visits) HIP_TRY(ctx, zero_counters());
 	if (c.scheduled && (rc = schedule_grid(ctx, c, p))) return rc;
-	if (rays) ctx->last_detect_count = c.detect ? r.count : 0;
 	HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
 	if (!rays && ctx->opts.count_visits) HIP_TRY(ctx, zero_counters());
 	ctx->queued_detect = c.detect; ctx->queued_alt_kernel = 0;
@@ -176,6 +191,7 @@ int finish_timing(mrt_ctx *ctx, bool h2d, bool sorted, bool d2h)
 	HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4])); ctx->stats.last_trace_ms = ms;
 	if (d2h) { HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5])); ctx->stats.last_d2h_ms = ms; }
 	// which kernel did the work: the stream has been waited for, so detect_grid_kernel's words are in h_auto
+	ctx->detect.waited(ctx->h_auto);
 	ctx->stats.detected_grid_w = ctx->queued_detect ? ctx->h_auto[0] : 0u;
 	ctx->stats.reserved = ctx->queued_detect ? ctx->h_auto[3] : 0u; // 1: the "coherent" batch was judged incoherent
 	const bool alt_ran = ctx->queued_detect && ctx->queued_alt_kernel && ctx->h_auto[3];
@@ -333,6 +349,7 @@ int mrt_cast(mrt_ctx *ctx, const void *rays, void *hits, uint64_t count, uint32_
 		}
 		if (ctx->h_small_in) {
 			std::memcpy(ctx->h_small_in, rays, count * rs_);
+			if (ctx->knobs.poison) std::memset(ctx->h_small_out, mrt::kPoisonByte, count * hs_); // (no cast is in flight: mrt_cast waits for each)
 			int rc2 = enqueue_cast(ctx, mrt::ENTRY_CAST, ctx->d_small_in, ctx->d_small_out, count, query_mask, mode, flags | MRT_FLAG_RAYS_ON_DEVICE, &d_hits);
 			if (rc2) return rc2;
 			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

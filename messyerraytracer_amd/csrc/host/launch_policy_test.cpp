@@ -1,9 +1,12 @@
 // launch_policy_test.cpp — pins the cast launch policy (launch_policy.cpp) without a device: a table of casts and the plan
-// each one must get, then the grid kernel tuner over fifteen frames with fake timings and the per-grid state LRU.
+// each one must get, then the grid kernel tuner over fifteen frames with fake timings, the per-grid state LRU and the detected
+// width across sequences of blocking, ASYNC, pipelined and submitted casts (DetectMemo).
 // Exit status 0 iff every check holds; one line per failure.
+#include <array>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 #include "../launch_policy.h"
 
 using namespace mrt;
@@ -248,12 +251,26 @@ CastPlan plan(const Case &t, GridStates &gs, const Knobs &k = Knobs())
 	return plan_cast(options(t.opt), scene(t.scene), r, prev, k, gs);
 }
 
+// A batch whose width is found on the device and scheduled from a consistent pair (the width of a cast of as many rays) gets a
+// launch of at least a lane per ray (launch_trace), and the prefetch rule counts at least a wave per 64 rays
+void covers(const Case &t, const CastPlan &c)
+{
+	if (!c.scheduled || c.lane_map != MAP_AUTO) return;
+	const uint32_t tw = tile_w_log2(options(t.opt)), th = 64u >> tw, unit = c.kernel == MRT_KERNEL_PACKET_DUAL ? 2u : 1u;
+	const uint32_t n_units = (uint32_t)(((uint64_t)c.tiles_x * ((c.rows + th - 1u) / th) + unit - 1u) / unit);
+	const uint32_t slots = schedule_slots(n_units, c.pieces);
+	const uint64_t waves = n_units > kWaveSlots ? n_units : (slots < kWaveSlots ? slots : kWaveSlots);
+	expect((uint64_t)slots * unit * 64u >= t.count && (unit != 1u || waves * 64u >= t.count), std::string(t.name) + ": the schedule's launch covers the batch");
+}
+
 void table()
 {
 	for (const Case &t : kCases) {
 		GridStates gs;
-		const std::string got = describe(plan(t, gs));
+		const CastPlan c = plan(t, gs);
+		const std::string got = describe(c);
 		expect(got == t.want, std::string(t.name) + ": got \"" + got + "\", want \"" + t.want + "\"");
+		covers(t, c);
 	}
 	// the schedule's bound from the environment (MRT_SCHEDULE_MIN_LOG2 = 15) moves the tuner's with it
 	Knobs k; k.schedule_min_rays = k.tune_min_rays = 1ull << 15;
@@ -315,6 +332,121 @@ void lru()
 	expect(at == 1 && g2.e[0].key.w == 100, "lru: select_grid_state evicts the least recently used");
 }
 
+// Sequences of casts against a fake stream: a queued detect writes its words only when the host waits (the worst case for the
+// planner: ASYNC casts, pipeline chunks and submits queued behind a long cast).  Rays are w x h grids (COHERENT), or not a grid.
+struct Seq {
+	GridStates gs;
+	DetectMemo memo;
+	Knobs k;
+	uint32_t h_auto[4] = {0, 0, 0, 0};               // what the device has written so far
+	std::vector<std::array<uint32_t, 4>> in_flight;  // detects queued, not run
+	CastRequest req(Entry e, uint64_t n, uint32_t flags) const
+	{
+		CastRequest r; r.entry = e; r.count = n; r.flags = flags; r.mode = MRT_MODE_NEAREST;
+		return r;
+	}
+	// the plan the rule before DetectMemo made: the count of the last cast queued, the words as they are now
+	PrevDetect racy() const
+	{
+		PrevDetect p; p.count = memo.queued_count;
+		for (int i = 0; i < 4; i++) p.word[i] = h_auto[i];
+		return p;
+	}
+	CastPlan cast(Entry e, uint32_t w, uint32_t h, uint32_t flags = COH, bool grid = true)
+	{
+		const CastRequest r = req(e, (uint64_t)w * h, flags);
+		const CastPlan c = plan_cast(options(AUTO), scene(FLAT), r, memo.prev(), k, gs);
+		memo.queued(c.detect, r.count);
+		if (c.detect) in_flight.push_back(grid ? std::array<uint32_t, 4>{w, h, w / 8u, 0u} : std::array<uint32_t, 4>{0u, 0u, 0u, 1u});
+		return c;
+	}
+	void wait()
+	{
+		for (const auto &q : in_flight) std::memcpy(h_auto, q.data(), sizeof(h_auto));
+		in_flight.clear();
+		memo.waited(h_auto);
+	}
+	CastPlan blocking(uint32_t w, uint32_t h) { const CastPlan c = cast(ENTRY_CAST, w, h); wait(); return c; }
+};
+
+std::string sched(const CastPlan &c)
+{
+	if (!c.scheduled) return "-";
+	return std::to_string(c.grid_w) + "x" + std::to_string(c.rows) + "/" + std::to_string(c.tiles_x);
+}
+
+void memo()
+{
+	constexpr uint32_t DEV = MRT_FLAG_RAYS_ON_DEVICE | MRT_FLAG_HITS_ON_DEVICE;
+	{   // blocking A until scheduled, then two ASYNC casts B1, B2 of another grid and as many rays as each other
+		Seq s;
+		expect(sched(s.blocking(640, 360)) == "-", "memo: the first cast of A has no width to go by");
+		const CastPlan a = s.blocking(640, 360);
+		expect(sched(a) == "640x360/80", "memo: A from A's width: " + sched(a));
+		expect(sched(s.cast(ENTRY_CAST, 1280, 960, COH | ASYNC)) == "-", "memo: ASYNC B1");
+		// B1's detect has not run: the count is B's, the words are still A's
+		expect(s.racy().count == 1228800u && s.racy().word[0] == 640u, "memo: the race is set up");
+		GridStates g2 = s.gs;
+		const CastPlan old = plan_cast(options(AUTO), scene(FLAT), s.req(ENTRY_CAST, 1228800, COH | ASYNC), s.racy(), s.k, g2);
+		expect(sched(old) == "640x360/80", "memo: the rule it replaces scheduled B2 from A's width: " + sched(old));
+		const CastPlan b2 = s.cast(ENTRY_CAST, 1280, 960, COH | ASYNC);
+		expect(sched(b2) == "-", "memo: ASYNC B2 is not scheduled from A: " + sched(b2));
+		s.wait(); // mrt_synchronize
+		expect(s.memo.prev().count == 1228800u && s.memo.prev().word[0] == 1280u && s.memo.prev().word[1] == 960u, "memo: after the wait, B's pair");
+		expect(sched(s.cast(ENTRY_CAST, 1280, 960, COH | ASYNC)) == "1280x960/160", "memo: ASYNC B3 from B's own width");
+		expect(sched(s.cast(ENTRY_CAST, 1280, 960, COH | ASYNC)) == "1280x960/160", "memo: ASYNC B4 from the same pair");
+		s.wait();
+		expect(sched(s.blocking(640, 360)) == "-", "memo: A after B: B's count");
+		expect(sched(s.blocking(640, 360)) == "640x360/80", "memo: A again");
+	}
+	{   // blocking 1024x576 casts, then a host cast of 2048x1152 in 2^20-ray chunks (2048 x 512, 2048 x 512, 2048 x 128)
+		Seq s;
+		for (int f = 0; f < 3; f++) s.blocking(1024, 576);
+		const uint32_t rows[3] = {512, 512, 128};
+		for (int k = 0; k < 3; k++) {
+			GridStates g2 = s.gs;
+			const CastPlan old = plan_cast(options(AUTO), scene(FLAT), s.req(ENTRY_CHUNK, 2048ull * rows[k], COH | DEV), s.racy(), s.k, g2);
+			if (k == 1) expect(sched(old) == "1024x576/128", "memo: the rule it replaces scheduled chunk 1 from 1024x576: " + sched(old));
+			const CastPlan c = s.cast(ENTRY_CHUNK, 2048, rows[k], COH | DEV);
+			expect(c.detect && sched(c) == "-", "memo: chunk " + std::to_string(k) + " not scheduled from a width of the queue: " + sched(c));
+		}
+		s.wait(); // the end of the pipelined cast
+		expect(s.memo.prev().count == 262144u && s.memo.prev().word[0] == 2048u && s.memo.prev().word[1] == 128u, "memo: after the pipeline, the tail chunk's pair");
+		expect(sched(s.cast(ENTRY_CHUNK, 2048, 128, COH | DEV)) == "2048x128/256", "memo: a chunk of the tail's size from the tail's width");
+		s.wait();
+	}
+	{   // submit and collect between blocking casts of other sizes
+		Seq s;
+		s.blocking(1280, 960);
+		const CastPlan sub = s.cast(ENTRY_SUBMIT, 640, 360);
+		expect(sched(sub) == "-", "memo: a submit of A after B");
+		expect(s.memo.prev().word[0] == 1280u, "memo: a submit in flight leaves the pair of the last wait");
+		s.wait(); // mrt_collect
+		expect(sched(s.cast(ENTRY_SUBMIT, 640, 360)) == "640x360/80", "memo: the next submit from the collected one's width");
+		s.wait();
+		expect(sched(s.blocking(640, 360)) == "640x360/80", "memo: a blocking cast after a collect");
+	}
+	{   // casts without a detect between: an incoherent batch queued last leaves no width; grid casts and shadow casts queue none
+		Seq s;
+		s.blocking(640, 360); s.blocking(640, 360);
+		const CastPlan inc = s.cast(ENTRY_CAST, 640, 360, 0u);
+		expect(!inc.detect && inc.sort, "memo: an incoherent batch runs no detect");
+		s.wait();
+		expect(s.memo.prev().count == 0u, "memo: the last cast queued had no detect: no width");
+		expect(sched(s.blocking(640, 360)) == "-", "memo: A after the incoherent batch");
+		expect(sched(s.blocking(640, 360)) == "640x360/80", "memo: A after A");
+		s.cast(ENTRY_CAST, 640, 360, ASYNC);                        // queued without a detect, no wait: the pair stays A's
+		expect(sched(s.cast(ENTRY_CAST, 640, 360, COH | ASYNC)) == "640x360/80", "memo: ASYNC A behind a cast without detect");
+		s.wait();
+		s.memo.waited(s.h_auto);                                     // a grid cast (no detect queued) waits: nothing changes
+		expect(s.memo.prev().count == 230400u && s.memo.prev().word[0] == 640u, "memo: a wait with nothing queued changes nothing");
+		s.cast(ENTRY_CAST, 640, 360, COH | ASYNC, false);             // not a grid after all
+		s.wait();
+		expect(s.memo.prev().count == 230400u && s.memo.prev().word[0] == 0u && s.memo.prev().word[3] == 1u, "memo: no width found");
+		expect(sched(s.blocking(640, 360)) == "-", "memo: no schedule from a batch in which no width was found");
+	}
+}
+
 } // namespace
 
 int main()
@@ -327,6 +459,7 @@ int main()
 	tuner("tuner, whole wins", whole_wins, "dual");
 	tuner("tuner, 64-ray kernel wins", asm_wins, "asm+pieces");
 	lru();
+	memo();
 	std::printf("%d of %d checks hold (%zu table cases)\n", checks - failures, checks, sizeof(kCases) / sizeof(kCases[0]));
 	return failures ? 1 : 0;
 }

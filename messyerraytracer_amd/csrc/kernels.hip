@@ -751,8 +751,12 @@ hipError_t launch_trace(const TraceParams &p_in, bool any_hit, bool count, hipSt
 	// (MRT_KERNEL_PACKET_DUAL) or 4 waves of one; every other kernel 4 waves of one tile
 	p.tile_group = (p.kernel == MRT_KERNEL_PACKET_DUAL && p.row_array != nullptr) ? 2u * ((p.rows_wg == 64u ? 64u : (uint32_t)MRT_ROWS_WG_LARGE) / MRT_WAVE) : MRT_WG / MRT_WAVE;
 	uint64_t threads;
-	if (p.tile_sched != nullptr && p.sched_hdr != nullptr && p.n_slots_max != 0u) threads = (uint64_t)p.n_slots_max * p.tile_unit * 64u; // (slots past sched_hdr[2] have nothing to do)
-	else if (p.lane_map == MAP_TILE8X8) {
+	if (p.tile_sched != nullptr && p.sched_hdr != nullptr && p.n_slots_max != 0u) {
+		threads = (uint64_t)p.n_slots_max * p.tile_unit * 64u; // (slots past sched_hdr[2] have nothing to do)
+		// a width found on the device was scheduled from an earlier cast's: should this batch's grid differ, the kernel ignores the
+		// schedule and maps tiles in plain order, a lane per ray (a schedule of the batch's own grid covers that already)
+		if (p.lane_map == MAP_AUTO && threads < p.count) threads = p.count;
+	} else if (p.lane_map == MAP_TILE8X8) {
 		const uint32_t th = 64u >> p.tile_w_log2;
 		threads = (uint64_t)p.tiles_x * ((p.rows + th - 1u) / th) * 64u * (p.quarter_all == 2u ? 16u : (p.quarter_all ? 4u : 1u));
 	} else if (p.lane_map == MAP_LINEAR && p.sparse_lanes) threads = (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u;
@@ -817,7 +821,8 @@ hipError_t launch_trace(const TraceParams &p_in, bool any_hit, bool count, hipSt
 		} else {
 			// the scalar-cache prefetch of both children: where the launch is about one round of waves (packet_asm_kernel.h)
 			// (a scheduled launch covers the slots the list MAY use: what counts is the units, or the one round the fill rule makes of fewer)
-			const uint64_t waves = p.tile_sched != nullptr && p.n_slots_max != 0u ? (p.n_units > kWaveSlots ? p.n_units : (p.n_slots_max < kWaveSlots ? p.n_slots_max : kWaveSlots)) : threads / MRT_WAVE;
+			uint64_t waves = p.tile_sched != nullptr && p.n_slots_max != 0u ? (p.n_units > kWaveSlots ? p.n_units : (p.n_slots_max < kWaveSlots ? p.n_slots_max : kWaveSlots)) : threads / MRT_WAVE;
+			if (p.lane_map == MAP_AUTO && waves < (p.count + MRT_WAVE - 1u) / MRT_WAVE) waves = (p.count + MRT_WAVE - 1u) / MRT_WAVE; // (as above)
 			const bool kpf = waves <= kPrefetchMaxWaves;
 			if (kpf) { if (any_hit) hipLaunchKernelGGL((trace_packet_asm_kernel<true, false, true>), grid, wg, p.extra_lds, stream, p);
 				else hipLaunchKernelGGL((trace_packet_asm_kernel<false, false, true>), grid, wg, p.extra_lds, stream, p); }

@@ -155,6 +155,15 @@ int select_grid_state(GridStates &g, const GridKey &k)
 	return g.cur = pick;
 }
 
+void DetectMemo::waited(const volatile uint32_t *words)
+{
+	if (!queued_since_wait) return; // nothing queued since the last wait: the words have not changed
+	seen.pending = false;
+	seen.count = queued_count;
+	for (int i = 0; i < 4; i++) seen.word[i] = queued_count ? words[i] : 0u;
+	queued_since_wait = false;
+}
+
 void tune_record(GridTune &t, float trace_ms)
 {
 	if (!t.armed) return;

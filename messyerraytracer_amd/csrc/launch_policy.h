@@ -27,7 +27,11 @@ struct Knobs {
 	uint64_t tune_min_rays = 1ull << 19;
 	uint32_t split_pct = 1;  // MRT_SCHED_SPLIT_PCT: the rank, in percent, above which a unit goes in pieces (schedule_plan_kernel)
 	bool dump = false;       // MRT_SCHED_DUMP: print what every schedule was made of (tools/bench_resolutions.py)
+	// MRT_POISON_OUTPUT (tests): every cast first fills its output range with kPoisonByte on the context's stream, so that a record
+	// no launch wrote shows up as one (0xA5: t < 0, prim_id and token out of range, a bool neither 0 nor 1); off, nothing is queued
+	bool poison = false;
 };
+constexpr uint8_t kPoisonByte = 0xA5;
 
 // What the cast path needs to know about the scene (and the device).
 struct SceneFacts {
@@ -52,9 +56,25 @@ struct CastRequest {
 
 // What detect_grid_kernel found for the previous cast ({row width, rows, tiles_x, verdict}), and for how many rays.
 struct PrevDetect {
-	bool pending = false;  // an ASYNC / submitted cast may not have written the words yet
+	bool pending = false;  // the words may still be written (a planner that cannot tell: no schedule)
 	uint64_t count = 0;    // rays of the last cast that ran detect_grid_kernel (0: none)
 	uint32_t word[4] = {0, 0, 0, 0};
+};
+
+// The PrevDetect a cast is planned from, as a consistent pair.  detect_grid_kernel writes its words to host-mapped memory when it
+// RUNS, but a cast is planned when it is QUEUED: ASYNC casts, pipeline chunks and a submit queue behind others, and a count noted at
+// queue time next to words read at plan time may belong to two different casts (the count of the cast just queued, the width of
+// one before it: a schedule of the wrong grid, whose launch covers too few rays).  So every cast from an array notes, as it is
+// queued, whether it runs a detect and for how many rays (queued), and only after the host has waited for the stream -- when the
+// words are those of the last detect queued -- are count and words taken together (waited).  Casts queued since then are planned
+// from the pair of the last wait (prev).  Plain host code: cast.hip calls it, launch_policy_test.cpp runs it through sequences.
+struct DetectMemo {
+	uint64_t queued_count = 0;   // rays of the last cast queued from an array if it ran detect_grid_kernel (0: it did not)
+	bool queued_since_wait = false;
+	PrevDetect seen;             // taken at the last wait after a queued cast
+	void queued(bool detect, uint64_t count) { queued_count = detect ? count : 0u; queued_since_wait = true; }
+	void waited(const volatile uint32_t *words); // the host has waited for the stream: words = what the last queued detect wrote
+	const PrevDetect &prev() const { return seen; }
 };
 
 // How a mid-size grid is cast is MEASURED per grid (tune_grid_kernel): four frames with the 64-ray kernel, four with the 128-ray
@@ -103,6 +123,13 @@ struct CastPlan {
 	bool arms_tuner = false;                // the cast's timing goes to tune_record
 	uint32_t launches = 0;                  // mrt_stats.last_kernel_launches (0: left as it is)
 };
+
+// Launch slots of a tile schedule of n_units units (schedule_grid): with pieces, room for half as many again or for what fills one
+// round of waves (schedule_plan_kernel).  A launch from the schedule covers slots * unit * 64 lanes: at least the batch's rays.
+inline uint32_t schedule_slots(uint32_t n_units, bool pieces)
+{
+	return pieces ? (n_units + n_units / 2u > kWaveSlots ? n_units + n_units / 2u : kWaveSlots) : n_units;
+}
 
 uint32_t tile_w_log2(const mrt_options &o);
 // Plans a cast.  May select (and reset) the grid state of the cast in `gs` (never for a shadow entry: those read neither `prev` nor `gs`).

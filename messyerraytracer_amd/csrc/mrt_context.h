@@ -92,7 +92,7 @@ struct mrt_ctx {
 		hipEvent_t traced = nullptr, ready[2] = {nullptr, nullptr};
 		void forget() { have_order[0] = have_order[1] = false; }
 	};
-	uint64_t last_detect_count = 0;   // rays of the last cast whose row width was looked for on the device (h_auto holds what it found)
+	mrt::DetectMemo detect;           // what the last detect found, for how many rays, as of the last wait (launch_policy.h)
 	// per grid and cast mode, for the last few of them (mrt::GridStates): how it is cast, and its tile schedule in sched[same index]
 	mrt::GridStates grids;
 	TileSchedule sched[mrt::GridStates::kCount];

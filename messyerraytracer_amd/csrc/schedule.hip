@@ -95,7 +95,7 @@ int schedule_grid(mrt_ctx *ctx, const mrt::CastPlan &c, mrt::TraceParams &p)
 	if (!same) {
 		HIP_TRY(ctx, hipStreamSynchronize(s.side)); // no sort of the old grid may still use the arrays
 		// room for pieces: half as many extra slots as there are units, or what fills one round of waves (schedule_plan_kernel)
-		s.n_slots_max = pieces ? (n_units + n_units / 2u > mrt::kWaveSlots ? n_units + n_units / 2u : mrt::kWaveSlots) : n_units;
+		s.n_slots_max = mrt::schedule_slots(n_units, pieces);
 		for (int k = 0; k < 2; k++)
 			if ((rc = ensure(ctx, s.cost[k], ((size_t)n_units + s.n_slots_max) * 4)) || (rc = ensure(ctx, s.order[k], (size_t)n_units * 4)) ||
 					(rc = ensure(ctx, s.slots[k], (size_t)s.n_slots_max * 4)) || (rc = ensure(ctx, s.hdr[k], 16))) return rc;

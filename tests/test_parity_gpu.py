@@ -228,6 +228,7 @@ def test_frame_coherent_tile_schedule_changes_no_record(built, kernel, monkeypat
     test_renderer_resolutions_on_the_c3_scene runs the tuner on grids of its own size.)"""
     monkeypatch.setenv("MRT_SCHEDULE_MIN_LOG2", "15")
     monkeypatch.setenv("MRT_SCHED_SPLIT_PCT", "5")
+    monkeypatch.setenv("MRT_POISON_OUTPUT", "1")   # every output starts as a pattern no kernel writes: a skipped tile shows
     v = synth.soup(20000, 0.25, 33)
     scene, osc = capi.Scene(v), po.OracleScene(v)
     for sched in (0, 2, 1):
@@ -259,6 +260,7 @@ def test_interleaved_views_keep_their_schedules(built, monkeypatch):
     cast against the oracle, whatever state each cast found."""
     monkeypatch.setenv("MRT_SCHEDULE_MIN_LOG2", "15")
     monkeypatch.setenv("MRT_SCHED_SPLIT_PCT", "5")
+    monkeypatch.setenv("MRT_POISON_OUTPUT", "1")
     v = synth.soup(20000, 0.25, 37)
     scene, osc = capi.Scene(v), po.OracleScene(v)
     views = []
@@ -319,7 +321,7 @@ def test_small_grids_in_quarter_tiles(built):
 
 
 @pytest.mark.parametrize("wh", [(1280, 960), (1920, 1080)])
-def test_renderer_resolutions_on_the_c3_scene(built, wh):
+def test_renderer_resolutions_on_the_c3_scene(built, wh, monkeypatch):
     """The reference's own workload size (1280x960: ROADMAP.md:175-181) and 1080p on the 1 M-triangle C3 scene: fifteen frames of
     the same grid -- the twelve measuring frames of the kernel tuner (the 64-ray kernel, the 128-ray walk with its most expensive
     units in pieces, the 128-ray walk whole), the frames launched in a measured tile order, what the library settles on -- every
@@ -327,6 +329,7 @@ def test_renderer_resolutions_on_the_c3_scene(built, wh):
     w, h = wh
     cfg = synth.CONFIGS["C3"]
     verts = synth.scene_vertices(cfg)
+    monkeypatch.setenv("MRT_POISON_OUTPUT", "1")   # every frame's records start as a pattern no kernel writes
     c = capi.Context(0)
     capi.Scene(verts).upload(c)
     cam = capi.camera_look(cfg["origin"], cfg["forward"], w, h, cfg["fov"])
