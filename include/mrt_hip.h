@@ -330,10 +330,12 @@ enum {
 	                                       of the union, Meister and Bittner 2018) instead of the default radix tree over
 	                                       the key bits: 2.9 against 1.2 ms per million triangles; on the soup scenes of
 	                                       BASELINE.md the two trees trace alike (1.05 / 1.07 x the host SAH tree) */
-	MRT_BUILD_SAH            = 1u << 4  /* the binned-SAH tree of tinybvh::BVH::Build (tiny_bvh.h:2332-2466; mrt_bvh2_build on
+	MRT_BUILD_SAH            = 1u << 4, /* the binned-SAH tree of tinybvh::BVH::Build (tiny_bvh.h:2332-2466; mrt_bvh2_build on
 	                                       the host) built level by level on the device: the host builder's decisions on the
 	                                       same boxes, leaves of several triangles, rows in its depth-first order -- the tree
 	                                       RayScene::build would upload, without the host build */
+	MRT_BUILD_INSTANCES_ON_DEVICE = 1u << 5 /* mrt_update_instances_device, mrt_refit_two_level_scene: `instances` is a device
+	                                       array (the top level is then built on the device) */
 };
 int mrt_build_scene_device(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris, uint32_t flags);
 
@@ -401,12 +403,24 @@ int mrt_upload_two_level_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mes
  * instances (same meshes, same order) with new transforms / masks.  Only the top level is rebuilt
  * and re-uploaded (n_instances rows + fewer than 2 n_instances nodes). */
 int mrt_update_instances(mrt_ctx *ctx, const mrt_instance *instances, uint32_t n_instances);
+/* mrt_update_instances with the top level built on the device: the same instances, meshes and order, with new
+ * transforms and masks; the casts after it return what they return after mrt_update_instances with the same instances.  One thread
+ * per instance checks it, inverts its transform and boxes it with the host path's arithmetic; the tree over the world boxes is built by
+ * the device builder of mrt_build_scene_device in the form flags choose: none the radix tree, MRT_BUILD_PLOC, or MRT_BUILD_SAH (the
+ * host builder's decisions).  instances: host array (staged with one copy), or device array with MRT_BUILD_INSTANCES_ON_DEVICE.
+ * Blocks until done; ordered on the context's stream (a cast queued before with MRT_FLAG_ASYNC sees the old instances); a pending
+ * mrt_submit is drained.  mrt_stats.last_build_ms = device time of the update.  Returns MRT_ERR_NO_SCENE (no two-level scene),
+ * MRT_ERR_INVALID (null instances, an unknown flag, two form bits, another count, a changed mesh range, a singular transform, a
+ * non-finite value), MRT_ERR_UNSUPPORTED (a top level too deep for the per-lane stack): the scene is then unchanged. */
+int mrt_update_instances_device(mrt_ctx *ctx, const mrt_instance *instances, uint32_t n_instances, uint32_t flags);
 
 /* New vertices for the resident two-level scene's meshes: the arguments of mrt_upload_two_level_scene, every
  * instance naming the mesh it named at upload (same first_tri, n_tris; same count).  Every BLAS keeps its shape and gets new boxes
  * and triangle rows from verts9 -- the rows an upload of the same vertices writes -- and the TLAS is rebuilt from the instances as
  * given: transforms and layers may change in the same call, so one call a frame covers deformation and motion.  flags: 0, or
- * MRT_BUILD_TRIS_ON_DEVICE (verts9 is a device pointer).  Blocks until done; ordered on the context's stream (a cast queued before
+ * MRT_BUILD_TRIS_ON_DEVICE (verts9 is a device pointer), and MRT_BUILD_INSTANCES_ON_DEVICE (instances is a device array: they are
+ * checked on the device before any row is written, and the top level is built on the device, in the radix form, from the mesh boxes
+ * the refit leaves there; with both flags nothing of the geometry goes through the host).  Blocks until done; ordered on the context's stream (a cast queued before
  * with MRT_FLAG_ASYNC sees the old meshes).  The grid tuner, tile schedules and detected widths are kept; mrt_stats.last_build_ms =
  * device time of the refit.  Returns MRT_ERR_INVALID (null or empty argument, unknown flag, another instance count or mesh range,
  * a range outside n_mesh_tris, a singular transform, a non-finite coordinate), MRT_ERR_NO_SCENE, MRT_ERR_UNSUPPORTED (a flat

@@ -19,7 +19,8 @@ ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_NO_SCENE, ERR_PENDING, ERR_NOT_PENDING,
 MODE_NEAREST, MODE_ANY_HIT = 0, 1
 FLAG_COHERENT, FLAG_RAYS_ON_DEVICE, FLAG_HITS_ON_DEVICE, FLAG_HOST_LAYOUT, FLAG_BOOL_OUT, FLAG_FORCE_SORT, FLAG_TOKEN_OUT, FLAG_ASYNC = (1 << i for i in range(8))
 TOKEN_MISS = 0xFFFFFFFF
-BUILD_TRIS_ON_DEVICE, BUILD_SAFE_HANDOFF, BUILD_BLAS_ON_DEVICE, BUILD_PLOC, BUILD_SAH = 1, 2, 4, 8, 16
+BUILD_TRIS_ON_DEVICE, BUILD_SAFE_HANDOFF, BUILD_BLAS_ON_DEVICE, BUILD_PLOC, BUILD_SAH, BUILD_INSTANCES_ON_DEVICE = 1, 2, 4, 8, 16, 32
+TLAS_FORMS = {"radix": 0, "ploc": BUILD_PLOC, "sah": BUILD_SAH}  # update_instances_device(form=...)
 KERNEL_AUTO, KERNEL_LANE, KERNEL_PACKET = 0, 1, 2   # (3 and 4: retired experiments, ids not reused)
 KERNEL_PACKET_ASM, KERNEL_LANE_PERSISTENT, KERNEL_LANE4_PERSISTENT, KERNEL_LANE8_PERSISTENT, KERNEL_PACKET_DUAL, KERNEL_PACKET_ROWS, KERNEL_PACKET_QUAD = 5, 6, 7, 8, 9, 10, 11
 KERNEL_TWO_LEVEL, KERNEL_TWO_LEVEL_PACKET, KERNEL_TWO_LEVEL_PERSISTENT, KERNEL_TWO_LEVEL_PERSISTENT8 = 100, 101, 102, 103  # reported only
@@ -28,7 +29,7 @@ KERNEL_TWO_LEVEL, KERNEL_TWO_LEVEL_PACKET, KERNEL_TWO_LEVEL_PERSISTENT, KERNEL_T
 SYMBOLS = [
     "mrt_create", "mrt_destroy", "mrt_last_error", "mrt_status_string", "mrt_version", "mrt_set_stream",
     "mrt_synchronize", "mrt_make_triangles", "mrt_pack_host_triangles", "mrt_bvh2_build", "mrt_bvh2_save", "mrt_bvh2_load", "mrt_upload_scene",
-    "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
+    "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_update_instances_device", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
     "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
@@ -112,6 +113,7 @@ def load():
     L.mrt_refit_two_level_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_upload_two_level_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_update_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.mrt_update_instances_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_is_available.argtypes = [C.c_void_p]
     L.mrt_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.mrt_cast.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32]
@@ -357,22 +359,35 @@ class Context:
         self._chk(self.L.mrt_upload_two_level_scene(self.h, _np(verts9), verts9.size // 9, _np(instances), instances.shape[0],
                                                     (BUILD_BLAS_ON_DEVICE if blas_on_device else 0) | (BUILD_SAH if sah else 0)))
 
-    def refit_two_level_scene(self, verts9, instances, n_mesh_tris=None, on_device=False):
+    def refit_two_level_scene(self, verts9, instances, n_mesh_tris=None, on_device=False, instances_on_device=False, n_instances=None):
         """The two-level scene of upload_two_level_scene with new mesh vertices (numpy array, or a device pointer with on_device)
-        and the instances as given (same meshes and count; transforms and layers may change): every BLAS is refit, the TLAS rebuilt."""
+        and the instances as given (same meshes and count; transforms and layers may change): every BLAS is refit, the TLAS rebuilt.
+        instances_on_device: instances is a device pointer (an int, with n_instances) and the TLAS is built on the device."""
         if isinstance(verts9, np.ndarray):
             verts9 = np.ascontiguousarray(verts9, dtype=np.float32)
             n_mesh_tris = verts9.size // 9
-        instances = np.ascontiguousarray(instances)
-        assert instances.dtype == T.INSTANCE
-        self._chk(self.L.mrt_refit_two_level_scene(self.h, _ptr(verts9), n_mesh_tris, _np(instances), instances.shape[0],
-                                                   BUILD_TRIS_ON_DEVICE if on_device else 0))
+        if not instances_on_device:
+            instances = np.ascontiguousarray(instances)
+            assert instances.dtype == T.INSTANCE
+            n_instances = instances.shape[0]
+        flags = (BUILD_TRIS_ON_DEVICE if on_device else 0) | (BUILD_INSTANCES_ON_DEVICE if instances_on_device else 0)
+        self._chk(self.L.mrt_refit_two_level_scene(self.h, _ptr(verts9), n_mesh_tris, _ptr(instances), n_instances, flags))
 
     def update_instances(self, instances):
         """SceneTLAS::refit_tlas: the same instances with new transforms."""
         instances = np.ascontiguousarray(instances)
         assert instances.dtype == T.INSTANCE
         self._chk(self.L.mrt_update_instances(self.h, _np(instances), instances.shape[0]))
+
+    def update_instances_device(self, instances, on_device=False, form="radix", n_instances=None):
+        """update_instances with the top level built on the device, in the form "radix", "ploc" or "sah".  instances: a numpy array
+        of types.INSTANCE (staged with one copy), or with on_device a device pointer (an int, with n_instances)."""
+        if not on_device:
+            instances = np.ascontiguousarray(instances)
+            assert instances.dtype == T.INSTANCE
+            n_instances = instances.shape[0]
+        flags = TLAS_FORMS[form] | (BUILD_INSTANCES_ON_DEVICE if on_device else 0)
+        self._chk(self.L.mrt_update_instances_device(self.h, _ptr(instances), n_instances, flags))
 
     def upload_scene(self, tris, nodes, prim_idx):
         tris = np.ascontiguousarray(tris)

@@ -97,6 +97,8 @@ void free_scene(mrt_ctx *ctx)
 	if (ctx->d_slot_src) (void)hipFree(ctx->d_slot_src);
 	if (ctx->d_parent) (void)hipFree(ctx->d_parent);
 	ctx->d_slot_src = nullptr; ctx->d_parent = nullptr;
+	release(ctx->tlas_inst_tab); release(ctx->tlas_blas_tab); // the device top level's tables (tlas_device.hip) belong to the scene
+	ctx->tlas_inst_ok = ctx->tlas_blas_ok = false;
 	ctx->d_nodes = nullptr; ctx->d_hot = nullptr; ctx->d_cold = nullptr; ctx->d_nodes4 = nullptr; ctx->d_nodes8 = nullptr;
 	ctx->n_nodes8 = ctx->stack8 = 0;
 	ctx->scene = false; ctx->n_nodes = ctx->n_tris = 0;
@@ -251,6 +253,7 @@ void mrt_destroy(mrt_ctx *ctx)
 	free_scene(ctx);
 	release(ctx->rays); release(ctx->hits); release(ctx->keys_in); release(ctx->keys_out);
 	release(ctx->idx_in); release(ctx->idx_out); release(ctx->sort_tmp); release(ctx->overflow); release(ctx->refit_in);
+	release(ctx->tlas_work);
 	for (auto &sc : ctx->sched) {
 		if (sc.side) { (void)hipStreamSynchronize(sc.side); (void)hipStreamDestroy(sc.side); }
 		if (sc.traced) (void)hipEventDestroy(sc.traced);

@@ -64,21 +64,28 @@ __device__ __forceinline__ float ulp_up(float f) { return f == 0.0f ? FLT_MIN : 
 //    bounds of all boxes: bounds[0..2] = min (ordered uint), bounds[3..5] = max.
 //    Grid-stride over at most LBVH_BOUNDS_BLOCKS blocks, one atomic per block and component: atomics on
 //    one address cost ~10 ns each chip-wide (one per wave made this kernel 1 ms per million triangles).
+//    With box_in (DeviceBuildResult::boxes_in, no triangles): the given boxes themselves, as they are (a top level over instances'
+//    world boxes: a box rebuilt from v0 + e1 would round, and a TLAS box must contain the world box).
 #define LBVH_BOUNDS_BLOCKS 1024u
-__global__ __launch_bounds__(LBVH_WG) void lbvh_bounds_kernel(const mrt_tri64 *tris, uint32_t n, Box *boxes, uint32_t *bounds)
+__global__ __launch_bounds__(LBVH_WG) void lbvh_bounds_kernel(const mrt_tri64 *tris, const Box *box_in, uint32_t n, Box *boxes, uint32_t *bounds)
 {
 	__shared__ float part[LBVH_WG / 64][6];
 	float mn[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, mx[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
 	for (uint32_t i = blockIdx.x * LBVH_WG + threadIdx.x; i < n; i += gridDim.x * LBVH_WG) {
-		const float4 *t = reinterpret_cast<const float4 *>(tris + i);
-		const float4 a = t[0], b = t[1], c = t[2];
-		const float v0[3] = { a.x, a.y, a.z }, e1[3] = { b.x, b.y, b.z }, e2[3] = { c.x, c.y, c.z };
 		Box bx;
-		for (int k = 0; k < 3; k++) {
-			const float p1 = v0[k] + e1[k], p2 = v0[k] + e2[k];
-			bx.mn[k] = ulp_down(fminf(v0[k], fminf(p1, p2)));
-			bx.mx[k] = ulp_up(fmaxf(v0[k], fmaxf(p1, p2)));
-			mn[k] = fminf(mn[k], bx.mn[k]); mx[k] = fmaxf(mx[k], bx.mx[k]);
+		if (box_in) {
+			bx = box_in[i];
+			for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], bx.mn[k]); mx[k] = fmaxf(mx[k], bx.mx[k]); }
+		} else {
+			const float4 *t = reinterpret_cast<const float4 *>(tris + i);
+			const float4 a = t[0], b = t[1], c = t[2];
+			const float v0[3] = { a.x, a.y, a.z }, e1[3] = { b.x, b.y, b.z }, e2[3] = { c.x, c.y, c.z };
+			for (int k = 0; k < 3; k++) {
+				const float p1 = v0[k] + e1[k], p2 = v0[k] + e2[k];
+				bx.mn[k] = ulp_down(fminf(v0[k], fminf(p1, p2)));
+				bx.mx[k] = ulp_up(fmaxf(v0[k], fmaxf(p1, p2)));
+				mn[k] = fminf(mn[k], bx.mn[k]); mx[k] = fmaxf(mx[k], bx.mx[k]);
+			}
 		}
 		boxes[i] = bx;
 	}
@@ -761,13 +768,22 @@ __global__ __launch_bounds__(LBVH_WG) void lbvh_collapse8_kernel(const DevNode *
 }
 
 // 6. triangle rows in leaf order (sorted position = slot); every leaf holds one triangle
-//    (leaf_key == nullptr), or the slots with one key form a leaf (the binned-SAH form: key = the leaf's first slot)
+//    (leaf_key == nullptr), or the slots with one key form a leaf (the binned-SAH form: key = the leaf's first slot).
+//    A build over boxes (tris == nullptr) writes only id = the box of the slot and the leaf-end flag; the rest of the row is zero.
 __global__ __launch_bounds__(LBVH_WG) void lbvh_leaves_kernel(const mrt_tri64 *tris, uint32_t n, const uint32_t *sorted_tri, const uint32_t *leaf_key,
 		TriHot *hot, TriCold *cold)
 {
 	const uint32_t slot = blockIdx.x * LBVH_WG + threadIdx.x;
 	if (slot >= n) return;
 	const bool last = leaf_key == nullptr || slot + 1u == n || leaf_key[slot + 1u] != leaf_key[slot];
+	if (tris == nullptr) {
+		float4 *h = reinterpret_cast<float4 *>(hot + slot);
+		h[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(sorted_tri[slot]));
+		h[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		h[2] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(last ? kLastInLeaf : 0u));
+		reinterpret_cast<float4 *>(cold)[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		return;
+	}
 	const float4 *t = reinterpret_cast<const float4 *>(tris + sorted_tri[slot]);
 	const float4 a = t[0], b = t[1], c = t[2], d = t[3];
 	float4 *h = reinterpret_cast<float4 *>(hot + slot);
@@ -890,7 +906,8 @@ hipError_t launch_flatten_instances(const float *d_verts9, const mrt_instance *d
 	} while (0)
 
 // Builds nodes / hot / cold (and nodes4 / nodes8 if wanted; hipMalloc'ed, owned by the caller on success) for
-// the n >= 2 triangles at d_tris (device).  depth = stack entries a traversal can need (incl. the sentinel).
+// the n >= 2 triangles at d_tris (device), or, with d_tris == nullptr, the n boxes at out->boxes_in (hot[slot].id = the box of the slot,
+// with the leaf-end flag).  depth = stack entries a traversal can need (incl. the sentinel).
 // Temporaries are carved from *arena (grown here if it is too small; owned by the caller, kept between builds).
 int device_build_lbvh(const mrt_tri64 *d_tris, uint32_t n, bool want4, bool want8, bool safe_handoff, int form, BuildArena *arena, void *stream_,
 		DeviceBuildResult *out, char *err, size_t err_len)
@@ -954,7 +971,7 @@ int device_build_lbvh(const mrt_tri64 *d_tris, uint32_t n, bool want4, bool want
 	const uint32_t init[16] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
 	DB_TRY(hipMemcpyAsync(scal, init, sizeof(init), hipMemcpyHostToDevice, stream));
 	hipLaunchKernelGGL(lbvh_bounds_kernel, dim3(blocks < LBVH_BOUNDS_BLOCKS ? blocks : LBVH_BOUNDS_BLOCKS), dim3(LBVH_WG), 0, stream,
-			d_tris, n, boxes, scal);
+			d_tris, (const Box *)out->boxes_in, n, boxes, scal);
 	if (form != 2) {
 		hipLaunchKernelGGL(lbvh_keys_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, boxes, n, scal, keys_a, idx_a);
 		DB_TRY(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, keys_a, keys_b, idx_a, idx_b, nn, 0, 63, stream));

@@ -6,6 +6,7 @@
 // first triangle has the running triangle count of the instances registered before it (the reference's
 // own TLAS path reports mesh-local ids; the flat id is what its callers index by).
 #include "../mrt_internal.h"
+#include "../instance_math.h"
 
 #include <cmath>
 #include <cstdio>
@@ -34,46 +35,7 @@ int fail_(char *err, size_t err_len, int code, const char *msg)
 	return code;
 }
 
-// Inverse of the affine map x -> B x + o in double (cofactors), rounded once to float.
-// false if B is singular (or not finite).
-bool invert_affine(const float basis[9], const float origin[3], float inv[12])
-{
-	const double a = basis[0], b = basis[1], c = basis[2], d = basis[3], e = basis[4], f = basis[5], g = basis[6], h = basis[7], i = basis[8];
-	const double c00 = e * i - f * h, c01 = c * h - b * i, c02 = b * f - c * e;
-	const double c10 = f * g - d * i, c11 = a * i - c * g, c12 = c * d - a * f;
-	const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
-	const double det = a * c00 + b * c10 + c * c20;
-	if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
-	const double m[9] = { c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det };
-	for (int r = 0; r < 3; r++) {
-		const double t = -(m[3 * r] * (double)origin[0] + m[3 * r + 1] * (double)origin[1] + m[3 * r + 2] * (double)origin[2]);
-		inv[4 * r] = (float)m[3 * r]; inv[4 * r + 1] = (float)m[3 * r + 1]; inv[4 * r + 2] = (float)m[3 * r + 2]; inv[4 * r + 3] = (float)t;
-		if (!std::isfinite(inv[4 * r]) || !std::isfinite(inv[4 * r + 1]) || !std::isfinite(inv[4 * r + 2]) || !std::isfinite(inv[4 * r + 3])) return false;
-	}
-	return true;
-}
-
-// World box of a mesh box under x -> B x + o: the eight corners (BLASInstance::compute_world_bounds,
-// blas_instance.h:76-107), evaluated in double and rounded outwards to float so that the box still
-// contains the exact image.
-void world_box(const float lo[3], const float hi[3], const float basis[9], const float origin[3], float wlo[3], float whi[3])
-{
-	double mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-	for (int k = 0; k < 8; k++) {
-		const double x = (k & 1) ? hi[0] : lo[0], y = (k & 2) ? hi[1] : lo[1], z = (k & 4) ? hi[2] : lo[2];
-		for (int r = 0; r < 3; r++) {
-			const double w = ((double)basis[3 * r] * x + (double)basis[3 * r + 1] * y) + (double)basis[3 * r + 2] * z + (double)origin[r];
-			if (w < mn[r]) mn[r] = w;
-			if (w > mx[r]) mx[r] = w;
-		}
-	}
-	for (int r = 0; r < 3; r++) {
-		float l = (float)mn[r], u = (float)mx[r];
-		if ((double)l > mn[r]) l = std::nextafterf(l, -INFINITY);
-		if ((double)u < mx[r]) u = std::nextafterf(u, INFINITY);
-		wlo[r] = l; whi[r] = u;
-	}
-}
+// (invert_affine and world_box: instance_math.h, shared with the device top-level build)
 
 // BVH2 over n boxes with the scene builder: box k goes in as the triangle {lo, hi, centre}, whose
 // AABB is the box.  Result in the device layout via prepare_scene (ids = box index, last-in-leaf flags).
@@ -149,8 +111,8 @@ int refit_two_level(TwoLevelHost *h, const mrt_instance *instances, uint32_t n, 
 
 int check_two_level_refit(const TwoLevelHost *h, const mrt_instance *instances, uint32_t n, uint32_t n_mesh_tris, char *err, size_t err_len)
 {
-	if (!h || !instances || n != h->n_inst) return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: the instance count of a refit must match the upload");
-	for (uint32_t i = 0; i < n; i++) {
+	if (!h || n != h->n_inst) return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: the instance count of a refit must match the upload");
+	for (uint32_t i = 0; instances && i < n; i++) {
 		const TwoLevelBlas &b = h->blas[h->inst_blas[i]];
 		if (instances[i].first_tri != b.first_tri || instances[i].n_tris != b.n_tris) return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: a refit may move instances, not change their meshes");
 	}
@@ -158,7 +120,7 @@ int check_two_level_refit(const TwoLevelHost *h, const mrt_instance *instances, 
 		if (h->blas[k].first_tri >= n_mesh_tris || h->blas[k].n_tris > n_mesh_tris - h->blas[k].first_tri)
 			return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: a mesh's triangle range lies outside the mesh array");
 	float inv[12];
-	for (uint32_t i = 0; i < n; i++)
+	for (uint32_t i = 0; instances && i < n; i++)
 		if (!invert_affine(instances[i].basis, instances[i].origin, inv)) return fail_(err, err_len, MRT_ERR_INVALID, "two-level scene: singular instance transform");
 	return MRT_OK;
 }

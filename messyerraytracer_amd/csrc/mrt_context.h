@@ -68,6 +68,11 @@ struct mrt_ctx {
 	// per-dispatch buffers (grow only, x1.5: gpu_ray_caster.cpp:776-817)
 	DevBuf rays, hits, keys_in, keys_out, idx_in, idx_out, sort_tmp, overflow;
 	DevBuf refit_in;               // a refit's triangles, staged from the host or flattened from instances
+	// top levels built on the device (tlas_device.hip): the scratch of one update (staged instances, registration rows, world boxes,
+	// status block; grow only) and the scene's tables, made from two_level on first use: per instance {its mesh, flat id base}, per mesh
+	// {range, roots, box}.  The mesh table goes stale when a refit moves the meshes (tlas_blas_ok = false); free_scene drops both.
+	DevBuf tlas_work, tlas_inst_tab, tlas_blas_tab;
+	bool tlas_inst_ok = false, tlas_blas_ok = false;
 	int cu_count = 256;
 	unsigned long long *d_counters = nullptr;
 	// what detect_grid_kernel decided, also written to this host-mapped word block {row width, rows, tiles_x, verdict}
@@ -137,6 +142,14 @@ inline int ensure(mrt_ctx *ctx, DevBuf &b, size_t bytes)
 }
 
 inline void release(DevBuf &b) { if (b.ptr) (void)hipFree(b.ptr); b.ptr = nullptr; b.cap = 0; }
+
+// tlas_device.hip: the top level of the resident two-level scene built on the device from n instances (a device array, or a host array
+// staged with one copy; form: 0 radix tree, 1 PLOC, 2 binned SAH) and committed, or refused with the scene unchanged; check_only: the
+// per-instance checks alone (mesh ranges, transforms), nothing built.  On the context's stream, blocks until done; *ms = its device
+// time.  Does not drain a pending dispatch.
+namespace mrt {
+int device_update_tlas(mrt_ctx *ctx, const mrt_instance *instances, uint32_t n, bool on_device, int form, bool check_only, float *ms);
+}
 
 // api.hip
 void free_scene(mrt_ctx *ctx);

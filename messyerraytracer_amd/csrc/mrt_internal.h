@@ -193,7 +193,7 @@ struct DeviceSceneHost {
 int prepare_scene(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *nodes, uint32_t used_nodes,
 		const uint32_t *prim_idx, DeviceSceneHost *out, char *err, size_t err_len);
 
-// device-side build (device_build.hip): LBVH over n >= 2 device-resident triangles, written in the
+// device-side build (device_build.hip): LBVH over n >= 2 device-resident triangles (or boxes: boxes_in), written in the
 // layout above.  Arrays are hipMalloc'ed and belong to the caller on success.  `stream` is a hipStream_t.
 struct DeviceBuildResult {
 	DevNode *nodes = nullptr; TriHot *hot = nullptr; TriCold *cold = nullptr;
@@ -203,6 +203,7 @@ struct DeviceBuildResult {
 	uint32_t n_nodes = 0, n_tris = 0, depth = 0, stack4 = 0, stack8 = 0;
 	float bounds_lo[3] = {0, 0, 0}, bounds_hi[3] = {0, 0, 0};
 	uint32_t *slot_src = nullptr; // in, optional: n device words, filled with the input triangle of every slot (what a refit rewrites slot k from)
+	const float *boxes_in = nullptr; // in, with d_tris == nullptr: n device boxes {min xyz, max xyz} to build over (a top level over world boxes)
 };
 struct BuildArena { void *ptr = nullptr; size_t cap = 0; uint32_t *pinned = nullptr; }; // the builder's temporaries: owned by the context, grown on demand (pinned: 64 host bytes the per-level counters are read back into)
 // form: 0 the radix tree over the Morton keys (fastest build), 1 PLOC, 2 binned SAH (the host builder's tree; leaves of several triangles)
@@ -258,7 +259,8 @@ int prepare_two_level(const float *verts9, uint32_t n_mesh_tris, const mrt_insta
 // New transforms for the same instances: inverse, world box, TLAS rebuilt into nodes[0, tlas_cap) and inst[].
 int refit_two_level(TwoLevelHost *h, const mrt_instance *instances, uint32_t n_instances, char *err, size_t err_len);
 // What refit_two_level would refuse (instance count, mesh ranges, singular transforms) and a mesh range outside n_mesh_tris,
-// checked without touching h: mrt_refit_two_level_scene refuses before any device write.
+// checked without touching h: mrt_refit_two_level_scene refuses before any device write.  instances == nullptr (instances on the
+// device): the count and the meshes' ranges only; the per-instance checks run on the device (tlas_device.hip).
 int check_two_level_refit(const TwoLevelHost *h, const mrt_instance *instances, uint32_t n_instances, uint32_t n_mesh_tris,
 		char *err, size_t err_len);
 

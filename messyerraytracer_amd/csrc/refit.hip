@@ -476,7 +476,7 @@ int refit_flat_scene(mrt_ctx *ctx, const mrt_tri64 *d_tris)
 // The refit of the resident two-level scene from the mesh array d_verts9 (on the device), for instances checked by
 // check_two_level_refit: every BLAS in the node rows [tlas_cap, n_nodes), then the mesh boxes, the 8-wide layout per BLAS and the
 // TLAS.  Blocks until it is done.
-int refit_two_level_scene(mrt_ctx *ctx, const float *d_verts9, const mrt_instance *instances, uint32_t n_instances)
+int refit_two_level_scene(mrt_ctx *ctx, const float *d_verts9, const mrt_instance *instances, uint32_t n_instances, bool inst_on_device)
 {
 	TwoLevelHost *tl = ctx->two_level;
 	const uint32_t n = ctx->n_tris, lo = tl->tlas_cap, nb = ctx->n_nodes - lo, n_blas = tl->n_blas;
@@ -541,6 +541,18 @@ int refit_two_level_scene(mrt_ctx *ctx, const float *d_verts9, const mrt_instanc
 		ctx->d_nodes8 = nullptr; ctx->d_leaf_box = nullptr; ctx->n_nodes8 = ctx->stack8 = 0;
 		tl->wide8 = false; tl->n_nodes8 = 0;
 	}
+	ctx->tlas_blas_ok = false; // the mesh table of device top-level builds (tlas_device.hip) holds the old boxes and roots
+	if (inst_on_device) {
+		// the TLAS built on the device from the device instances (checked on the device before the refit) and the new mesh boxes,
+		// in the radix form; a refusal here leaves new meshes behind an old top level, so the scene is released as below
+		r.done();
+		const float refit_ms = ctx->stats.last_build_ms;
+		float tlas_ms = 0.0f;
+		rc = device_update_tlas(ctx, instances, n_instances, true, 0, false, &tlas_ms);
+		if (rc) { if (ctx->scene) free_scene(ctx); return rc; }
+		ctx->stats.last_build_ms = refit_ms + tlas_ms;
+		return MRT_OK;
+	}
 	// the TLAS over the new world boxes, uploaded as mrt_update_instances does.  (The host's copy of the BLAS rows, tl->nodes beyond
 	// the TLAS range of a host-built scene, is stale from here on: nothing reads it after the upload.)
 	rc = refit_two_level(tl, instances, n_instances, ctx->err, sizeof(ctx->err));
@@ -568,7 +580,8 @@ extern "C" {
 // refusals that leave the scene as it is, in the order the header lists them, for a refit of a two-level scene or of a flat one
 static int refit_precheck(mrt_ctx *ctx, uint32_t flags, bool two_level)
 {
-	if (flags & ~(uint32_t)MRT_BUILD_TRIS_ON_DEVICE) return fail(ctx, MRT_ERR_INVALID, "refit: unknown flag");
+	const uint32_t known = MRT_BUILD_TRIS_ON_DEVICE | (two_level ? (uint32_t)MRT_BUILD_INSTANCES_ON_DEVICE : 0u);
+	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "refit: unknown flag");
 	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "refit: collect the pending dispatch first");
 	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "refit: no scene uploaded");
 	if (two_level && !ctx->two_level) return fail(ctx, MRT_ERR_UNSUPPORTED, "refit: a flat scene (mrt_refit_scene / mrt_refit_instanced_scene refit it)");
@@ -616,7 +629,10 @@ int mrt_refit_two_level_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh
 	if (!verts9 || !instances || n_instances == 0 || n_mesh_tris == 0) return fail(ctx, MRT_ERR_INVALID, "refit: null or empty argument");
 	int rc = refit_precheck(ctx, flags, true);
 	if (rc) return rc;
-	if ((rc = mrt::check_two_level_refit(ctx->two_level, instances, n_instances, n_mesh_tris, ctx->err, sizeof(ctx->err)))) return rc;
+	const bool inst_on_device = (flags & MRT_BUILD_INSTANCES_ON_DEVICE) != 0;
+	if ((rc = mrt::check_two_level_refit(ctx->two_level, inst_on_device ? nullptr : instances, n_instances, n_mesh_tris, ctx->err, sizeof(ctx->err)))) return rc;
+	// device instances: their mesh ranges and transforms checked on the device, before any row of the scene is written
+	if (inst_on_device && (rc = mrt::device_update_tlas(ctx, instances, n_instances, true, 0, true, nullptr))) return rc;
 	// the staged triangle rows, then (host vertices) a copy of the mesh array behind them
 	const size_t tri_bytes = (size_t)ctx->n_tris * sizeof(mrt_tri64), vert_bytes = (size_t)n_mesh_tris * 9u * sizeof(float);
 	const bool on_device = (flags & MRT_BUILD_TRIS_ON_DEVICE) != 0;
@@ -627,7 +643,7 @@ int mrt_refit_two_level_scene(mrt_ctx *ctx, const float *verts9, uint32_t n_mesh
 		HIP_TRY(ctx, hipMemcpyAsync(dst, verts9, vert_bytes, hipMemcpyHostToDevice, ctx->stream));
 		d_verts9 = dst;
 	}
-	return mrt::refit_two_level_scene(ctx, d_verts9, instances, n_instances);
+	return mrt::refit_two_level_scene(ctx, d_verts9, instances, n_instances, inst_on_device);
 }
 
 } // extern "C"

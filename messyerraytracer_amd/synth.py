@@ -203,6 +203,35 @@ def multi_mesh_instances(n_meshes: int = 64, tris_per_mesh: int = 156250, s: flo
     return local, inst
 
 
+def many_instances(n_instances: int = 65536, n_meshes: int = 4, tris_per_mesh: int = 24, extent: float = 5.0, seed: int = 11):
+    """A scene of many placed copies of a few small meshes (the top level dominates): n_meshes soups of tris_per_mesh triangles,
+    each placed n_instances / n_meshes times with a seeded rotation, a scale in [0.15, 0.6) and an origin in [-extent, extent]^3, so
+    that instances overlap; every 64th instance is an exact duplicate of the one before it (same mesh, transform and mask: ties
+    across instances, which the lower flat id wins).  Masks: one of bits 0-3 per instance.  Returns mesh-space vertices
+    (n_meshes*tris_per_mesh,3,3) float32 and n_instances types.INSTANCE rows."""
+    from . import types as T
+    local = np.concatenate([soup(tris_per_mesh, 0.35, seed + m) * np.float32(0.2) for m in range(n_meshes)]).astype(np.float32)
+    inst = np.zeros(n_instances, dtype=T.INSTANCE)
+    mesh = np.arange(n_instances, dtype=np.uint32) % np.uint32(n_meshes)
+    inst["first_tri"] = mesh * np.uint32(tris_per_mesh)
+    inst["n_tris"] = tris_per_mesh
+    u = uniform01(seed + 0xB0B, 0, 5 * n_instances).reshape(n_instances, 5)
+    inst["layers"] = np.uint32(1) << (u[:, 4] * 4).astype(np.uint32)
+    q = _unit_vectors(seed + 0x5CA1E, n_instances, 4).astype(np.float32)
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    one, two = np.float32(1.0), np.float32(2.0)
+    rot = np.stack([one - two * (y * y + z * z), two * (x * y - w * z), two * (x * z + w * y),
+                    two * (x * y + w * z), one - two * (x * x + z * z), two * (y * z - w * x),
+                    two * (x * z - w * y), two * (y * z + w * x), one - two * (x * x + y * y)], axis=1)
+    scale = (np.float32(0.15) + np.float32(0.45) * u[:, 3]).astype(np.float32)
+    inst["basis"] = (rot * scale[:, None]).astype(np.float32)
+    inst["origin"] = (np.float32(-extent) + np.float32(2.0 * extent) * u[:, :3]).astype(np.float32)
+    dup = np.arange(64, n_instances, 64)
+    for f in ("first_tri", "n_tris", "layers", "basis", "origin"):
+        inst[f][dup] = inst[f][dup - 1]
+    return local, inst
+
+
 def flatten_instances(local: np.ndarray, inst: np.ndarray) -> np.ndarray:
     """World-space vertices of every instance, in instance order: Transform3D::xform per vertex as
     RayTracerServer::_rebuild_scene applies it (raytracer_server.cpp:700-711): basis row . v summed
