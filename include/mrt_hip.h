@@ -520,6 +520,33 @@ int mrt_cast_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint6
 int mrt_cast_grid_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
 		const mrt_hit32 *d_hits, const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags);
 
+/* ---- mirror-reflection rays from resident hit records: RTReflectionEffect's ray
+ * (src/gpu/shaders/rt_reflections.comp.glsl:278-330), made in the trace kernel and traced closest-hit.
+ * For every record i that is a hit and selected (d_select null, or d_select[i] != 0), with d the incoming
+ * ray's direction: p = the hit position (mrt_host_hit44: its `position`; mrt_hit32: origin + direction * t
+ * of the incoming ray); n = the record's normal, negated if ((nx*dx + ny*dy) + nz*dz) > 0 (faced against
+ * the incoming ray); k = 2 * ((nx*dx + ny*dy) + nz*dz); dir = d - k * n (not renormalised);
+ * org = p + n * 0.01, t_min = 0, t_max = max_distance.  Plain fp32 operations in that order.  Any other
+ * record (a primary miss, or not selected) gets the reference's placeholder Ray(0, (0,1,0), 0, 0): no walk,
+ * and the record mrt_cast writes for it (t = 0 and a miss; Intersection::set_miss in the host layout). */
+/* Mirror-reflection rays for the hit records of a cast: rt_reflections.comp.glsl's ray, traced closest-hit.
+ * d_rays / d_hits: what mrt_cast read and wrote -- mrt_ray32 + mrt_hit32, or with MRT_FLAG_HOST_LAYOUT
+ * mrt_host_ray60 + mrt_host_hit44 (the rays are always read: the incoming direction).  d_select: optional,
+ * one byte per record, 0 = no ray.  d_out_hits[i] = the record mrt_cast(MRT_MODE_NEAREST) writes for ray i,
+ * in the input layout.  d_out_rays: optional, ray i in the input layout (mrt_host_ray60 as Ray(o, d, t_min,
+ * t_max) fills it): with d_out_hits, the input of mrt_cast_shadows (shadows at the reflected points) or of
+ * another mrt_cast_reflections (a second bounce).  All pointers are device pointers.  Flags:
+ * MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID for a null
+ * required pointer, an unknown flag, max_distance not finite or not > 0.  Flat and two-level scenes. */
+int mrt_cast_reflections(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count,
+		const uint8_t *d_select, float max_distance,
+		void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_hits as it wrote them, mrt_hit32):
+ * the primary rays are regenerated in the kernel.  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_cast_grid_reflections(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h,
+		uint32_t y0, uint32_t y1, const mrt_hit32 *d_hits, const uint8_t *d_select, float max_distance,
+		mrt_hit32 *d_out_hits, mrt_ray32 *d_out_rays, uint32_t query_mask, uint32_t flags);
+
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to
  * tokens written by a cast with MRT_FLAG_TOKEN_OUT: mrt_hit32 records (mrt_host_hit44 with

@@ -1,5 +1,6 @@
 // cast.hip — the casts of the C-ABI: mrt_cast / mrt_submit / mrt_collect (rays from arrays), mrt_cast_grid (rays made in the
 // kernel), mrt_cast_tiled.  launch_policy.cpp plans every cast (which kernel, how launched); launch_planned runs the plan.
+#include <cfloat>
 #include <cstdio>
 #include <cstring>
 #include <atomic>
@@ -67,16 +68,24 @@ void note_queued(mrt_ctx *ctx, uint32_t kernel)
 	std::snprintf(ctx->queued_variant, sizeof(ctx->queued_variant), "%s", mrt::last_trace_variant());
 }
 
-// A shadow cast (sh: its lights and records, src its SRC_SHADOW_* source) launches the shadow instantiation of the same kernel.
-struct ShadowLaunch { const mrt::ShadowParams *params; int src; };
+// A cast whose rays are made in the kernel launches its source's instantiation of the same kernel: a shadow cast (shadow: its lights
+// and records, src its SRC_SHADOW_* source) or a reflection cast (reflect: its records, mask and outputs, src its SRC_REFLECT_* source).
+struct SourceLaunch { const mrt::ShadowParams *shadow; const mrt::ReflectParams *reflect; int src; };
 
-int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uint64_t count, bool any_hit, const ShadowLaunch *sh = nullptr)
+hipError_t launch_source(const SourceLaunch &sl, const mrt::TraceParams &p, unsigned long long *next_ray, uint32_t *ovf,
+		const mrt::LaneLaunch &l, hipStream_t stream)
+{
+	if (sl.shadow) return mrt::launch_shadow(p, *sl.shadow, sl.src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
+	return mrt::launch_reflection(p, *sl.reflect, sl.src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
+}
+
+int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uint64_t count, bool any_hit, const SourceLaunch *sh = nullptr)
 {
 	int rc;
 	p.kernel = l.kernel;
 	if (!l.persistent) {
 		p.sparse_lanes = l.sparse_lanes;
-		if (sh) HIP_TRY(ctx, mrt::launch_shadow(p, *sh->params, sh->src, nullptr, nullptr, 0, 0, 0, 0, ctx->stream));
+		if (sh) HIP_TRY(ctx, launch_source(*sh, p, nullptr, nullptr, mrt::LaneLaunch(), ctx->stream));
 		else HIP_TRY(ctx, mrt::launch_trace(p, any_hit, l.count, ctx->stream));
 		note_queued(ctx, p.kernel);
 		return MRT_OK;
@@ -89,7 +98,7 @@ int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uin
 	// eight ray counters (one per region of the batch), 128 bytes apart
 	unsigned long long *next_ray = ctx->d_counters + mrt::kNextRayOff;
 	HIP_TRY(ctx, hipMemsetAsync(next_ray, 0, 128 * sizeof(unsigned long long), ctx->stream));
-	if (sh) HIP_TRY(ctx, mrt::launch_shadow(p, *sh->params, sh->src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, ctx->stream));
+	if (sh) HIP_TRY(ctx, launch_source(*sh, p, next_ray, ovf, l, ctx->stream));
 	else HIP_TRY(ctx, mrt::launch_trace_persistent(p, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, any_hit, l.count, ctx->stream));
 	note_queued(ctx, p.kernel);
 	return MRT_OK;
@@ -98,7 +107,7 @@ int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uin
 // Runs a plan on the context's stream: pre-processing of rays from an array (sort, detect) from ev[2] to ev[3] (last_sort_ms), the
 // trace launches from ev[3] to ev[4] (last_trace_ms), then the sort of a measuring frame's tile costs on the side stream.  p holds
 // the batch (rays, hits, formats, grid); the plan decides the rest.
-int launch_planned(mrt_ctx *ctx, const mrt::CastPlan &c, const mrt::CastRequest &r, mrt::TraceParams &p, const ShadowLaunch *sh = nullptr)
+int launch_planned(mrt_ctx *ctx, const mrt::CastPlan &c, const mrt::CastRequest &r, mrt::TraceParams &p, const SourceLaunch *sh = nullptr)
 {
 	int rc;
 	const bool rays = mrt::ray_entry(r.entry), any = r.mode == MRT_MODE_ANY_HIT;
@@ -303,8 +312,37 @@ int cast_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, c
 	// (the plan reads neither the detected grid nor the grid states: an empty PrevDetect)
 	const mrt::CastRequest r{entry, p.count, flags, MRT_MODE_ANY_HIT};
 	const mrt::CastPlan c = mrt::plan_cast(ctx->opts, scene_facts(ctx), r, mrt::PrevDetect{}, ctx->knobs, ctx->grids);
-	const ShadowLaunch sh{&s, src};
+	const SourceLaunch sh{&s, nullptr, src};
 	int rc = launch_planned(ctx, c, r, p, &sh);
+	if (rc) return rc;
+	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
+	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
+}
+
+// The reflection casts (mrt_cast_reflections, mrt_cast_grid_reflections) after their own checks: p holds the scene, the grid (grid
+// source) and the incoming rays (SRC_REFLECT_RAY32, SRC_REFLECT_HOST); count = records.
+int cast_reflections(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
+		const uint8_t *d_select, float max_distance, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
+{
+	const uint32_t known = (entry == mrt::ENTRY_REFLECTION ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
+	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a reflection cast");
+	if (!d_hits || !d_out_hits) return fail(ctx, MRT_ERR_INVALID, "null hits / output hits");
+	if (!(max_distance > 0.0f && max_distance <= FLT_MAX)) return fail(ctx, MRT_ERR_INVALID, "max_distance must be finite and > 0");
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (count == 0) return MRT_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	mrt::ReflectParams s;
+	s.records = d_hits; s.select = d_select; s.out_rays = d_out_rays; s.max_distance = max_distance;
+	p.hits = d_out_hits; p.count = count; p.query_mask = query_mask;
+	p.out_fmt = src == mrt::SRC_REFLECT_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32;
+	// (the plan reads neither the detected grid nor the grid states: an empty PrevDetect)
+	const mrt::CastRequest r{entry, count, flags, MRT_MODE_NEAREST};
+	const mrt::CastPlan c = mrt::plan_cast(ctx->opts, scene_facts(ctx), r, mrt::PrevDetect{}, ctx->knobs, ctx->grids);
+	const SourceLaunch sl{nullptr, &s, src};
+	int rc = launch_planned(ctx, c, r, p, &sl);
 	if (rc) return rc;
 	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -482,6 +520,33 @@ int mrt_cast_grid_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, 
 	if (rc) return rc;
 	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the pairs; the kernel regenerates the primary ray from p.cam itself)
 	return cast_shadows(ctx, mrt::ENTRY_GRID_SHADOW, mrt::SRC_SHADOW_GRID, p, d_hits, p.count, lights, n_lights, d_mask, query_mask, flags);
+}
+
+int mrt_cast_reflections(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const uint8_t *d_select,
+		float max_distance, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
+	mrt::TraceParams p;
+	base_params(ctx, p);
+	p.rays = d_rays; // (read for every source: the incoming direction)
+	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
+	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
+	return cast_reflections(ctx, mrt::ENTRY_REFLECTION, host ? mrt::SRC_REFLECT_HOST : mrt::SRC_REFLECT_RAY32, p, d_hits, count,
+			d_select, max_distance, d_out_hits, d_out_rays, query_mask, flags);
+}
+
+int mrt_cast_grid_reflections(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const mrt_hit32 *d_hits, const uint8_t *d_select, float max_distance, mrt_hit32 *d_out_hits, mrt_ray32 *d_out_rays,
+		uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	mrt::TraceParams p;
+	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
+	if (rc) return rc;
+	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the records; the kernel regenerates the incoming ray from p.cam itself)
+	return cast_reflections(ctx, mrt::ENTRY_GRID_REFLECTION, mrt::SRC_REFLECT_GRID, p, d_hits, p.count, d_select, max_distance,
+			d_out_hits, d_out_rays, query_mask, flags);
 }
 
 } // extern "C"

@@ -330,6 +330,7 @@ __device__ __forceinline__ void finish_two_level_ray(const TraceParams &p, uint6
 }
 
 #include "shadow_kernel.h"
+#include "reflection_kernel.h"
 
 // ---- the traversal kernel: one lane = one ray -------------------------------------
 // LDS: per-lane stack, entry d of lane l at dword d*64 + l of the wave's region
@@ -339,6 +340,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 {
 	constexpr int SRC = SRC_CAST;
 	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -358,6 +360,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_shadow_lane_kernel(const TracePa
 {
 	constexpr bool ANY_HIT = true, COUNT = false;
 	const ShadowParams *sh = &s;
+	const ReflectParams *rf = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC>
@@ -365,6 +368,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_shadow_two_level_kernel(const Tr
 {
 	constexpr bool ANY_HIT = true;
 	const ShadowParams *sh = &s;
+	const ReflectParams *rf = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC, int WIDTH, bool TL>
@@ -372,6 +376,33 @@ __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_shadow_persiste
 {
 	constexpr bool ANY_HIT = true, COUNT = false;
 	const ShadowParams *sh = &s;
+	const ReflectParams *rf = nullptr;
+#include "persistent_walk.inc" // (in scope: the names its first lines check)
+}
+
+// ---- reflection casts (reflection_kernel.h): the same lane kernels, closest-hit, with a reflection ray source ------------------
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void trace_reflection_lane_kernel(const TraceParams p, const ReflectParams s)
+{
+	constexpr bool ANY_HIT = false, COUNT = false;
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = &s;
+#include "lane_walk.inc" // (in scope: the names its first lines check)
+}
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void trace_reflection_two_level_kernel(const TraceParams p, const ReflectParams s)
+{
+	constexpr bool ANY_HIT = false;
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = &s;
+#include "two_level_walk.inc" // (in scope: the names its first lines check)
+}
+template <int SRC, int WIDTH, bool TL>
+__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_reflection_persistent_kernel(const TraceParams p, const PersistParams q, const ReflectParams s)
+{
+	constexpr bool ANY_HIT = false, COUNT = false;
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = &s;
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -945,6 +976,47 @@ hipError_t launch_shadow(const TraceParams &p, const ShadowParams &s, int src, u
 	if (src == SRC_SHADOW_RAY32) launch_shadow_src<SRC_SHADOW_RAY32>(p, s, q, blocks, stream);
 	else if (src == SRC_SHADOW_HOST44) launch_shadow_src<SRC_SHADOW_HOST44>(p, s, q, blocks, stream);
 	else if (src == SRC_SHADOW_GRID) launch_shadow_src<SRC_SHADOW_GRID>(p, s, q, blocks, stream);
+	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+// Reflection casts: the same, with the reflection instantiations (ENTRY_REFLECTION / ENTRY_GRID_REFLECTION); p.count = records.
+template <int SRC>
+static void launch_reflection_src(const TraceParams &p, const ReflectParams &s, const PersistParams &q, uint32_t blocks, hipStream_t stream)
+{
+	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
+	if (blocks == 0) {
+		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
+		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
+		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
+		if (tl) hipLaunchKernelGGL((trace_reflection_two_level_kernel<SRC>), grid, wg, lds, stream, p, s);
+		else hipLaunchKernelGGL((trace_reflection_lane_kernel<SRC>), grid, wg, lds, stream, p, s);
+		note_variant("trace_reflection_%s_kernel<%d>", tl ? "two_level" : "lane", SRC);
+		return;
+	}
+	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
+	int width = 2;
+	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
+		width = 8; hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else if (tl) hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) {
+		width = 8; hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 8, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) {
+		width = 4; hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 4, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 2, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	note_variant("trace_reflection_persistent_kernel<%d, %d, %s>", SRC, width, MRT_B(tl));
+}
+
+hipError_t launch_reflection(const TraceParams &p, const ReflectParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
+{
+	if (p.count == 0) return hipSuccess;
+	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
+	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
+	if (src == SRC_REFLECT_RAY32) launch_reflection_src<SRC_REFLECT_RAY32>(p, s, q, blocks, stream);
+	else if (src == SRC_REFLECT_HOST) launch_reflection_src<SRC_REFLECT_HOST>(p, s, q, blocks, stream);
+	else if (src == SRC_REFLECT_GRID) launch_reflection_src<SRC_REFLECT_GRID>(p, s, q, blocks, stream);
 	else return hipErrorInvalidValue;
 	return hipGetLastError();
 }

@@ -197,9 +197,19 @@ static CastPlan plan_shadow(const mrt_options &o, const SceneFacts &s, const Cas
 	return c;
 }
 
+// Reflection casts: count = records, one closest-hit mirror ray each, made in the kernel in record order.  Planned as shadow casts
+// are, for the same reasons (no sort: the rays never exist in memory; no detection, no tiling; the plain lane kernel below 2^16 rays,
+// the persistent ones from 2^16; a forced packet kernel means the policy's lane kernel; no counting variant): the mode does not enter
+// the lane plan.  Nothing of the grid state is read or changed.
+static CastPlan plan_reflection(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
+{
+	return plan_shadow(o, s, r);
+}
+
 CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest &r, const PrevDetect &prev, const Knobs &k, GridStates &gs)
 {
 	if (shadow_entry(r.entry)) return plan_shadow(o, s, r);
+	if (reflection_entry(r.entry)) return plan_reflection(o, s, r);
 	CastPlan c;
 	const uint64_t n = r.count;
 	const bool auto_k = o.kernel == MRT_KERNEL_AUTO, coherent = (r.flags & MRT_FLAG_COHERENT) != 0;

@@ -168,13 +168,26 @@ struct TraceParams {
 // Entry g of a shadow cast is the pair (light g / pixels, pixel g % pixels); TraceParams::count = pixels * lights, hits = the
 // lit mask (one byte per entry), rays = the primary rays (SRC_SHADOW_RAY32).  The ray source is a template parameter of the
 // kernels (SRC_CAST: the rays of an ordinary cast, the instantiations that existed before).
-enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, SRC_SHADOW_GRID = 3 };
+enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, SRC_SHADOW_GRID = 3,
+	SRC_REFLECT_RAY32 = 4, SRC_REFLECT_HOST = 5, SRC_REFLECT_GRID = 6 };
+constexpr bool shadow_source(int src) { return src >= SRC_SHADOW_RAY32 && src <= SRC_SHADOW_GRID; }
+constexpr bool reflection_source(int src) { return src >= SRC_REFLECT_RAY32 && src <= SRC_REFLECT_GRID; }
 enum ShadowKind : uint32_t { SHADOW_OFF = 0, SHADOW_DIRECTIONAL = 1, SHADOW_POINT = 2 }; // OFF: cast_shadows == 0 (lit)
 struct ShadowLight { uint32_t kind; float v[3]; }; // DIRECTIONAL: direction towards the light; POINT (point and spot): position
 struct ShadowParams {
 	const void *records;       // mrt_hit32 (SRC_SHADOW_RAY32, SRC_SHADOW_GRID) or mrt_host_hit44 (SRC_SHADOW_HOST44), `pixels` of them
 	uint64_t pixels;
 	ShadowLight light[MRT_MAX_LIGHTS];
+};
+
+// ---- mirror-reflection rays (reflection_kernel.h): one closest-hit ray per hit record of a cast --------------------------------
+// Entry i of a reflection cast is record i; TraceParams::count = records, hits = the output records (out_fmt OUT_HIT32 or OUT_HOST44),
+// rays = the incoming rays (SRC_REFLECT_RAY32: mrt_ray32, SRC_REFLECT_HOST: mrt_host_ray60; SRC_REFLECT_GRID regenerates them).
+struct ReflectParams {
+	const void *records;       // mrt_hit32 (SRC_REFLECT_RAY32, SRC_REFLECT_GRID) or mrt_host_hit44 (SRC_REFLECT_HOST)
+	const uint8_t *select;     // optional: 0 = no ray for this record
+	void *out_rays;            // optional: the rays made, mrt_ray32 (or mrt_host_ray60 for SRC_REFLECT_HOST)
+	float max_distance;        // t_max of every ray
 };
 
 // host-side preparation (scene_prep.cpp)

@@ -1,16 +1,19 @@
-// two_level_walk.inc -- the body of trace_two_level_kernel (two_level_kernel.h) and trace_shadow_two_level_kernel (kernels.hip),
-// included inside both (see lane_walk.inc).  In scope: p, sh, ANY_HIT, SRC.
+// two_level_walk.inc -- the body of trace_two_level_kernel (two_level_kernel.h), trace_shadow_two_level_kernel and
+// trace_reflection_two_level_kernel (kernels.hip), included inside each (see lane_walk.inc).  In scope: p, sh, rf, ANY_HIT, SRC.
 	// the contract with the including kernel, checked here rather than deep in the walk
-	static_assert(std::is_same<decltype(p), const TraceParams>::value && std::is_same<decltype(sh), const ShadowParams *>::value,
-			"two_level_walk.inc: p (const TraceParams) and sh (const ShadowParams *) in scope");
-	static_assert(SRC == SRC_CAST || ANY_HIT, "two_level_walk.inc: a shadow source is any-hit");
+	static_assert(std::is_same<decltype(p), const TraceParams>::value && std::is_same<decltype(sh), const ShadowParams *>::value &&
+			std::is_same<decltype(rf), const ReflectParams *>::value,
+			"two_level_walk.inc: p (const TraceParams), sh (const ShadowParams *) and rf (const ReflectParams *) in scope");
+	static_assert(SRC == SRC_CAST || (shadow_source(SRC) && ANY_HIT) || (reflection_source(SRC) && !ANY_HIT),
+			"two_level_walk.inc: shadow sources are any-hit, reflection sources closest-hit");
 	extern __shared__ uint32_t lds_stack[];
 	if (skip_launch(p)) return;
 	uint64_t ray_idx = 0; uint32_t px = 0, py = 0;
 	if (!lane_ray_index(p, blockIdx.x, ray_idx, px, py)) return;
 	RayRegs r;
 	if constexpr (SRC == SRC_CAST) load_ray(p, ray_idx, px, py, r);
-	else if (!shadow_ray<SRC>(p, *sh, ray_idx, r)) { store_lit(p, ray_idx, true); return; }
+	else if constexpr (shadow_source(SRC)) { if (!shadow_ray<SRC>(p, *sh, ray_idx, r)) { store_lit(p, ray_idx, true); return; } }
+	else if (!reflection_ray<SRC>(p, *rf, ray_idx, r)) { store_no_reflection(p, ray_idx); return; }
 
 	float best_t = r.t_max, best_u = 0.0f, best_v = 0.0f;
 	uint32_t best_slot = 0xFFFFFFFFu, best_id = 0xFFFFFFFFu, best_inst = 0u;
@@ -122,5 +125,5 @@
 		}
 	}
 
-	if constexpr (SRC == SRC_CAST) finish_two_level_ray(p, ray_idx, r, best_t, best_u, best_v, best_slot, best_id, best_inst);
+	if constexpr (!shadow_source(SRC)) finish_two_level_ray(p, ray_idx, r, best_t, best_u, best_v, best_slot, best_id, best_inst);
 	else store_lit(p, ray_idx, best_slot == 0xFFFFFFFFu);
