@@ -547,6 +547,70 @@ int mrt_cast_grid_reflections(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid
 		uint32_t y0, uint32_t y1, const mrt_hit32 *d_hits, const uint8_t *d_select, float max_distance,
 		mrt_hit32 *d_out_hits, mrt_ray32 *d_out_rays, uint32_t query_mask, uint32_t flags);
 
+/* ---- cosine-weighted hemisphere rays from resident hit records: the diffuse bounce of the reference's path
+ * tracer (cosine_hemisphere_sample, src/modules/graphics/path_trace.h:101-120, drawn from the PCG32 of
+ * path_state.h:40-67) and, any-hit with a short t_max, its ambient-occlusion ray.  n_samples rays per record,
+ * made in the trace kernel.  Entry g = sample g / pixels, pixel g % pixels.  For every entry whose record is a
+ * hit and selected (d_select null, or d_select[pixel] != 0), plain fp32 operations in this order, nothing
+ * contracted:
+ *   p, d = the hit position and the incoming direction as for mrt_cast_reflections; n = the record's normal,
+ *       negated if ((nx*dx + ny*dy) + nz*dz) > 0 (faced against the incoming ray: records carry the geometric
+ *       normal, and a back-face hit would otherwise start behind the surface).
+ *   PCG32 (32-bit state, state' = state * 747796405 + 2891336453; output of a state: word = ((state >>
+ *       ((state >> 28) + 4)) ^ state) * 277803737, (word >> 22) ^ word), seeded as PathState::init seeds it:
+ *       seed = pixel_index * 1009 + frame * 6529 + 7, state0 = (2891336453 + seed) * 747796405 + 2891336453.
+ *       pixel_index = y * grid_w + x of the whole grid (grid form: a row band draws what the whole frame draws)
+ *       or the record's index (array form), modulo 2^32.  Sample s takes draws number first_draw + 2s and
+ *       first_draw + 2s + 1 of that stream (draw 0 is the first after seeding) as u1, u2, each
+ *       float(output) * 2^-32: in [0, 1], exactly 1.0 for outputs from 0xFFFFFF80 up, as the reference's
+ *       next_float.  (first_draw = 1 is where the path tracer stands after its lobe-selection draw.)
+ *   r = sqrt(u1), z = sqrt(max(0, 1 - u1)), both correctly rounded.
+ *   cs, sn = cos and sin of 2 pi u2, defined here rather than taken from a math library (the reference calls
+ *       std::cos / std::sin on 2 * PT_PI * u2; device and host libraries differ in the last bits, and every
+ *       output of this library is reproducible on the CPU bit for bit): a = u2 * 4, k = rint(a) (ties to even),
+ *       f = a - k (all exact), x = f * 1.5707964f, x2 = x * x,
+ *         S = x + (x * x2) * ((((-2.5052108e-08f * x2 + 2.7557319e-06f) * x2 + -1.984127e-04f) * x2
+ *                 + 8.333334e-03f) * x2 + -1.6666667e-01f)
+ *         C = 1 + x2 * ((((-2.755732e-07f * x2 + 2.4801588e-05f) * x2 + -1.3888889e-03f) * x2
+ *                 + 4.1666668e-02f) * x2 + -5.0e-01f)
+ *       every multiply and add rounded on its own, and by k & 3: 0 (C, S); 1 (-S, C); 2 (-C, -S); 3 (S, -C).
+ *       Within 1e-7 of the exact value, closer than the reference's own float32 formula (4.2e-7).
+ *   x = r * cs, y = r * sn.
+ *   construct_onb (Duff et al.): sign = copysign(1, nz), a = -1 / (sign + nz), b = (nx * ny) * a,
+ *       t = (1 + ((sign * nx) * nx) * a, sign * b, (-sign) * nx), bt = (b, sign + (ny * ny) * a, -ny).
+ *   v = (t * x + bt * y) + n * z per component; dir = v / sqrt((vx*vx + vy*vy) + vz*vz) per component (0 where
+ *       the sum is 0).
+ *   org = p + n * 1e-3 (PT_SHADOW_BIAS), t_min = 1e-4, t_max = the descriptor's.
+ * An entry has no ray if its record is a miss, it is not selected, or ((nx*dirx + ny*diry) + nz*dirz) <= 0
+ * (the reference's "below surface -- invalid sample": u1 == 1 can produce it).  Nothing is walked for it. */
+#define MRT_MAX_HEMISPHERE_SAMPLES 16
+typedef struct mrt_hemisphere {
+	uint32_t n_samples;        /* 1 .. MRT_MAX_HEMISPHERE_SAMPLES rays per record                        */
+	uint32_t frame;            /* enters the seed                                                        */
+	uint32_t first_draw;       /* the stream's draws before sample 0 (the path tracer: 1)                */
+	float t_max;               /* finite and > 1e-4: 1e30f for a bounce, the radius for ambient occlusion */
+	const uint8_t *d_select;   /* optional device pointer, one byte per record: 0 = no ray               */
+} mrt_hemisphere;
+/* Hemisphere rays for the hit records of a cast.  d_rays / d_hits: what mrt_cast read and wrote -- mrt_ray32 +
+ * mrt_hit32, or with MRT_FLAG_HOST_LAYOUT mrt_host_ray60 + mrt_host_hit44 (the rays are always read: the
+ * incoming direction).  mode == MRT_MODE_ANY_HIT (ambient occlusion): d_out[s * count + i] = one byte,
+ * 1 - occluded, 1 for an entry without a ray; d_out_rays must be null.  mode == MRT_MODE_NEAREST (a diffuse
+ * bounce): d_out[s * count + i] = the record mrt_cast(MRT_MODE_NEAREST) writes for the ray, in the input
+ * layout; d_out_rays: optional, the ray in the input layout; an entry without a ray gets the placeholder ray
+ * and its record as mrt_cast_reflections writes them.  Both feed mrt_cast_shadows, mrt_cast_reflections or the
+ * next mrt_cast_hemisphere (count * n_samples records).  All pointers but desc are device pointers.  Flags:
+ * MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID for a null
+ * required pointer, n_samples outside 1 .. 16, t_max not finite or not > 1e-4, a mode other than the two,
+ * d_out_rays with any-hit, count * n_samples overflowing, an unknown flag.  Flat and two-level scenes. */
+int mrt_cast_hemisphere(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count,
+		const mrt_hemisphere *desc, void *d_out, void *d_out_rays, uint32_t query_mask, int mode, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_hits as it wrote them, mrt_hit32;
+ * d_select one byte per record of the band): the primary rays are regenerated in the kernel.
+ * count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_cast_grid_hemisphere(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h,
+		uint32_t y0, uint32_t y1, const void *d_hits, const mrt_hemisphere *desc, void *d_out, void *d_out_rays,
+		uint32_t query_mask, int mode, uint32_t flags);
+
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to
  * tokens written by a cast with MRT_FLAG_TOKEN_OUT: mrt_hit32 records (mrt_host_hit44 with

@@ -31,7 +31,7 @@ SYMBOLS = [
     "mrt_synchronize", "mrt_make_triangles", "mrt_pack_host_triangles", "mrt_bvh2_build", "mrt_bvh2_save", "mrt_bvh2_load", "mrt_upload_scene",
     "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_update_instances_device", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
-    "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_expand_tokens",
+    "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
     "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
     "mrt_group_create", "mrt_group_destroy", "mrt_group_size", "mrt_group_context", "mrt_group_last_error", "mrt_group_row_block",
@@ -58,6 +58,12 @@ class Camera(C.Structure):
                 ("half_w", C.c_float), ("half_h", C.c_float), ("t_min", C.c_float), ("t_max", C.c_float),
                 ("kind", C.c_uint32), ("inv_w", C.c_float), ("inv_h", C.c_float), ("jitter_x", C.c_float), ("jitter_y", C.c_float),
                 ("reserved", C.c_uint32 * 3)]
+
+
+class Hemisphere(C.Structure):
+    """mrt_hemisphere"""
+    _fields_ = [("n_samples", C.c_uint32), ("frame", C.c_uint32), ("first_draw", C.c_uint32), ("t_max", C.c_float),
+                ("d_select", C.c_void_p)]
 
 
 class Stats(C.Structure):
@@ -134,6 +140,10 @@ def load():
                                        C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_cast_grid_reflections.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.mrt_cast_hemisphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Hemisphere), C.c_void_p, C.c_void_p,
+                                      C.c_uint32, C.c_int, C.c_uint32]
+    L.mrt_cast_grid_hemisphere.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                           C.POINTER(Hemisphere), C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32]
     L.mrt_cast_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mrt_expand_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
     L.mrt_expand_grid_tokens.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -168,6 +178,12 @@ def _np(a):
 def _optr(x):
     """_ptr, or a null pointer for None (optional arguments)"""
     return None if x is None else _ptr(x)
+
+
+def hemisphere_desc(n_samples, frame, first_draw, t_max, d_select=None):
+    """mrt_hemisphere from its fields (d_select: device pointer / tensor or None)"""
+    sel = _optr(d_select)
+    return Hemisphere(n_samples, frame, first_draw, t_max, None if sel is None else sel.value)
 
 
 def _ptr(x):
@@ -504,6 +520,25 @@ class Context:
         y1 = grid_h if y1 is None else y1
         self._chk(self.L.mrt_cast_grid_reflections(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _optr(d_select),
                                                    max_distance, _ptr(d_out_hits), _optr(d_out_rays), query_mask, flags))
+
+    def cast_hemisphere(self, d_rays, d_hits, count, d_out, n_samples=1, frame=0, first_draw=1, t_max=1e30, mode=MODE_NEAREST,
+                        d_select=None, d_out_rays=None, query_mask=0xFFFFFFFF, flags=0):
+        """Cosine-weighted hemisphere rays for the hit records of a cast (device pointers / tensors: mrt_ray32 + mrt_hit32, or
+        mrt_host_ray60 + mrt_host_hit44 with FLAG_HOST_LAYOUT), n_samples per record, entry = sample * count + record.  MODE_ANY_HIT
+        (ambient occlusion): d_out one byte per entry, 1 - occluded.  MODE_NEAREST (a diffuse bounce): d_out one record per entry in the
+        input layout, d_out_rays (optional) the rays made.  d_select: optional byte per record (0 = no ray)."""
+        desc = hemisphere_desc(n_samples, frame, first_draw, t_max, d_select)
+        self._chk(self.L.mrt_cast_hemisphere(self.h, _ptr(d_rays), _ptr(d_hits), count, C.byref(desc), _ptr(d_out), _optr(d_out_rays),
+                                             query_mask, mode, flags))
+
+    def cast_grid_hemisphere(self, cam, grid_w, grid_h, d_hits, d_out, n_samples=1, frame=0, first_draw=1, t_max=1e30,
+                             mode=MODE_NEAREST, d_select=None, d_out_rays=None, y0=0, y1=None, query_mask=0xFFFFFFFF, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (d_hits: its mrt_hit32 records on the device); the random stream of a
+        pixel is seeded from its index in the whole grid."""
+        y1 = grid_h if y1 is None else y1
+        desc = hemisphere_desc(n_samples, frame, first_draw, t_max, d_select)
+        self._chk(self.L.mrt_cast_grid_hemisphere(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(desc), _ptr(d_out),
+                                                  _optr(d_out_rays), query_mask, mode, flags))
 
     def expand_tokens(self, d_rays, d_tokens, d_hits, count, flags=0, stream=None):
         """Device pointers; enqueued on `stream` (raw hipStream_t) or the context's stream, not waited for."""

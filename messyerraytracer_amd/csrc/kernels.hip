@@ -331,6 +331,7 @@ __device__ __forceinline__ void finish_two_level_ray(const TraceParams &p, uint6
 
 #include "shadow_kernel.h"
 #include "reflection_kernel.h"
+#include "hemisphere_kernel.h"
 
 // ---- the traversal kernel: one lane = one ray -------------------------------------
 // LDS: per-lane stack, entry d of lane l at dword d*64 + l of the wave's region
@@ -341,6 +342,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 	constexpr int SRC = SRC_CAST;
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -361,6 +363,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_shadow_lane_kernel(const TracePa
 	constexpr bool ANY_HIT = true, COUNT = false;
 	const ShadowParams *sh = &s;
 	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC>
@@ -369,6 +372,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_shadow_two_level_kernel(const Tr
 	constexpr bool ANY_HIT = true;
 	const ShadowParams *sh = &s;
 	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC, int WIDTH, bool TL>
@@ -377,6 +381,7 @@ __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_shadow_persiste
 	constexpr bool ANY_HIT = true, COUNT = false;
 	const ShadowParams *sh = &s;
 	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = nullptr;
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -387,6 +392,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_reflection_lane_kernel(const Tra
 	constexpr bool ANY_HIT = false, COUNT = false;
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = &s;
+	const HemiParams *hm = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC>
@@ -395,6 +401,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_reflection_two_level_kernel(cons
 	constexpr bool ANY_HIT = false;
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = &s;
+	const HemiParams *hm = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC, int WIDTH, bool TL>
@@ -403,6 +410,35 @@ __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_reflection_pers
 	constexpr bool ANY_HIT = false, COUNT = false;
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = &s;
+	const HemiParams *hm = nullptr;
+#include "persistent_walk.inc" // (in scope: the names its first lines check)
+}
+
+// ---- hemisphere casts (hemisphere_kernel.h): the same lane kernels, any-hit (ambient occlusion) or closest-hit (a diffuse bounce) ----
+template <int SRC, bool ANY_HIT>
+__global__ __launch_bounds__(MRT_WG) void trace_hemisphere_lane_kernel(const TraceParams p, const HemiParams s)
+{
+	constexpr bool COUNT = false;
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = &s;
+#include "lane_walk.inc" // (in scope: the names its first lines check)
+}
+template <int SRC, bool ANY_HIT>
+__global__ __launch_bounds__(MRT_WG) void trace_hemisphere_two_level_kernel(const TraceParams p, const HemiParams s)
+{
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = &s;
+#include "two_level_walk.inc" // (in scope: the names its first lines check)
+}
+template <int SRC, bool ANY_HIT, int WIDTH, bool TL>
+__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_hemisphere_persistent_kernel(const TraceParams p, const PersistParams q, const HemiParams s)
+{
+	constexpr bool COUNT = false;
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = &s;
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -1017,6 +1053,47 @@ hipError_t launch_reflection(const TraceParams &p, const ReflectParams &s, int s
 	if (src == SRC_REFLECT_RAY32) launch_reflection_src<SRC_REFLECT_RAY32>(p, s, q, blocks, stream);
 	else if (src == SRC_REFLECT_HOST) launch_reflection_src<SRC_REFLECT_HOST>(p, s, q, blocks, stream);
 	else if (src == SRC_REFLECT_GRID) launch_reflection_src<SRC_REFLECT_GRID>(p, s, q, blocks, stream);
+	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+// Hemisphere casts: the same, with the hemisphere instantiations (ENTRY_HEMISPHERE / ENTRY_GRID_HEMISPHERE); p.count = pixels * samples.
+template <int SRC, bool ANY_HIT>
+static void launch_hemisphere_src(const TraceParams &p, const HemiParams &s, const PersistParams &q, uint32_t blocks, hipStream_t stream)
+{
+	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
+	if (blocks == 0) {
+		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
+		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
+		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
+		if (tl) hipLaunchKernelGGL((trace_hemisphere_two_level_kernel<SRC, ANY_HIT>), grid, wg, lds, stream, p, s);
+		else hipLaunchKernelGGL((trace_hemisphere_lane_kernel<SRC, ANY_HIT>), grid, wg, lds, stream, p, s);
+		note_variant("trace_hemisphere_%s_kernel<%d, %s>", tl ? "two_level" : "lane", SRC, MRT_B(ANY_HIT));
+		return;
+	}
+	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
+	int width = 2;
+	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
+		width = 8; hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else if (tl) hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) {
+		width = 8; hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 8, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) {
+		width = 4; hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 4, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 2, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	note_variant("trace_hemisphere_persistent_kernel<%d, %s, %d, %s>", SRC, MRT_B(ANY_HIT), width, MRT_B(tl));
+}
+
+hipError_t launch_hemisphere(const TraceParams &p, const HemiParams &s, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
+{
+	if (p.count == 0) return hipSuccess;
+	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
+	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
+	if (src == SRC_HEMI_RAY32) { if (any_hit) launch_hemisphere_src<SRC_HEMI_RAY32, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_RAY32, false>(p, s, q, blocks, stream); }
+	else if (src == SRC_HEMI_HOST) { if (any_hit) launch_hemisphere_src<SRC_HEMI_HOST, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_HOST, false>(p, s, q, blocks, stream); }
+	else if (src == SRC_HEMI_GRID) { if (any_hit) launch_hemisphere_src<SRC_HEMI_GRID, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_GRID, false>(p, s, q, blocks, stream); }
 	else return hipErrorInvalidValue;
 	return hipGetLastError();
 }

@@ -206,10 +206,20 @@ static CastPlan plan_reflection(const mrt_options &o, const SceneFacts &s, const
 	return plan_shadow(o, s, r);
 }
 
+// Hemisphere casts: count = pixels * samples rays made in the kernel, sample-major in pixel order; any-hit (ambient occlusion) or
+// closest-hit (a diffuse bounce).  The shadow plan or the reflection plan of that many rays -- one plan, since the mode does not enter
+// it -- although these rays are far less coherent than either: unsorted all the same (the rays never exist in memory, so there is
+// nothing to sort), and the lane kernels are the ones for incoherent batches.  Nothing of the grid state is read or changed.
+static CastPlan plan_hemisphere(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
+{
+	return r.mode == MRT_MODE_ANY_HIT ? plan_shadow(o, s, r) : plan_reflection(o, s, r);
+}
+
 CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest &r, const PrevDetect &prev, const Knobs &k, GridStates &gs)
 {
 	if (shadow_entry(r.entry)) return plan_shadow(o, s, r);
 	if (reflection_entry(r.entry)) return plan_reflection(o, s, r);
+	if (hemisphere_entry(r.entry)) return plan_hemisphere(o, s, r);
 	CastPlan c;
 	const uint64_t n = r.count;
 	const bool auto_k = o.kernel == MRT_KERNEL_AUTO, coherent = (r.flags & MRT_FLAG_COHERENT) != 0;

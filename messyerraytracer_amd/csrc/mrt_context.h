@@ -18,6 +18,9 @@ hipError_t launch_shadow(const TraceParams &p, const ShadowParams &s, int src, u
 // reflection casts (reflection_kernel.h): src = SRC_REFLECT_*; the rest as launch_shadow
 hipError_t launch_reflection(const TraceParams &p, const ReflectParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
+// hemisphere casts (hemisphere_kernel.h): src = SRC_HEMI_*, any_hit: one byte per entry instead of a record; the rest as launch_shadow
+hipError_t launch_hemisphere(const TraceParams &p, const HemiParams &s, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
 hipError_t launch_build_rows4(const Dev4Node *nodes4, const TriHot *hot, const TriCold *cold, uint32_t n_nodes4, uint32_t n_tris,
 		void *rows, hipStream_t stream);
 hipError_t launch_build_rows(const DevNode *nodes, const TriHot *hot, const TriCold *cold, uint32_t n_nodes, uint32_t n_tris,

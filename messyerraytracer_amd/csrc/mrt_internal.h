@@ -169,9 +169,13 @@ struct TraceParams {
 // lit mask (one byte per entry), rays = the primary rays (SRC_SHADOW_RAY32).  The ray source is a template parameter of the
 // kernels (SRC_CAST: the rays of an ordinary cast, the instantiations that existed before).
 enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, SRC_SHADOW_GRID = 3,
-	SRC_REFLECT_RAY32 = 4, SRC_REFLECT_HOST = 5, SRC_REFLECT_GRID = 6 };
+	SRC_REFLECT_RAY32 = 4, SRC_REFLECT_HOST = 5, SRC_REFLECT_GRID = 6,
+	SRC_HEMI_RAY32 = 7, SRC_HEMI_HOST = 8, SRC_HEMI_GRID = 9 };
 constexpr bool shadow_source(int src) { return src >= SRC_SHADOW_RAY32 && src <= SRC_SHADOW_GRID; }
 constexpr bool reflection_source(int src) { return src >= SRC_REFLECT_RAY32 && src <= SRC_REFLECT_GRID; }
+constexpr bool hemisphere_source(int src) { return src >= SRC_HEMI_RAY32 && src <= SRC_HEMI_GRID; }
+// the result of an entry is one byte (1 = no occluder, or no ray): every shadow cast, and a hemisphere cast in any-hit mode
+constexpr bool lit_output(int src, bool any_hit) { return shadow_source(src) || (hemisphere_source(src) && any_hit); }
 enum ShadowKind : uint32_t { SHADOW_OFF = 0, SHADOW_DIRECTIONAL = 1, SHADOW_POINT = 2 }; // OFF: cast_shadows == 0 (lit)
 struct ShadowLight { uint32_t kind; float v[3]; }; // DIRECTIONAL: direction towards the light; POINT (point and spot): position
 struct ShadowParams {
@@ -188,6 +192,22 @@ struct ReflectParams {
 	const uint8_t *select;     // optional: 0 = no ray for this record
 	void *out_rays;            // optional: the rays made, mrt_ray32 (or mrt_host_ray60 for SRC_REFLECT_HOST)
 	float max_distance;        // t_max of every ray
+};
+
+// ---- cosine-weighted hemisphere rays (hemisphere_kernel.h): n_samples rays per hit record of a cast ----------------------------
+// Entry g of a hemisphere cast is the pair (sample g / pixels, pixel g % pixels); TraceParams::count = pixels * n_samples, hits = one
+// byte per entry (any-hit) or one record per entry (closest-hit), rays = the incoming rays as for reflections.  The generator's state
+// before a sample's first draw is jump[sample].a * state0 + jump[sample].c (hemisphere_jumps, cast.hip).
+constexpr uint32_t kPcgMul = 747796405u, kPcgInc = 2891336453u; // the reference's PCG32 (path_state.h): state' = state * mul + inc
+struct HemiJump { uint32_t a, c; };
+struct HemiParams {
+	const void *records;       // mrt_hit32 (SRC_HEMI_RAY32, SRC_HEMI_GRID) or mrt_host_hit44 (SRC_HEMI_HOST)
+	const uint8_t *select;     // optional: 0 = no ray for this pixel
+	void *out_rays;            // optional (closest-hit only): the rays made, mrt_ray32 (or mrt_host_ray60 for SRC_HEMI_HOST)
+	uint64_t pixels;
+	uint32_t seed_add;         // frame * 6529 + 7 (+ y0 * grid_w * 1009 for a row band): seed = pixel * 1009 + seed_add
+	float t_max;               // t_max of every ray
+	HemiJump jump[MRT_MAX_HEMISPHERE_SAMPLES];
 };
 
 // host-side preparation (scene_prep.cpp)

@@ -16,6 +16,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_two_level_kernel(const TracePara
 	constexpr int SRC = SRC_CAST;
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 

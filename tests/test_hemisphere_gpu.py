@@ -1,0 +1,530 @@
+"""mrt_cast_hemisphere / mrt_cast_grid_hemisphere: cosine-weighted hemisphere rays made in the trace kernels from resident hit
+records, against the sampler restated in numpy float32 (messyerraytracer_amd/hemisphere.py; pinned to the reference by
+test_hemisphere_cpu.py) and traced by the oracle -- byte for byte -- and against the same rays cast through mrt_cast(NEAREST).  A soup
+(back faces: the normal flip), flat and two-level synth.room(); closest-hit (a diffuse bounce: records and rays) and any-hit (ambient
+occlusion: bytes); grids with whole and clipped tiles and a row band, records of mrt_cast in both layouts; sample counts, frames, first
+draws; selection masks; query masks; the plain and the persistent kernels; chained shadow casts and a second bounce; ASYNC; primary
+grids unaffected; errors."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from messyerraytracer_amd import capi, synth, types as T
+from messyerraytracer_amd import hemisphere as H
+from oracle import pyoracle as po
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+DEV = capi.FLAG_RAYS_ON_DEVICE | capi.FLAG_HITS_ON_DEVICE
+ROOM_CAM = ((0.0, 3.0, 4.6), (0.0, -0.35, -1.0), 70.0)
+SOUP_CAM = ((0.0, 0.0, -12.0), (0.0, 0.0, 1.0), 50.0)
+FAR, AO_RADIUS = F(1e30), F(1.0)
+PLACEHOLDER_HIT = np.zeros(1, dtype=T.HIT32)  # what mrt_cast writes for the placeholder ray: t = t_max = 0, a miss
+PLACEHOLDER_HIT["prim_id"] = -1
+
+
+class Scene:
+    def __init__(self, kind):
+        self.kind = kind
+        if kind == "soup":
+            self.local, self.inst = synth.soup(2000, 0.4, 3), None
+            self.verts, self.layers, self.cam = self.local, np.full(2000, 0xFFFFFFFF, np.uint32), SOUP_CAM
+        else:
+            self.local, self.inst = synth.room()
+            self.verts = synth.flatten_instances(self.local, self.inst)
+            self.layers = np.repeat(self.inst["layers"], self.inst["n_tris"]).astype(np.uint32)
+            self.cam = ROOM_CAM
+        self._oracle = None
+
+    def upload(self, ctx):
+        if self.kind == "room_tl":
+            ctx.upload_two_level_scene(self.local, self.inst)
+        else:
+            tris = capi.make_triangles(self.verts, layers=self.layers)
+            nodes, prim_idx, _ = capi.bvh2_build(T.verts4_from_verts9(self.verts))
+            ctx.upload_scene(tris, nodes, prim_idx)
+
+    def oracle(self, rays, query_mask=0xFFFFFFFF, any_hit=False):
+        if self._oracle is None:
+            self._oracle = (po.OracleTwoLevelScene(self.local, self.inst) if self.kind == "room_tl"
+                            else po.OracleScene(self.verts, layers=self.layers))
+        return self._oracle.trace(rays, query_mask=query_mask, any_hit=any_hit)
+
+    def lit(self, rays, traced, query_mask=0xFFFFFFFF):
+        """the any-hit output: 1 - occluded, 1 for entries without a ray"""
+        occ = self.oracle(rays, query_mask, any_hit=True)["prim_id"] >= 0
+        return (~(traced & occ)).astype(np.uint8)
+
+
+SCENES = {}
+
+
+def scene(kind):
+    if kind not in SCENES:
+        SCENES[kind] = Scene(kind)
+    return SCENES[kind]
+
+
+def hit_point(rays, hits):
+    with np.errstate(over="ignore", invalid="ignore"):
+        return rays["origin"] + rays["direction"] * hits["t"][:, None]
+
+
+def same(a, b):
+    np.testing.assert_array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+class Dev:
+    """device buffers of one context, freed at the end"""
+
+    def __init__(self, ctx):
+        self.ctx, self.ptrs = ctx, []
+
+    def alloc(self, nbytes):
+        p = self.ctx.device_alloc(max(int(nbytes), 16))
+        self.ptrs.append(p)
+        return p
+
+    def put(self, arr):
+        p = self.alloc(arr.nbytes)
+        self.ctx.h2d(p, np.ascontiguousarray(arr))
+        return p
+
+    def get(self, p, n, dtype):
+        out = np.zeros(n, dtype=dtype)
+        self.ctx.d2h(out, p)
+        return out
+
+    def free(self):
+        for p in self.ptrs:
+            self.ctx.device_free(p)
+
+
+class Run:
+    """one context with the scene uploaded and the primary grid of rows [y0, y1) cast into device records"""
+
+    def __init__(self, kind, w, h, y0=0, y1=None, kernel=capi.KERNEL_AUTO):
+        self.sc, self.w, self.h, self.y0, self.y1 = scene(kind), w, h, y0, h if y1 is None else y1
+        self.ctx = capi.Context(0, kernel=kernel)
+        self.dev = Dev(self.ctx)
+        self.sc.upload(self.ctx)
+        origin, fwd, fov = self.sc.cam
+        self.cam = capi.camera_look(origin, fwd, w, h, fov)
+        self.n = w * (self.y1 - self.y0)
+        self.rays = po.grid_rays(origin, fwd, w, h, fov, self.y0, self.y1)
+        self.d_hits = self.dev.alloc(self.n * 32)
+        self.ctx.cast_grid(self.cam, w, h, y0=self.y0, y1=self.y1, hits=self.d_hits, flags=capi.FLAG_HITS_ON_DEVICE)
+        self.hits = self.dev.get(self.d_hits, self.n, T.HIT32)
+        assert (self.hits["prim_id"] != -1).any()
+
+    def close(self):
+        self.dev.free()
+        self.ctx.close()
+
+    def grid_cast(self, mode, samples=4, frame=3, first_draw=1, t_max=FAR, select=None, query_mask=0xFFFFFFFF, flags=0, rays_out=True):
+        """mrt_cast_grid_hemisphere: device pointers of the output and (closest-hit) the rays"""
+        any_hit = mode == capi.MODE_ANY_HIT
+        d_sel = self.dev.put(select.astype(np.uint8)) if select is not None else None
+        m = self.n * samples
+        d_out = self.dev.alloc(m * (1 if any_hit else 32))
+        d_orays = None if any_hit or not rays_out else self.dev.alloc(m * 32)
+        self.ctx.cast_grid_hemisphere(self.cam, self.w, self.h, self.d_hits, d_out, n_samples=samples, frame=frame, first_draw=first_draw,
+                                      t_max=t_max, mode=mode, d_select=d_sel, d_out_rays=d_orays, y0=self.y0, y1=self.y1,
+                                      query_mask=query_mask, flags=flags)
+        return d_out, d_orays
+
+    def expected(self, samples=4, frame=3, first_draw=1, t_max=FAR, select=None, grid=True):
+        """the restated rays (entry order), which entries have one, which pixels had their normal turned.  grid: the pixel index is
+        that of the whole grid; else the record's index (the array form)."""
+        pixel = np.arange(self.n, dtype=np.uint64) + (self.y0 * self.w if grid else 0)
+        return H.hemisphere_rays(self.rays["direction"], hit_point(self.rays, self.hits), self.hits["normal"],
+                                 self.hits["prim_id"] != -1, pixel, samples, frame, first_draw, t_max, select)
+
+
+def check_all_entry_points(kind, w, h, y0=0, y1=None, kernel=capi.KERNEL_AUTO, variant=None, samples=4):
+    """The grid form and the array form in both layouts on one grid of one scene, closest-hit and any-hit: rays, records and bytes against
+    the restated sampler traced by the oracle, byte for byte, and against mrt_cast(NEAREST) of the restated rays.  variant: a format
+    with the source and the mode for the kernel every cast must report."""
+    run = Run(kind, w, h, y0, y1, kernel)
+    ctx, dev, n, sc = run.ctx, run.dev, run.n, run.sc
+    m = n * samples
+    ao_radius = AO_RADIUS if kind != "soup" else F(3.0)
+
+    def named(src, any_hit):
+        if variant:
+            assert ctx.last_kernel_variant().startswith(variant % (src, "true" if any_hit else "false")), ctx.last_kernel_variant()
+
+    try:
+        for grid in (True, False):
+            want_rays, traced, flipped = run.expected(samples, grid=grid)
+            want = sc.oracle(want_rays)
+            ao_rays, ao_traced, _ = run.expected(samples, t_max=ao_radius, grid=grid)
+            want_lit = sc.lit(ao_rays, ao_traced)
+            assert traced.any() and (want["prim_id"][traced] != -1).any()
+            same(want[~traced], np.repeat(PLACEHOLDER_HIT, (~traced).sum()))
+            assert (want_lit[~ao_traced] == 1).all()
+            if kind == "soup":  # (the room is closed: every primary ray hits)
+                assert (~traced).any() and flipped.any()  # back faces: the normal was turned towards the incoming ray
+            else:
+                assert (want_lit == 0).any() and (want_lit == 1).any()   # an all-ones output cannot pass
+            if grid:
+                # (1) the grid: incoming rays regenerated in the kernel
+                d_out, d_orays = run.grid_cast(capi.MODE_NEAREST, samples)
+                named(9, False)
+                same(dev.get(d_orays, m, T.RAY32), want_rays)
+                same(dev.get(d_out, m, T.HIT32), want)
+                d_lit, _ = run.grid_cast(capi.MODE_ANY_HIT, samples, t_max=ao_radius)
+                named(9, True)
+                np.testing.assert_array_equal(dev.get(d_lit, m, np.uint8), want_lit)
+                continue
+            # (2) 32-byte records written by mrt_cast for the same rays
+            d_rays, d_h32 = dev.put(run.rays), dev.alloc(n * 32)
+            ctx.cast(d_rays, d_h32, count=n, flags=DEV)
+            d_out2, d_orays2, d_lit2 = dev.alloc(m * 32), dev.alloc(m * 32), dev.alloc(m)
+            ctx.cast_hemisphere(d_rays, d_h32, n, d_out2, n_samples=samples, frame=3, d_out_rays=d_orays2)
+            named(7, False)
+            same(dev.get(d_orays2, m, T.RAY32), want_rays)
+            same(dev.get(d_out2, m, T.HIT32), want)
+            ctx.cast_hemisphere(d_rays, d_h32, n, d_lit2, n_samples=samples, frame=3, t_max=ao_radius, mode=capi.MODE_ANY_HIT)
+            named(7, True)
+            np.testing.assert_array_equal(dev.get(d_lit2, m, np.uint8), want_lit)
+            # (3) the reference's host layout: Ray / Intersection records in, Ray / Intersection out
+            hrays = po.make_host_rays(run.rays)
+            d_hr, d_h44 = dev.put(hrays), dev.alloc(n * 44)
+            ctx.cast(d_hr, d_h44, count=n, flags=DEV | capi.FLAG_HOST_LAYOUT)
+            h44 = dev.get(d_h44, n, T.HOST_HIT44)
+            rays44, _, _ = H.hemisphere_rays(hrays["direction"], h44["position"], h44["normal"], h44["prim_id"] != T.NO_HIT,
+                                             np.arange(n), samples, 3, 1, FAR)
+            same(rays44, want_rays)  # the record's position is o + d * t too
+            d_out3, d_orays3, d_lit3 = dev.alloc(m * 44), dev.alloc(m * 60), dev.alloc(m)
+            ctx.cast_hemisphere(d_hr, d_h44, n, d_out3, n_samples=samples, frame=3, d_out_rays=d_orays3, flags=capi.FLAG_HOST_LAYOUT)
+            named(8, False)
+            host_want_rays = po.make_host_rays(want_rays)
+            same(dev.get(d_orays3, m, T.HOST_RAY60), host_want_rays)
+            same(dev.get(d_out3, m, T.HOST_HIT44), po.unpack_hits(want, host_want_rays))
+            ctx.cast_hemisphere(d_hr, d_h44, n, d_lit3, n_samples=samples, frame=3, t_max=ao_radius, mode=capi.MODE_ANY_HIT,
+                                flags=capi.FLAG_HOST_LAYOUT)
+            named(8, True)
+            np.testing.assert_array_equal(dev.get(d_lit3, m, np.uint8), want_lit)
+            # (4) the same rays uploaded and cast through mrt_cast(NEAREST)
+            d_rr, d_hr2 = dev.put(want_rays), dev.alloc(m * 32)
+            ctx.cast(d_rr, d_hr2, count=m, flags=DEV)
+            same(dev.get(d_hr2, m, T.HIT32), want)
+    finally:
+        run.close()
+
+
+GRIDS = [(128, 96, 0, 96), (100, 77, 0, 77), (128, 96, 20, 70)]   # 4 samples each: below 2^16 entries
+PLAIN = {"room": "trace_hemisphere_lane_kernel<%d, %s>", "room_tl": "trace_hemisphere_two_level_kernel<%d, %s>",
+         "soup": "trace_hemisphere_lane_kernel<%d, %s>"}
+
+
+@pytest.mark.parametrize("kind", ["soup", "room", "room_tl"])
+@pytest.mark.parametrize("grid", GRIDS, ids=["128x96", "100x77", "band"])
+def test_hemisphere_matches_the_oracle(built, kind, grid):
+    check_all_entry_points(kind, *grid, variant=PLAIN[kind])   # (below 2^16 entries: the plain kernels)
+
+
+@pytest.mark.parametrize("kind", ["room", "room_tl"])
+def test_large_batch_runs_the_persistent_kernels(built, kind):
+    """128 x 128 x 4 samples = 2^16 entries: the persistent kernels (8-wide; two-level: 8-wide BLASes), every source, both modes."""
+    check_all_entry_points(kind, 128, 128, variant="trace_hemisphere_persistent_kernel<%d, %s, 8, " + ("true>" if kind == "room_tl" else "false>"))
+
+
+@pytest.mark.parametrize("kernel, variant", [(capi.KERNEL_LANE, "trace_hemisphere_lane_kernel<%d, %s>"),
+                                             (capi.KERNEL_LANE4_PERSISTENT, "trace_hemisphere_persistent_kernel<%d, %s, 4, false>"),
+                                             (capi.KERNEL_LANE_PERSISTENT, "trace_hemisphere_persistent_kernel<%d, %s, 2, false>"),
+                                             (capi.KERNEL_PACKET_ASM, "trace_hemisphere_persistent_kernel<%d, %s, ")],
+                         ids=["lane", "lane4p", "lane2p", "packet"])
+def test_forced_kernels(built, kernel, variant):
+    """A forced kernel on 2^16 entries; a forced packet kernel falls back to the policy's lane kernel (persistent, of the width the
+    context's scene layouts allow)."""
+    check_all_entry_points("room", 128, 128, kernel=kernel, variant=variant)
+
+
+def test_forced_lane_kernel_two_level(built):
+    check_all_entry_points("room_tl", 128, 128, kernel=capi.KERNEL_LANE, variant="trace_hemisphere_two_level_kernel<%d, %s>")
+
+
+def test_a_row_band_draws_what_the_whole_frame_draws(built):
+    """The seed uses the whole-grid pixel index: the outputs of rows [20, 70) equal those rows of the whole frame's, sample by sample."""
+    whole, band = Run("room", 128, 96), Run("room", 128, 96, 20, 70)
+    try:
+        outs = []
+        for run in (whole, band):
+            d_out, d_orays = run.grid_cast(capi.MODE_NEAREST, 4)
+            d_lit, _ = run.grid_cast(capi.MODE_ANY_HIT, 4, t_max=AO_RADIUS)
+            m = run.n * 4
+            outs.append((run.dev.get(d_out, m, T.HIT32).reshape(4, -1), run.dev.get(d_orays, m, T.RAY32).reshape(4, -1),
+                         run.dev.get(d_lit, m, np.uint8).reshape(4, -1)))
+        rows = slice(20 * 128, 70 * 128)
+        for a, b in zip(outs[0], outs[1]):
+            same(a[:, rows], b)
+        assert (outs[1][2] == 0).any() and (outs[1][2] == 1).any()
+    finally:
+        whole.close()
+        band.close()
+
+
+@pytest.mark.parametrize("kind", ["room", "room_tl"])
+def test_sample_counts_frames_and_first_draws(built, kind):
+    run = Run(kind, 64, 48)
+    try:
+        seen = {}
+        for samples, frame, first_draw in ((1, 0, 1), (4, 0, 1), (16, 0, 1), (4, 1, 1), (4, 0, 0), (4, 5, 7)):
+            m = run.n * samples
+            want_rays, traced, _ = run.expected(samples, frame, first_draw)
+            d_out, d_orays = run.grid_cast(capi.MODE_NEAREST, samples, frame, first_draw)
+            got_rays = run.dev.get(d_orays, m, T.RAY32)
+            same(got_rays, want_rays)
+            same(run.dev.get(d_out, m, T.HIT32), run.sc.oracle(want_rays))
+            ao_rays, ao_traced, _ = run.expected(samples, frame, first_draw, t_max=AO_RADIUS)
+            d_lit, _ = run.grid_cast(capi.MODE_ANY_HIT, samples, frame, first_draw, t_max=AO_RADIUS)
+            np.testing.assert_array_equal(run.dev.get(d_lit, m, np.uint8), run.sc.lit(ao_rays, ao_traced))
+            seen[(samples, frame, first_draw)] = got_rays
+        n = run.n
+        same(seen[(16, 0, 1)][:4 * n], seen[(4, 0, 1)])      # the first samples of a longer cast are the shorter cast's
+        same(seen[(4, 0, 1)][:n], seen[(1, 0, 1)])
+        assert (seen[(4, 0, 1)]["direction"] != seen[(4, 1, 1)]["direction"]).any(axis=1).mean() > 0.99   # another frame: other rays
+        assert (seen[(4, 0, 1)]["direction"] != seen[(4, 0, 0)]["direction"]).any(axis=1).mean() > 0.99   # another first draw too
+        same(seen[(4, 0, 1)]["origin"], seen[(4, 1, 1)]["origin"])
+    finally:
+        run.close()
+
+
+@pytest.mark.parametrize("kind", ["room", "room_tl"])
+@pytest.mark.parametrize("size", [(64, 48), (128, 128)], ids=["plain", "persistent"])
+def test_selection_masks(built, kind, size):
+    """A seeded random mask and an all-zero one: unselected pixels hold the placeholder's record and ray (closest-hit), 1 (any-hit)."""
+    w, h = size
+    run = Run(kind, w, h)
+    try:
+        rng = np.random.default_rng(7)
+        m = run.n * 4
+        for sel in (rng.random(run.n) < 0.4, np.zeros(run.n, dtype=bool)):
+            want_rays, traced, _ = run.expected(4, select=sel)
+            want = run.sc.oracle(want_rays)
+            d_out, d_orays = run.grid_cast(capi.MODE_NEAREST, 4, select=sel)
+            same(run.dev.get(d_orays, m, T.RAY32), want_rays)
+            same(run.dev.get(d_out, m, T.HIT32), want)
+            same(want[~traced], np.repeat(PLACEHOLDER_HIT, (~traced).sum()))
+            assert not traced[~np.tile(sel, 4)].any()
+            ao_rays, ao_traced, _ = run.expected(4, t_max=AO_RADIUS, select=sel)
+            d_lit, _ = run.grid_cast(capi.MODE_ANY_HIT, 4, t_max=AO_RADIUS, select=sel)
+            np.testing.assert_array_equal(run.dev.get(d_lit, m, np.uint8), run.sc.lit(ao_rays, ao_traced))
+            # the array form in the host layout with the same mask
+            hrays = po.make_host_rays(run.rays)
+            d_hr, d_h44 = run.dev.put(hrays), run.dev.alloc(run.n * 44)
+            run.ctx.cast(d_hr, d_h44, count=run.n, flags=DEV | capi.FLAG_HOST_LAYOUT)
+            d_out3 = run.dev.alloc(m * 44)
+            run.ctx.cast_hemisphere(d_hr, d_h44, run.n, d_out3, n_samples=4, frame=3, d_select=run.dev.put(sel.astype(np.uint8)),
+                                    flags=capi.FLAG_HOST_LAYOUT)
+            same(run.dev.get(d_out3, m, T.HOST_HIT44), po.unpack_hits(want, po.make_host_rays(want_rays)))
+        assert not traced.any()
+    finally:
+        run.close()
+
+
+@pytest.mark.parametrize("kind", ["room", "room_tl"])
+def test_query_mask_leaves_the_walls_out(built, kind):
+    run = Run(kind, 128, 96)
+    try:
+        m = run.n * 4
+        want_rays, traced, _ = run.expected(4)
+        want_all, want_obj = run.sc.oracle(want_rays), run.sc.oracle(want_rays, 1)
+        assert (want_obj["prim_id"] != want_all["prim_id"]).any() and (want_obj["prim_id"] != -1).any()   # (walls: layer 2)
+        d_out, _ = run.grid_cast(capi.MODE_NEAREST, 4, query_mask=1)
+        same(run.dev.get(d_out, m, T.HIT32), want_obj)
+        ao_rays, ao_traced, _ = run.expected(4, t_max=AO_RADIUS)
+        lit_all, lit_obj = run.sc.lit(ao_rays, ao_traced), run.sc.lit(ao_rays, ao_traced, 1)
+        assert (lit_all != lit_obj).any() and (lit_obj == 0).any()
+        d_lit, _ = run.grid_cast(capi.MODE_ANY_HIT, 4, t_max=AO_RADIUS, query_mask=1)
+        np.testing.assert_array_equal(run.dev.get(d_lit, m, np.uint8), lit_obj)
+    finally:
+        run.close()
+
+
+def shadow_mask(sc, rays, hits, lights):
+    """The shadow formula of include/mrt_hip.h for a point light and a directional one (as test_shadow_gpu.py restates it), traced by
+    the oracle: 1 lit, 0 shadowed, light-major."""
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        hit = hits["prim_id"] != -1
+        org = hit_point(rays, hits) + hits["normal"] * F(1e-3)
+        out = []
+        for L in lights:
+            s = np.zeros(rays.shape[0], dtype=T.RAY32)
+            s["origin"] = org
+            if L["type"] == T.LIGHT_DIRECTIONAL:
+                s["direction"], s["t_max"], ok = L["direction"].astype(F), F(1000.0), hit
+            else:
+                to = L["position"].astype(F)[None, :] - org
+                dist = np.sqrt((to[:, 0] * to[:, 0] + to[:, 1] * to[:, 1]) + to[:, 2] * to[:, 2])
+                s["direction"], s["t_max"], ok = to / dist[:, None], dist, hit & ~(dist < F(1e-6))
+            s[~ok] = H.PLACEHOLDER[0]
+            occ = sc.oracle(s, any_hit=True)["prim_id"] >= 0
+            out.append((~(ok & occ)).astype(np.uint8))
+    return np.concatenate(out)
+
+
+@pytest.mark.parametrize("kind", ["room", "room_tl"])
+def test_chained_shadows_and_second_bounce(built, kind):
+    """A path tracer's loop: primary, bounce, shadows at the bounce's hits, second bounce from the first one's records and rays."""
+    run = Run(kind, 96, 72)
+    ctx, dev, n, sc = run.ctx, run.dev, run.n, run.sc
+    try:
+        m = n * 2
+        rays1, traced1, _ = run.expected(2)
+        hits1 = sc.oracle(rays1)
+        d_out, d_orays = run.grid_cast(capi.MODE_NEAREST, 2)
+        same(dev.get(d_out, m, T.HIT32), hits1)
+        lights = np.zeros(2, dtype=T.LIGHT)
+        lights["cast_shadows"] = 1
+        lights[0]["type"], lights[0]["position"] = T.LIGHT_POINT, (1.0, 4.5, 1.5)
+        lights[1]["type"], lights[1]["direction"] = T.LIGHT_DIRECTIONAL, (0.3, 1.0, 0.2)
+        want_mask = shadow_mask(sc, rays1, hits1, lights)
+        assert want_mask.min() == 0 and want_mask.max() == 1
+        d_mask = dev.alloc(2 * m)
+        ctx.cast_shadows(d_orays, d_out, m, lights, d_mask)
+        np.testing.assert_array_equal(dev.get(d_mask, 2 * m, np.uint8), want_mask)
+        # the second bounce: the first one's m records are the pixels of an array-form cast (draws 3 and 4 of record i's stream)
+        rays2, traced2, _ = H.hemisphere_rays(rays1["direction"], hit_point(rays1, hits1), hits1["normal"], hits1["prim_id"] != -1,
+                                              np.arange(m), 1, 3, 3, FAR)
+        hits2 = sc.oracle(rays2)
+        assert traced2.any() and (hits2["prim_id"] != -1).any()
+        d_out2, d_orays2 = dev.alloc(m * 32), dev.alloc(m * 32)
+        ctx.cast_hemisphere(d_orays, d_out, m, d_out2, n_samples=1, frame=3, first_draw=3, d_out_rays=d_orays2)
+        same(dev.get(d_orays2, m, T.RAY32), rays2)
+        same(dev.get(d_out2, m, T.HIT32), hits2)
+        # ambient occlusion at the first bounce's hits
+        ao2, ao_traced2, _ = H.hemisphere_rays(rays1["direction"], hit_point(rays1, hits1), hits1["normal"], hits1["prim_id"] != -1,
+                                               np.arange(m), 2, 3, 1, AO_RADIUS)
+        d_lit = dev.alloc(2 * m)
+        ctx.cast_hemisphere(d_orays, d_out, m, d_lit, n_samples=2, frame=3, t_max=AO_RADIUS, mode=capi.MODE_ANY_HIT)
+        np.testing.assert_array_equal(dev.get(d_lit, 2 * m, np.uint8), sc.lit(ao2, ao_traced2))
+        # the same chain in the host layout
+        hrays = po.make_host_rays(run.rays)
+        d_hr, d_h44 = dev.put(hrays), dev.alloc(n * 44)
+        ctx.cast(d_hr, d_h44, count=n, flags=DEV | capi.FLAG_HOST_LAYOUT)
+        rays1a, _, _ = run.expected(2, grid=False)
+        hits1a = sc.oracle(rays1a)
+        d_o44, d_or60 = dev.alloc(m * 44), dev.alloc(m * 60)
+        ctx.cast_hemisphere(d_hr, d_h44, n, d_o44, n_samples=2, frame=3, d_out_rays=d_or60, flags=capi.FLAG_HOST_LAYOUT)
+        d_mask44 = dev.alloc(2 * m)
+        ctx.cast_shadows(d_or60, d_o44, m, lights, d_mask44, flags=capi.FLAG_HOST_LAYOUT)
+        np.testing.assert_array_equal(dev.get(d_mask44, 2 * m, np.uint8), shadow_mask(sc, rays1a, hits1a, lights))
+        rays2a, _, _ = H.hemisphere_rays(rays1a["direction"], hit_point(rays1a, hits1a), hits1a["normal"], hits1a["prim_id"] != -1,
+                                         np.arange(m), 1, 3, 3, FAR)
+        d_o44b = dev.alloc(m * 44)
+        ctx.cast_hemisphere(d_or60, d_o44, m, d_o44b, n_samples=1, frame=3, first_draw=3, flags=capi.FLAG_HOST_LAYOUT)
+        same(dev.get(d_o44b, m, T.HOST_HIT44), po.unpack_hits(sc.oracle(rays2a), po.make_host_rays(rays2a)))
+    finally:
+        run.close()
+
+
+def test_async_grid_then_async_hemisphere(built):
+    run = Run("room", 160, 120)
+    ctx, dev, n = run.ctx, run.dev, run.n
+    try:
+        m = n * 2
+        want_rays, _, _ = run.expected(2)
+        want = run.sc.oracle(want_rays)
+        ao_rays, ao_traced, _ = run.expected(2, t_max=AO_RADIUS, grid=False)
+        d_hits2, d_out, d_lit = dev.alloc(n * 32), dev.alloc(m * 32), dev.alloc(m)
+        ctx.cast_grid(run.cam, run.w, run.h, hits=d_hits2, flags=capi.FLAG_HITS_ON_DEVICE | capi.FLAG_ASYNC)
+        ctx.cast_grid_hemisphere(run.cam, run.w, run.h, d_hits2, d_out, n_samples=2, frame=3, flags=capi.FLAG_ASYNC)
+        d_rays = dev.put(run.rays)
+        ctx.cast_hemisphere(d_rays, d_hits2, n, d_lit, n_samples=2, frame=3, t_max=AO_RADIUS, mode=capi.MODE_ANY_HIT, flags=capi.FLAG_ASYNC)
+        ctx.synchronize()
+        same(dev.get(d_out, m, T.HIT32), want)
+        np.testing.assert_array_equal(dev.get(d_lit, m, np.uint8), run.sc.lit(ao_rays, ao_traced))
+    finally:
+        run.close()
+
+
+def test_primary_grid_unaffected_by_hemisphere_casts(built):
+    """A renderer's frames: the primary grid (scheduled from the second frame on: 2^17 rays and more) with and without hemisphere
+    casts between frames -- the same kernel sequence, the same records."""
+    sc = scene("room")
+    w, h = 640, 480
+    runs = []
+    for hemisphere in (False, True):
+        ctx = capi.Context(0)
+        dev = Dev(ctx)
+        try:
+            sc.upload(ctx)
+            cam = capi.camera_look(sc.cam[0], sc.cam[1], w, h, sc.cam[2])
+            kernels, records = [], []
+            d_hits, d_out, d_lit = dev.alloc(w * h * 32), dev.alloc(w * h * 32), dev.alloc(w * h * 2)
+            for f in range(14):
+                ctx.cast_grid(cam, w, h, hits=d_hits, flags=capi.FLAG_HITS_ON_DEVICE)
+                kernels.append((ctx.stats()["last_kernel"], ctx.last_kernel_variant()))
+                records.append(dev.get(d_hits, w * h, T.HIT32).view(np.uint32))
+                if hemisphere and f & 1:
+                    ctx.cast_grid_hemisphere(cam, w, h, d_hits, d_out, n_samples=1, frame=f)
+                elif hemisphere:
+                    ctx.cast_grid_hemisphere(cam, w, h, d_hits, d_lit, n_samples=2, frame=f, t_max=AO_RADIUS, mode=capi.MODE_ANY_HIT)
+            runs.append((kernels, records))
+        finally:
+            dev.free()
+            ctx.close()
+    assert runs[0][0] == runs[1][0]
+    for a, b in zip(runs[0][1], runs[1][1]):
+        np.testing.assert_array_equal(a, b)
+
+
+def test_errors(built):
+    L = capi.load()
+    sc = scene("room")
+    ctx = capi.Context(0)
+    dev = Dev(ctx)
+    try:
+        w, h = 64, 48
+        n = w * h
+        cam = capi.camera_look(sc.cam[0], sc.cam[1], w, h, sc.cam[2])
+        d_rays, d_hits, d_out, d_orays = dev.alloc(n * 60), dev.alloc(n * 44), dev.alloc(n * 2 * 44), dev.alloc(n * 2 * 60)
+        R, Hp, O, OR = C.c_void_p(d_rays), C.c_void_p(d_hits), C.c_void_p(d_out), C.c_void_p(d_orays)
+        pattern = np.full(n * 2 * 44, 7, np.uint8)
+        ctx.h2d(d_out, pattern)
+        NEAR, ANY = capi.MODE_NEAREST, capi.MODE_ANY_HIT
+
+        def desc(samples=2, t_max=10.0):
+            return capi.Hemisphere(samples, 0, 1, t_max, None)
+
+        def arr(rays=R, hits=Hp, count=n, d=None, out=O, orays=None, mode=NEAR, flags=0, no_desc=False):
+            d = desc() if d is None else d
+            return L.mrt_cast_hemisphere(ctx.h, rays, hits, count, None if no_desc else C.byref(d), out, orays, 0xFFFFFFFF, mode, flags)
+
+        def grid(hits=Hp, d=None, out=O, orays=None, mode=NEAR, flags=0, camera=cam, y0=0, y1=h, no_desc=False):
+            d = desc() if d is None else d
+            return L.mrt_cast_grid_hemisphere(ctx.h, C.byref(camera) if camera is not None else None, w, h, y0, y1, hits,
+                                              None if no_desc else C.byref(d), out, orays, 0xFFFFFFFF, mode, flags)
+
+        def bad_calls():
+            common = [dict(hits=None), dict(out=None), dict(no_desc=True), dict(mode=2), dict(mode=-1), dict(mode=ANY, orays=OR)]
+            common += [dict(d=desc(samples=s)) for s in (0, 17)]
+            common += [dict(d=desc(t_max=t)) for t in (float("nan"), float("inf"), -float("inf"), 1e-4, 0.0, -1.0)]
+            for kw in common + [dict(rays=None)]:
+                assert arr(**kw) == capi.ERR_INVALID, kw
+            for kw in common + [dict(camera=None), dict(y0=10, y1=5), dict(y1=h + 1), dict(flags=capi.FLAG_HOST_LAYOUT)]:
+                assert grid(**kw) == capi.ERR_INVALID, kw
+            for f in (capi.FLAG_BOOL_OUT, capi.FLAG_TOKEN_OUT, capi.FLAG_COHERENT, capi.FLAG_FORCE_SORT, 1 << 20):
+                assert arr(flags=f) == capi.ERR_INVALID and grid(flags=f) == capi.ERR_INVALID, f
+
+        bad_calls()   # before a scene is uploaded: the arguments are checked first
+        assert arr() == capi.ERR_NO_SCENE and grid() == capi.ERR_NO_SCENE and arr(mode=ANY) == capi.ERR_NO_SCENE
+        assert arr(count=0) == capi.ERR_NO_SCENE
+        sc.upload(ctx)
+        bad_calls()
+        assert arr(count=0) == capi.MRT_OK  # nothing to do
+        assert (dev.get(d_out, n * 2 * 44, np.uint8) == 7).all()  # no call so far wrote anything
+        ctx.cast_grid(cam, w, h, hits=d_hits, flags=capi.FLAG_HITS_ON_DEVICE)
+        assert grid() == capi.MRT_OK and grid(y0=10, y1=10) == capi.MRT_OK and grid(mode=ANY) == capi.MRT_OK
+        assert grid(orays=OR) == capi.MRT_OK and grid(d=desc(samples=1, t_max=1.0001e-4)) == capi.MRT_OK
+        d = desc()
+        assert L.mrt_cast_hemisphere(None, R, Hp, n, C.byref(d), O, None, 0xFFFFFFFF, NEAR, 0) == capi.ERR_INVALID
+        assert L.mrt_cast_grid_hemisphere(None, C.byref(cam), w, h, 0, h, Hp, C.byref(d), O, None, 0xFFFFFFFF, NEAR, 0) == capi.ERR_INVALID
+    finally:
+        dev.free()
+        ctx.close()
