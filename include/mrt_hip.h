@@ -453,6 +453,63 @@ int mrt_two_level_prepare_host(const float *verts9, uint32_t n_mesh_tris, const 
 int mrt_two_level_host_arrays(const mrt_two_level_host *h, mrt_two_level_arrays *out);
 void mrt_two_level_free_host(mrt_two_level_host *h);
 
+/* The prepared FLAT scene on the host: exactly the arrays mrt_upload_scene uploads for these arguments (with the 8-wide layout, which
+ * an upload makes for the kernels that walk it), in the layouts described under mrt_debug_snapshot below.  nodes8 / leaf_box are
+ * NULL when a box fits no 8-bit grid (non-finite extent).  Host-only: no device, no context.  Errors as mrt_upload_scene. */
+typedef struct mrt_scene_host mrt_scene_host;
+typedef struct mrt_flat_scene_arrays {
+	const mrt_bvh_node_wide64 *nodes; uint32_t n_nodes;
+	const float *tri_hot, *tri_cold; uint32_t n_tris;
+	const void *nodes4; uint32_t n_nodes4, stack4;
+	const void *nodes8; uint32_t n_nodes8, stack8;
+	const float *leaf_box;
+	uint32_t depth;
+	float bounds_lo[3], bounds_hi[3];
+} mrt_flat_scene_arrays;
+int mrt_scene_prepare_host(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *nodes, uint32_t used_nodes,
+		const uint32_t *prim_idx, mrt_scene_host **out);
+int mrt_scene_host_arrays(const mrt_scene_host *h, mrt_flat_scene_arrays *out);
+void mrt_scene_free_host(mrt_scene_host *h);
+
+/* ---- debug: the RESIDENT scene's arrays copied to the host as they stand, for a validator (tests/layout_check.py).  Read-only: no
+ * state of the context changes (no allocation, no tuner / schedule / counter state); never called from a cast path.
+ * buffers == NULL: the query form, only *info is filled.  Otherwise buffers[MRT_SNAP_COUNT]: buffers[a] (may be NULL: skipped)
+ * receives info->count[a] elements of info->elem_bytes[a] bytes each, by device-to-host copies on the context's stream, then one
+ * wait.  count[a] == 0: the scene has no such array.  info->struct_size must be set by the caller.  MRT_ERR_PENDING with a dispatch
+ * pending, MRT_ERR_NO_SCENE without a scene.  Layouts (little-endian 32-bit words; nodes, tri_hot, tri_cold, instances as
+ * mrt_two_level_arrays above, inner nodes also carrying left_count / right_count in the last word of their third and fourth quarter:
+ * triangles in a leaf child, 0 for an inner child; a wrapped root leaf -- a scene of one leaf -- is one node whose two sides halve the
+ * leaf's run, or name the same one-triangle run twice):
+ *   NODES4    128-byte rows {4 x {min xyz, max xyz} | 4 refs | n_children, 3 unused}: refs in the node encoding with 4-wide indices,
+ *             unused slots 0x7FFFFFFF with boxes at +inf.  Compact (host upload: node 0 the root, every row reachable) or at binary
+ *             indices (device builds, after a refit: row b is the collapse rooted at binary node b; only rows reachable from 0 are read)
+ *   NODES8    128-byte rows {org xyz | exp[3], n_children | qlo[3][8] | qhi[3][8] | 8 refs | 8 unused}: child box on axis a =
+ *             [fma(qlo, 2^(exp - 127), org), fma(qhi, 2^(exp - 127), org)], containing the exact box.  Flat scenes as NODES4; two-level
+ *             scenes hold every BLAS's rows (instance row word 26 = its BLAS's 8-wide root)
+ *   LEAF_BOX  32-byte rows {min xyz, -, max xyz, -}, written at the FIRST slot of every leaf (other rows undefined): the exact leaf box
+ *   SLOT_SRC  u32 per slot: the input triangle the slot holds (two-level scenes, after a refit: BLAS slot base + mesh-local id)
+ *   PARENT    u32 per node (two-level: per node from tlas_cap), after a refit: the parent's index (two-level: minus tlas_cap), bit 31
+ *             set for a right child; 0xFFFFFFFF for a root
+ *   ROWS      64-byte rows: the n_nodes nodes with leaf refs rebased (0x80000000 | (n_nodes + slot)), then per slot
+ *             {v0, id | e1, layers | e2, flags | normal, -}
+ *   ROWS4     64-byte units: per 4-wide node two units {per child: min x, max x, min y, max y, min z, max z | 4 refs (inner: 2 * index,
+ *             leaf: 0x80000000 | (2 * n_nodes4 + slot)) | n_children, 3 zero}, then the triangle rows of ROWS */
+enum { MRT_SNAP_NODES = 0, MRT_SNAP_TRI_HOT, MRT_SNAP_TRI_COLD, MRT_SNAP_NODES4, MRT_SNAP_NODES8, MRT_SNAP_LEAF_BOX, MRT_SNAP_SLOT_SRC,
+	MRT_SNAP_PARENT, MRT_SNAP_ROWS, MRT_SNAP_ROWS4, MRT_SNAP_INSTANCES, MRT_SNAP_COUNT };
+typedef struct mrt_debug_snapshot_info {
+	uint32_t struct_size;       /* = sizeof(mrt_debug_snapshot_info) */
+	uint32_t two_level;         /* 0 flat scene, 1 two-level scene */
+	uint32_t n_nodes, n_tris, n_nodes4, n_nodes8;
+	uint32_t depth;             /* stack entries one ray can need (mrt_scene_info's bvh_depth) */
+	uint32_t stack_depth;       /* LDS stack entries per lane the casts launch with */
+	uint32_t stack4, stack8;    /* stack bounds of the 4- and 8-wide walks */
+	uint32_t n_tlas_nodes, tlas_cap, n_instances; /* two-level: TLAS rows in use, rows reserved for it (BLAS rows start there) */
+	float bounds_lo[3], bounds_hi[3], scene_abs_max;
+	uint32_t elem_bytes[MRT_SNAP_COUNT];
+	uint64_t count[MRT_SNAP_COUNT];
+} mrt_debug_snapshot_info;
+int mrt_debug_snapshot(mrt_ctx *ctx, mrt_debug_snapshot_info *info, void *const *buffers);
+
 int mrt_is_available(const mrt_ctx *ctx);      /* initialized && scene uploaded */
 int mrt_scene_info(const mrt_ctx *ctx, uint32_t *n_tris, uint32_t *n_wide_nodes, uint32_t *bvh_depth);
 

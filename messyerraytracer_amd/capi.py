@@ -29,7 +29,7 @@ KERNEL_TWO_LEVEL, KERNEL_TWO_LEVEL_PACKET, KERNEL_TWO_LEVEL_PERSISTENT, KERNEL_T
 SYMBOLS = [
     "mrt_create", "mrt_destroy", "mrt_last_error", "mrt_status_string", "mrt_version", "mrt_set_stream",
     "mrt_synchronize", "mrt_make_triangles", "mrt_pack_host_triangles", "mrt_bvh2_build", "mrt_bvh2_save", "mrt_bvh2_load", "mrt_upload_scene",
-    "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_update_instances_device", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
+    "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_update_instances_device", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_scene_prepare_host", "mrt_scene_host_arrays", "mrt_scene_free_host", "mrt_debug_snapshot", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
     "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
@@ -76,6 +76,33 @@ class Stats(C.Structure):
                 ("fetch_wait_cycles", C.c_uint64), ("wave_cycles", C.c_uint64), ("waves", C.c_uint64)]
 
 
+class TwoLevelArrays(C.Structure):
+    """mrt_two_level_arrays"""
+    _fields_ = [("nodes", C.c_void_p), ("n_nodes", C.c_uint32), ("n_tlas_nodes", C.c_uint32),
+                ("tri_hot", C.c_void_p), ("tri_cold", C.c_void_p), ("n_tris", C.c_uint32),
+                ("instances", C.c_void_p), ("n_instances", C.c_uint32), ("depth", C.c_uint32)]
+
+
+class SceneHostArrays(C.Structure):
+    """mrt_flat_scene_arrays"""
+    _fields_ = [("nodes", C.c_void_p), ("n_nodes", C.c_uint32), ("tri_hot", C.c_void_p), ("tri_cold", C.c_void_p), ("n_tris", C.c_uint32),
+                ("nodes4", C.c_void_p), ("n_nodes4", C.c_uint32), ("stack4", C.c_uint32),
+                ("nodes8", C.c_void_p), ("n_nodes8", C.c_uint32), ("stack8", C.c_uint32), ("leaf_box", C.c_void_p),
+                ("depth", C.c_uint32), ("bounds_lo", C.c_float * 3), ("bounds_hi", C.c_float * 3)]
+
+
+SNAP_COUNT = len(T.SNAPSHOT_ARRAYS)
+
+
+class SnapshotInfo(C.Structure):
+    """mrt_debug_snapshot_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("two_level", C.c_uint32), ("n_nodes", C.c_uint32), ("n_tris", C.c_uint32),
+                ("n_nodes4", C.c_uint32), ("n_nodes8", C.c_uint32), ("depth", C.c_uint32), ("stack_depth", C.c_uint32),
+                ("stack4", C.c_uint32), ("stack8", C.c_uint32), ("n_tlas_nodes", C.c_uint32), ("tlas_cap", C.c_uint32),
+                ("n_instances", C.c_uint32), ("bounds_lo", C.c_float * 3), ("bounds_hi", C.c_float * 3), ("scene_abs_max", C.c_float),
+                ("elem_bytes", C.c_uint32 * SNAP_COUNT), ("count", C.c_uint64 * SNAP_COUNT)]
+
+
 _lib = None
 
 
@@ -120,6 +147,15 @@ def load():
     L.mrt_upload_two_level_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_update_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.mrt_update_instances_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.mrt_two_level_prepare_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.mrt_two_level_host_arrays.argtypes = [C.c_void_p, C.POINTER(TwoLevelArrays)]
+    L.mrt_two_level_free_host.argtypes = [C.c_void_p]
+    L.mrt_two_level_free_host.restype = None
+    L.mrt_scene_prepare_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.mrt_scene_host_arrays.argtypes = [C.c_void_p, C.POINTER(SceneHostArrays)]
+    L.mrt_scene_free_host.argtypes = [C.c_void_p]
+    L.mrt_scene_free_host.restype = None
+    L.mrt_debug_snapshot.argtypes = [C.c_void_p, C.POINTER(SnapshotInfo), C.POINTER(C.c_void_p)]
     L.mrt_is_available.argtypes = [C.c_void_p]
     L.mrt_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.mrt_cast.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32]
@@ -242,6 +278,66 @@ def bvh2_load(path: str, n_tris: int):
     if rc:
         raise MrtError(rc, "mrt_bvh2_load")
     return nodes[:used.value].copy(), prim_idx, used.value
+
+
+def _copy_rows(ptr, count, dtype):
+    """count rows of dtype at a host pointer, copied into a numpy array (None for a null pointer)"""
+    if not ptr:
+        return None
+    dtype = np.dtype(dtype)
+    if count == 0:
+        return np.zeros((0,) + dtype.shape, dtype=dtype.base)
+    buf = (C.c_char * (count * dtype.itemsize)).from_address(ptr)
+    return np.frombuffer(buf, dtype=dtype.base).reshape((count,) + dtype.shape).copy()
+
+
+def prepare_scene_host(tris, nodes, prim_idx) -> dict:
+    """mrt_scene_prepare_host: the arrays upload_scene would upload (8-wide layout included), as numpy copies.  No device."""
+    tris = np.ascontiguousarray(tris)
+    nodes = np.ascontiguousarray(nodes)
+    prim_idx = np.ascontiguousarray(prim_idx, dtype=np.uint32)
+    assert tris.dtype == T.TRI64 and nodes.dtype == T.NODE32
+    L = load()
+    h = C.c_void_p()
+    rc = L.mrt_scene_prepare_host(_np(tris), tris.shape[0], _np(nodes), nodes.shape[0], _np(prim_idx), C.byref(h))
+    if rc:
+        raise MrtError(rc, "mrt_scene_prepare_host")
+    try:
+        a = SceneHostArrays()
+        rc = L.mrt_scene_host_arrays(h, C.byref(a))
+        if rc:
+            raise MrtError(rc, "mrt_scene_host_arrays")
+        return dict(two_level=0, n_nodes=a.n_nodes, n_tris=a.n_tris, n_nodes4=a.n_nodes4, n_nodes8=a.n_nodes8, depth=a.depth,
+                    stack4=a.stack4, stack8=a.stack8, bounds_lo=np.array(a.bounds_lo[:], np.float32), bounds_hi=np.array(a.bounds_hi[:], np.float32),
+                    nodes=_copy_rows(a.nodes, a.n_nodes, T.WIDE64), tri_hot=_copy_rows(a.tri_hot, a.n_tris, T.TRI_HOT),
+                    tri_cold=_copy_rows(a.tri_cold, a.n_tris, T.TRI_COLD), nodes4=_copy_rows(a.nodes4, a.n_nodes4, T.NODE4),
+                    nodes8=_copy_rows(a.nodes8, a.n_nodes8, T.NODE8), leaf_box=_copy_rows(a.leaf_box, a.n_tris, np.dtype(("<f4", 8))),
+                    slot_src=prim_idx.copy())
+    finally:
+        L.mrt_scene_free_host(h)
+
+
+def two_level_prepare_host(verts9, instances, n_threads: int = 1) -> dict:
+    """mrt_two_level_prepare_host + mrt_two_level_host_arrays: the arrays upload_two_level_scene uploads, as numpy copies.  No device."""
+    verts9 = np.ascontiguousarray(verts9, dtype=np.float32)
+    instances = np.ascontiguousarray(instances)
+    assert instances.dtype == T.INSTANCE
+    L = load()
+    h = C.c_void_p()
+    rc = L.mrt_two_level_prepare_host(_np(verts9), verts9.size // 9, _np(instances), instances.shape[0], n_threads, C.byref(h))
+    if rc:
+        raise MrtError(rc, "mrt_two_level_prepare_host")
+    try:
+        a = TwoLevelArrays()
+        rc = L.mrt_two_level_host_arrays(h, C.byref(a))
+        if rc:
+            raise MrtError(rc, "mrt_two_level_host_arrays")
+        return dict(two_level=1, n_nodes=a.n_nodes, n_tlas_nodes=a.n_tlas_nodes, tlas_cap=2 * a.n_instances, n_tris=a.n_tris,
+                    n_instances=a.n_instances, depth=a.depth, nodes=_copy_rows(a.nodes, a.n_nodes, T.WIDE64),
+                    tri_hot=_copy_rows(a.tri_hot, a.n_tris, T.TRI_HOT), tri_cold=_copy_rows(a.tri_cold, a.n_tris, T.TRI_COLD),
+                    instances=_copy_rows(a.instances, a.n_instances, T.DEV_INSTANCE))
+    finally:
+        L.mrt_two_level_free_host(h)
 
 
 def kernel_available(kernel_id: int) -> bool:
@@ -423,6 +519,28 @@ class Context:
 
     def is_available(self) -> bool:
         return bool(self.L.mrt_is_available(self.h))
+
+    def debug_snapshot(self, arrays=True) -> dict:
+        """mrt_debug_snapshot: the scalars of the resident scene and (arrays=True) every array it has, copied to numpy arrays named
+        as types.SNAPSHOT_ARRAYS; an array the scene does not have is None.  Reads only."""
+        info = SnapshotInfo()
+        info.struct_size = C.sizeof(SnapshotInfo)
+        self._chk(self.L.mrt_debug_snapshot(self.h, C.byref(info), None))
+        out = {k: getattr(info, k) for k, _ in SnapshotInfo._fields_[1:13]}
+        out["bounds_lo"] = np.array(info.bounds_lo[:], np.float32)
+        out["bounds_hi"] = np.array(info.bounds_hi[:], np.float32)
+        out["scene_abs_max"] = np.float32(info.scene_abs_max)
+        out["counts"] = {name: int(info.count[a]) for a, (name, _) in enumerate(T.SNAPSHOT_ARRAYS)}
+        if not arrays:
+            return out
+        bufs = (C.c_void_p * SNAP_COUNT)()
+        for a, (name, dt) in enumerate(T.SNAPSHOT_ARRAYS):
+            n = int(info.count[a])
+            assert info.elem_bytes[a] == dt.itemsize, name
+            out[name] = np.zeros((n,) + dt.shape, dtype=dt.base) if n else None
+            bufs[a] = out[name].ctypes.data if n else None
+        self._chk(self.L.mrt_debug_snapshot(self.h, C.byref(info), bufs))
+        return out
 
     def scene_info(self):
         a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()

@@ -633,6 +633,41 @@ int mrt_scene_info(const mrt_ctx *ctx, uint32_t *n_tris, uint32_t *n_wide_nodes,
 	return MRT_OK;
 }
 
+// The resident scene's arrays as they stand, for a validator on the host (include/mrt_hip.h).  Reads only: plain copies on the
+// context's stream into the caller's buffers, one wait at the end; no allocation, no tuner, schedule or counter state touched.
+int mrt_debug_snapshot(mrt_ctx *ctx, mrt_debug_snapshot_info *info, void *const *buffers)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (!info || info->struct_size != sizeof(mrt_debug_snapshot_info)) return fail(ctx, MRT_ERR_INVALID, "debug_snapshot: null info or bad struct_size");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "debug_snapshot: collect the pending dispatch first");
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "debug_snapshot: no scene uploaded");
+	const mrt::TwoLevelHost *tl = ctx->two_level;
+	std::memset(info, 0, sizeof(*info));
+	info->struct_size = sizeof(*info);
+	info->two_level = tl ? 1u : 0u;
+	info->n_nodes = ctx->n_nodes; info->n_tris = ctx->n_tris; info->n_nodes4 = ctx->d_nodes4 ? ctx->n_nodes4 : 0u; info->n_nodes8 = ctx->d_nodes8 ? ctx->n_nodes8 : 0u;
+	info->depth = ctx->depth; info->stack_depth = ctx->stack_depth; info->stack4 = ctx->stack4; info->stack8 = ctx->stack8;
+	info->n_tlas_nodes = tl ? tl->n_tlas_nodes : 0u; info->tlas_cap = tl ? tl->tlas_cap : 0u; info->n_instances = tl ? tl->n_inst : 0u;
+	for (int c = 0; c < 3; c++) {
+		info->bounds_lo[c] = ctx->bounds_lo[c]; info->bounds_hi[c] = ctx->bounds_hi[c];
+		info->scene_abs_max = std::fmax(info->scene_abs_max, std::fmax(std::fabs(ctx->bounds_lo[c]), std::fabs(ctx->bounds_hi[c])));
+	}
+	const void *src[MRT_SNAP_COUNT] = { ctx->d_nodes, ctx->d_hot, ctx->d_cold, ctx->d_nodes4, ctx->d_nodes8, ctx->d_leaf_box, ctx->d_slot_src,
+		ctx->d_parent, ctx->d_rows, ctx->d_rows4, ctx->d_instances };
+	static const uint32_t elem[MRT_SNAP_COUNT] = { sizeof(mrt::DevNode), sizeof(mrt::TriHot), sizeof(mrt::TriCold), sizeof(mrt::Dev4Node),
+		sizeof(mrt::Dev8Node), 32u, 4u, 4u, 64u, 64u, sizeof(mrt::DevInstance) };
+	const uint64_t count[MRT_SNAP_COUNT] = { ctx->n_nodes, ctx->n_tris, ctx->n_tris, ctx->n_nodes4, ctx->n_nodes8, ctx->n_tris, ctx->n_tris,
+		(uint64_t)ctx->n_nodes - (tl ? tl->tlas_cap : 0u), (uint64_t)ctx->n_nodes + ctx->n_tris, (uint64_t)2u * ctx->n_nodes4 + ctx->n_tris, tl ? tl->n_inst : 0u };
+	for (int a = 0; a < MRT_SNAP_COUNT; a++) { info->count[a] = src[a] ? count[a] : 0u; info->elem_bytes[a] = elem[a]; }
+	if (!buffers) return MRT_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	for (int a = 0; a < MRT_SNAP_COUNT; a++)
+		if (buffers[a] && info->count[a])
+			HIP_TRY(ctx, hipMemcpyAsync(buffers[a], src[a], (size_t)info->count[a] * elem[a], hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return MRT_OK;
+}
+
 int mrt_generate_grid(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h,
 		uint32_t y0, uint32_t y1, mrt_ray32 *d_rays)
 {

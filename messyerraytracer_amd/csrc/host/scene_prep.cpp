@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <new>
 #include <thread>
 #include <vector>
 #include "../mrt_internal.h"
@@ -277,7 +278,7 @@ int prepare_scene(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *
 		}
 		out->n_nodes4 = (uint32_t)dev4.size();
 		out->nodes4 = (Dev4Node *)std::malloc(dev4.size() * sizeof(Dev4Node));
-		if (!out->nodes4) { std::free(hot); std::free(cold); std::free(out->nodes); out->nodes = nullptr; return fail(MRT_ERR_OOM, "upload_scene: out of host memory"); }
+		if (!out->nodes4) { std::free(hot); std::free(cold); std::free(out->nodes); out->nodes = nullptr; out->hot = nullptr; out->cold = nullptr; return fail(MRT_ERR_OOM, "upload_scene: out of host memory"); }
 		std::memcpy(out->nodes4, dev4.data(), dev4.size() * sizeof(Dev4Node));
 		out->stack4 = stack4;
 	}
@@ -406,3 +407,42 @@ int prepare_scene(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *
 }
 
 } // namespace mrt
+
+// ---- the prepared flat scene on the host, through the C-ABI (include/mrt_hip.h: mrt_scene_prepare_host) ----------------
+struct mrt_scene_host { mrt::DeviceSceneHost s; };
+
+extern "C" void mrt_scene_free_host(mrt_scene_host *w)
+{
+	if (!w) return;
+	std::free(w->s.nodes); std::free(w->s.nodes4); std::free(w->s.nodes8); std::free(w->s.leaf_box); std::free(w->s.hot); std::free(w->s.cold);
+	delete w;
+}
+
+extern "C" int mrt_scene_prepare_host(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *nodes, uint32_t used_nodes,
+		const uint32_t *prim_idx, mrt_scene_host **out)
+{
+	if (!out) return MRT_ERR_INVALID;
+	*out = nullptr;
+	mrt_scene_host *w = new (std::nothrow) mrt_scene_host();
+	if (!w) return MRT_ERR_OOM;
+	w->s.want8 = true;
+	char err[256];
+	const int rc = mrt::prepare_scene(tris, n_tris, nodes, used_nodes, prim_idx, &w->s, err, sizeof(err));
+	if (rc != MRT_OK) { mrt_scene_free_host(w); return rc; }
+	*out = w;
+	return MRT_OK;
+}
+
+extern "C" int mrt_scene_host_arrays(const mrt_scene_host *w, mrt_flat_scene_arrays *out)
+{
+	if (!w || !out) return MRT_ERR_INVALID;
+	const mrt::DeviceSceneHost &s = w->s;
+	out->nodes = reinterpret_cast<const mrt_bvh_node_wide64 *>(s.nodes); out->n_nodes = s.n_nodes;
+	out->tri_hot = reinterpret_cast<const float *>(s.hot); out->tri_cold = reinterpret_cast<const float *>(s.cold); out->n_tris = s.n_tris;
+	out->nodes4 = s.nodes4; out->n_nodes4 = s.n_nodes4; out->stack4 = s.stack4;
+	out->nodes8 = s.nodes8; out->n_nodes8 = s.nodes8 ? s.n_nodes8 : 0u; out->stack8 = s.nodes8 ? s.stack8 : 0u;
+	out->leaf_box = s.leaf_box;
+	out->depth = s.depth;
+	for (int c = 0; c < 3; c++) { out->bounds_lo[c] = s.bounds_lo[c]; out->bounds_hi[c] = s.bounds_hi[c]; }
+	return MRT_OK;
+}

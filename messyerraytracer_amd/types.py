@@ -29,7 +29,21 @@ LIGHT = np.dtype([("type", "<u4"), ("cast_shadows", "<u4"), ("position", "<f4", 
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2
 MAX_LIGHTS = 16
 
+# rows of the device layouts (csrc/mrt_internal.h), as mrt_debug_snapshot and the host preparations return them
+TRI_HOT = np.dtype([("v0", "<f4", 3), ("id", "<u4"), ("e1", "<f4", 3), ("layers", "<u4"), ("e2", "<f4", 3), ("flags", "<u4")])
+TRI_COLD = np.dtype([("normal", "<f4", 3), ("pad", "<u4")])
+NODE4 = np.dtype([("box", "<f4", (4, 6)), ("ref", "<u4", 4), ("n_children", "<u4"), ("pad", "<u4", 3)])
+NODE8 = np.dtype([("org", "<f4", 3), ("exp", "u1", 3), ("n_children", "u1"), ("qlo", "u1", (3, 8)), ("qhi", "u1", (3, 8)),
+                  ("ref", "<u4", 8), ("pad", "<u4", 8)])
+DEV_INSTANCE = np.dtype([("inv", "<f4", 12), ("basis", "<f4", 9), ("root", "<u4"), ("id_base", "<u4"), ("layers", "<u4"),
+                         ("flags", "<u4"), ("index", "<u4"), ("root8", "<u4"), ("pad", "<u4", 5)])
+# mrt_debug_snapshot: array index -> (name, row dtype)
+SNAPSHOT_ARRAYS = [("nodes", WIDE64), ("tri_hot", TRI_HOT), ("tri_cold", TRI_COLD), ("nodes4", NODE4), ("nodes8", NODE8),
+                   ("leaf_box", np.dtype(("<f4", 8))), ("slot_src", np.dtype("<u4")), ("parent", np.dtype("<u4")),
+                   ("rows", np.dtype(("<u4", 16))), ("rows4", np.dtype(("<u4", 16))), ("instances", DEV_INSTANCE)]
+
 assert INSTANCE.itemsize == 64 and LIGHT.itemsize == 32
+assert TRI_HOT.itemsize == 48 and TRI_COLD.itemsize == 16 and NODE4.itemsize == 128 and NODE8.itemsize == 128 and DEV_INSTANCE.itemsize == 128
 assert RAY32.itemsize == 32 and HIT32.itemsize == 32 and TRI64.itemsize == 64
 assert NODE32.itemsize == 32 and WIDE64.itemsize == 64
 assert HOST_RAY60.itemsize == 60 and HOST_HIT44.itemsize == 44 and HOST_TRI80.itemsize == 80
