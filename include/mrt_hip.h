@@ -668,6 +668,63 @@ int mrt_cast_grid_hemisphere(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_
 		uint32_t y0, uint32_t y1, const void *d_hits, const mrt_hemisphere *desc, void *d_out, void *d_out_rays,
 		uint32_t query_mask, int mode, uint32_t flags);
 
+/* ---- the path tracer's bounce from resident hit records: the direction half of PathTrace::sample_bounce
+ * (src/modules/graphics/path_trace.h:185-251, called at every bounce from cpu_path_tracer.h:162): one draw chooses
+ * the lobe against a specular probability made from the surface's metallic and roughness, then either a GGX half
+ * vector (ggx_sample_half, :132-155) with the view direction reflected about it, or the cosine hemisphere above.
+ * One closest-hit ray per record, made in the trace kernel.  Weights, throughput and Russian roulette stay with the
+ * renderer (they need albedo and F0).  Shading (smooth) normals are not taken: n is the record's geometric normal,
+ * as for reflections and hemisphere rays.  For every record that is a hit and selected (d_select null, or
+ * d_select[i] != 0), plain fp32 operations in this order, nothing contracted:
+ *   p, d, n = exactly as mrt_cast_hemisphere takes them, n negated if ((nx*dx + ny*dy) + nz*dz) > 0.
+ *   metallic, roughness = d_surface[2i], d_surface[2i + 1], or the descriptor's two constants when d_surface is null.
+ *   m = fminf(fmaxf(metallic, 0), 1), ro = fminf(fmaxf(roughness, 0.04f), 1) (0.04: the clamp of the reference's
+ *       extract_surface; a NaN in d_surface takes the lower bound).
+ *   sp = m + ((1 - m) * (1 - ro)) * 0.5f, then sp = fmaxf(fminf(sp, 0.95f), 0.05f).
+ *   The PCG32 stream of mrt_cast_hemisphere with the same seed and pixel_index rule (grid form: y * grid_w + x of the
+ *       whole grid, so a row band draws what the whole frame draws; array form: the record's index).  u0, u1, u2 =
+ *       draws first_draw, first_draw + 1, first_draw + 2, each float(output) * 2^-32.  Bounce b of the reference's
+ *       loop stands at first_draw = 3b + max(0, b - 2) (its roulette draws from bounce 3 on included).
+ *   specular = u0 < sp.
+ *   diffuse: the direction of mrt_cast_hemisphere from (u1, u2), operation for operation: what
+ *       mrt_cast_hemisphere(n_samples = 1, first_draw + 1) casts for the record.
+ *   specular: a = ro * ro, a2 = a * a, c = sqrt((1 - u1) / ((1 + (a2 - 1) * u1) + 1e-7f)),
+ *       s = sqrt(fmaxf(0, 1 - c * c)), (cs, sn) = the sincos pair above of u2, lx = s * cs, ly = s * sn,
+ *       h = normalized((t * lx + bt * ly) + n * c) with t, bt from construct_onb(n) above, v = normalized(-d),
+ *       vh = fmaxf((vx*hx + vy*hy) + vz*hz, 0), dir = normalized(h * (2 * vh) - v) per component.
+ *   normalized(x, y, z): l2 = (x*x + y*y) + z*z; 0 if l2 == 0, else each component divided by sqrt(l2).
+ *   org = p + n * 1e-3, t_min = 1e-4, t_max = the descriptor's.
+ * An entry has no ray if its record is a miss, it is not selected, or ((nx*dirx + ny*diry) + nz*dirz) <= 0 (the
+ * reference's "below surface -- invalid sample").  Nothing is walked for it.  Its lobe byte is MRT_LOBE_NONE;
+ * every other entry's is the lobe sampled. */
+enum { MRT_LOBE_NONE = 0, MRT_LOBE_DIFFUSE = 1, MRT_LOBE_SPECULAR = 2 };
+typedef struct mrt_bounce {
+	uint32_t frame;            /* enters the seed, as mrt_hemisphere.frame                               */
+	uint32_t first_draw;       /* draws of the pixel's stream before the lobe draw                       */
+	float t_max;               /* finite and > 1e-4; the path tracer: 1e30f                              */
+	float metallic, roughness; /* used for every record when d_surface is null                           */
+	const uint8_t *d_select;   /* optional device pointer, one byte per record: 0 = no ray               */
+	const float *d_surface;    /* optional device pointer, 2 floats per record: {metallic, roughness}    */
+	uint8_t *d_out_lobe;       /* optional device pointer, one byte per record: MRT_LOBE_*               */
+} mrt_bounce;
+/* Bounce rays for the hit records of a cast.  d_rays / d_hits: what mrt_cast read and wrote -- mrt_ray32 +
+ * mrt_hit32, or with MRT_FLAG_HOST_LAYOUT mrt_host_ray60 + mrt_host_hit44 (the rays are always read: the incoming
+ * direction).  d_out_hits[i] = the record mrt_cast(MRT_MODE_NEAREST) writes for the ray, in the input layout;
+ * d_out_rays: optional, the ray in the input layout; an entry without a ray gets the placeholder ray and its
+ * record as mrt_cast_reflections writes them.  The outputs feed mrt_cast_shadows, mrt_cast_reflections,
+ * mrt_cast_hemisphere or the next mrt_cast_bounce.  All pointers but desc are device pointers.  Flags:
+ * MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID for a null required
+ * pointer, an unknown flag, t_max not finite or not > 1e-4 and, with d_surface null, metallic or roughness not
+ * finite or outside [0, 1]; all checked before the scene.  Flat and two-level scenes. */
+int mrt_cast_bounce(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const mrt_bounce *desc,
+		void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_hits as it wrote them, mrt_hit32; d_select,
+ * d_surface and d_out_lobe indexed by the record within the band): the primary rays are regenerated in the kernel.
+ * count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_cast_grid_bounce(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0,
+		uint32_t y1, const void *d_hits, const mrt_bounce *desc, void *d_out_hits, void *d_out_rays,
+		uint32_t query_mask, uint32_t flags);
+
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to
  * tokens written by a cast with MRT_FLAG_TOKEN_OUT: mrt_hit32 records (mrt_host_hit44 with

@@ -16,11 +16,12 @@ POLICY_TEST = os.path.join(HERE, "launch_policy_test")
 SHADOW_POLICY_TEST = os.path.join(HERE, "shadow_policy_test")
 REFLECTION_POLICY_TEST = os.path.join(HERE, "reflection_policy_test")
 HEMISPHERE_POLICY_TEST = os.path.join(HERE, "hemisphere_policy_test")
+BOUNCE_POLICY_TEST = os.path.join(HERE, "bounce_policy_test")
 INSTANCE_MATH_TEST = os.path.join(HERE, "instance_math_test")
 
 SOURCES = ["kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip", "device_build.hip", "refit.hip",
            "tlas_device.hip", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
-HEADERS = ["mrt_internal.h", "instance_math.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "shadow_kernel.h", "reflection_kernel.h", "hemisphere_kernel.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
+HEADERS = ["mrt_internal.h", "instance_math.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "shadow_kernel.h", "reflection_kernel.h", "hemisphere_kernel.h", "bounce_kernel.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
            "host/host_types.hpp", "host/cpu_backend.hpp", "host/ray_tracer_server.hpp"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
@@ -161,6 +162,18 @@ def build_hemisphere_policy_test(force: bool = False) -> str:
     return HEMISPHERE_POLICY_TEST
 
 
+def build_bounce_policy_test(force: bool = False) -> str:
+    """C++ test driver for the plans of bounce casts (launch_policy.cpp alone: host code, no device, no library)."""
+    srcs = [os.path.join(CSRC, "host", "bounce_policy_test.cpp"), os.path.join(CSRC, "launch_policy.cpp")]
+    deps = srcs + [os.path.join(CSRC, h) for h in HEADERS]
+    if force or _stale(BOUNCE_POLICY_TEST, deps):
+        cmd = [_hipcc(), "-O2", "-std=c++17", "-Wall"] + srcs + ["-o", BOUNCE_POLICY_TEST]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
+        if r.returncode != 0:
+            raise RuntimeError("bounce policy test build failed:\n" + r.stdout + r.stderr)
+    return BOUNCE_POLICY_TEST
+
+
 def build_instance_math_test(force: bool = False) -> str:
     """C++ test driver for the per-instance arithmetic shared by the host path and the device top-level build (instance_math.h
     compiled for the CPU alone: no device, no library)."""
@@ -183,4 +196,5 @@ if __name__ == "__main__":
     print(build_shadow_policy_test(force=True))
     print(build_reflection_policy_test(force=True))
     print(build_hemisphere_policy_test(force=True))
+    print(build_bounce_policy_test(force=True))
     print(build_instance_math_test(force=True))

@@ -31,7 +31,7 @@ SYMBOLS = [
     "mrt_synchronize", "mrt_make_triangles", "mrt_pack_host_triangles", "mrt_bvh2_build", "mrt_bvh2_save", "mrt_bvh2_load", "mrt_upload_scene",
     "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_update_instances_device", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_scene_prepare_host", "mrt_scene_host_arrays", "mrt_scene_free_host", "mrt_debug_snapshot", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
-    "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_expand_tokens",
+    "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_cast_bounce", "mrt_cast_grid_bounce", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
     "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
     "mrt_group_create", "mrt_group_destroy", "mrt_group_size", "mrt_group_context", "mrt_group_last_error", "mrt_group_row_block",
@@ -64,6 +64,15 @@ class Hemisphere(C.Structure):
     """mrt_hemisphere"""
     _fields_ = [("n_samples", C.c_uint32), ("frame", C.c_uint32), ("first_draw", C.c_uint32), ("t_max", C.c_float),
                 ("d_select", C.c_void_p)]
+
+
+class Bounce(C.Structure):
+    """mrt_bounce"""
+    _fields_ = [("frame", C.c_uint32), ("first_draw", C.c_uint32), ("t_max", C.c_float), ("metallic", C.c_float),
+                ("roughness", C.c_float), ("d_select", C.c_void_p), ("d_surface", C.c_void_p), ("d_out_lobe", C.c_void_p)]
+
+
+LOBE_NONE, LOBE_DIFFUSE, LOBE_SPECULAR = 0, 1, 2
 
 
 class Stats(C.Structure):
@@ -180,6 +189,10 @@ def load():
                                       C.c_uint32, C.c_int, C.c_uint32]
     L.mrt_cast_grid_hemisphere.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                            C.POINTER(Hemisphere), C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32]
+    L.mrt_cast_bounce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Bounce), C.c_void_p, C.c_void_p,
+                                  C.c_uint32, C.c_uint32]
+    L.mrt_cast_grid_bounce.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                       C.POINTER(Bounce), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_cast_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mrt_expand_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
     L.mrt_expand_grid_tokens.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -220,6 +233,12 @@ def hemisphere_desc(n_samples, frame, first_draw, t_max, d_select=None):
     """mrt_hemisphere from its fields (d_select: device pointer / tensor or None)"""
     sel = _optr(d_select)
     return Hemisphere(n_samples, frame, first_draw, t_max, None if sel is None else sel.value)
+
+
+def bounce_desc(frame, first_draw, t_max, metallic=0.0, roughness=0.5, d_select=None, d_surface=None, d_out_lobe=None):
+    """mrt_bounce from its fields (d_select, d_surface, d_out_lobe: device pointers / tensors or None)"""
+    v = [None if x is None else _ptr(x).value for x in (d_select, d_surface, d_out_lobe)]
+    return Bounce(frame, first_draw, t_max, metallic, roughness, v[0], v[1], v[2])
 
 
 def _ptr(x):
@@ -657,6 +676,26 @@ class Context:
         desc = hemisphere_desc(n_samples, frame, first_draw, t_max, d_select)
         self._chk(self.L.mrt_cast_grid_hemisphere(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(desc), _ptr(d_out),
                                                   _optr(d_out_rays), query_mask, mode, flags))
+
+    def cast_bounce(self, d_rays, d_hits, count, d_out_hits, frame=0, first_draw=0, t_max=1e30, metallic=0.0, roughness=0.5,
+                    d_select=None, d_surface=None, d_out_lobe=None, d_out_rays=None, query_mask=0xFFFFFFFF, flags=0):
+        """The path tracer's bounce for the hit records of a cast (device pointers / tensors: mrt_ray32 + mrt_hit32, or mrt_host_ray60 +
+        mrt_host_hit44 with FLAG_HOST_LAYOUT): one closest-hit ray per record, GGX-specular or cosine-diffuse by the lobe draw.
+        d_out_hits one record per entry in the input layout, d_out_rays (optional) the rays made.  d_select: optional byte per record
+        (0 = no ray); d_surface: optional {metallic, roughness} float pairs per record (else the two constants); d_out_lobe: optional
+        byte per record, LOBE_*."""
+        desc = bounce_desc(frame, first_draw, t_max, metallic, roughness, d_select, d_surface, d_out_lobe)
+        self._chk(self.L.mrt_cast_bounce(self.h, _ptr(d_rays), _ptr(d_hits), count, C.byref(desc), _ptr(d_out_hits), _optr(d_out_rays),
+                                         query_mask, flags))
+
+    def cast_grid_bounce(self, cam, grid_w, grid_h, d_hits, d_out_hits, frame=0, first_draw=0, t_max=1e30, metallic=0.0, roughness=0.5,
+                         d_select=None, d_surface=None, d_out_lobe=None, d_out_rays=None, y0=0, y1=None, query_mask=0xFFFFFFFF, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (d_hits: its mrt_hit32 records on the device; d_select, d_surface and
+        d_out_lobe indexed by the record within the band); the random stream of a pixel is seeded from its index in the whole grid."""
+        y1 = grid_h if y1 is None else y1
+        desc = bounce_desc(frame, first_draw, t_max, metallic, roughness, d_select, d_surface, d_out_lobe)
+        self._chk(self.L.mrt_cast_grid_bounce(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(desc), _ptr(d_out_hits),
+                                              _optr(d_out_rays), query_mask, flags))
 
     def expand_tokens(self, d_rays, d_tokens, d_hits, count, flags=0, stream=None):
         """Device pointers; enqueued on `stream` (raw hipStream_t) or the context's stream, not waited for."""

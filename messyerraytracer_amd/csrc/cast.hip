@@ -70,13 +70,16 @@ void note_queued(mrt_ctx *ctx, uint32_t kernel)
 
 // A cast whose rays are made in the kernel launches its source's instantiation of the same kernel: a shadow cast (shadow: its lights
 // and records, src its SRC_SHADOW_* source), a reflection cast (reflect: its records, mask and outputs, src its SRC_REFLECT_* source)
-// or a hemisphere cast (hemi: its records, mask, outputs and jump constants, src its SRC_HEMI_* source, any_hit its mode).
-struct SourceLaunch { const mrt::ShadowParams *shadow; const mrt::ReflectParams *reflect; int src; const mrt::HemiParams *hemi = nullptr; bool any_hit = false; };
+// a hemisphere cast (hemi: its records, mask, outputs and jump constants, src its SRC_HEMI_* source, any_hit its mode) or a bounce cast
+// (bounce: its records, mask, materials, outputs and jump constants, src its SRC_BOUNCE_* source).
+struct SourceLaunch { const mrt::ShadowParams *shadow; const mrt::ReflectParams *reflect; int src; const mrt::HemiParams *hemi = nullptr; bool any_hit = false;
+	const mrt::BounceParams *bounce = nullptr; };
 
 hipError_t launch_source(const SourceLaunch &sl, const mrt::TraceParams &p, unsigned long long *next_ray, uint32_t *ovf,
 		const mrt::LaneLaunch &l, hipStream_t stream)
 {
 	if (sl.shadow) return mrt::launch_shadow(p, *sl.shadow, sl.src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
+	if (sl.bounce) return mrt::launch_bounce(p, *sl.bounce, sl.src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
 	if (sl.hemi) return mrt::launch_hemisphere(p, *sl.hemi, sl.src, sl.any_hit, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
 	return mrt::launch_reflection(p, *sl.reflect, sl.src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
 }
@@ -414,6 +417,63 @@ int cast_hemisphere(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p
 	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
 }
 
+// The checks of a bounce descriptor and its outputs that need no context: what the entry points refuse before anything else.
+const char *bounce_invalid(const mrt_bounce *desc, const void *d_hits, const void *d_out_hits)
+{
+	if (!desc) return "null descriptor";
+	if (!(desc->t_max > 1e-4f && desc->t_max <= FLT_MAX)) return "t_max must be finite and > 1e-4 (t_min)";
+	if (!desc->d_surface) { // (the comparisons are false for a NaN)
+		if (!(desc->metallic >= 0.0f && desc->metallic <= 1.0f)) return "metallic must be in [0, 1]";
+		if (!(desc->roughness >= 0.0f && desc->roughness <= 1.0f)) return "roughness must be in [0, 1]";
+	}
+	if (!d_hits || !d_out_hits) return "null hits / output";
+	return nullptr;
+}
+
+// (A, C) with: PCG32 state before draw first_draw = A * state0 + C, modulo 2^32 (the method of hemisphere_jumps: steps by squaring)
+mrt::HemiJump bounce_jump(uint32_t first_draw)
+{
+	uint32_t A = 1u, C = 0u, a = mrt::kPcgMul, c = mrt::kPcgInc;
+	for (uint32_t k = first_draw; k != 0u; k >>= 1) {
+		if (k & 1u) { A = a * A; C = a * C + c; }
+		c = a * c + c; a = a * a;
+	}
+	return mrt::HemiJump{A, C};
+}
+
+// The bounce casts (mrt_cast_bounce, mrt_cast_grid_bounce) after their own checks: p holds the scene, the grid (grid source) and the
+// incoming rays (SRC_BOUNCE_RAY32, SRC_BOUNCE_HOST); count = records, pixel0 = the pixel index of record 0.
+int cast_bounce(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count, uint32_t pixel0,
+		const mrt_bounce *desc, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
+{
+	const uint32_t known = (entry == mrt::ENTRY_BOUNCE ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
+	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a bounce cast");
+	if (const char *why = bounce_invalid(desc, d_hits, d_out_hits)) return fail(ctx, MRT_ERR_INVALID, why);
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (count == 0) return MRT_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	mrt::BounceParams s;
+	std::memset(&s, 0, sizeof(s));
+	s.records = d_hits; s.select = desc->d_select; s.surface = desc->d_surface; s.out_rays = d_out_rays; s.out_lobe = desc->d_out_lobe;
+	s.t_max = desc->t_max; s.metallic = desc->metallic; s.roughness = desc->roughness;
+	s.seed_add = pixel0 * 1009u + desc->frame * 6529u + 7u;
+	s.jump = bounce_jump(desc->first_draw);
+	p.hits = d_out_hits; p.count = count; p.query_mask = query_mask;
+	p.out_fmt = src == mrt::SRC_BOUNCE_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32;
+	// (the plan reads neither the detected grid nor the grid states: an empty PrevDetect)
+	const mrt::CastRequest r{entry, count, flags, MRT_MODE_NEAREST};
+	const mrt::CastPlan c = mrt::plan_cast(ctx->opts, scene_facts(ctx), r, mrt::PrevDetect{}, ctx->knobs, ctx->grids);
+	SourceLaunch sl{nullptr, nullptr, src};
+	sl.bounce = &s;
+	int rc = launch_planned(ctx, c, r, p, &sl);
+	if (rc) return rc;
+	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
+	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
+}
+
 } // namespace
 
 extern "C" {
@@ -637,6 +697,32 @@ int mrt_cast_grid_hemisphere(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_
 	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the entries; the kernel regenerates the incoming ray from p.cam itself)
 	return cast_hemisphere(ctx, mrt::ENTRY_GRID_HEMISPHERE, mrt::SRC_HEMI_GRID, p, d_hits, p.count, y0 * grid_w, desc, d_out, d_out_rays,
 			query_mask, mode, flags);
+}
+
+int mrt_cast_bounce(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const mrt_bounce *desc, void *d_out_hits,
+		void *d_out_rays, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
+	mrt::TraceParams p;
+	base_params(ctx, p);
+	p.rays = d_rays; // (read for every source: the incoming direction)
+	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
+	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
+	return cast_bounce(ctx, mrt::ENTRY_BOUNCE, host ? mrt::SRC_BOUNCE_HOST : mrt::SRC_BOUNCE_RAY32, p, d_hits, count, 0u, desc, d_out_hits,
+			d_out_rays, query_mask, flags);
+}
+
+int mrt_cast_grid_bounce(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const void *d_hits, const mrt_bounce *desc, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	mrt::TraceParams p;
+	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
+	if (rc) return rc;
+	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the entries; the kernel regenerates the incoming ray from p.cam itself)
+	return cast_bounce(ctx, mrt::ENTRY_GRID_BOUNCE, mrt::SRC_BOUNCE_GRID, p, d_hits, p.count, y0 * grid_w, desc, d_out_hits, d_out_rays,
+			query_mask, flags);
 }
 
 } // extern "C"

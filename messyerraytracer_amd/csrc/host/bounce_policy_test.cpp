@@ -1,0 +1,191 @@
+// bounce_policy_test.cpp — pins the plans of bounce casts (launch_policy.cpp, ENTRY_BOUNCE / ENTRY_GRID_BOUNCE) without a device: a
+// table of bounce casts (count = records) and the plan each one must get -- the reflection plan of as many rays: unsorted,
+// non-coherent, the plain lane kernel below 2^16 rays and the persistent ones from 2^16, a forced packet kernel meaning the policy's
+// lane kernel -- then a renderer's frame loop -- a primary grid cast, the grid tuner's timing, a bounce cast -- against the same loop
+// without the bounce casts: the primary grid's plans must be the same, frame by frame, and a bounce plan must leave the grid states
+// (detected widths aside, which it is not even given: tuner and tile schedules) byte for byte as they were.  Exit status 0 iff every
+// check holds; one line per failure.
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "../launch_policy.h"
+
+using namespace mrt;
+
+namespace {
+
+int failures = 0, checks = 0;
+void expect(bool ok, const std::string &what)
+{
+	checks++;
+	if (!ok) { failures++; std::printf("FAIL %s\n", what.c_str()); }
+}
+
+const char *kname(uint32_t k)
+{
+	switch (k) {
+		case MRT_KERNEL_LANE: return "lane";
+		case MRT_KERNEL_PACKET_ASM: return "asm";
+		case MRT_KERNEL_LANE_PERSISTENT: return "lp";
+		case MRT_KERNEL_LANE4_PERSISTENT: return "l4p";
+		case MRT_KERNEL_LANE8_PERSISTENT: return "l8p";
+		case MRT_KERNEL_PACKET_DUAL: return "dual";
+		case MRT_KERNEL_TWO_LEVEL: return "tl";
+		case MRT_KERNEL_TWO_LEVEL_PACKET: return "tlpkt";
+		case MRT_KERNEL_TWO_LEVEL_PERSISTENT: return "tlp";
+		case MRT_KERNEL_TWO_LEVEL_PERSISTENT8: return "tlp8";
+		default: return "?";
+	}
+}
+
+// k=<kernel> <launch>(<lane launch>) [sort] [detect] [sched] [arms] n=<launches> [cnt]
+std::string describe(const CastPlan &c)
+{
+	char b[256];
+	int n = std::snprintf(b, sizeof(b), "k=%s ", kname(c.kernel));
+	if (c.launch == CastPlan::PLAIN) n += std::snprintf(b + n, sizeof(b) - n, "plain");
+	else {
+		const LaneLaunch &l = c.lane;
+		n += std::snprintf(b + n, sizeof(b) - n, "%s(%s ", c.launch == CastPlan::DUAL ? "dual" : "lane", kname(l.kernel));
+		if (l.persistent) n += std::snprintf(b + n, sizeof(b) - n, "pers blocks=%u lds=%u spill=%u wait=%u", l.blocks, l.lds_depth, l.spill, l.leaf_wait);
+		else n += std::snprintf(b + n, sizeof(b) - n, "sparse=%u", l.sparse_lanes);
+		n += std::snprintf(b + n, sizeof(b) - n, "%s)", l.count ? " cnt" : "");
+	}
+	if (c.lane_map != MAP_LINEAR || c.quarter_all) n += std::snprintf(b + n, sizeof(b) - n, " map=%u q=%u", c.lane_map, c.quarter_all);
+	if (c.sort) n += std::snprintf(b + n, sizeof(b) - n, " sort");
+	if (c.detect) n += std::snprintf(b + n, sizeof(b) - n, " detect");
+	if (c.scheduled) n += std::snprintf(b + n, sizeof(b) - n, " sched%s", c.pieces ? "+pieces" : "");
+	if (c.arms_tuner) n += std::snprintf(b + n, sizeof(b) - n, " arms");
+	n += std::snprintf(b + n, sizeof(b) - n, " n=%u%s", c.launches, c.count ? " cnt" : "");
+	return b;
+}
+
+// scenes as in launch_policy_test.cpp: flat with every layout, without the 8-wide one, 2-wide only; two-level with / without 8-wide BLASes
+enum { FLAT, NO8, BARE, TL, TL_NO8 };
+SceneFacts scene(int k)
+{
+	SceneFacts s;
+	s.rows = s.nodes4 = s.nodes8 = true; s.n_nodes = 40000; s.depth = 20; s.stack4 = 12; s.stack8 = 10;
+	if (k == NO8) s.nodes8 = false;
+	if (k == BARE) s.rows = s.nodes4 = s.nodes8 = false;
+	if (k == TL || k == TL_NO8) { s.two_level = true; s.rows = s.nodes4 = false; s.nodes8 = k == TL; s.depth = 30; s.stack8 = 14; }
+	return s;
+}
+
+mrt_options options(uint32_t kernel, uint32_t count_visits = 0)
+{
+	mrt_options o;
+	std::memset(&o, 0, sizeof(o));
+	o.struct_size = sizeof(o); o.kernel = kernel; o.count_visits = count_visits;
+	return o;
+}
+
+struct Case { const char *name; int scene; uint32_t kernel, count_visits; Entry entry; uint64_t count; uint32_t flags; const char *want; };
+// count = records.  Persistent: 16 LDS entries per lane -> 8 workgroups per CU -> 2 048 blocks (fewer for a small batch).
+const Case kCases[] = {
+	{"1k rays: one ray per wave", FLAT, MRT_KERNEL_AUTO, 0, ENTRY_BOUNCE, 1000, 0, "k=lane lane(lane sparse=1) n=1"},
+	{"20k rays: four rays per wave", FLAT, MRT_KERNEL_AUTO, 0, ENTRY_GRID_BOUNCE, 20000, 0, "k=lane lane(lane sparse=4) n=1"},
+	{"40k rays: full waves", FLAT, MRT_KERNEL_AUTO, 0, ENTRY_BOUNCE, 40000, 0, "k=lane lane(lane sparse=0) n=1"},
+	{"2^16 - 1 rays: still plain", FLAT, MRT_KERNEL_AUTO, 0, ENTRY_GRID_BOUNCE, 65535, 0, "k=lane lane(lane sparse=0) n=1"},
+	{"2^16 rays: 8-wide persistent", FLAT, MRT_KERNEL_AUTO, 0, ENTRY_GRID_BOUNCE, 65536, 0, "k=l8p lane(l8p pers blocks=256 lds=16 spill=0 wait=8) n=1"},
+	{"2^20 rays, async", FLAT, MRT_KERNEL_AUTO, 0, ENTRY_GRID_BOUNCE, 1u << 20, MRT_FLAG_ASYNC, "k=l8p lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) n=0"},
+	{"2^20 rays, no 8-wide nodes", NO8, MRT_KERNEL_AUTO, 0, ENTRY_BOUNCE, 1u << 20, 0, "k=l4p lane(l4p pers blocks=2048 lds=16 spill=0 wait=16) n=1"},
+	{"2^20 rays, 2-wide nodes only", BARE, MRT_KERNEL_AUTO, 0, ENTRY_BOUNCE, 1u << 20, MRT_FLAG_HOST_LAYOUT, "k=lp lane(lp pers blocks=2048 lds=16 spill=4 wait=16) n=1"},
+	{"two-level, 1k rays", TL, MRT_KERNEL_AUTO, 0, ENTRY_GRID_BOUNCE, 1000, 0, "k=tl lane(tl sparse=1) n=1"},
+	{"two-level, 2^20 rays", TL, MRT_KERNEL_AUTO, 0, ENTRY_GRID_BOUNCE, 1u << 20, 0, "k=tlp8 lane(tlp8 pers blocks=2048 lds=16 spill=0 wait=8) n=1"},
+	{"two-level without 8-wide BLASes", TL_NO8, MRT_KERNEL_AUTO, 0, ENTRY_BOUNCE, 1u << 20, 0, "k=tlp lane(tlp pers blocks=2048 lds=16 spill=14 wait=16) n=1"},
+	{"forced 64-ray packets: the policy's lane kernel", FLAT, MRT_KERNEL_PACKET_ASM, 0, ENTRY_GRID_BOUNCE, 1u << 20, 0, "k=l8p lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) n=1"},
+	{"forced 128-ray walk, small", FLAT, MRT_KERNEL_PACKET_DUAL, 0, ENTRY_BOUNCE, 1000, 0, "k=lane lane(lane sparse=1) n=1"},
+	{"forced generic packets", FLAT, MRT_KERNEL_PACKET, 0, ENTRY_BOUNCE, 40000, 0, "k=lane lane(lane sparse=0) n=1"},
+	{"forced packets, two-level", TL, MRT_KERNEL_PACKET_ASM, 0, ENTRY_GRID_BOUNCE, 1u << 20, 0, "k=tlp8 lane(tlp8 pers blocks=2048 lds=16 spill=0 wait=8) n=1"},
+	{"forced lane kernel", FLAT, MRT_KERNEL_LANE, 0, ENTRY_GRID_BOUNCE, 1u << 20, 0, "k=lane lane(lane sparse=0) n=1"},
+	{"forced 4-wide persistent, small", FLAT, MRT_KERNEL_LANE4_PERSISTENT, 0, ENTRY_BOUNCE, 1000, 0, "k=l4p lane(l4p pers blocks=4 lds=16 spill=0 wait=16) n=1"},
+	{"forced 8-wide persistent", FLAT, MRT_KERNEL_LANE8_PERSISTENT, 0, ENTRY_BOUNCE, 40000, 0, "k=l8p lane(l8p pers blocks=157 lds=16 spill=0 wait=8) n=1"},
+	{"counting build: no counting variant", FLAT, MRT_KERNEL_AUTO, 1, ENTRY_GRID_BOUNCE, 1u << 20, 0, "k=l8p lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) n=1"},
+	{"counting build, small", FLAT, MRT_KERNEL_AUTO, 1, ENTRY_BOUNCE, 1000, 0, "k=lane lane(lane sparse=1) n=1"},
+	{"counting build, two-level", TL, MRT_KERNEL_AUTO, 1, ENTRY_GRID_BOUNCE, 1u << 20, 0, "k=tlp8 lane(tlp8 pers blocks=2048 lds=16 spill=0 wait=8) n=1"},
+};
+
+void table()
+{
+	for (const Case &k : kCases) {
+		const std::string name = k.name;
+		GridStates gs;
+		PrevDetect prev;   // a detected grid of as many rays: a bounce plan must not take it
+		prev.count = k.count; prev.word[0] = 1024; prev.word[1] = (uint32_t)(k.count / 1024u); prev.word[2] = 128; prev.word[3] = 0;
+		const PrevDetect prev_before = prev;
+		CastRequest r;
+		r.entry = k.entry; r.count = k.count; r.flags = k.flags; r.mode = MRT_MODE_NEAREST;
+		std::vector<unsigned char> before(sizeof(GridStates)), after(sizeof(GridStates));
+		std::memcpy(before.data(), &gs, sizeof(gs));
+		const CastPlan c = plan_cast(options(k.kernel, k.count_visits), scene(k.scene), r, prev, Knobs(), gs);
+		std::memcpy(after.data(), &gs, sizeof(gs));
+		const std::string got = describe(c);
+		expect(got == k.want, name + ": got \"" + got + "\", want \"" + k.want + "\"");
+		expect(before == after, name + ": the plan changed the grid states");
+		expect(prev.count == prev_before.count && std::memcmp(prev.word, prev_before.word, sizeof(prev.word)) == 0, name + ": the plan changed the detected-grid words");
+		expect(!c.sort && !c.detect && !c.scheduled && !c.arms_tuner && !c.count && c.lane_map == MAP_LINEAR && c.quarter_all == 0u,
+				name + ": not an unsorted, untiled, non-counting plan: " + got);
+		// the plan of a reflection cast of as many rays, and the same plan whatever was detected before
+		CastRequest sr = r;
+		sr.entry = k.entry == ENTRY_BOUNCE ? ENTRY_REFLECTION : ENTRY_GRID_REFLECTION;
+		const std::string sibling = describe(plan_cast(options(k.kernel, k.count_visits), scene(k.scene), sr, prev, Knobs(), gs));
+		expect(got == sibling, name + ": bounce plan \"" + got + "\", reflection plan \"" + sibling + "\"");
+		const std::string blind = describe(plan_cast(options(k.kernel, k.count_visits), scene(k.scene), r, PrevDetect(), Knobs(), gs));
+		expect(got == blind, name + ": bounce plan \"" + got + "\" with a detected grid, \"" + blind + "\" without");
+	}
+}
+
+// A renderer's frame: the primary grid (blocking, so the grid tuner times it), then, if `bounce`, a bounce cast of the grid's records
+// (the grid form and the array form in turn).  The primary plans of 14 frames must not depend on them.
+std::vector<std::string> frames(int scn, bool bounce)
+{
+	GridStates gs;
+	const mrt_options o = options(MRT_KERNEL_AUTO);
+	std::vector<std::string> out;
+	const float ms[14] = {0.50f, 0.48f, 0.47f, 0.46f, 0.45f, 0.44f, 0.40f, 0.41f, 0.43f, 0.42f, 0.44f, 0.45f, 0.40f, 0.40f};
+	for (int f = 0; f < 14; f++) {
+		CastRequest g;
+		g.entry = ENTRY_GRID; g.count = 1280ull * 960ull; g.mode = MRT_MODE_NEAREST;
+		g.grid_w = 1280; g.grid_h = 960; g.y0 = 0; g.rows = 960;
+		const CastPlan c = plan_cast(o, scene(scn), g, PrevDetect(), Knobs(), gs);
+		out.push_back(describe(c));
+		tune_record(gs.tune(), ms[f]);
+		if (!bounce) continue;
+		std::vector<unsigned char> before(sizeof(GridStates)), after(sizeof(GridStates));
+		std::memcpy(before.data(), &gs, sizeof(gs));
+		CastRequest s;
+		s.entry = f & 2 ? ENTRY_BOUNCE : ENTRY_GRID_BOUNCE;
+		s.count = 1280ull * 960ull; s.mode = MRT_MODE_NEAREST; s.flags = f & 1 ? MRT_FLAG_ASYNC : 0u;
+		const CastPlan sc = plan_cast(o, scene(scn), s, PrevDetect(), Knobs(), gs);
+		std::memcpy(after.data(), &gs, sizeof(gs));
+		expect(before == after, "frame " + std::to_string(f) + ": a bounce plan changed the grid states");
+		expect(!sc.sort && !sc.detect && !sc.scheduled && !sc.arms_tuner && sc.lane_map == MAP_LINEAR, "frame " + std::to_string(f) + ": bounce plan " + describe(sc));
+	}
+	return out;
+}
+
+void alternation()
+{
+	for (int scn : {FLAT, TL}) {
+		const std::vector<std::string> a = frames(scn, false), b = frames(scn, true);
+		for (size_t f = 0; f < a.size(); f++)
+			expect(a[f] == b[f], "scene " + std::to_string(scn) + " frame " + std::to_string(f) + ": primary plan \"" + b[f] + "\" with bounce casts, \"" + a[f] + "\" without");
+		if (scn == FLAT) { // (the tuner does run here: its three candidates over the first twelve frames)
+			bool dual = false, asm_ = false;
+			for (const std::string &d : a) { dual |= d.rfind("k=dual", 0) == 0; asm_ |= d.rfind("k=asm", 0) == 0; }
+			expect(dual && asm_, "flat scene: the grid tuner tried both packet kernels");
+		}
+	}
+}
+
+} // namespace
+
+int main()
+{
+	table();
+	alternation();
+	std::printf("%d of %d checks hold (%zu table cases)\n", checks - failures, checks, sizeof(kCases) / sizeof(kCases[0]));
+	return failures ? 1 : 0;
+}

@@ -332,6 +332,7 @@ __device__ __forceinline__ void finish_two_level_ray(const TraceParams &p, uint6
 #include "shadow_kernel.h"
 #include "reflection_kernel.h"
 #include "hemisphere_kernel.h"
+#include "bounce_kernel.h"
 
 // ---- the traversal kernel: one lane = one ray -------------------------------------
 // LDS: per-lane stack, entry d of lane l at dword d*64 + l of the wave's region
@@ -343,6 +344,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -364,6 +366,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_shadow_lane_kernel(const TracePa
 	const ShadowParams *sh = &s;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC>
@@ -373,6 +376,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_shadow_two_level_kernel(const Tr
 	const ShadowParams *sh = &s;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC, int WIDTH, bool TL>
@@ -382,6 +386,7 @@ __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_shadow_persiste
 	const ShadowParams *sh = &s;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -393,6 +398,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_reflection_lane_kernel(const Tra
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = &s;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC>
@@ -402,6 +408,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_reflection_two_level_kernel(cons
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = &s;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC, int WIDTH, bool TL>
@@ -411,6 +418,7 @@ __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_reflection_pers
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = &s;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -422,6 +430,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_hemisphere_lane_kernel(const Tra
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = &s;
+	const BounceParams *bn = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC, bool ANY_HIT>
@@ -430,6 +439,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_hemisphere_two_level_kernel(cons
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = &s;
+	const BounceParams *bn = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 template <int SRC, bool ANY_HIT, int WIDTH, bool TL>
@@ -439,6 +449,39 @@ __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_hemisphere_pers
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = &s;
+	const BounceParams *bn = nullptr;
+#include "persistent_walk.inc" // (in scope: the names its first lines check)
+}
+
+// ---- bounce casts (bounce_kernel.h): the same lane kernels, closest-hit, with the path tracer's bounce as the ray source -------------
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void trace_bounce_lane_kernel(const TraceParams p, const BounceParams s)
+{
+	constexpr bool ANY_HIT = false, COUNT = false;
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = nullptr;
+	const BounceParams *bn = &s;
+#include "lane_walk.inc" // (in scope: the names its first lines check)
+}
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void trace_bounce_two_level_kernel(const TraceParams p, const BounceParams s)
+{
+	constexpr bool ANY_HIT = false;
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = nullptr;
+	const BounceParams *bn = &s;
+#include "two_level_walk.inc" // (in scope: the names its first lines check)
+}
+template <int SRC, int WIDTH, bool TL>
+__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_bounce_persistent_kernel(const TraceParams p, const PersistParams q, const BounceParams s)
+{
+	constexpr bool ANY_HIT = false, COUNT = false;
+	const ShadowParams *sh = nullptr;
+	const ReflectParams *rf = nullptr;
+	const HemiParams *hm = nullptr;
+	const BounceParams *bn = &s;
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -1094,6 +1137,47 @@ hipError_t launch_hemisphere(const TraceParams &p, const HemiParams &s, int src,
 	if (src == SRC_HEMI_RAY32) { if (any_hit) launch_hemisphere_src<SRC_HEMI_RAY32, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_RAY32, false>(p, s, q, blocks, stream); }
 	else if (src == SRC_HEMI_HOST) { if (any_hit) launch_hemisphere_src<SRC_HEMI_HOST, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_HOST, false>(p, s, q, blocks, stream); }
 	else if (src == SRC_HEMI_GRID) { if (any_hit) launch_hemisphere_src<SRC_HEMI_GRID, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_GRID, false>(p, s, q, blocks, stream); }
+	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+// Bounce casts: the same, with the bounce instantiations (ENTRY_BOUNCE / ENTRY_GRID_BOUNCE); p.count = records.
+template <int SRC>
+static void launch_bounce_src(const TraceParams &p, const BounceParams &s, const PersistParams &q, uint32_t blocks, hipStream_t stream)
+{
+	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
+	if (blocks == 0) {
+		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
+		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
+		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
+		if (tl) hipLaunchKernelGGL((trace_bounce_two_level_kernel<SRC>), grid, wg, lds, stream, p, s);
+		else hipLaunchKernelGGL((trace_bounce_lane_kernel<SRC>), grid, wg, lds, stream, p, s);
+		note_variant("trace_bounce_%s_kernel<%d>", tl ? "two_level" : "lane", SRC);
+		return;
+	}
+	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
+	int width = 2;
+	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
+		width = 8; hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else if (tl) hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) {
+		width = 8; hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 8, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) {
+		width = 4; hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 4, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	} else hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 2, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
+	note_variant("trace_bounce_persistent_kernel<%d, %d, %s>", SRC, width, MRT_B(tl));
+}
+
+hipError_t launch_bounce(const TraceParams &p, const BounceParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
+{
+	if (p.count == 0) return hipSuccess;
+	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
+	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
+	if (src == SRC_BOUNCE_RAY32) launch_bounce_src<SRC_BOUNCE_RAY32>(p, s, q, blocks, stream);
+	else if (src == SRC_BOUNCE_HOST) launch_bounce_src<SRC_BOUNCE_HOST>(p, s, q, blocks, stream);
+	else if (src == SRC_BOUNCE_GRID) launch_bounce_src<SRC_BOUNCE_GRID>(p, s, q, blocks, stream);
 	else return hipErrorInvalidValue;
 	return hipGetLastError();
 }

@@ -77,5 +77,6 @@ __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_lane_persistent
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }

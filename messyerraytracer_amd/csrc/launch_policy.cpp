@@ -215,11 +215,20 @@ static CastPlan plan_hemisphere(const mrt_options &o, const SceneFacts &s, const
 	return r.mode == MRT_MODE_ANY_HIT ? plan_shadow(o, s, r) : plan_reflection(o, s, r);
 }
 
+// Bounce casts: count = records, one closest-hit ray each -- a GGX reflection or a cosine-hemisphere ray, chosen per record -- made in
+// the kernel in record order.  The reflection plan of that many rays, for the reasons given there.  Nothing of the grid state is read
+// or changed.
+static CastPlan plan_bounce(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
+{
+	return plan_reflection(o, s, r);
+}
+
 CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest &r, const PrevDetect &prev, const Knobs &k, GridStates &gs)
 {
 	if (shadow_entry(r.entry)) return plan_shadow(o, s, r);
 	if (reflection_entry(r.entry)) return plan_reflection(o, s, r);
 	if (hemisphere_entry(r.entry)) return plan_hemisphere(o, s, r);
+	if (bounce_entry(r.entry)) return plan_bounce(o, s, r);
 	CastPlan c;
 	const uint64_t n = r.count;
 	const bool auto_k = o.kernel == MRT_KERNEL_AUTO, coherent = (r.flags & MRT_FLAG_COHERENT) != 0;

@@ -44,13 +44,16 @@ struct SceneFacts {
 // pixels * lights (shadow rays made in the kernel from hit records: an unsorted, non-coherent any-hit batch).  ENTRY_REFLECTION /
 // ENTRY_GRID_REFLECTION: mrt_cast_reflections / mrt_cast_grid_reflections, count = records (mirror rays made in the kernel: an
 // unsorted, non-coherent closest-hit batch).  ENTRY_HEMISPHERE / ENTRY_GRID_HEMISPHERE: mrt_cast_hemisphere / mrt_cast_grid_hemisphere,
-// count = pixels * samples (cosine-weighted hemisphere rays made in the kernel: an unsorted, non-coherent batch in either mode)
+// count = pixels * samples (cosine-weighted hemisphere rays made in the kernel: an unsorted, non-coherent batch in either mode).
+// ENTRY_BOUNCE / ENTRY_GRID_BOUNCE: mrt_cast_bounce / mrt_cast_grid_bounce, count = records (the path tracer's bounce rays made in the
+// kernel: an unsorted, non-coherent closest-hit batch)
 enum Entry : uint32_t { ENTRY_CAST, ENTRY_SUBMIT, ENTRY_CHUNK, ENTRY_GRID, ENTRY_TILED, ENTRY_SHADOW, ENTRY_GRID_SHADOW,
-	ENTRY_REFLECTION, ENTRY_GRID_REFLECTION, ENTRY_HEMISPHERE, ENTRY_GRID_HEMISPHERE };
+	ENTRY_REFLECTION, ENTRY_GRID_REFLECTION, ENTRY_HEMISPHERE, ENTRY_GRID_HEMISPHERE, ENTRY_BOUNCE, ENTRY_GRID_BOUNCE };
 inline bool ray_entry(Entry e) { return e <= ENTRY_CHUNK; } // rays from an array, through enqueue_cast
 inline bool shadow_entry(Entry e) { return e == ENTRY_SHADOW || e == ENTRY_GRID_SHADOW; }
 inline bool reflection_entry(Entry e) { return e == ENTRY_REFLECTION || e == ENTRY_GRID_REFLECTION; }
 inline bool hemisphere_entry(Entry e) { return e == ENTRY_HEMISPHERE || e == ENTRY_GRID_HEMISPHERE; }
+inline bool bounce_entry(Entry e) { return e == ENTRY_BOUNCE || e == ENTRY_GRID_BOUNCE; }
 
 struct CastRequest {
 	Entry entry = ENTRY_CAST;
@@ -138,8 +141,8 @@ inline uint32_t schedule_slots(uint32_t n_units, bool pieces)
 }
 
 uint32_t tile_w_log2(const mrt_options &o);
-// Plans a cast.  May select (and reset) the grid state of the cast in `gs` (never for a shadow, reflection or hemisphere entry: those read
-// neither `prev` nor `gs`).
+// Plans a cast.  May select (and reset) the grid state of the cast in `gs` (never for a shadow, reflection, hemisphere or bounce entry: those
+// read neither `prev` nor `gs`).
 CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest &r, const PrevDetect &prev, const Knobs &k, GridStates &gs);
 
 } // namespace mrt

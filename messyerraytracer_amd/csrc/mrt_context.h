@@ -21,6 +21,9 @@ hipError_t launch_reflection(const TraceParams &p, const ReflectParams &s, int s
 // hemisphere casts (hemisphere_kernel.h): src = SRC_HEMI_*, any_hit: one byte per entry instead of a record; the rest as launch_shadow
 hipError_t launch_hemisphere(const TraceParams &p, const HemiParams &s, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
+// bounce casts (bounce_kernel.h): src = SRC_BOUNCE_*; the rest as launch_shadow
+hipError_t launch_bounce(const TraceParams &p, const BounceParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
 hipError_t launch_build_rows4(const Dev4Node *nodes4, const TriHot *hot, const TriCold *cold, uint32_t n_nodes4, uint32_t n_tris,
 		void *rows, hipStream_t stream);
 hipError_t launch_build_rows(const DevNode *nodes, const TriHot *hot, const TriCold *cold, uint32_t n_nodes, uint32_t n_tris,

@@ -170,10 +170,12 @@ struct TraceParams {
 // kernels (SRC_CAST: the rays of an ordinary cast, the instantiations that existed before).
 enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, SRC_SHADOW_GRID = 3,
 	SRC_REFLECT_RAY32 = 4, SRC_REFLECT_HOST = 5, SRC_REFLECT_GRID = 6,
-	SRC_HEMI_RAY32 = 7, SRC_HEMI_HOST = 8, SRC_HEMI_GRID = 9 };
+	SRC_HEMI_RAY32 = 7, SRC_HEMI_HOST = 8, SRC_HEMI_GRID = 9,
+	SRC_BOUNCE_RAY32 = 10, SRC_BOUNCE_HOST = 11, SRC_BOUNCE_GRID = 12 };
 constexpr bool shadow_source(int src) { return src >= SRC_SHADOW_RAY32 && src <= SRC_SHADOW_GRID; }
 constexpr bool reflection_source(int src) { return src >= SRC_REFLECT_RAY32 && src <= SRC_REFLECT_GRID; }
 constexpr bool hemisphere_source(int src) { return src >= SRC_HEMI_RAY32 && src <= SRC_HEMI_GRID; }
+constexpr bool bounce_source(int src) { return src >= SRC_BOUNCE_RAY32 && src <= SRC_BOUNCE_GRID; }
 // the result of an entry is one byte (1 = no occluder, or no ray): every shadow cast, and a hemisphere cast in any-hit mode
 constexpr bool lit_output(int src, bool any_hit) { return shadow_source(src) || (hemisphere_source(src) && any_hit); }
 enum ShadowKind : uint32_t { SHADOW_OFF = 0, SHADOW_DIRECTIONAL = 1, SHADOW_POINT = 2 }; // OFF: cast_shadows == 0 (lit)
@@ -208,6 +210,21 @@ struct HemiParams {
 	uint32_t seed_add;         // frame * 6529 + 7 (+ y0 * grid_w * 1009 for a row band): seed = pixel * 1009 + seed_add
 	float t_max;               // t_max of every ray
 	HemiJump jump[MRT_MAX_HEMISPHERE_SAMPLES];
+};
+
+// ---- the path tracer's bounce (bounce_kernel.h): one closest-hit ray per hit record, lobe chosen and sampled in the kernel ---------
+// Entry i of a bounce cast is record i; TraceParams::count = records, hits = the output records, rays = the incoming rays as for
+// reflections.  The generator's state before the lobe draw is jump.a * state0 + jump.c (bounce_jump, cast.hip).
+struct BounceParams {
+	const void *records;       // mrt_hit32 (SRC_BOUNCE_RAY32, SRC_BOUNCE_GRID) or mrt_host_hit44 (SRC_BOUNCE_HOST)
+	const uint8_t *select;     // optional: 0 = no ray for this record
+	const float *surface;      // optional: {metallic, roughness} per record; null: the two constants below for every record
+	void *out_rays;            // optional: the rays made, mrt_ray32 (or mrt_host_ray60 for SRC_BOUNCE_HOST)
+	uint8_t *out_lobe;         // optional: MRT_LOBE_* per record
+	uint32_t seed_add;         // frame * 6529 + 7 (+ y0 * grid_w * 1009 for a row band): seed = record * 1009 + seed_add
+	float t_max;               // t_max of every ray
+	float metallic, roughness; // as the descriptor gave them (clamped in the kernel like a record's pair)
+	HemiJump jump;             // (A, C) of draw first_draw
 };
 
 // host-side preparation (scene_prep.cpp)

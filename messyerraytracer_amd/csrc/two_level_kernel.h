@@ -17,6 +17,7 @@ __global__ __launch_bounds__(MRT_WG) void trace_two_level_kernel(const TracePara
 	const ShadowParams *sh = nullptr;
 	const ReflectParams *rf = nullptr;
 	const HemiParams *hm = nullptr;
+	const BounceParams *bn = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 
