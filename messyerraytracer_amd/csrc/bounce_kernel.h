@@ -1,12 +1,11 @@
 // bounce_kernel.h — the path tracer's bounce made in the trace kernels (mrt_cast_bounce / mrt_cast_grid_bounce).
-// Included by kernels.hip (inside namespace mrt, after hemisphere_kernel.h, before the kernels that use it).
+// Included by kernels.hip (inside namespace mrt, after source_common.h, before the kernels that use it).
 //
 // PathTrace::sample_bounce of the reference (src/modules/graphics/path_trace.h:185-251): one draw chooses the lobe against a specular
 // probability made from the surface's metallic and roughness, then either a GGX half vector (ggx_sample_half, :132-155) with the view
 // direction reflected about it, or the cosine hemisphere of hemisphere_kernel.h.  The direction alone: weights, throughput and roulette
-// are the renderer's.  The lane kernels, persistent or not, and the two-level kernels take the source as a template parameter
-// (SRC_BOUNCE_*); entry i is record i and its result is the record mrt_cast(MRT_MODE_NEAREST) writes for the ray.  Plain float
-// operations in this order (nothing is contracted):
+// are the renderer's.  A source family of source_common.h (SRC_BOUNCE_*, closest-hit only); entry i is record i and its result is the
+// record mrt_cast(MRT_MODE_NEAREST) writes for the ray.  Plain float operations in this order (nothing is contracted):
 //   p, d, n  as hemisphere_kernel.h takes them; n = -n if ((nx*dx + ny*dy) + nz*dz) > 0
 //   m  = fminf(fmaxf(metallic, 0), 1), ro = fminf(fmaxf(roughness, 0.04f), 1)      (surface[2i], surface[2i + 1], or the constants;
 //                                                                                    a NaN takes the lower bound)
@@ -21,55 +20,19 @@
 //   normalized: l2 = (x*x + y*y) + z*z, 0 if l2 == 0, else three divisions by sqrt(l2)
 //   org = p + n * 1e-3, t_min = 1e-4, t_max = the descriptor's
 // No ray: a primary miss, select[i] == 0, or ((nx*dirx + ny*diry) + nz*dirz) <= 0 (the reference's "below surface").  The placeholder
-// ray and its record, as reflection_kernel.h writes them; lobe byte MRT_LOBE_NONE.  Nothing walks.
+// ray and its record (source_common.h); lobe byte MRT_LOBE_NONE.  Nothing walks.
 #pragma once
-
-// Vector3::normalized as hemisphere_kernel.h restates it
-__device__ __forceinline__ void bounce_normalize(float &x, float &y, float &z)
-{
-	const float l2 = (x * x + y * y) + z * z;
-	if (l2 == 0.0f) { x = y = z = 0.0f; }
-	else { const float l = __builtin_sqrtf(l2); x /= l; y /= l; z /= l; }
-}
 
 // The bounce ray of entry i (written to out_rays when asked for, its lobe to out_lobe).  false: no ray -- r is the placeholder.
 template <int SRC>
 __device__ __forceinline__ bool bounce_ray(const TraceParams &p, const BounceParams &s, uint64_t i, RayRegs &r)
 {
 	bool traced = s.select == nullptr || s.select[i] != 0;
-	float px = 0.0f, py = 0.0f, pz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f;
-	if (traced) {
-		if (SRC == SRC_BOUNCE_HOST) {
-			const float *h = reinterpret_cast<const float *>(s.records) + i * 11u;
-			if (reinterpret_cast<const uint32_t *>(h)[9] == 0xFFFFFFFFu) traced = false;
-			else {
-				const float *v = reinterpret_cast<const float *>(p.rays) + i * 15u;
-				px = h[1]; py = h[2]; pz = h[3];
-				nx = h[4]; ny = h[5]; nz = h[6];
-				dx = v[3]; dy = v[4]; dz = v[5];
-			}
-		} else {
-			const float4 *q = reinterpret_cast<const float4 *>(s.records) + i * 2u;
-			const float4 a = q[0];
-			if (__float_as_int(a.y) == -1) traced = false;
-			else {
-				const float4 b = q[1];
-				RayRegs o;
-				if (SRC == SRC_BOUNCE_GRID) { uint64_t gx; const uint64_t gy = udivmod(i, p.grid_w, gx); grid_ray(p, (uint32_t)gx, (uint32_t)gy, o); }
-				else {
-					const float4 *v = reinterpret_cast<const float4 *>(p.rays) + i * 2u;
-					const float4 c = v[0], d = v[1];
-					o.ox = c.x; o.oy = c.y; o.oz = c.z; o.dx = d.x; o.dy = d.y; o.dz = d.z;
-				}
-				px = o.ox + o.dx * a.x; py = o.oy + o.dy * a.x; pz = o.oz + o.dz * a.x;
-				nx = b.x; ny = b.y; nz = b.z;
-				dx = o.dx; dy = o.dy; dz = o.dz;
-			}
-		}
-	}
+	Surface sf = {};
+	if (traced) traced = record_surface<SRC == SRC_BOUNCE_HOST, SRC == SRC_BOUNCE_GRID>(p, s.records, i, sf);
 	uint32_t lobe = MRT_LOBE_NONE;
 	if (traced) {
-		if ((nx * dx + ny * dy) + nz * dz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+		face_normal(sf);
 		float metallic = s.metallic, roughness = s.roughness;
 		if (s.surface != nullptr) { metallic = s.surface[i * 2u]; roughness = s.surface[i * 2u + 1u]; }
 		const float m = fminf(fmaxf(metallic, 0.0f), 1.0f), ro = fminf(fmaxf(roughness, 0.04f), 1.0f);
@@ -90,27 +53,20 @@ __device__ __forceinline__ bool bounce_ray(const TraceParams &p, const BouncePar
 		} else {
 			rr = __builtin_sqrtf(u1); z = __builtin_sqrtf(fmaxf(0.0f, 1.0f - u1));
 		}
-		float cs, sn;
-		sincos_2pi(u2, cs, sn);
-		const float x = rr * cs, y = rr * sn;
-		const float sign = __builtin_copysignf(1.0f, nz);
-		const float a = -1.0f / (sign + nz), b = (nx * ny) * a;
-		const float tx = 1.0f + ((sign * nx) * nx) * a, ty = sign * b, tz = (-sign) * nx;
-		const float bx = b, by = sign + (ny * ny) * a, bz = -ny;
-		float vx = (tx * x + bx * y) + nx * z, vy = (ty * x + by * y) + ny * z, vz = (tz * x + bz * y) + nz * z;
-		bounce_normalize(vx, vy, vz);
+		float vx, vy, vz;
+		onb_direction(sf, rr, z, u2, vx, vy, vz);
 		if (specular) { // v is the half vector: the view direction reflected about it
-			float wx = -dx, wy = -dy, wz = -dz;
-			bounce_normalize(wx, wy, wz);
+			float wx = -sf.dx, wy = -sf.dy, wz = -sf.dz;
+			normalize3(wx, wy, wz);
 			const float k = 2.0f * fmaxf((wx * vx + wy * vy) + wz * vz, 0.0f);
 			vx = vx * k - wx; vy = vy * k - wy; vz = vz * k - wz;
-			bounce_normalize(vx, vy, vz);
+			normalize3(vx, vy, vz);
 		}
-		if ((nx * vx + ny * vy) + nz * vz <= 0.0f) traced = false; // below the surface: an invalid sample, no ray
+		if ((sf.nx * vx + sf.ny * vy) + sf.nz * vz <= 0.0f) traced = false; // below the surface: an invalid sample, no ray
 		else {
 			lobe = specular ? MRT_LOBE_SPECULAR : MRT_LOBE_DIFFUSE;
 			r.dx = vx; r.dy = vy; r.dz = vz;
-			r.ox = px + nx * 1e-3f; r.oy = py + ny * 1e-3f; r.oz = pz + nz * 1e-3f;
+			r.ox = sf.px + sf.nx * 1e-3f; r.oy = sf.py + sf.ny * 1e-3f; r.oz = sf.pz + sf.nz * 1e-3f;
 			r.t_min = 1e-4f; r.t_max = s.t_max;
 		}
 	}
@@ -121,10 +77,11 @@ __device__ __forceinline__ bool bounce_ray(const TraceParams &p, const BouncePar
 }
 
 // The ray of entry i, or (false) the record of an entry without one, stored.
-template <int SRC>
-__device__ __forceinline__ bool bounce_entry(const TraceParams &p, const BounceParams &s, uint64_t i, RayRegs &r)
+template <int SRC, bool ANY_HIT>
+__device__ __forceinline__ bool source_entry(const TraceParams &p, const BounceParams &s, uint64_t i, RayRegs &r)
 {
+	static_assert(bounce_source(SRC) && !ANY_HIT, "bounce sources are closest-hit");
 	if (bounce_ray<SRC>(p, s, i, r)) return true;
-	store_no_reflection(p, i);
+	store_placeholder_record(p, i);
 	return false;
 }

@@ -68,21 +68,13 @@ void note_queued(mrt_ctx *ctx, uint32_t kernel)
 	std::snprintf(ctx->queued_variant, sizeof(ctx->queued_variant), "%s", mrt::last_trace_variant());
 }
 
-// A cast whose rays are made in the kernel launches its source's instantiation of the same kernel: a shadow cast (shadow: its lights
-// and records, src its SRC_SHADOW_* source), a reflection cast (reflect: its records, mask and outputs, src its SRC_REFLECT_* source)
-// a hemisphere cast (hemi: its records, mask, outputs and jump constants, src its SRC_HEMI_* source, any_hit its mode) or a bounce cast
-// (bounce: its records, mask, materials, outputs and jump constants, src its SRC_BOUNCE_* source).
-struct SourceLaunch { const mrt::ShadowParams *shadow; const mrt::ReflectParams *reflect; int src; const mrt::HemiParams *hemi = nullptr; bool any_hit = false;
-	const mrt::BounceParams *bounce = nullptr; };
-
-hipError_t launch_source(const SourceLaunch &sl, const mrt::TraceParams &p, unsigned long long *next_ray, uint32_t *ovf,
-		const mrt::LaneLaunch &l, hipStream_t stream)
-{
-	if (sl.shadow) return mrt::launch_shadow(p, *sl.shadow, sl.src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
-	if (sl.bounce) return mrt::launch_bounce(p, *sl.bounce, sl.src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
-	if (sl.hemi) return mrt::launch_hemisphere(p, *sl.hemi, sl.src, sl.any_hit, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
-	return mrt::launch_reflection(p, *sl.reflect, sl.src, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, stream);
-}
+// A cast whose rays are made in the kernel launches its source family's instantiation of the same lane kernels: the family's launcher
+// (mrt::launch_source<S>), its parameters (an S) and which of its three sources.  launch_planned and launch_lane pass it through.
+struct SourceLaunch {
+	hipError_t (*launch)(const mrt::TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+	const void *params;
+	int src;
+};
 
 int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uint64_t count, bool any_hit, const SourceLaunch *sh = nullptr)
 {
@@ -90,7 +82,7 @@ int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uin
 	p.kernel = l.kernel;
 	if (!l.persistent) {
 		p.sparse_lanes = l.sparse_lanes;
-		if (sh) HIP_TRY(ctx, launch_source(*sh, p, nullptr, nullptr, mrt::LaneLaunch(), ctx->stream));
+		if (sh) HIP_TRY(ctx, sh->launch(p, sh->params, sh->src, any_hit, nullptr, nullptr, 0u, 0u, 0u, 0u, ctx->stream));
 		else HIP_TRY(ctx, mrt::launch_trace(p, any_hit, l.count, ctx->stream));
 		note_queued(ctx, p.kernel);
 		return MRT_OK;
@@ -103,7 +95,7 @@ int launch_lane(mrt_ctx *ctx, const mrt::LaneLaunch &l, mrt::TraceParams &p, uin
 	// eight ray counters (one per region of the batch), 128 bytes apart
 	unsigned long long *next_ray = ctx->d_counters + mrt::kNextRayOff;
 	HIP_TRY(ctx, hipMemsetAsync(next_ray, 0, 128 * sizeof(unsigned long long), ctx->stream));
-	if (sh) HIP_TRY(ctx, launch_source(*sh, p, next_ray, ovf, l, ctx->stream));
+	if (sh) HIP_TRY(ctx, sh->launch(p, sh->params, sh->src, any_hit, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, ctx->stream));
 	else HIP_TRY(ctx, mrt::launch_trace_persistent(p, next_ray, ovf, l.lds_depth, l.refill, l.leaf_wait, l.blocks, any_hit, l.count, ctx->stream));
 	note_queued(ctx, p.kernel);
 	return MRT_OK;
@@ -287,66 +279,32 @@ int cast_host_pipelined(mrt_ctx *ctx, const void *rays, void *hits, uint64_t cou
 	return finish_timing(ctx, false, launches >= 2, false);
 }
 
-// The shadow casts (mrt_cast_shadows, mrt_cast_grid_shadows) after their own checks: p holds the scene, the grid (grid source) and
-// the primary rays (SRC_SHADOW_RAY32); count = records.
-int cast_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
-		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+// What every record-driven cast checks before it touches the device, in this order: its flags (HOST_LAYOUT for the entry that takes
+// arrays, ASYNC), then invalid() (what the family's own checks of its arguments find, or null; the arguments are not looked at before the
+// flags are known), the scene, a pending dispatch.  MRT_OK: go on (an empty cast is OK only after all of those: run_source_cast).
+template <class Invalid>
+int source_cast_check(mrt_ctx *ctx, bool array_entry, uint32_t flags, const char *unknown_flag, Invalid invalid)
 {
-	const uint32_t known = (entry == mrt::ENTRY_SHADOW ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
-	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a shadow cast");
-	if (n_lights > MRT_MAX_LIGHTS) return fail(ctx, MRT_ERR_INVALID, "more than MRT_MAX_LIGHTS lights");
-	if (!d_hits || !d_mask || (n_lights && !lights)) return fail(ctx, MRT_ERR_INVALID, "null hits / lights / mask");
-	if (n_lights && count > ~0ull / n_lights) return fail(ctx, MRT_ERR_INVALID, "count * n_lights overflows");
-	mrt::ShadowParams s;
-	std::memset(&s, 0, sizeof(s));
-	s.records = d_hits; s.pixels = count;
-	for (uint32_t l = 0; l < n_lights; l++) {
-		const mrt_light &L = lights[l];
-		if (L.type > MRT_LIGHT_SPOT) return fail(ctx, MRT_ERR_INVALID, "unknown light type");
-		mrt::ShadowLight &d = s.light[l];
-		d.kind = !L.cast_shadows ? mrt::SHADOW_OFF : (L.type == MRT_LIGHT_DIRECTIONAL ? mrt::SHADOW_DIRECTIONAL : mrt::SHADOW_POINT);
-		const float *v = L.type == MRT_LIGHT_DIRECTIONAL ? L.direction : L.position;
-		d.v[0] = v[0]; d.v[1] = v[1]; d.v[2] = v[2];
-	}
+	const uint32_t known = (array_entry ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
+	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, unknown_flag);
+	if (const char *why = invalid()) return fail(ctx, MRT_ERR_INVALID, why);
 	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
 	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (count == 0 || n_lights == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	p.hits = d_mask; p.count = count * n_lights; p.query_mask = query_mask;
-	p.out_fmt = mrt::OUT_BOOL8;
-	// (the plan reads neither the detected grid nor the grid states: an empty PrevDetect)
-	const mrt::CastRequest r{entry, p.count, flags, MRT_MODE_ANY_HIT};
-	const mrt::CastPlan c = mrt::plan_cast(ctx->opts, scene_facts(ctx), r, mrt::PrevDetect{}, ctx->knobs, ctx->grids);
-	const SourceLaunch sh{&s, nullptr, src};
-	int rc = launch_planned(ctx, c, r, p, &sh);
-	if (rc) return rc;
-	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
-	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
+	return MRT_OK;
 }
 
-// The reflection casts (mrt_cast_reflections, mrt_cast_grid_reflections) after their own checks: p holds the scene, the grid (grid
-// source) and the incoming rays (SRC_REFLECT_RAY32, SRC_REFLECT_HOST); count = records.
-int cast_reflections(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
-		const uint8_t *d_select, float max_distance, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
+// Plans and runs a record-driven cast of family S: p holds the scene, the batch (count = entries, hits = the output, out_fmt) and what
+// the source reads of the incoming rays (rays or the grid); s the family's parameters.  Blocking unless ASYNC.  No entries (no
+// records, or no lights or samples for them): MRT_OK, nothing is touched.
+template <class S>
+int run_source_cast(mrt_ctx *ctx, mrt::Entry entry, int src, int mode, mrt::TraceParams &p, const S &s, uint32_t flags)
 {
-	const uint32_t known = (entry == mrt::ENTRY_REFLECTION ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
-	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a reflection cast");
-	if (!d_hits || !d_out_hits) return fail(ctx, MRT_ERR_INVALID, "null hits / output hits");
-	if (!(max_distance > 0.0f && max_distance <= FLT_MAX)) return fail(ctx, MRT_ERR_INVALID, "max_distance must be finite and > 0");
-	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (count == 0) return MRT_OK;
+	if (p.count == 0) return MRT_OK;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	mrt::ReflectParams s;
-	s.records = d_hits; s.select = d_select; s.out_rays = d_out_rays; s.max_distance = max_distance;
-	p.hits = d_out_hits; p.count = count; p.query_mask = query_mask;
-	p.out_fmt = src == mrt::SRC_REFLECT_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32;
 	// (the plan reads neither the detected grid nor the grid states: an empty PrevDetect)
-	const mrt::CastRequest r{entry, count, flags, MRT_MODE_NEAREST};
+	const mrt::CastRequest r{entry, p.count, flags, mode};
 	const mrt::CastPlan c = mrt::plan_cast(ctx->opts, scene_facts(ctx), r, mrt::PrevDetect{}, ctx->knobs, ctx->grids);
-	const SourceLaunch sl{nullptr, &s, src};
+	const SourceLaunch sl{&mrt::launch_source<S>, &s, src};
 	int rc = launch_planned(ctx, c, r, p, &sl);
 	if (rc) return rc;
 	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
@@ -355,8 +313,58 @@ int cast_reflections(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &
 	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
 }
 
+// The checks of a shadow cast's arguments that need no context (lights and nulls: before the scene), filling s as they go.
+const char *shadow_invalid(const void *d_hits, uint64_t count, const mrt_light *lights, uint32_t n_lights, const uint8_t *d_mask, mrt::ShadowParams &s)
+{
+	if (n_lights > MRT_MAX_LIGHTS) return "more than MRT_MAX_LIGHTS lights";
+	if (!d_hits || !d_mask || (n_lights && !lights)) return "null hits / lights / mask";
+	if (n_lights && count > ~0ull / n_lights) return "count * n_lights overflows";
+	std::memset(&s, 0, sizeof(s));
+	s.records = d_hits; s.pixels = count;
+	for (uint32_t l = 0; l < n_lights; l++) {
+		const mrt_light &L = lights[l];
+		if (L.type > MRT_LIGHT_SPOT) return "unknown light type";
+		mrt::ShadowLight &d = s.light[l];
+		d.kind = !L.cast_shadows ? mrt::SHADOW_OFF : (L.type == MRT_LIGHT_DIRECTIONAL ? mrt::SHADOW_DIRECTIONAL : mrt::SHADOW_POINT);
+		const float *v = L.type == MRT_LIGHT_DIRECTIONAL ? L.direction : L.position;
+		d.v[0] = v[0]; d.v[1] = v[1]; d.v[2] = v[2];
+	}
+	return nullptr;
+}
+
+// The shadow casts (mrt_cast_shadows, mrt_cast_grid_shadows) after their own checks: p holds the scene, the grid (grid source) and
+// the primary rays (SRC_SHADOW_RAY32); count = records.
+int cast_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
+		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	mrt::ShadowParams s;
+	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_SHADOW, flags, "unknown flag for a shadow cast",
+			[&] { return shadow_invalid(d_hits, count, lights, n_lights, d_mask, s); })) return rc;
+	p.hits = d_mask; p.count = count * n_lights; p.query_mask = query_mask;
+	p.out_fmt = mrt::OUT_BOOL8;
+	return run_source_cast(ctx, entry, src, MRT_MODE_ANY_HIT, p, s, flags);
+}
+
+// The reflection casts (mrt_cast_reflections, mrt_cast_grid_reflections) after their own checks: p holds the scene, the grid (grid
+// source) and the incoming rays (SRC_REFLECT_RAY32, SRC_REFLECT_HOST); count = records.
+int cast_reflections(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
+		const uint8_t *d_select, float max_distance, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
+{
+	const auto invalid = [&]() -> const char * {
+		if (!d_hits || !d_out_hits) return "null hits / output hits";
+		if (!(max_distance > 0.0f && max_distance <= FLT_MAX)) return "max_distance must be finite and > 0";
+		return nullptr;
+	};
+	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_REFLECTION, flags, "unknown flag for a reflection cast", invalid)) return rc;
+	mrt::ReflectParams s;
+	s.records = d_hits; s.select = d_select; s.out_rays = d_out_rays; s.max_distance = max_distance;
+	p.hits = d_out_hits; p.count = count; p.query_mask = query_mask;
+	p.out_fmt = src == mrt::SRC_REFLECT_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32;
+	return run_source_cast(ctx, entry, src, MRT_MODE_NEAREST, p, s, flags);
+}
+
 // The checks of a hemisphere descriptor and its outputs that need no context: what the entry points refuse before anything else.
-const char *hemisphere_invalid(const mrt_hemisphere *desc, const void *d_hits, const void *d_out, const void *d_out_rays, int mode)
+const char *hemisphere_invalid(const mrt_hemisphere *desc, const void *d_hits, uint64_t count, const void *d_out, const void *d_out_rays, int mode)
 {
 	if (!desc) return "null descriptor";
 	if (desc->n_samples < 1u || desc->n_samples > MRT_MAX_HEMISPHERE_SAMPLES) return "n_samples outside 1 .. MRT_MAX_HEMISPHERE_SAMPLES";
@@ -364,22 +372,29 @@ const char *hemisphere_invalid(const mrt_hemisphere *desc, const void *d_hits, c
 	if (mode != MRT_MODE_NEAREST && mode != MRT_MODE_ANY_HIT) return "unknown mode";
 	if (mode == MRT_MODE_ANY_HIT && d_out_rays) return "any-hit writes no rays: d_out_rays must be null";
 	if (!d_hits || !d_out) return "null hits / output";
+	if (count > ~0ull / desc->n_samples) return "count * n_samples overflows";
 	return nullptr;
 }
 
-// (A, C) with: PCG32 state before draw k = A * state0 + C, for the first draw of every sample (k = first_draw + 2 * sample), all
-// modulo 2^32: one pass over the draws on the host, once per call, so that the kernel has no loop over draws.
-void hemisphere_jumps(uint32_t first_draw, uint32_t n_samples, mrt::HemiJump *out)
+// (A, C) with: PCG32 state before draw k = A * state0 + C, modulo 2^32, by squaring: the step (a, c) applied twice is (a * a, a * c + c).
+// Once per call on the host, so that the kernel has no loop over draws.
+mrt::HemiJump pcg_jump(uint32_t first_draw)
 {
-	// (A, C) of `first_draw` steps by squaring: the step (a, c) applied twice is (a * a, a * c + c)
 	uint32_t A = 1u, C = 0u, a = mrt::kPcgMul, c = mrt::kPcgInc;
 	for (uint32_t k = first_draw; k != 0u; k >>= 1) {
 		if (k & 1u) { A = a * A; C = a * C + c; }
 		c = a * c + c; a = a * a;
 	}
+	return mrt::HemiJump{A, C};
+}
+
+// The jump of the first draw of every sample (k = first_draw + 2 * sample): one pass over the draws.
+void hemisphere_jumps(uint32_t first_draw, uint32_t n_samples, mrt::HemiJump *out)
+{
+	mrt::HemiJump j = pcg_jump(first_draw);
 	for (uint32_t s = 0; s < n_samples; s++) {
-		out[s].a = A; out[s].c = C;
-		for (int k = 0; k < 2; k++) { A = mrt::kPcgMul * A; C = mrt::kPcgMul * C + mrt::kPcgInc; }
+		out[s] = j;
+		for (int k = 0; k < 2; k++) { j.a = mrt::kPcgMul * j.a; j.c = mrt::kPcgMul * j.c + mrt::kPcgInc; }
 	}
 }
 
@@ -388,14 +403,8 @@ void hemisphere_jumps(uint32_t first_draw, uint32_t n_samples, mrt::HemiJump *ou
 int cast_hemisphere(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count, uint32_t pixel0,
 		const mrt_hemisphere *desc, void *d_out, void *d_out_rays, uint32_t query_mask, int mode, uint32_t flags)
 {
-	const uint32_t known = (entry == mrt::ENTRY_HEMISPHERE ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
-	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a hemisphere cast");
-	if (const char *why = hemisphere_invalid(desc, d_hits, d_out, d_out_rays, mode)) return fail(ctx, MRT_ERR_INVALID, why);
-	if (count > ~0ull / desc->n_samples) return fail(ctx, MRT_ERR_INVALID, "count * n_samples overflows");
-	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_HEMISPHERE, flags, "unknown flag for a hemisphere cast",
+			[&] { return hemisphere_invalid(desc, d_hits, count, d_out, d_out_rays, mode); })) return rc;
 	const bool any = mode == MRT_MODE_ANY_HIT;
 	mrt::HemiParams s;
 	std::memset(&s, 0, sizeof(s));
@@ -404,17 +413,7 @@ int cast_hemisphere(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p
 	hemisphere_jumps(desc->first_draw, desc->n_samples, s.jump);
 	p.hits = d_out; p.count = count * desc->n_samples; p.query_mask = query_mask;
 	p.out_fmt = any ? mrt::OUT_BOOL8 : (src == mrt::SRC_HEMI_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32);
-	// (the plan reads neither the detected grid nor the grid states: an empty PrevDetect)
-	const mrt::CastRequest r{entry, p.count, flags, mode};
-	const mrt::CastPlan c = mrt::plan_cast(ctx->opts, scene_facts(ctx), r, mrt::PrevDetect{}, ctx->knobs, ctx->grids);
-	SourceLaunch sl{nullptr, nullptr, src};
-	sl.hemi = &s; sl.any_hit = any;
-	int rc = launch_planned(ctx, c, r, p, &sl);
-	if (rc) return rc;
-	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
-	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
+	return run_source_cast(ctx, entry, src, mode, p, s, flags);
 }
 
 // The checks of a bounce descriptor and its outputs that need no context: what the entry points refuse before anything else.
@@ -430,48 +429,22 @@ const char *bounce_invalid(const mrt_bounce *desc, const void *d_hits, const voi
 	return nullptr;
 }
 
-// (A, C) with: PCG32 state before draw first_draw = A * state0 + C, modulo 2^32 (the method of hemisphere_jumps: steps by squaring)
-mrt::HemiJump bounce_jump(uint32_t first_draw)
-{
-	uint32_t A = 1u, C = 0u, a = mrt::kPcgMul, c = mrt::kPcgInc;
-	for (uint32_t k = first_draw; k != 0u; k >>= 1) {
-		if (k & 1u) { A = a * A; C = a * C + c; }
-		c = a * c + c; a = a * a;
-	}
-	return mrt::HemiJump{A, C};
-}
-
 // The bounce casts (mrt_cast_bounce, mrt_cast_grid_bounce) after their own checks: p holds the scene, the grid (grid source) and the
 // incoming rays (SRC_BOUNCE_RAY32, SRC_BOUNCE_HOST); count = records, pixel0 = the pixel index of record 0.
 int cast_bounce(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count, uint32_t pixel0,
 		const mrt_bounce *desc, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
 {
-	const uint32_t known = (entry == mrt::ENTRY_BOUNCE ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
-	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a bounce cast");
-	if (const char *why = bounce_invalid(desc, d_hits, d_out_hits)) return fail(ctx, MRT_ERR_INVALID, why);
-	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_BOUNCE, flags, "unknown flag for a bounce cast",
+			[&] { return bounce_invalid(desc, d_hits, d_out_hits); })) return rc;
 	mrt::BounceParams s;
 	std::memset(&s, 0, sizeof(s));
 	s.records = d_hits; s.select = desc->d_select; s.surface = desc->d_surface; s.out_rays = d_out_rays; s.out_lobe = desc->d_out_lobe;
 	s.t_max = desc->t_max; s.metallic = desc->metallic; s.roughness = desc->roughness;
 	s.seed_add = pixel0 * 1009u + desc->frame * 6529u + 7u;
-	s.jump = bounce_jump(desc->first_draw);
+	s.jump = pcg_jump(desc->first_draw);
 	p.hits = d_out_hits; p.count = count; p.query_mask = query_mask;
 	p.out_fmt = src == mrt::SRC_BOUNCE_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32;
-	// (the plan reads neither the detected grid nor the grid states: an empty PrevDetect)
-	const mrt::CastRequest r{entry, count, flags, MRT_MODE_NEAREST};
-	const mrt::CastPlan c = mrt::plan_cast(ctx->opts, scene_facts(ctx), r, mrt::PrevDetect{}, ctx->knobs, ctx->grids);
-	SourceLaunch sl{nullptr, nullptr, src};
-	sl.bounce = &s;
-	int rc = launch_planned(ctx, c, r, p, &sl);
-	if (rc) return rc;
-	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
-	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
+	return run_source_cast(ctx, entry, src, MRT_MODE_NEAREST, p, s, flags);
 }
 
 } // namespace

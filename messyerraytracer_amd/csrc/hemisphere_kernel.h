@@ -1,50 +1,24 @@
 // hemisphere_kernel.h — cosine-weighted hemisphere rays made in the trace kernels (mrt_cast_hemisphere / mrt_cast_grid_hemisphere).
-// Included by kernels.hip (inside namespace mrt, after reflection_kernel.h, before the kernels that use it).
+// Included by kernels.hip (inside namespace mrt, after source_common.h, before the kernels that use it).
 //
 // The diffuse bounce of the reference's path tracer (cosine_hemisphere_sample, src/modules/graphics/path_trace.h:101-120, drawn
 // from the PCG32 of path_state.h:40-67 seeded as PathState::init seeds it), and with a short t_max and any-hit its ambient-occlusion
-// ray.  The lane kernels, persistent or not, and the two-level kernels take the source as a template parameter (SRC_HEMI_*); entry g
-// is the pair (sample g / pixels, pixel g % pixels).  Any-hit: one byte per entry, 1 - occluded.  Closest-hit: the record
+// ray.  A source family of source_common.h (SRC_HEMI_*, either mode); entry g is the pair (sample g / pixels, pixel g % pixels).  Any-hit: one byte per entry, 1 - occluded.  Closest-hit: the record
 // mrt_cast(MRT_MODE_NEAREST) writes for the ray.  Plain float operations in this order (nothing is contracted):
 //   p, d, n  as reflection_kernel.h takes them from the record and the incoming ray; n = -n if ((nx*dx + ny*dy) + nz*dz) > 0
 //   state0   = (inc + seed) * mul + inc  with seed = pixel_index * 1009 + frame * 6529 + 7           (PCG32::seed)
 //   state    = A * state0 + C            (A, C) of draw first_draw + 2 * sample: HemiParams::jump
 //   u1 = float(out(state)) * 2^-32, u2 = float(out(state * mul + inc)) * 2^-32                       (can be exactly 1.0)
 //   r = sqrt(u1), z = sqrt(max(0, 1 - u1))
-//   (cs, sn) = sincos_2pi(u2): the pair below, not a math library's                                  (mrt_hip.h says why)
+//   (cs, sn) = sincos_2pi(u2): source_common.h's pair, not a math library's                     (mrt_hip.h says why)
 //   x = r * cs, y = r * sn
 //   construct_onb(n): sign = copysign(1, nz), a = -1 / (sign + nz), b = (nx * ny) * a,
 //       t = (1 + ((sign * nx) * nx) * a, sign * b, (-sign) * nx), bt = (b, sign + (ny * ny) * a, -ny)
 //   v = (t * x + bt * y) + n * z per component, dir = v / sqrt((vx*vx + vy*vy) + vz*vz)  (0 if the sum is 0: Vector3::normalized)
 //   org = p + n * 1e-3, t_min = 1e-4, t_max = the descriptor's
 // No ray: a primary miss, select[pixel] == 0, or ((nx*dirx + ny*diry) + nz*dirz) <= 0 (the reference's "below surface").  Any-hit:
-// the byte is 1.  Closest-hit: the placeholder ray and its record, as reflection_kernel.h writes them.  Nothing walks.
+// the byte is 1.  Closest-hit: the placeholder ray and its record (source_common.h).  Nothing walks.
 #pragma once
-
-// PCG32::next's output permutation of a state, as PCG32::next_float scales it
-__device__ __forceinline__ float pcg_float(uint32_t state)
-{
-	const uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
-	return (float)((word >> 22u) ^ word) * 2.3283064e-10f; // 2^-32; 0xFFFFFF80 and above round to 2^32: 1.0
-}
-
-// cos and sin of 2 pi u for u in [0, 1]: the quadrant k = rint(4u) (ties to even), f = 4u - k in [-1/2, 1/2] (both exact),
-// x = f * float(pi / 2), Taylor polynomials to x^10 / x^11 in Horner form with separate multiplies and adds, then the quadrant's
-// swap and signs.  The same operations as messyerraytracer_amd/hemisphere.py: bit-identical on both sides.
-__device__ __forceinline__ void sincos_2pi(float u, float &cs, float &sn)
-{
-	const float a = u * 4.0f, k = __builtin_rintf(a), f = a - k;
-	const float x = f * 1.5707964e+00f, x2 = x * x;
-	float s = -2.5052108e-08f;
-	s = s * x2 + 2.7557319e-06f; s = s * x2 + -1.984127e-04f; s = s * x2 + 8.333334e-03f; s = s * x2 + -1.6666667e-01f;
-	s = x + (x * x2) * s;
-	float c = -2.755732e-07f;
-	c = c * x2 + 2.4801588e-05f; c = c * x2 + -1.3888889e-03f; c = c * x2 + 4.1666668e-02f; c = c * x2 + -5.0e-01f;
-	c = 1.0f + x2 * c;
-	const uint32_t q = (uint32_t)(int32_t)k & 3u;
-	cs = q == 0u ? c : q == 1u ? -s : q == 2u ? -c : s;
-	sn = q == 0u ? s : q == 1u ? c : q == 2u ? -s : -c;
-}
 
 // The hemisphere ray of entry g (written to out_rays when asked for).  false: no ray -- r is the placeholder.
 template <int SRC>
@@ -53,58 +27,21 @@ __device__ __forceinline__ bool hemisphere_ray(const TraceParams &p, const HemiP
 	uint64_t i;
 	const uint64_t si = udivmod(g, s.pixels, i);
 	bool traced = s.select == nullptr || s.select[i] != 0;
-	float px = 0.0f, py = 0.0f, pz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f;
+	Surface sf = {};
+	if (traced) traced = record_surface<SRC == SRC_HEMI_HOST, SRC == SRC_HEMI_GRID>(p, s.records, i, sf);
 	if (traced) {
-		if (SRC == SRC_HEMI_HOST) {
-			const float *h = reinterpret_cast<const float *>(s.records) + i * 11u;
-			if (reinterpret_cast<const uint32_t *>(h)[9] == 0xFFFFFFFFu) traced = false;
-			else {
-				const float *v = reinterpret_cast<const float *>(p.rays) + i * 15u;
-				px = h[1]; py = h[2]; pz = h[3];
-				nx = h[4]; ny = h[5]; nz = h[6];
-				dx = v[3]; dy = v[4]; dz = v[5];
-			}
-		} else {
-			const float4 *q = reinterpret_cast<const float4 *>(s.records) + i * 2u;
-			const float4 a = q[0];
-			if (__float_as_int(a.y) == -1) traced = false;
-			else {
-				const float4 b = q[1];
-				RayRegs o;
-				if (SRC == SRC_HEMI_GRID) { uint64_t gx; const uint64_t gy = udivmod(i, p.grid_w, gx); grid_ray(p, (uint32_t)gx, (uint32_t)gy, o); }
-				else {
-					const float4 *v = reinterpret_cast<const float4 *>(p.rays) + i * 2u;
-					const float4 c = v[0], d = v[1];
-					o.ox = c.x; o.oy = c.y; o.oz = c.z; o.dx = d.x; o.dy = d.y; o.dz = d.z;
-				}
-				px = o.ox + o.dx * a.x; py = o.oy + o.dy * a.x; pz = o.oz + o.dz * a.x;
-				nx = b.x; ny = b.y; nz = b.z;
-				dx = o.dx; dy = o.dy; dz = o.dz;
-			}
-		}
-	}
-	if (traced) {
-		if ((nx * dx + ny * dy) + nz * dz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+		face_normal(sf);
 		const HemiJump j = s.jump[si];
 		uint32_t state = (kPcgInc + ((uint32_t)i * 1009u + s.seed_add)) * kPcgMul + kPcgInc;
 		state = j.a * state + j.c;
 		const float u1 = pcg_float(state), u2 = pcg_float(state * kPcgMul + kPcgInc);
 		const float rr = __builtin_sqrtf(u1), z = __builtin_sqrtf(fmaxf(0.0f, 1.0f - u1));
-		float cs, sn;
-		sincos_2pi(u2, cs, sn);
-		const float x = rr * cs, y = rr * sn;
-		const float sign = __builtin_copysignf(1.0f, nz);
-		const float a = -1.0f / (sign + nz), b = (nx * ny) * a;
-		const float tx = 1.0f + ((sign * nx) * nx) * a, ty = sign * b, tz = (-sign) * nx;
-		const float bx = b, by = sign + (ny * ny) * a, bz = -ny;
-		float vx = (tx * x + bx * y) + nx * z, vy = (ty * x + by * y) + ny * z, vz = (tz * x + bz * y) + nz * z;
-		const float l2 = (vx * vx + vy * vy) + vz * vz;
-		if (l2 == 0.0f) { vx = vy = vz = 0.0f; }
-		else { const float l = __builtin_sqrtf(l2); vx /= l; vy /= l; vz /= l; }
-		if ((nx * vx + ny * vy) + nz * vz <= 0.0f) traced = false; // below the surface: an invalid sample, no ray
+		float vx, vy, vz;
+		onb_direction(sf, rr, z, u2, vx, vy, vz);
+		if ((sf.nx * vx + sf.ny * vy) + sf.nz * vz <= 0.0f) traced = false; // below the surface: an invalid sample, no ray
 		else {
 			r.dx = vx; r.dy = vy; r.dz = vz;
-			r.ox = px + nx * 1e-3f; r.oy = py + ny * 1e-3f; r.oz = pz + nz * 1e-3f;
+			r.ox = sf.px + sf.nx * 1e-3f; r.oy = sf.py + sf.ny * 1e-3f; r.oz = sf.pz + sf.nz * 1e-3f;
 			r.t_min = 1e-4f; r.t_max = s.t_max;
 		}
 	}
@@ -115,10 +52,11 @@ __device__ __forceinline__ bool hemisphere_ray(const TraceParams &p, const HemiP
 
 // The ray of entry g, or (false) the result of an entry without one, stored: the byte 1 (any-hit) or the placeholder's record.
 template <int SRC, bool ANY_HIT>
-__device__ __forceinline__ bool hemisphere_entry(const TraceParams &p, const HemiParams &s, uint64_t g, RayRegs &r)
+__device__ __forceinline__ bool source_entry(const TraceParams &p, const HemiParams &s, uint64_t g, RayRegs &r)
 {
+	static_assert(hemisphere_source(SRC), "a hemisphere source");
 	if (hemisphere_ray<SRC>(p, s, g, r)) return true;
 	if (ANY_HIT) store_lit(p, g, true);
-	else store_no_reflection(p, g);
+	else store_placeholder_record(p, g);
 	return false;
 }

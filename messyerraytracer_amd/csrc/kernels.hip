@@ -329,6 +329,7 @@ __device__ __forceinline__ void finish_two_level_ray(const TraceParams &p, uint6
 	store_hit(p, ray_idx, r, best_t, prim, best_u, best_v, nx, ny, nz, layers, best_slot);
 }
 
+#include "source_common.h"
 #include "shadow_kernel.h"
 #include "reflection_kernel.h"
 #include "hemisphere_kernel.h"
@@ -341,10 +342,7 @@ template <bool ANY_HIT, bool COUNT>
 __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 {
 	constexpr int SRC = SRC_CAST;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
+	const NoSource s{};
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -357,131 +355,25 @@ __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 #endif
 #include "two_level_kernel.h"
 
-// ---- shadow casts (shadow_kernel.h): the lane kernels a non-coherent any-hit batch can get, with a shadow ray source -------
-// (the bodies are the ones of trace_lane_kernel, trace_two_level_kernel and trace_lane_persistent_kernel, included with SRC set)
-template <int SRC>
-__global__ __launch_bounds__(MRT_WG) void trace_shadow_lane_kernel(const TraceParams p, const ShadowParams s)
-{
-	constexpr bool ANY_HIT = true, COUNT = false;
-	const ShadowParams *sh = &s;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
-#include "lane_walk.inc" // (in scope: the names its first lines check)
-}
-template <int SRC>
-__global__ __launch_bounds__(MRT_WG) void trace_shadow_two_level_kernel(const TraceParams p, const ShadowParams s)
-{
-	constexpr bool ANY_HIT = true;
-	const ShadowParams *sh = &s;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
-#include "two_level_walk.inc" // (in scope: the names its first lines check)
-}
-template <int SRC, int WIDTH, bool TL>
-__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_shadow_persistent_kernel(const TraceParams p, const PersistParams q, const ShadowParams s)
-{
-	constexpr bool ANY_HIT = true, COUNT = false;
-	const ShadowParams *sh = &s;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
-#include "persistent_walk.inc" // (in scope: the names its first lines check)
-}
-
-// ---- reflection casts (reflection_kernel.h): the same lane kernels, closest-hit, with a reflection ray source ------------------
-template <int SRC>
-__global__ __launch_bounds__(MRT_WG) void trace_reflection_lane_kernel(const TraceParams p, const ReflectParams s)
-{
-	constexpr bool ANY_HIT = false, COUNT = false;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = &s;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
-#include "lane_walk.inc" // (in scope: the names its first lines check)
-}
-template <int SRC>
-__global__ __launch_bounds__(MRT_WG) void trace_reflection_two_level_kernel(const TraceParams p, const ReflectParams s)
-{
-	constexpr bool ANY_HIT = false;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = &s;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
-#include "two_level_walk.inc" // (in scope: the names its first lines check)
-}
-template <int SRC, int WIDTH, bool TL>
-__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_reflection_persistent_kernel(const TraceParams p, const PersistParams q, const ReflectParams s)
-{
-	constexpr bool ANY_HIT = false, COUNT = false;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = &s;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
-#include "persistent_walk.inc" // (in scope: the names its first lines check)
-}
-
-// ---- hemisphere casts (hemisphere_kernel.h): the same lane kernels, any-hit (ambient occlusion) or closest-hit (a diffuse bounce) ----
-template <int SRC, bool ANY_HIT>
-__global__ __launch_bounds__(MRT_WG) void trace_hemisphere_lane_kernel(const TraceParams p, const HemiParams s)
+// ---- record-driven casts (source_common.h): the lane kernels a non-coherent batch can get, with a ray source -------------------
+// S = the source family's parameters (its own kernel argument: ShadowParams and HemiParams are large, and a union of the four would
+// grow every family's argument block), SRC one of its three sources, ANY_HIT a mode its source_entry accepts.  The bodies are the
+// ones of trace_lane_kernel, trace_two_level_kernel and trace_lane_persistent_kernel, included with SRC set.
+template <class S, int SRC, bool ANY_HIT>
+__global__ __launch_bounds__(MRT_WG) void trace_source_lane_kernel(const TraceParams p, const S s)
 {
 	constexpr bool COUNT = false;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = &s;
-	const BounceParams *bn = nullptr;
 #include "lane_walk.inc" // (in scope: the names its first lines check)
 }
-template <int SRC, bool ANY_HIT>
-__global__ __launch_bounds__(MRT_WG) void trace_hemisphere_two_level_kernel(const TraceParams p, const HemiParams s)
+template <class S, int SRC, bool ANY_HIT>
+__global__ __launch_bounds__(MRT_WG) void trace_source_two_level_kernel(const TraceParams p, const S s)
 {
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = &s;
-	const BounceParams *bn = nullptr;
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
-template <int SRC, bool ANY_HIT, int WIDTH, bool TL>
-__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_hemisphere_persistent_kernel(const TraceParams p, const PersistParams q, const HemiParams s)
+template <class S, int SRC, bool ANY_HIT, int WIDTH, bool TL>
+__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_source_persistent_kernel(const TraceParams p, const PersistParams q, const S s)
 {
 	constexpr bool COUNT = false;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = &s;
-	const BounceParams *bn = nullptr;
-#include "persistent_walk.inc" // (in scope: the names its first lines check)
-}
-
-// ---- bounce casts (bounce_kernel.h): the same lane kernels, closest-hit, with the path tracer's bounce as the ray source -------------
-template <int SRC>
-__global__ __launch_bounds__(MRT_WG) void trace_bounce_lane_kernel(const TraceParams p, const BounceParams s)
-{
-	constexpr bool ANY_HIT = false, COUNT = false;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = &s;
-#include "lane_walk.inc" // (in scope: the names its first lines check)
-}
-template <int SRC>
-__global__ __launch_bounds__(MRT_WG) void trace_bounce_two_level_kernel(const TraceParams p, const BounceParams s)
-{
-	constexpr bool ANY_HIT = false;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = &s;
-#include "two_level_walk.inc" // (in scope: the names its first lines check)
-}
-template <int SRC, int WIDTH, bool TL>
-__global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_bounce_persistent_kernel(const TraceParams p, const PersistParams q, const BounceParams s)
-{
-	constexpr bool ANY_HIT = false, COUNT = false;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = &s;
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }
 
@@ -1017,170 +909,67 @@ hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *nex
 	return hipGetLastError();
 }
 
-// Shadow casts: p.kernel is the lane kernel the plan chose (launch_policy.cpp, ENTRY_SHADOW / ENTRY_GRID_SHADOW); p.count = pairs.
-// persistent: blocks != 0 (as launch_trace_persistent), else the plain kernel with p.sparse_lanes.
-template <int SRC>
-static void launch_shadow_src(const TraceParams &p, const ShadowParams &s, const PersistParams &q, uint32_t blocks, hipStream_t stream)
+// Record-driven casts: p.kernel is the lane kernel the plan chose (launch_policy.cpp plan_source); p.count = entries.  persistent:
+// blocks != 0 (as launch_trace_persistent), else the plain kernel with p.sparse_lanes.  The label noted for mrt_last_kernel_variant
+// names (family, source, mode where the family has two, width, two-level) in the form the GPU tests and the recorded profiles pin,
+// "trace_shadow_lane_kernel<3>", "trace_hemisphere_persistent_kernel<9, true, 8, false>": not a symbol of this library.
+template <class S, int SRC, bool ANY_HIT>
+static void launch_source_as(const TraceParams &p, const S &s, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
 {
+	using F = SourceFamily<S>;
 	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
+	char mode[8] = "";
+	if (F::any_hit && F::nearest) snprintf(mode, sizeof(mode), ", %s", MRT_B(ANY_HIT));
 	if (blocks == 0) {
 		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
 		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
 		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
-		if (tl) hipLaunchKernelGGL((trace_shadow_two_level_kernel<SRC>), grid, wg, lds, stream, p, s);
-		else hipLaunchKernelGGL((trace_shadow_lane_kernel<SRC>), grid, wg, lds, stream, p, s);
-		note_variant("trace_shadow_%s_kernel<%d>", tl ? "two_level" : "lane", SRC);
+		if (tl) hipLaunchKernelGGL((trace_source_two_level_kernel<S, SRC, ANY_HIT>), grid, wg, lds, stream, p, s);
+		else hipLaunchKernelGGL((trace_source_lane_kernel<S, SRC, ANY_HIT>), grid, wg, lds, stream, p, s);
+		note_variant("trace_%s_%s_kernel<%d%s>", F::name, tl ? "two_level" : "lane", SRC, mode);
 		return;
 	}
+	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
 	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
+#define MRT_LS(W, T) hipLaunchKernelGGL((trace_source_persistent_kernel<S, SRC, ANY_HIT, W, T>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s)
 	int width = 2;
-	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
-		width = 8; hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else if (tl) hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) {
-		width = 8; hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 8, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) {
-		width = 4; hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 4, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else hipLaunchKernelGGL((trace_shadow_persistent_kernel<SRC, 2, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	note_variant("trace_shadow_persistent_kernel<%d, %d, %s>", SRC, width, MRT_B(tl));
+	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) { width = 8; MRT_LS(8, true); }
+	else if (tl) MRT_LS(2, true);
+	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) { width = 8; MRT_LS(8, false); }
+	else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) { width = 4; MRT_LS(4, false); }
+	else MRT_LS(2, false);
+#undef MRT_LS
+	note_variant("trace_%s_persistent_kernel<%d%s, %d, %s>", F::name, SRC, mode, width, MRT_B(tl));
 }
 
-hipError_t launch_shadow(const TraceParams &p, const ShadowParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
+// src = one of the family's three sources; any_hit = a mode the family has (shadows any-hit, reflections and bounces closest-hit,
+// hemispheres either: the other instantiations do not compile, source_entry).  Anything else is hipErrorInvalidValue.
+template <class S>
+hipError_t launch_source(const TraceParams &p, const void *params, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
 {
+	using F = SourceFamily<S>;
+	const S &s = *static_cast<const S *>(params);
 	if (p.count == 0) return hipSuccess;
 	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
 	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
-	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
-	if (src == SRC_SHADOW_RAY32) launch_shadow_src<SRC_SHADOW_RAY32>(p, s, q, blocks, stream);
-	else if (src == SRC_SHADOW_HOST44) launch_shadow_src<SRC_SHADOW_HOST44>(p, s, q, blocks, stream);
-	else if (src == SRC_SHADOW_GRID) launch_shadow_src<SRC_SHADOW_GRID>(p, s, q, blocks, stream);
-	else return hipErrorInvalidValue;
+	if ((src != F::ray32 && src != F::host && src != F::grid) || !(any_hit ? F::any_hit : F::nearest)) return hipErrorInvalidValue;
+#define MRT_LS_SRC(A)                                                                                                                        \
+	do {                                                                                                                                 \
+		if (src == F::ray32) launch_source_as<S, F::ray32, A>(p, s, next_ray, overflow, lds_depth, refill, leaf_wait, blocks, stream);   \
+		else if (src == F::host) launch_source_as<S, F::host, A>(p, s, next_ray, overflow, lds_depth, refill, leaf_wait, blocks, stream); \
+		else launch_source_as<S, F::grid, A>(p, s, next_ray, overflow, lds_depth, refill, leaf_wait, blocks, stream);                     \
+	} while (0)
+	if constexpr (F::any_hit) { if (any_hit) MRT_LS_SRC(true); }
+	if constexpr (F::nearest) { if (!any_hit) MRT_LS_SRC(false); }
+#undef MRT_LS_SRC
 	return hipGetLastError();
 }
-
-// Reflection casts: the same, with the reflection instantiations (ENTRY_REFLECTION / ENTRY_GRID_REFLECTION); p.count = records.
-template <int SRC>
-static void launch_reflection_src(const TraceParams &p, const ReflectParams &s, const PersistParams &q, uint32_t blocks, hipStream_t stream)
-{
-	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
-	if (blocks == 0) {
-		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
-		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
-		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
-		if (tl) hipLaunchKernelGGL((trace_reflection_two_level_kernel<SRC>), grid, wg, lds, stream, p, s);
-		else hipLaunchKernelGGL((trace_reflection_lane_kernel<SRC>), grid, wg, lds, stream, p, s);
-		note_variant("trace_reflection_%s_kernel<%d>", tl ? "two_level" : "lane", SRC);
-		return;
-	}
-	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
-	int width = 2;
-	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
-		width = 8; hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else if (tl) hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) {
-		width = 8; hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 8, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) {
-		width = 4; hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 4, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else hipLaunchKernelGGL((trace_reflection_persistent_kernel<SRC, 2, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	note_variant("trace_reflection_persistent_kernel<%d, %d, %s>", SRC, width, MRT_B(tl));
-}
-
-hipError_t launch_reflection(const TraceParams &p, const ReflectParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
-{
-	if (p.count == 0) return hipSuccess;
-	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
-	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
-	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
-	if (src == SRC_REFLECT_RAY32) launch_reflection_src<SRC_REFLECT_RAY32>(p, s, q, blocks, stream);
-	else if (src == SRC_REFLECT_HOST) launch_reflection_src<SRC_REFLECT_HOST>(p, s, q, blocks, stream);
-	else if (src == SRC_REFLECT_GRID) launch_reflection_src<SRC_REFLECT_GRID>(p, s, q, blocks, stream);
-	else return hipErrorInvalidValue;
-	return hipGetLastError();
-}
-
-// Hemisphere casts: the same, with the hemisphere instantiations (ENTRY_HEMISPHERE / ENTRY_GRID_HEMISPHERE); p.count = pixels * samples.
-template <int SRC, bool ANY_HIT>
-static void launch_hemisphere_src(const TraceParams &p, const HemiParams &s, const PersistParams &q, uint32_t blocks, hipStream_t stream)
-{
-	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
-	if (blocks == 0) {
-		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
-		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
-		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
-		if (tl) hipLaunchKernelGGL((trace_hemisphere_two_level_kernel<SRC, ANY_HIT>), grid, wg, lds, stream, p, s);
-		else hipLaunchKernelGGL((trace_hemisphere_lane_kernel<SRC, ANY_HIT>), grid, wg, lds, stream, p, s);
-		note_variant("trace_hemisphere_%s_kernel<%d, %s>", tl ? "two_level" : "lane", SRC, MRT_B(ANY_HIT));
-		return;
-	}
-	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
-	int width = 2;
-	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
-		width = 8; hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else if (tl) hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) {
-		width = 8; hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 8, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) {
-		width = 4; hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 4, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else hipLaunchKernelGGL((trace_hemisphere_persistent_kernel<SRC, ANY_HIT, 2, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	note_variant("trace_hemisphere_persistent_kernel<%d, %s, %d, %s>", SRC, MRT_B(ANY_HIT), width, MRT_B(tl));
-}
-
-hipError_t launch_hemisphere(const TraceParams &p, const HemiParams &s, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
-{
-	if (p.count == 0) return hipSuccess;
-	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
-	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
-	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
-	if (src == SRC_HEMI_RAY32) { if (any_hit) launch_hemisphere_src<SRC_HEMI_RAY32, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_RAY32, false>(p, s, q, blocks, stream); }
-	else if (src == SRC_HEMI_HOST) { if (any_hit) launch_hemisphere_src<SRC_HEMI_HOST, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_HOST, false>(p, s, q, blocks, stream); }
-	else if (src == SRC_HEMI_GRID) { if (any_hit) launch_hemisphere_src<SRC_HEMI_GRID, true>(p, s, q, blocks, stream); else launch_hemisphere_src<SRC_HEMI_GRID, false>(p, s, q, blocks, stream); }
-	else return hipErrorInvalidValue;
-	return hipGetLastError();
-}
-
-// Bounce casts: the same, with the bounce instantiations (ENTRY_BOUNCE / ENTRY_GRID_BOUNCE); p.count = records.
-template <int SRC>
-static void launch_bounce_src(const TraceParams &p, const BounceParams &s, const PersistParams &q, uint32_t blocks, hipStream_t stream)
-{
-	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
-	if (blocks == 0) {
-		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
-		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
-		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
-		if (tl) hipLaunchKernelGGL((trace_bounce_two_level_kernel<SRC>), grid, wg, lds, stream, p, s);
-		else hipLaunchKernelGGL((trace_bounce_lane_kernel<SRC>), grid, wg, lds, stream, p, s);
-		note_variant("trace_bounce_%s_kernel<%d>", tl ? "two_level" : "lane", SRC);
-		return;
-	}
-	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
-	int width = 2;
-	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
-		width = 8; hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else if (tl) hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) {
-		width = 8; hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 8, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) {
-		width = 4; hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 4, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	} else hipLaunchKernelGGL((trace_bounce_persistent_kernel<SRC, 2, false>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s);
-	note_variant("trace_bounce_persistent_kernel<%d, %d, %s>", SRC, width, MRT_B(tl));
-}
-
-hipError_t launch_bounce(const TraceParams &p, const BounceParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
-{
-	if (p.count == 0) return hipSuccess;
-	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
-	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
-	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
-	if (src == SRC_BOUNCE_RAY32) launch_bounce_src<SRC_BOUNCE_RAY32>(p, s, q, blocks, stream);
-	else if (src == SRC_BOUNCE_HOST) launch_bounce_src<SRC_BOUNCE_HOST>(p, s, q, blocks, stream);
-	else if (src == SRC_BOUNCE_GRID) launch_bounce_src<SRC_BOUNCE_GRID>(p, s, q, blocks, stream);
-	else return hipErrorInvalidValue;
-	return hipGetLastError();
-}
+template hipError_t launch_source<ShadowParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+template hipError_t launch_source<ReflectParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+template hipError_t launch_source<HemiParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+template hipError_t launch_source<BounceParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 
 hipError_t launch_grid_rays(const TraceParams &p, mrt_ray32 *out, hipStream_t stream)
 {

@@ -74,9 +74,6 @@ template <bool ANY_HIT, int WIDTH, bool TL = false, bool COUNT = false> // WIDTH
 __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_lane_persistent_kernel(const TraceParams p, const PersistParams q)
 {
 	constexpr int SRC = SRC_CAST;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
+	const NoSource s{};
 #include "persistent_walk.inc" // (in scope: the names its first lines check)
 }

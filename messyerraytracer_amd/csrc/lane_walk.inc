@@ -1,16 +1,11 @@
-// lane_walk.inc -- the body of trace_lane_kernel, trace_shadow_lane_kernel, trace_reflection_lane_kernel, trace_hemisphere_lane_kernel
-// and trace_bounce_lane_kernel (kernels.hip), included inside each: the kernel that existed before the shadow source keeps the very code it had (a walk inlined from
-// a function compiles differently).  In scope: p (TraceParams), sh (const ShadowParams *), rf (const ReflectParams *), hm (const
-// HemiParams *), bn (const BounceParams *), ANY_HIT, COUNT, SRC (SRC_CAST: the batch's rays; SRC_SHADOW_*: shadow_kernel.h;
-// SRC_REFLECT_*: reflection_kernel.h; SRC_HEMI_*: hemisphere_kernel.h; SRC_BOUNCE_*: bounce_kernel.h).
+// lane_walk.inc -- the body of trace_lane_kernel and trace_source_lane_kernel (kernels.hip), included inside each: the kernel that
+// existed before the ray sources keeps the very code it had (a walk inlined from a function compiles differently).  In scope: p
+// (TraceParams), s (the parameters of the kernel's source family, source_common.h; NoSource in a SRC_CAST kernel), ANY_HIT, COUNT, SRC
+// (SRC_CAST: the batch's rays, load_ray; else the family's source_entry makes the ray of an entry or stores its result).
 	// the contract with the including kernel, checked here rather than deep in the walk
-	static_assert(std::is_same<decltype(p), const TraceParams>::value && std::is_same<decltype(sh), const ShadowParams *>::value &&
-			std::is_same<decltype(rf), const ReflectParams *>::value && std::is_same<decltype(hm), const HemiParams *>::value &&
-			std::is_same<decltype(bn), const BounceParams *>::value,
-			"lane_walk.inc: p (const TraceParams), sh (const ShadowParams *), rf (const ReflectParams *), hm (const HemiParams *) and bn (const BounceParams *) in scope");
-	static_assert(SRC == SRC_CAST || (shadow_source(SRC) && ANY_HIT && !COUNT) || (reflection_source(SRC) && !ANY_HIT && !COUNT) ||
-			(hemisphere_source(SRC) && !COUNT) || (bounce_source(SRC) && !ANY_HIT && !COUNT),
-			"lane_walk.inc: shadow sources are any-hit, reflection and bounce sources closest-hit, hemisphere sources either, none counts");
+	static_assert(std::is_same<decltype(p), const TraceParams>::value && (SRC == SRC_CAST) == std::is_same<decltype(s), const NoSource>::value,
+			"lane_walk.inc: p (const TraceParams) and s (the source family's parameters; const NoSource for SRC_CAST) in scope");
+	static_assert(SRC == SRC_CAST || !COUNT, "lane_walk.inc: no ray source counts (source_entry checks the family's modes)");
 	extern __shared__ uint32_t lds_stack[];
 	if (skip_launch(p)) return;
 	uint32_t block = blockIdx.x;
@@ -22,10 +17,7 @@
 	if (!lane_ray_index(p, block, ray_idx, px, py)) return;
 	RayRegs r;
 	if constexpr (SRC == SRC_CAST) load_ray(p, ray_idx, px, py, r);
-	else if constexpr (shadow_source(SRC)) { if (!shadow_ray<SRC>(p, *sh, ray_idx, r)) { store_lit(p, ray_idx, true); return; } }
-	else if constexpr (reflection_source(SRC)) { if (!reflection_ray<SRC>(p, *rf, ray_idx, r)) { store_no_reflection(p, ray_idx); return; } }
-	else if constexpr (hemisphere_source(SRC)) { if (!hemisphere_entry<SRC, ANY_HIT>(p, *hm, ray_idx, r)) return; }
-	else if (!bounce_entry<SRC>(p, *bn, ray_idx, r)) return;
+	else if (!source_entry<SRC, ANY_HIT>(p, s, ray_idx, r)) return;
 
 	float best_t = r.t_max, best_u = 0.0f, best_v = 0.0f;
 	uint32_t best_slot = 0xFFFFFFFFu, best_id = 0xFFFFFFFFu;

@@ -176,13 +176,18 @@ void tune_record(GridTune &t, float trace_ms)
 	t.armed = false;
 }
 
-// Shadow casts: count = pixels * lights any-hit rays made in the kernel, in pixel order (which already groups nearby origins), never
-// sorted (the rays never exist in memory) and never tiled.  The lane kernels as for any incoherent batch: the plain one (small batches on
-// emptier waves), from 2^16 rays the persistent ones (8-, 4- or 2-wide, two-level scenes their own).  The packet kernels have no shadow
-// source: a forced one means the policy's own lane kernel.  Shadow kernels have no counting variant.  Nothing of the grid state
-// (detected widths, the grid tuner, tile schedules) is read or changed: a renderer that alternates primary and shadow casts keeps its
-// primary grid's plan exactly as it is without them.
-static CastPlan plan_shadow(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
+// Record-driven casts (shadow, reflection, hemisphere, bounce: record_cast_entry): count rays made in the kernel from resident hit records
+// -- pixels * lights any-hit shadow rays, one closest-hit mirror or bounce ray per record, pixels * samples hemisphere rays in either
+// mode -- in entry order (which already groups nearby origins, though hemisphere and bounce rays are far less coherent than the
+// others).  One plan for all of them, since neither the family nor the mode enters it:
+//   - never sorted: the rays never exist in memory, so there is nothing to sort; no detection and no tiling;
+//   - the lane kernels as for any incoherent batch: the plain one below 2^16 rays (small batches on emptier waves), the persistent ones
+//     from 2^16 (8-, 4- or 2-wide, two-level scenes their own);
+//   - the packet kernels have no ray source: a forced one means the policy's own lane kernel;
+//   - there is no counting variant;
+//   - nothing of the grid state (detected widths, the grid tuner, tile schedules) is read or changed: a renderer that alternates primary
+//     casts with these keeps its primary grid's plan exactly as it is without them.
+static CastPlan plan_source(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
 {
 	CastPlan c;
 	mrt_options so = o;
@@ -197,38 +202,9 @@ static CastPlan plan_shadow(const mrt_options &o, const SceneFacts &s, const Cas
 	return c;
 }
 
-// Reflection casts: count = records, one closest-hit mirror ray each, made in the kernel in record order.  Planned as shadow casts
-// are, for the same reasons (no sort: the rays never exist in memory; no detection, no tiling; the plain lane kernel below 2^16 rays,
-// the persistent ones from 2^16; a forced packet kernel means the policy's lane kernel; no counting variant): the mode does not enter
-// the lane plan.  Nothing of the grid state is read or changed.
-static CastPlan plan_reflection(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
-{
-	return plan_shadow(o, s, r);
-}
-
-// Hemisphere casts: count = pixels * samples rays made in the kernel, sample-major in pixel order; any-hit (ambient occlusion) or
-// closest-hit (a diffuse bounce).  The shadow plan or the reflection plan of that many rays -- one plan, since the mode does not enter
-// it -- although these rays are far less coherent than either: unsorted all the same (the rays never exist in memory, so there is
-// nothing to sort), and the lane kernels are the ones for incoherent batches.  Nothing of the grid state is read or changed.
-static CastPlan plan_hemisphere(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
-{
-	return r.mode == MRT_MODE_ANY_HIT ? plan_shadow(o, s, r) : plan_reflection(o, s, r);
-}
-
-// Bounce casts: count = records, one closest-hit ray each -- a GGX reflection or a cosine-hemisphere ray, chosen per record -- made in
-// the kernel in record order.  The reflection plan of that many rays, for the reasons given there.  Nothing of the grid state is read
-// or changed.
-static CastPlan plan_bounce(const mrt_options &o, const SceneFacts &s, const CastRequest &r)
-{
-	return plan_reflection(o, s, r);
-}
-
 CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest &r, const PrevDetect &prev, const Knobs &k, GridStates &gs)
 {
-	if (shadow_entry(r.entry)) return plan_shadow(o, s, r);
-	if (reflection_entry(r.entry)) return plan_reflection(o, s, r);
-	if (hemisphere_entry(r.entry)) return plan_hemisphere(o, s, r);
-	if (bounce_entry(r.entry)) return plan_bounce(o, s, r);
+	if (record_cast_entry(r.entry)) return plan_source(o, s, r);
 	CastPlan c;
 	const uint64_t n = r.count;
 	const bool auto_k = o.kernel == MRT_KERNEL_AUTO, coherent = (r.flags & MRT_FLAG_COHERENT) != 0;

@@ -50,10 +50,7 @@ struct SceneFacts {
 enum Entry : uint32_t { ENTRY_CAST, ENTRY_SUBMIT, ENTRY_CHUNK, ENTRY_GRID, ENTRY_TILED, ENTRY_SHADOW, ENTRY_GRID_SHADOW,
 	ENTRY_REFLECTION, ENTRY_GRID_REFLECTION, ENTRY_HEMISPHERE, ENTRY_GRID_HEMISPHERE, ENTRY_BOUNCE, ENTRY_GRID_BOUNCE };
 inline bool ray_entry(Entry e) { return e <= ENTRY_CHUNK; } // rays from an array, through enqueue_cast
-inline bool shadow_entry(Entry e) { return e == ENTRY_SHADOW || e == ENTRY_GRID_SHADOW; }
-inline bool reflection_entry(Entry e) { return e == ENTRY_REFLECTION || e == ENTRY_GRID_REFLECTION; }
-inline bool hemisphere_entry(Entry e) { return e == ENTRY_HEMISPHERE || e == ENTRY_GRID_HEMISPHERE; }
-inline bool bounce_entry(Entry e) { return e == ENTRY_BOUNCE || e == ENTRY_GRID_BOUNCE; }
+inline bool record_cast_entry(Entry e) { return e >= ENTRY_SHADOW && e <= ENTRY_GRID_BOUNCE; } // rays made in the kernel from hit records
 
 struct CastRequest {
 	Entry entry = ENTRY_CAST;

@@ -12,17 +12,11 @@ hipError_t launch_trace(const TraceParams &p, bool any_hit, bool count, hipStrea
 const char *last_trace_variant();
 bool quad_kernel_built();
 hipError_t launch_grid_rays(const TraceParams &p, mrt_ray32 *out, hipStream_t stream);
-// shadow casts (shadow_kernel.h): src = SRC_SHADOW_*; blocks != 0: the persistent kernel (next_ray .. leaf_wait as launch_trace_persistent)
-hipError_t launch_shadow(const TraceParams &p, const ShadowParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
-// reflection casts (reflection_kernel.h): src = SRC_REFLECT_*; the rest as launch_shadow
-hipError_t launch_reflection(const TraceParams &p, const ReflectParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
-// hemisphere casts (hemisphere_kernel.h): src = SRC_HEMI_*, any_hit: one byte per entry instead of a record; the rest as launch_shadow
-hipError_t launch_hemisphere(const TraceParams &p, const HemiParams &s, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
-// bounce casts (bounce_kernel.h): src = SRC_BOUNCE_*; the rest as launch_shadow
-hipError_t launch_bounce(const TraceParams &p, const BounceParams &s, int src, unsigned long long *next_ray, uint32_t *overflow,
+// record-driven casts (source_common.h): S = the family's parameter struct (instantiated in kernels.hip for ShadowParams, ReflectParams,
+// HemiParams and BounceParams), params = an S, src = one of SourceFamily<S>'s sources, any_hit = a mode the family has; blocks != 0: the
+// persistent kernel (next_ray .. leaf_wait as launch_trace_persistent)
+template <class S>
+hipError_t launch_source(const TraceParams &p, const void *params, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
 hipError_t launch_build_rows4(const Dev4Node *nodes4, const TriHot *hot, const TriCold *cold, uint32_t n_nodes4, uint32_t n_tris,
 		void *rows, hipStream_t stream);

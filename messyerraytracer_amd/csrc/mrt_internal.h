@@ -167,7 +167,7 @@ struct TraceParams {
 // ---- shadow rays (shadow_kernel.h): made in the trace kernel from the hit records of a cast -----------------------------
 // Entry g of a shadow cast is the pair (light g / pixels, pixel g % pixels); TraceParams::count = pixels * lights, hits = the
 // lit mask (one byte per entry), rays = the primary rays (SRC_SHADOW_RAY32).  The ray source is a template parameter of the
-// kernels (SRC_CAST: the rays of an ordinary cast, the instantiations that existed before).
+// kernels (SRC_CAST: the rays of an ordinary cast, the instantiations that existed before); source_common.h says what a family is.
 enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, SRC_SHADOW_GRID = 3,
 	SRC_REFLECT_RAY32 = 4, SRC_REFLECT_HOST = 5, SRC_REFLECT_GRID = 6,
 	SRC_HEMI_RAY32 = 7, SRC_HEMI_HOST = 8, SRC_HEMI_GRID = 9,
@@ -214,7 +214,7 @@ struct HemiParams {
 
 // ---- the path tracer's bounce (bounce_kernel.h): one closest-hit ray per hit record, lobe chosen and sampled in the kernel ---------
 // Entry i of a bounce cast is record i; TraceParams::count = records, hits = the output records, rays = the incoming rays as for
-// reflections.  The generator's state before the lobe draw is jump.a * state0 + jump.c (bounce_jump, cast.hip).
+// reflections.  The generator's state before the lobe draw is jump.a * state0 + jump.c (pcg_jump, cast.hip).
 struct BounceParams {
 	const void *records;       // mrt_hit32 (SRC_BOUNCE_RAY32, SRC_BOUNCE_GRID) or mrt_host_hit44 (SRC_BOUNCE_HOST)
 	const uint8_t *select;     // optional: 0 = no ray for this record
@@ -225,6 +225,30 @@ struct BounceParams {
 	float t_max;               // t_max of every ray
 	float metallic, roughness; // as the descriptor gave them (clamped in the kernel like a record's pair)
 	HemiJump jump;             // (A, C) of draw first_draw
+};
+
+// What the one launcher and the one set of kernels need to know of a source family, by its parameter struct: its three sources
+// (RaySrc values: they are printed in mrt_last_kernel_variant), the modes it has (a family with one does not print it) and its name.
+template <class S> struct SourceFamily;
+template <> struct SourceFamily<ShadowParams> {
+	static constexpr int ray32 = SRC_SHADOW_RAY32, host = SRC_SHADOW_HOST44, grid = SRC_SHADOW_GRID;
+	static constexpr bool any_hit = true, nearest = false;
+	static constexpr const char *name = "shadow";
+};
+template <> struct SourceFamily<ReflectParams> {
+	static constexpr int ray32 = SRC_REFLECT_RAY32, host = SRC_REFLECT_HOST, grid = SRC_REFLECT_GRID;
+	static constexpr bool any_hit = false, nearest = true;
+	static constexpr const char *name = "reflection";
+};
+template <> struct SourceFamily<HemiParams> {
+	static constexpr int ray32 = SRC_HEMI_RAY32, host = SRC_HEMI_HOST, grid = SRC_HEMI_GRID;
+	static constexpr bool any_hit = true, nearest = true;
+	static constexpr const char *name = "hemisphere";
+};
+template <> struct SourceFamily<BounceParams> {
+	static constexpr int ray32 = SRC_BOUNCE_RAY32, host = SRC_BOUNCE_HOST, grid = SRC_BOUNCE_GRID;
+	static constexpr bool any_hit = false, nearest = true;
+	static constexpr const char *name = "bounce";
 };
 
 // host-side preparation (scene_prep.cpp)

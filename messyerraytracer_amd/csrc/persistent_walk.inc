@@ -1,16 +1,12 @@
-// persistent_walk.inc -- the body of trace_lane_persistent_kernel (lane_persistent_kernel.h), trace_shadow_persistent_kernel,
-// trace_reflection_persistent_kernel, trace_hemisphere_persistent_kernel and trace_bounce_persistent_kernel (kernels.hip), included
-// inside each (see lane_walk.inc).  In scope: p, q, sh, rf, hm, bn, ANY_HIT, WIDTH, TL, COUNT, SRC (shadow, reflection, hemisphere and
-// bounce sources: an entry without a ray writes its result when it is handed out, and the lane takes the next entry at once).
+// persistent_walk.inc -- the body of trace_lane_persistent_kernel (lane_persistent_kernel.h) and trace_source_persistent_kernel
+// (kernels.hip), included inside each (see lane_walk.inc).  In scope: p, q, s, ANY_HIT, WIDTH, TL, COUNT, SRC (a ray source: an entry
+// without a ray writes its result when it is handed out, and the lane takes the next entry at once).
 	// the contract with the including kernel, checked here rather than deep in the walk
 	static_assert(std::is_same<decltype(p), const TraceParams>::value && std::is_same<decltype(q), const PersistParams>::value &&
-			std::is_same<decltype(sh), const ShadowParams *>::value && std::is_same<decltype(rf), const ReflectParams *>::value &&
-			std::is_same<decltype(hm), const HemiParams *>::value && std::is_same<decltype(bn), const BounceParams *>::value,
-			"persistent_walk.inc: p (const TraceParams), q (const PersistParams), sh (const ShadowParams *), rf (const ReflectParams *), hm (const HemiParams *) and bn (const BounceParams *) in scope");
+			(SRC == SRC_CAST) == std::is_same<decltype(s), const NoSource>::value,
+			"persistent_walk.inc: p (const TraceParams), q (const PersistParams) and s (the source family's parameters; const NoSource for SRC_CAST) in scope");
 	static_assert(WIDTH == 2 || WIDTH == 4 || WIDTH == 8, "persistent_walk.inc: WIDTH is 2, 4 or 8");
-	static_assert(SRC == SRC_CAST || (shadow_source(SRC) && ANY_HIT && !COUNT) || (reflection_source(SRC) && !ANY_HIT && !COUNT) ||
-			(hemisphere_source(SRC) && !COUNT) || (bounce_source(SRC) && !ANY_HIT && !COUNT),
-			"persistent_walk.inc: shadow sources are any-hit, reflection and bounce sources closest-hit, hemisphere sources either, none counts");
+	static_assert(SRC == SRC_CAST || !COUNT, "persistent_walk.inc: no ray source counts (source_entry checks the family's modes)");
 	uint32_t n_rays = 0, n_hits = 0, n_nodes = 0, n_tris = 0, n_boxchk = 0; // COUNT: this lane's totals over all its rays
 	static_assert(!TL || WIDTH == 2 || WIDTH == 8, "two-level scenes: 2-wide, or 8-wide inside the instances (the TLAS is always 2-wide)");
 	constexpr uint32_t kNode = TL ? kInstanceReturn : kSentinel; // refs below this are inner nodes
@@ -67,7 +63,7 @@
 	for (;;) {
 		// ---- retire finished lanes, hand out new rays ----
 	hand_out:
-		bool skipped = false; // (shadow, reflection, hemisphere and bounce sources) this lane drew an entry without a ray
+		bool skipped = false; // (a ray source) this lane drew an entry without a ray
 		const bool idle = cur == kSentinel;
 		if (idle && has_ray) {
 			if constexpr (lit_output(SRC, ANY_HIT)) store_lit(p, ray_idx, best_slot == 0xFFFFFFFFu);
@@ -130,10 +126,7 @@
 					ray_idx = p.perm ? (uint64_t)p.perm[g] : g;
 					bool traced = true;
 					if constexpr (SRC == SRC_CAST) load_ray(p, ray_idx, 0, 0, r);
-					else if constexpr (shadow_source(SRC)) { if (!(traced = shadow_ray<SRC>(p, *sh, ray_idx, r))) { store_lit(p, ray_idx, true); skipped = true; } }
-					else if constexpr (reflection_source(SRC)) { if (!(traced = reflection_ray<SRC>(p, *rf, ray_idx, r))) { store_no_reflection(p, ray_idx); skipped = true; } }
-					else if constexpr (hemisphere_source(SRC)) { if (!(traced = hemisphere_entry<SRC, ANY_HIT>(p, *hm, ray_idx, r))) skipped = true; }
-					else if (!(traced = bounce_entry<SRC>(p, *bn, ray_idx, r))) skipped = true;
+					else if (!(traced = source_entry<SRC, ANY_HIT>(p, s, ray_idx, r))) skipped = true;
 					if (traced) {
 						has_ray = true;
 						best_t = r.t_max; best_u = 0.0f; best_v = 0.0f; best_slot = 0xFFFFFFFFu; best_id = 0xFFFFFFFFu;

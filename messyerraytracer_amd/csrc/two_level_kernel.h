@@ -14,10 +14,7 @@ template <bool ANY_HIT>
 __global__ __launch_bounds__(MRT_WG) void trace_two_level_kernel(const TraceParams p)
 {
 	constexpr int SRC = SRC_CAST;
-	const ShadowParams *sh = nullptr;
-	const ReflectParams *rf = nullptr;
-	const HemiParams *hm = nullptr;
-	const BounceParams *bn = nullptr;
+	const NoSource s{};
 #include "two_level_walk.inc" // (in scope: the names its first lines check)
 }
 

@@ -1,24 +1,15 @@
-// two_level_walk.inc -- the body of trace_two_level_kernel (two_level_kernel.h), trace_shadow_two_level_kernel,
-// trace_reflection_two_level_kernel, trace_hemisphere_two_level_kernel and trace_bounce_two_level_kernel (kernels.hip), included inside
-// each (see lane_walk.inc).  In scope: p, sh, rf, hm, bn, ANY_HIT, SRC.
+// two_level_walk.inc -- the body of trace_two_level_kernel (two_level_kernel.h) and trace_source_two_level_kernel (kernels.hip),
+// included inside each (see lane_walk.inc).  In scope: p, s, ANY_HIT, SRC.
 	// the contract with the including kernel, checked here rather than deep in the walk
-	static_assert(std::is_same<decltype(p), const TraceParams>::value && std::is_same<decltype(sh), const ShadowParams *>::value &&
-			std::is_same<decltype(rf), const ReflectParams *>::value && std::is_same<decltype(hm), const HemiParams *>::value &&
-			std::is_same<decltype(bn), const BounceParams *>::value,
-			"two_level_walk.inc: p (const TraceParams), sh (const ShadowParams *), rf (const ReflectParams *), hm (const HemiParams *) and bn (const BounceParams *) in scope");
-	static_assert(SRC == SRC_CAST || (shadow_source(SRC) && ANY_HIT) || (reflection_source(SRC) && !ANY_HIT) || hemisphere_source(SRC) ||
-			(bounce_source(SRC) && !ANY_HIT),
-			"two_level_walk.inc: shadow sources are any-hit, reflection and bounce sources closest-hit, hemisphere sources either");
+	static_assert(std::is_same<decltype(p), const TraceParams>::value && (SRC == SRC_CAST) == std::is_same<decltype(s), const NoSource>::value,
+			"two_level_walk.inc: p (const TraceParams) and s (the source family's parameters; const NoSource for SRC_CAST) in scope");
 	extern __shared__ uint32_t lds_stack[];
 	if (skip_launch(p)) return;
 	uint64_t ray_idx = 0; uint32_t px = 0, py = 0;
 	if (!lane_ray_index(p, blockIdx.x, ray_idx, px, py)) return;
 	RayRegs r;
 	if constexpr (SRC == SRC_CAST) load_ray(p, ray_idx, px, py, r);
-	else if constexpr (shadow_source(SRC)) { if (!shadow_ray<SRC>(p, *sh, ray_idx, r)) { store_lit(p, ray_idx, true); return; } }
-	else if constexpr (reflection_source(SRC)) { if (!reflection_ray<SRC>(p, *rf, ray_idx, r)) { store_no_reflection(p, ray_idx); return; } }
-	else if constexpr (hemisphere_source(SRC)) { if (!hemisphere_entry<SRC, ANY_HIT>(p, *hm, ray_idx, r)) return; }
-	else if (!bounce_entry<SRC>(p, *bn, ray_idx, r)) return;
+	else if (!source_entry<SRC, ANY_HIT>(p, s, ray_idx, r)) return;
 
 	float best_t = r.t_max, best_u = 0.0f, best_v = 0.0f;
 	uint32_t best_slot = 0xFFFFFFFFu, best_id = 0xFFFFFFFFu, best_inst = 0u;
