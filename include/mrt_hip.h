@@ -673,8 +673,9 @@ int mrt_cast_grid_hemisphere(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_
  * the lobe against a specular probability made from the surface's metallic and roughness, then either a GGX half
  * vector (ggx_sample_half, :132-155) with the view direction reflected about it, or the cosine hemisphere above.
  * One closest-hit ray per record, made in the trace kernel.  Weights, throughput and Russian roulette stay with the
- * renderer (they need albedo and F0).  Shading (smooth) normals are not taken: n is the record's geometric normal,
- * as for reflections and hemisphere rays.  For every record that is a hit and selected (d_select null, or
+ * renderer (they need albedo and F0: mrt_resolve_surfaces below gives them per record, and d_surface).  n is the record's
+ * normal, as for reflections and hemisphere rays: the geometric normal as a cast wrote it, or the shading (smooth) normal
+ * in records that went through mrt_resolve_surfaces' d_out_hits.  For every record that is a hit and selected (d_select null, or
  * d_select[i] != 0), plain fp32 operations in this order, nothing contracted:
  *   p, d, n = exactly as mrt_cast_hemisphere takes them, n negated if ((nx*dx + ny*dy) + nz*dz) > 0.
  *   metallic, roughness = d_surface[2i], d_surface[2i + 1], or the descriptor's two constants when d_surface is null.
@@ -724,6 +725,86 @@ int mrt_cast_bounce(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64
 int mrt_cast_grid_bounce(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0,
 		uint32_t y1, const void *d_hits, const mrt_bounce *desc, void *d_out_hits, void *d_out_rays,
 		uint32_t query_mask, uint32_t flags);
+
+/* ---- shading surfaces from resident hit records: the reference's SceneShadeData (src/api/scene_shade_data.h) held on
+ * the device, and ShadePass::extract_surface (src/modules/graphics/shade_pass.h:509-587) run per hit record as one kernel.
+ * What the casts above leave to the renderer -- metallic and roughness for mrt_bounce.d_surface, the shading (smooth)
+ * normal, albedo and emission for weights and throughput -- without downloading the records.  Texture sampling, normal-map
+ * perturbation, tangents, lighting and throughput stay with the renderer: it gets the UV and the material index. */
+
+/* MaterialData (src/api/material_data.h) without its images; 48 bytes */
+typedef struct mrt_material {
+	float albedo[3];   float metallic;
+	float roughness;   float specular;   float emission[3];
+	float emission_energy;
+	uint32_t flags;    /* bit 0 has_albedo_texture, bit 1 has_normal_texture: carried, not used */
+	uint32_t reserved;
+} mrt_material;
+
+enum { MRT_SHADE_ARRAYS_ON_DEVICE = 1u << 0 };   /* material_ids, normals9 and uvs6 are device pointers */
+/* The three per-triangle arrays are indexed by the prim_id a hit record carries ("Indexed by prim_id (global triangle
+ * ID)"): on a two-level scene the flat id.  Each is optional (null: absent for the whole context).  Normals are world-space
+ * as given: a caller whose instances move uploads them again. */
+typedef struct mrt_shade_data {
+	uint32_t struct_size, n_tris, n_materials, flags;   /* flags: MRT_SHADE_* */
+	const mrt_material *materials;   /* host array, n_materials (may be 0 / null) */
+	const uint32_t *material_ids;    /* n_tris, optional */
+	const float *normals9;           /* n_tris x {n0, n1, n2}: TriangleNormals (src/core/triangle_normals.h), optional */
+	const float *uvs6;               /* n_tris x {uv0, uv1, uv2}: TriangleUV (src/core/triangle_uv.h), optional */
+} mrt_shade_data;
+/* Makes the shade data resident.  It belongs to the context, not to the scene: it survives scene uploads, refits and
+ * instance updates, is replaced by the next upload and released by mrt_clear_shade_data or mrt_destroy.  On the device
+ * a triangle is one 64-byte row {n0 xyz, material id | n1 xyz, uv0.x | n2 xyz, uv0.y | uv1 xy, uv2 xy}, packed here (on
+ * the host for host arrays, by a kernel for device arrays), a material one 48-byte row.  Blocks; ordered on the context's
+ * stream.  MRT_ERR_INVALID for a null context or descriptor, a wrong struct_size, an unknown flag, n_materials > 0 with
+ * null materials, a non-finite float in a material (the resident data is then unchanged); MRT_ERR_PENDING while a dispatch
+ * is pending.  Material ids are not range-checked: an id >= n_materials selects the default material, exactly as the
+ * reference's bounds test does. */
+int mrt_upload_shade_data(mrt_ctx *ctx, const mrt_shade_data *data);
+/* Releases the resident shade data (none resident: MRT_OK).  Waits for the context's stream.  MRT_ERR_PENDING as above. */
+int mrt_clear_shade_data(mrt_ctx *ctx);
+
+/* The surface of one record; 64 bytes.  A miss: all zero with material = 0xFFFFFFFF. */
+typedef struct mrt_surface64 {
+	float normal[3];   float n_dot_v;
+	float albedo[3];   float metallic;
+	float emission[3]; float roughness;
+	float uv[2];       float specular;   uint32_t material;   /* 0xFFFFFFFF: the default material */
+} mrt_surface64;
+typedef struct mrt_surface_out {
+	mrt_surface64 *d_rows;      /* optional */
+	float *d_bounce_surface;    /* optional, 2 floats per record {metallic, roughness}: mrt_bounce.d_surface's layout */
+	void *d_out_hits;           /* optional: the records in the input layout with `normal` replaced by the shading normal
+	                             * (may be d_hits itself: every record is read before it is written) */
+} mrt_surface_out;
+/* Resolves every record to its surface.  With hit, p and d of a record as mrt_cast_reflections takes them, plain fp32
+ * operations in this order, nothing contracted (normalized(x, y, z): l2 = (x*x + y*y) + z*z; 0 if l2 == 0, else each
+ * component divided by sqrt(l2)):
+ *   in_range = prim_id < n_tris (unsigned; n_tris of the resident shade data, 0 with none).
+ *   w = (1.0f - u) - v with the record's barycentrics.
+ *   n: normals resident and in_range: c = (n0.c * w + n1.c * u) + n2.c * v per component, then normalized
+ *       (TriangleNormals::interpolate); otherwise the record's normal as it stands.
+ *   vd = normalized(-d); ndv = (nx*vdx + ny*vdy) + nz*vdz; n_dot_v = ndv < 0.001f ? 0.001f : ndv.
+ *   material: albedo 0.75 x3, metallic 0, roughness 0.5, specular 0.5, emission 0, material = 0xFFFFFFFF; with ids
+ *       resident, in_range and id < n_materials: albedo, metallic, specular copied, roughness = mat.roughness < 0.04f ?
+ *       0.04f : mat.roughness, emission = mat.emission * mat.emission_energy if emission_energy > 0, else 0, material = id.
+ *   uv: uvs resident and in_range: (uv0.c * w + uv1.c * u) + uv2.c * v per component; else 0.  (The reference
+ *       interpolates only for textured materials: a superset.)
+ * A miss writes an all-zero row with material = 0xFFFFFFFF, {0, 0.5} to d_bounce_surface and the record unchanged to
+ * d_out_hits.  F0 = (0.04f * specular * 2) * (1 - metallic) + albedo * metallic and the diffuse albedo = albedo *
+ * (1 - metallic) are one line each from the row and are not stored.  No scene is required and nothing is walked; with no
+ * shade data resident every hit resolves as against an empty SceneShadeData (face normal, default material, uv 0).
+ * d_rays / d_hits: what mrt_cast read and wrote -- mrt_ray32 + mrt_hit32, or with MRT_FLAG_HOST_LAYOUT mrt_host_ray60 +
+ * mrt_host_hit44.  All pointers but `out` are device pointers.  Flags: MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC (queue on the
+ * context's stream without waiting).  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID for a null required pointer,
+ * all three outputs null, an unknown flag; MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_resolve_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count,
+		const mrt_surface_out *out, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_hits as it wrote them, mrt_hit32; the outputs
+ * indexed by the record within the band): the primary rays are regenerated in the kernel, so a band resolves what the
+ * whole frame resolves.  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_resolve_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h,
+		uint32_t y0, uint32_t y1, const void *d_hits, const mrt_surface_out *out, uint32_t flags);
 
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to

@@ -18,10 +18,11 @@ REFLECTION_POLICY_TEST = os.path.join(HERE, "reflection_policy_test")
 HEMISPHERE_POLICY_TEST = os.path.join(HERE, "hemisphere_policy_test")
 BOUNCE_POLICY_TEST = os.path.join(HERE, "bounce_policy_test")
 INSTANCE_MATH_TEST = os.path.join(HERE, "instance_math_test")
+SHADE_DATA_TEST = os.path.join(HERE, "shade_data_test")
 
 SOURCES = ["kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip", "device_build.hip", "refit.hip",
-           "tlas_device.hip", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
-HEADERS = ["mrt_internal.h", "instance_math.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "source_common.h", "shadow_kernel.h", "reflection_kernel.h", "hemisphere_kernel.h", "bounce_kernel.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
+           "tlas_device.hip", "surface.hip", "host/shade_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
+HEADERS = ["mrt_internal.h", "instance_math.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "source_common.h", "shadow_kernel.h", "reflection_kernel.h", "hemisphere_kernel.h", "bounce_kernel.h", "surface_kernel.h", "shade_data.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
            "host/host_types.hpp", "host/cpu_backend.hpp", "host/ray_tracer_server.hpp", "host/record_policy_test.h"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
@@ -187,6 +188,19 @@ def build_instance_math_test(force: bool = False) -> str:
     return INSTANCE_MATH_TEST
 
 
+def build_shade_data_test(force: bool = False) -> str:
+    """C++ test driver for the checks and the row packing of shade data (host/shade_data.cpp alone: host code, no device, no
+    library)."""
+    srcs = [os.path.join(CSRC, "host", "shade_data_test.cpp"), os.path.join(CSRC, "host", "shade_data.cpp")]
+    deps = srcs + [os.path.join(CSRC, "shade_data.h"), os.path.join(CSRC, "../../include/mrt_hip.h")]
+    if force or _stale(SHADE_DATA_TEST, deps):
+        cmd = [_hipcc(), "-x", "c++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall"] + srcs + ["-o", SHADE_DATA_TEST]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
+        if r.returncode != 0:
+            raise RuntimeError("shade data test build failed:\n" + r.stdout + r.stderr)
+    return SHADE_DATA_TEST
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_host_test(force=True))
@@ -198,3 +212,4 @@ if __name__ == "__main__":
     print(build_hemisphere_policy_test(force=True))
     print(build_bounce_policy_test(force=True))
     print(build_instance_math_test(force=True))
+    print(build_shade_data_test(force=True))

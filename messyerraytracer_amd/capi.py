@@ -31,7 +31,8 @@ SYMBOLS = [
     "mrt_synchronize", "mrt_make_triangles", "mrt_pack_host_triangles", "mrt_bvh2_build", "mrt_bvh2_save", "mrt_bvh2_load", "mrt_upload_scene",
     "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_update_instances_device", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_scene_prepare_host", "mrt_scene_host_arrays", "mrt_scene_free_host", "mrt_debug_snapshot", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
-    "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_cast_bounce", "mrt_cast_grid_bounce", "mrt_expand_tokens",
+    "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_cast_bounce", "mrt_cast_grid_bounce",
+    "mrt_upload_shade_data", "mrt_clear_shade_data", "mrt_resolve_surfaces", "mrt_resolve_grid_surfaces", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
     "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
     "mrt_group_create", "mrt_group_destroy", "mrt_group_size", "mrt_group_context", "mrt_group_last_error", "mrt_group_row_block",
@@ -73,6 +74,21 @@ class Bounce(C.Structure):
 
 
 LOBE_NONE, LOBE_DIFFUSE, LOBE_SPECULAR = 0, 1, 2
+
+
+class ShadeData(C.Structure):
+    """mrt_shade_data"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_tris", C.c_uint32), ("n_materials", C.c_uint32), ("flags", C.c_uint32),
+                ("materials", C.c_void_p), ("material_ids", C.c_void_p), ("normals9", C.c_void_p), ("uvs6", C.c_void_p)]
+
+
+class SurfaceOut(C.Structure):
+    """mrt_surface_out"""
+    _fields_ = [("d_rows", C.c_void_p), ("d_bounce_surface", C.c_void_p), ("d_out_hits", C.c_void_p)]
+
+
+SHADE_ARRAYS_ON_DEVICE = 1
+STRUCT_MATERIAL, STRUCT_SHADE_DATA, STRUCT_SURFACE64, STRUCT_SURFACE_OUT = 6, 7, 8, 9   # mrt_struct_size indices
 
 
 class Stats(C.Structure):
@@ -193,6 +209,11 @@ def load():
                                   C.c_uint32, C.c_uint32]
     L.mrt_cast_grid_bounce.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                        C.POINTER(Bounce), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.mrt_upload_shade_data.argtypes = [C.c_void_p, C.POINTER(ShadeData)]
+    L.mrt_clear_shade_data.argtypes = [C.c_void_p]
+    L.mrt_resolve_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SurfaceOut), C.c_uint32]
+    L.mrt_resolve_grid_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                            C.POINTER(SurfaceOut), C.c_uint32]
     L.mrt_cast_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mrt_expand_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
     L.mrt_expand_grid_tokens.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -239,6 +260,12 @@ def bounce_desc(frame, first_draw, t_max, metallic=0.0, roughness=0.5, d_select=
     """mrt_bounce from its fields (d_select, d_surface, d_out_lobe: device pointers / tensors or None)"""
     v = [None if x is None else _ptr(x).value for x in (d_select, d_surface, d_out_lobe)]
     return Bounce(frame, first_draw, t_max, metallic, roughness, v[0], v[1], v[2])
+
+
+def surface_out(d_rows=None, d_bounce_surface=None, d_out_hits=None):
+    """mrt_surface_out from its fields (device pointers / tensors or None)"""
+    v = [None if x is None else _ptr(x).value for x in (d_rows, d_bounce_surface, d_out_hits)]
+    return SurfaceOut(v[0], v[1], v[2])
 
 
 def _ptr(x):
@@ -696,6 +723,41 @@ class Context:
         desc = bounce_desc(frame, first_draw, t_max, metallic, roughness, d_select, d_surface, d_out_lobe)
         self._chk(self.L.mrt_cast_grid_bounce(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(desc), _ptr(d_out_hits),
                                               _optr(d_out_rays), query_mask, flags))
+
+    def upload_shade_data(self, n_tris, materials=None, material_ids=None, normals9=None, uvs6=None, on_device=False):
+        """Makes the shade data of the context resident (mrt_upload_shade_data).  materials: a host array of T.MATERIAL or None; the
+        three per-triangle arrays, each optional: numpy arrays (uint32 [n_tris], float32 [n_tris, 9], float32 [n_tris, 6]) or, with
+        on_device, device pointers / tensors.  Indexed by the prim_id a record carries; replaced by the next upload."""
+        mats = None if materials is None else np.ascontiguousarray(materials, dtype=T.MATERIAL)
+        keep = [mats]
+        ptrs = []
+        for a, dt in ((material_ids, np.uint32), (normals9, np.float32), (uvs6, np.float32)):
+            if a is not None and not on_device:
+                a = np.ascontiguousarray(a, dtype=dt)
+                keep.append(a)
+            ptrs.append(None if a is None else _ptr(a).value)
+        d = ShadeData(C.sizeof(ShadeData), n_tris, 0 if mats is None else mats.shape[0], SHADE_ARRAYS_ON_DEVICE if on_device else 0,
+                      None if mats is None or mats.shape[0] == 0 else _np(mats).value, ptrs[0], ptrs[1], ptrs[2])
+        self._chk(self.L.mrt_upload_shade_data(self.h, C.byref(d)))
+
+    def clear_shade_data(self):
+        self._chk(self.L.mrt_clear_shade_data(self.h))
+
+    def resolve_surfaces(self, d_rays, d_hits, count, d_rows=None, d_bounce_surface=None, d_out_hits=None, flags=0):
+        """The shading surface of every hit record of a cast (device pointers / tensors: mrt_ray32 + mrt_hit32, or mrt_host_ray60 +
+        mrt_host_hit44 with FLAG_HOST_LAYOUT) against the resident shade data.  Outputs, each optional, at least one: d_rows one
+        T.SURFACE64 per record; d_bounce_surface {metallic, roughness} float pairs, cast_bounce's d_surface; d_out_hits the records in
+        the input layout with the shading normal in place of the normal."""
+        out = surface_out(d_rows, d_bounce_surface, d_out_hits)
+        self._chk(self.L.mrt_resolve_surfaces(self.h, _ptr(d_rays), _ptr(d_hits), count, C.byref(out), flags))
+
+    def resolve_grid_surfaces(self, cam, grid_w, grid_h, d_hits, d_rows=None, d_bounce_surface=None, d_out_hits=None, y0=0, y1=None,
+                              flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (d_hits: its mrt_hit32 records on the device; the outputs indexed by
+        the record within the band)."""
+        y1 = grid_h if y1 is None else y1
+        out = surface_out(d_rows, d_bounce_surface, d_out_hits)
+        self._chk(self.L.mrt_resolve_grid_surfaces(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(out), flags))
 
     def expand_tokens(self, d_rays, d_tokens, d_hits, count, flags=0, stream=None):
         """Device pointers; enqueued on `stream` (raw hipStream_t) or the context's stream, not waited for."""

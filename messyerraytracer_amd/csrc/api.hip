@@ -153,6 +153,10 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 2: return (uint32_t)sizeof(mrt_stats);
 		case 3: return (uint32_t)sizeof(mrt_instance);
 		case 4: return (uint32_t)sizeof(mrt_light);
+		case 6: return (uint32_t)sizeof(mrt_material); // (5: not a struct)
+		case 7: return (uint32_t)sizeof(mrt_shade_data);
+		case 8: return (uint32_t)sizeof(mrt_surface64);
+		case 9: return (uint32_t)sizeof(mrt_surface_out);
 		default: return 0u;
 	}
 }
@@ -254,6 +258,7 @@ void mrt_destroy(mrt_ctx *ctx)
 	release(ctx->rays); release(ctx->hits); release(ctx->keys_in); release(ctx->keys_out);
 	release(ctx->idx_in); release(ctx->idx_out); release(ctx->sort_tmp); release(ctx->overflow); release(ctx->refit_in);
 	release(ctx->tlas_work);
+	release(ctx->shade_rows); release(ctx->shade_materials);
 	for (auto &sc : ctx->sched) {
 		if (sc.side) { (void)hipStreamSynchronize(sc.side); (void)hipStreamDestroy(sc.side); }
 		if (sc.traced) (void)hipEventDestroy(sc.traced);

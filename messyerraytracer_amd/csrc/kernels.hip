@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "mrt_internal.h"
+#include "shade_data.h"
 
 namespace mrt {
 
@@ -970,6 +971,29 @@ template hipError_t launch_source<ShadowParams>(const TraceParams &, const void 
 template hipError_t launch_source<ReflectParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<HemiParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<BounceParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+
+#include "surface_kernel.h"
+
+// src = a SurfaceSrc; anything else is hipErrorInvalidValue
+hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream)
+{
+	if (p.count == 0) return hipSuccess;
+	const uint64_t blocks = (p.count + MRT_WG - 1) / MRT_WG;
+	if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	if (src == SURF_RAY32) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_RAY32>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else if (src == SURF_HOST) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_HOST>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else if (src == SURF_GRID) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_GRID>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream)
+{
+	if (n_tris == 0) return hipSuccess;
+	const uint32_t blocks = (n_tris + MRT_WG - 1) / MRT_WG;
+	hipLaunchKernelGGL(pack_shade_rows_kernel, dim3(blocks), dim3(MRT_WG), 0, stream, ids, normals9, uvs6, n_tris, reinterpret_cast<uint4 *>(rows));
+	return hipGetLastError();
+}
 
 hipError_t launch_grid_rays(const TraceParams &p, mrt_ray32 *out, hipStream_t stream)
 {

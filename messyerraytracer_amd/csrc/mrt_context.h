@@ -23,6 +23,9 @@ hipError_t launch_build_rows4(const Dev4Node *nodes4, const TriHot *hot, const T
 hipError_t launch_build_rows(const DevNode *nodes, const TriHot *hot, const TriCold *cold, uint32_t n_nodes, uint32_t n_tris,
 		void *rows, hipStream_t stream);
 hipError_t launch_expand_tokens(const TraceParams &p, const uint32_t *tokens, hipStream_t stream);
+// shading surfaces (surface_kernel.h): src = a SurfaceSrc; the rows of shade data given as device arrays (any of the three may be null)
+hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream);
+hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream);
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);
 hipError_t launch_collapse8(const DevNode *nodes, uint32_t n_nodes, Dev8Node *nodes8, float *leaf_box, uint32_t *bad, hipStream_t stream);
 hipError_t launch_offset_refs(DevNode *dst, const DevNode *src, uint32_t n, uint32_t node_base, uint32_t tri_base, void *stream);
@@ -114,6 +117,9 @@ struct mrt_ctx {
 	uint64_t pending_count = 0; uint32_t pending_flags = 0; int pending_mode = 0;
 	const void *pending_dev_hits = nullptr;
 	mrt_stats stats{};
+	// shade data (surface.hip): the context's, not the scene's -- free_scene leaves it alone
+	DevBuf shade_rows, shade_materials;
+	uint32_t shade_n_tris = 0, shade_n_materials = 0, shade_present = 0; // present: mrt::SHADE_HAS_* (shade_data.h)
 };
 
 #define HIP_TRY(ctx, call)                                                                          \

@@ -227,6 +227,21 @@ struct BounceParams {
 	HemiJump jump;             // (A, C) of draw first_draw
 };
 
+// ---- shading surfaces (surface_kernel.h): one mrt_surface64 row per hit record, nothing walked ---------------------------------
+// Record i of a resolve is entry i; TraceParams::count = records, rays = the incoming rays as for reflections (or the grid).  The
+// resident shade data (shade_data.h): n_tris rows of 64 bytes, n_materials rows of 48; an absent per-triangle array is a bit not set
+// in `present` (SHADE_HAS_*), never a per-row sentinel.
+enum SurfaceSrc : int { SURF_RAY32 = 0, SURF_HOST = 1, SURF_GRID = 2 };
+struct SurfaceParams {
+	const void *records;       // mrt_hit32 (SURF_RAY32, SURF_GRID) or mrt_host_hit44 (SURF_HOST)
+	const void *shade_rows;    // n_tris x 64 bytes (null when no per-triangle array is resident)
+	const void *materials;     // n_materials x mrt_material
+	uint32_t n_tris, n_materials, present;
+	void *out_rows;            // optional: mrt_surface64 per record
+	float *out_bounce;         // optional: {metallic, roughness} per record
+	void *out_hits;            // optional: the records in the input layout, shading normal in place of the normal
+};
+
 // What the one launcher and the one set of kernels need to know of a source family, by its parameter struct: its three sources
 // (RaySrc values: they are printed in mrt_last_kernel_variant), the modes it has (a family with one does not print it) and its name.
 template <class S> struct SourceFamily;

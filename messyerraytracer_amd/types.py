@@ -29,6 +29,14 @@ LIGHT = np.dtype([("type", "<u4"), ("cast_shadows", "<u4"), ("position", "<f4", 
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2
 MAX_LIGHTS = 16
 
+# shading surfaces (mrt_upload_shade_data, mrt_resolve_surfaces)
+MATERIAL = np.dtype([("albedo", "<f4", 3), ("metallic", "<f4"), ("roughness", "<f4"), ("specular", "<f4"), ("emission", "<f4", 3),
+                     ("emission_energy", "<f4"), ("flags", "<u4"), ("reserved", "<u4")])  # mrt_material
+SURFACE64 = np.dtype([("normal", "<f4", 3), ("n_dot_v", "<f4"), ("albedo", "<f4", 3), ("metallic", "<f4"), ("emission", "<f4", 3),
+                      ("roughness", "<f4"), ("uv", "<f4", 2), ("specular", "<f4"), ("material", "<u4")])  # mrt_surface64
+DEFAULT_MATERIAL = 0xFFFFFFFF
+assert MATERIAL.itemsize == 48 and SURFACE64.itemsize == 64
+
 # rows of the device layouts (csrc/mrt_internal.h), as mrt_debug_snapshot and the host preparations return them
 TRI_HOT = np.dtype([("v0", "<f4", 3), ("id", "<u4"), ("e1", "<f4", 3), ("layers", "<u4"), ("e2", "<f4", 3), ("flags", "<u4")])
 TRI_COLD = np.dtype([("normal", "<f4", 3), ("pad", "<u4")])
