@@ -17,6 +17,7 @@
 #include <type_traits>
 #include "mrt_internal.h"
 #include "shade_data.h"
+#include "lane_map.h"
 
 namespace mrt {
 
@@ -57,101 +58,54 @@ __device__ __forceinline__ bool lane_ray_index(const TraceParams &p, uint32_t bl
 {
 	return lane_ray_index_g(p, (uint64_t)block * MRT_WG + threadIdx.x, ray_idx, px, py);
 }
+// The map itself is lane_map.h: what a group's 64 lanes share (the tile: wave_tile) and what differs between them (tile_lane).
+//
 // tile_order 3: every XCD works on its own column strips of the image.  Workgroups are dealt to the 8 XCDs round-robin
 // (workgroup i runs on XCD i & 7), and each XCD has its own 4 MB L2: in row-major launch order every XCD sees every
 // tile column, so the rows a band of tiles needs are fetched into all eight L2s (C5: 13 GB of L2 fills per launch for a
 // 1.8 GB scene).  Here the image is cut into 8 m strips (about 256 pixels wide), XCD k takes strips k, k + 8, ..., one
 // after the other, each from top to bottom: the ~1000 waves an XCD has in flight cover one compact region, and the
 // strips of every XCD are spread evenly over the image, so cheap and expensive regions balance (a contiguous band per
-// XCD, xcd_swizzle = 1, measured 6 % slower for that reason).  tile_group = consecutive tiles per workgroup.  Returns
-// false (row-major order) when the width does not split into 8 m strips of whole workgroups.
-__device__ __forceinline__ bool xcd_strips(const TraceParams &p, uint64_t tile, uint32_t tiles_x, uint32_t tiles_y, uint32_t &tx, uint32_t &ty)
+// XCD, xcd_swizzle = 1, measured 6 % slower for that reason).  tile_group = consecutive tiles per workgroup.  Row-major
+// order when the width does not split into 8 m strips of whole workgroups.
+
+// The launch's grid as lane_map.h takes it; false = the linear map.  The schedule of the previous frame (launch slot -> unit of
+// tile_unit consecutive tiles) counts only if it is a schedule of THIS grid (a batch whose row width is found on the device,
+// MAP_AUTO, was scheduled from the last cast's width).
+__device__ __forceinline__ bool tile_grid(const TraceParams &p, TileGrid &g)
 {
-	const uint32_t tg = p.tile_group ? p.tile_group : 1u;
-	uint32_t m = (tiles_x + 128u) >> 8;
-	if (m == 0u) m = 1u;
-	const uint32_t S = tiles_x / (8u * m);
-	if (S == 0u || S * 8u * m != tiles_x || S % tg != 0u) return false;
-	const uint64_t wg = tile / tg;
-	const uint32_t k = (uint32_t)wg & 7u;
-	const uint64_t j = (wg >> 3) * tg + tile % tg; // the tile's place in its XCD's own sequence
-	const uint64_t per_strip = (uint64_t)S * tiles_y;
-	const uint32_t sl = (uint32_t)(j / per_strip), r = (uint32_t)(j % per_strip);
-	ty = r / S;
-	tx = (sl * 8u + k) * S + r % S;
+	uint32_t lane_map = p.lane_map;
+	g.grid_w = p.grid_w; g.rows = p.rows; g.tiles_x = p.tiles_x;
+	if (lane_map == MAP_AUTO) { // row width found on the device by detect_grid_kernel (0 = not a grid)
+		const uint32_t w = p.auto_grid[0];
+		lane_map = w ? MAP_TILE8X8 : MAP_LINEAR;
+		g.grid_w = w; g.rows = p.auto_grid[1]; g.tiles_x = p.auto_grid[2];
+	}
+	g.k = p.tile_w_log2; g.tiles_y = tile_rows_of(g.rows, g.k);
+	g.order = p.tile_order; g.group = p.tile_group; g.quarter_all = p.quarter_all;
+	g.sched = nullptr; g.unit = 1u; g.sched_slots = 0u;
+	if (lane_map != MAP_TILE8X8) return false;
+	if (!p.quarter_all && p.tile_sched != nullptr && sched_matches((uint64_t)g.tiles_x * g.tiles_y, p.tile_unit, p.n_units)) {
+		g.sched = p.tile_sched; g.unit = p.tile_unit; g.sched_slots = p.sched_hdr ? p.sched_hdr[2] : p.n_units;
+	}
+	return true;
+}
+// the linear map's lane: entry -> ray (perm), and its pixel for rays made from a camera
+__device__ __forceinline__ bool linear_ray(const TraceParams &p, uint64_t group, uint32_t l, uint64_t &ray_idx, uint32_t &px, uint32_t &py)
+{
+	uint64_t e = 0;
+	if (!linear_lane(group, l, p.sparse_lanes, p.count, e)) return false;
+	ray_idx = p.perm ? (uint64_t)p.perm[e] : e;
+	if (p.in_fmt == IN_GRID) { px = (uint32_t)(ray_idx % p.grid_w); py = (uint32_t)(ray_idx / p.grid_w); }
 	return true;
 }
 
 // g = virtual thread index: 64 consecutive g form one wave-sized group of rays
 __device__ __forceinline__ bool lane_ray_index_g(const TraceParams &p, uint64_t g, uint64_t &ray_idx, uint32_t &px, uint32_t &py)
 {
-	uint32_t lane_map = p.lane_map, grid_w = p.grid_w, rows = p.rows, tiles_x = p.tiles_x;
-	if (lane_map == MAP_AUTO) { // row width found on the device by detect_grid_kernel (0 = not a grid)
-		const uint32_t w = p.auto_grid[0];
-		lane_map = w ? MAP_TILE8X8 : MAP_LINEAR;
-		grid_w = w; rows = p.auto_grid[1]; tiles_x = p.auto_grid[2];
-	}
-	if (lane_map == MAP_TILE8X8) {
-		uint64_t tile = g >> 6;
-		const uint32_t l = (uint32_t)g & 63u;
-		uint32_t tx, ty;
-		const uint32_t k = p.tile_w_log2; // tile is 2^k wide, 64 / 2^k high
-		const uint32_t tiles_y = (rows + (64u >> k) - 1u) >> (6u - k);
-		// the schedule of the previous frame: launch slot -> unit of tile_unit consecutive tiles.  Only if it is a schedule
-		// of THIS grid (a batch whose row width is found on the device, MAP_AUTO, was scheduled from the last cast's width)
-		uint32_t quarter = 4u; // 0..3: the slot's wave works on that 4x4 quarter of its tile, in lanes 0..15
-		uint32_t sixteenth = 16u; // 0..15 (quarter_all == 2): on that 2x2 sixteenth of its tile, in lanes 0..3
-		if (p.quarter_all == 2u) { sixteenth = (uint32_t)tile & 15u; tile >>= 4; if (l >= 4u || tile >= (uint64_t)tiles_x * tiles_y) return false; }
-		else if (p.quarter_all) { quarter = (uint32_t)tile & 3u; tile >>= 2; if (l >= 16u || tile >= (uint64_t)tiles_x * tiles_y) return false; }
-		else if (p.tile_sched != nullptr && ((uint64_t)tiles_x * tiles_y + p.tile_unit - 1u) / p.tile_unit == p.n_units) {
-			const uint64_t slot = tile / p.tile_unit;
-			if (slot >= (p.sched_hdr ? p.sched_hdr[2] : p.n_units)) return false;
-			const uint32_t e = p.tile_sched[slot], what = e >> 28, id = e & 0x0FFFFFFFu;
-			if (what == 0u) tile = (uint64_t)id * p.tile_unit + tile % p.tile_unit;
-			else {
-				if (tile % p.tile_unit != 0u) return false; // a piece is (part of) one tile: a second group of the wave has nothing to do
-				tile = id;
-				if (what >= 2u) { quarter = what - 2u; if (l >= 16u) return false; }
-			}
-		}
-		if (p.tile_order == 1u && (tiles_x & 15u) == 0u && (tiles_y & 15u) == 0u) {
-			// 16x16-tile super-tiles in row-major order, Z-order inside: the tiles in flight at
-			// any moment cover a compact image region, so they share deep BVH nodes in L2
-			const uint32_t st = (uint32_t)(tile >> 8), in = (uint32_t)tile & 255u;
-			uint32_t mx = in & 0x55u, my = (in >> 1) & 0x55u; // de-interleave 4+4 bits
-			mx = (mx | (mx >> 1)) & 0x33u; mx = (mx | (mx >> 2)) & 0x0Fu;
-			my = (my | (my >> 1)) & 0x33u; my = (my | (my >> 2)) & 0x0Fu;
-			const uint32_t stx = st % (tiles_x >> 4), sty = st / (tiles_x >> 4);
-			tx = (stx << 4) + mx; ty = (sty << 4) + my;
-		} else if (p.tile_order == 2u && (tiles_x & 31u) == 0u && (tiles_y & 31u) == 0u) {
-			// the same with 32x32-tile super-tiles
-			const uint32_t st = (uint32_t)(tile >> 10), in = (uint32_t)tile & 1023u;
-			uint32_t mx = in & 0x155u, my = (in >> 1) & 0x155u; // de-interleave 5+5 bits
-			mx = (mx | (mx >> 1)) & 0x133u; mx = (mx | (mx >> 2)) & 0x10Fu; mx = (mx | (mx >> 4)) & 0x1Fu;
-			my = (my | (my >> 1)) & 0x133u; my = (my | (my >> 2)) & 0x10Fu; my = (my | (my >> 4)) & 0x1Fu;
-			const uint32_t stx = st % (tiles_x >> 5), sty = st / (tiles_x >> 5);
-			tx = (stx << 5) + mx; ty = (sty << 5) + my;
-		} else if (p.tile_order == 3u && xcd_strips(p, tile, tiles_x, tiles_y, tx, ty)) {
-		} else { tx = (uint32_t)(tile % tiles_x); ty = (uint32_t)(tile / tiles_x); }
-		if (sixteenth < 16u) {
-			px = (tx << 3) + ((sixteenth & 3u) << 1) + (l & 1u);
-			py = (ty << 3) + ((sixteenth >> 2) << 1) + (l >> 1);
-		} else if (quarter < 4u) { // (schedule pieces exist for 8x8 tiles only: k == 3)
-			px = (tx << 3) + ((quarter & 1u) << 2) + (l & 3u);
-			py = (ty << 3) + ((quarter >> 1) << 2) + (l >> 2);
-		} else {
-			px = (tx << k) + (l & ((1u << k) - 1u));
-			py = (ty << (6u - k)) + (l >> k);
-		}
-		if (px >= grid_w || py >= rows) return false;
-		ray_idx = (uint64_t)py * grid_w + px;
-		return true;
-	}
-	if (p.sparse_lanes) { const uint32_t l = (uint32_t)g & 63u; if (l >= p.sparse_lanes) return false; g = (g >> 6) * p.sparse_lanes + l; }
-	if (g >= p.count) return false;
-	ray_idx = p.perm ? (uint64_t)p.perm[g] : g;
-	if (p.in_fmt == IN_GRID) { px = (uint32_t)(ray_idx % p.grid_w); py = (uint32_t)(ray_idx / p.grid_w); }
-	return true;
+	TileGrid tg;
+	if (tile_grid(p, tg)) return tile_lane(tg, wave_tile(tg, g >> 6), (uint32_t)g & 63u, ray_idx, px, py);
+	return linear_ray(p, g >> 6, (uint32_t)g & 63u, ray_idx, px, py);
 }
 
 // What a wave's schedule unit cost (shader cycles, modulo 2^32), for the next frame's longest-first launch order.  The
@@ -164,8 +118,9 @@ __device__ __forceinline__ bool tile_cost_word(const TraceParams &p, uint64_t g_
 	if (p.lane_map == MAP_AUTO) { if (p.auto_grid[0] == 0u) return false; rows = p.auto_grid[1]; tiles_x = p.auto_grid[2]; }
 	else if (p.lane_map != MAP_TILE8X8) return false;
 	const uint32_t k = p.tile_w_log2, tiles_y = (rows + (64u >> k) - 1u) >> (6u - k);
-	if (((uint64_t)tiles_x * tiles_y + p.tile_unit - 1u) / p.tile_unit != p.n_units) return false; // not the grid the arrays were sized for
-	const uint64_t slot = (g_first >> 6) / p.tile_unit;
+	if (!sched_matches((uint64_t)tiles_x * tiles_y, p.tile_unit, p.n_units)) return false; // not the grid the arrays were sized for
+	const uint64_t group = g_first >> 6;
+	const uint64_t slot = p.tile_unit == 1u ? group : (p.tile_unit == 2u ? group >> 1 : group / p.tile_unit);
 	what = 0u;
 	if (p.tile_sched == nullptr) { if (slot >= p.n_units) return false; park = sum = p.tile_cost + slot; return true; }
 	if (slot >= (p.sched_hdr ? p.sched_hdr[2] : p.n_units)) return false;
@@ -238,6 +193,20 @@ __device__ __forceinline__ void grid_ray(const TraceParams &p, uint32_t px, uint
 	r.t_min = c.t_min; r.t_max = c.t_max;
 }
 
+// streaming forms of a 16-byte load and store: data touched once per launch (rays, records) that should not displace the scene's rows
+typedef float mrt_v4f __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 stream_load4(const float4 *q)
+{
+	const mrt_v4f v = __builtin_nontemporal_load(reinterpret_cast<const mrt_v4f *>(q));
+	return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void stream_store4(float4 *q, const float4 &a)
+{
+	const mrt_v4f v = {a.x, a.y, a.z, a.w};
+	__builtin_nontemporal_store(v, reinterpret_cast<mrt_v4f *>(q));
+}
+
+template <bool STREAM = false>
 __device__ __forceinline__ void load_ray(const TraceParams &p, uint64_t idx, uint32_t px, uint32_t py, RayRegs &r)
 {
 	if (p.in_fmt == IN_GRID) { grid_ray(p, px, py, r); return; }
@@ -248,7 +217,7 @@ __device__ __forceinline__ void load_ray(const TraceParams &p, uint64_t idx, uin
 		t0 = h[12]; t1 = h[13];
 	} else {
 		const float4 *q = reinterpret_cast<const float4 *>(p.rays) + idx * 2u;
-		const float4 a = q[0], b = q[1];
+		const float4 a = STREAM ? stream_load4(q) : q[0], b = STREAM ? stream_load4(q + 1) : q[1];
 		ox = a.x; oy = a.y; oz = a.z; t1 = a.w;
 		dx = b.x; dy = b.y; dz = b.z; t0 = b.w;
 	}
@@ -257,6 +226,7 @@ __device__ __forceinline__ void load_ray(const TraceParams &p, uint64_t idx, uin
 
 // Result store: bvh_traverse.comp.glsl:322-327, plus the readback conversion of
 // gpu_ray_caster.cpp:442-456 (OUT_HOST44) / :482-487 (OUT_BOOL8) fused in.
+template <bool STREAM = false>
 __device__ __forceinline__ void store_hit(const TraceParams &p, uint64_t idx, const RayRegs &r,
 		float t, int32_t prim, float u, float v, float nx, float ny, float nz, uint32_t layers, uint32_t slot)
 {
@@ -280,11 +250,12 @@ __device__ __forceinline__ void store_hit(const TraceParams &p, uint64_t idx, co
 	float4 a, b;
 	a.x = t; a.y = __int_as_float(prim); a.z = u; a.w = v;
 	b.x = nx; b.y = ny; b.z = nz; b.w = __uint_as_float(layers);
-	q[0] = a; q[1] = b;
+	if (STREAM) { stream_store4(q, a); stream_store4(q + 1, b); }
+	else { q[0] = a; q[1] = b; }
 }
 
-// End of a ray in every kernel: look up what the record needs about the winning triangle (id,
-// layers, the cold normal row) and store it.  Bool and token outputs need none of that.
+// End of a ray in every kernel but the row kernels (finish_row_ray, packet_rows_kernel.h): look up what the record
+// needs about the winning triangle (id, layers, the cold normal row) and store it.  Bool and token outputs need none of that.
 __device__ __forceinline__ void finish_ray(const TraceParams &p, uint64_t ray_idx, const RayRegs &r,
 		float best_t, float best_u, float best_v, uint32_t best_slot)
 {

@@ -832,6 +832,34 @@ __device__ __forceinline__ int rows_octant(const RayRegs &r, bool part, unsigned
 	return uniform ? ((sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0)) : 8;
 }
 
+// the generic walk (mixed octants) reports a leaf-order slot: the row and the id the record is made from
+__device__ __forceinline__ void rows_hit_of_slot(const float4 *rows, uint32_t n_nodes, uint32_t slot, PacketRegs &s)
+{
+	s.bs = 0xFFFFFFFFu;
+	if (slot != 0xFFFFFFFFu) { s.bs = slot + n_nodes; s.bi = __float_as_uint(rows[(size_t)s.bs * 4u].w); }
+}
+
+// End of a ray in the row kernels: the record from what the walk holds.  The id is the one kept for the tie rule; layers and the
+// normal are dwords 7 and 12..14 of the winning triangle's own row, a line the packet fetched moments ago (finish_ray gathers
+// them from the hot and the cold array, which this kernel never touches otherwise).  Bool and token outputs need none of that.
+template <bool STREAM>
+__device__ __forceinline__ void finish_row_ray(const TraceParams &p, const float4 *rows, uint64_t ray_idx, const RayRegs &r,
+		float best_t, float best_u, float best_v, uint32_t best_row, uint32_t best_id, uint32_t best_slot)
+{
+	int32_t prim = -1; float nx = 0.0f, ny = 0.0f, nz = 0.0f; uint32_t layers = 0u;
+	if (best_row != 0xFFFFFFFFu) {
+		if (p.out_fmt == OUT_BOOL8 || p.out_fmt == OUT_TOKEN4) prim = 0; // only "hit or not" (and the slot) is stored
+		else {
+			const float4 *row = rows + (size_t)best_row * 4u;
+			prim = (int32_t)best_id;
+			layers = __float_as_uint(reinterpret_cast<const float *>(row)[7]);
+			const float4 nn = row[3];
+			nx = nn.x; ny = nn.y; nz = nn.z;
+		}
+	}
+	store_hit<STREAM>(p, ray_idx, r, best_t, prim, best_u, best_v, nx, ny, nz, layers, best_slot);
+}
+
 #ifndef MRT_ROWS_WPE
 #define MRT_ROWS_WPE 8
 #endif
@@ -846,6 +874,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS_WPE
 	// per wave and packet: 16-byte stack entries {ref, -, lane mask}; entry 0 holds the sentinel
 	__shared__ __attribute__((aligned(16))) uint32_t wave_stack[WG / MRT_WAVE][PACKETS][(MRT_PACKET_STACK + 1) * 4];
 	if (skip_launch(p)) return;
+	// Rays are read and records written once per launch: in the one-wave workgroups api.hip picks for scenes whose rows the caches can
+	// hold (up to 256 MB) they stream past those rows (non-temporal: C3 1.89 -> 1.73 ms); beyond, the rows fit no cache either way (C5
+	// measured the same with and without), and the 256-thread culling form spilled registers with the streaming loads.
+	constexpr bool STREAM = WG == MRT_WAVE;
 	uint32_t block = blockIdx.x;
 	if (p.xcd_swizzle) {
 		const uint32_t per = gridDim.x >> 3;
@@ -853,16 +885,28 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS_WPE
 	}
 	const uint32_t wave = threadIdx.x / MRT_WAVE, lane = threadIdx.x & (MRT_WAVE - 1);
 	const uint32_t wave_s = __builtin_amdgcn_readfirstlane(wave), block_s = block; // (scalars: for the epilogue)
-	const uint64_t g_a = (((uint64_t)block * (WG / MRT_WAVE) + wave) * PACKETS) * MRT_WAVE + lane, g_b = g_a + MRT_WAVE;
+	const uint64_t group_a = ((uint64_t)block_s * (WG / MRT_WAVE) + wave_s) * PACKETS; // the wave's first group of 64 rays
+	// The wave's tiles, once, on the scalar unit (lane_map.h): the second group's follows from the first's.  They stay in scalar
+	// registers across the walk, for the epilogue: tile_a / tile_b = column | row of a tile, tile_code = the two pieces.
+	TileGrid tg;
+	const bool tiled = tile_grid(p, tg);
+	WaveTile ta = {0u, 0u, kPieceNone}, tb = ta;
+	if (tiled) {
+		ta = wave_tile(tg, group_a);
+		if (PACKETS == 2) tb = wave_tile_next(tg, ta, group_a);
+	}
+	const uint32_t tile_ax = __builtin_amdgcn_readfirstlane(ta.tx), tile_ay = __builtin_amdgcn_readfirstlane(ta.ty);
+	const uint32_t tile_bx = __builtin_amdgcn_readfirstlane(tb.tx), tile_by = __builtin_amdgcn_readfirstlane(tb.ty);
+	const uint32_t tile_code = __builtin_amdgcn_readfirstlane((ta.code & 0xFFu) | (tb.code & 0xFFu) << 8 | (tiled ? 1u << 16 : 0u));
 	uint64_t idx = 0; uint32_t px = 0, py = 0;
-	const bool valid_a = lane_ray_index_g(p, g_a, idx, px, py);
+	const bool valid_a = tiled ? tile_lane(tg, ta, lane, idx, px, py) : linear_ray(p, group_a, lane, idx, px, py);
 	// a lane without a ray in a packet walks along with an empty interval
 	RayRegs ra = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f}, rb = ra;
-	if (valid_a) load_ray(p, idx, px, py, ra);
+	if (valid_a) load_ray<STREAM>(p, idx, px, py, ra);
 	bool valid_b = false;
 	if (PACKETS == 2) {
-		valid_b = lane_ray_index_g(p, g_b, idx, px, py);
-		if (valid_b) load_ray(p, idx, px, py, rb);
+		valid_b = tiled ? tile_lane(tg, tb, lane, idx, px, py) : linear_ray(p, group_a + 1u, lane, idx, px, py);
+		if (valid_b) load_ray<STREAM>(p, idx, px, py, rb);
 	}
 	if (__ballot(valid_a || valid_b) == 0ull) return; // nothing for this wave (otherwise every lane stays in)
 
@@ -883,7 +927,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS_WPE
 	uint32_t sp_wide = 0u, sp_one = 0u; // COUNT: highest stack pointers seen (LDS byte addresses) by the 128-ray / the one-packet walk
 	// the wave's start time waits in memory, not in registers (none to spare in the walk): in the cost array itself
 	// (note_tile_start / note_tile_cost), and for the counting builds in the unused words of the stack's sentinel entry
-	if (p.tile_cost != nullptr && lane == 0u) note_tile_start(p, g_a);
+	if (p.tile_cost != nullptr && lane == 0u) note_tile_start(p, group_a << 6);
 	if (COUNT) *(volatile unsigned long long *)&stack_a[2] = __builtin_amdgcn_s_memtime();
 	bool done_a = part_a == 0ull, done_b = part_b == 0ull;
 	if (PACKETS == 2 && !done_a && !done_b && oct_a == oct_b && oct_a != 8) {
@@ -917,24 +961,32 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS_WPE
 		A.bt = ra.t_max;
 		packet_traverse<8, ANY_HIT, COUNT>(p, ra, stack_a, A.bt, A.bu, A.bv, slot_a, nn, nt, nd, 0u, 0u, nullptr, !valid_a);
 		if (COUNT) { cnt_n += __builtin_amdgcn_readfirstlane(nn); cnt_t += __builtin_amdgcn_readfirstlane(nt); }
+		rows_hit_of_slot(rows, p.n_nodes, slot_a, A);
 	}
 	if (PACKETS == 2 && !done_b) {
 		uint32_t nn = 0, nt = 0, nd = 0;
 		B.bt = rb.t_max;
 		packet_traverse<8, ANY_HIT, COUNT>(p, rb, stack_b, B.bt, B.bu, B.bv, slot_b, nn, nt, nd, 0u, 0u, nullptr, !valid_b);
 		if (COUNT) { cnt_n += __builtin_amdgcn_readfirstlane(nn); cnt_t += __builtin_amdgcn_readfirstlane(nt); }
+		rows_hit_of_slot(rows, p.n_nodes, slot_b, B);
 	}
 
-	// The rays' indices again, from nothing the prologue computed (the wave from a scalar, the lane from the exec-mask
-	// count): no index, pixel or validity flag stays live across the walk, where every vector register is spoken for
-	// (the compiler spilled 18 of them to scratch around the assembly block: 0.3 GB of writes per C3 launch).
+	// The rays' indices again, from the wave's tiles (scalars) and the lane (the exec-mask count): no index, pixel or validity
+	// flag stays live across the walk, where every vector register is spoken for (the compiler spilled 18 of them to scratch
+	// around the assembly block: 0.3 GB of writes per C3 launch).  Only the lane's part of the map runs again.
 	{
 		const uint32_t lane2 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-		const uint64_t h_a = (((uint64_t)block_s * (WG / MRT_WAVE) + wave_s) * PACKETS) * MRT_WAVE + lane2;
+		const uint64_t h_a = ((uint64_t)block_s * (WG / MRT_WAVE) + wave_s) * PACKETS;
+		const bool tiled2 = (tile_code >> 16 & 1u) != 0u;
+		TileGrid tg2;
+		(void)tile_grid(p, tg2); // (of which the lane's part reads the clip rectangle and the tile's shape)
+		const WaveTile ua = {tile_ax, tile_ay, tile_code & 0xFFu}, ub = {tile_bx, tile_by, tile_code >> 8 & 0xFFu};
 		uint64_t idx2 = 0; uint32_t px2 = 0, py2 = 0;
-		if (lane_ray_index_g(p, h_a, idx2, px2, py2)) finish_ray(p, idx2, ra, A.bt, A.bu, A.bv, slot_a);
-		if (PACKETS == 2 && lane_ray_index_g(p, h_a + MRT_WAVE, idx2, px2, py2)) finish_ray(p, idx2, rb, B.bt, B.bu, B.bv, slot_b);
-		if (p.tile_cost != nullptr && lane2 == 0u) note_tile_cost(p, h_a);
+		if (tiled2 ? tile_lane(tg2, ua, lane2, idx2, px2, py2) : linear_ray(p, h_a, lane2, idx2, px2, py2))
+			finish_row_ray<STREAM>(p, rows, idx2, ra, A.bt, A.bu, A.bv, A.bs, A.bi, slot_a);
+		if (PACKETS == 2 && (tiled2 ? tile_lane(tg2, ub, lane2, idx2, px2, py2) : linear_ray(p, h_a + 1u, lane2, idx2, px2, py2)))
+			finish_row_ray<STREAM>(p, rows, idx2, rb, B.bt, B.bu, B.bv, B.bs, B.bi, slot_b);
+		if (p.tile_cost != nullptr && lane2 == 0u) note_tile_cost(p, h_a << 6);
 	}
 	const unsigned long long t_start = COUNT ? *(volatile unsigned long long *)&stack_a[2] : 0ull;
 	if (COUNT && lane == 0u && (p.count_mode != 2u || (blockIdx.x & 15u) == 0u)) { // the wave's clock: cycles in the row-fetch waits of the one-packet loop, cycles in all
