@@ -271,8 +271,9 @@ const char *mrt_last_error(const mrt_ctx *ctx);
 const char *mrt_status_string(int status);
 uint32_t mrt_version(void);
 /* sizeof() of the boundary's structs as this library was compiled, for bindings in other languages to check
- * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light (0 for anything
- * else). */
+ * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light, 6 mrt_material,
+ * 7 mrt_shade_data, 8 mrt_surface64, 9 mrt_surface_out, 11 mrt_shade_light, 12 mrt_environment, 13 mrt_light_out (0 for
+ * anything else). */
 uint32_t mrt_struct_size(uint32_t which);
 /* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream). */
 int mrt_set_stream(mrt_ctx *ctx, void *hip_stream);
@@ -805,6 +806,101 @@ int mrt_resolve_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_hits, u
  * whole frame resolves.  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
 int mrt_resolve_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h,
 		uint32_t y0, uint32_t y1, const void *d_hits, const mrt_surface_out *out, uint32_t flags);
+
+/* ---- direct light on resolved surfaces: ShadePass::cook_torrance_multi_light (src/modules/graphics/shade_pass.h:597-657),
+ * the loop shade_material runs for RayRenderer's frame and PathTrace::compute_direct_light for next-event estimation, and the
+ * three plain terms shade_material adds around it (the analytic sky for a miss, the hemisphere ambient, the emission), run
+ * per record as one kernel on the rows mrt_resolve_surfaces wrote and the mask mrt_cast_shadows wrote.  Tone mapping, gamma,
+ * the panorama sky, throughput and path state stay with the renderer. */
+
+/* LightData (src/api/light_data.h); 64 bytes.  The first 32 bytes are mrt_light field for field. */
+typedef struct mrt_shade_light {
+	uint32_t type;           /* MRT_LIGHT_*                                                                     */
+	uint32_t cast_shadows;   /* as mrt_light (not read by the lighting calls: the mask already carries it)      */
+	float position[3];       /* POINT / SPOT                                                                    */
+	float direction[3];      /* DIRECTIONAL: towards the light; SPOT: the cone's axis; used as given            */
+	float color[3];          /* colour x energy, linear                                                         */
+	float range;             /* POINT / SPOT: > 0                                                               */
+	float attenuation;       /* POINT / SPOT: the distance falloff's exponent, >= 0                             */
+	float spot_angle;        /* SPOT: the outer half angle in radians                                           */
+	float spot_angle_attenuation;   /* SPOT: the cone falloff's exponent, >= 0                                  */
+	uint32_t reserved;       /* must be 0                                                                       */
+} mrt_shade_light;
+/* The shadow half of each light (its first 32 bytes), so that one light list feeds mrt_cast_shadows and the lighting calls.
+ * Host only; nothing is checked.  MRT_ERR_INVALID for a null pointer with n > 0. */
+int mrt_shadow_lights(const mrt_shade_light *lights, uint32_t n, mrt_light *out);
+
+/* The analytic half of ShadePass::EnvironmentData (ProceduralSkyMaterial's gradient and the ambient light); 64 bytes. */
+typedef struct mrt_environment {
+	float sky_zenith[3], sky_horizon[3], sky_ground[3];
+	float ambient[3];        /* ambient light colour */
+	float ambient_energy;
+	uint32_t reserved[3];    /* not read */
+} mrt_environment;
+
+typedef struct mrt_light_out {
+	float *d_rgba;           /* 4 floats per record {r, g, b, a}: a = 1 for a hit, 0 for a miss (an RGBAF32 frame) */
+} mrt_light_out;
+
+/* Lights every record.  hit, p (the position) and d (the incoming direction) of a record as mrt_resolve_surfaces takes
+ * them; n, n_dot_v, albedo, metallic, roughness, specular, emission from the record's row of d_rows (what
+ * mrt_resolve_surfaces wrote).  Plain fp32 operations in this order, nothing contracted; normalized() as for the resolve;
+ * max(x, 0) is x < 0 ? 0 : x; a . b is (ax*bx + ay*by) + az*bz; PI = 3.14159265358979323846f:
+ *   v = normalized(-d); one_m = 1 - metallic; per channel c: f0.c = ((0.04f * specular) * 2.0f) * one_m + albedo.c * metallic,
+ *   diff.c = albedo.c * one_m.  rgb = 0, then per light in list order:
+ *     DIRECTIONAL: L = direction as given, atten = 1.
+ *     POINT / SPOT: to = position - p; dist = sqrt((to.x*to.x + to.y*to.y) + to.z*to.z); skip the light if dist < 1e-6f ||
+ *       dist > range; L = to / dist per component; ratio = dist / range;
+ *       atten = pow01(max(1.0f - ratio * ratio, 0), attenuation).
+ *     SPOT in addition: cos_angle = (L.x*direction.x + L.y*direction.y) + L.z*direction.z; the factor is 0 if cos_angle <=
+ *       cos_outer, else pow01(max((cos_angle - cos_outer) / (1.0f - cos_outer), 0), spot_angle_attenuation); atten = atten *
+ *       factor.  cos_outer = cosf(spot_angle) and 1.0f - cos_outer are computed once per call on the host (the C library's
+ *       cosf) and passed to the kernel: never on the device.
+ *     skip if atten < 1e-6f.  ndl = n . L; skip if ndl <= 0.  skip if d_mask is given and d_mask[l * count + i] == 0.
+ *     h = normalized(v + L); n_dot_h = max(n . h, 0); v_dot_h = max(v . h, 0); a = roughness * roughness; a2 = a * a.
+ *     D = a2 / ((PI * den) * den + 1e-7f) with den = (n_dot_h * n_dot_h) * (a2 - 1.0f) + 1.0f            (distribution_ggx)
+ *     G = g1(n_dot_v) * g1(ndl), g1(x) = (2.0f * x) / ((x + sqrt(a2 + ((1.0f - a2) * x) * x)) + 1e-7f)  (geometry_smith_ggx)
+ *     t = 1.0f - v_dot_h; t2 = t * t; F.c = f0.c + (1.0f - f0.c) * ((t2 * t2) * t)                       (fresnel_schlick)
+ *     spec_scale = (D * G) / ((4.0f * n_dot_v) * ndl + 1e-7f); diff_scale = 1.0f / PI (one float constant)
+ *     rgb.c = rgb.c + ((((diff.c * (1.0f - F.c)) * diff_scale + F.c * spec_scale) * (color.c * atten)) * ndl)
+ *   env == NULL: a hit writes {rgb, 1}, a miss {0, 0, 0, 0}.
+ *   env given (shade_material just before tonemap_rgb): a hit adds, per channel, first
+ *     ((diff.c * (ground.c + (zenith.c - ground.c) * (n.y * 0.5f + 0.5f))) * ambient.c) * ambient_energy, then emission.c;
+ *     a miss writes the sky gradient of d as given: t = d.y * 0.5f + 0.5f; t > 0.5f: horizon.c + (zenith.c - horizon.c) *
+ *     ((t - 0.5f) * 2.0f); else ground.c + (horizon.c - ground.c) * (t * 2.0f); a = 0.
+ * pow01(b, e), for b in [0, 1] and finite e >= 0, is defined by arithmetic alone so that the device, the host and numpy
+ * float64 hold the same bits: e == 0 -> 1; b == 0 -> 0; b == 1 -> 1 (in that order); otherwise in fp64, one operation at a
+ * time, + - * / only (the exponent field of a double is read and written as integer bits):
+ *   x = (double)b = m * 2^k with m in [1, 2); if m > 1.4142135623730951: m = m * 0.5, k = k + 1.
+ *   s = (m - 1) / (m + 1); s2 = s * s; q = Horner in s2 of LOG[k] = 2 / (2k + 1), k = 11 .. 0 (q = q * s2 + LOG[k]);
+ *   lg = k * LN2_HI + (s * q + k * LN2_LO); y = (double)e * lg.  y < -104: 0.  y > 89: +infinity.
+ *   n = (y * INV_LN2 + 6755399441055744.0) - 6755399441055744.0 (the nearest integer); r = (y - n * LN2_HI) - n * LN2_LO;
+ *   p = Horner in r of EXP[k] = 1 / k!, k = 13 .. 0; the result is (float)(p * 2^n), rounded once.
+ *   LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10, INV_LN2 = 1.44269504088896338700e+00;
+ *   LOG = {2.0, 0.66666666666666663, 0.40000000000000002, 0.2857142857142857, 0.22222222222222221, 0.18181818181818182,
+ *     0.15384615384615385, 0.13333333333333333, 0.11764705882352941, 0.10526315789473684, 0.095238095238095233,
+ *     0.086956521739130432};
+ *   EXP = {1.0, 1.0, 0.5, 0.16666666666666666, 0.041666666666666664, 0.0083333333333333332, 0.0013888888888888889,
+ *     0.00019841269841269841, 2.4801587301587302e-05, 2.7557319223985893e-06, 2.7557319223985888e-07,
+ *     2.505210838544172e-08, 2.08767569878681e-09, 1.6059043836821613e-10}.
+ *   pow01(b, 1) == b for every b; elsewhere it is within 1 fp32 ulp of the correctly rounded power.
+ * d_rays / d_hits as for mrt_resolve_surfaces (MRT_FLAG_HOST_LAYOUT: mrt_host_ray60 + mrt_host_hit44); d_rows, d_mask and
+ * out->d_rgba are device pointers, `lights` and `env` host pointers.  d_mask (optional) is indexed [l * count + i] as
+ * mrt_cast_shadows writes it; null: every pair is lit.  n_lights == 0 is valid (lights may then be null): direct is 0 and
+ * the environment terms still apply.  No scene is required and nothing is walked.  Flags: MRT_FLAG_HOST_LAYOUT,
+ * MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID, before any device work, for: a null required
+ * pointer, an unknown flag, n_lights > MRT_MAX_LIGHTS, an unknown light type, a non-zero reserved word of a light, a light
+ * float that is not finite, range not > 0 on a point or spot light, a negative attenuation or spot_angle_attenuation, an
+ * environment float that is not finite, count * n_lights overflowing; MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_light_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_hits, const mrt_surface64 *d_rows, uint64_t count,
+		const mrt_shade_light *lights, uint32_t n_lights, const uint8_t *d_mask, const mrt_environment *env,
+		const mrt_light_out *out, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_hits as it wrote them, mrt_hit32; d_rows, d_mask and
+ * the output indexed by the record within the band): the primary rays are regenerated in the kernel, so a band lights what
+ * the whole frame lights.  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_light_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const void *d_hits, const mrt_surface64 *d_rows, const mrt_shade_light *lights, uint32_t n_lights,
+		const uint8_t *d_mask, const mrt_environment *env, const mrt_light_out *out, uint32_t flags);
 
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to

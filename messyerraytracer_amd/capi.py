@@ -32,7 +32,8 @@ SYMBOLS = [
     "mrt_build_scene_device", "mrt_flatten_instances", "mrt_build_instanced_scene_device", "mrt_refit_scene", "mrt_refit_instanced_scene", "mrt_upload_two_level_scene", "mrt_refit_two_level_scene", "mrt_update_instances", "mrt_update_instances_device", "mrt_two_level_prepare_host", "mrt_two_level_host_arrays", "mrt_two_level_free_host", "mrt_scene_prepare_host", "mrt_scene_host_arrays", "mrt_scene_free_host", "mrt_debug_snapshot", "mrt_is_available", "mrt_scene_info", "mrt_cast", "mrt_submit", "mrt_collect", "mrt_has_pending",
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
     "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_cast_bounce", "mrt_cast_grid_bounce",
-    "mrt_upload_shade_data", "mrt_clear_shade_data", "mrt_resolve_surfaces", "mrt_resolve_grid_surfaces", "mrt_expand_tokens",
+    "mrt_upload_shade_data", "mrt_clear_shade_data", "mrt_resolve_surfaces", "mrt_resolve_grid_surfaces",
+    "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
     "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
     "mrt_group_create", "mrt_group_destroy", "mrt_group_size", "mrt_group_context", "mrt_group_last_error", "mrt_group_row_block",
@@ -87,7 +88,13 @@ class SurfaceOut(C.Structure):
     _fields_ = [("d_rows", C.c_void_p), ("d_bounce_surface", C.c_void_p), ("d_out_hits", C.c_void_p)]
 
 
+class LightOut(C.Structure):
+    """mrt_light_out"""
+    _fields_ = [("d_rgba", C.c_void_p)]
+
+
 SHADE_ARRAYS_ON_DEVICE = 1
+STRUCT_SHADE_LIGHT, STRUCT_ENVIRONMENT, STRUCT_LIGHT_OUT = 11, 12, 13   # mrt_struct_size indices
 STRUCT_MATERIAL, STRUCT_SHADE_DATA, STRUCT_SURFACE64, STRUCT_SURFACE_OUT = 6, 7, 8, 9   # mrt_struct_size indices
 
 
@@ -214,6 +221,11 @@ def load():
     L.mrt_resolve_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SurfaceOut), C.c_uint32]
     L.mrt_resolve_grid_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                             C.POINTER(SurfaceOut), C.c_uint32]
+    L.mrt_shadow_lights.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.mrt_light_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.POINTER(LightOut), C.c_uint32]
+    L.mrt_light_grid_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(LightOut), C.c_uint32]
     L.mrt_cast_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mrt_expand_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
     L.mrt_expand_grid_tokens.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -266,6 +278,16 @@ def surface_out(d_rows=None, d_bounce_surface=None, d_out_hits=None):
     """mrt_surface_out from its fields (device pointers / tensors or None)"""
     v = [None if x is None else _ptr(x).value for x in (d_rows, d_bounce_surface, d_out_hits)]
     return SurfaceOut(v[0], v[1], v[2])
+
+
+def shadow_lights(lights) -> np.ndarray:
+    """mrt_shadow_lights: the shadow half (T.LIGHT) of each T.SHADE_LIGHT row, for cast_shadows"""
+    lights = np.ascontiguousarray(lights, dtype=T.SHADE_LIGHT).reshape(-1)
+    out = np.zeros(lights.shape[0], T.LIGHT)
+    st = load().mrt_shadow_lights(_np(lights) if lights.shape[0] else None, lights.shape[0], _np(out) if lights.shape[0] else None)
+    if st != 0:
+        raise MrtError(st, "mrt_shadow_lights")
+    return out
 
 
 def _ptr(x):
@@ -758,6 +780,31 @@ class Context:
         y1 = grid_h if y1 is None else y1
         out = surface_out(d_rows, d_bounce_surface, d_out_hits)
         self._chk(self.L.mrt_resolve_grid_surfaces(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(out), flags))
+
+    @staticmethod
+    def _shade_lights(lights, env):
+        lights = np.ascontiguousarray(lights, dtype=T.SHADE_LIGHT).reshape(-1)
+        env = None if env is None else np.ascontiguousarray(env, dtype=T.ENVIRONMENT).reshape(1)
+        return lights, (_np(lights) if lights.shape[0] else None), env, (None if env is None else _np(env))
+
+    def light_surfaces(self, d_rays, d_hits, d_rows, count, lights, d_rgba, d_mask=None, env=None, flags=0):
+        """Direct light (Cook-Torrance over all lights) on the rows resolve_surfaces wrote, for the records of a cast (device pointers /
+        tensors: mrt_ray32 + mrt_hit32, or mrt_host_ray60 + mrt_host_hit44 with FLAG_HOST_LAYOUT).  lights: T.SHADE_LIGHT array on the
+        host; d_mask: optional, what cast_shadows wrote for shadow_lights(lights); env: optional T.ENVIRONMENT row (sky for a miss,
+        ambient and emission for a hit).  d_rgba: 4 floats per record."""
+        lights, lp, env, ep = self._shade_lights(lights, env)
+        out = LightOut(_ptr(d_rgba).value)
+        self._chk(self.L.mrt_light_surfaces(self.h, _ptr(d_rays), _ptr(d_hits), _ptr(d_rows), count, lp, lights.shape[0], _optr(d_mask),
+                                            ep, C.byref(out), flags))
+
+    def light_grid_surfaces(self, cam, grid_w, grid_h, d_hits, d_rows, lights, d_rgba, d_mask=None, env=None, y0=0, y1=None, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (d_hits: its mrt_hit32 records on the device; d_rows, d_mask and d_rgba
+        indexed by the record within the band)."""
+        y1 = grid_h if y1 is None else y1
+        lights, lp, env, ep = self._shade_lights(lights, env)
+        out = LightOut(_ptr(d_rgba).value)
+        self._chk(self.L.mrt_light_grid_surfaces(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _ptr(d_rows), lp,
+                                                 lights.shape[0], _optr(d_mask), ep, C.byref(out), flags))
 
     def expand_tokens(self, d_rays, d_tokens, d_hits, count, flags=0, stream=None):
         """Device pointers; enqueued on `stream` (raw hipStream_t) or the context's stream, not waited for."""

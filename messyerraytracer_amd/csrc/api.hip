@@ -157,6 +157,9 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 7: return (uint32_t)sizeof(mrt_shade_data);
 		case 8: return (uint32_t)sizeof(mrt_surface64);
 		case 9: return (uint32_t)sizeof(mrt_surface_out);
+		case 11: return (uint32_t)sizeof(mrt_shade_light); // (10: not a struct)
+		case 12: return (uint32_t)sizeof(mrt_environment);
+		case 13: return (uint32_t)sizeof(mrt_light_out);
 		default: return 0u;
 	}
 }

@@ -17,6 +17,7 @@
 #include <type_traits>
 #include "mrt_internal.h"
 #include "shade_data.h"
+#include "lighting.h"
 #include "lane_map.h"
 
 namespace mrt {
@@ -954,6 +955,21 @@ hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s,
 	if (src == SURF_RAY32) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_RAY32>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
 	else if (src == SURF_HOST) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_HOST>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
 	else if (src == SURF_GRID) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_GRID>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+#include "light_kernel.h"
+
+// src = a SurfaceSrc; anything else is hipErrorInvalidValue
+hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int src, hipStream_t stream)
+{
+	if (p.count == 0) return hipSuccess;
+	const uint64_t blocks = (p.count + MRT_WG - 1) / MRT_WG;
+	if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	if (src == SURF_RAY32) hipLaunchKernelGGL(light_surfaces_kernel<SURF_RAY32>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else if (src == SURF_HOST) hipLaunchKernelGGL(light_surfaces_kernel<SURF_HOST>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else if (src == SURF_GRID) hipLaunchKernelGGL(light_surfaces_kernel<SURF_GRID>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
 	else return hipErrorInvalidValue;
 	return hipGetLastError();
 }

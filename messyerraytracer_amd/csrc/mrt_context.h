@@ -25,6 +25,9 @@ hipError_t launch_build_rows(const DevNode *nodes, const TriHot *hot, const TriC
 hipError_t launch_expand_tokens(const TraceParams &p, const uint32_t *tokens, hipStream_t stream);
 // shading surfaces (surface_kernel.h): src = a SurfaceSrc; the rows of shade data given as device arrays (any of the three may be null)
 hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream);
+// direct light on resolved surfaces (light_kernel.h): src = a SurfaceSrc
+struct LightParams;
+hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int src, hipStream_t stream);
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream);
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);
 hipError_t launch_collapse8(const DevNode *nodes, uint32_t n_nodes, Dev8Node *nodes8, float *leaf_box, uint32_t *bad, hipStream_t stream);

@@ -37,6 +37,14 @@ SURFACE64 = np.dtype([("normal", "<f4", 3), ("n_dot_v", "<f4"), ("albedo", "<f4"
 DEFAULT_MATERIAL = 0xFFFFFFFF
 assert MATERIAL.itemsize == 48 and SURFACE64.itemsize == 64
 
+# direct light on resolved surfaces (mrt_light_surfaces)
+SHADE_LIGHT = np.dtype([("type", "<u4"), ("cast_shadows", "<u4"), ("position", "<f4", 3), ("direction", "<f4", 3), ("color", "<f4", 3),
+                        ("range", "<f4"), ("attenuation", "<f4"), ("spot_angle", "<f4"), ("spot_angle_attenuation", "<f4"),
+                        ("reserved", "<u4")])  # mrt_shade_light: mrt_light, then the rest of LightData
+ENVIRONMENT = np.dtype([("sky_zenith", "<f4", 3), ("sky_horizon", "<f4", 3), ("sky_ground", "<f4", 3), ("ambient", "<f4", 3),
+                        ("ambient_energy", "<f4"), ("reserved", "<u4", 3)])  # mrt_environment
+assert SHADE_LIGHT.itemsize == 64 and ENVIRONMENT.itemsize == 64
+
 # rows of the device layouts (csrc/mrt_internal.h), as mrt_debug_snapshot and the host preparations return them
 TRI_HOT = np.dtype([("v0", "<f4", 3), ("id", "<u4"), ("e1", "<f4", 3), ("layers", "<u4"), ("e2", "<f4", 3), ("flags", "<u4")])
 TRI_COLD = np.dtype([("normal", "<f4", 3), ("pad", "<u4")])
