@@ -1,6 +1,8 @@
-// launch_policy_test.cpp — pins the cast launch policy (launch_policy.cpp) without a device: a table of casts and the plan
-// each one must get, then the grid kernel tuner over fifteen frames with fake timings, the per-grid state LRU and the detected
-// width across sequences of blocking, ASYNC, pipelined and submitted casts (DetectMemo).
+// launch_policy_test.cpp — pins the cast launch policy (launch_policy.cpp) without a device: a table of casts, the plan each one
+// must get and what that plan runs (the instantiation's name and its launch geometry, resolve_trace / resolve_persistent), a second
+// table of hand-made TraceParams on both sides of every branch the resolvers have, the labels of record-driven casts, then the
+// grid kernel tuner over fifteen frames with fake timings, the per-grid state LRU and the detected width across sequences of
+// blocking, ASYNC, pipelined and submitted casts (DetectMemo).
 // Exit status 0 iff every check holds; one line per failure.
 #include <array>
 #include <cstdio>
@@ -98,6 +100,7 @@ struct Case {
 	uint32_t w, h, y0, rows; // grids; for a previous detect (array casts): what it found, {w, h, w / 8}
 	int prev;
 	const char *want;
+	const char *runs; // what launch_planned puts on the stream for the plan: runs()
 };
 
 constexpr uint32_t COH = MRT_FLAG_COHERENT, FORCE = MRT_FLAG_FORCE_SORT, ASYNC = MRT_FLAG_ASYNC | MRT_FLAG_RAYS_ON_DEVICE | MRT_FLAG_HITS_ON_DEVICE;
@@ -108,129 +111,321 @@ Opt with(Opt o, uint32_t Opt::*f, uint32_t v) { o.*f = v; return o; }
 
 const Case kCases[] = {
 	// ---- rays from an array, not declared coherent: the lane kernels; a sort from 256 rays unless one ray per wave (<= 8 192 rays)
-	{"incoherent 1", AUTO, FLAT, ENTRY_CAST, 1, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"incoherent 63", AUTO, FLAT, ENTRY_CAST, 63, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"incoherent 255", AUTO, FLAT, ENTRY_CAST, 255, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"incoherent 256", AUTO, FLAT, ENTRY_CAST, 256, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"incoherent 8192", AUTO, FLAT, ENTRY_CAST, 8192, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"incoherent 8193", AUTO, FLAT, ENTRY_CAST, 8193, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=2) sort n=3"},
-	{"incoherent 2^15-1", AUTO, FLAT, ENTRY_CAST, 32767, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=4) sort n=3"},
-	{"incoherent 2^15", AUTO, FLAT, ENTRY_CAST, 32768, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=4) sort n=3"},
-	{"incoherent 2^15+1", AUTO, FLAT, ENTRY_CAST, 32769, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=0) sort n=3"},
-	{"incoherent 65535", AUTO, FLAT, ENTRY_CAST, 65535, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=0) sort n=3"},
-	{"incoherent 65536", AUTO, FLAT, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=16 spill=0 wait=8) sort n=3"},
-	{"incoherent 2^17", AUTO, FLAT, ENTRY_CAST, 1u << 17, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=512 lds=16 spill=0 wait=8) sort n=3"},
-	{"incoherent 2^22", AUTO, FLAT, ENTRY_CAST, 1u << 22, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3"},
-	{"incoherent 2^24", AUTO, FLAT, ENTRY_CAST, 1u << 24, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3"},
-	{"FORCE_SORT 1", AUTO, FLAT, ENTRY_CAST, 1, FORCE, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3"},
-	{"TOKEN_OUT 100000", AUTO, FLAT, ENTRY_CAST, 100000, TOKEN, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=391 lds=16 spill=0 wait=8) sort n=3"},
-	{"BOOL_OUT 10", AUTO, FLAT, ENTRY_CAST, 10, BOOL, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"ASYNC 65536", AUTO, FLAT, ENTRY_CAST, 65536, ASYNC, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=16 spill=0 wait=8) sort n=3"},
-	{"no 8-wide 65536", AUTO, NO8, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l4p map=lin q=0 lane(l4p pers blocks=256 lds=16 spill=0 wait=16) sort n=3"},
-	{"2-wide only 65536", AUTO, BARE, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=256 lds=16 spill=4 wait=16) sort n=3"},
-	{"stack_override 8", with(AUTO, &Opt::stack_override, 8), FLAT, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=8 spill=2 wait=8) sort n=3"},
-	{"stack_override 32", with(AUTO, &Opt::stack_override, 32), FLAT, ENTRY_CAST, 1u << 22, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=1280 lds=32 spill=0 wait=8) sort n=3"},
-	{"pipelined chunk 2^20", AUTO, FLAT, ENTRY_CHUNK, 1u << 20, MRT_FLAG_RAYS_ON_DEVICE | MRT_FLAG_HITS_ON_DEVICE, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3"},
+	{"incoherent 1", AUTO, FLAT, ENTRY_CAST, 1, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 1x256 lds=24576"},
+	{"incoherent 63", AUTO, FLAT, ENTRY_CAST, 63, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 16x256 lds=24576"},
+	{"incoherent 255", AUTO, FLAT, ENTRY_CAST, 255, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 64x256 lds=24576"},
+	{"incoherent 256", AUTO, FLAT, ENTRY_CAST, 256, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 64x256 lds=24576"},
+	{"incoherent 8192", AUTO, FLAT, ENTRY_CAST, 8192, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 2048x256 lds=24576"},
+	{"incoherent 8193", AUTO, FLAT, ENTRY_CAST, 8193, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=2) sort n=3",
+		"trace_lane_kernel<false, false> 1025x256 lds=24576"},
+	{"incoherent 2^15-1", AUTO, FLAT, ENTRY_CAST, 32767, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=4) sort n=3",
+		"trace_lane_kernel<false, false> 2048x256 lds=24576"},
+	{"incoherent 2^15", AUTO, FLAT, ENTRY_CAST, 32768, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=4) sort n=3",
+		"trace_lane_kernel<false, false> 2048x256 lds=24576"},
+	{"incoherent 2^15+1", AUTO, FLAT, ENTRY_CAST, 32769, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=0) sort n=3",
+		"trace_lane_kernel<false, false> 129x256 lds=24576"},
+	{"incoherent 65535", AUTO, FLAT, ENTRY_CAST, 65535, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=0) sort n=3",
+		"trace_lane_kernel<false, false> 256x256 lds=24576"},
+	{"incoherent 65536", AUTO, FLAT, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 256x256 lds=16384"},
+	{"incoherent 2^17", AUTO, FLAT, ENTRY_CAST, 1u << 17, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=512 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 512x256 lds=16384"},
+	{"incoherent 2^22", AUTO, FLAT, ENTRY_CAST, 1u << 22, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"incoherent 2^24", AUTO, FLAT, ENTRY_CAST, 1u << 24, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"FORCE_SORT 1", AUTO, FLAT, ENTRY_CAST, 1, FORCE, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3",
+		"trace_lane_kernel<false, false> 1x256 lds=24576"},
+	{"TOKEN_OUT 100000", AUTO, FLAT, ENTRY_CAST, 100000, TOKEN, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=391 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 391x256 lds=16384"},
+	{"BOOL_OUT 10", AUTO, FLAT, ENTRY_CAST, 10, BOOL, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 3x256 lds=24576"},
+	{"ASYNC 65536", AUTO, FLAT, ENTRY_CAST, 65536, ASYNC, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 256x256 lds=16384"},
+	{"no 8-wide 65536", AUTO, NO8, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l4p map=lin q=0 lane(l4p pers blocks=256 lds=16 spill=0 wait=16) sort n=3",
+		"trace_lane_persistent_kernel<false, 4, false, false> 256x256 lds=16384"},
+	{"2-wide only 65536", AUTO, BARE, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=256 lds=16 spill=4 wait=16) sort n=3",
+		"trace_lane_persistent_kernel<false, 2, false, false> 256x256 lds=16384"},
+	{"stack_override 8", with(AUTO, &Opt::stack_override, 8), FLAT, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=256 lds=8 spill=2 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 256x256 lds=8192"},
+	{"stack_override 32", with(AUTO, &Opt::stack_override, 32), FLAT, ENTRY_CAST, 1u << 22, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=1280 lds=32 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 1280x256 lds=32768"},
+	{"pipelined chunk 2^20", AUTO, FLAT, ENTRY_CHUNK, 1u << 20, MRT_FLAG_RAYS_ON_DEVICE | MRT_FLAG_HITS_ON_DEVICE, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=2048 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
 	// ---- declared coherent: the width is looked for on the device from 256 rays; packets with the lane launch queued behind
-	{"coherent 63", AUTO, FLAT, ENTRY_CAST, 63, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"coherent 64", AUTO, FLAT, ENTRY_CAST, 64, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"coherent 255", AUTO, FLAT, ENTRY_CAST, 255, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"coherent 256", AUTO, FLAT, ENTRY_CAST, 256, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2"},
-	{"coherent 2^15", AUTO, FLAT, ENTRY_CAST, 32768, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=4) detect n=2"},
-	{"coherent 2^15+1", AUTO, FLAT, ENTRY_CAST, 32769, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(lane sparse=0) detect n=2"},
-	{"coherent 65535", AUTO, FLAT, ENTRY_CAST, 65535, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(lane sparse=0) detect n=2"},
-	{"coherent 65536", AUTO, FLAT, ENTRY_CAST, 65536, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(l8p pers blocks=256 lds=16 spill=0 wait=8) detect n=2"},
-	{"coherent 3600 tiles of rays", AUTO, FLAT, ENTRY_CAST, 230400, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
-	{"coherent 3600 tiles + 1 ray", AUTO, FLAT, ENTRY_CAST, 230401, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=901 lds=16 spill=0 wait=8) detect n=2"},
-	{"coherent 2^19", AUTO, FLAT, ENTRY_CAST, 1u << 19, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
-	{"coherent 2^22-1", AUTO, FLAT, ENTRY_CAST, (1u << 22) - 1, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
-	{"coherent 2^22", AUTO, FLAT, ENTRY_CAST, 1u << 22, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
-	{"coherent 2^22+1", AUTO, FLAT, ENTRY_CAST, (1u << 22) + 1, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
-	{"coherent 2^24", AUTO, FLAT, ENTRY_CAST, 1u << 24, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
-	{"coherent + FORCE_SORT 300", AUTO, FLAT, ENTRY_CAST, 300, COH | FORCE, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2"},
-	{"coherent HOST_LAYOUT 1024", AUTO, FLAT, ENTRY_CAST, 1024, COH | HOST, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2"},
-	{"coherent submit 4096", AUTO, FLAT, ENTRY_SUBMIT, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2"},
-	{"coherent grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"coherent count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0 cnt) detect n=2 cnt"},
-	{"coherent tile_w_log2 2", with(AUTO, &Opt::tile_w_log2, 2), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2"},
-	{"coherent 2^22 no rows", AUTO, BARE, ENTRY_CAST, 1u << 22, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(lp pers blocks=2048 lds=16 spill=4 wait=16) detect n=2"},
-	{"coherent 4096 past kAsmNodeLimit", AUTO, BIG, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2"},
-	{"coherent 65536 past kAsmNodeLimit", AUTO, BIG, ENTRY_CAST, 65536, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=256 lds=16 spill=0 wait=8) detect n=2"},
+	{"coherent 63", AUTO, FLAT, ENTRY_CAST, 63, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 16x256 lds=24576"},
+	{"coherent 64", AUTO, FLAT, ENTRY_CAST, 64, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 16x256 lds=24576"},
+	{"coherent 255", AUTO, FLAT, ENTRY_CAST, 255, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 64x256 lds=24576"},
+	{"coherent 256", AUTO, FLAT, ENTRY_CAST, 256, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 16x256 lds=0 | trace_lane_kernel<false, false> 64x256 lds=24576"},
+	{"coherent 2^15", AUTO, FLAT, ENTRY_CAST, 32768, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=4) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0 | trace_lane_kernel<false, false> 2048x256 lds=24576"},
+	{"coherent 2^15+1", AUTO, FLAT, ENTRY_CAST, 32769, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(lane sparse=0) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 513x256 lds=0 | trace_lane_kernel<false, false> 129x256 lds=24576"},
+	{"coherent 65535", AUTO, FLAT, ENTRY_CAST, 65535, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(lane sparse=0) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 1024x256 lds=0 | trace_lane_kernel<false, false> 256x256 lds=24576"},
+	{"coherent 65536", AUTO, FLAT, ENTRY_CAST, 65536, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(l8p pers blocks=256 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 1024x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 256x256 lds=16384"},
+	{"coherent 3600 tiles of rays", AUTO, FLAT, ENTRY_CAST, 230400, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false> 3600x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 900x256 lds=16384"},
+	{"coherent 3600 tiles + 1 ray", AUTO, FLAT, ENTRY_CAST, 230401, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=901 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 901x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 901x256 lds=16384"},
+	{"coherent 2^19", AUTO, FLAT, ENTRY_CAST, 1u << 19, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"coherent 2^22-1", AUTO, FLAT, ENTRY_CAST, (1u << 22) - 1, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false> 16384x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"coherent 2^22", AUTO, FLAT, ENTRY_CAST, 1u << 22, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_rows_kernel<false, false, 2, 64, false> 32768x64 lds=0 group=2 | trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"coherent 2^22+1", AUTO, FLAT, ENTRY_CAST, (1u << 22) + 1, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_rows_kernel<false, false, 2, 64, false> 32769x64 lds=0 group=2 | trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"coherent 2^24", AUTO, FLAT, ENTRY_CAST, 1u << 24, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_rows_kernel<false, false, 2, 64, false> 131072x64 lds=0 group=2 | trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"coherent + FORCE_SORT 300", AUTO, FLAT, ENTRY_CAST, 300, COH | FORCE, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 19x256 lds=0 | trace_lane_kernel<false, false> 75x256 lds=24576"},
+	{"coherent HOST_LAYOUT 1024", AUTO, FLAT, ENTRY_CAST, 1024, COH | HOST, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 64x256 lds=0 | trace_lane_kernel<false, false> 256x256 lds=24576"},
+	{"coherent submit 4096", AUTO, FLAT, ENTRY_SUBMIT, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=2 dual(lane sparse=1) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 256x256 lds=0 | trace_lane_kernel<false, false> 1024x256 lds=24576"},
+	{"coherent grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 1024x256 lds=24576"},
+	{"coherent count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0 cnt) detect n=2 cnt",
+		"trace_lane_kernel<false, true> 16x256 lds=24576"},
+	{"coherent tile_w_log2 2", with(AUTO, &Opt::tile_w_log2, 2), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2",
+		"trace_lane_kernel<false, false> 16x256 lds=24576"},
+	{"coherent 2^22 no rows", AUTO, BARE, ENTRY_CAST, 1u << 22, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(lp pers blocks=2048 lds=16 spill=4 wait=16) detect n=2",
+		"trace_packet_asm_kernel<false, false> 16384x256 lds=0 | trace_lane_persistent_kernel<false, 2, false, false> 2048x256 lds=16384"},
+	{"coherent 4096 past kAsmNodeLimit", AUTO, BIG, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2",
+		"trace_lane_kernel<false, false> 16x256 lds=24576"},
+	{"coherent 65536 past kAsmNodeLimit", AUTO, BIG, ENTRY_CAST, 65536, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 dual(l8p pers blocks=256 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_kernel<false, false> 256x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 256x256 lds=16384"},
 	// ---- two-level scenes
-	{"two-level incoherent 1", AUTO, TL, ENTRY_CAST, 1, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=1) n=1"},
-	{"two-level incoherent 65536", AUTO, TL, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tlp8 map=lin q=0 lane(tlp8 pers blocks=256 lds=16 spill=0 wait=8) sort n=3"},
-	{"two-level no 8-wide 65536", AUTO, TL_NO8, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tlp map=lin q=0 lane(tlp pers blocks=256 lds=16 spill=14 wait=16) sort n=3"},
-	{"two-level count_visits 65536", with(AUTO, &Opt::count_visits, 1), TL, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=0 cnt) sort n=3 cnt"},
-	{"two-level coherent 4096", AUTO, TL, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=2 dual(tl sparse=1) detect n=2"},
-	{"two-level coherent 2^17", AUTO, TL, ENTRY_CAST, 1u << 17, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=1 dual(tlp8 pers blocks=512 lds=16 spill=0 wait=8) detect n=2"},
-	{"two-level coherent 2^19", AUTO, TL, ENTRY_CAST, 1u << 19, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=0 dual(tlp8 pers blocks=2048 lds=16 spill=0 wait=8) detect n=2"},
+	{"two-level incoherent 1", AUTO, TL, ENTRY_CAST, 1, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=1) n=1",
+		"trace_two_level_kernel<false> 1x256 lds=32768"},
+	{"two-level incoherent 65536", AUTO, TL, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tlp8 map=lin q=0 lane(tlp8 pers blocks=256 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, true, false> 256x256 lds=16384"},
+	{"two-level no 8-wide 65536", AUTO, TL_NO8, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tlp map=lin q=0 lane(tlp pers blocks=256 lds=16 spill=14 wait=16) sort n=3",
+		"trace_lane_persistent_kernel<false, 2, true, false> 256x256 lds=16384"},
+	{"two-level count_visits 65536", with(AUTO, &Opt::count_visits, 1), TL, ENTRY_CAST, 65536, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=0 cnt) sort n=3 cnt",
+		"trace_two_level_kernel<false> 256x256 lds=32768"},
+	{"two-level coherent 4096", AUTO, TL, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=2 dual(tl sparse=1) detect n=2",
+		"trace_two_level_packet_kernel<false> 256x256 lds=0 | trace_two_level_kernel<false> 1024x256 lds=32768"},
+	{"two-level coherent 2^17", AUTO, TL, ENTRY_CAST, 1u << 17, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=1 dual(tlp8 pers blocks=512 lds=16 spill=0 wait=8) detect n=2",
+		"trace_two_level_packet_kernel<false> 2048x256 lds=0 | trace_lane_persistent_kernel<false, 8, true, false> 512x256 lds=16384"},
+	{"two-level coherent 2^19", AUTO, TL, ENTRY_CAST, 1u << 19, COH, 0, 0, 0, 0, NONE, "k=tlpkt map=auto q=0 dual(tlp8 pers blocks=2048 lds=16 spill=0 wait=8) detect n=2",
+		"trace_two_level_packet_kernel<false> 2048x256 lds=0 | trace_lane_persistent_kernel<false, 8, true, false> 2048x256 lds=16384"},
 	// ---- explicit kernels
-	{"ASM coherent", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2"},
-	{"ASM incoherent", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_CAST, 4096, 0, 0, 0, 0, 0, NONE, "k=asm map=lin q=0 plain sort n=3"},
-	{"LANE 255", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 255, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1"},
-	{"LANE 256", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 256, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3"},
-	{"LANE coherent", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2"},
-	{"LANE_PERSISTENT incoherent", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=4 lds=16 spill=4 wait=16) sort n=3"},
-	{"LANE_PERSISTENT coherent", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_CAST, 1000, COH, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=4 lds=16 spill=4 wait=16) n=1"},
-	{"LANE4_PERSISTENT", kernel(MRT_KERNEL_LANE4_PERSISTENT), FLAT, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=l4p map=lin q=0 lane(l4p pers blocks=1 lds=16 spill=0 wait=16) n=1"},
-	{"LANE8_PERSISTENT", kernel(MRT_KERNEL_LANE8_PERSISTENT), FLAT, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=1 lds=16 spill=0 wait=8) n=1"},
-	{"LANE8_PERSISTENT without 8-wide", kernel(MRT_KERNEL_LANE8_PERSISTENT), BARE, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=1 lds=16 spill=4 wait=16) n=1"},
-	{"PACKET_DUAL coherent", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 plain detect n=2"},
-	{"PACKET_DUAL coherent no rows", kernel(MRT_KERNEL_PACKET_DUAL), NO_ROWS, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2"},
-	{"PACKET_DUAL incoherent", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_CAST, 4096, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3"},
-	{"PACKET_ROWS coherent", kernel(MRT_KERNEL_PACKET_ROWS), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=rows map=auto q=0 plain detect n=2"},
-	{"PACKET_QUAD coherent no 4-wide rows", kernel(MRT_KERNEL_PACKET_QUAD), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2"},
-	{"LANE two-level coherent", kernel(MRT_KERNEL_LANE), TL, ENTRY_CAST, 1u << 17, COH, 0, 0, 0, 0, NONE, "k=tl map=auto q=0 lane(tl sparse=0) detect n=2"},
-	{"LANE_PERSISTENT two-level", kernel(MRT_KERNEL_LANE_PERSISTENT), TL, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=1) sort n=3"},
-	{"LANE8_PERSISTENT two-level", kernel(MRT_KERNEL_LANE8_PERSISTENT), TL, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=tlp8 map=lin q=0 lane(tlp8 pers blocks=4 lds=16 spill=0 wait=8) sort n=3"},
+	{"ASM coherent", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 16x256 lds=0"},
+	{"ASM incoherent", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_CAST, 4096, 0, 0, 0, 0, 0, NONE, "k=asm map=lin q=0 plain sort n=3",
+		"trace_packet_asm_kernel<false, false, true> 16x256 lds=0"},
+	{"LANE 255", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 255, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) n=1",
+		"trace_lane_kernel<false, false> 64x256 lds=24576"},
+	{"LANE 256", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 256, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3",
+		"trace_lane_kernel<false, false> 64x256 lds=24576"},
+	{"LANE coherent", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=lane map=auto q=0 lane(lane sparse=0) detect n=2",
+		"trace_lane_kernel<false, false> 16x256 lds=24576"},
+	{"LANE_PERSISTENT incoherent", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=4 lds=16 spill=4 wait=16) sort n=3",
+		"trace_lane_persistent_kernel<false, 2, false, false> 4x256 lds=16384"},
+	{"LANE_PERSISTENT coherent", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_CAST, 1000, COH, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=4 lds=16 spill=4 wait=16) n=1",
+		"trace_lane_persistent_kernel<false, 2, false, false> 4x256 lds=16384"},
+	{"LANE4_PERSISTENT", kernel(MRT_KERNEL_LANE4_PERSISTENT), FLAT, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=l4p map=lin q=0 lane(l4p pers blocks=1 lds=16 spill=0 wait=16) n=1",
+		"trace_lane_persistent_kernel<false, 4, false, false> 1x256 lds=16384"},
+	{"LANE8_PERSISTENT", kernel(MRT_KERNEL_LANE8_PERSISTENT), FLAT, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=l8p map=lin q=0 lane(l8p pers blocks=1 lds=16 spill=0 wait=8) n=1",
+		"trace_lane_persistent_kernel<false, 8, false, false> 1x256 lds=16384"},
+	{"LANE8_PERSISTENT without 8-wide", kernel(MRT_KERNEL_LANE8_PERSISTENT), BARE, ENTRY_CAST, 100, 0, 0, 0, 0, 0, NONE, "k=lp map=lin q=0 lane(lp pers blocks=1 lds=16 spill=4 wait=16) n=1",
+		"trace_lane_persistent_kernel<false, 2, false, false> 1x256 lds=16384"},
+	{"PACKET_DUAL coherent", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=dual map=auto q=0 plain detect n=2",
+		"trace_packet_rows_kernel<false, false, 2, 64, false> 32x64 lds=0 group=2"},
+	{"PACKET_DUAL coherent no rows", kernel(MRT_KERNEL_PACKET_DUAL), NO_ROWS, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 16x256 lds=0"},
+	{"PACKET_DUAL incoherent", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_CAST, 4096, 0, 0, 0, 0, 0, NONE, "k=lane map=lin q=0 lane(lane sparse=1) sort n=3",
+		"trace_lane_kernel<false, false> 1024x256 lds=24576"},
+	{"PACKET_ROWS coherent", kernel(MRT_KERNEL_PACKET_ROWS), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=rows map=auto q=0 plain detect n=2",
+		"trace_packet_rows_kernel<false, false, 1, 256, false> 16x256 lds=0 group=4"},
+	{"PACKET_QUAD coherent no 4-wide rows", kernel(MRT_KERNEL_PACKET_QUAD), FLAT, ENTRY_CAST, 4096, COH, 0, 0, 0, 0, NONE, "k=asm map=auto q=0 plain detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 16x256 lds=0"},
+	{"LANE two-level coherent", kernel(MRT_KERNEL_LANE), TL, ENTRY_CAST, 1u << 17, COH, 0, 0, 0, 0, NONE, "k=tl map=auto q=0 lane(tl sparse=0) detect n=2",
+		"trace_two_level_kernel<false> 512x256 lds=32768"},
+	{"LANE_PERSISTENT two-level", kernel(MRT_KERNEL_LANE_PERSISTENT), TL, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=tl map=lin q=0 lane(tl sparse=1) sort n=3",
+		"trace_two_level_kernel<false> 250x256 lds=32768"},
+	{"LANE8_PERSISTENT two-level", kernel(MRT_KERNEL_LANE8_PERSISTENT), TL, ENTRY_CAST, 1000, 0, 0, 0, 0, 0, NONE, "k=tlp8 map=lin q=0 lane(tlp8 pers blocks=4 lds=16 spill=0 wait=8) sort n=3",
+		"trace_lane_persistent_kernel<false, 8, true, false> 4x256 lds=16384"},
 	// ---- the width found by the previous cast of as many rays: a tile schedule (and the tuner) as for a grid of that width
-	{"prev detect 640x360", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect sched=640x360/80+pieces n=2"},
-	{"prev detect other count", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, OTHER_COUNT, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
-	{"prev detect incoherent", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, INCOHERENT, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
-	{"prev detect pending", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, PENDING, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
-	{"prev detect no width", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, NO_WIDTH, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2"},
-	{"prev detect 512x256 (all in quarters)", AUTO, FLAT, ENTRY_CAST, 131072, COH, 512, 256, 0, 0, SAME, "k=asm map=auto q=1 dual(l8p pers blocks=512 lds=16 spill=0 wait=8) detect n=2"},
-	{"prev detect 1280x960", AUTO, FLAT, ENTRY_CAST, 1228800, COH, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces arms n=2"},
-	{"prev detect 1280x960 submit", AUTO, FLAT, ENTRY_SUBMIT, 1228800, COH, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces n=2"},
-	{"prev detect 1280x960 ASYNC", AUTO, FLAT, ENTRY_CAST, 1228800, COH | ASYNC, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces n=2"},
-	{"prev detect count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, SAME, "k=asm map=auto q=0 plain detect n=2 cnt"},
+	{"prev detect 640x360", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect sched=640x360/80+pieces n=2",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 900x256 lds=16384"},
+	{"prev detect other count", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, OTHER_COUNT, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false> 3600x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 900x256 lds=16384"},
+	{"prev detect incoherent", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, INCOHERENT, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false> 3600x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 900x256 lds=16384"},
+	{"prev detect pending", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, PENDING, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false> 3600x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 900x256 lds=16384"},
+	{"prev detect no width", AUTO, FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, NO_WIDTH, "k=asm map=auto q=1 dual(l8p pers blocks=900 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false> 3600x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 900x256 lds=16384"},
+	{"prev detect 512x256 (all in quarters)", AUTO, FLAT, ENTRY_CAST, 131072, COH, 512, 256, 0, 0, SAME, "k=asm map=auto q=1 dual(l8p pers blocks=512 lds=16 spill=0 wait=8) detect n=2",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 512x256 lds=16384"},
+	{"prev detect 1280x960", AUTO, FLAT, ENTRY_CAST, 1228800, COH, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces arms n=2",
+		"trace_packet_asm_kernel<false, false> 7200x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"prev detect 1280x960 submit", AUTO, FLAT, ENTRY_SUBMIT, 1228800, COH, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces n=2",
+		"trace_packet_asm_kernel<false, false> 7200x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"prev detect 1280x960 ASYNC", AUTO, FLAT, ENTRY_CAST, 1228800, COH | ASYNC, 1280, 960, 0, 0, SAME, "k=asm map=auto q=0 dual(l8p pers blocks=2048 lds=16 spill=0 wait=8) detect sched=1280x960/160+pieces n=2",
+		"trace_packet_asm_kernel<false, false> 7200x256 lds=0 | trace_lane_persistent_kernel<false, 8, false, false> 2048x256 lds=16384"},
+	{"prev detect count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_CAST, 230400, COH, 640, 360, 0, 0, SAME, "k=asm map=auto q=0 plain detect n=2 cnt",
+		"trace_packet_asm_kernel<false, true> 900x256 lds=0"},
 	// ---- grids of known width (mrt_cast_grid): quarter / sixteenth tiles up to 3 600 / 512 tiles, the schedule from 2^17 rays
-	{"grid 7x5", AUTO, FLAT, ENTRY_GRID, 0, 0, 7, 5, 0, 5, NONE, "k=lane map=tile q=0 plain n=1"},
-	{"grid 8x8", AUTO, FLAT, ENTRY_GRID, 0, 0, 8, 8, 0, 8, NONE, "k=asm map=tile q=2 plain n=1"},
-	{"grid 16x12", AUTO, FLAT, ENTRY_GRID, 0, 0, 16, 12, 0, 12, NONE, "k=asm map=tile q=2 plain n=1"},
-	{"grid 184x176 (506 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 184, 176, 0, 176, NONE, "k=asm map=tile q=2 plain n=1"},
-	{"grid 192x176 (528 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 192, 176, 0, 176, NONE, "k=asm map=tile q=1 plain n=1"},
-	{"grid 512x255", AUTO, FLAT, ENTRY_GRID, 0, 0, 512, 255, 0, 255, NONE, "k=asm map=tile q=1 plain n=1"},
-	{"grid 512x256 (2^17, all in quarters)", AUTO, FLAT, ENTRY_GRID, 0, 0, 512, 256, 0, 256, NONE, "k=asm map=tile q=1 plain n=1"},
-	{"grid 640x360 (3600 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=640x360/80+pieces n=1"},
-	{"grid 648x360 (3645 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1"},
-	{"grid 1280x960", AUTO, FLAT, ENTRY_GRID, 0, 0, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain sched=1280x960/160+pieces arms n=1"},
-	{"grid 1280x960 ASYNC", AUTO, FLAT, ENTRY_GRID, 0, ASYNC, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain sched=1280x960/160+pieces n=0"},
-	{"grid row block 1280x[100,300)", AUTO, FLAT, ENTRY_GRID, 0, 0, 1280, 960, 100, 200, NONE, "k=asm map=tile q=0 plain sched=1280x200/160+pieces n=1"},
-	{"grid 2048x2048 (2^22)", AUTO, FLAT, ENTRY_GRID, 0, 0, 2048, 2048, 0, 2048, NONE, "k=dual map=tile q=0 plain sched=2048x2048/256+pieces n=1"},
-	{"grid 4096x4096 (2^24)", AUTO, FLAT, ENTRY_GRID, 0, 0, 4096, 4096, 0, 4096, NONE, "k=dual map=tile q=0 plain n=1"},
-	{"grid grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=lin q=0 plain n=1"},
-	{"grid tile_schedule 1", with(AUTO, &Opt::tile_schedule, 1), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1"},
-	{"grid tile_schedule 2", with(AUTO, &Opt::tile_schedule, 2), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81 n=1"},
-	{"grid count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1 cnt"},
-	{"grid count_visits 64x64", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=lane map=tile q=0 plain n=1 cnt"},
-	{"grid tile_w_log2 4", with(AUTO, &Opt::tile_w_log2, 4), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/41 n=1"},
-	{"grid past kAsmNodeLimit", AUTO, BIG, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=640x360/80+pieces n=1"},
-	{"grid two-level 64x64", AUTO, TL, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=tlpkt map=tile q=2 plain n=1"},
-	{"grid two-level 1280x960", AUTO, TL, ENTRY_GRID, 0, 0, 1280, 960, 0, 960, NONE, "k=tlpkt map=tile q=0 plain n=1"},
-	{"grid ASM 648x360", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1"},
-	{"grid ASM 64x64", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=asm map=tile q=0 plain n=1"},
-	{"grid PACKET_DUAL 648x360", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=dual map=tile q=0 plain sched=648x360/81+pieces n=1"},
-	{"grid PACKET_DUAL no rows", kernel(MRT_KERNEL_PACKET_DUAL), NO_ROWS, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1"},
-	{"grid LANE 648x360", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=lane map=tile q=0 plain n=1"},
-	{"grid LANE_PERSISTENT 648x360", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=lp map=tile q=0 plain n=1"},
+	{"grid 7x5", AUTO, FLAT, ENTRY_GRID, 0, 0, 7, 5, 0, 5, NONE, "k=lane map=tile q=0 plain n=1",
+		"trace_lane_kernel<false, false> 1x256 lds=24576"},
+	{"grid 8x8", AUTO, FLAT, ENTRY_GRID, 0, 0, 8, 8, 0, 8, NONE, "k=asm map=tile q=2 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 4x256 lds=0"},
+	{"grid 16x12", AUTO, FLAT, ENTRY_GRID, 0, 0, 16, 12, 0, 12, NONE, "k=asm map=tile q=2 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 16x256 lds=0"},
+	{"grid 184x176 (506 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 184, 176, 0, 176, NONE, "k=asm map=tile q=2 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 2024x256 lds=0"},
+	{"grid 192x176 (528 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 192, 176, 0, 176, NONE, "k=asm map=tile q=1 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 528x256 lds=0"},
+	{"grid 512x255", AUTO, FLAT, ENTRY_GRID, 0, 0, 512, 255, 0, 255, NONE, "k=asm map=tile q=1 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0"},
+	{"grid 512x256 (2^17, all in quarters)", AUTO, FLAT, ENTRY_GRID, 0, 0, 512, 256, 0, 256, NONE, "k=asm map=tile q=1 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0"},
+	{"grid 640x360 (3600 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=640x360/80+pieces n=1",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0"},
+	{"grid 648x360 (3645 tiles)", AUTO, FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0"},
+	{"grid 1280x960", AUTO, FLAT, ENTRY_GRID, 0, 0, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain sched=1280x960/160+pieces arms n=1",
+		"trace_packet_asm_kernel<false, false> 7200x256 lds=0"},
+	{"grid 1280x960 ASYNC", AUTO, FLAT, ENTRY_GRID, 0, ASYNC, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain sched=1280x960/160+pieces n=0",
+		"trace_packet_asm_kernel<false, false> 7200x256 lds=0"},
+	{"grid row block 1280x[100,300)", AUTO, FLAT, ENTRY_GRID, 0, 0, 1280, 960, 100, 200, NONE, "k=asm map=tile q=0 plain sched=1280x200/160+pieces n=1",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0"},
+	{"grid 2048x2048 (2^22)", AUTO, FLAT, ENTRY_GRID, 0, 0, 2048, 2048, 0, 2048, NONE, "k=dual map=tile q=0 plain sched=2048x2048/256+pieces n=1",
+		"trace_packet_rows_kernel<false, false, 2, 64, true> 49152x64 lds=0 group=2"},
+	{"grid 4096x4096 (2^24)", AUTO, FLAT, ENTRY_GRID, 0, 0, 4096, 4096, 0, 4096, NONE, "k=dual map=tile q=0 plain n=1",
+		"trace_packet_rows_kernel<false, false, 2, 64, true> 131072x64 lds=0 group=2"},
+	{"grid grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=lin q=0 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 900x256 lds=0"},
+	{"grid tile_schedule 1", with(AUTO, &Opt::tile_schedule, 1), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 912x256 lds=0"},
+	{"grid tile_schedule 2", with(AUTO, &Opt::tile_schedule, 2), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81 n=1",
+		"trace_packet_asm_kernel<false, false, true> 912x256 lds=0"},
+	{"grid count_visits", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1 cnt",
+		"trace_packet_asm_kernel<false, true> 912x256 lds=0"},
+	{"grid count_visits 64x64", with(AUTO, &Opt::count_visits, 1), FLAT, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=lane map=tile q=0 plain n=1 cnt",
+		"trace_lane_kernel<false, true> 16x256 lds=24576"},
+	{"grid tile_w_log2 4", with(AUTO, &Opt::tile_w_log2, 4), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/41 n=1",
+		"trace_packet_asm_kernel<false, false, true> 923x256 lds=0"},
+	{"grid past kAsmNodeLimit", AUTO, BIG, ENTRY_GRID, 0, 0, 640, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=640x360/80+pieces n=1",
+		"trace_packet_kernel<false, false> 2048x256 lds=0"},
+	{"grid two-level 64x64", AUTO, TL, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=tlpkt map=tile q=2 plain n=1",
+		"trace_two_level_packet_kernel<false> 256x256 lds=0"},
+	{"grid two-level 1280x960", AUTO, TL, ENTRY_GRID, 0, 0, 1280, 960, 0, 960, NONE, "k=tlpkt map=tile q=0 plain n=1",
+		"trace_two_level_packet_kernel<false> 4800x256 lds=0"},
+	{"grid ASM 648x360", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0"},
+	{"grid ASM 64x64", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_GRID, 0, 0, 64, 64, 0, 64, NONE, "k=asm map=tile q=0 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 16x256 lds=0"},
+	{"grid PACKET_DUAL 648x360", kernel(MRT_KERNEL_PACKET_DUAL), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=dual map=tile q=0 plain sched=648x360/81+pieces n=1",
+		"trace_packet_rows_kernel<false, false, 2, 64, true> 8192x64 lds=0 group=2"},
+	{"grid PACKET_DUAL no rows", kernel(MRT_KERNEL_PACKET_DUAL), NO_ROWS, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain sched=648x360/81+pieces n=1",
+		"trace_packet_asm_kernel<false, false, true> 2048x256 lds=0"},
+	{"grid LANE 648x360", kernel(MRT_KERNEL_LANE), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=lane map=tile q=0 plain n=1",
+		"trace_lane_kernel<false, false> 912x256 lds=24576"},
+	{"grid LANE_PERSISTENT 648x360", kernel(MRT_KERNEL_LANE_PERSISTENT), FLAT, ENTRY_GRID, 0, 0, 648, 360, 0, 360, NONE, "k=lp map=tile q=0 plain n=1",
+		"trace_lane_kernel<false, false> 912x256 lds=24576"},
 	// ---- tiled casts (mrt_cast_tiled): the grid rules without schedule or tuner
-	{"tiled 64x64", AUTO, FLAT, ENTRY_TILED, 0, 0, 64, 64, 0, 64, NONE, "k=asm map=tile q=2 plain n=1"},
-	{"tiled 648x360", AUTO, FLAT, ENTRY_TILED, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1"},
-	{"tiled 1280x960", AUTO, FLAT, ENTRY_TILED, 0, 0, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain n=1"},
-	{"tiled 2048x2048", AUTO, FLAT, ENTRY_TILED, 0, 0, 2048, 2048, 0, 2048, NONE, "k=dual map=tile q=0 plain n=1"},
-	{"tiled grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_TILED, 0, 0, 64, 64, 0, 64, NONE, "k=lane map=lin q=0 plain n=1"},
+	{"tiled 64x64", AUTO, FLAT, ENTRY_TILED, 0, 0, 64, 64, 0, 64, NONE, "k=asm map=tile q=2 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 256x256 lds=0"},
+	{"tiled 648x360", AUTO, FLAT, ENTRY_TILED, 0, 0, 648, 360, 0, 360, NONE, "k=asm map=tile q=0 plain n=1",
+		"trace_packet_asm_kernel<false, false, true> 912x256 lds=0"},
+	{"tiled 1280x960", AUTO, FLAT, ENTRY_TILED, 0, 0, 1280, 960, 0, 960, NONE, "k=asm map=tile q=0 plain n=1",
+		"trace_packet_asm_kernel<false, false> 4800x256 lds=0"},
+	{"tiled 2048x2048", AUTO, FLAT, ENTRY_TILED, 0, 0, 2048, 2048, 0, 2048, NONE, "k=dual map=tile q=0 plain n=1",
+		"trace_packet_rows_kernel<false, false, 2, 64, false> 32768x64 lds=0 group=2"},
+	{"tiled grid_tile 1", with(AUTO, &Opt::grid_tile, 1), FLAT, ENTRY_TILED, 0, 0, 64, 64, 0, 64, NONE, "k=lane map=lin q=0 plain n=1",
+		"trace_lane_kernel<false, false> 16x256 lds=24576"},
 };
+
+// ---- what a plan runs ---------------------------------------------------------------------------------------------------------
+// <name> <workgroups>x<threads> lds=<bytes> [group=<tile_group>]; "nothing" for a launch without rays, "error" past 2^31 - 1 workgroups
+std::string describe(const TraceLaunch &l, const char *family = nullptr, int src = 0, bool with_mode = false)
+{
+	if (l.error) return "error";
+	if (l.blocks == 0) return "nothing";
+	char name[96], b[192];
+	format_variant(name, sizeof(name), l.v, family, src, with_mode);
+	int n = std::snprintf(b, sizeof(b), "%s %ux%u lds=%zu", name, l.blocks, l.threads, l.lds);
+	if (l.v.kernel == TraceKernel::PACKET_ROWS) std::snprintf(b + n, sizeof(b) - n, " group=%u", l.tile_group);
+	return b;
+}
+
+// The lanes a plain or packet launch must cover: a lane per ray and piece of a tile; a lane per ray where the width is found on the device
+uint64_t lanes_needed(const TraceParams &p)
+{
+	return p.lane_map == MAP_TILE8X8 ? p.count * (p.quarter_all == 2u ? 16u : (p.quarter_all ? 4u : 1u)) : p.count;
+}
+void covers(const std::string &name, const TraceParams &p, const TraceLaunch &l)
+{
+	if (l.error || l.v.kernel == TraceKernel::LANE_PERSISTENT) return; // (resident waves pull their rays from a counter)
+	expect((uint64_t)l.blocks * l.threads * l.packets_per_wave() >= lanes_needed(p), name + ": the launch covers the batch (" + describe(l) + ")");
+}
+
+const uint32_t kResidentWords[4] = {0, 0, 0, 0};
+template <class T> const T *resident() { return reinterpret_cast<const T *>(kResidentWords); } // an array the resolvers only test for null
+
+// TraceParams as api.hip base_params makes them for a scene that fits the Infinity Cache (64-thread workgroups for the 128-ray
+// walk, culling by where the rays come from)
+TraceParams scene_params(const SceneFacts &s, const mrt_options &o)
+{
+	TraceParams p;
+	std::memset(&p, 0, sizeof(p));
+	if (s.rows) p.row_array = resident<void>();
+	if (s.rows4) p.row_array4 = resident<void>();
+	if (s.nodes4) p.nodes4 = resident<Dev4Node>();
+	if (s.nodes8) { p.nodes8 = resident<Dev8Node>(); p.leaf_box = resident<float>(); }
+	p.n_nodes = s.n_nodes; p.stack_depth = (s.depth + 7u) / 8u * 8u;
+	p.tile_w_log2 = tile_w_log2(o); p.rows_wg = 64u; p.rows_cull = 2u; p.kernel = MRT_KERNEL_LANE;
+	return p;
+}
+
+// What cast.hip launch_planned (with launch_lane, and schedule.hip schedule_grid once the grid has an order) puts on the stream
+// for a plan, closest hit: the packet launch, the lane launch, or "packet | lane" where both are queued
+std::string runs(const Case &t, const CastPlan &c)
+{
+	const mrt_options o = options(t.opt);
+	TraceParams p = scene_params(scene(t.scene), o);
+	if (ray_entry(t.entry)) { p.count = t.count; p.in_fmt = (t.flags & HOST) ? IN_HOST60 : IN_RAY32; }
+	else {
+		p.count = (uint64_t)t.w * t.rows; p.in_fmt = t.entry == ENTRY_GRID ? IN_GRID : IN_RAY32;
+		p.grid_w = t.w; p.grid_h = t.h; p.y0 = t.y0; p.rows = t.rows; p.tiles_x = c.tiles_x;
+	}
+	p.kernel = c.kernel; p.lane_map = c.lane_map; p.quarter_all = c.quarter_all;
+	if (c.scheduled) {
+		const uint32_t th = 64u >> p.tile_w_log2;
+		p.tile_unit = c.kernel == MRT_KERNEL_PACKET_DUAL ? 2u : 1u;
+		p.n_units = (uint32_t)(((uint64_t)c.tiles_x * ((c.rows + th - 1u) / th) + p.tile_unit - 1u) / p.tile_unit);
+		p.tile_sched = p.sched_hdr = resident<uint32_t>(); p.n_slots_max = schedule_slots(p.n_units, c.pieces);
+	}
+	const auto traced = [&](const TraceParams &q, const TraceLaunch &l) { covers(t.name, q, l); return describe(l); };
+	const auto lane = [&](TraceParams q) {
+		const LaneLaunch &l = c.lane;
+		q.kernel = l.kernel;
+		if (l.persistent) return describe(resolve_persistent(q, l.lds_depth, l.blocks, false, l.count));
+		q.sparse_lanes = l.sparse_lanes;
+		return traced(q, resolve_trace(q, false, l.count, false));
+	};
+	if (c.launch == CastPlan::LANE) return lane(p);
+	const std::string packet = traced(p, resolve_trace(p, false, c.count, false));
+	if (c.launch == CastPlan::PLAIN) return packet;
+	TraceParams lp = p;
+	lp.lane_map = MAP_LINEAR; lp.quarter_all = 0u;
+	return packet + " | " + lane(lp);
+}
 
 CastPlan plan(const Case &t, GridStates &gs, const Knobs &k = Knobs())
 {
@@ -253,7 +448,7 @@ CastPlan plan(const Case &t, GridStates &gs, const Knobs &k = Knobs())
 
 // A batch whose width is found on the device and scheduled from a consistent pair (the width of a cast of as many rays) gets a
 // launch of at least a lane per ray (launch_trace), and the prefetch rule counts at least a wave per 64 rays
-void covers(const Case &t, const CastPlan &c)
+void schedule_covers(const Case &t, const CastPlan &c)
 {
 	if (!c.scheduled || c.lane_map != MAP_AUTO) return;
 	const uint32_t tw = tile_w_log2(options(t.opt)), th = 64u >> tw, unit = c.kernel == MRT_KERNEL_PACKET_DUAL ? 2u : 1u;
@@ -270,7 +465,9 @@ void table()
 		const CastPlan c = plan(t, gs);
 		const std::string got = describe(c);
 		expect(got == t.want, std::string(t.name) + ": got \"" + got + "\", want \"" + t.want + "\"");
-		covers(t, c);
+		schedule_covers(t, c);
+		const std::string ran = runs(t, c);
+		expect(ran == t.runs, std::string(t.name) + ": runs \"" + ran + "\", want \"" + t.runs + "\"");
 	}
 	// the schedule's bound from the environment (MRT_SCHEDULE_MIN_LOG2 = 15) moves the tuner's with it
 	Knobs k; k.schedule_min_rays = k.tune_min_rays = 1ull << 15;
@@ -278,6 +475,226 @@ void table()
 	const Case t{"grid ASM 256x128 with the bound at 2^15", kernel(MRT_KERNEL_PACKET_ASM), FLAT, ENTRY_GRID, 0, 0, 256, 128, 0, 128, NONE, ""};
 	expect(describe(plan(t, gs, k)) == "k=asm map=tile q=0 plain sched=256x128/32+pieces n=1", "schedule bound 2^15: " + describe(plan(t, gs, k)));
 	expect(describe(plan(t, gs)) == "k=asm map=tile q=0 plain n=1", "schedule bound 2^17: " + describe(plan(t, gs)));
+}
+
+// ---- every branch of the resolvers, on TraceParams made by hand -------------------------------------------------------------------
+// a flat scene of 40 000 nodes with nothing but the 2-wide nodes resident; the setters add the rest
+struct P : TraceParams {
+	P(uint32_t k, uint32_t map, uint64_t n)
+	{
+		std::memset(static_cast<TraceParams *>(this), 0, sizeof(TraceParams));
+		kernel = k; lane_map = map; count = n; in_fmt = IN_RAY32;
+		n_nodes = 40000; stack_depth = 24; tile_w_log2 = 3; rows_wg = 64; rows_cull = 2;
+	}
+	P &with_rows() { row_array = resident<void>(); return *this; }
+	P &with_rows4() { row_array4 = resident<void>(); return *this; }
+	P &with_nodes4() { nodes4 = resident<Dev4Node>(); return *this; }
+	P &with_nodes8(bool boxes = true) { nodes8 = resident<Dev8Node>(); if (boxes) leaf_box = resident<float>(); return *this; }
+	P &grid(uint32_t w, uint32_t r) { grid_w = w; grid_h = rows = r; tiles_x = (w + 7u) / 8u; count = (uint64_t)w * r; in_fmt = IN_GRID; return *this; }
+	P &from(uint32_t fmt) { in_fmt = fmt; return *this; }
+	P &wg(uint32_t w) { rows_wg = w; return *this; }
+	P &cull(uint32_t c) { rows_cull = c; return *this; }
+	P &quarter(uint32_t q) { quarter_all = q; return *this; }
+	P &sparse(uint32_t l) { sparse_lanes = l; return *this; }
+	P &nodes(uint32_t n) { n_nodes = n; return *this; }
+	P &lds(uint32_t bytes) { extra_lds = bytes; return *this; }
+	// a tile schedule with an order (schedule.hip schedule_grid); hdr = false: the list without its header
+	P &sched(uint32_t units, uint32_t unit, bool pieces, bool hdr = true)
+	{
+		tile_sched = resident<uint32_t>(); sched_hdr = hdr ? resident<uint32_t>() : nullptr;
+		tile_unit = unit; n_units = units; n_slots_max = schedule_slots(units, pieces);
+		return *this;
+	}
+};
+constexpr uint32_t LIN = MAP_LINEAR, TILE = MAP_TILE8X8, FOUND = MAP_AUTO;
+constexpr uint32_t K_LANE = MRT_KERNEL_LANE, K_PKT = MRT_KERNEL_PACKET, K_ASM = MRT_KERNEL_PACKET_ASM, K_ROWS = MRT_KERNEL_PACKET_ROWS,
+	K_DUAL = MRT_KERNEL_PACKET_DUAL, K_QUAD = MRT_KERNEL_PACKET_QUAD, K_LP = MRT_KERNEL_LANE_PERSISTENT, K_L4P = MRT_KERNEL_LANE4_PERSISTENT,
+	K_L8P = MRT_KERNEL_LANE8_PERSISTENT, K_TL = MRT_KERNEL_TWO_LEVEL, K_TLPKT = MRT_KERNEL_TWO_LEVEL_PACKET,
+	K_TLP = MRT_KERNEL_TWO_LEVEL_PERSISTENT, K_TLP8 = MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
+constexpr uint64_t kPrefetchRays = (uint64_t)kPrefetchMaxWaves * 64u; // 10 240 waves of rays
+constexpr uint64_t kMaxBlockRays = 0x7FFFFFFFull * 256u;
+
+struct Launch {
+	const char *name;
+	P p;
+	bool any_hit, count;
+	const char *want;
+	bool quad_built = false;
+};
+// launch_trace: closest hit without counters unless the row says otherwise
+const Launch kTrace[] = {
+	// ---- the rows kernels, and what takes their place without a row array
+	{"DUAL grid", P(K_DUAL, TILE, 0).with_rows().grid(64, 64), false, false, "trace_packet_rows_kernel<false, false, 2, 64, true> 32x64 lds=0 group=2"},
+	{"DUAL grid any-hit counting", P(K_DUAL, TILE, 0).with_rows().grid(64, 64), true, true, "trace_packet_rows_kernel<true, true, 2, 64, true> 32x64 lds=0 group=2"},
+	{"DUAL grid without rows", P(K_DUAL, TILE, 0).grid(64, 64), false, false, "trace_packet_asm_kernel<false, false, true> 16x256 lds=0"},
+	{"ROWS grid", P(K_ROWS, TILE, 0).with_rows().grid(64, 64), false, false, "trace_packet_rows_kernel<false, false, 1, 256, false> 16x256 lds=0 group=4"},
+	{"ROWS grid any-hit", P(K_ROWS, TILE, 0).with_rows().grid(64, 64), true, false, "trace_packet_rows_kernel<true, false, 1, 256, false> 16x256 lds=0 group=4"},
+	{"ROWS grid without rows", P(K_ROWS, TILE, 0).grid(64, 64), false, true, "trace_packet_asm_kernel<false, true> 16x256 lds=0"},
+	{"DUAL workgroups of 256", P(K_DUAL, TILE, 0).with_rows().grid(64, 64).wg(256), false, false, "trace_packet_rows_kernel<false, false, 2, 256, true> 8x256 lds=0 group=8"},
+	{"DUAL workgroups of 256, 130x66", P(K_DUAL, TILE, 0).with_rows().grid(130, 66).wg(256), false, false, "trace_packet_rows_kernel<false, false, 2, 256, true> 20x256 lds=0 group=8"},
+	{"ROWS ignores rows_wg", P(K_ROWS, TILE, 0).with_rows().grid(64, 64).wg(64), false, false, "trace_packet_rows_kernel<false, false, 1, 256, false> 16x256 lds=0 group=4"},
+	{"DUAL cull 0 grid", P(K_DUAL, TILE, 0).with_rows().grid(64, 64).cull(0), false, false, "trace_packet_rows_kernel<false, false, 2, 64, false> 32x64 lds=0 group=2"},
+	{"DUAL cull 0 rays", P(K_DUAL, FOUND, 4096).with_rows().cull(0), false, false, "trace_packet_rows_kernel<false, false, 2, 64, false> 32x64 lds=0 group=2"},
+	{"DUAL cull 1 grid", P(K_DUAL, TILE, 0).with_rows().grid(64, 64).cull(1), false, false, "trace_packet_rows_kernel<false, false, 2, 64, true> 32x64 lds=0 group=2"},
+	{"DUAL cull 1 rays", P(K_DUAL, FOUND, 4096).with_rows().cull(1), false, false, "trace_packet_rows_kernel<false, false, 2, 64, true> 32x64 lds=0 group=2"},
+	{"DUAL cull 2 grid", P(K_DUAL, TILE, 0).with_rows().grid(64, 64).cull(2), false, false, "trace_packet_rows_kernel<false, false, 2, 64, true> 32x64 lds=0 group=2"},
+	{"DUAL cull 2 rays", P(K_DUAL, FOUND, 4096).with_rows().cull(2), false, false, "trace_packet_rows_kernel<false, false, 2, 64, false> 32x64 lds=0 group=2"},
+	{"DUAL cull 2 host rays", P(K_DUAL, FOUND, 4096).with_rows().cull(2).from(IN_HOST60), false, false, "trace_packet_rows_kernel<false, false, 2, 64, false> 32x64 lds=0 group=2"},
+	{"ROWS never culls", P(K_ROWS, TILE, 0).with_rows().grid(64, 64).cull(1), false, false, "trace_packet_rows_kernel<false, false, 1, 256, false> 16x256 lds=0 group=4"},
+	{"DUAL with rows past kAsmNodeLimit", P(K_DUAL, TILE, 0).with_rows().grid(64, 64).nodes(kAsmNodeLimit), false, false, "trace_packet_rows_kernel<false, false, 2, 64, true> 32x64 lds=0 group=2"},
+	// ---- the four-wide walk: only with its rows, only in a build that has it
+	{"QUAD", P(K_QUAD, TILE, 0).with_rows4().grid(64, 64), false, false, "trace_packet_quad_kernel<false, false> 8x256 lds=0", true},
+	{"QUAD any-hit counting", P(K_QUAD, TILE, 0).with_rows4().grid(130, 66), true, true, "trace_packet_quad_kernel<true, true> 20x256 lds=0", true},
+	{"QUAD not built", P(K_QUAD, TILE, 0).with_rows4().grid(64, 64), false, false, "trace_packet_asm_kernel<false, false, true> 16x256 lds=0", false},
+	{"QUAD without row_array4", P(K_QUAD, TILE, 0).with_rows().grid(64, 64), false, false, "trace_packet_asm_kernel<false, false, true> 16x256 lds=0", true},
+	{"QUAD without row_array4, not built", P(K_QUAD, TILE, 0).grid(64, 64), true, false, "trace_packet_asm_kernel<true, false, true> 16x256 lds=0", false},
+	{"QUAD not built past kAsmNodeLimit", P(K_QUAD, TILE, 0).with_rows4().grid(64, 64).nodes(kAsmNodeLimit), false, false, "trace_packet_kernel<false, false> 16x256 lds=0", false},
+	// ---- node offsets past the asm loop's 32 bits: the C++ packet kernel
+	{"ASM one node below kAsmNodeLimit", P(K_ASM, TILE, 0).grid(64, 64).nodes(kAsmNodeLimit - 1u), false, false, "trace_packet_asm_kernel<false, false, true> 16x256 lds=0"},
+	{"ASM at kAsmNodeLimit", P(K_ASM, TILE, 0).grid(64, 64).nodes(kAsmNodeLimit), false, false, "trace_packet_kernel<false, false> 16x256 lds=0"},
+	{"DUAL without rows at kAsmNodeLimit", P(K_DUAL, TILE, 0).grid(64, 64).nodes(kAsmNodeLimit), true, true, "trace_packet_kernel<true, true> 16x256 lds=0"},
+	{"ROWS without rows at kAsmNodeLimit", P(K_ROWS, TILE, 0).grid(64, 64).nodes(kAsmNodeLimit), false, true, "trace_packet_kernel<false, true> 16x256 lds=0"},
+	{"PACKET", P(K_PKT, TILE, 0).grid(64, 64), false, false, "trace_packet_kernel<false, false> 16x256 lds=0"},
+	{"PACKET any-hit counting", P(K_PKT, LIN, 4096), true, true, "trace_packet_kernel<true, true> 16x256 lds=0"},
+	// ---- the asm kernel's prefetch: up to kPrefetchMaxWaves waves, counted three ways; never when counting
+	{"ASM linear, kPrefetchMaxWaves", P(K_ASM, LIN, kPrefetchRays + 63u), false, false, "trace_packet_asm_kernel<false, false, true> 2561x256 lds=0"},
+	{"ASM linear, one wave more", P(K_ASM, LIN, kPrefetchRays + 64u), false, false, "trace_packet_asm_kernel<false, false> 2561x256 lds=0"},
+	{"ASM grid, kPrefetchMaxWaves tiles", P(K_ASM, TILE, 0).grid(1280, 512), true, false, "trace_packet_asm_kernel<true, false, true> 2560x256 lds=0"},
+	{"ASM grid, one column of tiles more", P(K_ASM, TILE, 0).grid(1288, 512), true, false, "trace_packet_asm_kernel<true, false> 2576x256 lds=0"},
+	{"ASM width found, kPrefetchMaxWaves", P(K_ASM, FOUND, kPrefetchRays), false, false, "trace_packet_asm_kernel<false, false, true> 2560x256 lds=0"},
+	{"ASM width found, one ray more", P(K_ASM, FOUND, kPrefetchRays + 1u), false, false, "trace_packet_asm_kernel<false, false> 2561x256 lds=0"},
+	{"ASM scheduled, kPrefetchMaxWaves units", P(K_ASM, TILE, 0).grid(1280, 512).sched(kPrefetchMaxWaves, 1, false), false, false, "trace_packet_asm_kernel<false, false, true> 2560x256 lds=0"},
+	{"ASM scheduled, one unit more", P(K_ASM, TILE, 0).grid(616, 1064).sched(kPrefetchMaxWaves + 1u, 1, false), false, false, "trace_packet_asm_kernel<false, false> 2561x256 lds=0"},
+	{"ASM scheduled in pieces, a round of slots", P(K_ASM, TILE, 0).grid(640, 360).sched(3600, 1, true), false, false, "trace_packet_asm_kernel<false, false, true> 2048x256 lds=0"},
+	{"ASM scheduled in pieces, units past a round", P(K_ASM, TILE, 0).grid(1280, 512).sched(kPrefetchMaxWaves, 1, true), false, false, "trace_packet_asm_kernel<false, false, true> 3840x256 lds=0"},
+	{"ASM scheduled, width found, kPrefetchMaxWaves", P(K_ASM, FOUND, kPrefetchRays).sched(kPrefetchMaxWaves, 1, false), false, false, "trace_packet_asm_kernel<false, false, true> 2560x256 lds=0"},
+	{"ASM scheduled, width found, one ray more", P(K_ASM, FOUND, kPrefetchRays + 1u).sched(kPrefetchMaxWaves, 1, false), false, false, "trace_packet_asm_kernel<false, false> 2561x256 lds=0"},
+	{"ASM counting", P(K_ASM, TILE, 0).grid(64, 64), false, true, "trace_packet_asm_kernel<false, true> 16x256 lds=0"},
+	{"ASM any-hit counting", P(K_ASM, TILE, 0).grid(64, 64), true, true, "trace_packet_asm_kernel<true, true> 16x256 lds=0"},
+	// ---- every tile in quarters or sixteenths
+	{"quarters, grid", P(K_ASM, TILE, 0).grid(64, 64).quarter(1), false, false, "trace_packet_asm_kernel<false, false, true> 64x256 lds=0"},
+	{"sixteenths, grid", P(K_ASM, TILE, 0).grid(64, 64).quarter(2), false, false, "trace_packet_asm_kernel<false, false, true> 256x256 lds=0"},
+	{"quarters, clipped grid", P(K_ASM, TILE, 0).grid(130, 66).quarter(1), false, false, "trace_packet_asm_kernel<false, false, true> 153x256 lds=0"},
+	{"quarters, width found", P(K_ASM, FOUND, 4096).quarter(1), false, false, "trace_packet_asm_kernel<false, false, true> 64x256 lds=0"},
+	{"sixteenths, width found", P(K_ASM, FOUND, 4096).quarter(2), false, false, "trace_packet_asm_kernel<false, false, true> 256x256 lds=0"},
+	{"sixteenths, two-level packets", P(K_TLPKT, TILE, 0).grid(64, 64).quarter(2), false, false, "trace_two_level_packet_kernel<false> 256x256 lds=0"},
+	{"quarters mean nothing to linear lanes", P(K_LANE, LIN, 4096).quarter(1), false, false, "trace_lane_kernel<false, false> 16x256 lds=24576"},
+	// ---- a small batch on emptier waves
+	{"sparse lanes 1", P(K_LANE, LIN, 1000).sparse(1), false, false, "trace_lane_kernel<false, false> 250x256 lds=24576"},
+	{"sparse lanes 2", P(K_LANE, LIN, 1000).sparse(2), false, false, "trace_lane_kernel<false, false> 125x256 lds=24576"},
+	{"sparse lanes 4", P(K_LANE, LIN, 1001).sparse(4), true, false, "trace_lane_kernel<true, false> 63x256 lds=24576"},
+	{"sparse lanes 4, two-level", P(K_TL, LIN, 1001).sparse(4), false, false, "trace_two_level_kernel<false> 63x256 lds=24576"},
+	{"sparse lanes mean nothing to tiles", P(K_LANE, TILE, 0).grid(64, 64).sparse(4), false, true, "trace_lane_kernel<false, true> 16x256 lds=24576"},
+	// ---- launches from a tile schedule: schedule_slots slots of tile_unit tiles
+	{"scheduled 640x360, whole units", P(K_ASM, TILE, 0).grid(640, 360).sched(3600, 1, false), false, false, "trace_packet_asm_kernel<false, false, true> 900x256 lds=0"},
+	{"scheduled 640x360, pieces", P(K_ASM, TILE, 0).grid(640, 360).sched(3600, 1, true), true, false, "trace_packet_asm_kernel<true, false, true> 2048x256 lds=0"},
+	{"scheduled 2048x2048 DUAL, whole units", P(K_DUAL, TILE, 0).with_rows().grid(2048, 2048).sched(32768, 2, false), false, false, "trace_packet_rows_kernel<false, false, 2, 64, true> 32768x64 lds=0 group=2"},
+	{"scheduled 2048x2048 DUAL, pieces", P(K_DUAL, TILE, 0).with_rows().grid(2048, 2048).sched(32768, 2, true), false, false, "trace_packet_rows_kernel<false, false, 2, 64, true> 49152x64 lds=0 group=2"},
+	{"a schedule without its header is not used", P(K_ASM, TILE, 0).grid(640, 360).sched(100, 1, false, false), false, false, "trace_packet_asm_kernel<false, false, true> 900x256 lds=0"},
+	{"scheduled from a narrower grid, width found", P(K_ASM, FOUND, 230400).sched(100, 1, false), false, false, "trace_packet_asm_kernel<false, false, true> 900x256 lds=0"},
+	{"scheduled from this grid, width found", P(K_DUAL, FOUND, 2048u * 2048u).with_rows().sched(32768, 2, true), false, false, "trace_packet_rows_kernel<false, false, 2, 64, false> 49152x64 lds=0 group=2"},
+	// ---- two-level scenes, the lane kernel
+	{"two-level packets", P(K_TLPKT, TILE, 0).grid(64, 64).lds(4096), true, true, "trace_two_level_packet_kernel<true> 16x256 lds=4096"},
+	{"two-level lanes", P(K_TL, FOUND, 4096), false, true, "trace_two_level_kernel<false> 16x256 lds=24576"},
+	{"lanes", P(K_LANE, LIN, 4097), false, false, "trace_lane_kernel<false, false> 17x256 lds=24576"},
+	{"lanes any-hit counting", P(K_LANE, FOUND, 4096), true, true, "trace_lane_kernel<true, true> 16x256 lds=24576"},
+	{"a persistent id launched plain", P(K_LP, TILE, 0).grid(64, 64), false, false, "trace_lane_kernel<false, false> 16x256 lds=24576"},
+	// ---- nothing to launch; too much to launch
+	{"no rays", P(K_LANE, LIN, 0), false, false, "nothing"},
+	{"no rows", P(K_ASM, TILE, 0).grid(64, 0), false, false, "nothing"},
+	{"2^31 - 1 workgroups", P(K_LANE, LIN, kMaxBlockRays), false, false, "trace_lane_kernel<false, false> 2147483647x256 lds=24576"},
+	{"2^31 workgroups", P(K_LANE, LIN, kMaxBlockRays + 1u), false, false, "error"},
+	{"2^31 - 1 workgroups of lanes, half the waves", P(K_DUAL, LIN, kMaxBlockRays).with_rows(), false, false, "trace_packet_rows_kernel<false, false, 2, 64, false> 4294967294x64 lds=0 group=2"},
+	{"2^31 workgroups of sparse lanes", P(K_LANE, LIN, 1ull << 33).sparse(1), false, false, "error"},
+	{"2^31 workgroups of sixteenths", P(K_ASM, FOUND, 1ull << 35).quarter(2), false, false, "error"},
+};
+
+// launch_trace_persistent (kPersistent) and launch_source (kSource: named as a hemisphere cast from a grid, the family with both modes)
+struct Resident {
+	const char *name;
+	P p;
+	uint32_t lds_depth, blocks;
+	bool any_hit, count;
+	const char *want;
+};
+const Resident kPersistent[] = {
+	{"LP", P(K_LP, LIN, 100000), 16, 391, false, false, "trace_lane_persistent_kernel<false, 2, false, false> 391x256 lds=16384"},
+	{"LP any-hit counting", P(K_LP, LIN, 100000).with_nodes4().with_nodes8(), 16, 391, true, true, "trace_lane_persistent_kernel<true, 2, false, true> 391x256 lds=16384"},
+	{"L4P", P(K_L4P, LIN, 100000).with_nodes4().with_nodes8(), 16, 391, true, false, "trace_lane_persistent_kernel<true, 4, false, false> 391x256 lds=16384"},
+	{"L4P counting", P(K_L4P, LIN, 100000).with_nodes4(), 8, 2048, false, true, "trace_lane_persistent_kernel<false, 4, false, true> 2048x256 lds=8192"},
+	{"L4P without the 4-wide nodes", P(K_L4P, LIN, 100000).with_nodes8(), 16, 391, false, false, "trace_lane_persistent_kernel<false, 2, false, false> 391x256 lds=16384"},
+	{"L8P", P(K_L8P, LIN, 100000).with_nodes4().with_nodes8(), 32, 1280, false, false, "trace_lane_persistent_kernel<false, 8, false, false> 1280x256 lds=32768"},
+	{"L8P any-hit counting", P(K_L8P, LIN, 100000).with_nodes8(false), 16, 391, true, true, "trace_lane_persistent_kernel<true, 8, false, true> 391x256 lds=16384"},
+	{"L8P without the 8-wide nodes", P(K_L8P, LIN, 100000).with_nodes4(), 16, 391, false, true, "trace_lane_persistent_kernel<false, 2, false, true> 391x256 lds=16384"},
+	{"TLP", P(K_TLP, LIN, 100000).with_nodes8(), 16, 391, false, false, "trace_lane_persistent_kernel<false, 2, true, false> 391x256 lds=16384"},
+	{"TLP any-hit, no counting form", P(K_TLP, LIN, 100000), 16, 391, true, true, "trace_lane_persistent_kernel<true, 2, true, false> 391x256 lds=16384"},
+	{"TLP8", P(K_TLP8, LIN, 100000).with_nodes8(), 16, 391, false, false, "trace_lane_persistent_kernel<false, 8, true, false> 391x256 lds=16384"},
+	{"TLP8 any-hit, no counting form", P(K_TLP8, LIN, 100000).with_nodes8(), 16, 391, true, true, "trace_lane_persistent_kernel<true, 8, true, false> 391x256 lds=16384"},
+	{"TLP8 without leaf boxes", P(K_TLP8, LIN, 100000).with_nodes8(false), 16, 391, false, false, "trace_lane_persistent_kernel<false, 2, true, false> 391x256 lds=16384"},
+	{"TLP8 without the 8-wide nodes", P(K_TLP8, LIN, 100000), 16, 391, true, false, "trace_lane_persistent_kernel<true, 2, true, false> 391x256 lds=16384"},
+	{"a plain id launched persistent", P(K_TL, LIN, 100000).with_nodes8(), 16, 391, false, true, "trace_lane_persistent_kernel<false, 2, false, true> 391x256 lds=16384"},
+	{"no rays", P(K_LP, LIN, 0), 16, 391, false, false, "nothing"},
+	{"no workgroups", P(K_LP, LIN, 100000), 16, 0, false, false, "nothing"},
+};
+const Resident kSource[] = {
+	{"lanes", P(K_LANE, LIN, 40000), 0, 0, true, false, "trace_hemisphere_lane_kernel<9, true> 157x256 lds=24576"},
+	{"sparse lanes", P(K_LANE, LIN, 1001).sparse(4), 0, 0, false, false, "trace_hemisphere_lane_kernel<9, false> 63x256 lds=24576"},
+	{"two-level lanes", P(K_TL, LIN, 40000), 0, 0, true, false, "trace_hemisphere_two_level_kernel<9, true> 157x256 lds=24576"},
+	{"LP", P(K_LP, LIN, 100000), 16, 391, false, false, "trace_hemisphere_persistent_kernel<9, false, 2, false> 391x256 lds=16384"},
+	{"L4P", P(K_L4P, LIN, 100000).with_nodes4(), 16, 391, true, false, "trace_hemisphere_persistent_kernel<9, true, 4, false> 391x256 lds=16384"},
+	{"L4P without the 4-wide nodes", P(K_L4P, LIN, 100000), 16, 391, true, false, "trace_hemisphere_persistent_kernel<9, true, 2, false> 391x256 lds=16384"},
+	{"L8P", P(K_L8P, LIN, 100000).with_nodes8(), 16, 391, true, false, "trace_hemisphere_persistent_kernel<9, true, 8, false> 391x256 lds=16384"},
+	{"L8P without the 8-wide nodes", P(K_L8P, LIN, 100000).with_nodes4(), 16, 391, false, false, "trace_hemisphere_persistent_kernel<9, false, 2, false> 391x256 lds=16384"},
+	{"TLP", P(K_TLP, LIN, 100000).with_nodes8(), 16, 391, false, false, "trace_hemisphere_persistent_kernel<9, false, 2, true> 391x256 lds=16384"},
+	{"TLP8", P(K_TLP8, LIN, 100000).with_nodes8(), 16, 391, true, false, "trace_hemisphere_persistent_kernel<9, true, 8, true> 391x256 lds=16384"},
+	{"TLP8 without leaf boxes", P(K_TLP8, LIN, 100000).with_nodes8(false), 16, 391, false, false, "trace_hemisphere_persistent_kernel<9, false, 2, true> 391x256 lds=16384"},
+	{"a plain two-level id launched persistent", P(K_TL, LIN, 100000).with_nodes8(), 16, 391, false, false, "trace_hemisphere_persistent_kernel<9, false, 2, true> 391x256 lds=16384"},
+	{"no entries", P(K_LANE, LIN, 0), 16, 391, false, false, "nothing"},
+	{"2^31 - 1 workgroups", P(K_LANE, LIN, kMaxBlockRays), 0, 0, false, false, "trace_hemisphere_lane_kernel<9, false> 2147483647x256 lds=24576"},
+	{"2^31 workgroups", P(K_LANE, LIN, kMaxBlockRays + 1u), 0, 0, false, false, "error"},
+	{"2^31 workgroups of sparse lanes", P(K_TL, LIN, 1ull << 33).sparse(1), 0, 0, false, false, "error"},
+	{"2^31 workgroups of entries, persistent", P(K_LP, LIN, kMaxBlockRays + 1u), 16, 2048, false, false, "trace_hemisphere_persistent_kernel<9, false, 2, false> 2048x256 lds=16384"},
+};
+
+void launches()
+{
+	for (const Launch &t : kTrace) {
+		const TraceLaunch l = resolve_trace(t.p, t.any_hit, t.count, t.quad_built);
+		const std::string got = describe(l);
+		expect(got == t.want, std::string("launch_trace, ") + t.name + ": got \"" + got + "\", want \"" + t.want + "\"");
+		covers(std::string("launch_trace, ") + t.name, t.p, l);
+	}
+	for (const Resident &t : kPersistent) {
+		const std::string got = describe(resolve_persistent(t.p, t.lds_depth, t.blocks, t.any_hit, t.count));
+		expect(got == t.want, std::string("launch_trace_persistent, ") + t.name + ": got \"" + got + "\", want \"" + t.want + "\"");
+	}
+	for (const Resident &t : kSource) {
+		const TraceLaunch l = resolve_source(t.p, t.lds_depth, t.blocks, t.any_hit);
+		const std::string got = describe(l, "hemisphere", SRC_HEMI_GRID, true);
+		expect(got == t.want, std::string("launch_source, ") + t.name + ": got \"" + got + "\", want \"" + t.want + "\"");
+		covers(std::string("launch_source, ") + t.name, t.p, l);
+	}
+	// a build with MRT_ROWS_WG_LARGE = 64 has one workgroup size
+	const P dual = P(K_DUAL, TILE, 0).with_rows().grid(64, 64).wg(256);
+	expect(describe(resolve_trace(dual, false, false, false, 64u)) == "trace_packet_rows_kernel<false, false, 2, 64, true> 32x64 lds=0 group=2", "launch_trace, MRT_ROWS_WG_LARGE 64: " + describe(resolve_trace(dual, false, false, false, 64u)));
+	// the names of record-driven casts: a family with one mode does not print it
+	const auto name = [](const TraceLaunch &l, const char *family, int src, bool with_mode) {
+		char b[96];
+		format_variant(b, sizeof(b), l.v, family, src, with_mode);
+		return std::string(b);
+	};
+	const TraceLaunch plain = resolve_source(P(K_LANE, LIN, 4096), 0, 0, true), tl = resolve_source(P(K_TL, LIN, 4096), 0, 0, false);
+	const TraceLaunch wide = resolve_source(P(K_L8P, LIN, 100000).with_nodes8(), 16, 391, true), tlp = resolve_source(P(K_TLP, LIN, 100000), 16, 391, false);
+	expect(name(plain, "shadow", SRC_SHADOW_GRID, false) == "trace_shadow_lane_kernel<3>", "names: " + name(plain, "shadow", SRC_SHADOW_GRID, false));
+	expect(name(tl, "reflection", SRC_REFLECT_RAY32, false) == "trace_reflection_two_level_kernel<4>", "names: " + name(tl, "reflection", SRC_REFLECT_RAY32, false));
+	expect(name(wide, "hemisphere", SRC_HEMI_GRID, true) == "trace_hemisphere_persistent_kernel<9, true, 8, false>", "names: " + name(wide, "hemisphere", SRC_HEMI_GRID, true));
+	expect(name(tlp, "bounce", SRC_BOUNCE_HOST, false) == "trace_bounce_persistent_kernel<11, 2, true>", "names: " + name(tlp, "bounce", SRC_BOUNCE_HOST, false));
+	expect(name(wide, "shadow", SRC_SHADOW_RAY32, false) == "trace_shadow_persistent_kernel<1, 8, false>", "names: " + name(wide, "shadow", SRC_SHADOW_RAY32, false));
+	expect(name(tl, "hemisphere", SRC_HEMI_HOST, true) == "trace_hemisphere_two_level_kernel<8, false>", "names: " + name(tl, "hemisphere", SRC_HEMI_HOST, true));
+	// a name that does not fit is cut, never written past its buffer
+	char small[16];
+	format_variant(small, sizeof(small), wide.v, "hemisphere", SRC_HEMI_GRID, true);
+	expect(std::string(small) == "trace_hemispher", std::string("names: cut to the buffer: ") + small);
 }
 
 // 15 frames of one 1280x960 grid: frames 0-3 the 64-ray kernel, 4-7 the 128-ray walk in pieces, 8-11 whole; the last two of every
@@ -452,6 +869,7 @@ void memo()
 int main()
 {
 	table();
+	launches();
 	const float pieces_win[12] = {0, 0, 0.40f, 0.38f, 0, 0, 0.35f, 0.36f, 0, 0, 0.37f, 0.38f};   // whole 0.37 > 1.03 x 0.35
 	const float whole_wins[12] = {0, 0, 0.40f, 0.38f, 0, 0, 0.35f, 0.36f, 0, 0, 0.36f, 0.361f};  // whole 0.36 <= 1.03 x 0.35
 	const float asm_wins[12] = {0, 0, 0.30f, 0.31f, 0, 0, 0.35f, 0.36f, 0, 0, 0.36f, 0.37f};

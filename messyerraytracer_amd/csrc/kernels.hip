@@ -11,11 +11,11 @@
 // __builtin_fmaf, so results are bit-identical to oracle/mrt_oracle.c.
 #include <hip/hip_runtime.h>
 #include <cfloat>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include "mrt_internal.h"
+#include "launch_policy.h"
 #include "shade_data.h"
 #include "lighting.h"
 #include "lane_map.h"
@@ -705,129 +705,58 @@ bool quad_kernel_built()
 	return false;
 #endif
 }
-// The instantiation the last launch_trace / launch_trace_persistent of this thread put on a stream, spelled as rocprofv3
-// prints it ("trace_packet_rows_kernel<false, false, 2, 64, true>"): mrt_last_kernel_variant, which bench.py uses to
-// accept committed counter passes only for the very kernel the run used.
+// The instantiation the last launch_trace / launch_trace_persistent / launch_source of this thread put on a stream, spelled by
+// format_variant (launch_policy.h) from the very TraceVariant that selected the kernel: mrt_last_kernel_variant, which bench.py uses
+// to accept committed counter passes only for the kernel the run used.
 static thread_local char g_variant[96] = "";
 const char *last_trace_variant() { return g_variant; }
-static void note_variant(const char *fmt, ...)
-{
-	va_list ap; va_start(ap, fmt); vsnprintf(g_variant, sizeof(g_variant), fmt, ap); va_end(ap);
-}
-#define MRT_B(x) ((x) ? "true" : "false")
 #ifndef MRT_ROWS_WG_LARGE
 #define MRT_ROWS_WG_LARGE MRT_WG // threads per workgroup of the rows kernel on large scenes
 #endif
-constexpr uint32_t kPrefetchMaxWaves = kWaveSlots + kWaveSlots / 4u; // 1.25 rounds of the device's wave slots
+
+// Runtime values as template arguments.  dispatch(f, Among<Vs...>{v}, ...) calls f(std::integral_constant...) with, for every
+// Among, the one of its Vs that equals its v (none: f is not called).  The first Among varies slowest, and the instantiations f
+// makes are emitted in that order: the launchers below list theirs so that the code object keeps its kernels where they were.
+template <auto... Vs> struct Among { std::common_type_t<decltype(Vs)...> v; };
+using Bool = Among<true, false>;
+template <class F> static void dispatch(F &&f) { f(); }
+template <class F, auto... Vs, class... Rest>
+static void dispatch(F &&f, Among<Vs...> first, Rest... rest)
+{
+	(void)(... || (first.v == Vs && (dispatch([&](auto... cs) { f(std::integral_constant<decltype(Vs), Vs>{}, cs...); }, rest...), true)));
+}
+
+// launch_policy.cpp resolve_trace decides everything -- the kernel, its template arguments, the grid --; this is the lookup.
 hipError_t launch_trace(const TraceParams &p_in, bool any_hit, bool count, hipStream_t stream)
 {
+	const TraceLaunch l = resolve_trace(p_in, any_hit, count, quad_kernel_built(), MRT_ROWS_WG_LARGE);
+	if (l.error) return hipErrorInvalidValue;
+	if (l.blocks == 0) return hipSuccess;
 	TraceParams p = p_in;
-	// consecutive tiles per workgroup (tile_order 3): the rows kernel's workgroup holds rows_wg / 64 waves of two tiles each
-	// (MRT_KERNEL_PACKET_DUAL) or 4 waves of one; every other kernel 4 waves of one tile
-	p.tile_group = (p.kernel == MRT_KERNEL_PACKET_DUAL && p.row_array != nullptr) ? 2u * ((p.rows_wg == 64u ? 64u : (uint32_t)MRT_ROWS_WG_LARGE) / MRT_WAVE) : MRT_WG / MRT_WAVE;
-	uint64_t threads;
-	if (p.tile_sched != nullptr && p.sched_hdr != nullptr && p.n_slots_max != 0u) {
-		threads = (uint64_t)p.n_slots_max * p.tile_unit * 64u; // (slots past sched_hdr[2] have nothing to do)
-		// a width found on the device was scheduled from an earlier cast's: should this batch's grid differ, the kernel ignores the
-		// schedule and maps tiles in plain order, a lane per ray (a schedule of the batch's own grid covers that already)
-		if (p.lane_map == MAP_AUTO && threads < p.count) threads = p.count;
-	} else if (p.lane_map == MAP_TILE8X8) {
-		const uint32_t th = 64u >> p.tile_w_log2;
-		threads = (uint64_t)p.tiles_x * ((p.rows + th - 1u) / th) * 64u * (p.quarter_all == 2u ? 16u : (p.quarter_all ? 4u : 1u));
-	} else if (p.lane_map == MAP_LINEAR && p.sparse_lanes) threads = (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u;
-	else threads = p.count * ((p.lane_map == MAP_AUTO && p.quarter_all) ? (p.quarter_all == 2u ? 16u : 4u) : 1u); // (a width found on the device: whole tiles, count / 64 of them)
-	if (threads == 0) return hipSuccess;
-	const uint64_t blocks = (threads + MRT_WG - 1) / MRT_WG;
-	if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-	dim3 grid((uint32_t)blocks), wg(MRT_WG);
-	if (p.kernel == MRT_KERNEL_TWO_LEVEL_PACKET) { // two-level scene, coherent batch: one wave per packet
-		if (any_hit) hipLaunchKernelGGL((trace_two_level_packet_kernel<true>), grid, wg, p.extra_lds, stream, p);
-		else hipLaunchKernelGGL((trace_two_level_packet_kernel<false>), grid, wg, p.extra_lds, stream, p);
-		note_variant("trace_two_level_packet_kernel<%s>", MRT_B(any_hit));
-		return hipGetLastError();
-	}
-	if (p.kernel == MRT_KERNEL_TWO_LEVEL) { // two-level scene: one lane per ray, per-lane LDS stack
-		const size_t lds2 = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
-		if (any_hit) hipLaunchKernelGGL((trace_two_level_kernel<true>), grid, wg, lds2, stream, p);
-		else hipLaunchKernelGGL((trace_two_level_kernel<false>), grid, wg, lds2, stream, p);
-		note_variant("trace_two_level_kernel<%s>", MRT_B(any_hit));
-		return hipGetLastError();
-	}
+	p.tile_group = l.tile_group;
+	const TraceVariant &v = l.v;
+	const Bool a{v.any_hit}, c{v.count};
+	const auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(l.blocks), dim3(l.threads), l.lds, stream, p); };
+	switch (v.kernel) {
+		case TraceKernel::TWO_LEVEL_PACKET: dispatch([&](auto A) { go(trace_two_level_packet_kernel<A>); }, a); break;
+		case TraceKernel::TWO_LEVEL: dispatch([&](auto A) { go(trace_two_level_kernel<A>); }, a); break;
 #ifdef MRT_WITH_QUAD
-	if (p.kernel == MRT_KERNEL_PACKET_QUAD && p.row_array4 != nullptr) {
-		// the 128-ray walk over 4-wide node rows: two packets per wave (half the waves)
-		const uint64_t rblocks = (threads + 2u * MRT_WG - 1) / (2u * MRT_WG);
-		dim3 rgrid((uint32_t)rblocks);
-		if (count) {
-			if (any_hit) hipLaunchKernelGGL((trace_packet_quad_kernel<true, true>), rgrid, wg, p.extra_lds, stream, p);
-			else hipLaunchKernelGGL((trace_packet_quad_kernel<false, true>), rgrid, wg, p.extra_lds, stream, p);
-		} else if (any_hit) hipLaunchKernelGGL((trace_packet_quad_kernel<true, false>), rgrid, wg, p.extra_lds, stream, p);
-		else hipLaunchKernelGGL((trace_packet_quad_kernel<false, false>), rgrid, wg, p.extra_lds, stream, p);
-		note_variant("trace_packet_quad_kernel<%s, %s>", MRT_B(any_hit), MRT_B(count));
-		return hipGetLastError();
-	}
+		case TraceKernel::PACKET_QUAD: dispatch([&](auto C, auto A) { go(trace_packet_quad_kernel<A, C>); }, c, a); break;
 #endif
-	if ((p.kernel == MRT_KERNEL_PACKET_DUAL || p.kernel == MRT_KERNEL_PACKET_ROWS) && p.row_array != nullptr) {
-		// the walk over the unified row array: one or two packets per wave (two: half the waves)
-		const uint32_t packets = p.kernel == MRT_KERNEL_PACKET_DUAL ? 2u : 1u;
-		const uint32_t rows_wg = packets == 2u && p.rows_wg == 64u ? 64u : (packets == 2u ? (uint32_t)MRT_ROWS_WG_LARGE : (uint32_t)MRT_WG);
-		const uint64_t rblocks = (threads + packets * rows_wg - 1) / (packets * rows_wg);
-		dim3 rgrid((uint32_t)rblocks), rwg(rows_wg);
-#define MRT_LAUNCH_ROWS(A, C, N, W, F) hipLaunchKernelGGL((trace_packet_rows_kernel<A, C, N, W, F>), rgrid, rwg, p.extra_lds, stream, p)
-#define MRT_LAUNCH_ROWS_AC(N, W, F)                                                                                    \
-		do {                                                                                                        \
-			if (count) { if (any_hit) MRT_LAUNCH_ROWS(true, true, N, W, F); else MRT_LAUNCH_ROWS(false, true, N, W, F); } \
-			else { if (any_hit) MRT_LAUNCH_ROWS(true, false, N, W, F); else MRT_LAUNCH_ROWS(false, false, N, W, F); }   \
-		} while (0)
-		const bool cull = packets == 2u && (p.rows_cull == 1u || (p.rows_cull == 2u && p.in_fmt == IN_GRID));
-		if (packets == 2u && rows_wg == 64u) { if (cull) MRT_LAUNCH_ROWS_AC(2, 64, true); else MRT_LAUNCH_ROWS_AC(2, 64, false); }
-		else if (packets == 2u) { if (cull) MRT_LAUNCH_ROWS_AC(2, MRT_ROWS_WG_LARGE, true); else MRT_LAUNCH_ROWS_AC(2, MRT_ROWS_WG_LARGE, false); }
-		else MRT_LAUNCH_ROWS_AC(1, MRT_WG, false);
-#undef MRT_LAUNCH_ROWS_AC
-#undef MRT_LAUNCH_ROWS
-		note_variant("trace_packet_rows_kernel<%s, %s, %u, %u, %s>", MRT_B(any_hit), MRT_B(count), packets, rows_wg, MRT_B(cull));
-		return hipGetLastError();
+		case TraceKernel::PACKET_ROWS:
+			if (v.packets == 2u)
+				dispatch([&](auto W, auto F, auto C, auto A) { go(trace_packet_rows_kernel<A, C, 2, W, F>); },
+						Among<64, MRT_ROWS_WG_LARGE>{(int)v.wg}, Bool{v.cull}, c, a);
+			else dispatch([&](auto C, auto A) { go(trace_packet_rows_kernel<A, C, 1, MRT_WG, false>); }, c, a);
+			break;
+		case TraceKernel::PACKET_ASM:
+			dispatch([&](auto C, auto KPF, auto A) { if constexpr (!(C && KPF)) go(trace_packet_asm_kernel<A, C, KPF>); }, c, Bool{v.prefetch}, a);
+			break;
+		case TraceKernel::PACKET: dispatch([&](auto A, auto C) { go(trace_packet_kernel<A, C>); }, a, c); break;
+		case TraceKernel::LANE: dispatch([&](auto A, auto C) { go(trace_lane_kernel<A, C>); }, a, c); break;
+		default: return hipErrorInvalidValue; // (resolve_trace names no other; the persistent walk is launch_trace_persistent's)
 	}
-	// scenes whose node offsets pass the asm loop's 32 bits use the C++ packet kernel
-	if ((p.kernel == MRT_KERNEL_PACKET_ASM || p.kernel == MRT_KERNEL_PACKET_DUAL || p.kernel == MRT_KERNEL_PACKET_ROWS || p.kernel == MRT_KERNEL_PACKET_QUAD) && p.n_nodes < kAsmNodeLimit) {
-		if (count) {
-			if (any_hit) hipLaunchKernelGGL((trace_packet_asm_kernel<true, true>), grid, wg, p.extra_lds, stream, p);
-			else hipLaunchKernelGGL((trace_packet_asm_kernel<false, true>), grid, wg, p.extra_lds, stream, p);
-		} else {
-			// the scalar-cache prefetch of both children: where the launch is about one round of waves (packet_asm_kernel.h)
-			// (a scheduled launch covers the slots the list MAY use: what counts is the units, or the one round the fill rule makes of fewer)
-			uint64_t waves = p.tile_sched != nullptr && p.n_slots_max != 0u ? (p.n_units > kWaveSlots ? p.n_units : (p.n_slots_max < kWaveSlots ? p.n_slots_max : kWaveSlots)) : threads / MRT_WAVE;
-			if (p.lane_map == MAP_AUTO && waves < (p.count + MRT_WAVE - 1u) / MRT_WAVE) waves = (p.count + MRT_WAVE - 1u) / MRT_WAVE; // (as above)
-			const bool kpf = waves <= kPrefetchMaxWaves;
-			if (kpf) { if (any_hit) hipLaunchKernelGGL((trace_packet_asm_kernel<true, false, true>), grid, wg, p.extra_lds, stream, p);
-				else hipLaunchKernelGGL((trace_packet_asm_kernel<false, false, true>), grid, wg, p.extra_lds, stream, p); }
-			else if (any_hit) hipLaunchKernelGGL((trace_packet_asm_kernel<true>), grid, wg, p.extra_lds, stream, p);
-			else hipLaunchKernelGGL((trace_packet_asm_kernel<false>), grid, wg, p.extra_lds, stream, p);
-			if (kpf) { note_variant("trace_packet_asm_kernel<%s, false, true>", MRT_B(any_hit)); return hipGetLastError(); }
-		}
-		note_variant("trace_packet_asm_kernel<%s, %s>", MRT_B(any_hit), MRT_B(count));
-		return hipGetLastError();
-	}
-	if (p.kernel == MRT_KERNEL_PACKET || p.kernel == MRT_KERNEL_PACKET_ASM || p.kernel == MRT_KERNEL_PACKET_DUAL || p.kernel == MRT_KERNEL_PACKET_ROWS || p.kernel == MRT_KERNEL_PACKET_QUAD) {
-		if (any_hit) {
-			if (count) hipLaunchKernelGGL((trace_packet_kernel<true, true>), grid, wg, 0, stream, p);
-			else hipLaunchKernelGGL((trace_packet_kernel<true, false>), grid, wg, 0, stream, p);
-		} else {
-			if (count) hipLaunchKernelGGL((trace_packet_kernel<false, true>), grid, wg, 0, stream, p);
-			else hipLaunchKernelGGL((trace_packet_kernel<false, false>), grid, wg, 0, stream, p);
-		}
-		note_variant("trace_packet_kernel<%s, %s>", MRT_B(any_hit), MRT_B(count));
-		return hipGetLastError();
-	}
-	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
-	if (any_hit) {
-		if (count) hipLaunchKernelGGL((trace_lane_kernel<true, true>), grid, wg, lds, stream, p);
-		else hipLaunchKernelGGL((trace_lane_kernel<true, false>), grid, wg, lds, stream, p);
-	} else {
-		if (count) hipLaunchKernelGGL((trace_lane_kernel<false, true>), grid, wg, lds, stream, p);
-		else hipLaunchKernelGGL((trace_lane_kernel<false, false>), grid, wg, lds, stream, p);
-	}
-	note_variant("trace_lane_kernel<%s, %s>", MRT_B(any_hit), MRT_B(count));
+	format_variant(g_variant, sizeof(g_variant), v);
 	return hipGetLastError();
 }
 
@@ -843,100 +772,47 @@ static PersistParams persist_params(const TraceParams &p, unsigned long long *ne
 	return q;
 }
 
-// Persistent lane kernel: `blocks` workgroups stay resident and pull rays from *next_ray.
+// Persistent lane kernel: `blocks` workgroups stay resident and pull rays from *next_ray (resolve_persistent: which walk).
 hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream)
 {
-	if (p.count == 0 || blocks == 0) return hipSuccess;
+	const TraceLaunch l = resolve_persistent(p, lds_depth, blocks, any_hit, count);
+	if (l.blocks == 0) return hipSuccess;
 	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
-	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * lds_depth * MRT_WAVE * sizeof(uint32_t);
-	const bool wide8 = p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr;
-	const bool wide4 = p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr;
-	if (p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) {
-		if (any_hit) hipLaunchKernelGGL((trace_lane_persistent_kernel<true, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-		else hipLaunchKernelGGL((trace_lane_persistent_kernel<false, 8, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-	} else if (p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8) {
-		if (any_hit) hipLaunchKernelGGL((trace_lane_persistent_kernel<true, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-		else hipLaunchKernelGGL((trace_lane_persistent_kernel<false, 2, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-	} else if (count) { // counting builds (flat scenes)
-#define MRT_LP(A, W) hipLaunchKernelGGL((trace_lane_persistent_kernel<A, W, false, true>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q)
-		if (wide8) { if (any_hit) MRT_LP(true, 8); else MRT_LP(false, 8); }
-		else if (wide4) { if (any_hit) MRT_LP(true, 4); else MRT_LP(false, 4); }
-		else { if (any_hit) MRT_LP(true, 2); else MRT_LP(false, 2); }
-#undef MRT_LP
-	} else if (wide8) {
-		if (any_hit) hipLaunchKernelGGL((trace_lane_persistent_kernel<true, 8>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-		else hipLaunchKernelGGL((trace_lane_persistent_kernel<false, 8>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-	} else if (wide4) {
-		if (any_hit) hipLaunchKernelGGL((trace_lane_persistent_kernel<true, 4>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-		else hipLaunchKernelGGL((trace_lane_persistent_kernel<false, 4>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-	} else {
-		if (any_hit) hipLaunchKernelGGL((trace_lane_persistent_kernel<true, 2>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-		else hipLaunchKernelGGL((trace_lane_persistent_kernel<false, 2>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q);
-	}
-	{
-		const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
-		const int width = tl ? ((p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) ? 8 : 2) : (wide8 ? 8 : (wide4 ? 4 : 2));
-		note_variant("trace_lane_persistent_kernel<%s, %d, %s, %s>", MRT_B(any_hit), width, MRT_B(tl), MRT_B(count && !tl));
-	}
+	const TraceVariant &v = l.v;
+	dispatch([&](auto TL, auto C, auto W, auto A) {
+		if constexpr (!TL || (W != 4 && !C)) // (the two-level walk is 8- or 2-wide and does not count)
+			hipLaunchKernelGGL((trace_lane_persistent_kernel<A, W, TL, C>), dim3(l.blocks), dim3(l.threads), l.lds, stream, p, q);
+	}, Bool{v.two_level}, Bool{v.count}, Among<8, 4, 2>{v.width}, Bool{v.any_hit});
+	format_variant(g_variant, sizeof(g_variant), v);
 	return hipGetLastError();
 }
 
 // Record-driven casts: p.kernel is the lane kernel the plan chose (launch_policy.cpp plan_source); p.count = entries.  persistent:
-// blocks != 0 (as launch_trace_persistent), else the plain kernel with p.sparse_lanes.  The label noted for mrt_last_kernel_variant
-// names (family, source, mode where the family has two, width, two-level) in the form the GPU tests and the recorded profiles pin,
-// "trace_shadow_lane_kernel<3>", "trace_hemisphere_persistent_kernel<9, true, 8, false>": not a symbol of this library.
-template <class S, int SRC, bool ANY_HIT>
-static void launch_source_as(const TraceParams &p, const S &s, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
-{
-	using F = SourceFamily<S>;
-	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
-	char mode[8] = "";
-	if (F::any_hit && F::nearest) snprintf(mode, sizeof(mode), ", %s", MRT_B(ANY_HIT));
-	if (blocks == 0) {
-		const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
-		const dim3 grid((uint32_t)((threads + MRT_WG - 1) / MRT_WG)), wg(MRT_WG);
-		const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * p.stack_depth * MRT_WAVE * sizeof(uint32_t);
-		if (tl) hipLaunchKernelGGL((trace_source_two_level_kernel<S, SRC, ANY_HIT>), grid, wg, lds, stream, p, s);
-		else hipLaunchKernelGGL((trace_source_lane_kernel<S, SRC, ANY_HIT>), grid, wg, lds, stream, p, s);
-		note_variant("trace_%s_%s_kernel<%d%s>", F::name, tl ? "two_level" : "lane", SRC, mode);
-		return;
-	}
-	const PersistParams q = persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks);
-	const size_t lds = (size_t)(MRT_WG / MRT_WAVE) * q.lds_depth * MRT_WAVE * sizeof(uint32_t);
-#define MRT_LS(W, T) hipLaunchKernelGGL((trace_source_persistent_kernel<S, SRC, ANY_HIT, W, T>), dim3(blocks), dim3(MRT_WG), lds, stream, p, q, s)
-	int width = 2;
-	if (tl && p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr) { width = 8; MRT_LS(8, true); }
-	else if (tl) MRT_LS(2, true);
-	else if (p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr) { width = 8; MRT_LS(8, false); }
-	else if (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr) { width = 4; MRT_LS(4, false); }
-	else MRT_LS(2, false);
-#undef MRT_LS
-	note_variant("trace_%s_persistent_kernel<%d%s, %d, %s>", F::name, SRC, mode, width, MRT_B(tl));
-}
-
-// src = one of the family's three sources; any_hit = a mode the family has (shadows any-hit, reflections and bounces closest-hit,
-// hemispheres either: the other instantiations do not compile, source_entry).  Anything else is hipErrorInvalidValue.
+// blocks != 0 (as launch_trace_persistent), else the plain kernel with p.sparse_lanes (resolve_source).  src = one of the family's
+// three sources; any_hit = a mode the family has (shadows any-hit, reflections and bounces closest-hit, hemispheres either: the other
+// instantiations do not compile, source_entry).  Anything else is hipErrorInvalidValue.
 template <class S>
 hipError_t launch_source(const TraceParams &p, const void *params, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream)
 {
 	using F = SourceFamily<S>;
 	const S &s = *static_cast<const S *>(params);
-	if (p.count == 0) return hipSuccess;
-	const uint64_t threads = p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count;
-	if (blocks == 0 && (threads + MRT_WG - 1) / MRT_WG > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	const TraceLaunch l = resolve_source(p, lds_depth, blocks, any_hit);
+	if (l.error) return hipErrorInvalidValue;
+	if (l.blocks == 0) return hipSuccess;
 	if ((src != F::ray32 && src != F::host && src != F::grid) || !(any_hit ? F::any_hit : F::nearest)) return hipErrorInvalidValue;
-#define MRT_LS_SRC(A)                                                                                                                        \
-	do {                                                                                                                                 \
-		if (src == F::ray32) launch_source_as<S, F::ray32, A>(p, s, next_ray, overflow, lds_depth, refill, leaf_wait, blocks, stream);   \
-		else if (src == F::host) launch_source_as<S, F::host, A>(p, s, next_ray, overflow, lds_depth, refill, leaf_wait, blocks, stream); \
-		else launch_source_as<S, F::grid, A>(p, s, next_ray, overflow, lds_depth, refill, leaf_wait, blocks, stream);                     \
-	} while (0)
-	if constexpr (F::any_hit) { if (any_hit) MRT_LS_SRC(true); }
-	if constexpr (F::nearest) { if (!any_hit) MRT_LS_SRC(false); }
-#undef MRT_LS_SRC
+	const TraceVariant &v = l.v;
+	const dim3 grid(l.blocks), wg(l.threads);
+	const PersistParams q = blocks ? persist_params(p, next_ray, overflow, lds_depth, refill, leaf_wait, blocks) : PersistParams{};
+	dispatch([&](auto A, auto SRC, auto TL, auto W) {
+		if constexpr ((A ? F::any_hit : F::nearest) && (!TL || W != 4)) { // (the plain kernels take neither TL nor W: a variant's defaults)
+			if (v.kernel == TraceKernel::TWO_LEVEL) hipLaunchKernelGGL((trace_source_two_level_kernel<S, SRC, A>), grid, wg, l.lds, stream, p, s);
+			else if (v.kernel == TraceKernel::LANE) hipLaunchKernelGGL((trace_source_lane_kernel<S, SRC, A>), grid, wg, l.lds, stream, p, s);
+			else hipLaunchKernelGGL((trace_source_persistent_kernel<S, SRC, A, W, TL>), grid, wg, l.lds, stream, p, q, s);
+		}
+	}, Bool{any_hit}, Among<F::ray32, F::host, F::grid>{src}, Bool{v.two_level}, Among<8, 4, 2>{v.width});
+	format_variant(g_variant, sizeof(g_variant), v, F::name, src, F::any_hit && F::nearest);
 	return hipGetLastError();
 }
 template hipError_t launch_source<ShadowParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);

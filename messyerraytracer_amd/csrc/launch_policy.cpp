@@ -1,5 +1,6 @@
 // launch_policy.cpp — the cast launch policy (launch_policy.h): plain host code, no HIP.
 #include <cstdint>
+#include <cstdio>
 #include "../../include/mrt_hip.h"
 #include "mrt_internal.h"
 #include "launch_policy.h"
@@ -283,6 +284,138 @@ CastPlan plan_cast(const mrt_options &o, const SceneFacts &s, const CastRequest 
 	c.arms_tuner = t.armed && (r.entry == ENTRY_CAST || r.entry == ENTRY_GRID);
 	gs.tune().armed = c.arms_tuner;
 	return c;
+}
+
+// ---- plan -> variant -> launch -> label (launch_policy.h) ------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kWg = 256, kWave = 64; // MRT_WG and MRT_WAVE of kernels.hip: every kernel's workgroup but the 128-ray walk's
+
+// the per-lane LDS stack of the lane kernels: entry d of lane l at dword d * 64 + l of its wave's region
+size_t lane_stack_lds(uint32_t depth) { return (size_t)(kWg / kWave) * depth * kWave * sizeof(uint32_t); }
+uint32_t pieces_per_tile(uint32_t quarter_all) { return quarter_all == 2u ? 16u : (quarter_all ? 4u : 1u); }
+uint64_t linear_lanes(const TraceParams &p) { return p.sparse_lanes ? (p.count + p.sparse_lanes - 1u) / p.sparse_lanes * 64u : p.count; }
+
+// The lanes a plain or packet launch covers (one per ray, or 64 per piece of a tile): at least the batch's rays.
+uint64_t launch_lanes(const TraceParams &p)
+{
+	if (p.tile_sched != nullptr && p.sched_hdr != nullptr && p.n_slots_max != 0u) {
+		const uint64_t lanes = (uint64_t)p.n_slots_max * p.tile_unit * 64u; // (slots past sched_hdr[2] have nothing to do)
+		// a width found on the device was scheduled from an earlier cast's: should this batch's grid differ, the kernel ignores the
+		// schedule and maps tiles in plain order, a lane per ray (a schedule of the batch's own grid covers that already)
+		return p.lane_map == MAP_AUTO && lanes < p.count ? p.count : lanes;
+	}
+	if (p.lane_map == MAP_TILE8X8) {
+		const uint32_t th = 64u >> p.tile_w_log2;
+		return (uint64_t)p.tiles_x * ((p.rows + th - 1u) / th) * 64u * pieces_per_tile(p.quarter_all);
+	}
+	if (p.lane_map == MAP_LINEAR) return linear_lanes(p);
+	return p.count * (p.lane_map == MAP_AUTO ? pieces_per_tile(p.quarter_all) : 1u); // (a width found on the device: whole tiles, count / 64 of them)
+}
+
+// The asm kernel's scalar-cache prefetch of both children pays where the launch is about one round of waves (packet_asm_kernel.h).
+// A scheduled launch covers the slots the list MAY use: what counts is the units, or the one round the fill rule makes of fewer.
+bool prefetch_pays(const TraceParams &p, uint64_t lanes)
+{
+	uint64_t waves = p.tile_sched != nullptr && p.n_slots_max != 0u
+			? (p.n_units > kWaveSlots ? p.n_units : (p.n_slots_max < kWaveSlots ? p.n_slots_max : kWaveSlots)) : lanes / kWave;
+	if (p.lane_map == MAP_AUTO && waves < (p.count + kWave - 1u) / kWave) waves = (p.count + kWave - 1u) / kWave; // (as in launch_lanes)
+	return waves <= kPrefetchMaxWaves;
+}
+
+// The persistent walk of p.kernel: 8- or 4-wide where the id asks for it and the layout is resident, else 2-wide.
+void persistent_launch(TraceLaunch &l, const TraceParams &p, bool two_level, uint32_t lds_depth, uint32_t blocks)
+{
+	TraceVariant &v = l.v;
+	v.kernel = TraceKernel::LANE_PERSISTENT; v.two_level = two_level;
+	if (two_level) v.width = p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8 && p.nodes8 != nullptr && p.leaf_box != nullptr ? 8 : 2;
+	else v.width = p.kernel == MRT_KERNEL_LANE8_PERSISTENT && p.nodes8 != nullptr ? 8 : (p.kernel == MRT_KERNEL_LANE4_PERSISTENT && p.nodes4 != nullptr ? 4 : 2);
+	l.blocks = blocks; l.lds = lane_stack_lds(lds_depth);
+}
+
+} // namespace
+
+TraceLaunch resolve_trace(const TraceParams &p, bool any_hit, bool count, bool quad_built, uint32_t rows_wg_large)
+{
+	TraceLaunch l;
+	TraceVariant &v = l.v;
+	const uint64_t lanes = launch_lanes(p);
+	if (lanes == 0) return l;
+	if ((lanes + kWg - 1) / kWg > 0x7FFFFFFFull) { l.error = true; return l; }
+	const bool rows_id = p.kernel == MRT_KERNEL_PACKET_DUAL || p.kernel == MRT_KERNEL_PACKET_ROWS;
+	const bool packet_id = p.kernel == MRT_KERNEL_PACKET_ASM || rows_id || p.kernel == MRT_KERNEL_PACKET_QUAD;
+	uint64_t per_block = kWg; // lanes a workgroup covers
+	v.any_hit = any_hit; v.count = count;
+	if (p.kernel == MRT_KERNEL_TWO_LEVEL_PACKET) { // two-level scene, coherent batch: one wave per packet
+		v.kernel = TraceKernel::TWO_LEVEL_PACKET; v.count = false; l.lds = p.extra_lds;
+	} else if (p.kernel == MRT_KERNEL_TWO_LEVEL) { // two-level scene: one lane per ray, per-lane LDS stack
+		v.kernel = TraceKernel::TWO_LEVEL; v.count = false; l.lds = lane_stack_lds(p.stack_depth);
+	} else if (quad_built && p.kernel == MRT_KERNEL_PACKET_QUAD && p.row_array4 != nullptr) {
+		// the 128-ray walk over 4-wide node rows: two packets per wave (half the waves)
+		v.kernel = TraceKernel::PACKET_QUAD; l.lds = p.extra_lds; per_block = 2u * kWg;
+	} else if (rows_id && p.row_array != nullptr) {
+		// the walk over the unified row array: one or two packets per wave (two: half the waves, rows_wg / 64 waves of two tiles each
+		// per workgroup, culling by where the rays come from unless forced)
+		v.kernel = TraceKernel::PACKET_ROWS; l.lds = p.extra_lds;
+		v.packets = p.kernel == MRT_KERNEL_PACKET_DUAL ? 2u : 1u;
+		if (v.packets == 2u) {
+			v.wg = p.rows_wg == 64u ? 64u : rows_wg_large;
+			v.cull = p.rows_cull == 1u || (p.rows_cull == 2u && p.in_fmt == IN_GRID);
+			l.tile_group = 2u * (v.wg / kWave);
+		}
+		l.threads = v.wg; per_block = (uint64_t)v.packets * v.wg;
+	} else if (packet_id && p.n_nodes < kAsmNodeLimit) {
+		v.kernel = TraceKernel::PACKET_ASM; l.lds = p.extra_lds;
+		v.prefetch = !count && prefetch_pays(p, lanes);
+	} else if (p.kernel == MRT_KERNEL_PACKET || packet_id) { // (scenes whose node offsets pass the asm loop's 32 bits)
+		v.kernel = TraceKernel::PACKET;
+	} else l.lds = lane_stack_lds(p.stack_depth);
+	l.blocks = (uint32_t)((lanes + per_block - 1) / per_block);
+	return l;
+}
+
+TraceLaunch resolve_persistent(const TraceParams &p, uint32_t lds_depth, uint32_t blocks, bool any_hit, bool count)
+{
+	TraceLaunch l;
+	if (p.count == 0 || blocks == 0) return l;
+	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
+	persistent_launch(l, p, tl, lds_depth, blocks);
+	l.v.any_hit = any_hit; l.v.count = count && !tl; // (the counting form exists for flat scenes)
+	return l;
+}
+
+TraceLaunch resolve_source(const TraceParams &p, uint32_t lds_depth, uint32_t blocks, bool any_hit)
+{
+	TraceLaunch l;
+	if (p.count == 0) return l;
+	const bool tl = p.kernel == MRT_KERNEL_TWO_LEVEL || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT || p.kernel == MRT_KERNEL_TWO_LEVEL_PERSISTENT8;
+	l.v.any_hit = any_hit;
+	if (blocks != 0) { persistent_launch(l, p, tl, lds_depth, blocks); return l; }
+	const uint64_t n = (linear_lanes(p) + kWg - 1) / kWg;
+	if (n > 0x7FFFFFFFull) { l.error = true; return l; }
+	l.v.kernel = tl ? TraceKernel::TWO_LEVEL : TraceKernel::LANE;
+	l.blocks = (uint32_t)n; l.lds = lane_stack_lds(p.stack_depth);
+	return l;
+}
+
+void format_variant(char *out, size_t n, const TraceVariant &v, const char *family, int src, bool with_mode)
+{
+	static const char *const names[] = {"lane", "two_level", "two_level_packet", "packet", "packet_asm", "packet_rows", "packet_quad", "lane_persistent"};
+	const auto b = [](bool x) { return x ? "true" : "false"; };
+	const char *name = names[(uint32_t)v.kernel], *a = b(v.any_hit), *c = b(v.count);
+	if (family != nullptr) { // not a symbol of the library: (family, source, mode where the family has two, width, two-level)
+		const char *mode = !with_mode ? "" : (v.any_hit ? ", true" : ", false");
+		if (v.kernel == TraceKernel::LANE_PERSISTENT) std::snprintf(out, n, "trace_%s_persistent_kernel<%d%s, %d, %s>", family, src, mode, v.width, b(v.two_level));
+		else std::snprintf(out, n, "trace_%s_%s_kernel<%d%s>", family, name, src, mode);
+		return;
+	}
+	switch (v.kernel) {
+		case TraceKernel::TWO_LEVEL: case TraceKernel::TWO_LEVEL_PACKET: std::snprintf(out, n, "trace_%s_kernel<%s>", name, a); break;
+		case TraceKernel::PACKET_ROWS: std::snprintf(out, n, "trace_%s_kernel<%s, %s, %u, %u, %s>", name, a, c, v.packets, v.wg, b(v.cull)); break;
+		case TraceKernel::LANE_PERSISTENT: std::snprintf(out, n, "trace_%s_kernel<%s, %d, %s, %s>", name, a, v.width, b(v.two_level), c); break;
+		// (the asm kernel's KPF is spelled only where it is not the default, and then COUNT is false)
+		default: std::snprintf(out, n, v.prefetch ? "trace_%s_kernel<%s, false, true>" : "trace_%s_kernel<%s, %s>", name, a, c); break;
+	}
 }
 
 } // namespace mrt

@@ -1,6 +1,12 @@
-// launch_policy.h — which kernel a cast gets and how it is launched, as plain host code (no HIP calls, no allocation).
-// The HIP side (cast.hip launch_planned) executes a CastPlan; csrc/host/launch_policy_test.cpp pins the plans on the CPU.
+// launch_policy.h — which kernel a cast gets and how it is launched, as plain host code (no HIP calls, no allocation), in two steps:
+//   plan_cast:      the cast -> a CastPlan (kernel id, lane map, sort / detect / schedule, the lane launch); cast.hip launch_planned
+//                   executes it and fills a TraceParams per launch;
+//   resolve_trace / resolve_persistent / resolve_source: that TraceParams -> a TraceLaunch, the one instantiation (TraceVariant) with
+//                   its grid, workgroup, LDS and tile_group.  kernels.hip looks the instantiation up from the variant, launches it
+//                   with that geometry and prints the label of mrt_last_kernel_variant from the same value (format_variant).
+// csrc/host/launch_policy_test.cpp pins both steps on the CPU: every plan with the label and the geometry it resolves to.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include "../../include/mrt_hip.h"
 #include "mrt_internal.h"
@@ -136,6 +142,43 @@ inline uint32_t schedule_slots(uint32_t n_units, bool pieces)
 {
 	return pieces ? (n_units + n_units / 2u > kWaveSlots ? n_units + n_units / 2u : kWaveSlots) : n_units;
 }
+
+// ---- plan -> variant -> launch -> label ---------------------------------------------------------------------------------------
+// One instantiation of the trace kernels.  The template arguments a kernel does not have stay at their defaults here.
+enum class TraceKernel : uint32_t { LANE, TWO_LEVEL, TWO_LEVEL_PACKET, PACKET, PACKET_ASM, PACKET_ROWS, PACKET_QUAD, LANE_PERSISTENT };
+struct TraceVariant {
+	TraceKernel kernel = TraceKernel::LANE;
+	bool any_hit = false, count = false;
+	uint32_t packets = 1, wg = 256; bool cull = false; // PACKET_ROWS: packets per wave, threads per workgroup, the frustum cull
+	bool prefetch = false;                             // PACKET_ASM: the scalar-cache prefetch of both children (never with count)
+	int width = 2; bool two_level = false;             // LANE_PERSISTENT: children per node step, the two-level walk
+};
+// A variant with its launch.  blocks == 0: nothing to launch (no rays; the label stays as it was); error: more than 0x7FFFFFFF
+// workgroups of 256 lanes (hipErrorInvalidValue).
+struct TraceLaunch {
+	TraceVariant v;
+	bool error = false;
+	uint32_t blocks = 0, threads = 256;  // workgroups, threads per workgroup
+	size_t lds = 0;                      // dynamic LDS bytes per workgroup
+	uint32_t tile_group = 4;             // plain and packet launches: the TraceParams::tile_group the kernel must see (tiles per workgroup)
+	uint32_t packets_per_wave() const { return v.kernel == TraceKernel::PACKET_QUAD ? 2u : (v.kernel == TraceKernel::PACKET_ROWS ? v.packets : 1u); }
+};
+constexpr uint32_t kPrefetchMaxWaves = kWaveSlots + kWaveSlots / 4u; // the asm kernel prefetches up to 1.25 rounds of the device's wave slots
+
+// A plain or packet launch of a primary cast (launch_trace): p as launch_planned filled it.  Fallbacks, in this order: a two-level id
+// takes its own kernel; PACKET_QUAD without row_array4 (or a build without the kernel: quad_built) and PACKET_DUAL / PACKET_ROWS
+// without row_array take the asm kernel; any of the four packet ids with n_nodes >= kAsmNodeLimit takes the C++ packet kernel.
+// rows_wg_large: threads per workgroup of the 128-ray walk where p.rows_wg != 64 (the build's MRT_ROWS_WG_LARGE).
+TraceLaunch resolve_trace(const TraceParams &p, bool any_hit, bool count, bool quad_built, uint32_t rows_wg_large = 256);
+// A persistent launch of a primary cast (launch_trace_persistent): `blocks` resident workgroups with lds_depth stack entries per lane.
+TraceLaunch resolve_persistent(const TraceParams &p, uint32_t lds_depth, uint32_t blocks, bool any_hit, bool count);
+// A record-driven cast (launch_source): persistent as above if blocks != 0, else the plain lane kernel with p.sparse_lanes; LANE,
+// TWO_LEVEL or LANE_PERSISTENT.  There is no counting variant.
+TraceLaunch resolve_source(const TraceParams &p, uint32_t lds_depth, uint32_t blocks, bool any_hit);
+// The name mrt_last_kernel_variant reports.  family == nullptr: the kernel's symbol as rocprofv3 prints it,
+// "trace_packet_rows_kernel<false, false, 2, 64, true>".  A record-driven cast: its family, source (a RaySrc) and, where the family
+// has two modes (with_mode), the mode: "trace_shadow_lane_kernel<3>", "trace_hemisphere_persistent_kernel<9, true, 8, false>".
+void format_variant(char *out, size_t n, const TraceVariant &v, const char *family = nullptr, int src = 0, bool with_mode = false);
 
 uint32_t tile_w_log2(const mrt_options &o);
 // Plans a cast.  May select (and reset) the grid state of the cast in `gs` (never for a shadow, reflection, hemisphere or bounce entry: those

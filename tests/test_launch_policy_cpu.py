@@ -1,6 +1,7 @@
 """The cast launch policy without a device: which kernel a cast gets and how it is launched (launch_policy.cpp), for a table of
 casts on both sides of every threshold -- counts, flags, scene layouts, options, entry points, the previous cast's detected
-width -- plus the grid kernel tuner over fifteen frames with fake timings, the per-grid state LRU and the detected width across
+width --, each with the instantiation its plan resolves to and the launch geometry (resolve_trace / resolve_persistent), a table of
+hand-made launches on both sides of every branch of the resolvers, plus the grid kernel tuner over fifteen frames with fake timings, the per-grid state LRU and the detected width across
 sequences of blocking, ASYNC, pipelined and submitted casts (csrc/host/launch_policy_test.cpp, which links launch_policy.cpp alone)."""
 import subprocess
 
