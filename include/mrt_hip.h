@@ -902,6 +902,88 @@ int mrt_light_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w
 		const void *d_hits, const mrt_surface64 *d_rows, const mrt_shade_light *lights, uint32_t n_lights,
 		const uint8_t *d_mask, const mrt_environment *env, const mrt_light_out *out, uint32_t flags);
 
+/* ---- the path tracer's per-pixel state: the rest of CPUPathTracer's loop body (src/modules/graphics/cpu_path_tracer.h:110-194)
+ * and the frame's last pass (:202-222) -- radiance accumulation, the throughput weights of PathTrace::sample_bounce
+ * (path_trace.h:213-246), Russian roulette, the `active` flag, tone mapping and gamma -- on the rows mrt_resolve_surfaces wrote
+ * and the direct light mrt_light_surfaces wrote with env == NULL.  Per bounce a renderer queues
+ *   cast -> resolve (d_rows, d_bounce_surface, d_out_hits) -> shadows -> light with env = NULL -> step -> bounce cast with d_select
+ * and reads back four bytes (d_active_count); after the last bounce, mrt_path_finish.  The panorama sky, textures, normal maps and
+ * the average over sample_index frames stay with the renderer. */
+
+/* PathState without its generator (the stream is a function of pixel, frame and bounce: mrt_cast_bounce); 32 bytes */
+typedef struct mrt_path_state {
+	float throughput[3];   uint32_t active;     /* 1: the pixel's path goes on; 0: it has ended */
+	float radiance[3];     uint32_t reserved;   /* written 0 by mrt_path_init, kept by mrt_path_step */
+} mrt_path_state;
+#define MRT_PATH_MAX_FRAME 999999u    /* PathState::init asserts frame < 1000000 */
+#define MRT_PATH_MAX_BOUNCES 32u      /* RayRenderer::set_max_bounces clamps to 32 */
+
+/* Writes {1, 1, 1, 1, 0, 0, 0, 0} to every entry.  d_state: device pointer.  Flags: MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing
+ * written.  MRT_ERR_INVALID for a null pointer or an unknown flag; MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_path_init(mrt_ctx *ctx, mrt_path_state *d_state, uint64_t count, uint32_t flags);
+
+typedef struct mrt_path_step_desc {
+	uint32_t frame;                 /* enters the seed, as mrt_bounce.frame; <= MRT_PATH_MAX_FRAME                         */
+	uint32_t bounce;                /* the loop's index, 0 = the primary hit; <= max_bounces                              */
+	uint32_t max_bounces;           /* <= MRT_PATH_MAX_BOUNCES; at bounce == max_bounces every path ends                   */
+	uint32_t reserved;              /* not read                                                                            */
+	const float *d_direct;          /* 4 floats per record as mrt_light_surfaces wrote them with env == NULL; rgb is read  */
+	mrt_path_state *d_state;        /* read and written in place                                                           */
+	const mrt_environment *env;     /* host pointer, required: the sky of a miss and the ambient term of bounce 0          */
+	uint8_t *d_out_select;          /* one byte per record, mrt_bounce.d_select's layout: 1 = the path goes on             */
+	uint8_t *d_out_lobe;            /* optional, one byte per record: MRT_LOBE_*                                           */
+	uint32_t *d_active_count;       /* optional, one word the caller zeroed: the step adds the number of entries left active */
+} mrt_path_step_desc;
+/* Advances every entry by one bounce.  hit, p, d of record i as mrt_resolve_surfaces takes them; emission, albedo, metallic,
+ * roughness, specular and n_dot_v from row i of d_rows; direct = d_direct[4i .. 4i + 2]; t = state.throughput, r = state.radiance.
+ * Plain fp32 operations in this order, one at a time, nothing contracted; a . b, max(x, 0), normalized() as for the lighting calls:
+ *   state.active == 0: select 0, lobe MRT_LOBE_NONE, the state is not written.
+ *   a miss: sky = the gradient mrt_light_surfaces writes for a miss, of d as given; r.c = r.c + t.c * sky.c; active = 0, select 0.
+ *   a hit: one_m = 1 - metallic; f0.c = ((0.04f * specular) * 2.0f) * one_m + albedo.c * metallic; diff.c = albedo.c * one_m;
+ *     r.c = r.c + t.c * emission.c; r.c = r.c + t.c * direct.c;
+ *     only when bounce == 0: r.c = r.c + ((t.c * diff.c) * ambient.c) * ambient_energy   (no hemisphere blend, unlike the light call);
+ *     bounce == max_bounces: active = 0, select 0.  Otherwise the sampler of mrt_cast_bounce runs on the same record with
+ *     {metallic, roughness} from the row and first_draw = 3 * bounce + max(0, bounce - 2): its p, d, faced n, the clamps m, ro, sp,
+ *     the stream (grid form: pixel y * grid_w + x of the whole grid; array form: the record's index), u0, u1, u2, the lobe, the half
+ *     vector h (specular), v, vh and dir, operation for operation.
+ *     ndl = n . dir; ndl <= 0: active = 0, select 0, lobe MRT_LOBE_NONE (the throughput is not touched).  Otherwise the weight w:
+ *       specular: ndh = max(n . h, 0); a = ro * ro; a2 = a * a; G = g1(n_dot_v) * g1(ndl) and F.c from f0.c and vh by the formulas of
+ *         the lighting calls; common = (G * vh) / (((n_dot_v * ndh) * sp) + 1e-7f); w.c = F.c * common.
+ *       diffuse: inv = 1.0f / (1.0f - sp); w.c = diff.c * inv.
+ *     t.c = t.c * w.c.  For bounce >= 2: surv = min(max(max(t.r, t.g), t.b), 0.95f) (max(a, b) = a < b ? b : a, min(a, b) = b < a ? b : a);
+ *       u3 = draw first_draw + 3 of the stream; u3 >= surv: active = 0, select 0 (the throughput keeps the multiplied value, as in
+ *       the reference); otherwise t.c = t.c * (1.0f / surv).
+ *     An entry still active: select 1 and its lobe.
+ * The caller passes the records that went through the resolve's d_out_hits (the shading normal) to this call and to the
+ * mrt_cast_bounce that follows with d_select = d_out_select, d_surface = the resolve's d_bounce_surface and the same frame and
+ * first_draw: the two then agree entry for entry on the lobe and on which entries have a ray.  The array form draws by record
+ * index, as mrt_cast_bounce does: a band of a later bounce passed as an array does not draw what the whole frame draws.
+ * d_rays / d_hits as for mrt_resolve_surfaces (MRT_FLAG_HOST_LAYOUT: mrt_host_ray60 + mrt_host_hit44).  No scene is required and
+ * nothing is walked.  Flags: MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID, before any
+ * device work and in this order, for: a null required pointer (rays, hits, rows, desc, d_direct, d_state, env, d_out_select); an
+ * unknown flag; bounce > max_bounces; frame > MRT_PATH_MAX_FRAME or max_bounces > MRT_PATH_MAX_BOUNCES; an environment float that is
+ * not finite.  Then MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_path_step(mrt_ctx *ctx, const void *d_rays, const void *d_hits, const mrt_surface64 *d_rows, uint64_t count,
+		const mrt_path_step_desc *desc, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (every per-record array indexed by the record within the band):
+ * the primary rays are regenerated in the kernel and the stream is seeded from the pixel's index in the whole grid, so a band
+ * steps what the whole frame steps.  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_path_grid_step(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const void *d_hits, const mrt_surface64 *d_rows, const mrt_path_step_desc *desc, uint32_t flags);
+/* The frame's last pass: d_rgba[4i ..] = {g(tm(r.r)), g(tm(r.g)), g(tm(r.b)), 1} with r = d_state[i].radiance, tm = tonemap_rgb
+ * (shade_pass.h:404-447) in the reference's operand order, fp32, nothing contracted:
+ *   0 linear: c.   1 Reinhard: c / (c + 1.0f).
+ *   2 Hable: hp(c) / hp(11.2f), hp(x) = ((x * (0.15f * x + CB) + DE) / (x * (0.15f * x + 0.50f) + DF)) - EF with the float
+ *     constants CB = 0.10f * 0.50f, DE = 0.20f * 0.02f, DF = 0.20f * 0.30f, EF = 0.02f / 0.30f; hp(11.2f) once per call on the host.
+ *   3 ACES: m = (c * (2.51f * c + 0.03f)) / (c * (2.43f * c + 0.59f) + 0.14f); m < 0 ? 0 : (m > 1 ? 1 : m).
+ *   4 AgX: x = c < 0 ? 0 : c; x2 = x * x; m = x2 / ((x2 + 0.09f * x) + 0.0009f); m > 1 ? 1 : m.
+ * and g(c) = pow01(c < 0 ? 0 : c, 1.0f / 2.2f).  pow01's arithmetic runs unchanged for every finite base >= 0: for b > 1 the
+ * exponent k of x = m * 2^k is positive and y > 0; with e = 1 / 2.2f it is within 1 fp32 ulp of the correctly rounded power over
+ * the whole float range.  Flags: MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID for a null
+ * pointer, an unknown flag, tonemap_mode > 4 (in this order); MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_path_finish(mrt_ctx *ctx, const mrt_path_state *d_state, uint64_t count, uint32_t tonemap_mode, float *d_rgba,
+		uint32_t flags);
+
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to
  * tokens written by a cast with MRT_FLAG_TOKEN_OUT: mrt_hit32 records (mrt_host_hit44 with

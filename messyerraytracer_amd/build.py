@@ -21,10 +21,11 @@ INSTANCE_MATH_TEST = os.path.join(HERE, "instance_math_test")
 SHADE_DATA_TEST = os.path.join(HERE, "shade_data_test")
 LANE_MAP_TEST = os.path.join(HERE, "lane_map_test")
 LIGHT_DATA_TEST = os.path.join(HERE, "light_data_test")
+PATH_DATA_TEST = os.path.join(HERE, "path_data_test")
 
 SOURCES = ["kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip", "device_build.hip", "refit.hip",
-           "tlas_device.hip", "surface.hip", "lighting.hip", "host/shade_data.cpp", "host/light_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
-HEADERS = ["mrt_internal.h", "instance_math.h", "lane_map.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "source_common.h", "shadow_kernel.h", "reflection_kernel.h", "hemisphere_kernel.h", "bounce_kernel.h", "surface_kernel.h", "shade_data.h", "light_kernel.h", "lighting.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
+           "tlas_device.hip", "surface.hip", "lighting.hip", "path.hip", "host/shade_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
+HEADERS = ["mrt_internal.h", "instance_math.h", "lane_map.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "source_common.h", "shadow_kernel.h", "reflection_kernel.h", "hemisphere_kernel.h", "bounce_kernel.h", "surface_kernel.h", "shade_data.h", "light_kernel.h", "lighting.h", "path_kernel.h", "path_frame_kernel.h", "path.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
            "host/host_types.hpp", "host/cpu_backend.hpp", "host/ray_tracer_server.hpp", "host/record_policy_test.h"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
@@ -216,6 +217,19 @@ def build_light_data_test(force: bool = False) -> str:
     return LIGHT_DATA_TEST
 
 
+def build_path_data_test(force: bool = False) -> str:
+    """C++ test driver for the refusals of the path state calls, the generator's jump, the kernel's copy of a descriptor, the tone
+    mappers and the gamma (host/path_data.cpp, path.h and lighting.h alone: host code, no device, no library)."""
+    srcs = [os.path.join(CSRC, "host", "path_data_test.cpp"), os.path.join(CSRC, "host", "path_data.cpp")]
+    deps = srcs + [os.path.join(CSRC, "path.h"), os.path.join(CSRC, "lighting.h"), os.path.join(CSRC, "../../include/mrt_hip.h")]
+    if force or _stale(PATH_DATA_TEST, deps):
+        cmd = [_hipcc(), "-x", "c++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall"] + srcs + ["-o", PATH_DATA_TEST]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
+        if r.returncode != 0:
+            raise RuntimeError("path data test build failed:\n" + r.stdout + r.stderr)
+    return PATH_DATA_TEST
+
+
 def build_lane_map_test(force: bool = False, sanitize: bool = False) -> str:
     """C++ test driver for the lane map (lane_map.h compiled for the CPU alone: no device, no library); sanitize = a second binary
     under AddressSanitizer and UndefinedBehaviorSanitizer."""
@@ -244,4 +258,5 @@ if __name__ == "__main__":
     print(build_instance_math_test(force=True))
     print(build_shade_data_test(force=True))
     print(build_light_data_test(force=True))
+    print(build_path_data_test(force=True))
     print(build_lane_map_test(force=True))

@@ -33,7 +33,8 @@ SYMBOLS = [
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
     "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_cast_bounce", "mrt_cast_grid_bounce",
     "mrt_upload_shade_data", "mrt_clear_shade_data", "mrt_resolve_surfaces", "mrt_resolve_grid_surfaces",
-    "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces", "mrt_expand_tokens",
+    "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
+    "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
     "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
     "mrt_group_create", "mrt_group_destroy", "mrt_group_size", "mrt_group_context", "mrt_group_last_error", "mrt_group_row_block",
@@ -93,7 +94,15 @@ class LightOut(C.Structure):
     _fields_ = [("d_rgba", C.c_void_p)]
 
 
+class PathStepDesc(C.Structure):
+    """mrt_path_step_desc"""
+    _fields_ = [("frame", C.c_uint32), ("bounce", C.c_uint32), ("max_bounces", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_direct", C.c_void_p), ("d_state", C.c_void_p), ("env", C.c_void_p), ("d_out_select", C.c_void_p),
+                ("d_out_lobe", C.c_void_p), ("d_active_count", C.c_void_p)]
+
+
 SHADE_ARRAYS_ON_DEVICE = 1
+STRUCT_PATH_STATE, STRUCT_PATH_STEP_DESC = 15, 16   # mrt_struct_size indices (14: not a struct)
 STRUCT_SHADE_LIGHT, STRUCT_ENVIRONMENT, STRUCT_LIGHT_OUT = 11, 12, 13   # mrt_struct_size indices
 STRUCT_MATERIAL, STRUCT_SHADE_DATA, STRUCT_SURFACE64, STRUCT_SURFACE_OUT = 6, 7, 8, 9   # mrt_struct_size indices
 
@@ -226,6 +235,11 @@ def load():
                                      C.c_void_p, C.POINTER(LightOut), C.c_uint32]
     L.mrt_light_grid_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(LightOut), C.c_uint32]
+    L.mrt_path_init.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+    L.mrt_path_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PathStepDesc), C.c_uint32]
+    L.mrt_path_grid_step.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.POINTER(PathStepDesc), C.c_uint32]
+    L.mrt_path_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]
     L.mrt_cast_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mrt_expand_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
     L.mrt_expand_grid_tokens.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -805,6 +819,39 @@ class Context:
         out = LightOut(_ptr(d_rgba).value)
         self._chk(self.L.mrt_light_grid_surfaces(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _ptr(d_rows), lp,
                                                  lights.shape[0], _optr(d_mask), ep, C.byref(out), flags))
+
+    def path_init(self, d_state, count, flags=0):
+        """Every T.PATH_STATE entry to throughput 1, active, radiance 0."""
+        self._chk(self.L.mrt_path_init(self.h, _ptr(d_state), count, flags))
+
+    @staticmethod
+    def _path_desc(frame, bounce, max_bounces, d_direct, d_state, env, d_out_select, d_out_lobe, d_active_count):
+        env = np.ascontiguousarray(env, dtype=T.ENVIRONMENT).reshape(1)
+        desc = PathStepDesc(frame, bounce, max_bounces, 0, _ptr(d_direct).value, _ptr(d_state).value, _np(env).value,
+                            _ptr(d_out_select).value, _optr(d_out_lobe).value if d_out_lobe is not None else None,
+                            _optr(d_active_count).value if d_active_count is not None else None)
+        return desc, env
+
+    def path_step(self, d_rays, d_hits, d_rows, count, d_direct, d_state, env, d_out_select, frame=0, bounce=0, max_bounces=4,
+                  d_out_lobe=None, d_active_count=None, flags=0):
+        """One bounce of the path tracer's per-pixel state for the records of a cast (device pointers / tensors: mrt_ray32 + mrt_hit32,
+        or mrt_host_ray60 + mrt_host_hit44 with FLAG_HOST_LAYOUT; the records with the shading normal, resolve_surfaces' d_out_hits):
+        radiance and throughput of d_state advanced in place from d_rows and d_direct (light_surfaces with env=None), Russian roulette,
+        d_out_select for the cast_bounce that follows.  env: T.ENVIRONMENT row; d_active_count: optional zeroed word."""
+        desc, env = self._path_desc(frame, bounce, max_bounces, d_direct, d_state, env, d_out_select, d_out_lobe, d_active_count)
+        self._chk(self.L.mrt_path_step(self.h, _ptr(d_rays), _ptr(d_hits), _ptr(d_rows), count, C.byref(desc), flags))
+
+    def path_grid_step(self, cam, grid_w, grid_h, d_hits, d_rows, d_direct, d_state, env, d_out_select, frame=0, bounce=0, max_bounces=4,
+                       d_out_lobe=None, d_active_count=None, y0=0, y1=None, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (every per-record array indexed by the record within the band)."""
+        y1 = grid_h if y1 is None else y1
+        desc, env = self._path_desc(frame, bounce, max_bounces, d_direct, d_state, env, d_out_select, d_out_lobe, d_active_count)
+        self._chk(self.L.mrt_path_grid_step(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _ptr(d_rows), C.byref(desc), flags))
+
+    def path_finish(self, d_state, count, d_rgba, tonemap_mode=0, flags=0):
+        """The frame's last pass: tone mapping (0 linear, 1 Reinhard, 2 Hable, 3 ACES, 4 AgX) and gamma 2.2 of every entry's radiance,
+        4 floats per entry with alpha 1."""
+        self._chk(self.L.mrt_path_finish(self.h, _ptr(d_state), count, tonemap_mode, _ptr(d_rgba), flags))
 
     def expand_tokens(self, d_rays, d_tokens, d_hits, count, flags=0, stream=None):
         """Device pointers; enqueued on `stream` (raw hipStream_t) or the context's stream, not waited for."""

@@ -160,6 +160,8 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 11: return (uint32_t)sizeof(mrt_shade_light); // (10: not a struct)
 		case 12: return (uint32_t)sizeof(mrt_environment);
 		case 13: return (uint32_t)sizeof(mrt_light_out);
+		case 15: return (uint32_t)sizeof(mrt_path_state); // (14: not a struct)
+		case 16: return (uint32_t)sizeof(mrt_path_step_desc);
 		default: return 0u;
 	}
 }

@@ -18,6 +18,7 @@
 #include "launch_policy.h"
 #include "shade_data.h"
 #include "lighting.h"
+#include "path.h"
 #include "lane_map.h"
 
 namespace mrt {
@@ -820,6 +821,7 @@ template hipError_t launch_source<ReflectParams>(const TraceParams &, const void
 template hipError_t launch_source<HemiParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<BounceParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 
+#include "path_frame_kernel.h"
 #include "surface_kernel.h"
 
 // src = a SurfaceSrc; anything else is hipErrorInvalidValue
@@ -847,6 +849,39 @@ hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int
 	else if (src == SURF_HOST) hipLaunchKernelGGL(light_surfaces_kernel<SURF_HOST>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
 	else if (src == SURF_GRID) hipLaunchKernelGGL(light_surfaces_kernel<SURF_GRID>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
 	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+#include "path_kernel.h"
+
+hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream)
+{
+	if (count == 0) return hipSuccess;
+	const uint64_t blocks = (count + MRT_WG - 1) / MRT_WG;
+	if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(path_init_kernel, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, state, count);
+	return hipGetLastError();
+}
+
+// src = a SurfaceSrc; anything else is hipErrorInvalidValue
+hipError_t launch_path_step(const TraceParams &p, const PathParams &s, int src, hipStream_t stream)
+{
+	if (p.count == 0) return hipSuccess;
+	const uint64_t blocks = (p.count + MRT_WG - 1) / MRT_WG;
+	if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	if (src == SURF_RAY32) hipLaunchKernelGGL(path_step_kernel<SURF_RAY32>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else if (src == SURF_HOST) hipLaunchKernelGGL(path_step_kernel<SURF_HOST>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else if (src == SURF_GRID) hipLaunchKernelGGL(path_step_kernel<SURF_GRID>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+hipError_t launch_path_finish(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba, hipStream_t stream)
+{
+	if (count == 0) return hipSuccess;
+	const uint64_t blocks = (count + MRT_WG - 1) / MRT_WG;
+	if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(path_finish_kernel, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, state, count, mode, white, rgba);
 	return hipGetLastError();
 }
 

@@ -28,6 +28,11 @@ hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s,
 // direct light on resolved surfaces (light_kernel.h): src = a SurfaceSrc
 struct LightParams;
 hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int src, hipStream_t stream);
+// the path tracer's per-pixel state (path_kernel.h): src = a SurfaceSrc; white = Hable's white value for tone-map mode 2
+struct PathParams;
+hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream);
+hipError_t launch_path_step(const TraceParams &p, const PathParams &s, int src, hipStream_t stream);
+hipError_t launch_path_finish(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba, hipStream_t stream);
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream);
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);
 hipError_t launch_collapse8(const DevNode *nodes, uint32_t n_nodes, Dev8Node *nodes8, float *leaf_box, uint32_t *bad, hipStream_t stream);

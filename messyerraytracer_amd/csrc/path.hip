@@ -1,0 +1,83 @@
+// path.hip — the path tracer's per-pixel state on the device (include/mrt_hip.h: mrt_path_init, mrt_path_step, mrt_path_grid_step,
+// mrt_path_finish).  The refusals and the kernel's copy of a descriptor are host/path_data.cpp; the kernels are path_kernel.h
+// (kernels.hip).
+#include <cstring>
+#include <hip/hip_runtime.h>
+#include "mrt_context.h"
+#include "path.h"
+
+namespace {
+
+// Both steps after their own checks: p holds the incoming rays (or the grid) and the count; pixel0 = the pixel index of record 0.
+int step(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, const mrt_surface64 *d_rows, uint32_t pixel0,
+		const mrt_path_step_desc *desc, uint32_t flags)
+{
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (p.count == 0) return MRT_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	mrt::PathParams s;
+	std::memset(&s, 0, sizeof(s));
+	s.records = d_hits; s.rows = d_rows;
+	mrt::fill_path_params(desc, pixel0, s);
+	HIP_TRY(ctx, mrt::launch_path_step(p, s, src, ctx->stream));
+	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return MRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int mrt_path_init(mrt_ctx *ctx, mrt_path_state *d_state, uint64_t count, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (const char *why = mrt::path_frame_invalid(d_state, nullptr, false, flags, 0u)) return fail(ctx, MRT_ERR_INVALID, why);
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (count == 0) return MRT_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, mrt::launch_path_init(d_state, count, ctx->stream));
+	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return MRT_OK;
+}
+
+int mrt_path_step(mrt_ctx *ctx, const void *d_rays, const void *d_hits, const mrt_surface64 *d_rows, uint64_t count,
+		const mrt_path_step_desc *desc, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (const char *why = mrt::path_step_invalid(d_rays, d_hits, d_rows, desc, flags, MRT_FLAG_HOST_LAYOUT | MRT_FLAG_ASYNC))
+		return fail(ctx, MRT_ERR_INVALID, why);
+	mrt::TraceParams p;
+	std::memset(&p, 0, sizeof(p)); // (no scene: nothing is walked)
+	p.rays = d_rays; p.count = count;
+	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
+	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
+	return step(ctx, host ? mrt::SURF_HOST : mrt::SURF_RAY32, p, d_hits, d_rows, 0u, desc, flags);
+}
+
+int mrt_path_grid_step(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const void *d_hits, const mrt_surface64 *d_rows, const mrt_path_step_desc *desc, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (const char *why = mrt::path_step_invalid(cam, d_hits, d_rows, desc, flags, MRT_FLAG_ASYNC)) return fail(ctx, MRT_ERR_INVALID, why);
+	mrt::TraceParams p;
+	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
+	if (rc) return rc;
+	return step(ctx, mrt::SURF_GRID, p, d_hits, d_rows, y0 * grid_w, desc, flags);
+}
+
+int mrt_path_finish(mrt_ctx *ctx, const mrt_path_state *d_state, uint64_t count, uint32_t tonemap_mode, float *d_rgba, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (const char *why = mrt::path_frame_invalid(d_state, d_rgba, true, flags, tonemap_mode)) return fail(ctx, MRT_ERR_INVALID, why);
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (count == 0) return MRT_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, mrt::launch_path_finish(d_state, count, tonemap_mode, mrt::hable_partial(11.2f), d_rgba, ctx->stream));
+	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return MRT_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,30 @@
+// path_frame_kernel.h — the two small kernels around a path-traced frame: mrt_path_init's and mrt_path_finish's (the frame's last pass,
+// src/modules/graphics/cpu_path_tracer.h:202-222: tone mapping and gamma; path.h holds both, shared with the host).  Included by
+// kernels.hip inside namespace mrt, ahead of surface_kernel.h: plain kernels are laid out in source order, and the padding that ends
+// the section then stays behind the kernel that had it, so that tools/isa_symbols.py shows every earlier kernel unchanged.  One thread
+// per entry, 16-byte loads and stores; pow01 is fp64.
+#pragma once
+
+__global__ __launch_bounds__(MRT_WG) void path_init_kernel(mrt_path_state *state, uint64_t count)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * MRT_WG + threadIdx.x;
+	if (i >= count) return;
+	float4 *st = reinterpret_cast<float4 *>(state) + i * 2u;
+	float4 a, b;
+	a.x = 1.0f; a.y = 1.0f; a.z = 1.0f; a.w = __uint_as_float(1u);
+	b.x = 0.0f; b.y = 0.0f; b.z = 0.0f; b.w = __uint_as_float(0u);
+	st[0] = a; st[1] = b;
+}
+
+__global__ __launch_bounds__(MRT_WG) void path_finish_kernel(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * MRT_WG + threadIdx.x;
+	if (i >= count) return;
+	const float4 r = (reinterpret_cast<const float4 *>(state) + i * 2u)[1];
+	float4 o;
+	o.x = path_gamma(tonemap(r.x, mode, white));
+	o.y = path_gamma(tonemap(r.y, mode, white));
+	o.z = path_gamma(tonemap(r.z, mode, white));
+	o.w = 1.0f;
+	reinterpret_cast<float4 *>(rgba)[i] = o;
+}

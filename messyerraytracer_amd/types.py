@@ -45,6 +45,11 @@ ENVIRONMENT = np.dtype([("sky_zenith", "<f4", 3), ("sky_horizon", "<f4", 3), ("s
                         ("ambient_energy", "<f4"), ("reserved", "<u4", 3)])  # mrt_environment
 assert SHADE_LIGHT.itemsize == 64 and ENVIRONMENT.itemsize == 64
 
+# the path tracer's per-pixel state (mrt_path_init, mrt_path_step, mrt_path_finish)
+PATH_STATE = np.dtype([("throughput", "<f4", 3), ("active", "<u4"), ("radiance", "<f4", 3), ("reserved", "<u4")])  # mrt_path_state
+PATH_MAX_FRAME, PATH_MAX_BOUNCES = 999999, 32
+assert PATH_STATE.itemsize == 32
+
 # rows of the device layouts (csrc/mrt_internal.h), as mrt_debug_snapshot and the host preparations return them
 TRI_HOT = np.dtype([("v0", "<f4", 3), ("id", "<u4"), ("e1", "<f4", 3), ("layers", "<u4"), ("e2", "<f4", 3), ("flags", "<u4")])
 TRI_COLD = np.dtype([("normal", "<f4", 3), ("pad", "<u4")])
