@@ -272,8 +272,9 @@ const char *mrt_status_string(int status);
 uint32_t mrt_version(void);
 /* sizeof() of the boundary's structs as this library was compiled, for bindings in other languages to check
  * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light, 6 mrt_material,
- * 7 mrt_shade_data, 8 mrt_surface64, 9 mrt_surface_out, 11 mrt_shade_light, 12 mrt_environment, 13 mrt_light_out (0 for
- * anything else). */
+ * 7 mrt_shade_data, 8 mrt_surface64, 9 mrt_surface_out, 11 mrt_shade_light, 12 mrt_environment, 13 mrt_light_out,
+ * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set (0 for anything
+ * else). */
 uint32_t mrt_struct_size(uint32_t which);
 /* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream). */
 int mrt_set_stream(mrt_ctx *ctx, void *hip_stream);
@@ -730,15 +731,17 @@ int mrt_cast_grid_bounce(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, u
 /* ---- shading surfaces from resident hit records: the reference's SceneShadeData (src/api/scene_shade_data.h) held on
  * the device, and ShadePass::extract_surface (src/modules/graphics/shade_pass.h:509-587) run per hit record as one kernel.
  * What the casts above leave to the renderer -- metallic and roughness for mrt_bounce.d_surface, the shading (smooth)
- * normal, albedo and emission for weights and throughput -- without downloading the records.  Texture sampling, normal-map
- * perturbation, tangents, lighting and throughput stay with the renderer: it gets the UV and the material index. */
+ * normal, albedo and emission for weights and throughput -- without downloading the records.  With a texture set resident
+ * (mrt_upload_textures, below) the resolve also samples albedo textures and normal maps: all of extract_surface but F0 and
+ * the diffuse albedo.  Lighting and throughput are the calls further down. */
 
 /* MaterialData (src/api/material_data.h) without its images; 48 bytes */
 typedef struct mrt_material {
 	float albedo[3];   float metallic;
 	float roughness;   float specular;   float emission[3];
 	float emission_energy;
-	uint32_t flags;    /* bit 0 has_albedo_texture, bit 1 has_normal_texture: carried, not used */
+	uint32_t flags;    /* bit 0 has_albedo_texture, bit 1 has_normal_texture: carried, not used (informational: what is sampled is
+	                    * decided by the material's mrt_material_textures binding, mrt_upload_textures) */
 	uint32_t reserved;
 } mrt_material;
 
@@ -806,6 +809,76 @@ int mrt_resolve_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_hits, u
  * whole frame resolves.  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
 int mrt_resolve_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h,
 		uint32_t y0, uint32_t y1, const void *d_hits, const mrt_surface_out *out, uint32_t flags);
+
+/* ---- resident textures: the Images of MaterialData (albedo_texture, normal_texture; src/api/material_data.h), its
+ * normal_scale and the TriangleTangents of SceneShadeData (src/core/triangle_tangents.h) held on the device, so that the two
+ * resolves above run TextureSampler::sample_bilinear (src/modules/graphics/texture_sampler.h:45-88) and perturb_normal
+ * (shade_pass.h:110-162) themselves. */
+#define MRT_TEXTURE_MAX_DIM 16384u        /* Godot's Image limit: (float)width is exact and every texel index below 2^28 */
+#define MRT_NO_TEXTURE 0xFFFFFFFFu
+enum { MRT_TEXEL_RGBA8 = 0, MRT_TEXEL_RGBA32F = 1 };
+enum { MRT_TEXTURES_ON_DEVICE = 1u << 0 };   /* every mrt_texture.pixels and tangents12 are device pointers */
+/* One image: rows tightly packed, row 0 first -- texel (x, y), what Image::get_pixel(x, y) addresses, is entry y * width + x.
+ * MRT_TEXEL_RGBA8: 4 bytes a texel, a channel's value is (float)byte / 255.0f (one fp32 division: the definition);
+ * MRT_TEXEL_RGBA32F: 4 floats a texel, used as given.  24 bytes. */
+typedef struct mrt_texture {
+	uint32_t width, height;   /* 1 .. MRT_TEXTURE_MAX_DIM */
+	uint32_t format;          /* MRT_TEXEL_* */
+	uint32_t reserved;
+	const void *pixels;
+} mrt_texture;
+/* What material id m samples: entry m of the binding list.  16 bytes. */
+typedef struct mrt_material_textures {
+	uint32_t albedo_texture, normal_texture;   /* an index into the texture list, or MRT_NO_TEXTURE */
+	float normal_scale;                        /* MaterialData::normal_scale (finite) */
+	uint32_t reserved;
+} mrt_material_textures;
+typedef struct mrt_texture_set {
+	uint32_t struct_size, flags;        /* flags: MRT_TEXTURES_* */
+	uint32_t n_textures, n_bindings;
+	uint32_t n_tangent_tris, reserved;
+	const mrt_texture *textures;                /* host array, n_textures */
+	const mrt_material_textures *bindings;      /* host array, n_bindings: indexed by the material id */
+	const float *tangents12;   /* optional: n_tangent_tris x {t0 xyz, t1 xyz, t2 xyz, sign0, sign1, sign2}: TriangleTangents field
+	                            * for field, indexed by prim_id */
+} mrt_texture_set;
+/* Makes a texture set resident.  Like the shade data it belongs to the context: it survives scene uploads, refits and
+ * instance updates, is replaced by the next upload and released by mrt_clear_textures or mrt_destroy.  On the device: one
+ * pooled texel buffer (every image starts on a 16-byte boundary), a table of one 16-byte descriptor per texture {offset in
+ * 16-byte units, width, height, format}, the bindings as given (16 bytes each) and the tangents as given (48-byte rows).
+ * Waits for the context's stream, copies on it and waits again; nothing is resident until everything is.  MRT_ERR_INVALID,
+ * checked in this order before any device work and with the resident set unchanged: a null context or descriptor; a wrong
+ * struct_size; an unknown flag; a count > 0 with a null array (textures, bindings, tangents12 with n_tangent_tris > 0); per
+ * texture in list order a width or height of 0 or above MRT_TEXTURE_MAX_DIM, an unknown format, null pixels; per binding in
+ * list order an index that is neither MRT_NO_TEXTURE nor < n_textures, a normal_scale that is not finite; a pooled size of
+ * 2^32 16-byte units or more (what a descriptor's offset can address).  MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_upload_textures(mrt_ctx *ctx, const mrt_texture_set *set);
+/* Releases the resident texture set (none resident: MRT_OK).  Waits for the context's stream.  MRT_ERR_PENDING as above. */
+int mrt_clear_textures(mrt_ctx *ctx);
+/* With a texture set resident, mrt_resolve_surfaces and mrt_resolve_grid_surfaces compute extract_surface in full (another
+ * kernel; with none resident exactly the kernel and the results stated above).  Plain fp32, one operation at a time, nothing
+ * contracted, with in_range, w, n, vd, the material and uv as above and uv taken first:
+ *   bound = ids resident, in_range, id < n_materials and id < n_bindings; b = bindings[id].
+ *   uv_ok = uvs resident, in_range, and uv.x and uv.y both finite.  A record whose interpolated UV is not finite (the
+ *       reference only asserts there) samples neither texture: unmultiplied albedo, the smooth normal, no texel read.
+ *   sample(tex, u, v) (sample_bilinear): u = u - floorf(u), v likewise; fx = u * (float)width - 0.5f; x0 = (int)floorf(fx);
+ *       sx = fx - (float)x0; x1 = x0 + 1, then x1 = x1 >= width ? x1 - width : x1 and x0 = x0 < 0 ? x0 + width : x0 (the
+ *       reference's wrap on the only values that occur: x0 in -1 .. width - 1); the same for y with height; the texels
+ *       c00 = (x0, y0), c10 = (x1, y0), c01 = (x0, y1), c11 = (x1, y1); lerp(a, b, t) = a + (b - a) * t per channel;
+ *       top = lerp(c00, c10, sx), bot = lerp(c01, c11, sx), the sample = lerp(top, bot, sy).
+ *   normal map (perturb_normal), when bound, b.normal_texture != MRT_NO_TEXTURE, tangents resident, prim_id < n_tangent_tris,
+ *       any of the row's three signs != 0 and uv_ok -- with N = n:
+ *       T.c = (t0.c * w + t1.c * u) + t2.c * v; l2 = (Tx*Tx + Ty*Ty) + Tz*Tz; T = (1, 0, 0) if l2 < 1e-8f, else T.c / sqrt(l2);
+ *       s = (sign0 * w + sign1 * u) + sign2 * v; bsign = s >= 0 ? 1 : -1;
+ *       k = (Nx*Tx + Ny*Ty) + Nz*Tz; T = normalized(T - N * k);
+ *       B = (Ny*Tz - Nz*Ty, Nz*Tx - Nx*Tz, Nx*Ty - Ny*Tx) * bsign;
+ *       c = sample(b.normal_texture, uv); ts.c = c.c * 2 - 1; ts.x and ts.y then multiplied by b.normal_scale;
+ *       P.c = (T.c * ts.x + B.c * ts.y) + N.c * ts.z; l2 = (Px*Px + Py*Py) + Pz*Pz; n = N if l2 < 1e-8f, else P.c / sqrt(l2).
+ *       n_dot_v is taken from this n; it is the row's normal and the normal d_out_hits carries.
+ *   albedo texture, when bound, b.albedo_texture != MRT_NO_TEXTURE and uv_ok: albedo.c = albedo.c * sample(...).c for r, g, b
+ *       (no sRGB step, as in the reference).
+ * Misses and ids out of range resolve exactly as above; where no binding applies the row, the pair and the record equal the
+ * untextured resolve's byte for byte. */
 
 /* ---- direct light on resolved surfaces: ShadePass::cook_torrance_multi_light (src/modules/graphics/shade_pass.h:597-657),
  * the loop shade_material runs for RayRenderer's frame and PathTrace::compute_direct_light for next-event estimation, and the

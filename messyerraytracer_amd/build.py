@@ -22,10 +22,11 @@ SHADE_DATA_TEST = os.path.join(HERE, "shade_data_test")
 LANE_MAP_TEST = os.path.join(HERE, "lane_map_test")
 LIGHT_DATA_TEST = os.path.join(HERE, "light_data_test")
 PATH_DATA_TEST = os.path.join(HERE, "path_data_test")
+TEXTURE_DATA_TEST = os.path.join(HERE, "texture_data_test")
 
 SOURCES = ["kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip", "device_build.hip", "refit.hip",
-           "tlas_device.hip", "surface.hip", "lighting.hip", "path.hip", "host/shade_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
-HEADERS = ["mrt_internal.h", "instance_math.h", "lane_map.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "source_common.h", "shadow_kernel.h", "reflection_kernel.h", "hemisphere_kernel.h", "bounce_kernel.h", "surface_kernel.h", "shade_data.h", "light_kernel.h", "lighting.h", "path_kernel.h", "path_frame_kernel.h", "path.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
+           "tlas_device.hip", "surface.hip", "texture.hip", "lighting.hip", "path.hip", "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
+HEADERS = ["mrt_internal.h", "instance_math.h", "lane_map.h", "mrt_context.h", "launch_policy.h", "packet_kernel.h", "packet_asm_kernel.h", "packet_rows_kernel.h", "packet_quad_kernel.h", "two_level_kernel.h", "lane_persistent_kernel.h", "source_common.h", "shadow_kernel.h", "reflection_kernel.h", "hemisphere_kernel.h", "bounce_kernel.h", "surface_kernel.h", "surface_tex_kernel.h", "shade_data.h", "texture.h", "light_kernel.h", "lighting.h", "path_kernel.h", "path_frame_kernel.h", "path.h", "lane_walk.inc", "two_level_walk.inc", "persistent_walk.inc", "../../include/mrt_hip.h", "host/gpu_ray_caster.hpp", "host/ray_dispatcher.hpp",
            "host/host_types.hpp", "host/cpu_backend.hpp", "host/ray_tracer_server.hpp", "host/record_policy_test.h"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
@@ -230,6 +231,19 @@ def build_path_data_test(force: bool = False) -> str:
     return PATH_DATA_TEST
 
 
+def build_texture_data_test(force: bool = False) -> str:
+    """C++ test driver for the refusals of a texture set and the layout of its texel pool (host/texture_data.cpp and texture.h alone:
+    host code, no device, no library)."""
+    srcs = [os.path.join(CSRC, "host", "texture_data_test.cpp"), os.path.join(CSRC, "host", "texture_data.cpp")]
+    deps = srcs + [os.path.join(CSRC, "texture.h"), os.path.join(CSRC, "../../include/mrt_hip.h")]
+    if force or _stale(TEXTURE_DATA_TEST, deps):
+        cmd = [_hipcc(), "-x", "c++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall"] + srcs + ["-o", TEXTURE_DATA_TEST]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
+        if r.returncode != 0:
+            raise RuntimeError("texture data test build failed:\n" + r.stdout + r.stderr)
+    return TEXTURE_DATA_TEST
+
+
 def build_lane_map_test(force: bool = False, sanitize: bool = False) -> str:
     """C++ test driver for the lane map (lane_map.h compiled for the CPU alone: no device, no library); sanitize = a second binary
     under AddressSanitizer and UndefinedBehaviorSanitizer."""
@@ -259,4 +273,5 @@ if __name__ == "__main__":
     print(build_shade_data_test(force=True))
     print(build_light_data_test(force=True))
     print(build_path_data_test(force=True))
+    print(build_texture_data_test(force=True))
     print(build_lane_map_test(force=True))

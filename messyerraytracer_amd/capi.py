@@ -33,6 +33,7 @@ SYMBOLS = [
     "mrt_camera_look", "mrt_camera_perspective", "mrt_camera_orthographic", "mrt_generate_grid", "mrt_cast_grid", "mrt_cast_tiled",
     "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_cast_bounce", "mrt_cast_grid_bounce",
     "mrt_upload_shade_data", "mrt_clear_shade_data", "mrt_resolve_surfaces", "mrt_resolve_grid_surfaces",
+    "mrt_upload_textures", "mrt_clear_textures",
     "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
     "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
@@ -89,6 +90,18 @@ class SurfaceOut(C.Structure):
     _fields_ = [("d_rows", C.c_void_p), ("d_bounce_surface", C.c_void_p), ("d_out_hits", C.c_void_p)]
 
 
+class Texture(C.Structure):
+    """mrt_texture"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_void_p)]
+
+
+class TextureSet(C.Structure):
+    """mrt_texture_set"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_textures", C.c_uint32), ("n_bindings", C.c_uint32),
+                ("n_tangent_tris", C.c_uint32), ("reserved", C.c_uint32), ("textures", C.c_void_p), ("bindings", C.c_void_p),
+                ("tangents12", C.c_void_p)]
+
+
 class LightOut(C.Structure):
     """mrt_light_out"""
     _fields_ = [("d_rgba", C.c_void_p)]
@@ -102,6 +115,9 @@ class PathStepDesc(C.Structure):
 
 
 SHADE_ARRAYS_ON_DEVICE = 1
+TEXTURES_ON_DEVICE = 1
+TEXEL_RGBA8, TEXEL_RGBA32F = 0, 1
+STRUCT_TEXTURE, STRUCT_MATERIAL_TEXTURES, STRUCT_TEXTURE_SET = 18, 19, 20   # mrt_struct_size indices (17: not a struct)
 STRUCT_PATH_STATE, STRUCT_PATH_STEP_DESC = 15, 16   # mrt_struct_size indices (14: not a struct)
 STRUCT_SHADE_LIGHT, STRUCT_ENVIRONMENT, STRUCT_LIGHT_OUT = 11, 12, 13   # mrt_struct_size indices
 STRUCT_MATERIAL, STRUCT_SHADE_DATA, STRUCT_SURFACE64, STRUCT_SURFACE_OUT = 6, 7, 8, 9   # mrt_struct_size indices
@@ -227,6 +243,8 @@ def load():
                                        C.POINTER(Bounce), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.mrt_upload_shade_data.argtypes = [C.c_void_p, C.POINTER(ShadeData)]
     L.mrt_clear_shade_data.argtypes = [C.c_void_p]
+    L.mrt_upload_textures.argtypes = [C.c_void_p, C.POINTER(TextureSet)]
+    L.mrt_clear_textures.argtypes = [C.c_void_p]
     L.mrt_resolve_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SurfaceOut), C.c_uint32]
     L.mrt_resolve_grid_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                             C.POINTER(SurfaceOut), C.c_uint32]
@@ -778,6 +796,39 @@ class Context:
 
     def clear_shade_data(self):
         self._chk(self.L.mrt_clear_shade_data(self.h))
+
+    def upload_textures(self, textures=(), bindings=None, tangents12=None, n_tangent_tris=None, on_device=False):
+        """Makes a texture set resident (mrt_upload_textures).  textures: [height, width, 4] numpy arrays, uint8 (RGBA8) or float32
+        (RGBA32F), or with on_device (width, height, format, device pointer / tensor) tuples; bindings: a host array of
+        T.MATERIAL_TEXTURES indexed by the material id, or None; tangents12: float32 [n, 12] indexed by prim_id, or with on_device a
+        device pointer / tensor and n_tangent_tris, or None.  While a set is resident the two resolves sample it."""
+        keep, tex = [], (Texture * max(len(textures), 1))()
+        for k, im in enumerate(textures):
+            if on_device:
+                w, h, fmt, ptr = im
+                tex[k] = Texture(w, h, fmt, 0, _ptr(ptr).value)
+            else:
+                im = np.ascontiguousarray(im)
+                if im.ndim != 3 or im.shape[2] != 4 or im.dtype not in (np.uint8, np.float32):
+                    raise ValueError("a texture is a [height, width, 4] array of uint8 or float32")
+                keep.append(im)
+                tex[k] = Texture(im.shape[1], im.shape[0], TEXEL_RGBA8 if im.dtype == np.uint8 else TEXEL_RGBA32F, 0, _np(im).value)
+        bind = None if bindings is None else np.ascontiguousarray(bindings, dtype=T.MATERIAL_TEXTURES)
+        n_tan, tan_ptr = 0, None
+        if tangents12 is not None:
+            if on_device:
+                n_tan, tan_ptr = int(n_tangent_tris), _ptr(tangents12).value
+            else:
+                tan = np.ascontiguousarray(tangents12, dtype=np.float32).reshape(-1, 12)
+                keep.append(tan)
+                n_tan, tan_ptr = tan.shape[0], (_np(tan).value if tan.shape[0] else None)
+        d = TextureSet(C.sizeof(TextureSet), TEXTURES_ON_DEVICE if on_device else 0, len(textures), 0 if bind is None else bind.shape[0],
+                       n_tan, 0, C.cast(tex, C.c_void_p).value if len(textures) else None,
+                       None if bind is None or bind.shape[0] == 0 else _np(bind).value, tan_ptr)
+        self._chk(self.L.mrt_upload_textures(self.h, C.byref(d)))
+
+    def clear_textures(self):
+        self._chk(self.L.mrt_clear_textures(self.h))
 
     def resolve_surfaces(self, d_rays, d_hits, count, d_rows=None, d_bounce_surface=None, d_out_hits=None, flags=0):
         """The shading surface of every hit record of a cast (device pointers / tensors: mrt_ray32 + mrt_hit32, or mrt_host_ray60 +

@@ -162,6 +162,9 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 13: return (uint32_t)sizeof(mrt_light_out);
 		case 15: return (uint32_t)sizeof(mrt_path_state); // (14: not a struct)
 		case 16: return (uint32_t)sizeof(mrt_path_step_desc);
+		case 18: return (uint32_t)sizeof(mrt_texture); // (17: not a struct)
+		case 19: return (uint32_t)sizeof(mrt_material_textures);
+		case 20: return (uint32_t)sizeof(mrt_texture_set);
 		default: return 0u;
 	}
 }
@@ -264,6 +267,7 @@ void mrt_destroy(mrt_ctx *ctx)
 	release(ctx->idx_in); release(ctx->idx_out); release(ctx->sort_tmp); release(ctx->overflow); release(ctx->refit_in);
 	release(ctx->tlas_work);
 	release(ctx->shade_rows); release(ctx->shade_materials);
+	release(ctx->tex_texels); release(ctx->tex_table); release(ctx->tex_bindings); release(ctx->tex_tangents);
 	for (auto &sc : ctx->sched) {
 		if (sc.side) { (void)hipStreamSynchronize(sc.side); (void)hipStreamDestroy(sc.side); }
 		if (sc.traced) (void)hipEventDestroy(sc.traced);

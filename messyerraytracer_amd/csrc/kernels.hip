@@ -17,6 +17,7 @@
 #include "mrt_internal.h"
 #include "launch_policy.h"
 #include "shade_data.h"
+#include "texture.h"
 #include "lighting.h"
 #include "path.h"
 #include "lane_map.h"
@@ -822,6 +823,7 @@ template hipError_t launch_source<HemiParams>(const TraceParams &, const void *,
 template hipError_t launch_source<BounceParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 
 #include "path_frame_kernel.h"
+#include "surface_tex_kernel.h"
 #include "surface_kernel.h"
 
 // src = a SurfaceSrc; anything else is hipErrorInvalidValue
@@ -833,6 +835,19 @@ hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s,
 	if (src == SURF_RAY32) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_RAY32>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
 	else if (src == SURF_HOST) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_HOST>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
 	else if (src == SURF_GRID) hipLaunchKernelGGL(resolve_surfaces_kernel<SURF_GRID>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s);
+	else return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+// the same with a texture set resident (surface_tex_kernel.h)
+hipError_t launch_resolve_textured_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams &t, int src, hipStream_t stream)
+{
+	if (p.count == 0) return hipSuccess;
+	const uint64_t blocks = (p.count + MRT_WG - 1) / MRT_WG;
+	if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	if (src == SURF_RAY32) hipLaunchKernelGGL(resolve_textured_surfaces_kernel<SURF_RAY32>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s, t);
+	else if (src == SURF_HOST) hipLaunchKernelGGL(resolve_textured_surfaces_kernel<SURF_HOST>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s, t);
+	else if (src == SURF_GRID) hipLaunchKernelGGL(resolve_textured_surfaces_kernel<SURF_GRID>, dim3((uint32_t)blocks), dim3(MRT_WG), 0, stream, p, s, t);
 	else return hipErrorInvalidValue;
 	return hipGetLastError();
 }

@@ -25,6 +25,9 @@ hipError_t launch_build_rows(const DevNode *nodes, const TriHot *hot, const TriC
 hipError_t launch_expand_tokens(const TraceParams &p, const uint32_t *tokens, hipStream_t stream);
 // shading surfaces (surface_kernel.h): src = a SurfaceSrc; the rows of shade data given as device arrays (any of the three may be null)
 hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream);
+// the same with a texture set resident (surface_tex_kernel.h; texture.h)
+struct TextureParams;
+hipError_t launch_resolve_textured_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams &t, int src, hipStream_t stream);
 // direct light on resolved surfaces (light_kernel.h): src = a SurfaceSrc
 struct LightParams;
 hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int src, hipStream_t stream);
@@ -128,6 +131,10 @@ struct mrt_ctx {
 	// shade data (surface.hip): the context's, not the scene's -- free_scene leaves it alone
 	DevBuf shade_rows, shade_materials;
 	uint32_t shade_n_tris = 0, shade_n_materials = 0, shade_present = 0; // present: mrt::SHADE_HAS_* (shade_data.h)
+	// texture set (texture.hip): the context's, like the shade data; tex_resident: the resolves launch the textured kernel
+	DevBuf tex_texels, tex_table, tex_bindings, tex_tangents;
+	uint32_t tex_n_bindings = 0, tex_n_tangent_tris = 0; // (no tangents resident: 0)
+	bool tex_resident = false;
 };
 
 #define HIP_TRY(ctx, call)                                                                          \

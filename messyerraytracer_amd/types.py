@@ -37,6 +37,11 @@ SURFACE64 = np.dtype([("normal", "<f4", 3), ("n_dot_v", "<f4"), ("albedo", "<f4"
 DEFAULT_MATERIAL = 0xFFFFFFFF
 assert MATERIAL.itemsize == 48 and SURFACE64.itemsize == 64
 
+# resident textures (mrt_upload_textures)
+MATERIAL_TEXTURES = np.dtype([("albedo_texture", "<u4"), ("normal_texture", "<u4"), ("normal_scale", "<f4"), ("reserved", "<u4")])  # mrt_material_textures
+NO_TEXTURE, TEXTURE_MAX_DIM = 0xFFFFFFFF, 16384
+assert MATERIAL_TEXTURES.itemsize == 16
+
 # direct light on resolved surfaces (mrt_light_surfaces)
 SHADE_LIGHT = np.dtype([("type", "<u4"), ("cast_shadows", "<u4"), ("position", "<f4", 3), ("direction", "<f4", 3), ("color", "<f4", 3),
                         ("range", "<f4"), ("attenuation", "<f4"), ("spot_angle", "<f4"), ("spot_angle_attenuation", "<f4"),
