@@ -50,7 +50,7 @@ void base_params(mrt_ctx *ctx, mrt::TraceParams &p)
 	const size_t scene_bytes = (size_t)ctx->n_nodes * sizeof(mrt::DevNode) + (size_t)ctx->n_tris * (sizeof(mrt::TriHot) + sizeof(mrt::TriCold));
 	p.tile_order = ctx->opts.tile_order == 2 || (ctx->opts.tile_order == 0 && scene_bytes > (size_t)256 << 20) ? 1u : 0u;
 	if (ctx->opts.tile_order == 3) p.tile_order = 2u; // 32x32-tile super-tiles (C5: 23.3 against 23.5 ms; not the default)
-	if (ctx->opts.tile_order == 4) p.tile_order = 3u; // column strips per XCD (kernels.hip, xcd_strips)
+	if (ctx->opts.tile_order == 4) p.tile_order = 3u; // column strips per XCD (device_common.h, xcd_strips)
 	p.extra_lds = ctx->opts.extra_lds <= 60000u ? ctx->opts.extra_lds : 60000u;
 	p.count_mode = ctx->opts.count_visits;
 	// packet-level frustum culling in the 128-ray walk (packet_rows_kernel.h): 0 off, 1 on, 2 = by where the rays come from

@@ -1,4 +1,4 @@
-// lane_map.h -- which ray a lane of a launch traces (lane_ray_index_g, kernels.hip), in two parts: what the 64 lanes of a group
+// lane_map.h -- which ray a lane of a launch traces (lane_ray_index_g, device_common.h), in two parts: what the 64 lanes of a group
 // share (its tile, and which piece of the tile) and what differs between them (the pixel inside the tile, the clip test).  The first
 // part divides and takes remainders, all of wave-uniform values: a kernel that keeps its group index in scalar registers gets it
 // done on the scalar unit, once per group, in 32-bit arithmetic whenever the numbers fit.  No HIP types: csrc/host/lane_map_test.cpp
@@ -47,7 +47,7 @@ MRT_LM_HD bool sched_matches(uint64_t total, uint32_t unit, uint32_t n_units)
 	return (uint64_t)(n_units - 1u) * unit < total && total <= (uint64_t)n_units * unit;
 }
 
-// tile_order 3 (kernels.hip, xcd_strips): every XCD works down its own column strips.  T = uint32_t or uint64_t.
+// tile_order 3 (device_common.h, xcd_strips): every XCD works down its own column strips.  T = uint32_t or uint64_t.
 template <class T>
 MRT_LM_HD bool strip_tile(const TileGrid &g, T tile, uint32_t &tx, uint32_t &ty)
 {

@@ -1,4 +1,4 @@
-// light_kernel.h — direct light on resolved surfaces (mrt_light_surfaces / mrt_light_grid_surfaces).  Included by kernels.hip (inside
+// light_kernel.h — direct light on resolved surfaces (mrt_light_surfaces / mrt_light_grid_surfaces).  Included by shade_kernels.hip (inside
 // namespace mrt, after source_common.h; lighting.h holds LightParams and pow01).
 //
 // ShadePass::cook_torrance_multi_light of the reference (src/modules/graphics/shade_pass.h:597-657) and the terms shade_material adds

@@ -1,6 +1,6 @@
 // lighting.hip — direct light on resolved surfaces (include/mrt_hip.h: mrt_shadow_lights, mrt_light_surfaces,
 // mrt_light_grid_surfaces).  The checks of the light list and the environment and the kernel's copy of both are host/light_data.cpp;
-// the kernel is light_kernel.h (kernels.hip).
+// the kernel is light_kernel.h (shade_kernels.hip).
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
@@ -24,9 +24,7 @@ int light(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, const 
 	s.records = d_hits; s.rows = d_rows; s.mask = d_mask; s.out = out->d_rgba;
 	mrt::fill_light_params(lights, n_lights, env, s);
 	HIP_TRY(ctx, mrt::launch_light_surfaces(p, s, src, ctx->stream));
-	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	return MRT_OK;
+	return finish_call(ctx, flags);
 }
 
 } // namespace
@@ -47,11 +45,8 @@ int mrt_light_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_hits, con
 	if (!ctx) return MRT_ERR_INVALID;
 	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
 	mrt::TraceParams p;
-	std::memset(&p, 0, sizeof(p)); // (no scene: nothing is walked)
-	p.rays = d_rays; p.count = count;
-	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
-	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
-	return light(ctx, host ? mrt::SURF_HOST : mrt::SURF_RAY32, p, d_hits, d_rows, lights, n_lights, d_mask, env, out, flags);
+	const int src = record_params(d_rays, count, flags, p);
+	return light(ctx, src, p, d_hits, d_rows, lights, n_lights, d_mask, env, out, flags);
 }
 
 int mrt_light_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,

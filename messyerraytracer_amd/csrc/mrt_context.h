@@ -1,28 +1,39 @@
 // mrt_context.h — the context behind the C-ABI (mrt_ctx) and what api.hip, cast.hip and schedule.hip share: the kernel
-// launchers of kernels.hip / device_build.hip, the error and buffer helpers.
+// launchers of kernels.hip / prep_kernels.hip / shade_kernels.hip / device_build.hip, the error and buffer helpers.
 #pragma once
 #include <cstdio>
+#include <cstring>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"
 #include "launch_policy.h"
 
 namespace mrt {
+// ---- kernels.hip: the walks
 hipError_t launch_trace(const TraceParams &p, bool any_hit, bool count, hipStream_t stream);
 const char *last_trace_variant();
 bool quad_kernel_built();
-hipError_t launch_grid_rays(const TraceParams &p, mrt_ray32 *out, hipStream_t stream);
+hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
+		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream);
 // record-driven casts (source_common.h): S = the family's parameter struct (instantiated in kernels.hip for ShadowParams, ReflectParams,
 // HemiParams and BounceParams), params = an S, src = one of SourceFamily<S>'s sources, any_hit = a mode the family has; blocks != 0: the
 // persistent kernel (next_ray .. leaf_wait as launch_trace_persistent)
 template <class S>
 hipError_t launch_source(const TraceParams &p, const void *params, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, hipStream_t stream);
+// ---- prep_kernels.hip: what prepares a scene or a cast
 hipError_t launch_build_rows4(const Dev4Node *nodes4, const TriHot *hot, const TriCold *cold, uint32_t n_nodes4, uint32_t n_tris,
 		void *rows, hipStream_t stream);
 hipError_t launch_build_rows(const DevNode *nodes, const TriHot *hot, const TriCold *cold, uint32_t n_nodes, uint32_t n_tris,
 		void *rows, hipStream_t stream);
+hipError_t launch_grid_rays(const TraceParams &p, mrt_ray32 *out, hipStream_t stream);
 hipError_t launch_expand_tokens(const TraceParams &p, const uint32_t *tokens, hipStream_t stream);
+hipError_t launch_detect_grid(const void *rays, uint32_t in_fmt, uint64_t count, uint32_t tile_w_log2,
+		unsigned long long *scratch, uint32_t *out, uint32_t *host_out, hipStream_t stream);
+hipError_t launch_morton_keys(const void *rays, uint32_t in_fmt, uint64_t count, uint32_t *keys, uint32_t *index, hipStream_t stream);
+hipError_t launch_origin_dir_keys(const void *rays, uint32_t in_fmt, uint64_t count, const float lo[3], const float hi[3],
+		uint32_t *keys, uint32_t *index, hipStream_t stream);
+// ---- shade_kernels.hip: the passes over hit records
 // shading surfaces (surface_kernel.h): src = a SurfaceSrc; the rows of shade data given as device arrays (any of the three may be null)
 hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream);
 // the same with a texture set resident (surface_tex_kernel.h; texture.h)
@@ -37,19 +48,13 @@ hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t s
 hipError_t launch_path_step(const TraceParams &p, const PathParams &s, int src, hipStream_t stream);
 hipError_t launch_path_finish(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba, hipStream_t stream);
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream);
+// ---- device_build.hip
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);
 hipError_t launch_collapse8(const DevNode *nodes, uint32_t n_nodes, Dev8Node *nodes8, float *leaf_box, uint32_t *bad, hipStream_t stream);
 hipError_t launch_offset_refs(DevNode *dst, const DevNode *src, uint32_t n, uint32_t node_base, uint32_t tri_base, void *stream);
 hipError_t launch_offset_refs8(Dev8Node *dst, const Dev8Node *src, uint32_t n, uint32_t node_base, uint32_t tri_base, void *stream);
 hipError_t launch_flatten_instances(const float *d_verts9, const mrt_instance *d_instances, const uint32_t *d_first_out,
 		uint32_t n_instances, uint32_t max_tris_per_instance, mrt_tri64 *d_out, void *stream);
-hipError_t launch_morton_keys(const void *rays, uint32_t in_fmt, uint64_t count, uint32_t *keys, uint32_t *index, hipStream_t stream);
-hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
-		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream);
-hipError_t launch_origin_dir_keys(const void *rays, uint32_t in_fmt, uint64_t count, const float lo[3], const float hi[3],
-		uint32_t *keys, uint32_t *index, hipStream_t stream);
-hipError_t launch_detect_grid(const void *rays, uint32_t in_fmt, uint64_t count, uint32_t tile_w_log2,
-		unsigned long long *scratch, uint32_t *out, uint32_t *host_out, hipStream_t stream);
 }
 
 struct DevBuf {
@@ -182,6 +187,23 @@ size_t hit_stride(const mrt_ctx *ctx, uint32_t flags, int mode);
 uint32_t out_format(const mrt_ctx *ctx, uint32_t flags, int mode);
 void base_params(mrt_ctx *ctx, mrt::TraceParams &p);
 int grid_params(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1, mrt::TraceParams &p);
+// The rays of a call over hit records (surface.hip, lighting.hip, path.hip) that are an array, not a grid: p for count rays at d_rays in
+// the layout flags names (no scene: nothing is walked); returns the SurfaceSrc.
+inline int record_params(const void *d_rays, uint64_t count, uint32_t flags, mrt::TraceParams &p)
+{
+	std::memset(&p, 0, sizeof(p));
+	p.rays = d_rays; p.count = count;
+	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
+	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
+	return host ? mrt::SURF_HOST : mrt::SURF_RAY32;
+}
+// ... and the end of such a call, its pass queued: back at once for MRT_FLAG_ASYNC, else when the stream is done
+inline int finish_call(mrt_ctx *ctx, uint32_t flags)
+{
+	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return MRT_OK;
+}
 // schedule.hip: before the launch of a scheduled cast (fills p's schedule fields), after it (ev[4] recorded)
 int schedule_grid(mrt_ctx *ctx, const mrt::CastPlan &c, mrt::TraceParams &p);
 int schedule_sort(mrt_ctx *ctx);

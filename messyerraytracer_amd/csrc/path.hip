@@ -1,6 +1,6 @@
 // path.hip — the path tracer's per-pixel state on the device (include/mrt_hip.h: mrt_path_init, mrt_path_step, mrt_path_grid_step,
 // mrt_path_finish).  The refusals and the kernel's copy of a descriptor are host/path_data.cpp; the kernels are path_kernel.h
-// (kernels.hip).
+// (shade_kernels.hip).
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
@@ -20,9 +20,7 @@ int step(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, const m
 	s.records = d_hits; s.rows = d_rows;
 	mrt::fill_path_params(desc, pixel0, s);
 	HIP_TRY(ctx, mrt::launch_path_step(p, s, src, ctx->stream));
-	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	return MRT_OK;
+	return finish_call(ctx, flags);
 }
 
 } // namespace
@@ -37,9 +35,7 @@ int mrt_path_init(mrt_ctx *ctx, mrt_path_state *d_state, uint64_t count, uint32_
 	if (count == 0) return MRT_OK;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	HIP_TRY(ctx, mrt::launch_path_init(d_state, count, ctx->stream));
-	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	return MRT_OK;
+	return finish_call(ctx, flags);
 }
 
 int mrt_path_step(mrt_ctx *ctx, const void *d_rays, const void *d_hits, const mrt_surface64 *d_rows, uint64_t count,
@@ -49,11 +45,8 @@ int mrt_path_step(mrt_ctx *ctx, const void *d_rays, const void *d_hits, const mr
 	if (const char *why = mrt::path_step_invalid(d_rays, d_hits, d_rows, desc, flags, MRT_FLAG_HOST_LAYOUT | MRT_FLAG_ASYNC))
 		return fail(ctx, MRT_ERR_INVALID, why);
 	mrt::TraceParams p;
-	std::memset(&p, 0, sizeof(p)); // (no scene: nothing is walked)
-	p.rays = d_rays; p.count = count;
-	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
-	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
-	return step(ctx, host ? mrt::SURF_HOST : mrt::SURF_RAY32, p, d_hits, d_rows, 0u, desc, flags);
+	const int src = record_params(d_rays, count, flags, p);
+	return step(ctx, src, p, d_hits, d_rows, 0u, desc, flags);
 }
 
 int mrt_path_grid_step(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
@@ -75,9 +68,7 @@ int mrt_path_finish(mrt_ctx *ctx, const mrt_path_state *d_state, uint64_t count,
 	if (count == 0) return MRT_OK;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	HIP_TRY(ctx, mrt::launch_path_finish(d_state, count, tonemap_mode, mrt::hable_partial(11.2f), d_rgba, ctx->stream));
-	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	return MRT_OK;
+	return finish_call(ctx, flags);
 }
 
 } // extern "C"

@@ -1,8 +1,8 @@
 // path_frame_kernel.h — the two small kernels around a path-traced frame: mrt_path_init's and mrt_path_finish's (the frame's last pass,
 // src/modules/graphics/cpu_path_tracer.h:202-222: tone mapping and gamma; path.h holds both, shared with the host).  Included by
-// kernels.hip inside namespace mrt, ahead of surface_kernel.h: plain kernels are laid out in source order, and the padding that ends
-// the section then stays behind the kernel that had it, so that tools/isa_symbols.py shows every earlier kernel unchanged.  One thread
-// per entry, 16-byte loads and stores; pow01 is fp64.
+// shade_kernels.hip inside namespace mrt, ahead of surface_kernel.h.  The order matters to nothing outside that unit: plain kernels
+// are laid out in source order and the last one carries the padding that ends the section, which tools/isa_symbols.py leaves out.
+// One thread per entry, 16-byte loads and stores; pow01 is fp64.
 #pragma once
 
 __global__ __launch_bounds__(MRT_WG) void path_init_kernel(mrt_path_state *state, uint64_t count)

@@ -1,5 +1,5 @@
 // path_kernel.h — the path tracer's per-pixel state (mrt_path_step / mrt_path_grid_step; the two small kernels of mrt_path_init and
-// mrt_path_finish are path_frame_kernel.h).  Included by kernels.hip (inside namespace mrt, after light_kernel.h; path.h holds PathParams).
+// mrt_path_finish are path_frame_kernel.h).  Included by shade_kernels.hip (inside namespace mrt, after light_kernel.h; path.h holds PathParams).
 //
 // The rest of CPUPathTracer's loop body (src/modules/graphics/cpu_path_tracer.h:110-194) around the links already resident: the
 // radiance accumulation, the throughput weights of PathTrace::sample_bounce (path_trace.h:213-246), Russian roulette and the `active`

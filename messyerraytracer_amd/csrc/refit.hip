@@ -11,7 +11,7 @@
 //   3. every node's parent, once per scene                                              (refit_parents_kernel)
 //   4. the boxes bottom-up                                                              (refit_climb_kernel)
 //   5. a check that every box a node holds is its child's own union                     (refit_verify_kernel)
-//   6. the wide layouts and the row arrays, as a build derives them                     (device_build.hip, kernels.hip)
+//   6. the wide layouts and the row arrays, as a build derives them                     (device_build.hip, prep_kernels.hip)
 // DESIGN.md 4.8 has the pipeline and the measurements.  A two-level scene adds kernels of its own where a pass needs
 // the mesh array (refit2_tris_kernel, refit2_slots_kernel, refit2_roots_kernel), then rebuilds its TLAS.
 #include <cfloat>

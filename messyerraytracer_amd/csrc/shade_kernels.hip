@@ -1,0 +1,58 @@
+// shade_kernels.hip — gfx950 kernels of the shading passes over hit records: the resolve to shading surfaces (plain and textured), the
+// direct light, the path tracer's per-pixel state and the packing of shade rows.  None of them walks a scene; they share the ray and
+// record helpers of device_common.h and record_surface of source_common.h with the walks of kernels.hip, and are compiled apart from
+// them.  The arithmetic is the canonical form of DESIGN.md ("Arithmetic"), as in kernels.hip.
+#include <hip/hip_runtime.h>
+#include <cfloat>
+#include <type_traits>
+#include "mrt_internal.h"
+#include "shade_data.h"
+#include "texture.h"
+#include "lighting.h"
+#include "path.h"
+#include "lane_map.h"
+
+namespace mrt {
+
+#include "device_common.h"
+#include "dispatch.h"
+#include "source_common.h"
+
+#include "path_frame_kernel.h"
+#include "surface_tex_kernel.h"
+#include "surface_kernel.h"
+#include "light_kernel.h"
+#include "path_kernel.h"
+
+// ---- launch wrappers (called from surface.hip, lighting.hip and path.hip); src = a SurfaceSrc ------------------------------------
+hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream)
+{
+	return launch_surface_pass([](auto SRC) { return resolve_surfaces_kernel<SRC>; }, src, p, stream, s);
+}
+// the same with a texture set resident (surface_tex_kernel.h)
+hipError_t launch_resolve_textured_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams &t, int src, hipStream_t stream)
+{
+	return launch_surface_pass([](auto SRC) { return resolve_textured_surfaces_kernel<SRC>; }, src, p, stream, s, t);
+}
+hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int src, hipStream_t stream)
+{
+	return launch_surface_pass([](auto SRC) { return light_surfaces_kernel<SRC>; }, src, p, stream, s);
+}
+hipError_t launch_path_step(const TraceParams &p, const PathParams &s, int src, hipStream_t stream)
+{
+	return launch_surface_pass([](auto SRC) { return path_step_kernel<SRC>; }, src, p, stream, s);
+}
+hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream)
+{
+	return launch_per_entry<true>(path_init_kernel, count, stream, state, count);
+}
+hipError_t launch_path_finish(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba, hipStream_t stream)
+{
+	return launch_per_entry<true>(path_finish_kernel, count, stream, state, count, mode, white, rgba);
+}
+hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream)
+{
+	return launch_per_entry<false>(pack_shade_rows_kernel, n_tris, stream, ids, normals9, uvs6, n_tris, reinterpret_cast<uint4 *>(rows));
+}
+
+} // namespace mrt

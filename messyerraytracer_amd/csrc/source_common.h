@@ -1,5 +1,6 @@
 // source_common.h — what every record-driven ray source shares (shadow_kernel.h, reflection_kernel.h, hemisphere_kernel.h,
-// bounce_kernel.h).  Included by kernels.hip (inside namespace mrt, after the ray and record helpers, before the four family headers).
+// bounce_kernel.h).  Included by kernels.hip (inside namespace mrt, after device_common.h, before the four family headers) and, for
+// record_surface, by shade_kernels.hip.
 //
 // A source family is a parameter struct (mrt_internal.h: ShadowParams, ReflectParams, HemiParams, BounceParams; SourceFamily<S> names
 // its three sources and its modes) plus one overload of

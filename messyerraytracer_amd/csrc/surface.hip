@@ -1,7 +1,7 @@
 // surface.hip — the shade data a context holds and the resolve of hit records to shading surfaces (include/mrt_hip.h:
 // mrt_upload_shade_data, mrt_clear_shade_data, mrt_resolve_surfaces, mrt_resolve_grid_surfaces).  The descriptor's checks and the
 // packing of host arrays are host/shade_data.cpp; the kernels are surface_kernel.h and, with a texture set resident (texture.hip),
-// surface_tex_kernel.h (kernels.hip).
+// surface_tex_kernel.h (shade_kernels.hip).
 #include <cstring>
 #include <vector>
 #include <hip/hip_runtime.h>
@@ -41,9 +41,7 @@ int resolve(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, cons
 		t.n_bindings = ctx->tex_n_bindings; t.n_tangent_tris = ctx->tex_n_tangent_tris;
 		HIP_TRY(ctx, mrt::launch_resolve_textured_surfaces(p, s, t, src, ctx->stream));
 	} else HIP_TRY(ctx, mrt::launch_resolve_surfaces(p, s, src, ctx->stream));
-	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	return MRT_OK;
+	return finish_call(ctx, flags);
 }
 
 } // namespace
@@ -100,11 +98,8 @@ int mrt_resolve_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_hits, u
 	if (!ctx) return MRT_ERR_INVALID;
 	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
 	mrt::TraceParams p;
-	std::memset(&p, 0, sizeof(p)); // (no scene: nothing is walked)
-	p.rays = d_rays; p.count = count;
-	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
-	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
-	return resolve(ctx, host ? mrt::SURF_HOST : mrt::SURF_RAY32, p, d_hits, out, flags);
+	const int src = record_params(d_rays, count, flags, p);
+	return resolve(ctx, src, p, d_hits, out, flags);
 }
 
 int mrt_resolve_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,

@@ -1,5 +1,5 @@
 // surface_kernel.h — hit records resolved to shading surfaces (mrt_resolve_surfaces / mrt_resolve_grid_surfaces), and the row packing
-// of shade data given as device arrays.  Included by kernels.hip (inside namespace mrt, after source_common.h).
+// of shade data given as device arrays.  Included by shade_kernels.hip (inside namespace mrt, after source_common.h).
 //
 // ShadePass::extract_surface of the reference (src/modules/graphics/shade_pass.h:509-587) without textures, normal maps, F0 and the
 // diffuse albedo, against the SceneShadeData the context holds (shade_data.h).  One thread per record, nothing walked: a streaming

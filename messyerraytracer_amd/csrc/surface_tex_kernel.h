@@ -1,7 +1,7 @@
 // surface_tex_kernel.h — the resolve of surface_kernel.h with a texture set resident (mrt_upload_textures; texture.h): all of
 // ShadePass::extract_surface (shade_pass.h:509-587) but F0 and the diffuse albedo -- the smooth normal, perturb_normal
 // (shade_pass.h:110-162) over TriangleTangents (triangle_tangents.h:21-56), the material and its albedo texture through
-// TextureSampler::sample_bilinear (texture_sampler.h:45-88).  Included by kernels.hip (inside namespace mrt, after source_common.h).
+// TextureSampler::sample_bilinear (texture_sampler.h:45-88).  Included by shade_kernels.hip (inside namespace mrt, after source_common.h).
 //
 // One thread per record, 256 per workgroup, no LDS, no scratch; the gather of resolve_surfaces_kernel plus, per record and only where
 // a binding applies: one 16-byte binding, three 16-byte tangent loads, per sampled texture one 16-byte descriptor and four texels.
