@@ -38,6 +38,9 @@ DRIVERS = {
     "hemisphere_policy_test": (["host/hemisphere_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
     "bounce_policy_test": (["host/bounce_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
     "instance_math_test": (["host/instance_math_test.cpp"], CPU, False),  # instance_math.h, shared by the host path and the device TLAS build
+    "build_rules_test": (["host/build_rules_test.cpp"], CPU, False),  # build_rules.h, shared by the host and the device scene builders
+    "build_rules_test_san": (["host/build_rules_test.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
+                                                               "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
     "shade_data_test": (["host/shade_data_test.cpp", "host/shade_data.cpp"], CPU, False),
     "light_data_test": (["host/light_data_test.cpp", "host/light_data.cpp"], CPU, False),
     "path_data_test": (["host/path_data_test.cpp", "host/path_data.cpp"], CPU, False),
@@ -167,6 +170,11 @@ build_shade_data_test = _driver("shade_data_test")
 build_light_data_test = _driver("light_data_test")
 build_path_data_test = _driver("path_data_test")
 build_texture_data_test = _driver("texture_data_test")
+
+
+def build_build_rules_test(force: bool = False, sanitize: bool = False) -> str:
+    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
+    return build_driver("build_rules_test_san" if sanitize else "build_rules_test", force)
 
 
 def build_lane_map_test(force: bool = False, sanitize: bool = False) -> str:

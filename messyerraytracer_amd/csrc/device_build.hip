@@ -40,6 +40,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "mrt_internal.h"
+#include "build_rules.h"
 
 namespace mrt {
 
@@ -47,23 +48,9 @@ namespace {
 
 #define LBVH_WG 256
 
-struct Box { float mn[3], mx[3]; };
-
-// order-preserving float <-> uint (for atomicMin / atomicMax on floats of either sign)
-__device__ __forceinline__ uint32_t f2ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__host__ __device__ __forceinline__ float ord2f(uint32_t o) {
-	const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-	float f; memcpy(&f, &u, 4); return f;
-}
-
-// One ulp outwards: v0 + e1 is a rounded sum, the true vertex may lie half an ulp outside it.
-__device__ __forceinline__ float ulp_down(float f) { return f == 0.0f ? -FLT_MIN : __uint_as_float(__float_as_uint(f) + (f > 0.0f ? -1 : 1)); }
-__device__ __forceinline__ float ulp_up(float f) { return f == 0.0f ? FLT_MIN : __uint_as_float(__float_as_uint(f) + (f > 0.0f ? 1 : -1)); }
-
-// 1. box of every triangle (vertices v0, v0+e1, v0+e2 as the intersection test sees them) and the
-//    bounds of all boxes: bounds[0..2] = min (ordered uint), bounds[3..5] = max.
-//    Grid-stride over at most LBVH_BOUNDS_BLOCKS blocks, one atomic per block and component: atomics on
-//    one address cost ~10 ns each chip-wide (one per wave made this kernel 1 ms per million triangles).
+// 1. box of every triangle and the bounds of all boxes: bounds[0..2] = min (ordered uint), bounds[3..5] = max, one atomic per block
+//    and component.  tri_box and block_bounds (build_rules.h) written out by hand: with the calls this kernel's machine code moved,
+//    and it is on every device top level's path; as written it is the code it was.
 //    With box_in (DeviceBuildResult::boxes_in, no triangles): the given boxes themselves, as they are (a top level over instances'
 //    world boxes: a box rebuilt from v0 + e1 would round, and a TLAS box must contain the world box).
 #define LBVH_BOUNDS_BLOCKS 1024u
@@ -263,13 +250,9 @@ __global__ __launch_bounds__(LBVH_WG) void lbvh_verify_kernel(const DevNode *nod
 		if (ref & kLeafBit) { // the union of the leaf's triangle boxes (one triangle per leaf in the radix and PLOC forms)
 			const uint32_t first = ref & 0x7FFFFFFFu, cnt = side ? g.right_count : g.left_count;
 			want = tri_boxes[sorted_tri[first]];
-			for (uint32_t j = 1; j < cnt; j++) {
-				const Box t = tri_boxes[sorted_tri[first + j]];
-				for (int k = 0; k < 3; k++) { want.mn[k] = fminf(want.mn[k], t.mn[k]); want.mx[k] = fmaxf(want.mx[k], t.mx[k]); }
-			}
+			for (uint32_t j = 1; j < cnt; j++) want = unite(want, tri_boxes[sorted_tri[first + j]]);
 		} else {
-			const DevNode c = nodes[ref];
-			for (int k = 0; k < 3; k++) { want.mn[k] = fminf(c.lmin[k], c.rmin[k]); want.mx[k] = fmaxf(c.lmax[k], c.rmax[k]); }
+			want = unite(get_side(nodes + ref, 0), get_side(nodes + ref, 1));
 			const uint32_t d = node_depth[ref];
 			deepest = d > deepest ? d : deepest;
 		}
@@ -652,118 +635,45 @@ __global__ void sah_wrap_kernel(const uint32_t *bounds, uint32_t n, uint32_t lc,
 	rows[0] = g; node_depth[0] = 1u; *max_depth = 1u;
 }
 
-// 5b. 4-wide collapse for the incoherent-ray kernel (one 128-byte line per step): the rule of
-//     scene_prep.cpp (start from a node's two children, keep opening the internal child with the
-//     largest half-area until there are four).  Every binary node gets the 4-wide node it WOULD be
-//     the root of, at its own index, so no allocation or top-down pass is needed; only the ones
-//     reachable from node 0 are ever read (the others cost HBM capacity, not bandwidth).
+// 5b. 4-wide collapse for the incoherent-ray kernel (one 128-byte line per step): a node's children by open_widest
+//     (build_rules.h).  Every binary node gets the 4-wide node it WOULD be the root of, at its own index, so no
+//     allocation or top-down pass is needed; only the ones reachable from node 0 are ever read (the others cost HBM capacity,
+//     not bandwidth).
 __global__ __launch_bounds__(LBVH_WG) void lbvh_collapse4_kernel(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4)
 {
 	const uint32_t b = blockIdx.x * LBVH_WG + threadIdx.x;
 	if (b >= n_nodes) return;
-	float box[4][6]; uint32_t ref[4]; uint32_t n = 2;
-	auto take = [&](const DevNode &g, uint32_t at_l, uint32_t at_r) {
-		for (int k = 0; k < 3; k++) {
-			box[at_l][k] = g.lmin[k]; box[at_l][3 + k] = g.lmax[k];
-			box[at_r][k] = g.rmin[k]; box[at_r][3 + k] = g.rmax[k];
-		}
-		ref[at_l] = g.left_ref; ref[at_r] = g.right_ref;
-	};
-	take(nodes[b], 0, 1);
-	while (n < 4) {
-		int best = -1; float best_a = -1.0f;
-		for (uint32_t i = 0; i < n; i++) {
-			if (ref[i] >= kSentinel) continue; // a leaf
-			const float e0 = box[i][3] - box[i][0], e1 = box[i][4] - box[i][1], e2 = box[i][5] - box[i][2];
-			const float a = e0 * e1 + e1 * e2 + e2 * e0;
-			if (a > best_a) { best_a = a; best = (int)i; }
-		}
-		if (best < 0) break;
-		take(nodes[ref[best]], (uint32_t)best, n);
-		n++;
-	}
+	float box[4][6]; uint32_t ref[4];
+	take_children(nodes[b], box, ref, 0, 1);
+	const uint32_t n = open_widest(box, ref, [&](uint32_t r) -> const DevNode & { return nodes[r]; });
 	Dev4Node out;
 	for (uint32_t i = 0; i < 4; i++) {
-		for (int k = 0; k < 6; k++) out.box[i][k] = i < n ? box[i][k] : __builtin_inff(); // unused slot: never hit
+		for (int c = 0; c < 6; c++) out.box[i][c] = i < n ? box[i][c] : __builtin_inff(); // unused slot: never hit
 		out.ref[i] = i < n ? ref[i] : kSentinel;
 	}
 	out.n_children = n; out.pad[0] = out.pad[1] = out.pad[2] = 0u;
 	nodes4[b] = out;
 }
 
-// 5c. 8-wide compressed collapse (Dev8Node), same scheme as 5b: every binary node gets the 8-wide
-//     node it would be the root of, at its own index.  Quantisation exactly as on the host
-//     (scene_prep.cpp): power-of-two grid step with one step of headroom, outward rounding, and every
-//     quantised coordinate checked on the value the trace kernel will decode, fmaf(q, step, origin).
-//     A box that cannot be put on a grid (non-finite) raises *bad: the scene then goes without this layout.
-//     Also writes the exact box of every leaf (leaf_box, 8 floats per slot; each leaf once, by its binary
-//     parent): the 8-wide walk checks a candidate hit against it (mrt_internal.h, Dev8Node).
+// 5c. 8-wide compressed collapse (Dev8Node), same scheme as 5b: every binary node gets the 8-wide node it would be the root of, at
+//     its own index, on the grid quantise8 (build_rules.h) gives it.  A box that cannot be put on a grid (non-finite) raises *bad:
+//     the scene then goes without this layout.  Also writes the exact box of every leaf (leaf_box, 8 floats per slot; each leaf
+//     once, by its binary parent): the 8-wide walk checks a candidate hit against it (mrt_internal.h, Dev8Node).
 __global__ __launch_bounds__(LBVH_WG) void lbvh_collapse8_kernel(const DevNode *nodes, uint32_t n_nodes, Dev8Node *nodes8, float *leaf_box, uint32_t *bad)
 {
 	const uint32_t b = blockIdx.x * LBVH_WG + threadIdx.x;
 	if (b >= n_nodes) return;
-	float box[8][6]; uint32_t ref[8]; uint32_t n = 2;
-	auto take = [&](const DevNode &g, uint32_t at_l, uint32_t at_r) {
-		for (int k = 0; k < 3; k++) {
-			box[at_l][k] = g.lmin[k]; box[at_l][3 + k] = g.lmax[k];
-			box[at_r][k] = g.rmin[k]; box[at_r][3 + k] = g.rmax[k];
-		}
-		ref[at_l] = g.left_ref; ref[at_r] = g.right_ref;
-	};
-	take(nodes[b], 0, 1);
+	float box[8][6]; uint32_t ref[8];
+	take_children(nodes[b], box, ref, 0, 1);
 	for (uint32_t i = 0; i < 2; i++)
 		if (ref[i] >= kLeafBit) {
 			float4 *lb = (float4 *)leaf_box + (size_t)(ref[i] & 0x7FFFFFFFu) * 2u;
 			lb[0] = make_float4(box[i][0], box[i][1], box[i][2], 0.0f);
 			lb[1] = make_float4(box[i][3], box[i][4], box[i][5], 0.0f);
 		}
-	while (n < 8) {
-		int best = -1; float best_a = -1.0f;
-		for (uint32_t i = 0; i < n; i++) {
-			if (ref[i] >= kSentinel) continue; // a leaf
-			const float e0 = box[i][3] - box[i][0], e1 = box[i][4] - box[i][1], e2 = box[i][5] - box[i][2];
-			const float a = e0 * e1 + e1 * e2 + e2 * e0;
-			if (a > best_a) { best_a = a; best = (int)i; }
-		}
-		if (best < 0) break;
-		take(nodes[ref[best]], (uint32_t)best, n);
-		n++;
-	}
+	const uint32_t n = open_widest(box, ref, [&](uint32_t r) -> const DevNode & { return nodes[r]; });
 	Dev8Node out;
-	memset(&out, 0, sizeof(out));
-	out.n_children = (uint8_t)n;
-	float step[3] = { 1.0f, 1.0f, 1.0f };
-	bool ok = true;
-	for (int a = 0; a < 3; a++) {
-		float lo = box[0][a], hi = box[0][3 + a];
-		for (uint32_t i = 1; i < n; i++) { lo = fminf(lo, box[i][a]); hi = fmaxf(hi, box[i][3 + a]); }
-		out.org[a] = lo;
-		const double ext = (double)hi - (double)lo;
-		if (!(ext >= 0.0) || !(ext < 1.0e300)) { ok = false; continue; }
-		int e = 1;
-		if (ext > 0.0) { e = (int)ceil(log2(ext / 254.0)) + 127; if (e < 1) e = 1; if (e > 254) e = 254; }
-		for (;;) {
-			const float s = __uint_as_float((uint32_t)e << 23);
-			if ((double)s * 254.0 >= ext || e >= 254) { step[a] = s; break; }
-			e++;
-		}
-		out.exp[a] = (uint8_t)e;
-	}
-	for (uint32_t i = 0; i < 8; i++) {
-		if (i >= n) { out.ref[i] = kSentinel; continue; }
-		out.ref[i] = ref[i];
-		for (int a = 0; a < 3 && ok; a++) {
-			int ql = (int)floor(((double)box[i][a] - (double)out.org[a]) / (double)step[a]);
-			ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
-			while (ql > 0 && __builtin_fmaf((float)ql, step[a], out.org[a]) > box[i][a]) ql--;
-			int qh = (int)ceil(((double)box[i][3 + a] - (double)out.org[a]) / (double)step[a]);
-			qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
-			while (qh < 255 && __builtin_fmaf((float)qh, step[a], out.org[a]) < box[i][3 + a]) qh++;
-			if (__builtin_fmaf((float)ql, step[a], out.org[a]) > box[i][a] || __builtin_fmaf((float)qh, step[a], out.org[a]) < box[i][3 + a]) ok = false;
-			out.qlo[a][i] = (uint8_t)ql; out.qhi[a][i] = (uint8_t)qh;
-		}
-	}
-	if (!ok) atomicOr(bad, 1u);
+	if (!quantise8(box, ref, n, out)) atomicOr(bad, 1u);
 	nodes8[b] = out;
 }
 
@@ -796,9 +706,8 @@ __global__ __launch_bounds__(LBVH_WG) void lbvh_leaves_kernel(const mrt_tri64 *t
 
 // Instances -> world-space triangles: the loop of RayTracerServer::_rebuild_scene
 // (src/godot/raytracer_server.cpp:700-711).  Per vertex Transform3D::xform = basis row . v + origin
-// (dot product summed left to right), then the Triangle ctor (src/core/triangle.h:41-51, the
-// arithmetic of mrt_make_triangles), id = running triangle offset in instance order, layers = the
-// mesh's layer mask.  blockIdx.y = instance.
+// (dot product summed left to right), then the Triangle ctor (make_tri64, build_rules.h), id = running
+// triangle offset in instance order, layers = the mesh's layer mask.  blockIdx.y = instance.
 __global__ __launch_bounds__(LBVH_WG) void flatten_instances_kernel(const float *verts9, const mrt_instance *instances,
 		const uint32_t *first_out, mrt_tri64 *out)
 {
@@ -812,22 +721,8 @@ __global__ __launch_bounds__(LBVH_WG) void flatten_instances_kernel(const float 
 		for (int r = 0; r < 3; r++)
 			w[v][r] = ((in.basis[3 * r] * x + in.basis[3 * r + 1] * y) + in.basis[3 * r + 2] * z) + in.origin[r];
 	}
-	float e1[3], e2[3], n[3];
-	for (int c = 0; c < 3; c++) { e1[c] = w[1][c] - w[0][c]; e2[c] = w[2][c] - w[0][c]; }
-	n[0] = e1[1] * e2[2] - e1[2] * e2[1];
-	n[1] = e1[2] * e2[0] - e1[0] * e2[2];
-	n[2] = e1[0] * e2[1] - e1[1] * e2[0];
-	const float l2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
-	if (l2 == 0.0f) { n[0] = n[1] = n[2] = 0.0f; }
-	else { const float l = __builtin_sqrtf(l2); n[0] /= l; n[1] /= l; n[2] /= l; }
 	const uint32_t id = first_out[blockIdx.y] + k;
-	float4 *dst = reinterpret_cast<float4 *>(out + id);
-	float4 a, b, c, d;
-	a.x = w[0][0]; a.y = w[0][1]; a.z = w[0][2]; a.w = __uint_as_float(id);
-	b.x = e1[0]; b.y = e1[1]; b.z = e1[2]; b.w = __uint_as_float(in.layers);
-	c.x = e2[0]; c.y = e2[1]; c.z = e2[2]; c.w = 0.0f;
-	d.x = n[0]; d.y = n[1]; d.z = n[2]; d.w = 0.0f;
-	dst[0] = a; dst[1] = b; dst[2] = c; dst[3] = d;
+	out[id] = make_tri64(w[0], w[1], w[2], id, in.layers);
 }
 
 // A BLAS built on its own (refs from 0) into its place in a two-level scene's node array
@@ -836,8 +731,7 @@ __global__ __launch_bounds__(LBVH_WG) void offset_refs_kernel(DevNode *dst, cons
 	const uint32_t i = blockIdx.x * LBVH_WG + threadIdx.x;
 	if (i >= n) return;
 	DevNode g = src[i];
-	auto fix = [&](uint32_t ref) { return ref < kSentinel ? ref + node_base : (ref >= kLeafBit ? (kLeafBit | ((ref & 0x7FFFFFFFu) + tri_base)) : ref); };
-	g.left_ref = fix(g.left_ref); g.right_ref = fix(g.right_ref);
+	g.left_ref = rebase_ref(g.left_ref, node_base, tri_base); g.right_ref = rebase_ref(g.right_ref, node_base, tri_base);
 	dst[i] = g;
 }
 
@@ -847,10 +741,7 @@ __global__ __launch_bounds__(LBVH_WG) void offset_refs8_kernel(Dev8Node *dst, co
 	const uint32_t i = blockIdx.x * LBVH_WG + threadIdx.x;
 	if (i >= n) return;
 	Dev8Node g = src[i];
-	for (int c = 0; c < 8; c++) {
-		const uint32_t ref = g.ref[c];
-		g.ref[c] = ref < kSentinel ? ref + node_base : (ref >= kLeafBit ? (kLeafBit | ((ref & 0x7FFFFFFFu) + tri_base)) : ref);
-	}
+	for (int c = 0; c < 8; c++) g.ref[c] = rebase_ref(g.ref[c], node_base, tri_base);
 	dst[i] = g;
 }
 
@@ -895,15 +786,223 @@ hipError_t launch_flatten_instances(const float *d_verts9, const mrt_instance *d
 	return hipGetLastError();
 }
 
+// the context's arena at least `need` bytes large: a larger one is allocated after the stream has drained (a kernel may still use
+// the old one).  hipErrorOutOfMemory: the allocation failed and the arena is empty; any other error is the synchronisation's.
+hipError_t grow_arena(BuildArena *arena, size_t need, hipStream_t stream)
+{
+	if (arena->cap >= need) return hipSuccess;
+	if (arena->ptr) { // (nothing runs on an arena that does not exist yet)
+		const hipError_t e = hipStreamSynchronize(stream);
+		if (e != hipSuccess) return e;
+		(void)hipFree(arena->ptr);
+		arena->ptr = nullptr; arena->cap = 0;
+	}
+	if (hipMalloc(&arena->ptr, need) != hipSuccess) { arena->ptr = nullptr; return hipErrorOutOfMemory; }
+	arena->cap = need;
+	return hipSuccess;
+}
+
+namespace {
+
 #define DB_TRY(call)                                                                                    \
 	do {                                                                                                 \
 		hipError_t e_ = (call);                                                                          \
 		if (e_ != hipSuccess) {                                                                          \
-			std::snprintf(err, err_len, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-			cleanup();                                                                                   \
+			std::snprintf(B.err, B.err_len, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
 			return MRT_ERR_HIP;                                                                          \
 		}                                                                                                \
 	} while (0)
+#define DB_FAIL(...) do { std::snprintf(B.err, B.err_len, __VA_ARGS__); return MRT_ERR_HIP; } while (0)
+
+// What every form of a build works with: the input, the part of the arena all forms use, the scene's new arrays (nodes4 / nodes8 /
+// leaf_box null if not wanted), and what the tail reads back.
+struct Build {
+	hipStream_t stream; const mrt_tri64 *d_tris; uint32_t n, blocks; // blocks: of LBVH_WG threads over the n triangles
+	BuildArena *arena; char *err; size_t err_len;
+	Box *boxes; uint32_t *scal; // scal: bounds[6], max_depth, 8-wide "bad" flag, verification failures, [10..11] PLOC round totals, [12..14] SAH counters
+	uint64_t *keys_a, *keys_b; uint32_t *idx_a, *idx_b, *node_depth; void *tmp; size_t tmp_bytes, scan_bytes; // tmp: rocPRIM's workspace
+	DevNode *nodes; TriHot *hot; TriCold *cold; Dev4Node *nodes4; Dev8Node *nodes8; float *leaf_box;
+	uint32_t n_rows, h[16]; // the node rows the form made; scal as the tail read it back
+};
+// the temporaries of one form each; the three share their place in the arena, as only one of them runs
+struct RadixArena { uint32_t *left, *right, *par_node, *par_leaf, *arrivals; Box *node_box; };
+struct PlocArena { Box *cbox[2]; uint32_t *cref[2], *cdep[2], *nn; unsigned long long *flags, *pos; DevNode *staged; uint32_t *sdepth; }; // two cluster lines, neighbours, flags, positions, staged rows
+struct SahArena { SahNode *snodes; uint32_t *slot_of, *split_of, *size, *height, *rank, *first, *open[2], *node_of, *bins; }; // 2 n nodes with their side arrays, the open lists, node_of, the bins of the widest level (<= n / 2 open nodes)
+
+// one allocation, carved in 256-byte steps (base 0: only the sizes are wanted); end = the furthest any carving went
+struct Carver {
+	uintptr_t base; size_t used = 0; size_t *end;
+	template <class T> T *take(size_t count) { T *p = (T *)(base + used); used += align256(count * sizeof(T)); if (used > *end) *end = used; return p; }
+};
+// a by value: each form starts where the common part ends; the fields in their struct's order (a braced list runs left to right)
+RadixArena carve_radix(Carver a, size_t nn)
+{
+	return { a.take<uint32_t>(nn), a.take<uint32_t>(nn), a.take<uint32_t>(nn), a.take<uint32_t>(nn), a.take<uint32_t>(nn), a.take<Box>(nn) };
+}
+PlocArena carve_ploc(Carver a, size_t nn)
+{
+	return { { a.take<Box>(nn), a.take<Box>(nn) }, { a.take<uint32_t>(nn), a.take<uint32_t>(nn) }, { a.take<uint32_t>(nn), a.take<uint32_t>(nn) },
+			a.take<uint32_t>(nn), a.take<unsigned long long>(nn), a.take<unsigned long long>(nn), a.take<DevNode>(nn), a.take<uint32_t>(nn) };
+}
+SahArena carve_sah(Carver a, size_t nn)
+{
+	return { a.take<SahNode>(2 * nn), a.take<uint32_t>(2 * nn), a.take<uint32_t>(2 * nn), a.take<uint32_t>(2 * nn), a.take<uint32_t>(2 * nn),
+			a.take<uint32_t>(2 * nn), a.take<uint32_t>(2 * nn), { a.take<uint32_t>(nn), a.take<uint32_t>(nn) }, a.take<uint32_t>(nn),
+			a.take<uint32_t>((nn / 2 + SAH_LDS_SLOTS) * SAH_SLOT_WORDS) };
+}
+
+// The end of every form, over the B.n_rows rows it made: the verification pass (not for a wrapped root: it has no child rows), the
+// wide layouts, the scalars read back.  A tree that failed its verification is an error unless the caller has a retry.
+int build_tail(Build &B, bool verify, bool retry)
+{
+	const uint32_t rb = (B.n_rows + LBVH_WG - 1) / LBVH_WG;
+	if (verify) hipLaunchKernelGGL(lbvh_verify_kernel, dim3(rb), dim3(LBVH_WG), 0, B.stream, B.nodes, B.n_rows, B.boxes, B.idx_b, B.node_depth, B.scal + 6, B.scal + 8);
+	if (B.nodes4) hipLaunchKernelGGL(lbvh_collapse4_kernel, dim3(rb), dim3(LBVH_WG), 0, B.stream, B.nodes, B.n_rows, B.nodes4);
+	if (B.nodes8) hipLaunchKernelGGL(lbvh_collapse8_kernel, dim3(rb), dim3(LBVH_WG), 0, B.stream, B.nodes, B.n_rows, B.nodes8, B.leaf_box, B.scal + 7);
+	DB_TRY(hipGetLastError());
+	DB_TRY(hipMemcpyAsync(B.h, B.scal, sizeof(B.h), hipMemcpyDeviceToHost, B.stream));
+	DB_TRY(hipStreamSynchronize(B.stream));
+	if (B.h[8] != 0u && !retry) DB_FAIL("device build: the tree failed its verification pass (%u nodes)", B.h[8]);
+	return MRT_OK;
+}
+
+// steps 2, 3 and 6 of the radix tree and PLOC: Morton keys, their sort, the triangle rows in sorted order
+int sort_by_morton_key(Build &B)
+{
+	hipLaunchKernelGGL(lbvh_keys_kernel, dim3(B.blocks), dim3(LBVH_WG), 0, B.stream, B.boxes, B.n, B.scal, B.keys_a, B.idx_a);
+	DB_TRY(rocprim::radix_sort_pairs(B.tmp, B.tmp_bytes, B.keys_a, B.keys_b, B.idx_a, B.idx_b, (size_t)B.n, 0, 63, B.stream));
+	hipLaunchKernelGGL(lbvh_leaves_kernel, dim3(B.blocks), dim3(LBVH_WG), 0, B.stream, B.d_tris, B.n, B.idx_b, (const uint32_t *)nullptr, B.hot, B.cold);
+	return MRT_OK;
+}
+
+int build_radix_tree(Build &B, const RadixArena &R, bool safe_handoff)
+{
+	const uint32_t n = B.n;
+	int rc = sort_by_morton_key(B);
+	if (rc) return rc;
+	DB_TRY(hipMemsetAsync(R.arrivals, 0, (size_t)n * 4, B.stream));
+	hipLaunchKernelGGL(lbvh_hierarchy_kernel, dim3(B.blocks), dim3(LBVH_WG), 0, B.stream, B.keys_b, n, R.left, R.right, R.par_node, R.par_leaf);
+	// attempt 0: write-through hand-off; attempt 1: acquire-release hand-off, if the verification failed (or asked for)
+	for (int attempt = safe_handoff ? 1 : 0;; attempt++) {
+		if (attempt == 0)
+			hipLaunchKernelGGL(lbvh_fit_kernel<false>, dim3(B.blocks), dim3(LBVH_WG), 0, B.stream, n, B.boxes, B.idx_b, R.left, R.right, R.par_node, R.par_leaf,
+					R.arrivals, R.node_box, B.node_depth, B.nodes, B.scal + 6);
+		else {
+			DB_TRY(hipMemsetAsync(R.arrivals, 0, (size_t)n * 4, B.stream));
+			DB_TRY(hipMemsetAsync(B.scal + 6, 0, 3 * sizeof(uint32_t), B.stream));
+			hipLaunchKernelGGL(lbvh_fit_kernel<true>, dim3(B.blocks), dim3(LBVH_WG), 0, B.stream, n, B.boxes, B.idx_b, R.left, R.right, R.par_node, R.par_leaf,
+					R.arrivals, R.node_box, B.node_depth, B.nodes, B.scal + 6);
+		}
+		if ((rc = build_tail(B, true, attempt == 0))) return rc;
+		if (B.h[8] == 0u) return MRT_OK;
+	}
+}
+
+// PLOC: rounds of nearest neighbour / flags / prefix sum / merge on the line of clusters
+int build_ploc(Build &B, const PlocArena &P)
+{
+	const uint32_t n = B.n;
+	int rc = sort_by_morton_key(B);
+	if (rc) return rc;
+	hipLaunchKernelGGL(ploc_init_kernel, dim3(B.blocks), dim3(LBVH_WG), 0, B.stream, B.boxes, B.idx_b, n, P.cbox[0], P.cref[0], P.cdep[0]);
+	uint32_t m = n, node_base = 0u;
+	int cur = 0;
+	int ploc_radius = 8;
+	if (const char *e = std::getenv("MRT_PLOC_RADIUS")) { const int r = std::atoi(e); if (r >= 1 && r <= PLOC_R_MAX) ploc_radius = r; } // tuning knob (tools/bench_build.py)
+	for (uint32_t round = 0; m > 1u; round++) {
+		if (round > 4096u) DB_FAIL("device build: clustering did not converge");
+		const uint32_t mb = (m + LBVH_WG - 1) / LBVH_WG;
+		hipLaunchKernelGGL(ploc_nn_kernel, dim3(mb), dim3(LBVH_WG), 0, B.stream, P.cbox[cur], m, ploc_radius, P.nn);
+		hipLaunchKernelGGL(ploc_flags_kernel, dim3(mb), dim3(LBVH_WG), 0, B.stream, P.nn, m, P.flags);
+		DB_TRY(rocprim::exclusive_scan(B.tmp, B.scan_bytes, P.flags, P.pos, 0ull, (size_t)m, rocprim::plus<unsigned long long>(), B.stream));
+		hipLaunchKernelGGL(ploc_merge_kernel, dim3(mb), dim3(LBVH_WG), 0, B.stream, P.cbox[cur], P.cref[cur], P.cdep[cur], P.nn, P.flags, P.pos, m, node_base,
+				P.cbox[cur ^ 1], P.cref[cur ^ 1], P.cdep[cur ^ 1], P.staged, P.sdepth, B.scal + 10);
+		uint32_t totals[2];
+		DB_TRY(hipMemcpyAsync(totals, B.scal + 10, sizeof(totals), hipMemcpyDeviceToHost, B.stream));
+		DB_TRY(hipStreamSynchronize(B.stream));
+		if (totals[1] == 0u || totals[0] + totals[1] != m) DB_FAIL("device build: a clustering round made no progress");
+		m = totals[0]; node_base += totals[1];
+		cur ^= 1;
+	}
+	if (node_base != n - 1u) DB_FAIL("device build: clustering produced %u nodes for %u triangles", node_base, n);
+	hipLaunchKernelGGL(ploc_finish_kernel, dim3(B.blocks), dim3(LBVH_WG), 0, B.stream, P.staged, P.sdepth, n - 1, B.nodes, B.node_depth, B.scal + 6);
+	return build_tail(B, true, false);
+}
+
+// binned SAH, level by level
+int build_sah(Build &B, const SahArena &S)
+{
+	const uint32_t n = B.n;
+	const size_t nn = n;
+	hipStream_t stream = B.stream;
+	if (!B.arena->pinned) DB_TRY(hipHostMalloc((void **)&B.arena->pinned, 64));
+	uint32_t *ctr = B.scal + 12; // [12] next free node id, [13] open nodes of the next level, [14] the triangles in them
+	// the list of active triangles and its sort keys, in / out of the sort: the halves of the two Morton-key arrays (unused by this form)
+	uint32_t *key_in = (uint32_t *)B.keys_a, *val_in = key_in + nn, *key_out = (uint32_t *)B.keys_b, *val_out = key_out + nn;
+	DB_TRY(hipMemsetAsync(S.node_of, 0, nn * 4, stream));
+	hipLaunchKernelGGL(sah_root_kernel, dim3(1), dim3(1), 0, stream, S.snodes, n, B.scal, S.slot_of, S.open[0], S.rank, S.first, ctr);
+	std::vector<uint32_t> level_lo; // ids of the nodes of depth d: [level_lo[d], level_lo[d + 1])
+	level_lo.push_back(0u); level_lo.push_back(1u);
+	uint32_t n_open = 1u, n_ids = 1u, n_list = n, n_act = n; // n_list: triangles on the list; n_act: those in this level's open nodes
+	const uint32_t *act = nullptr;                          // nullptr: the list is every triangle, in index order
+	int cur = 0;
+	while (n_open > 0u) {
+		if (level_lo.size() > 4096u) DB_FAIL("device build: the SAH subdivision did not end");
+		if ((size_t)n_open > nn / 2 + SAH_LDS_SLOTS || n_act > n_list) DB_FAIL("device build: inconsistent SAH level (%u open nodes, %u of %u triangles)", n_open, n_act, n_list);
+		DB_TRY(hipMemsetAsync(ctr + 1, 0, 8, stream)); // (ctr[0], the next free id, runs on from level to level)
+		DB_TRY(hipMemsetAsync(S.bins, 0, (size_t)(n_open < SAH_LDS_SLOTS ? SAH_LDS_SLOTS : n_open) * SAH_SLOT_WORDS * 4, stream));
+		if (act == nullptr && n_open <= SAH_LDS_SLOTS)
+			hipLaunchKernelGGL(sah_bin_kernel, dim3(B.blocks < 1024u ? B.blocks : 1024u), dim3(LBVH_WG), 0, stream, B.boxes, n, S.node_of, S.snodes, S.slot_of, S.split_of, S.bins);
+		else {
+			hipLaunchKernelGGL(sah_descend_kernel, dim3((n_list + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, B.boxes, act, n_list, S.node_of, S.snodes, S.slot_of, S.split_of, key_in, val_in);
+			// the closed triangles' key is all ones: above every slot in the low `bits` bits too
+			const unsigned bits = 32u - (unsigned)__builtin_clz(n_open);
+			size_t sort32 = 0;
+			DB_TRY(rocprim::radix_sort_pairs(nullptr, sort32, key_in, key_out, val_in, val_out, (size_t)n_list, 0, bits, stream));
+			if (sort32 > B.tmp_bytes) DB_FAIL("device build: sort workspace");
+			DB_TRY(rocprim::radix_sort_pairs(B.tmp, sort32, key_in, key_out, val_in, val_out, (size_t)n_list, 0, bits, stream));
+			act = val_out; n_list = n_act;
+			hipLaunchKernelGGL(sah_bin_sorted_kernel, dim3((n_list + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, B.boxes, act, key_out, n_list, S.node_of, S.snodes, S.bins);
+		}
+		hipLaunchKernelGGL(sah_split_kernel, dim3((n_open + 63u) / 64u), dim3(64), 0, stream, S.snodes, S.open[cur], n_open, S.bins, S.slot_of, S.split_of, ctr, S.open[cur ^ 1], B.scal);
+		uint32_t *got = B.arena->pinned;
+		DB_TRY(hipMemcpyAsync(got, ctr, 12, hipMemcpyDeviceToHost, stream));
+		DB_TRY(hipStreamSynchronize(stream));
+		if (got[0] < n_ids || got[0] > 2u * n - 1u) DB_FAIL("device build: the SAH subdivision made %u nodes for %u triangles", got[0], n);
+		if (got[0] > n_ids) level_lo.push_back(got[0]);
+		n_ids = got[0]; n_open = got[1]; n_act = got[2];
+		cur ^= 1;
+	}
+	// the triangles of the nodes split last still sit in their parent: one more descent
+	hipLaunchKernelGGL(sah_descend_kernel, dim3((n_list + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, B.boxes, act, n_list, S.node_of, S.snodes, S.slot_of, S.split_of, key_in, val_in);
+	const uint32_t depths = (uint32_t)level_lo.size() - 1u;
+	uint32_t wrap_lc = 0u;
+	if (n_ids == 1u) { // the root stayed a leaf (coincident triangles): one row, its halves
+		wrap_lc = (n + 1u) / 2u; B.n_rows = 1u;
+		hipLaunchKernelGGL(sah_wrap_kernel, dim3(1), dim3(1), 0, stream, B.scal, n, wrap_lc, B.nodes, B.node_depth, B.scal + 6);
+	} else {
+		B.n_rows = (n_ids - 1u) / 2u;
+		for (uint32_t d = depths; d-- > 0u;) {
+			const uint32_t lo = level_lo[d], hi = level_lo[d + 1];
+			hipLaunchKernelGGL(sah_size_kernel, dim3((hi - lo + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, S.snodes, lo, hi, S.size, S.height);
+		}
+		for (uint32_t d = 0; d < depths; d++) {
+			const uint32_t lo = level_lo[d], hi = level_lo[d + 1];
+			hipLaunchKernelGGL(sah_emit_kernel, dim3((hi - lo + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, S.snodes, lo, hi, S.size, S.height, S.rank, S.first,
+					B.nodes, B.node_depth, B.scal + 6);
+		}
+	}
+	uint32_t *key32_a = (uint32_t *)B.keys_a, *key32_b = (uint32_t *)B.keys_b;
+	hipLaunchKernelGGL(sah_keys_kernel, dim3(B.blocks), dim3(LBVH_WG), 0, stream, S.node_of, S.first, n, wrap_lc, key32_a, B.idx_a);
+	size_t sort32 = 0;
+	DB_TRY(rocprim::radix_sort_pairs(nullptr, sort32, key32_a, key32_b, B.idx_a, B.idx_b, nn, 0, 32, stream));
+	if (sort32 > B.tmp_bytes) DB_FAIL("device build: sort workspace");
+	DB_TRY(rocprim::radix_sort_pairs(B.tmp, sort32, key32_a, key32_b, B.idx_a, B.idx_b, nn, 0, 32, stream));
+	hipLaunchKernelGGL(lbvh_leaves_kernel, dim3(B.blocks), dim3(LBVH_WG), 0, stream, B.d_tris, n, B.idx_b, (const uint32_t *)key32_b, B.hot, B.cold);
+	return build_tail(B, !wrap_lc, false);
+}
+
+} // namespace
 
 // Builds nodes / hot / cold (and nodes4 / nodes8 if wanted; hipMalloc'ed, owned by the caller on success) for
 // the n >= 2 triangles at d_tris (device), or, with d_tris == nullptr, the n boxes at out->boxes_in (hot[slot].id = the box of the slot,
@@ -912,223 +1011,59 @@ hipError_t launch_flatten_instances(const float *d_verts9, const mrt_instance *d
 int device_build_lbvh(const mrt_tri64 *d_tris, uint32_t n, bool want4, bool want8, bool safe_handoff, int form, BuildArena *arena, void *stream_,
 		DeviceBuildResult *out, char *err, size_t err_len)
 {
-	hipStream_t stream = (hipStream_t)stream_;
-	DevNode *nodes = nullptr; TriHot *hot = nullptr; TriCold *cold = nullptr; Dev4Node *nodes4 = nullptr; Dev8Node *nodes8 = nullptr;
-	float *leaf_box = nullptr;
-	auto cleanup = [&] {
-		if (nodes) (void)hipFree(nodes);
-		if (nodes4) (void)hipFree(nodes4);
-		if (nodes8) (void)hipFree(nodes8);
-		if (leaf_box) (void)hipFree(leaf_box);
-		if (hot) (void)hipFree(hot);
-		if (cold) (void)hipFree(cold);
-	};
+	Build B{};
+	B.stream = (hipStream_t)stream_; B.d_tris = d_tris; B.n = n; B.arena = arena; B.err = err; B.err_len = err_len;
 	const size_t nn = n;
-	// ---- the arena: one allocation, carved in 256-byte steps ----
-	size_t sort_bytes = 0, scan_bytes = 0;
-	DB_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, nn, 0, 63, stream));
-	DB_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0ull, nn, rocprim::plus<unsigned long long>(), stream));
-	size_t need = 0;
-	auto reserve = [&](size_t bytes) { const size_t at = need; need += (bytes + 255u) & ~(size_t)255u; return at; };
-	const size_t o_boxes = reserve(nn * sizeof(Box)), o_scal = reserve(64), o_keys_a = reserve(nn * 8), o_keys_b = reserve(nn * 8),
-			o_idx_a = reserve(nn * 4), o_idx_b = reserve(nn * 4), o_depth = reserve(nn * 4), o_sort = reserve(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
-	// radix-tree form: left / right / parents / arrivals / node boxes; PLOC form: two cluster lines, nn, flags, positions, staged rows
-	const size_t o_left = reserve(nn * 4), o_right = reserve(nn * 4), o_par_node = reserve(nn * 4), o_par_leaf = reserve(nn * 4),
-			o_arrivals = reserve(nn * 4), o_node_box = reserve(nn * sizeof(Box));
-	const size_t lbvh_end = need;
-	need = o_left; // the two forms never run together: their temporaries share the space
-	const size_t o_cbox0 = reserve(nn * sizeof(Box)), o_cbox1 = reserve(nn * sizeof(Box)), o_cref0 = reserve(nn * 4), o_cref1 = reserve(nn * 4),
-			o_cdep0 = reserve(nn * 4), o_cdep1 = reserve(nn * 4), o_nn = reserve(nn * 4), o_flags = reserve(nn * 8), o_pos = reserve(nn * 8),
-			o_staged = reserve(nn * sizeof(DevNode)), o_sdepth = reserve(nn * 4);
-	const size_t ploc_end = need;
-	need = o_left;
-	// binned-SAH form: 2 n nodes with their side arrays, the open lists, node_of, the bins of the widest level (<= n / 2 open nodes)
-	const size_t o_snodes = reserve(2 * nn * sizeof(SahNode)), o_slot = reserve(2 * nn * 4), o_split = reserve(2 * nn * 4), o_size = reserve(2 * nn * 4),
-			o_height = reserve(2 * nn * 4), o_rank = reserve(2 * nn * 4), o_first = reserve(2 * nn * 4), o_open0 = reserve(nn * 4), o_open1 = reserve(nn * 4),
-			o_node_of = reserve(nn * 4), o_bins = reserve((nn / 2 + SAH_LDS_SLOTS) * SAH_SLOT_WORDS * 4);
-	if (form != 2) need = o_left; // (the bins are 384 bytes per triangle: only a build that asks for this form pays for them)
-	if (need < lbvh_end) need = lbvh_end;
-	if (need < ploc_end) need = ploc_end;
-	if (arena->cap < need) {
-		if (arena->ptr) { DB_TRY(hipStreamSynchronize(stream)); (void)hipFree(arena->ptr); arena->ptr = nullptr; arena->cap = 0; }
-		if (hipMalloc(&arena->ptr, need) != hipSuccess) { arena->ptr = nullptr; std::snprintf(err, err_len, "device build: out of device memory"); return MRT_ERR_OOM; }
-		arena->cap = need;
-	}
-	char *A = (char *)arena->ptr;
-	Box *boxes = (Box *)(A + o_boxes);
-	uint32_t *scal = (uint32_t *)(A + o_scal); // bounds[6], max_depth, 8-wide "bad" flag, verification failures, [10..11] PLOC round totals
-	uint64_t *keys_a = (uint64_t *)(A + o_keys_a), *keys_b = (uint64_t *)(A + o_keys_b);
-	uint32_t *idx_a = (uint32_t *)(A + o_idx_a), *idx_b = (uint32_t *)(A + o_idx_b);
-	uint32_t *node_depth = (uint32_t *)(A + o_depth);
-	void *sort_tmp = A + o_sort;
-	bool ok = hipMalloc(&nodes, (nn - 1) * sizeof(DevNode)) == hipSuccess && hipMalloc(&hot, nn * sizeof(TriHot) + 16) == hipSuccess &&
-			hipMalloc(&cold, nn * sizeof(TriCold)) == hipSuccess &&
-			(!want4 || hipMalloc(&nodes4, (nn - 1) * sizeof(Dev4Node)) == hipSuccess) &&
-			(!want8 || (hipMalloc(&nodes8, (nn - 1) * sizeof(Dev8Node)) == hipSuccess && hipMalloc(&leaf_box, nn * 32) == hipSuccess));
+	B.blocks = (uint32_t)((nn + LBVH_WG - 1) / LBVH_WG);
+	B.n_rows = n - 1u;
+	size_t sort_bytes = 0;
+	DB_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, nn, 0, 63, B.stream));
+	DB_TRY(rocprim::exclusive_scan(nullptr, B.scan_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0ull, nn, rocprim::plus<unsigned long long>(), B.stream));
+	B.tmp_bytes = sort_bytes > B.scan_bytes ? sort_bytes : B.scan_bytes;
+	// the forms share their place behind the common part: sized for the radix tree and PLOC always, for SAH (384 bytes of bins per triangle) on demand
+	RadixArena R{}; PlocArena P{}; SahArena S{};
+	auto carve = [&](uintptr_t base) {
+		size_t end = 0;
+		Carver a{ base, 0, &end };
+		B.boxes = a.take<Box>(nn); B.scal = a.take<uint32_t>(16);
+		B.keys_a = a.take<uint64_t>(nn); B.keys_b = a.take<uint64_t>(nn); B.idx_a = a.take<uint32_t>(nn); B.idx_b = a.take<uint32_t>(nn);
+		B.node_depth = a.take<uint32_t>(nn); B.tmp = a.take<char>(B.tmp_bytes);
+		R = carve_radix(a, nn); P = carve_ploc(a, nn);
+		if (form == 2) S = carve_sah(a, nn);
+		return end;
+	};
+	const hipError_t arena_sync = grow_arena(arena, carve(0), B.stream);
+	if (arena_sync == hipErrorOutOfMemory) { std::snprintf(err, err_len, "device build: out of device memory"); return MRT_ERR_OOM; }
+	DB_TRY(arena_sync);
+	carve((uintptr_t)arena->ptr);
+
+	auto cleanup = [&] { for (void *p : { (void *)B.nodes, (void *)B.nodes4, (void *)B.nodes8, (void *)B.leaf_box, (void *)B.hot, (void *)B.cold }) (void)hipFree(p); }; // (null: a no-op)
+	const bool ok = hipMalloc(&B.nodes, (nn - 1) * sizeof(DevNode)) == hipSuccess && hipMalloc(&B.hot, nn * sizeof(TriHot) + 16) == hipSuccess &&
+			hipMalloc(&B.cold, nn * sizeof(TriCold)) == hipSuccess &&
+			(!want4 || hipMalloc(&B.nodes4, (nn - 1) * sizeof(Dev4Node)) == hipSuccess) &&
+			(!want8 || (hipMalloc(&B.nodes8, (nn - 1) * sizeof(Dev8Node)) == hipSuccess && hipMalloc(&B.leaf_box, nn * 32) == hipSuccess));
 	if (!ok) { std::snprintf(err, err_len, "device build: out of device memory"); cleanup(); return MRT_ERR_OOM; }
 
-	const uint32_t blocks = (uint32_t)((nn + LBVH_WG - 1) / LBVH_WG);
-	const uint32_t init[16] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
-	DB_TRY(hipMemcpyAsync(scal, init, sizeof(init), hipMemcpyHostToDevice, stream));
-	hipLaunchKernelGGL(lbvh_bounds_kernel, dim3(blocks < LBVH_BOUNDS_BLOCKS ? blocks : LBVH_BOUNDS_BLOCKS), dim3(LBVH_WG), 0, stream,
-			d_tris, (const Box *)out->boxes_in, n, boxes, scal);
-	if (form != 2) {
-		hipLaunchKernelGGL(lbvh_keys_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, boxes, n, scal, keys_a, idx_a);
-		DB_TRY(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, keys_a, keys_b, idx_a, idx_b, nn, 0, 63, stream));
-	}
-	if (form != 2) hipLaunchKernelGGL(lbvh_leaves_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, d_tris, n, idx_b, (const uint32_t *)nullptr, hot, cold);
-	uint32_t h[16];
-	uint32_t n_rows = n - 1u;
-	if (form == 2) {
-		// ---- binned SAH, level by level ----
-		SahNode *snodes = (SahNode *)(A + o_snodes);
-		uint32_t *slot_of = (uint32_t *)(A + o_slot), *split_of = (uint32_t *)(A + o_split), *size = (uint32_t *)(A + o_size), *height = (uint32_t *)(A + o_height),
-				*rank = (uint32_t *)(A + o_rank), *first = (uint32_t *)(A + o_first), *node_of = (uint32_t *)(A + o_node_of), *bins = (uint32_t *)(A + o_bins);
-		uint32_t *open[2] = { (uint32_t *)(A + o_open0), (uint32_t *)(A + o_open1) };
-		if (!arena->pinned) DB_TRY(hipHostMalloc((void **)&arena->pinned, 64));
-		uint32_t *ctr = scal + 12; // [12] next free node id, [13] open nodes of the next level, [14] the triangles in them
-		// the list of active triangles and its sort keys, in / out of the sort: the halves of the two Morton-key arrays (unused by this form)
-		uint32_t *key_in = (uint32_t *)keys_a, *val_in = key_in + nn, *key_out = (uint32_t *)keys_b, *val_out = key_out + nn;
-		DB_TRY(hipMemsetAsync(node_of, 0, nn * 4, stream));
-		hipLaunchKernelGGL(sah_root_kernel, dim3(1), dim3(1), 0, stream, snodes, n, scal, slot_of, open[0], rank, first, ctr);
-		std::vector<uint32_t> level_lo; // ids of the nodes of depth d: [level_lo[d], level_lo[d + 1])
-		level_lo.push_back(0u); level_lo.push_back(1u);
-		uint32_t n_open = 1u, n_ids = 1u, n_list = n, n_act = n; // n_list: triangles on the list; n_act: those in this level's open nodes
-		const uint32_t *act = nullptr;                          // nullptr: the list is every triangle, in index order
-		int cur = 0;
-		while (n_open > 0u) {
-			if (level_lo.size() > 4096u) { std::snprintf(err, err_len, "device build: the SAH subdivision did not end"); cleanup(); return MRT_ERR_HIP; }
-			if ((size_t)n_open > nn / 2 + SAH_LDS_SLOTS || n_act > n_list) { std::snprintf(err, err_len, "device build: inconsistent SAH level (%u open nodes, %u of %u triangles)", n_open, n_act, n_list); cleanup(); return MRT_ERR_HIP; }
-			DB_TRY(hipMemsetAsync(ctr + 1, 0, 8, stream)); // (ctr[0], the next free id, runs on from level to level)
-			DB_TRY(hipMemsetAsync(bins, 0, (size_t)(n_open < SAH_LDS_SLOTS ? SAH_LDS_SLOTS : n_open) * SAH_SLOT_WORDS * 4, stream));
-			if (act == nullptr && n_open <= SAH_LDS_SLOTS)
-				hipLaunchKernelGGL(sah_bin_kernel, dim3(blocks < 1024u ? blocks : 1024u), dim3(LBVH_WG), 0, stream, boxes, n, node_of, snodes, slot_of, split_of, bins);
-			else {
-				hipLaunchKernelGGL(sah_descend_kernel, dim3((n_list + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, boxes, act, n_list, node_of, snodes, slot_of, split_of, key_in, val_in);
-				// the closed triangles' key is all ones: above every slot in the low `bits` bits too
-				const unsigned bits = 32u - (unsigned)__builtin_clz(n_open);
-				size_t sort32 = 0;
-				DB_TRY(rocprim::radix_sort_pairs(nullptr, sort32, key_in, key_out, val_in, val_out, (size_t)n_list, 0, bits, stream));
-				if (sort32 > (sort_bytes > scan_bytes ? sort_bytes : scan_bytes)) { std::snprintf(err, err_len, "device build: sort workspace"); cleanup(); return MRT_ERR_HIP; }
-				DB_TRY(rocprim::radix_sort_pairs(sort_tmp, sort32, key_in, key_out, val_in, val_out, (size_t)n_list, 0, bits, stream));
-				act = val_out; n_list = n_act;
-				hipLaunchKernelGGL(sah_bin_sorted_kernel, dim3((n_list + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, boxes, act, key_out, n_list, node_of, snodes, bins);
-			}
-			hipLaunchKernelGGL(sah_split_kernel, dim3((n_open + 63u) / 64u), dim3(64), 0, stream, snodes, open[cur], n_open, bins, slot_of, split_of, ctr, open[cur ^ 1], scal);
-			uint32_t *got = arena->pinned;
-			DB_TRY(hipMemcpyAsync(got, ctr, 12, hipMemcpyDeviceToHost, stream));
-			DB_TRY(hipStreamSynchronize(stream));
-			if (got[0] < n_ids || got[0] > 2u * n - 1u) { std::snprintf(err, err_len, "device build: the SAH subdivision made %u nodes for %u triangles", got[0], n); cleanup(); return MRT_ERR_HIP; }
-			if (got[0] > n_ids) level_lo.push_back(got[0]);
-			n_ids = got[0]; n_open = got[1]; n_act = got[2];
-			cur ^= 1;
-		}
-		// the triangles of the nodes split last still sit in their parent: one more descent
-		hipLaunchKernelGGL(sah_descend_kernel, dim3((n_list + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, boxes, act, n_list, node_of, snodes, slot_of, split_of, key_in, val_in);
-		const uint32_t depths = (uint32_t)level_lo.size() - 1u;
-		uint32_t wrap_lc = 0u;
-		if (n_ids == 1u) { // the root stayed a leaf (coincident triangles): one row, its halves
-			wrap_lc = (n + 1u) / 2u; n_rows = 1u;
-			hipLaunchKernelGGL(sah_wrap_kernel, dim3(1), dim3(1), 0, stream, scal, n, wrap_lc, nodes, node_depth, scal + 6);
-		} else {
-			n_rows = (n_ids - 1u) / 2u;
-			for (uint32_t d = depths; d-- > 0u;) {
-				const uint32_t lo = level_lo[d], hi = level_lo[d + 1];
-				hipLaunchKernelGGL(sah_size_kernel, dim3((hi - lo + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, snodes, lo, hi, size, height);
-			}
-			for (uint32_t d = 0; d < depths; d++) {
-				const uint32_t lo = level_lo[d], hi = level_lo[d + 1];
-				hipLaunchKernelGGL(sah_emit_kernel, dim3((hi - lo + LBVH_WG - 1) / LBVH_WG), dim3(LBVH_WG), 0, stream, snodes, lo, hi, size, height, rank, first,
-						nodes, node_depth, scal + 6);
-			}
-		}
-		uint32_t *key32_a = (uint32_t *)keys_a, *key32_b = (uint32_t *)keys_b;
-		hipLaunchKernelGGL(sah_keys_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, node_of, first, n, wrap_lc, key32_a, idx_a);
-		size_t sort32 = 0;
-		DB_TRY(rocprim::radix_sort_pairs(nullptr, sort32, key32_a, key32_b, idx_a, idx_b, nn, 0, 32, stream));
-		if (sort32 > (sort_bytes > scan_bytes ? sort_bytes : scan_bytes)) { std::snprintf(err, err_len, "device build: sort workspace"); cleanup(); return MRT_ERR_HIP; }
-		DB_TRY(rocprim::radix_sort_pairs(sort_tmp, sort32, key32_a, key32_b, idx_a, idx_b, nn, 0, 32, stream));
-		hipLaunchKernelGGL(lbvh_leaves_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, d_tris, n, idx_b, (const uint32_t *)key32_b, hot, cold);
-		const uint32_t rb = (n_rows + LBVH_WG - 1) / LBVH_WG;
-		if (!wrap_lc) hipLaunchKernelGGL(lbvh_verify_kernel, dim3(rb), dim3(LBVH_WG), 0, stream, nodes, n_rows, boxes, idx_b, node_depth, scal + 6, scal + 8);
-		if (want4) hipLaunchKernelGGL(lbvh_collapse4_kernel, dim3(rb), dim3(LBVH_WG), 0, stream, nodes, n_rows, nodes4);
-		if (want8) hipLaunchKernelGGL(lbvh_collapse8_kernel, dim3(rb), dim3(LBVH_WG), 0, stream, nodes, n_rows, nodes8, leaf_box, scal + 7);
-		DB_TRY(hipGetLastError());
-		DB_TRY(hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, stream));
-		DB_TRY(hipStreamSynchronize(stream));
-		if (h[8] != 0u) { std::snprintf(err, err_len, "device build: the tree failed its verification pass (%u nodes)", h[8]); cleanup(); return MRT_ERR_HIP; }
-	} else if (form == 1) {
-		// ---- PLOC: rounds of nearest neighbour / flags / prefix sum / merge on the line of clusters ----
-		Box *cbox[2] = { (Box *)(A + o_cbox0), (Box *)(A + o_cbox1) };
-		uint32_t *cref[2] = { (uint32_t *)(A + o_cref0), (uint32_t *)(A + o_cref1) }, *cdep[2] = { (uint32_t *)(A + o_cdep0), (uint32_t *)(A + o_cdep1) };
-		uint32_t *nnb = (uint32_t *)(A + o_nn);
-		unsigned long long *flags = (unsigned long long *)(A + o_flags), *pos = (unsigned long long *)(A + o_pos);
-		DevNode *staged = (DevNode *)(A + o_staged);
-		uint32_t *sdepth = (uint32_t *)(A + o_sdepth);
-		hipLaunchKernelGGL(ploc_init_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, boxes, idx_b, n, cbox[0], cref[0], cdep[0]);
-		uint32_t m = n, node_base = 0u;
-		int cur = 0;
-		int ploc_radius = 8;
-		if (const char *e = std::getenv("MRT_PLOC_RADIUS")) { const int r = std::atoi(e); if (r >= 1 && r <= PLOC_R_MAX) ploc_radius = r; } // tuning knob (tools/bench_build.py)
-		for (uint32_t round = 0; m > 1u; round++) {
-			if (round > 4096u) { std::snprintf(err, err_len, "device build: clustering did not converge"); cleanup(); return MRT_ERR_HIP; }
-			const uint32_t mb = (m + LBVH_WG - 1) / LBVH_WG;
-			hipLaunchKernelGGL(ploc_nn_kernel, dim3(mb), dim3(LBVH_WG), 0, stream, cbox[cur], m, ploc_radius, nnb);
-			hipLaunchKernelGGL(ploc_flags_kernel, dim3(mb), dim3(LBVH_WG), 0, stream, nnb, m, flags);
-			DB_TRY(rocprim::exclusive_scan(sort_tmp, scan_bytes, flags, pos, 0ull, (size_t)m, rocprim::plus<unsigned long long>(), stream));
-			hipLaunchKernelGGL(ploc_merge_kernel, dim3(mb), dim3(LBVH_WG), 0, stream, cbox[cur], cref[cur], cdep[cur], nnb, flags, pos, m, node_base,
-					cbox[cur ^ 1], cref[cur ^ 1], cdep[cur ^ 1], staged, sdepth, scal + 10);
-			uint32_t totals[2];
-			DB_TRY(hipMemcpyAsync(totals, scal + 10, sizeof(totals), hipMemcpyDeviceToHost, stream));
-			DB_TRY(hipStreamSynchronize(stream));
-			if (totals[1] == 0u || totals[0] + totals[1] != m) { std::snprintf(err, err_len, "device build: a clustering round made no progress"); cleanup(); return MRT_ERR_HIP; }
-			m = totals[0]; node_base += totals[1];
-			cur ^= 1;
-		}
-		if (node_base != n - 1u) { std::snprintf(err, err_len, "device build: clustering produced %u nodes for %u triangles", node_base, n); cleanup(); return MRT_ERR_HIP; }
-		hipLaunchKernelGGL(ploc_finish_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, staged, sdepth, n - 1, nodes, node_depth, scal + 6);
-		hipLaunchKernelGGL(lbvh_verify_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, nodes, n - 1, boxes, idx_b, node_depth, scal + 6, scal + 8);
-		if (want4) hipLaunchKernelGGL(lbvh_collapse4_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, nodes, n - 1, nodes4);
-		if (want8) hipLaunchKernelGGL(lbvh_collapse8_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, nodes, n - 1, nodes8, leaf_box, scal + 7);
-		DB_TRY(hipGetLastError());
-		DB_TRY(hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, stream));
-		DB_TRY(hipStreamSynchronize(stream));
-		if (h[8] != 0u) { std::snprintf(err, err_len, "device build: the tree failed its verification pass (%u nodes)", h[8]); cleanup(); return MRT_ERR_HIP; }
-	} else {
-		uint32_t *left = (uint32_t *)(A + o_left), *right = (uint32_t *)(A + o_right), *par_node = (uint32_t *)(A + o_par_node), *par_leaf = (uint32_t *)(A + o_par_leaf);
-		uint32_t *arrivals = (uint32_t *)(A + o_arrivals);
-		Box *node_box = (Box *)(A + o_node_box);
-		DB_TRY(hipMemsetAsync(arrivals, 0, nn * 4, stream));
-		hipLaunchKernelGGL(lbvh_hierarchy_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, keys_b, n, left, right, par_node, par_leaf);
-		// attempt 0: write-through hand-off; attempt 1: acquire-release hand-off, if the verification failed (or asked for)
-		for (int attempt = safe_handoff ? 1 : 0;; attempt++) {
-			if (attempt == 0)
-				hipLaunchKernelGGL(lbvh_fit_kernel<false>, dim3(blocks), dim3(LBVH_WG), 0, stream, n, boxes, idx_b, left, right, par_node, par_leaf,
-						arrivals, node_box, node_depth, nodes, scal + 6);
-			else {
-				DB_TRY(hipMemsetAsync(arrivals, 0, nn * 4, stream));
-				DB_TRY(hipMemsetAsync(scal + 6, 0, 3 * sizeof(uint32_t), stream));
-				hipLaunchKernelGGL(lbvh_fit_kernel<true>, dim3(blocks), dim3(LBVH_WG), 0, stream, n, boxes, idx_b, left, right, par_node, par_leaf,
-						arrivals, node_box, node_depth, nodes, scal + 6);
-			}
-			hipLaunchKernelGGL(lbvh_verify_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, nodes, n - 1, boxes, idx_b, node_depth, scal + 6, scal + 8);
-			if (want4) hipLaunchKernelGGL(lbvh_collapse4_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, nodes, n - 1, nodes4);
-			if (want8) hipLaunchKernelGGL(lbvh_collapse8_kernel, dim3(blocks), dim3(LBVH_WG), 0, stream, nodes, n - 1, nodes8, leaf_box, scal + 7);
-			DB_TRY(hipGetLastError());
-			DB_TRY(hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, stream));
-			DB_TRY(hipStreamSynchronize(stream));
-			if (h[8] == 0u) break;
-			if (attempt >= 1) { std::snprintf(err, err_len, "device build: the tree failed its verification pass (%u nodes)", h[8]); cleanup(); return MRT_ERR_HIP; }
-		}
-	}
-	if (out->slot_src) DB_TRY(hipMemcpyAsync(out->slot_src, idx_b, nn * 4, hipMemcpyDeviceToDevice, stream)); // (before the arena is reused)
-	out->nodes = nodes; out->hot = hot; out->cold = cold;
-	out->n_nodes = n_rows; out->n_tris = n;
+	auto run = [&]() -> int {
+		const uint32_t init[16] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+		DB_TRY(hipMemcpyAsync(B.scal, init, sizeof(init), hipMemcpyHostToDevice, B.stream));
+		hipLaunchKernelGGL(lbvh_bounds_kernel, dim3(B.blocks < LBVH_BOUNDS_BLOCKS ? B.blocks : LBVH_BOUNDS_BLOCKS), dim3(LBVH_WG), 0, B.stream,
+				d_tris, (const Box *)out->boxes_in, n, B.boxes, B.scal);
+		const int rc = form == 2 ? build_sah(B, S) : form == 1 ? build_ploc(B, P) : build_radix_tree(B, R, safe_handoff);
+		if (rc) return rc;
+		if (out->slot_src) DB_TRY(hipMemcpyAsync(out->slot_src, B.idx_b, nn * 4, hipMemcpyDeviceToDevice, B.stream)); // (before the arena is reused)
+		return MRT_OK;
+	};
+	const int rc = run();
+	if (rc) { cleanup(); return rc; }
+	const uint32_t *h = B.h;
+	out->nodes = B.nodes; out->hot = B.hot; out->cold = B.cold;
+	out->n_nodes = B.n_rows; out->n_tris = n;
 	out->depth = h[6] + 1u; // pending entries on the deepest path + the sentinel
 	// 4-wide walk: every 4-wide node on a path leaves at most 3 entries pending and descends at least one binary level
-	out->nodes4 = nodes4; out->stack4 = nodes4 ? 3u * h[6] + 1u : 0u;
-	if (nodes8 && h[7] != 0u) { (void)hipFree(nodes8); (void)hipFree(leaf_box); nodes8 = nullptr; leaf_box = nullptr; } // a box that fits no grid: go without this layout
-	out->nodes8 = nodes8; out->leaf_box = leaf_box; out->stack8 = nodes8 ? 7u * h[6] + 1u : 0u;
+	out->nodes4 = B.nodes4; out->stack4 = B.nodes4 ? 3u * h[6] + 1u : 0u;
+	if (B.nodes8 && h[7] != 0u) { (void)hipFree(B.nodes8); (void)hipFree(B.leaf_box); B.nodes8 = nullptr; B.leaf_box = nullptr; } // a box that fits no grid: go without this layout
+	out->nodes8 = B.nodes8; out->leaf_box = B.leaf_box; out->stack8 = B.nodes8 ? 7u * h[6] + 1u : 0u;
 	for (int k = 0; k < 3; k++) { out->bounds_lo[k] = ord2f(h[k]); out->bounds_hi[k] = ord2f(h[3 + k]); }
 	return MRT_OK;
 }

@@ -1,13 +1,14 @@
 // scene_prep.cpp — host-side scene preparation for the device layout.
 //
-//  * mrt_make_triangles / mrt_pack_host_triangles: Triangle ctor and the
-//    Triangle -> GPUTrianglePacked loop (src/core/triangle.h:41-51,
-//    src/gpu/gpu_ray_caster.cpp:205-217).
+//  * mrt_make_triangles / mrt_pack_host_triangles: Triangle ctor (make_tri64,
+//    build_rules.h) and the Triangle -> GPUTrianglePacked loop
+//    (src/gpu/gpu_ray_caster.cpp:205-217).
 //  * prepare_scene: TinyBVH BVH2 -> dual-AABB nodes, the conversion half of
 //    GPURayCaster::upload_scene (src/gpu/gpu_ray_caster.cpp:219-311), with the
 //    prim_idx indirection resolved and arrays sized by used_nodes
 //    (defects 1 and 2), validated before anything is
-//    handed to a kernel.
+//    handed to a kernel; the 4- and 8-wide collapses by the rules the device
+//    builder shares (open_widest, quantise8: build_rules.h).
 //  * mrt_camera_look: camera basis of RayTracerDebug::cast_debug_rays
 //    (src/godot/raytracer_debug.cpp:573-583).
 //
@@ -22,7 +23,7 @@
 #include <new>
 #include <thread>
 #include <vector>
-#include "../mrt_internal.h"
+#include "../build_rules.h"
 
 namespace {
 
@@ -48,14 +49,8 @@ extern "C" int mrt_make_triangles(const float *verts9, const uint32_t *ids, cons
 {
 	if (!verts9 || !out) return MRT_ERR_INVALID;
 	for (uint32_t i = 0; i < n_tris; i++) {
-		const float *a = verts9 + 9 * (size_t)i, *b = a + 3, *c = a + 6;
-		mrt_tri64 &t = out[i];
-		for (int k = 0; k < 3; k++) { t.v0[k] = a[k]; t.edge1[k] = b[k] - a[k]; t.edge2[k] = c[k] - a[k]; }
-		cross3(t.edge1, t.edge2, t.normal);
-		normalize3(t.normal);
-		t.id = ids ? ids[i] : i;
-		t.layers = layers ? layers[i] : 0xFFFFFFFFu;
-		t.pad2 = 0.0f; t.pad3 = 0.0f;
+		const float *a = verts9 + 9 * (size_t)i;
+		out[i] = mrt::make_tri64(a, a + 3, a + 6, ids ? ids[i] : i, layers ? layers[i] : 0xFFFFFFFFu);
 	}
 	return MRT_OK;
 }
@@ -224,20 +219,9 @@ int prepare_scene(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *
 		out->bounds_hi[c] = dev[0].lmax[c] > dev[0].rmax[c] ? dev[0].lmax[c] : dev[0].rmax[c];
 	}
 
-	// ---- 4-wide collapse of the same tree (MRT_KERNEL_LANE4_PERSISTENT) ----
-	// Children of a 4-node: start from the two children of a BVH2 node and keep opening the
-	// internal child with the largest half-area until there are four (or only leaves remain).
+	// ---- 4-wide collapse of the same tree (MRT_KERNEL_LANE4_PERSISTENT): the children of a 4-node by open_widest (build_rules.h) ----
+	auto node_of = [&](uint32_t w) -> const DevNode & { return dev[w]; };
 	{
-		struct Child { float mn[3], mx[3]; uint32_t ref; };
-		auto area = [](const Child &c) {
-			const float e0 = c.mx[0] - c.mn[0], e1 = c.mx[1] - c.mn[1], e2 = c.mx[2] - c.mn[2];
-			return e0 * e1 + e1 * e2 + e2 * e0;
-		};
-		auto children_of = [&](uint32_t w, Child &l, Child &r) {
-			const DevNode &g = dev[w];
-			for (int c = 0; c < 3; c++) { l.mn[c] = g.lmin[c]; l.mx[c] = g.lmax[c]; r.mn[c] = g.rmin[c]; r.mx[c] = g.rmax[c]; }
-			l.ref = g.left_ref; r.ref = g.right_ref;
-		};
 		struct Work { uint32_t w2, idx4, need; };
 		std::vector<Dev4Node> dev4;
 		std::vector<Work> work;
@@ -246,28 +230,22 @@ int prepare_scene(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *
 		uint32_t stack4 = 1;
 		while (!work.empty()) {
 			const Work wk = work.back(); work.pop_back();
-			Child ch[4]; uint32_t n = 2;
-			children_of(wk.w2, ch[0], ch[1]);
-			while (n < 4) {
-				int best = -1; float best_a = -1.0f;
-				for (uint32_t i = 0; i < n; i++) if (ch[i].ref < kSentinel) { const float a = area(ch[i]); if (a > best_a) { best_a = a; best = (int)i; } }
-				if (best < 0) break;
-				Child l, r; children_of(ch[best].ref, l, r);
-				ch[best] = l; ch[n++] = r;
-			}
+			float box[4][6]; uint32_t ref[4];
+			take_children(dev[wk.w2], box, ref, 0, 1);
+			const uint32_t n = open_widest(box, ref, node_of);
 			const uint32_t need = wk.need + (n - 1);
 			if (need + 1 > stack4) stack4 = need + 1;
 			Dev4Node node{};
 			node.n_children = n;
 			for (uint32_t i = 0; i < 4; i++) {
 				if (i < n) {
-					for (int c = 0; c < 3; c++) { node.box[i][c] = ch[i].mn[c]; node.box[i][3 + c] = ch[i].mx[c]; }
-					if (ch[i].ref < kSentinel) {
+					for (int c = 0; c < 6; c++) node.box[i][c] = box[i][c];
+					if (ref[i] < kSentinel) {
 						const uint32_t idx = (uint32_t)dev4.size();
 						dev4.emplace_back();
-						work.push_back({ ch[i].ref, idx, need });
+						work.push_back({ ref[i], idx, need });
 						node.ref[i] = idx;
-					} else node.ref[i] = ch[i].ref;
+					} else node.ref[i] = ref[i];
 				} else {
 					// unused slot: the point box at +inf; its slab test fails for every finite ray interval
 					for (int c = 0; c < 6; c++) node.box[i][c] = std::numeric_limits<float>::infinity();
@@ -288,18 +266,8 @@ int prepare_scene(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *
 	//      that cannot be put on a grid (non-finite) only means the scene goes without it ----
 	bool ok8 = out->want8;
 	if (ok8) {
-		struct Child { float mn[3], mx[3]; uint32_t ref; };
-		auto area = [](const Child &c) {
-			const float e0 = c.mx[0] - c.mn[0], e1 = c.mx[1] - c.mn[1], e2 = c.mx[2] - c.mn[2];
-			return e0 * e1 + e1 * e2 + e2 * e0;
-		};
-		auto children_of = [&](uint32_t w, Child &l, Child &r) {
-			const DevNode &g = dev[w];
-			for (int c = 0; c < 3; c++) { l.mn[c] = g.lmin[c]; l.mx[c] = g.lmax[c]; r.mn[c] = g.rmin[c]; r.mx[c] = g.rmax[c]; }
-			l.ref = g.left_ref; r.ref = g.right_ref;
-		};
 		// phase 1 (sequential, cheap): topology -- which boxes and refs every 8-wide node holds
-		struct Kids { Child ch[8]; uint32_t n; };
+		struct Kids { float box[8][6]; uint32_t ref[8], n; };
 		struct Work { uint32_t w2, idx8, need; };
 		std::vector<Kids> kids;
 		std::vector<Work> work;
@@ -308,23 +276,17 @@ int prepare_scene(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *
 		uint32_t stack8 = 1;
 		while (!work.empty()) {
 			const Work wk = work.back(); work.pop_back();
-			Kids k; k.n = 2;
-			children_of(wk.w2, k.ch[0], k.ch[1]);
-			while (k.n < 8) {
-				int best = -1; float best_a = -1.0f;
-				for (uint32_t i = 0; i < k.n; i++) if (k.ch[i].ref < kSentinel) { const float a = area(k.ch[i]); if (a > best_a) { best_a = a; best = (int)i; } }
-				if (best < 0) break;
-				Child l, r; children_of(k.ch[best].ref, l, r);
-				k.ch[best] = l; k.ch[k.n++] = r;
-			}
+			Kids k;
+			take_children(dev[wk.w2], k.box, k.ref, 0, 1);
+			k.n = open_widest(k.box, k.ref, node_of);
 			const uint32_t need = wk.need + (k.n - 1);
 			if (need + 1 > stack8) stack8 = need + 1;
 			for (uint32_t i = 0; i < k.n; i++) {
-				if (k.ch[i].ref < kSentinel) { // an inner child becomes an 8-wide node of its own
+				if (k.ref[i] < kSentinel) { // an inner child becomes an 8-wide node of its own
 					const uint32_t idx = (uint32_t)kids.size();
 					kids.emplace_back();
-					work.push_back({ k.ch[i].ref, idx, need });
-					k.ch[i].ref = idx;
+					work.push_back({ k.ref[i], idx, need });
+					k.ref[i] = idx;
 				}
 			}
 			kids[wk.idx8] = k;
@@ -340,45 +302,12 @@ int prepare_scene(const mrt_tri64 *tris, uint32_t n_tris, const mrt_bvh_node32 *
 			for (size_t w = first; w < last; w++) {
 				const Kids &k = kids[w];
 				Dev8Node node;
-				std::memset(&node, 0, sizeof(node));
-				node.n_children = (uint8_t)k.n;
-				float scale[3] = { 1.0f, 1.0f, 1.0f };
-				for (int a = 0; a < 3; a++) {
-					float lo = k.ch[0].mn[a], hi = k.ch[0].mx[a];
-					for (uint32_t i = 1; i < k.n; i++) { lo = std::min(lo, k.ch[i].mn[a]); hi = std::max(hi, k.ch[i].mx[a]); }
-					node.org[a] = lo;
-					// smallest power-of-two step with (hi - lo) / step <= 254 (one step of headroom for the outward rounding)
-					int e = 1;
-					const double ext = (double)hi - (double)lo;
-					if (!(ext >= 0.0) || !std::isfinite(ext)) { bad = true; continue; } // NaN / infinite box
-					if (ext > 0.0) { e = (int)std::ceil(std::log2(ext / 254.0)) + 127; if (e < 1) e = 1; if (e > 254) e = 254; }
-					for (;;) { // guard against log2 rounding: make sure the extent fits
-						uint32_t bits = (uint32_t)e << 23; float s; std::memcpy(&s, &bits, 4);
-						if ((double)s * 254.0 >= ext || e >= 254) { scale[a] = s; break; }
-						e++;
+				if (!quantise8(k.box, k.ref, k.n, node)) bad = true;
+				for (uint32_t i = 0; i < k.n && leaf_box; i++)
+					if (k.ref[i] >= kLeafBit) {
+						float *lb = leaf_box + (size_t)(k.ref[i] & 0x7FFFFFFFu) * 8u;
+						for (int a = 0; a < 3; a++) { lb[a] = k.box[i][a]; lb[4 + a] = k.box[i][3 + a]; }
 					}
-					node.exp[a] = (uint8_t)e;
-				}
-				for (uint32_t i = 0; i < 8; i++) {
-					if (i >= k.n) { node.ref[i] = kSentinel; continue; }
-					node.ref[i] = k.ch[i].ref;
-					if (k.ch[i].ref >= kLeafBit && leaf_box) {
-						float *lb = leaf_box + (size_t)(k.ch[i].ref & 0x7FFFFFFFu) * 8u;
-						for (int a = 0; a < 3; a++) { lb[a] = k.ch[i].mn[a]; lb[4 + a] = k.ch[i].mx[a]; }
-					}
-					for (int a = 0; a < 3 && !bad; a++) {
-						// outward rounding, verified on the value the kernel will decode: fmaf(q, scale, org)
-						int ql = (int)std::floor(((double)k.ch[i].mn[a] - (double)node.org[a]) / (double)scale[a]);
-						if (ql < 0) ql = 0; if (ql > 255) ql = 255;
-						while (ql > 0 && std::fmaf((float)ql, scale[a], node.org[a]) > k.ch[i].mn[a]) ql--;
-						int qh = (int)std::ceil(((double)k.ch[i].mx[a] - (double)node.org[a]) / (double)scale[a]);
-						if (qh < 0) qh = 0; if (qh > 255) qh = 255;
-						while (qh < 255 && std::fmaf((float)qh, scale[a], node.org[a]) < k.ch[i].mx[a]) qh++;
-						if (std::fmaf((float)ql, scale[a], node.org[a]) > k.ch[i].mn[a] || std::fmaf((float)qh, scale[a], node.org[a]) < k.ch[i].mx[a])
-							bad = true; // cannot happen for finite boxes (one step of headroom); never ship a box that does not contain its child
-						node.qlo[a][i] = (uint8_t)ql; node.qhi[a][i] = (uint8_t)qh;
-					}
-				}
 				dev8[w] = node;
 			}
 		};

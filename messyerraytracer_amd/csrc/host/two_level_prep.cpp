@@ -5,7 +5,7 @@
 // The flat ids follow RayTracerServer::_rebuild_scene (raytracer_server.cpp:700-711): an instance's
 // first triangle has the running triangle count of the instances registered before it (the reference's
 // own TLAS path reports mesh-local ids; the flat id is what its callers index by).
-#include "../mrt_internal.h"
+#include "../build_rules.h"
 #include "../instance_math.h"
 
 #include <cmath>
@@ -220,19 +220,17 @@ int prepare_two_level(const float *verts9, uint32_t n_mesh_tris, const mrt_insta
 	uint32_t node_base = tlas_cap, tri_base = 0, base8 = 0;
 	for (size_t k = 0; k < blas.size(); k++) { // concatenate, making node and leaf refs global
 		const DeviceSceneHost &s = built[k];
-		auto fix = [&](uint32_t ref) { return ref < kSentinel ? ref + node_base : (ref >= kLeafBit ? (kLeafBit | ((ref & 0x7FFFFFFFu) + tri_base)) : ref); };
 		for (uint32_t w = 0; w < s.n_nodes; w++) {
 			DevNode g = s.nodes[w];
-			g.left_ref = fix(g.left_ref); g.right_ref = fix(g.right_ref);
+			g.left_ref = rebase_ref(g.left_ref, node_base, tri_base); g.right_ref = rebase_ref(g.right_ref, node_base, tri_base);
 			h.nodes[node_base + w] = g;
 		}
 		std::memcpy(h.hot + tri_base, s.hot, (size_t)s.n_tris * sizeof(TriHot));
 		std::memcpy(h.cold + tri_base, s.cold, (size_t)s.n_tris * sizeof(TriCold));
 		if (h.wide8) {
-			auto fix8 = [&](uint32_t ref) { return ref < kSentinel ? ref + base8 : (ref >= kLeafBit ? (kLeafBit | ((ref & 0x7FFFFFFFu) + tri_base)) : ref); };
 			for (uint32_t w = 0; w < s.n_nodes8; w++) {
 				Dev8Node g = s.nodes8[w];
-				for (int c = 0; c < 8; c++) g.ref[c] = fix8(g.ref[c]);
+				for (int c = 0; c < 8; c++) g.ref[c] = rebase_ref(g.ref[c], base8, tri_base);
 				h.nodes8[base8 + w] = g;
 			}
 			std::memcpy(h.leaf_box + (size_t)tri_base * 8, s.leaf_box, (size_t)s.n_tris * 8 * sizeof(float));

@@ -21,6 +21,7 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
+#include "build_rules.h"
 
 namespace mrt {
 
@@ -28,22 +29,6 @@ namespace {
 
 #define REFIT_WG 256
 #define REFIT_BOXES_BLOCKS 1024u
-
-struct Box { float mn[3], mx[3]; };
-
-// The box rule of lbvh_bounds_kernel (device_build.hip): the vertices v0, v0 + e1, v0 + e2 as the intersection test
-// sees them, one ulp outwards (a rounded sum may lie half an ulp inside the true vertex).
-__device__ __forceinline__ float ulp_down(float f) { return f == 0.0f ? -FLT_MIN : __uint_as_float(__float_as_uint(f) + (f > 0.0f ? -1 : 1)); }
-__device__ __forceinline__ float ulp_up(float f) { return f == 0.0f ? FLT_MIN : __uint_as_float(__float_as_uint(f) + (f > 0.0f ? 1 : -1)); }
-__device__ __forceinline__ uint32_t f2ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-
-// left then right: every union of the refit is taken in this order, so the climb and the check agree bit for bit
-__device__ __forceinline__ Box unite(const Box &l, const Box &r)
-{
-	Box u;
-	for (int k = 0; k < 3; k++) { u.mn[k] = fminf(l.mn[k], r.mn[k]); u.mx[k] = fmaxf(l.mx[k], r.mx[k]); }
-	return u;
-}
 
 // the union of the slots [first, first + count) (a host SAH leaf holds several; the root leaf of a tiny scene is wrapped
 // as two children over the halves of one range)
@@ -71,13 +56,6 @@ __device__ __forceinline__ void put_side_sc1(DevNode *row, int side, const Box &
 	__hip_atomic_store((refit_gu64 *)mx, (unsigned long long)__float_as_uint(b.mx[0]) | ((unsigned long long)__float_as_uint(b.mx[1]) << 32), REFIT_RLX);
 	__hip_atomic_store((refit_gu32 *)(mx + 2), __float_as_uint(b.mx[2]), REFIT_RLX);
 }
-__device__ __forceinline__ Box get_side(const DevNode *row, int side)
-{
-	const float *mn = side ? row->rmin : row->lmin, *mx = side ? row->rmax : row->lmax;
-	Box b;
-	for (int k = 0; k < 3; k++) { b.mn[k] = mn[k]; b.mx[k] = mx[k]; }
-	return b;
-}
 
 // One row per BLAS, in blas[] order: its node rows [root, root + n_nodes), its slots [slot_base, slot_base + n_tris), its triangles
 // [first_tri, first_tri + n_tris) of the mesh array.  Roots and slot bases grow with the index.  A flat scene is the one row
@@ -99,37 +77,22 @@ __device__ __forceinline__ RefitBlas blas_of(const RefitBlas *blas, uint32_t n_b
 //    (ordered uint: min, max), scal[6] != 0 if any coordinate is not finite.  Grid-stride, one atomic per block and component.
 __global__ __launch_bounds__(REFIT_WG) void refit_boxes_kernel(const mrt_tri64 *tris, const uint32_t *slot_src, uint32_t n, Box *boxes, uint32_t *scal)
 {
-	__shared__ float part[REFIT_WG / 64][6];
 	float mn[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, mx[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
 	bool finite = true;
 	for (uint32_t k = blockIdx.x * REFIT_WG + threadIdx.x; k < n; k += gridDim.x * REFIT_WG) {
 		const float4 *t = reinterpret_cast<const float4 *>(tris + slot_src[k]);
 		const float4 a = t[0], b = t[1], c = t[2];
 		const float v0[3] = { a.x, a.y, a.z }, e1[3] = { b.x, b.y, b.z }, e2[3] = { c.x, c.y, c.z };
-		Box bx;
+		const Box bx = tri_box(v0, e1, e2);
 		for (int i = 0; i < 3; i++) {
-			const float p1 = v0[i] + e1[i], p2 = v0[i] + e2[i];
 			finite = finite && __builtin_isfinite(v0[i]) && __builtin_isfinite(e1[i]) && __builtin_isfinite(e2[i]) &&
-					__builtin_isfinite(p1) && __builtin_isfinite(p2);
-			bx.mn[i] = ulp_down(fminf(v0[i], fminf(p1, p2)));
-			bx.mx[i] = ulp_up(fmaxf(v0[i], fmaxf(p1, p2)));
+					__builtin_isfinite(v0[i] + e1[i]) && __builtin_isfinite(v0[i] + e2[i]);
 			mn[i] = fminf(mn[i], bx.mn[i]); mx[i] = fmaxf(mx[i], bx.mx[i]);
 		}
 		boxes[k] = bx;
 	}
 	if (!finite) atomicOr(&scal[6], 1u);
-	for (int i = 0; i < 3; i++) {
-		float lo = mn[i], hi = mx[i];
-		for (int off = 32; off > 0; off >>= 1) { lo = fminf(lo, __shfl_xor(lo, off)); hi = fmaxf(hi, __shfl_xor(hi, off)); }
-		if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][i] = lo; part[threadIdx.x >> 6][3 + i] = hi; }
-	}
-	__syncthreads();
-	if (threadIdx.x < 6u) {
-		const bool is_min = threadIdx.x < 3u;
-		float v = part[0][threadIdx.x];
-		for (uint32_t w = 1; w < REFIT_WG / 64; w++) v = is_min ? fminf(v, part[w][threadIdx.x]) : fmaxf(v, part[w][threadIdx.x]);
-		if (is_min) atomicMin(&scal[threadIdx.x], f2ord(v)); else atomicMax(&scal[threadIdx.x], f2ord(v));
-	}
+	block_bounds<REFIT_WG>(mn, mx, scal);
 }
 
 // 2. slot k <- input triangle slot_src[k]: the whole row (v0, edges, id, layers, normal) but the leaf-end flag, which is the tree's
@@ -248,29 +211,16 @@ __global__ __launch_bounds__(REFIT_WG) void refit_verify_kernel(const DevNode *n
 // over the BLAS rows [lo, hi) = [tlas_cap, n_nodes) only (TLAS leaves hold instance slots, not triangles); the TLAS is rebuilt on
 // the host from the new mesh boxes, as mrt_update_instances rebuilds it.
 
-// 0. the triangles of every BLAS as mrt_make_triangles (scene_prep.cpp) makes them for an upload -- v0, edges, cross product,
-//    normalised; mesh-local id, all layers -- BLAS after BLAS: row slot_base + j is triangle first_tri + j of the mesh array.
-//    The same fp32 operations in the same order (nothing is contracted: -ffp-contract=off), so the rows are the upload's bit for bit.
+// 0. the triangles of every BLAS by make_tri64 (build_rules.h), as an upload makes them: mesh-local id, all layers -- BLAS after
+//    BLAS: row slot_base + j is triangle first_tri + j of the mesh array.
 __global__ __launch_bounds__(REFIT_WG) void refit2_tris_kernel(const float *verts9, const RefitBlas *blas, uint32_t n_blas, uint32_t n, mrt_tri64 *out)
 {
 	const uint32_t s = blockIdx.x * REFIT_WG + threadIdx.x;
 	if (s >= n) return;
 	const RefitBlas bl = blas_of(blas, n_blas, s, false);
 	const uint32_t j = s - bl.slot_base;
-	const float *a = verts9 + 9u * (size_t)(bl.first_tri + j), *b = a + 3, *c = a + 6;
-	float e1[3], e2[3], nn[3];
-	for (int k = 0; k < 3; k++) { e1[k] = b[k] - a[k]; e2[k] = c[k] - a[k]; }
-	nn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-	nn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-	nn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-	const float l2 = nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2];
-	if (l2 == 0.0f) { nn[0] = nn[1] = nn[2] = 0.0f; }
-	else { const float l = __builtin_sqrtf(l2); nn[0] /= l; nn[1] /= l; nn[2] /= l; }
-	float4 *dst = reinterpret_cast<float4 *>(out + s);
-	dst[0] = make_float4(a[0], a[1], a[2], __uint_as_float(j));
-	dst[1] = make_float4(e1[0], e1[1], e1[2], __uint_as_float(0xFFFFFFFFu));
-	dst[2] = make_float4(e2[0], e2[1], e2[2], 0.0f);
-	dst[3] = make_float4(nn[0], nn[1], nn[2], 0.0f);
+	const float *a = verts9 + 9u * (size_t)(bl.first_tri + j);
+	out[s] = make_tri64(a, a + 3, a + 6, j, 0xFFFFFFFFu);
 }
 
 // the slot map, once per scene: slot k holds triangle hot[k].id of its BLAS, staged at slot_base + id.  (An id beyond its mesh
@@ -293,14 +243,6 @@ __global__ __launch_bounds__(REFIT_WG) void refit2_roots_kernel(const DevNode *n
 	out[k] = unite(get_side(g, 0), get_side(g, 1));
 }
 
-inline float ord2f(uint32_t o)
-{
-	const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-	float f; std::memcpy(&f, &u, 4); return f;
-}
-
-inline size_t align256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
-
 // One refit, flat or two-level: the node rows [lo, hi) of the n_blas BLASes of a table, over n slots, on the context's stream.
 // What a scene's first refit allocates -- the slot map (two-level scenes), the parents, and a host-uploaded scene's wide layouts at
 // binary-node indices (its compact host collapse has no map from binary nodes to wide nodes) -- starts as the scene's own array;
@@ -322,13 +264,9 @@ struct Refit {
 	{
 		const size_t box_bytes = align256((size_t)n * sizeof(Box)), arr_bytes = align256((size_t)(hi - lo) * 4u),
 				tab_bytes = align256((size_t)n_blas * sizeof(RefitBlas)), need = box_bytes + arr_bytes + 256u + tab_bytes + extra_bytes;
-		if (ctx->build_arena.cap < need) {
-			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-			if (ctx->build_arena.ptr) (void)hipFree(ctx->build_arena.ptr);
-			ctx->build_arena.ptr = nullptr; ctx->build_arena.cap = 0;
-			if (hipMalloc(&ctx->build_arena.ptr, need) != hipSuccess) { ctx->build_arena.ptr = nullptr; return fail(ctx, MRT_ERR_OOM, "refit: out of device memory"); }
-			ctx->build_arena.cap = need;
-		}
+		const hipError_t arena_sync = grow_arena(&ctx->build_arena, need, ctx->stream);
+		if (arena_sync == hipErrorOutOfMemory) return fail(ctx, MRT_ERR_OOM, "refit: out of device memory");
+		HIP_TRY(ctx, arena_sync);
 		boxes = (Box *)ctx->build_arena.ptr;
 		arrivals = (uint32_t *)((char *)boxes + box_bytes);
 		scal = (uint32_t *)((char *)arrivals + arr_bytes);

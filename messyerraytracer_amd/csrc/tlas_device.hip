@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
 #include "instance_math.h"
+#include "build_rules.h"
 
 namespace mrt {
 
@@ -26,7 +27,6 @@ namespace {
 
 #define TLAS_WG 256
 
-struct Box { float mn[3], mx[3]; };                                   // the device builder's box input layout
 struct TlasInst { uint32_t blas, id_base; };                          // per registered instance: its mesh, the flat id of its first triangle
 struct TlasBlas { uint32_t first_tri, n_tris, root, root8; float lo[3], hi[3]; }; // per mesh: range, BLAS roots, mesh-space box
 
@@ -83,8 +83,6 @@ __global__ __launch_bounds__(TLAS_WG) void tlas_commit_kernel(const DevNode *bui
 		instances[k] = d;
 	}
 }
-
-inline size_t align256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
 
 // the scene's tables, from the host copy (two_level); the instance table once per scene, the mesh table after every refit
 int upload_tables(mrt_ctx *ctx)

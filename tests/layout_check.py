@@ -79,7 +79,7 @@ def _differ(a, b, zeros_equal=True):
 
 
 def ulp_down(f):
-    """device_build.hip / refit.hip ulp_down: one float32 step towards -inf (0 -> -FLT_MIN)"""
+    """csrc/build_rules.h ulp_down: one float32 step towards -inf (0 -> -FLT_MIN)"""
     f = np.ascontiguousarray(f, dtype=np.float32)
     u = f.view(np.uint32)
     step = np.where(f > 0, np.uint32(0xFFFFFFFF), np.uint32(1)).astype(np.uint32)  # + (-1) or + 1, modulo 2^32
@@ -94,7 +94,7 @@ def ulp_up(f):
 
 
 def slot_boxes_device(hot):
-    """The box rule of lbvh_bounds_kernel / refit_boxes_kernel: bounds of v0, v0 + e1, v0 + e2 in float32, one ulp outwards."""
+    """csrc/build_rules.h tri_box (device builds and refits): bounds of v0, v0 + e1, v0 + e2 in float32, one ulp outwards."""
     v0, e1, e2 = hot["v0"], hot["e1"], hot["e2"]
     p1, p2 = v0 + e1, v0 + e2  # float32 sums
     mn = ulp_down(np.minimum(v0, np.minimum(p1, p2)))
@@ -355,7 +355,7 @@ def check_wide(width, wnodes, wroots, t, t_roots, node_base, n_slots, stack_have
     """rules 7 (width 4) and 8 (width 8) against the walked 2-wide tree t (with signatures).  wroots[k] is the wide root that goes with
     the 2-wide root t_roots[k]; node_base: a layout at binary-node indices holds binary node b at wide index b - node_base.
 
-    The 8-wide looseness bound, from lbvh_collapse8_kernel (the host quantiser in scene_prep.cpp is the same text): the grid step s is
+    The 8-wide looseness bound, from quantise8 (csrc/build_rules.h, the one text of the host and the device collapse): the grid step s is
     the smallest power of two with 254 s >= the node's extent.  qlo starts as floor((lo - org) / s) computed in double (a start
     value only: the difference of two floats is exact in double while their exponents are within 29 bits of each other, and nothing
     below relies on it), and the loop lowers qlo while the DECODED value fma(qlo, s, org) is still above lo; the kernel then
@@ -630,7 +630,7 @@ def world_box(lo, hi, basis, origin):
 
 
 def mesh_triangles(verts9, first_tri, n_tris):
-    """mrt_make_triangles restated for one mesh of a two-level scene: mesh-local ids, all layers (float32, nothing contracted)"""
+    """make_tri64 (csrc/build_rules.h) restated for one mesh of a two-level scene: mesh-local ids, all layers (float32, nothing contracted)"""
     from messyerraytracer_amd import types as T
     v = np.ascontiguousarray(verts9, dtype=np.float32).reshape(-1, 3, 3)[first_tri:first_tri + n_tris]
     out = np.zeros(n_tris, dtype=T.TRI64)

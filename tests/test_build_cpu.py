@@ -58,12 +58,13 @@ def test_compile_pool_is_not_sized_by_the_cpu_count(monkeypatch):
 def test_public_build_names():
     for name in ("build_lib", "build_host_test", "build_host_cpu_test", "build_host_tlas_test", "build_policy_test",
                  "build_shadow_policy_test", "build_reflection_policy_test", "build_hemisphere_policy_test", "build_bounce_policy_test",
-                 "build_instance_math_test", "build_shade_data_test", "build_light_data_test", "build_path_data_test",
+                 "build_instance_math_test", "build_build_rules_test", "build_shade_data_test", "build_light_data_test", "build_path_data_test",
                  "build_texture_data_test", "build_lane_map_test"):
         f = getattr(build, name)
         params = inspect.signature(f).parameters
         assert "force" in params and params["force"].default is False, name
     assert inspect.signature(build.build_lane_map_test).parameters["sanitize"].default is False
+    assert inspect.signature(build.build_build_rules_test).parameters["sanitize"].default is False
     lib = inspect.signature(build.build_lib).parameters
     assert [lib[k].default for k in ("verbose", "lib", "obj_dir", "defines")] == [False, None, None, None]
     assert build.LIB == os.path.join(build.HERE, "libmrt_hip.so")
