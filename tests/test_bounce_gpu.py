@@ -120,7 +120,8 @@ def check_all_entry_points(kind, w, h, y0=0, y1=None, kernel=capi.KERNEL_AUTO, v
 
 
 GRIDS = [(128, 96, 0, 96), (100, 77, 0, 77), (128, 96, 20, 70)]   # below 2^16 records
-PLAIN = {"room": "trace_bounce_lane_kernel<%d>", "room_tl": "trace_bounce_two_level_kernel<%d>", "soup": "trace_bounce_lane_kernel<%d>"}
+PLAIN = {"room": "trace_bounce_lane_kernel<%d>", "room_tl": "trace_bounce_two_level_kernel<%d>", "soup": "trace_bounce_lane_kernel<%d>",
+         "affine_tl": "trace_bounce_two_level_kernel<%d>"}
 
 
 @pytest.mark.parametrize("kind", ["soup", "room", "room_tl"])

@@ -10,6 +10,7 @@ import pytest
 
 from messyerraytracer_amd import capi, synth, types as T
 from oracle import pyoracle as po
+import affine_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -30,15 +31,19 @@ class Scene:
         if kind == "soup":
             self.local, self.inst = synth.soup(2000, 0.4, 3), None
             self.verts, self.layers, self.cam = self.local, np.full(2000, 0xFFFFFFFF, np.uint32), SOUP_CAM
+        elif kind == "affine_tl":   # mirrored, scaled and sheared instances, seen by their own camera (tests/affine_scene.py)
+            a = affine_scene.scene()
+            self.local, self.inst, self.verts, self.layers, self.cam = a.local, a.inst, a.world, a.layers, affine_scene.CAM
         else:
             self.local, self.inst = synth.room()
             self.verts = synth.flatten_instances(self.local, self.inst)
             self.layers = np.repeat(self.inst["layers"], self.inst["n_tris"]).astype(np.uint32)
             self.cam = ROOM_CAM
+        self.two_level = kind.endswith("_tl")
         self._oracle = None
 
     def upload(self, ctx):
-        if self.kind == "room_tl":
+        if self.two_level:
             ctx.upload_two_level_scene(self.local, self.inst)
         else:
             tris = capi.make_triangles(self.verts, layers=self.layers)
@@ -47,7 +52,7 @@ class Scene:
 
     def oracle(self, rays, query_mask=0xFFFFFFFF, any_hit=False):
         if self._oracle is None:
-            self._oracle = (po.OracleTwoLevelScene(self.local, self.inst) if self.kind == "room_tl"
+            self._oracle = (po.OracleTwoLevelScene(self.local, self.inst) if self.two_level
                             else po.OracleScene(self.verts, layers=self.layers))
         return self._oracle.trace(rays, query_mask=query_mask, any_hit=any_hit)
 
@@ -206,7 +211,7 @@ def check_all_entry_points(kind, w, h, y0=0, y1=None, kernel=capi.KERNEL_AUTO, v
 
 GRIDS = [(128, 96, 0, 96), (100, 77, 0, 77), (128, 96, 20, 70)]
 PLAIN = {"room": "trace_reflection_lane_kernel<6>", "room_tl": "trace_reflection_two_level_kernel<6>",
-         "soup": "trace_reflection_lane_kernel<6>"}
+         "soup": "trace_reflection_lane_kernel<6>", "affine_tl": "trace_reflection_two_level_kernel<6>"}
 
 
 @pytest.mark.parametrize("kind", ["soup", "room", "room_tl"])

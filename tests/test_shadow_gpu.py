@@ -9,6 +9,7 @@ import pytest
 
 from messyerraytracer_amd import capi, synth, types as T
 from oracle import pyoracle as po
+import affine_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -26,15 +27,19 @@ class Scene:
         if kind == "soup":
             self.local, self.inst = synth.soup(2000, 0.4, 3), None
             self.verts, self.layers, self.cam = self.local, np.full(2000, 0xFFFFFFFF, np.uint32), SOUP_CAM
+        elif kind == "affine_tl":   # mirrored, scaled and sheared instances, seen by their own camera (tests/affine_scene.py)
+            a = affine_scene.scene()
+            self.local, self.inst, self.verts, self.layers, self.cam = a.local, a.inst, a.world, a.layers, affine_scene.CAM
         else:
             self.local, self.inst = synth.room()
             self.verts = synth.flatten_instances(self.local, self.inst)
             self.layers = np.repeat(self.inst["layers"], self.inst["n_tris"]).astype(np.uint32)
             self.cam = ROOM_CAM
+        self.two_level = kind.endswith("_tl")
         self._oracle = None
 
     def upload(self, ctx):
-        if self.kind == "room_tl":
+        if self.two_level:
             ctx.upload_two_level_scene(self.local, self.inst)
         else:
             tris = capi.make_triangles(self.verts, layers=self.layers)
@@ -43,7 +48,7 @@ class Scene:
 
     def oracle_any(self, rays, query_mask=0xFFFFFFFF):
         if self._oracle is None:
-            self._oracle = (po.OracleTwoLevelScene(self.local, self.inst) if self.kind == "room_tl"
+            self._oracle = (po.OracleTwoLevelScene(self.local, self.inst) if self.two_level
                             else po.OracleScene(self.verts, layers=self.layers))
         return self._oracle.trace(rays, query_mask=query_mask, any_hit=True)["prim_id"] >= 0
 
@@ -215,7 +220,7 @@ def test_shadow_masks_match_the_oracle(built, kind, grid):
     check_entry_points(kind, *grid)   # (5 lights: 77 000 - 245 760 pairs, the persistent kernels)
 
 
-PLAIN = {"room": "trace_shadow_lane_kernel<", "room_tl": "trace_shadow_two_level_kernel<"}
+PLAIN = {"room": "trace_shadow_lane_kernel<", "room_tl": "trace_shadow_two_level_kernel<", "affine_tl": "trace_shadow_two_level_kernel<"}
 
 
 # Below 2^16 pairs the plain kernels: 64x48 with one light is 3 072 pairs (one ray per wave), with five 15 360 (two per wave), 256x192
