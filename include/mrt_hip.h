@@ -273,8 +273,8 @@ uint32_t mrt_version(void);
 /* sizeof() of the boundary's structs as this library was compiled, for bindings in other languages to check
  * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light, 6 mrt_material,
  * 7 mrt_shade_data, 8 mrt_surface64, 9 mrt_surface_out, 11 mrt_shade_light, 12 mrt_environment, 13 mrt_light_out,
- * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set (0 for anything
- * else). */
+ * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set, 22 mrt_panorama
+ * (0 for anything else). */
 uint32_t mrt_struct_size(uint32_t which);
 /* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream). */
 int mrt_set_stream(mrt_ctx *ctx, void *hip_stream);
@@ -883,8 +883,9 @@ int mrt_clear_textures(mrt_ctx *ctx);
 /* ---- direct light on resolved surfaces: ShadePass::cook_torrance_multi_light (src/modules/graphics/shade_pass.h:597-657),
  * the loop shade_material runs for RayRenderer's frame and PathTrace::compute_direct_light for next-event estimation, and the
  * three plain terms shade_material adds around it (the analytic sky for a miss, the hemisphere ambient, the emission), run
- * per record as one kernel on the rows mrt_resolve_surfaces wrote and the mask mrt_cast_shadows wrote.  Tone mapping, gamma,
- * the panorama sky, throughput and path state stay with the renderer. */
+ * per record as one kernel on the rows mrt_resolve_surfaces wrote and the mask mrt_cast_shadows wrote.  With a panorama resident
+ * (mrt_upload_panorama, below) the sky of a miss and the ambient factor of a hit are samples of it.  Tone mapping, gamma,
+ * throughput and path state stay with the renderer. */
 
 /* LightData (src/api/light_data.h); 64 bytes.  The first 32 bytes are mrt_light field for field. */
 typedef struct mrt_shade_light {
@@ -980,8 +981,8 @@ int mrt_light_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w
  * (path_trace.h:213-246), Russian roulette, the `active` flag, tone mapping and gamma -- on the rows mrt_resolve_surfaces wrote
  * and the direct light mrt_light_surfaces wrote with env == NULL.  Per bounce a renderer queues
  *   cast -> resolve (d_rows, d_bounce_surface, d_out_hits) -> shadows -> light with env = NULL -> step -> bounce cast with d_select
- * and reads back four bytes (d_active_count); after the last bounce, mrt_path_finish.  The panorama sky, textures, normal maps and
- * the average over sample_index frames stay with the renderer. */
+ * and reads back four bytes (d_active_count); after the last bounce, mrt_path_finish.  With a panorama resident
+ * (mrt_upload_panorama, below) the sky of a miss is a sample of it.  The average over sample_index frames stays with the renderer. */
 
 /* PathState without its generator (the stream is a function of pixel, frame and bounce: mrt_cast_bounce); 32 bytes */
 typedef struct mrt_path_state {
@@ -1057,6 +1058,62 @@ int mrt_path_grid_step(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uin
 int mrt_path_finish(mrt_ctx *ctx, const mrt_path_state *d_state, uint64_t count, uint32_t tonemap_mode, float *d_rgba,
 		uint32_t flags);
 
+/* ---- resident panorama: the panorama half of ShadePass::EnvironmentData (panorama_data, _width, _height, _energy), the
+ * equirectangular RGBAF32 image of a PanoramaSkyMaterial that ray_renderer.cpp:676-703 binds, held on the device, so that the
+ * lighting calls and the path steps run sky_color's and shade_material's panorama branches (shade_pass.h:164-257, :684-711)
+ * themselves. */
+#define MRT_PANORAMA_MAX_DIM 16384u        /* (float)width is exact and every texel index below 2^28 */
+#define MRT_PANORAMA_ON_DEVICE 1u          /* pixels is a device pointer */
+typedef struct mrt_panorama {              /* 24 bytes */
+	const float *pixels;                   /* RGBAF32, 4 floats per texel, row-major, top row first; alpha is not read */
+	uint32_t width, height;                /* 1 .. MRT_PANORAMA_MAX_DIM each */
+	float energy;                          /* PanoramaSkyMaterial.energy_multiplier; finite */
+	uint32_t flags;                        /* MRT_PANORAMA_ON_DEVICE or 0 */
+} mrt_panorama;
+/* Makes a panorama resident: a copy of the image in a buffer the context owns.  Like the texture set it belongs to the context: it
+ * survives scene uploads, refits and instance updates, is replaced by the next upload and released by mrt_clear_panorama or
+ * mrt_destroy; neither call touches the scene, the tuner, the tile schedule or mrt_stats.  Waits for the context's stream, copies
+ * on it and waits again; nothing is resident until the copy is.  MRT_ERR_INVALID, checked in this order before any device work and
+ * with the resident panorama unchanged: a null context or descriptor; null pixels; a width or height of 0 or above
+ * MRT_PANORAMA_MAX_DIM; an energy that is not finite; an unknown flag; then, for a host-resident image, a texel whose r, g or b is
+ * not finite (a device-resident image is taken as given).  MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_upload_panorama(mrt_ctx *ctx, const mrt_panorama *pano);
+/* Releases the resident panorama (none resident: MRT_OK).  Waits for the context's stream.  MRT_ERR_PENDING as above. */
+int mrt_clear_panorama(mrt_ctx *ctx);
+/* While a panorama is resident (other kernels; with none resident exactly the kernels and the results stated above):
+ *   mrt_light_surfaces / mrt_light_grid_surfaces with env given: a miss writes {sample(d).c * energy, a = 0}, d as given; a hit's
+ *     ambient factor ground.c + (zenith.c - ground.c) * (n.y * 0.5f + 0.5f) is replaced by amb.c = sample(n).c * energy, n the
+ *     row's normal: rgb.c = rgb.c + ((diff.c * amb.c) * ambient.c) * ambient_energy, then emission.c.  With env == NULL the
+ *     panorama is not read and nothing changes.
+ *   mrt_path_step / mrt_path_grid_step: the sky of a miss is sample(d).c * energy; the ambient line of bounce 0 is unchanged
+ *     (cpu_path_tracer.h:148-153 does not sample there).
+ * mrt_environment is as above; its reserved words stay unread.
+ * sample(dir), plain fp32, one operation at a time, nothing contracted, PI = 3.14159265358979323846f, (0.5f / PI) and (1.0f / PI)
+ * one float constant each:
+ *   a component of dir that is an infinity or a NaN: {0, 0, 0}, no texel read (the reference only asserts there).
+ *   u = atan2_def(dir.x, dir.z) * (0.5f / PI) + 0.5f;  c = dir.y < -1 ? -1 : (dir.y > 1 ? 1 : dir.y);  v = acos_def(c) * (1.0f / PI)
+ *   (direction_to_equirect_uv), then sample_panorama: u = u - floorf(u); v = v < 1 ? v : 1; v = v > 0 ? v : 0;
+ *   fx = u * (float)width - 0.5f; fy = v * (float)height - 0.5f; x0 = (int)floorf(fx); y0 = (int)floorf(fy);
+ *   sx = fx - (float)x0; sy = fy - (float)y0; x1 = x0 + 1, then x1 = x1 >= width ? x1 - width : x1 and x0 = x0 < 0 ? x0 + width : x0
+ *   (the reference's cyclic wrap on the only values that occur: x0 in -1 .. width - 1); y1 = min(y0 + 1, height - 1),
+ *   y0 = max(y0, 0) (its clamp: y0 in -1 .. height - 1); the texels p00 = (x0, y0), p10 = (x1, y0), p01 = (x0, y1), p11 = (x1, y1);
+ *   w00 = (1 - sx) * (1 - sy); w10 = sx * (1 - sy); w01 = (1 - sx) * sy; w11 = sx * sy;
+ *   sample.c = ((p00.c * w00 + p10.c * w10) + p01.c * w01) + p11.c * w11.
+ * atan2_def(y, x) and acos_def(c) return a float and are defined by arithmetic alone, like pow01, so that the device, the host and
+ * numpy float64 hold the same bits -- in fp64, one operation at a time, + - * / and the IEEE square root only, the two signs read
+ * as integer bits (so -0 counts as negative):
+ *   core(y, x), doubles: ay = |y|, ax = |x|; steep = ay > ax; mx = steep ? ay : ax; mn = steep ? ax : ay.
+ *     mx == 0: r = 0.  Otherwise (num, den, base) = (mn, mx, 0), or, if mn > 0.41421356237309503 * mx,
+ *     (mn - mx, mn + mx, 0.7853981633974483); t = num / den; t2 = t * t; q = Horner in t2 of A[k] = (-1)^k / (2k + 1), k = 15 .. 0,
+ *     each coefficient the correctly rounded quotient (q = -1.0 / 31.0; q = q * t2 + A[k]); r = base + t * q.
+ *     steep: r = 1.5707963267948966 - r.  x negative: r = 3.141592653589793 - r.  y negative: -r.
+ *   atan2_def(y, x) = (float)core((double)y, (double)x), rounded once: C99's atan2 for finite arguments, signed zeros and the
+ *     four axis cases included ((+0, -1) -> pi, (-0, -1) -> -pi, (+-0, +0) -> +-0, (+-0, -0) -> +-pi, (y > 0, +-0) -> pi / 2).
+ *   acos_def(c), c in [-1, 1] = (float)core(sqrt((1.0 - c) * (1.0 + c)), c) with c as a double: acos_def(1) = +0,
+ *     acos_def(-1) = (float)pi.
+ *   Both are within 1 fp32 ulp of the correctly rounded function.
+ * Not taken: prefiltered or importance-sampled IBL, mipmaps, RGBE or half-float images, the running average over sample_index,
+ * and a panorama per member of an mrt_group (a group's contexts take uploads one by one, mrt_group_context). */
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to
  * tokens written by a cast with MRT_FLAG_TOKEN_OUT: mrt_hit32 records (mrt_host_hit44 with

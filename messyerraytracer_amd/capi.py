@@ -34,6 +34,7 @@ SYMBOLS = [
     "mrt_cast_shadows", "mrt_cast_grid_shadows", "mrt_cast_reflections", "mrt_cast_grid_reflections", "mrt_cast_hemisphere", "mrt_cast_grid_hemisphere", "mrt_cast_bounce", "mrt_cast_grid_bounce",
     "mrt_upload_shade_data", "mrt_clear_shade_data", "mrt_resolve_surfaces", "mrt_resolve_grid_surfaces",
     "mrt_upload_textures", "mrt_clear_textures",
+    "mrt_upload_panorama", "mrt_clear_panorama",
     "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
     "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
@@ -102,6 +103,11 @@ class TextureSet(C.Structure):
                 ("tangents12", C.c_void_p)]
 
 
+class Panorama(C.Structure):
+    """mrt_panorama"""
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("energy", C.c_float), ("flags", C.c_uint32)]
+
+
 class LightOut(C.Structure):
     """mrt_light_out"""
     _fields_ = [("d_rgba", C.c_void_p)]
@@ -117,6 +123,9 @@ class PathStepDesc(C.Structure):
 SHADE_ARRAYS_ON_DEVICE = 1
 TEXTURES_ON_DEVICE = 1
 TEXEL_RGBA8, TEXEL_RGBA32F = 0, 1
+PANORAMA_ON_DEVICE = 1
+PANORAMA_MAX_DIM = 16384
+STRUCT_PANORAMA = 22   # mrt_struct_size index (21: not a struct)
 STRUCT_TEXTURE, STRUCT_MATERIAL_TEXTURES, STRUCT_TEXTURE_SET = 18, 19, 20   # mrt_struct_size indices (17: not a struct)
 STRUCT_PATH_STATE, STRUCT_PATH_STEP_DESC = 15, 16   # mrt_struct_size indices (14: not a struct)
 STRUCT_SHADE_LIGHT, STRUCT_ENVIRONMENT, STRUCT_LIGHT_OUT = 11, 12, 13   # mrt_struct_size indices
@@ -245,6 +254,8 @@ def load():
     L.mrt_clear_shade_data.argtypes = [C.c_void_p]
     L.mrt_upload_textures.argtypes = [C.c_void_p, C.POINTER(TextureSet)]
     L.mrt_clear_textures.argtypes = [C.c_void_p]
+    L.mrt_upload_panorama.argtypes = [C.c_void_p, C.POINTER(Panorama)]
+    L.mrt_clear_panorama.argtypes = [C.c_void_p]
     L.mrt_resolve_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SurfaceOut), C.c_uint32]
     L.mrt_resolve_grid_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                             C.POINTER(SurfaceOut), C.c_uint32]
@@ -829,6 +840,23 @@ class Context:
 
     def clear_textures(self):
         self._chk(self.L.mrt_clear_textures(self.h))
+
+    def upload_panorama(self, pixels, energy=1.0, on_device=False, size=None):
+        """Makes an equirectangular panorama resident (mrt_upload_panorama).  pixels: a [height, width, 4] float32 numpy array, top row
+        first, or with on_device a device pointer / tensor and size = (width, height).  While one is resident the lighting calls
+        with an environment and the path steps sample it for the sky of a miss (and the lighting calls for a hit's ambient factor)."""
+        if on_device:
+            (w, h), ptr, keep = size, _ptr(pixels).value, None
+        else:
+            keep = np.ascontiguousarray(pixels, dtype=np.float32)
+            if keep.ndim != 3 or keep.shape[2] != 4:
+                raise ValueError("a panorama is a [height, width, 4] array of float32")
+            (h, w), ptr = keep.shape[:2], _np(keep).value
+        d = Panorama(ptr, w, h, energy, PANORAMA_ON_DEVICE if on_device else 0)
+        self._chk(self.L.mrt_upload_panorama(self.h, C.byref(d)))
+
+    def clear_panorama(self):
+        self._chk(self.L.mrt_clear_panorama(self.h))
 
     def resolve_surfaces(self, d_rays, d_hits, count, d_rows=None, d_bounce_surface=None, d_out_hits=None, flags=0):
         """The shading surface of every hit record of a cast (device pointers / tensors: mrt_ray32 + mrt_hit32, or mrt_host_ray60 +

@@ -165,6 +165,7 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 18: return (uint32_t)sizeof(mrt_texture); // (17: not a struct)
 		case 19: return (uint32_t)sizeof(mrt_material_textures);
 		case 20: return (uint32_t)sizeof(mrt_texture_set);
+		case 22: return (uint32_t)sizeof(mrt_panorama); // (21: not a struct)
 		default: return 0u;
 	}
 }
@@ -268,6 +269,7 @@ void mrt_destroy(mrt_ctx *ctx)
 	release(ctx->tlas_work);
 	release(ctx->shade_rows); release(ctx->shade_materials);
 	release(ctx->tex_texels); release(ctx->tex_table); release(ctx->tex_bindings); release(ctx->tex_tangents);
+	release(ctx->pano_texels);
 	for (auto &sc : ctx->sched) {
 		if (sc.side) { (void)hipStreamSynchronize(sc.side); (void)hipStreamDestroy(sc.side); }
 		if (sc.traced) (void)hipEventDestroy(sc.traced);

@@ -1,10 +1,11 @@
 // lighting.hip — direct light on resolved surfaces (include/mrt_hip.h: mrt_shadow_lights, mrt_light_surfaces,
 // mrt_light_grid_surfaces).  The checks of the light list and the environment and the kernel's copy of both are host/light_data.cpp;
-// the kernel is light_kernel.h (shade_kernels.hip).
+// the kernel is light_kernel.h, with a panorama resident light_panorama_kernel.h (shade_kernels.hip).
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
 #include "lighting.h"
+#include "panorama.h"
 
 namespace {
 
@@ -23,7 +24,10 @@ int light(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, const 
 	std::memset(&s, 0, sizeof(s));
 	s.records = d_hits; s.rows = d_rows; s.mask = d_mask; s.out = out->d_rgba;
 	mrt::fill_light_params(lights, n_lights, env, s);
-	HIP_TRY(ctx, mrt::launch_light_surfaces(p, s, src, ctx->stream));
+	if (ctx->pano_resident && env) { // (without an environment no kernel reads the panorama)
+		const mrt::PanoramaParams pano = {ctx->pano_texels.ptr, ctx->pano_width, ctx->pano_height, ctx->pano_energy, 0u};
+		HIP_TRY(ctx, mrt::launch_light_panorama_surfaces(p, s, pano, src, ctx->stream));
+	} else HIP_TRY(ctx, mrt::launch_light_surfaces(p, s, src, ctx->stream));
 	return finish_call(ctx, flags);
 }
 

@@ -47,6 +47,10 @@ struct PathParams;
 hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream);
 hipError_t launch_path_step(const TraceParams &p, const PathParams &s, int src, hipStream_t stream);
 hipError_t launch_path_finish(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba, hipStream_t stream);
+// the lighting and the path step with a panorama resident (light_panorama_kernel.h, path_kernel.h; panorama.h)
+struct PanoramaParams;
+hipError_t launch_light_panorama_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams &pano, int src, hipStream_t stream);
+hipError_t launch_path_panorama_step(const TraceParams &p, const PathParams &s, const PanoramaParams &pano, int src, hipStream_t stream);
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream);
 // ---- device_build.hip
 hipError_t grow_arena(BuildArena *arena, size_t need, hipStream_t stream); // hipErrorOutOfMemory: no allocation, the arena is empty
@@ -141,6 +145,12 @@ struct mrt_ctx {
 	DevBuf tex_texels, tex_table, tex_bindings, tex_tangents;
 	uint32_t tex_n_bindings = 0, tex_n_tangent_tris = 0; // (no tangents resident: 0)
 	bool tex_resident = false;
+	// panorama (panorama.hip): the context's, like the texture set; pano_resident: the lighting calls with an environment and the path
+	// steps launch the panorama kernels
+	DevBuf pano_texels;
+	uint32_t pano_width = 0, pano_height = 0;
+	float pano_energy = 0.0f;
+	bool pano_resident = false;
 };
 
 #define HIP_TRY(ctx, call)                                                                          \

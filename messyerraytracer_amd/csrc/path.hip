@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
 #include "path.h"
+#include "panorama.h"
 
 namespace {
 
@@ -19,7 +20,10 @@ int step(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, const m
 	std::memset(&s, 0, sizeof(s));
 	s.records = d_hits; s.rows = d_rows;
 	mrt::fill_path_params(desc, pixel0, s);
-	HIP_TRY(ctx, mrt::launch_path_step(p, s, src, ctx->stream));
+	if (ctx->pano_resident) {
+		const mrt::PanoramaParams pano = {ctx->pano_texels.ptr, ctx->pano_width, ctx->pano_height, ctx->pano_energy, 0u};
+		HIP_TRY(ctx, mrt::launch_path_panorama_step(p, s, pano, src, ctx->stream));
+	} else HIP_TRY(ctx, mrt::launch_path_step(p, s, src, ctx->stream));
 	return finish_call(ctx, flags);
 }
 

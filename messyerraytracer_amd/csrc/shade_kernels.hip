@@ -1,7 +1,8 @@
 // shade_kernels.hip — gfx950 kernels of the shading passes over hit records: the resolve to shading surfaces (plain and textured), the
-// direct light, the path tracer's per-pixel state and the packing of shade rows.  None of them walks a scene; they share the ray and
-// record helpers of device_common.h and record_surface of source_common.h with the walks of kernels.hip, and are compiled apart from
-// them.  The arithmetic is the canonical form of DESIGN.md ("Arithmetic"), as in kernels.hip.
+// direct light and the path tracer's per-pixel state (the lighting and the step also with a resident panorama) and the packing of
+// shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
+// source_common.h with the walks of kernels.hip, and are compiled apart from them.  The arithmetic is the canonical form of DESIGN.md
+// ("Arithmetic"), as in kernels.hip.
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <type_traits>
@@ -10,6 +11,7 @@
 #include "texture.h"
 #include "lighting.h"
 #include "path.h"
+#include "panorama.h"
 #include "lane_map.h"
 
 namespace mrt {
@@ -22,6 +24,7 @@ namespace mrt {
 #include "surface_tex_kernel.h"
 #include "surface_kernel.h"
 #include "light_kernel.h"
+#include "light_panorama_kernel.h"
 #include "path_kernel.h"
 
 // ---- launch wrappers (called from surface.hip, lighting.hip and path.hip); src = a SurfaceSrc ------------------------------------
@@ -41,6 +44,15 @@ hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int
 hipError_t launch_path_step(const TraceParams &p, const PathParams &s, int src, hipStream_t stream)
 {
 	return launch_surface_pass([](auto SRC) { return path_step_kernel<SRC>; }, src, p, stream, s);
+}
+// the two with a panorama resident (light_panorama_kernel.h, path_kernel.h)
+hipError_t launch_light_panorama_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams &pano, int src, hipStream_t stream)
+{
+	return launch_surface_pass([](auto SRC) { return light_panorama_surfaces_kernel<SRC>; }, src, p, stream, s, pano);
+}
+hipError_t launch_path_panorama_step(const TraceParams &p, const PathParams &s, const PanoramaParams &pano, int src, hipStream_t stream)
+{
+	return launch_surface_pass([](auto SRC) { return path_step_panorama_kernel<SRC>; }, src, p, stream, s, pano);
 }
 hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream)
 {

@@ -9,6 +9,7 @@ import ctypes.util
 import numpy as np
 
 from . import bounce as B
+from . import panorama as Pn
 from . import types as T
 
 F = np.float32
@@ -218,10 +219,11 @@ def sky_gradient(d, env):
     return np.where(up[:, None], hi, lo).astype(F)
 
 
-def shade_linear(rows, hit, p, d, lights, mask=None, env=None, cos_outer=None):
+def shade_linear(rows, hit, p, d, lights, mask=None, env=None, cos_outer=None, panorama=None):
     """mrt_light_surfaces for N records: rows as mrt_resolve_surfaces wrote them, hit [N] bool, p [N, 3] positions (used for hits),
-    d [N, 3] incoming directions, mask [n_lights, N] or None, env one T.ENVIRONMENT row or None.  Returns (rgba [N, 4] float32,
-    (pixel, light) pairs that reached pow01)."""
+    d [N, 3] incoming directions, mask [n_lights, N] or None, env one T.ENVIRONMENT row or None, panorama (pixels [H, W, 4], energy)
+    as resident (mrt_upload_panorama) or None; without env it is not read.  Returns (rgba [N, 4] float32, (pixel, light) pairs that
+    reached pow01)."""
     hit = np.asarray(hit, dtype=bool)
     N = rows.shape[0]
     out = np.zeros((N, 4), F)
@@ -234,12 +236,14 @@ def shade_linear(rows, hit, p, d, lights, mask=None, env=None, cos_outer=None):
             zen, gnd, amb = (np.asarray(env[k], dtype=F) for k in ("sky_zenith", "sky_ground", "ambient"))
             blend = r["normal"][:, 1] * F(0.5) + F(0.5)
             one_m = F(1) - r["metallic"]
+            sampled = None if panorama is None else Pn.sky_panorama(panorama[0], panorama[1], r["normal"])
             for c in range(3):
-                a = gnd[c] + (zen[c] - gnd[c]) * blend
+                a = gnd[c] + (zen[c] - gnd[c]) * blend if sampled is None else sampled[:, c]
                 diff = r["albedo"][:, c] * one_m
                 rgb[:, c] = rgb[:, c] + ((diff * a) * amb[c]) * F(env["ambient_energy"])
                 rgb[:, c] = rgb[:, c] + r["emission"][:, c]
-        out[~hit, :3] = sky_gradient(np.asarray(d, dtype=F)[~hit], env)
+        miss_d = np.asarray(d, dtype=F)[~hit]
+        out[~hit, :3] = sky_gradient(miss_d, env) if panorama is None else Pn.sky_panorama(panorama[0], panorama[1], miss_d)
     out[idx, :3] = rgb
     out[idx, 3] = 1
     return out, n_pow

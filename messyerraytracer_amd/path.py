@@ -8,6 +8,7 @@ import numpy as np
 from . import bounce as B
 from . import hemisphere as H
 from . import lighting as Lg
+from . import panorama as Pn
 from . import types as T
 
 F = np.float32
@@ -122,12 +123,13 @@ def roulette(t):
     return np.where(SURVIVAL_CAP < mx, SURVIVAL_CAP, mx).astype(F)
 
 
-def path_step(state, rows, hit, nrm, in_dirs, direct, env, pixel_index, frame, bounce, max_bounces, info=None):
+def path_step(state, rows, hit, nrm, in_dirs, direct, env, pixel_index, frame, bounce, max_bounces, info=None, panorama=None):
     """mrt_path_step for N records: state [N] T.PATH_STATE (not modified), rows as mrt_resolve_surfaces wrote them, hit [N] bool, nrm
     [N, 3] the records' normals, in_dirs [N, 3] the incoming directions as given, direct [N, >= 3] what mrt_light_surfaces wrote with
     env == NULL, env one T.ENVIRONMENT row, pixel_index [N].  Returns (state', select [N] uint8, lobe [N] uint8, active count).  info: an
     optional dict that receives what happened to each entry, [N] bool each: missed, invalid (a sample below the surface), killed and
-    survived (roulette), stopped (the last bounce)."""
+    survived (roulette), stopped (the last bounce).  panorama: (pixels [H, W, 4], energy) as resident (mrt_upload_panorama) or None -- the
+    sky of a miss is then its sample."""
     N = state.shape[0]
     st = state.copy()
     hit = np.asarray(hit, dtype=bool)
@@ -141,7 +143,8 @@ def path_step(state, rows, hit, nrm, in_dirs, direct, env, pixel_index, frame, b
         what["missed"] = miss
         what["stopped"] = on & hit & (bounce == max_bounces)
         if miss.any():
-            sky = Lg.sky_gradient(np.asarray(in_dirs, dtype=F)[miss], env)
+            miss_d = np.asarray(in_dirs, dtype=F)[miss]
+            sky = Lg.sky_gradient(miss_d, env) if panorama is None else Pn.sky_panorama(panorama[0], panorama[1], miss_d)
             r[miss] = r[miss] + t[miss] * sky
         idx = np.nonzero(on & hit)[0]
         if idx.size:
