@@ -1114,6 +1114,73 @@ int mrt_clear_panorama(mrt_ctx *ctx);
  *   Both are within 1 fp32 ulp of the correctly rounded function.
  * Not taken: prefiltered or importance-sampled IBL, mipmaps, RGBE or half-float images, the running average over sample_index,
  * and a panorama per member of an mrt_group (a group's contexts take uploads one by one, mrt_group_context). */
+
+/* ---- the renderer's AOV channels and its 8-bit image: the ten channels of RayImage besides COLOR as ShadePass's per-channel
+ * functions write them (src/modules/graphics/shade_pass.h:337-395, :732-884; the enum is ray_image.h:43-56), the last two lines of
+ * shade_material for a lit frame (tone map and gamma on hits, the sky as it is on misses: shade_pass.h:669-675, :718-725), and
+ * RayImage::to_image (ray_image.cpp:22-35) -- from the hit records, the regenerated rays, the resident shade data and the resident
+ * texture set, so that a RayRenderer frame ends on the device in displayable bytes.  No scene is required and nothing is walked. */
+enum { MRT_CHANNEL_COLOR = 0, MRT_CHANNEL_NORMAL, MRT_CHANNEL_DEPTH, MRT_CHANNEL_BARYCENTRIC, MRT_CHANNEL_POSITION,
+       MRT_CHANNEL_PRIM_ID, MRT_CHANNEL_HIT_MASK, MRT_CHANNEL_ALBEDO, MRT_CHANNEL_WIREFRAME, MRT_CHANNEL_UV,
+       MRT_CHANNEL_FRESNEL, MRT_CHANNEL_COUNT };          /* RayImage::Channel, value for value */
+typedef struct mrt_channel_out {                          /* 192 bytes */
+	uint32_t struct_size, reserved;                       /* sizeof(mrt_channel_out); reserved is not read */
+	float inv_depth_range, inv_pos_range;                 /* ray_renderer.cpp:752-753; finite */
+	float   *d_rgba [MRT_CHANNEL_COUNT];                  /* per channel, optional: 4 floats per record */
+	uint8_t *d_rgba8[MRT_CHANNEL_COUNT];                  /* per channel, optional: to_image of the same values, 4 bytes per record */
+} mrt_channel_out;
+/* A channel is selected when either of its two pointers is non-null; either alone is allowed (bytes alone save the 16-byte store).
+ * Entry MRT_CHANNEL_COLOR of both arrays must be null: COLOR is mrt_light_surfaces / mrt_light_grid_surfaces followed by
+ * mrt_finish_color.  Records, rays and the grid are those of mrt_resolve_surfaces / mrt_resolve_grid_surfaces (device pointers;
+ * every output indexed by the record, within the band for the grid form).  With no shade data or textures resident every hit shades
+ * as against an empty SceneShadeData.  Plain fp32, one operation at a time, nothing contracted.
+ *   hit, p, d, t, u, v, prim of a record as for mrt_resolve_surfaces: in the device layout p = o + d * t per component, in the host
+ *   layout the carried position; d is the ray's direction as given.  in_range, w = (1 - u) - v, the smooth normal ns (the record's
+ *   normal where no normals are resident or prim is out of range), uv, uv_ok, bound, the perturbed normal n and the textured albedo
+ *   exactly as mrt_resolve_surfaces states them, with and without a texture set resident.
+ * A miss writes {0, 0, 0, 1} to every selected channel.  A hit writes alpha 1 and:
+ *   NORMAL       n.c * 0.5f + 0.5f -- n the row normal of the resolve, perturbed where the textured resolve perturbs it.
+ *   DEPTH        x = 1.0f - t * inv_depth_range; x < 0 ? 0 : (x > 1 ? 1 : x), three times.
+ *   BARYCENTRIC  {u, v, w}.
+ *   POSITION     f = p.c * inv_pos_range; f - floorf(f).
+ *   PRIM_ID      h = prim (uint32_t); twice h = ((h >> 16) ^ h) * 0x45d9f3bu; h = (h >> 16) ^ h;
+ *                {(float)(h & 255) / 255.0f, (float)((h >> 8) & 255) / 255.0f, (float)((h >> 16) & 255) / 255.0f}.
+ *   HIT_MASK     1, three times.
+ *   ALBEDO       the resolve's albedo: 0.75 three times by default, else the material's, times the albedo texture's sample where the
+ *                textured resolve samples it.
+ *   WIREFRAME    m = min(w, u, v) as std::min({w, u, v}) selects (m = w; if (u < m) m = u; if (v < m) m = v);
+ *                s = (m - 0.01f) / (0.03f - 0.01f), the divisor one fp32 constant; s = s < 0 ? 0 : (s > 1 ? 1 : s);
+ *                e = 1.0f - (s * s) * (3.0f - 2.0f * s); x = 0.08f + e * (1.0f - 0.08f), three times.
+ *   UV           {0.5, 0.5, 0}; with UVs resident and in_range {uv.x - floorf(uv.x), uv.y - floorf(uv.y), 0} -- no finiteness
+ *                test: a UV that is not finite gives what the arithmetic gives.
+ *   FRESNEL      q = (ns.x * -d.x + ns.y * -d.y) + ns.z * -d.z -- the smooth normal, and -d not normalized (both unlike the
+ *                resolve's n_dot_v); q = q < 0 ? 0 : (q > 1 ? 1 : q); {q, q, 0.3f + q * 0.7f}.
+ * to_rgba8(c), RayImage::to_image per component: x = c * 255.0f + 0.5f; x = 0.0f < x ? x : 0.0f (a NaN becomes 0);
+ *   x = x < 255.0f ? x : 255.0f; (uint8_t)x, truncated.  A channel's d_rgba8 is this of the four floats the channel writes or would
+ *   write.
+ * Flags: the array form MRT_FLAG_HOST_LAYOUT and MRT_FLAG_ASYNC, the grid form MRT_FLAG_ASYNC.  count == 0 or an empty band:
+ * MRT_OK, nothing written.  Neither call touches the scene, the tuner, the tile schedule or mrt_stats.
+ * MRT_ERR_INVALID before any device work, in this order: a null context, descriptor or required pointer (rays or camera, hits);
+ * a wrong struct_size; an unknown flag; a non-null COLOR entry; no channel selected; an inv_*_range that is not finite; a bad band
+ * or camera (as mrt_resolve_grid_surfaces).  MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_shade_channels(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const mrt_channel_out *out,
+		uint32_t flags);
+int mrt_shade_grid_channels(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const void *d_hits, const mrt_channel_out *out, uint32_t flags);
+/* The end of shade_material for a lit frame.  Per record, {r, g, b, a} from d_lit_rgba (what mrt_light_surfaces /
+ * mrt_light_grid_surfaces wrote with an environment: a is 1 for a hit and 0 for a miss):
+ *   a != 0: {g(tm(r)), g(tm(g)), g(tm(b)), 1} with mrt_path_finish's tm, g and pow01, hp(11.2f) once per call on the host;
+ *   otherwise {r, g, b, 1}: the sky as it is.
+ * d_rgba (4 floats per record, optional) may be d_lit_rgba itself; d_rgba8 (4 bytes per record, optional) is to_rgba8 of the result.
+ * Flags: MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID, in this order: a null context or d_lit_rgba; an
+ * unknown flag; tonemap_mode > 4; both outputs null.  MRT_ERR_PENDING while a dispatch is pending. */
+int mrt_finish_color(mrt_ctx *ctx, const float *d_lit_rgba, uint64_t count, uint32_t tonemap_mode, float *d_rgba,
+		uint8_t *d_rgba8, uint32_t flags);
+/* RayImage::to_image of any channel: d_rgba8[4 i + c] = to_rgba8(d_rgba[4 i + c]).  Flags: MRT_FLAG_ASYNC.  count == 0: MRT_OK.
+ * MRT_ERR_INVALID: a null context or pointer; an unknown flag (in this order).  MRT_ERR_PENDING while a dispatch is pending.
+ * Not taken: RayImage's other image formats, resizing, and COLOR inside mrt_shade_channels (it needs the lights and the shadow
+ * masks: the lighting calls). */
+int mrt_image_to_rgba8(mrt_ctx *ctx, const float *d_rgba, uint64_t count, uint8_t *d_rgba8, uint32_t flags);
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to
  * tokens written by a cast with MRT_FLAG_TOKEN_OUT: mrt_hit32 records (mrt_host_hit44 with

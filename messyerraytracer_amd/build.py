@@ -14,8 +14,8 @@ OBJ = os.path.join(HERE, "_obj")  # object files, their dependency files and the
 # The library's translation units.  The kernels are three of them: kernels.hip = the walks, shade_kernels.hip = the
 # passes over hit records, prep_kernels.hip = what prepares a scene or a cast; an edit to one is compiled apart from the others.
 SOURCES = ["kernels.hip", "shade_kernels.hip", "prep_kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip",
-           "device_build.hip", "refit.hip", "tlas_device.hip", "surface.hip", "texture.hip", "lighting.hip", "path.hip", "panorama.hip",
-           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
+           "device_build.hip", "refit.hip", "tlas_device.hip", "surface.hip", "texture.hip", "lighting.hip", "path.hip", "panorama.hip", "channels.hip",
+           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
 # implicitly (-ffp-contract=off), so every result is unchanged.
@@ -46,6 +46,7 @@ DRIVERS = {
     "path_data_test": (["host/path_data_test.cpp", "host/path_data.cpp"], CPU, False),
     "texture_data_test": (["host/texture_data_test.cpp", "host/texture_data.cpp"], CPU, False),
     "panorama_data_test": (["host/panorama_data_test.cpp", "host/panorama_data.cpp"], CPU, False),  # panorama.h, shared with the kernels
+    "channel_data_test": (["host/channel_data_test.cpp", "host/channel_data.cpp"], CPU, False),  # channels.h, shared with the kernels
     "lane_map_test": (["host/lane_map_test.cpp"], LANE + ["-O2"], False),  # lane_map.h
     "lane_map_test_san": (["host/lane_map_test.cpp"], LANE + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
                                                               "-fno-sanitize-recover=undefined"], False),
@@ -172,6 +173,7 @@ build_light_data_test = _driver("light_data_test")
 build_path_data_test = _driver("path_data_test")
 build_texture_data_test = _driver("texture_data_test")
 build_panorama_data_test = _driver("panorama_data_test")
+build_channel_data_test = _driver("channel_data_test")
 
 
 def build_build_rules_test(force: bool = False, sanitize: bool = False) -> str:

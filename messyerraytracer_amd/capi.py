@@ -35,6 +35,7 @@ SYMBOLS = [
     "mrt_upload_shade_data", "mrt_clear_shade_data", "mrt_resolve_surfaces", "mrt_resolve_grid_surfaces",
     "mrt_upload_textures", "mrt_clear_textures",
     "mrt_upload_panorama", "mrt_clear_panorama",
+    "mrt_shade_channels", "mrt_shade_grid_channels", "mrt_finish_color", "mrt_image_to_rgba8",
     "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
     "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
@@ -108,6 +109,16 @@ class Panorama(C.Structure):
     _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("energy", C.c_float), ("flags", C.c_uint32)]
 
 
+CHANNEL_COLOR, CHANNEL_NORMAL, CHANNEL_DEPTH, CHANNEL_BARYCENTRIC, CHANNEL_POSITION, CHANNEL_PRIM_ID, CHANNEL_HIT_MASK, CHANNEL_ALBEDO, \
+    CHANNEL_WIREFRAME, CHANNEL_UV, CHANNEL_FRESNEL, CHANNEL_COUNT = range(12)   # RayImage::Channel
+
+
+class ChannelOut(C.Structure):
+    """mrt_channel_out"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("inv_depth_range", C.c_float), ("inv_pos_range", C.c_float),
+                ("d_rgba", C.c_void_p * CHANNEL_COUNT), ("d_rgba8", C.c_void_p * CHANNEL_COUNT)]
+
+
 class LightOut(C.Structure):
     """mrt_light_out"""
     _fields_ = [("d_rgba", C.c_void_p)]
@@ -125,6 +136,7 @@ TEXTURES_ON_DEVICE = 1
 TEXEL_RGBA8, TEXEL_RGBA32F = 0, 1
 PANORAMA_ON_DEVICE = 1
 PANORAMA_MAX_DIM = 16384
+STRUCT_CHANNEL_OUT = 24   # mrt_struct_size index (23: not a struct)
 STRUCT_PANORAMA = 22   # mrt_struct_size index (21: not a struct)
 STRUCT_TEXTURE, STRUCT_MATERIAL_TEXTURES, STRUCT_TEXTURE_SET = 18, 19, 20   # mrt_struct_size indices (17: not a struct)
 STRUCT_PATH_STATE, STRUCT_PATH_STEP_DESC = 15, 16   # mrt_struct_size indices (14: not a struct)
@@ -269,6 +281,11 @@ def load():
     L.mrt_path_grid_step.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.POINTER(PathStepDesc), C.c_uint32]
     L.mrt_path_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]
+    L.mrt_shade_channels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ChannelOut), C.c_uint32]
+    L.mrt_shade_grid_channels.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.POINTER(ChannelOut), C.c_uint32]
+    L.mrt_finish_color.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.mrt_image_to_rgba8.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
     L.mrt_cast_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mrt_expand_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
     L.mrt_expand_grid_tokens.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -321,6 +338,16 @@ def surface_out(d_rows=None, d_bounce_surface=None, d_out_hits=None):
     """mrt_surface_out from its fields (device pointers / tensors or None)"""
     v = [None if x is None else _ptr(x).value for x in (d_rows, d_bounce_surface, d_out_hits)]
     return SurfaceOut(v[0], v[1], v[2])
+
+
+def channel_out(inv_depth_range, inv_pos_range, rgba=None, rgba8=None):
+    """mrt_channel_out from its fields: rgba / rgba8 map a CHANNEL_* value to the device pointer / tensor of that channel's float / byte
+    plane (a channel in neither is not selected)"""
+    d = ChannelOut(C.sizeof(ChannelOut), 0, inv_depth_range, inv_pos_range)
+    for planes, field in ((rgba, d.d_rgba), (rgba8, d.d_rgba8)):
+        for c, x in (planes or {}).items():
+            field[c] = None if x is None else _ptr(x).value
+    return d
 
 
 def shadow_lights(lights) -> np.ndarray:
@@ -931,6 +958,29 @@ class Context:
         """The frame's last pass: tone mapping (0 linear, 1 Reinhard, 2 Hable, 3 ACES, 4 AgX) and gamma 2.2 of every entry's radiance,
         4 floats per entry with alpha 1."""
         self._chk(self.L.mrt_path_finish(self.h, _ptr(d_state), count, tonemap_mode, _ptr(d_rgba), flags))
+
+    def shade_channels(self, d_rays, d_hits, count, inv_depth_range, inv_pos_range, rgba=None, rgba8=None, flags=0):
+        """The renderer's channels besides COLOR for the records of a cast (device pointers / tensors: mrt_ray32 + mrt_hit32, or
+        mrt_host_ray60 + mrt_host_hit44 with FLAG_HOST_LAYOUT) against the resident shade data and textures.  rgba / rgba8: dicts from a
+        CHANNEL_* value to that channel's plane, 4 floats / 4 bytes per record; a channel in either is shaded."""
+        out = channel_out(inv_depth_range, inv_pos_range, rgba, rgba8)
+        self._chk(self.L.mrt_shade_channels(self.h, _ptr(d_rays), _ptr(d_hits), count, C.byref(out), flags))
+
+    def shade_grid_channels(self, cam, grid_w, grid_h, d_hits, inv_depth_range, inv_pos_range, rgba=None, rgba8=None, y0=0, y1=None, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (d_hits: its mrt_hit32 records on the device; the planes indexed by
+        the record within the band)."""
+        y1 = grid_h if y1 is None else y1
+        out = channel_out(inv_depth_range, inv_pos_range, rgba, rgba8)
+        self._chk(self.L.mrt_shade_grid_channels(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(out), flags))
+
+    def finish_color(self, d_lit_rgba, count, d_rgba=None, d_rgba8=None, tonemap_mode=0, flags=0):
+        """The last pass of a lit frame (what light_surfaces wrote with an environment): tone mapping and gamma 2.2 on the hits, the sky
+        as it is on the misses, alpha 1; d_rgba (may be d_lit_rgba) 4 floats per record, d_rgba8 its 8-bit image, at least one."""
+        self._chk(self.L.mrt_finish_color(self.h, _ptr(d_lit_rgba), count, tonemap_mode, _optr(d_rgba), _optr(d_rgba8), flags))
+
+    def image_to_rgba8(self, d_rgba, count, d_rgba8, flags=0):
+        """The 8-bit image of a float plane: 4 bytes per record."""
+        self._chk(self.L.mrt_image_to_rgba8(self.h, _ptr(d_rgba), count, _ptr(d_rgba8), flags))
 
     def expand_tokens(self, d_rays, d_tokens, d_hits, count, flags=0, stream=None):
         """Device pointers; enqueued on `stream` (raw hipStream_t) or the context's stream, not waited for."""

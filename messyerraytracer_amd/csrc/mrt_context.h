@@ -52,6 +52,11 @@ struct PanoramaParams;
 hipError_t launch_light_panorama_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams &pano, int src, hipStream_t stream);
 hipError_t launch_path_panorama_step(const TraceParams &p, const PathParams &s, const PanoramaParams &pano, int src, hipStream_t stream);
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream);
+// the renderer's channels (channel_kernel.h): src = a SurfaceSrc, t all zero with no texture set resident; the lit frame's last pass
+// and the 8-bit image (path_frame_kernel.h)
+hipError_t launch_shade_channels(const TraceParams &p, const ChannelParams &c, const TextureParams &t, int src, hipStream_t stream);
+hipError_t launch_finish_color(const float *lit, uint64_t count, uint32_t mode, float white, float *rgba, uint8_t *rgba8, hipStream_t stream);
+hipError_t launch_image_to_rgba8(const float *rgba, uint64_t count, uint8_t *rgba8, hipStream_t stream);
 // ---- device_build.hip
 hipError_t grow_arena(BuildArena *arena, size_t need, hipStream_t stream); // hipErrorOutOfMemory: no allocation, the arena is empty
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);

@@ -242,6 +242,23 @@ struct SurfaceParams {
 	void *out_hits;            // optional: the records in the input layout, shading normal in place of the normal
 };
 
+// ---- the renderer's channels (channel_kernel.h): up to ten RGBA planes per hit record, floats and / or bytes, nothing walked -------
+// Record i of a channel pass is entry i, as for a resolve; the shade data as in SurfaceParams.  mask: bit c set = channel c is
+// selected (one of its two planes is given); a launch may carry a subset of a call's selection (channels.hip).
+struct ChannelParams {
+	const void *records;       // mrt_hit32 (SURF_RAY32, SURF_GRID) or mrt_host_hit44 (SURF_HOST)
+	const void *shade_rows;    // n_tris x 64 bytes (null when no per-triangle array is resident)
+	const void *materials;     // n_materials x mrt_material
+	uint32_t n_tris, n_materials, present;
+	uint32_t mask;
+	float inv_depth_range, inv_pos_range;
+	float *rgba[MRT_CHANNEL_COUNT];    // float4 per record, or null
+	uint8_t *rgba8[MRT_CHANNEL_COUNT]; // 4 bytes per record, or null
+};
+// the channels that read the shade row, and those that read the material, the binding, the tangents and the texels
+constexpr uint32_t CHANNELS_ROW = (1u << MRT_CHANNEL_NORMAL) | (1u << MRT_CHANNEL_ALBEDO) | (1u << MRT_CHANNEL_UV) | (1u << MRT_CHANNEL_FRESNEL);
+constexpr uint32_t CHANNELS_MATERIAL = (1u << MRT_CHANNEL_NORMAL) | (1u << MRT_CHANNEL_ALBEDO);
+
 // What the one launcher and the one set of kernels need to know of a source family, by its parameter struct: its three sources
 // (RaySrc values: they are printed in mrt_last_kernel_variant), the modes it has (a family with one does not print it) and its name.
 template <class S> struct SourceFamily;

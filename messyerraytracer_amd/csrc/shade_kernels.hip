@@ -1,6 +1,6 @@
 // shade_kernels.hip — gfx950 kernels of the shading passes over hit records: the resolve to shading surfaces (plain and textured), the
-// direct light and the path tracer's per-pixel state (the lighting and the step also with a resident panorama) and the packing of
-// shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
+// direct light and the path tracer's per-pixel state (the lighting and the step also with a resident panorama), the renderer's
+// channels with the two image passes, and the packing of shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
 // source_common.h with the walks of kernels.hip, and are compiled apart from them.  The arithmetic is the canonical form of DESIGN.md
 // ("Arithmetic"), as in kernels.hip.
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 #include "lighting.h"
 #include "path.h"
 #include "panorama.h"
+#include "channels.h"
 #include "lane_map.h"
 
 namespace mrt {
@@ -26,6 +27,7 @@ namespace mrt {
 #include "light_kernel.h"
 #include "light_panorama_kernel.h"
 #include "path_kernel.h"
+#include "channel_kernel.h"
 
 // ---- launch wrappers (called from surface.hip, lighting.hip and path.hip); src = a SurfaceSrc ------------------------------------
 hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream)
@@ -61,6 +63,19 @@ hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t s
 hipError_t launch_path_finish(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba, hipStream_t stream)
 {
 	return launch_per_entry<true>(path_finish_kernel, count, stream, state, count, mode, white, rgba);
+}
+// the renderer's channels (channel_kernel.h) and the two image passes (path_frame_kernel.h), called from channels.hip
+hipError_t launch_shade_channels(const TraceParams &p, const ChannelParams &c, const TextureParams &t, int src, hipStream_t stream)
+{
+	return launch_surface_pass([](auto SRC) { return shade_channels_kernel<SRC>; }, src, p, stream, c, t);
+}
+hipError_t launch_finish_color(const float *lit, uint64_t count, uint32_t mode, float white, float *rgba, uint8_t *rgba8, hipStream_t stream)
+{
+	return launch_per_entry<true>(finish_color_kernel, count, stream, lit, count, mode, white, rgba, rgba8);
+}
+hipError_t launch_image_to_rgba8(const float *rgba, uint64_t count, uint8_t *rgba8, hipStream_t stream)
+{
+	return launch_per_entry<true>(image_to_rgba8_kernel, count, stream, rgba, count, rgba8);
 }
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream)
 {

@@ -23,7 +23,8 @@
 //        P = (T * ts.x + B * ts.y) + N * ts.z; l2(P) < 1e-8f ? N : P / sqrt(l2)
 //        n_dot_v from the result, which is the row's normal and d_out_hits' normal
 //   albedo texture: bound, b.albedo_texture != none, uv_ok: albedo.c *= sample.c (no sRGB step)
-// Misses and ids out of range as surface_kernel.h; where no binding applies the outputs equal resolve_surfaces_kernel's byte for byte.
+// (The row gather, uv, the smooth normal, the binding and the normal map's lines are surface_tex_steps.inc, which channel_kernel.h
+// includes too.)  Misses and ids out of range as surface_kernel.h; where no binding applies the outputs equal resolve_surfaces_kernel's byte for byte.
 // Every texel address lies inside the pool: u - floorf(u) of a finite u is in [0, 1], so fx is in [-0.5, width - 0.5] (width <= 16384:
 // exact), x0 in -1 .. width - 1, and after the wrap x0 and x1 are in 0 .. width - 1; texture indices and sizes were checked at upload.
 #pragma once
@@ -83,59 +84,23 @@ __global__ __launch_bounds__(MRT_WG) void resolve_textured_surfaces_kernel(const
 	float metallic = 0.0f, roughness = 0.5f; // (a miss's bounce pair)
 	float nx = sf.nx, ny = sf.ny, nz = sf.nz;
 	if (hit) {
-		const bool in_range = prim < s.n_tris;
-		float4 t0 = {}, t1 = {}, t2 = {}, t3 = {};
-		if (in_range && s.present != 0u) {
-			const float4 *row = reinterpret_cast<const float4 *>(s.shade_rows) + (size_t)prim * 4u;
-			t0 = row[0]; t1 = row[1]; t2 = row[2]; t3 = row[3];
-		}
+		// the row, uv, the smooth normal, the binding and perturb_normal: surface_tex_steps.inc, shared with channel_kernel.h
+#define MRT_TEX_STEP 1
+#include "surface_tex_steps.inc"
+#undef MRT_TEX_STEP
 		const float w = (1.0f - u) - v;
-		bool uv_ok = false;
-		if (in_range && (s.present & SHADE_HAS_UVS)) {
-			o3.x = (t1.w * w + t3.x * u) + t3.z * v;
-			o3.y = (t2.w * w + t3.y * u) + t3.w * v;
-			uv_ok = fabsf(o3.x) < __builtin_inff() && fabsf(o3.y) < __builtin_inff(); // (false for a NaN)
-		}
-		if (in_range && (s.present & SHADE_HAS_NORMALS)) {
-			nx = (t0.x * w + t1.x * u) + t2.x * v;
-			ny = (t0.y * w + t1.y * u) + t2.y * v;
-			nz = (t0.z * w + t1.z * u) + t2.z * v;
-			normalize3(nx, ny, nz);
-		}
-		// the material's binding
-		const uint32_t id = __float_as_uint(t0.w);
-		const bool material = in_range && (s.present & SHADE_HAS_IDS) && id < s.n_materials;
-		uint32_t albedo_tex = MRT_NO_TEXTURE, normal_tex = MRT_NO_TEXTURE;
-		float normal_scale = 0.0f;
-		if (material && id < t.n_bindings) {
-			const uint4 b = reinterpret_cast<const uint4 *>(t.bindings)[id];
-			albedo_tex = b.x; normal_tex = b.y; normal_scale = __uint_as_float(b.z);
-		}
-		if (normal_tex != MRT_NO_TEXTURE && t.tangents != nullptr && prim < t.n_tangent_tris && uv_ok) {
-			const float4 *tr = reinterpret_cast<const float4 *>(t.tangents) + (size_t)prim * 3u;
-			const float4 a0 = tr[0], a1 = tr[1], a2 = tr[2]; // {t0 xyz, t1.x | t1 yz, t2 xy | t2.z, sign0, sign1, sign2}
-			if (a2.y != 0.0f || a2.z != 0.0f || a2.w != 0.0f) {
-				float tx = (a0.x * w + a0.w * u) + a1.z * v;
-				float ty = (a0.y * w + a1.x * u) + a1.w * v;
-				float tz = (a0.z * w + a1.y * u) + a2.x * v;
-				const float tl2 = (tx * tx + ty * ty) + tz * tz;
-				if (tl2 < 1e-8f) { tx = 1.0f; ty = 0.0f; tz = 0.0f; }
-				else { const float l = sqrtf(tl2); tx = tx / l; ty = ty / l; tz = tz / l; }
-				const float bsign = ((a2.y * w + a2.z * u) + a2.w * v) >= 0.0f ? 1.0f : -1.0f;
-				const float k = (nx * tx + ny * ty) + nz * tz;
-				tx = tx - nx * k; ty = ty - ny * k; tz = tz - nz * k;
-				normalize3(tx, ty, tz);
-				const float bx = (ny * tz - nz * ty) * bsign, by = (nz * tx - nx * tz) * bsign, bz = (nx * ty - ny * tx) * bsign;
-				float cr, cg, cb;
-				sample_bilinear(t, normal_tex, o3.x, o3.y, cr, cg, cb);
-				float sx = cr * 2.0f - 1.0f, sy = cg * 2.0f - 1.0f;
-				const float sz = cb * 2.0f - 1.0f;
-				sx = sx * normal_scale; sy = sy * normal_scale;
-				const float px = (tx * sx + bx * sy) + nx * sz, py = (ty * sx + by * sy) + ny * sz, pz = (tz * sx + bz * sy) + nz * sz;
-				const float pl2 = (px * px + py * py) + pz * pz;
-				if (!(pl2 < 1e-8f)) { const float l = sqrtf(pl2); nx = px / l; ny = py / l; nz = pz / l; }
-			}
-		}
+#define MRT_TEX_STEP 2
+#include "surface_tex_steps.inc"
+#undef MRT_TEX_STEP
+#define MRT_TEX_STEP 3
+#include "surface_tex_steps.inc"
+#undef MRT_TEX_STEP
+#define MRT_TEX_STEP 4
+#include "surface_tex_steps.inc"
+#undef MRT_TEX_STEP
+#define MRT_TEX_STEP 5
+#include "surface_tex_steps.inc"
+#undef MRT_TEX_STEP
 		float vx = -sf.dx, vy = -sf.dy, vz = -sf.dz;
 		normalize3(vx, vy, vz);
 		const float ndv = (nx * vx + ny * vy) + nz * vz;
