@@ -12,6 +12,7 @@ import pytest
 
 from messyerraytracer_amd import capi, synth, types as T
 from messyerraytracer_amd import hemisphere as H
+from messyerraytracer_amd import shadow as S
 from oracle import pyoracle as po
 import affine_scene
 
@@ -352,25 +353,10 @@ def test_query_mask_leaves_the_walls_out(built, kind):
 
 
 def shadow_mask(sc, rays, hits, lights):
-    """The shadow formula of include/mrt_hip.h for a point light and a directional one (as test_shadow_gpu.py restates it), traced by
-    the oracle: 1 lit, 0 shadowed, light-major."""
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        hit = hits["prim_id"] != -1
-        org = hit_point(rays, hits) + hits["normal"] * F(1e-3)
-        out = []
-        for L in lights:
-            s = np.zeros(rays.shape[0], dtype=T.RAY32)
-            s["origin"] = org
-            if L["type"] == T.LIGHT_DIRECTIONAL:
-                s["direction"], s["t_max"], ok = L["direction"].astype(F), F(1000.0), hit
-            else:
-                to = L["position"].astype(F)[None, :] - org
-                dist = np.sqrt((to[:, 0] * to[:, 0] + to[:, 1] * to[:, 1]) + to[:, 2] * to[:, 2])
-                s["direction"], s["t_max"], ok = to / dist[:, None], dist, hit & ~(dist < F(1e-6))
-            s[~ok] = H.PLACEHOLDER[0]
-            occ = sc.oracle(s, any_hit=True)["prim_id"] >= 0
-            out.append((~(ok & occ)).astype(np.uint8))
-    return np.concatenate(out)
+    """The shadow formula of include/mrt_hip.h (messyerraytracer_amd/shadow.py) traced by the oracle: 1 lit, 0 shadowed, light-major."""
+    srays, traced = S.shadow_rays(hit_point(rays, hits), hits["normal"], hits["prim_id"] != -1, lights)
+    occ = sc.oracle(srays, any_hit=True)["prim_id"] >= 0
+    return (~(traced & occ)).astype(np.uint8)
 
 
 @pytest.mark.parametrize("kind", ["room", "room_tl"])

@@ -1,5 +1,5 @@
 """mrt_cast_reflections / mrt_cast_grid_reflections: mirror-reflection rays made in the trace kernels from resident hit records,
-against the formula restated here in numpy float32 (one operation at a time) and traced by the oracle -- byte for byte -- and against
+against the formula restated in numpy float32 (messyerraytracer_amd/reflection.py, one operation at a time) and traced by the oracle -- byte for byte -- and against
 the same rays cast through mrt_cast(NEAREST).  A soup (back faces: the normal flip), flat and two-level synth.room(); grids with whole
 and clipped tiles and a row band, records of mrt_cast in both layouts; the rays written out; selection masks; query masks; the plain
 and the persistent kernels; chained shadow casts and a second bounce; ASYNC; primary grids unaffected; errors."""
@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 from messyerraytracer_amd import capi, synth, types as T
+from messyerraytracer_amd import reflection as R
+from messyerraytracer_amd import shadow as S
 from oracle import pyoracle as po
 import affine_scene
 
@@ -19,10 +21,7 @@ DEV = capi.FLAG_RAYS_ON_DEVICE | capi.FLAG_HITS_ON_DEVICE
 ROOM_CAM = ((0.0, 3.0, 4.6), (0.0, -0.35, -1.0), 70.0)
 SOUP_CAM = ((0.0, 0.0, -12.0), (0.0, 0.0, 1.0), 50.0)
 MAX_DIST = F(25.0)
-PLACEHOLDER = np.zeros(1, dtype=T.RAY32)  # the reference's Ray(0, (0, 1, 0), 0, 0) for records without a ray
-PLACEHOLDER["direction"] = (0.0, 1.0, 0.0)
-PLACEHOLDER_HIT = np.zeros(1, dtype=T.HIT32)  # what mrt_cast writes for it: t = t_max = 0, a miss
-PLACEHOLDER_HIT["prim_id"] = -1
+PLACEHOLDER, PLACEHOLDER_HIT = R.PLACEHOLDER, R.PLACEHOLDER_HIT  # the reference's Ray(0, (0, 1, 0), 0, 0) and mrt_cast's record of it
 
 
 class Scene:
@@ -67,20 +66,8 @@ def scene(kind):
 
 
 def reflection_rays(dirs, pos, nrm, traced, max_distance=MAX_DIST):
-    """The formula of include/mrt_hip.h in float32, one operation at a time; the placeholder where no ray is traced."""
-    with np.errstate(over="ignore", invalid="ignore"):  # (the position of a miss is not used)
-        dx, dy, dz = dirs[:, 0], dirs[:, 1], dirs[:, 2]
-        n = nrm.astype(F).copy()
-        c = (n[:, 0] * dx + n[:, 1] * dy) + n[:, 2] * dz
-        flip = c > F(0)
-        n[flip] = -n[flip]
-        k = F(2) * ((n[:, 0] * dx + n[:, 1] * dy) + n[:, 2] * dz)
-        rays = np.zeros(dirs.shape[0], dtype=T.RAY32)
-        rays["direction"] = np.stack([dx - k * n[:, 0], dy - k * n[:, 1], dz - k * n[:, 2]], axis=1)
-        rays["origin"] = pos + n * F(0.01)
-        rays["t_min"], rays["t_max"] = F(0), max_distance
-    rays[~traced] = PLACEHOLDER[0]
-    return rays, flip & traced
+    """messyerraytracer_amd/reflection.py at this file's max_distance"""
+    return R.reflection_rays(dirs, pos, nrm, traced, max_distance)
 
 
 def hit_point(rays, hits):
@@ -282,25 +269,10 @@ def test_query_mask_leaves_the_walls_out(built, kind):
 
 
 def shadow_mask(sc, rays, hits, lights):
-    """The shadow formula of include/mrt_hip.h for a point light and a directional one (as test_shadow_gpu.py restates it), traced by
-    the oracle: 1 lit, 0 shadowed, light-major."""
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        hit = hits["prim_id"] != -1
-        org = hit_point(rays, hits) + hits["normal"] * F(1e-3)
-        out = []
-        for L in lights:
-            s = np.zeros(rays.shape[0], dtype=T.RAY32)
-            s["origin"] = org
-            if L["type"] == T.LIGHT_DIRECTIONAL:
-                s["direction"], s["t_max"], ok = L["direction"].astype(F), F(1000.0), hit
-            else:
-                to = L["position"].astype(F)[None, :] - org
-                dist = np.sqrt((to[:, 0] * to[:, 0] + to[:, 1] * to[:, 1]) + to[:, 2] * to[:, 2])
-                s["direction"], s["t_max"], ok = to / dist[:, None], dist, hit & ~(dist < F(1e-6))
-            s[~ok] = PLACEHOLDER[0]
-            occ = sc.oracle(s, any_hit=True)["prim_id"] >= 0
-            out.append((~(ok & occ)).astype(np.uint8))
-    return np.concatenate(out)
+    """The shadow formula of include/mrt_hip.h (messyerraytracer_amd/shadow.py) traced by the oracle: 1 lit, 0 shadowed, light-major."""
+    srays, traced = S.shadow_rays(hit_point(rays, hits), hits["normal"], hits["prim_id"] != -1, lights)
+    occ = sc.oracle(srays, any_hit=True)["prim_id"] >= 0
+    return (~(traced & occ)).astype(np.uint8)
 
 
 @pytest.mark.parametrize("kind", ["room", "room_tl"])

@@ -1,5 +1,5 @@
 """mrt_cast_shadows / mrt_cast_grid_shadows: shadow rays made in the trace kernels from resident hit records, against the formula
-restated here in numpy float32 (the way the oracle restates RayCamera) and traced by the oracle -- byte for byte -- and against the
+restated in numpy float32 (messyerraytracer_amd/shadow.py, the way the oracle restates RayCamera) and traced by the oracle -- byte for byte -- and against the
 same rays cast through mrt_cast(ANY_HIT, BOOL_OUT).  Flat and two-level synth.room(), a soup; grids with whole and clipped tiles and a
 row band; one batch large enough for the persistent kernels; ASYNC; primary grids unaffected by shadow casts between them; errors."""
 import ctypes as C
@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from messyerraytracer_amd import capi, synth, types as T
+from messyerraytracer_amd.shadow import shadow_rays
 from oracle import pyoracle as po
 import affine_scene
 
@@ -17,8 +18,6 @@ F = np.float32
 DEV = capi.FLAG_RAYS_ON_DEVICE | capi.FLAG_HITS_ON_DEVICE
 ROOM_CAM = ((0.0, 3.0, 4.6), (0.0, -0.35, -1.0), 70.0)
 SOUP_CAM = ((0.0, 0.0, -12.0), (0.0, 0.0, 1.0), 50.0)
-DEGENERATE = np.zeros(1, dtype=T.RAY32)  # the reference's Ray(0, (0, 1, 0), 0, 0) for pairs it does not trace
-DEGENERATE["direction"] = (0.0, 1.0, 0.0)
 
 
 class Scene:
@@ -66,35 +65,6 @@ def light(kind, pos=(0, 0, 0), direction=(0, 0, 0), cast=1):
     L = np.zeros(1, dtype=T.LIGHT)
     L["type"], L["cast_shadows"], L["position"], L["direction"] = kind, cast, pos, direction
     return L
-
-
-def shadow_rays(pos, nrm, hit, lights):
-    """The formula of include/mrt_hip.h in float32, one operation at a time.  Returns the rays of all pairs (light-major; the
-    reference's degenerate ray where a pair is not traced) and which pairs are traced."""
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):  # (the position of a miss is not used)
-        return _shadow_rays(pos, nrm, hit, lights)
-
-
-def _shadow_rays(pos, nrm, hit, lights):
-    org = pos + nrm * F(1e-3)
-    rays = np.zeros((len(lights), pos.shape[0]), dtype=T.RAY32)
-    traced = np.zeros(rays.shape, dtype=bool)
-    for l, L in enumerate(lights):
-        r = rays[l]
-        r["origin"] = org
-        if L["type"] == T.LIGHT_DIRECTIONAL:
-            r["direction"] = L["direction"].astype(F)
-            r["t_max"] = F(1000.0)
-            ok = np.ones(pos.shape[0], dtype=bool)
-        else:
-            to = L["position"].astype(F)[None, :] - org
-            dist = np.sqrt((to[:, 0] * to[:, 0] + to[:, 1] * to[:, 1]) + to[:, 2] * to[:, 2])
-            ok = ~(dist < F(1e-6))
-            r["direction"] = to / dist[:, None]
-            r["t_max"] = dist
-        traced[l] = hit & (L["cast_shadows"] != 0) & ok
-        r[~traced[l]] = DEGENERATE[0]
-    return rays.reshape(-1), traced.reshape(-1)
 
 
 def lights_for(sc, org_of_a_hit):
