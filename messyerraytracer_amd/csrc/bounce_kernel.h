@@ -35,37 +35,13 @@ __device__ __forceinline__ bool bounce_ray(const TraceParams &p, const BouncePar
 		face_normal(sf);
 		float metallic = s.metallic, roughness = s.roughness;
 		if (s.surface != nullptr) { metallic = s.surface[i * 2u]; roughness = s.surface[i * 2u + 1u]; }
-		const float m = fminf(fmaxf(metallic, 0.0f), 1.0f), ro = fminf(fmaxf(roughness, 0.04f), 1.0f);
-		float sp = m + ((1.0f - m) * (1.0f - ro)) * 0.5f;
-		sp = fmaxf(fminf(sp, 0.95f), 0.05f);
 		uint32_t state = (kPcgInc + ((uint32_t)i * 1009u + s.seed_add)) * kPcgMul + kPcgInc;
 		state = s.jump.a * state + s.jump.c;
-		const float u0 = pcg_float(state);
-		state = state * kPcgMul + kPcgInc;
-		const float u1 = pcg_float(state), u2 = pcg_float(state * kPcgMul + kPcgInc);
-		const bool specular = u0 < sp;
-		// the local direction before the basis: the half vector's (specular) or the ray's (diffuse)
-		float rr, z;
-		if (specular) {
-			const float a = ro * ro, a2 = a * a;
-			z = __builtin_sqrtf((1.0f - u1) / ((1.0f + (a2 - 1.0f) * u1) + 1e-7f));
-			rr = __builtin_sqrtf(fmaxf(0.0f, 1.0f - z * z));
-		} else {
-			rr = __builtin_sqrtf(u1); z = __builtin_sqrtf(fmaxf(0.0f, 1.0f - u1));
-		}
-		float vx, vy, vz;
-		onb_direction(sf, rr, z, u2, vx, vy, vz);
-		if (specular) { // v is the half vector: the view direction reflected about it
-			float wx = -sf.dx, wy = -sf.dy, wz = -sf.dz;
-			normalize3(wx, wy, wz);
-			const float k = 2.0f * fmaxf((wx * vx + wy * vy) + wz * vz, 0.0f);
-			vx = vx * k - wx; vy = vy * k - wy; vz = vz * k - wz;
-			normalize3(vx, vy, vz);
-		}
-		if ((sf.nx * vx + sf.ny * vy) + sf.nz * vz <= 0.0f) traced = false; // below the surface: an invalid sample, no ray
+		const BounceSample b = sample_bounce(sf, metallic, roughness, state);
+		if (b.ndl <= 0.0f) traced = false; // below the surface: an invalid sample, no ray
 		else {
-			lobe = specular ? MRT_LOBE_SPECULAR : MRT_LOBE_DIFFUSE;
-			r.dx = vx; r.dy = vy; r.dz = vz;
+			lobe = b.specular ? MRT_LOBE_SPECULAR : MRT_LOBE_DIFFUSE;
+			r.dx = b.vx; r.dy = b.vy; r.dz = b.vz;
 			r.ox = sf.px + sf.nx * 1e-3f; r.oy = sf.py + sf.ny * 1e-3f; r.oz = sf.pz + sf.nz * 1e-3f;
 			r.t_min = 1e-4f; r.t_max = s.t_max;
 		}

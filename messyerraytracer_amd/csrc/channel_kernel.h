@@ -1,7 +1,7 @@
 // channel_kernel.h — the renderer's channels from hit records (mrt_shade_channels / mrt_shade_grid_channels): the ten channels of
 // RayImage besides COLOR as ShadePass's per-channel functions write them (src/modules/graphics/shade_pass.h:337-395, :732-884), as
 // float planes, as the bytes of RayImage::to_image (ray_image.cpp:22-35), or both.  Included by shade_kernels.hip (inside namespace
-// mrt, after surface_tex_kernel.h, whose sampler it calls).
+// mrt, after surface_kernel.h, whose steps it calls).
 //
 // One thread per record, 256 per workgroup, no LDS, no scratch.  The record and its ray are read once for all selected channels (16-byte
 // loads, as the resolve's).  The selection is ChannelParams::mask and the plane pointers, kernel arguments: every test on them is a
@@ -9,10 +9,9 @@
 // NORMAL, ALBEDO, UV or FRESNEL is selected; the binding, the tangents and the normal map's texels only for NORMAL, the material's
 // first 16 bytes and the albedo texture's texels only for ALBEDO, each where the textured resolve would read them.  A float plane is
 // one 16-byte store per record (a wave writes 1 KB contiguously), a byte plane one 4-byte store (256 B per wave).
-// Plain float operations in the order include/mrt_hip.h states (nothing is contracted).  in_range, the row, uv, uv_ok, the smooth
-// normal, the binding and the perturbed normal are the textured resolve's own lines (surface_tex_steps.inc, included here and there:
-// the kernel's parameter block is called s and the UV lives in o3 for that reason); record_surface, normalize3 and sample_bilinear
-// are called.  With no texture set resident t is all zero: no binding applies, and the normal and the albedo are the plain resolve's.
+// Plain float operations in the order include/mrt_hip.h states (nothing is contracted).  The record's words, in_range, the row, uv, uv_ok, the smooth
+// normal, the binding, the perturbed normal and the albedo are the resolve's own steps, called (surface_kernel.h, surface_tex_kernel.h).
+// With no texture set resident t is all zero: no binding applies, and the normal and the albedo are the plain resolve's.
 #pragma once
 
 // one record of plane k: {r, g, b, 1}, and / or its bytes
@@ -37,16 +36,9 @@ __global__ __launch_bounds__(MRT_WG) void shade_channels_kernel(const TraceParam
 			if (s.mask & (1u << k)) store_channel(s, k, i, 0.0f, 0.0f, 0.0f);
 		return;
 	}
-	// the record's own words (the loads record_surface made, once more by name: the compiler keeps one of each)
-	float tt, u, v; uint32_t prim;
-	if (HOST) {
-		const float *h = reinterpret_cast<const float *>(s.records) + i * 11u;
-		tt = h[0]; u = h[7]; v = h[8]; prim = reinterpret_cast<const uint32_t *>(h)[9];
-	} else {
-		const float4 ra = (reinterpret_cast<const float4 *>(s.records) + i * 2u)[0];
-		tt = ra.x; prim = __float_as_uint(ra.y); u = ra.z; v = ra.w;
-	}
-	const float w = (1.0f - u) - v;
+	const RecordWords rec = record_words<HOST>(s.records, i);
+	const float tt = rec.t, u = rec.u, v = rec.v, w = (1.0f - u) - v;
+	const uint32_t prim = rec.prim;
 
 	if (s.mask & (1u << MRT_CHANNEL_DEPTH)) {
 		float x = 1.0f - tt * s.inv_depth_range;
@@ -80,22 +72,16 @@ __global__ __launch_bounds__(MRT_WG) void shade_channels_kernel(const TraceParam
 	if (!(s.mask & CHANNELS_ROW)) return;
 
 	// the channels that read the shade row
-	float2 o3 = {0.0f, 0.0f};                 // the UV
+	float uvx = 0.0f, uvy = 0.0f;
 	float nx = sf.nx, ny = sf.ny, nz = sf.nz; // the record's normal, then the smooth normal, then (NORMAL) the perturbed one
-#define MRT_TEX_STEP 1
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
-#define MRT_TEX_STEP 2
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
+	const ShadeRow row = load_shade_row(s, prim);
+	const bool uv_ok = shade_uv(s, row, u, v, w, uvx, uvy);
 	if (s.mask & (1u << MRT_CHANNEL_UV)) {
 		float r = 0.5f, g = 0.5f;
-		if (in_range && (s.present & SHADE_HAS_UVS)) { r = o3.x - floorf(o3.x); g = o3.y - floorf(o3.y); }
+		if (row.in_range && (s.present & SHADE_HAS_UVS)) { r = uvx - floorf(uvx); g = uvy - floorf(uvy); }
 		store_channel(s, MRT_CHANNEL_UV, i, r, g, 0.0f);
 	}
-#define MRT_TEX_STEP 3
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
+	smooth_normal(s, row, u, v, w, nx, ny, nz);
 	if (s.mask & (1u << MRT_CHANNEL_FRESNEL)) {
 		float q = (nx * -sf.dx + ny * -sf.dy) + nz * -sf.dz;
 		q = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
@@ -103,26 +89,14 @@ __global__ __launch_bounds__(MRT_WG) void shade_channels_kernel(const TraceParam
 	}
 	if (!(s.mask & CHANNELS_MATERIAL)) return;
 
-#define MRT_TEX_STEP 4
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
+	const Binding b = material_binding<true>(s, t, row);
 	if (s.mask & (1u << MRT_CHANNEL_NORMAL)) {
-#define MRT_TEX_STEP 5
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
+		perturb_normal(t, b.normal_tex, b.normal_scale, prim, uv_ok, u, v, w, uvx, uvy, nx, ny, nz);
 		store_channel(s, MRT_CHANNEL_NORMAL, i, nx * 0.5f + 0.5f, ny * 0.5f + 0.5f, nz * 0.5f + 0.5f);
 	}
 	if (s.mask & (1u << MRT_CHANNEL_ALBEDO)) {
-		float r = 0.75f, g = 0.75f, b = 0.75f;
-		if (material) { // the resolve's o1 = m0 and its product with the albedo texture's sample
-			const float4 m0 = (reinterpret_cast<const float4 *>(s.materials) + (size_t)id * 3u)[0]; // {albedo, metallic}
-			r = m0.x; g = m0.y; b = m0.z;
-			if (albedo_tex != MRT_NO_TEXTURE && uv_ok) {
-				float cr, cg, cb;
-				sample_bilinear(t, albedo_tex, o3.x, o3.y, cr, cg, cb);
-				r = r * cr; g = g * cg; b = b * cb;
-			}
-		}
-		store_channel(s, MRT_CHANNEL_ALBEDO, i, r, g, b);
+		float4 a = {0.75f, 0.75f, 0.75f, 0.0f};
+		if (b.material) a = material_albedo<true>(s, t, b, uv_ok, uvx, uvy);
+		store_channel(s, MRT_CHANNEL_ALBEDO, i, a.x, a.y, a.z);
 	}
 }

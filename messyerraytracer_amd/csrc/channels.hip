@@ -13,23 +13,13 @@ namespace {
 // Both channel passes after their own checks: p holds the incoming rays (or the grid) and the count.
 int shade(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, const mrt_channel_out *out, uint32_t flags)
 {
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (p.count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	BEGIN_PASS(ctx, p.count);
 	mrt::ChannelParams c;
 	std::memset(&c, 0, sizeof(c));
 	c.records = d_hits;
-	c.shade_rows = ctx->shade_rows.ptr; c.materials = ctx->shade_materials.ptr;
-	c.n_tris = ctx->shade_n_tris; c.n_materials = ctx->shade_n_materials; c.present = ctx->shade_present;
+	shade_data_params(ctx, c);
 	mrt::fill_channel_params(out, c);
-	mrt::TextureParams t;
-	std::memset(&t, 0, sizeof(t)); // (no texture set resident: no binding applies)
-	if (ctx->tex_resident) {
-		t.texels = ctx->tex_texels.ptr; t.table = ctx->tex_table.ptr; t.bindings = ctx->tex_bindings.ptr;
-		t.tangents = ctx->tex_n_tangent_tris ? ctx->tex_tangents.ptr : nullptr;
-		t.n_bindings = ctx->tex_n_bindings; t.n_tangent_tris = ctx->tex_n_tangent_tris;
-	}
-	HIP_TRY(ctx, mrt::launch_shade_channels(p, c, t, src, ctx->stream));
+	HIP_TRY(ctx, mrt::launch_shade_channels(p, c, texture_params(ctx), src, ctx->stream));
 	return finish_call(ctx, flags);
 }
 
@@ -63,9 +53,7 @@ int mrt_finish_color(mrt_ctx *ctx, const float *d_lit_rgba, uint64_t count, uint
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	if (const char *why = mrt::image_call_invalid(d_lit_rgba, d_rgba, d_rgba8, true, flags, tonemap_mode)) return fail(ctx, MRT_ERR_INVALID, why);
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	BEGIN_PASS(ctx, count);
 	HIP_TRY(ctx, mrt::launch_finish_color(d_lit_rgba, count, tonemap_mode, mrt::finish_white(), d_rgba, d_rgba8, ctx->stream));
 	return finish_call(ctx, flags);
 }
@@ -74,9 +62,7 @@ int mrt_image_to_rgba8(mrt_ctx *ctx, const float *d_rgba, uint64_t count, uint8_
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	if (const char *why = mrt::image_call_invalid(d_rgba, nullptr, d_rgba8, false, flags, 0u)) return fail(ctx, MRT_ERR_INVALID, why);
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	BEGIN_PASS(ctx, count);
 	HIP_TRY(ctx, mrt::launch_image_to_rgba8(d_rgba, count, d_rgba8, ctx->stream));
 	return finish_call(ctx, flags);
 }

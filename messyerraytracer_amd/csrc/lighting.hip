@@ -1,6 +1,6 @@
 // lighting.hip — direct light on resolved surfaces (include/mrt_hip.h: mrt_shadow_lights, mrt_light_surfaces,
 // mrt_light_grid_surfaces).  The checks of the light list and the environment and the kernel's copy of both are host/light_data.cpp;
-// the kernel is light_kernel.h, with a panorama resident light_panorama_kernel.h (shade_kernels.hip).
+// the kernels are light_kernel.h (shade_kernels.hip), one of them for a context with a panorama resident.
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
@@ -17,17 +17,13 @@ int light(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, const 
 	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a lighting call");
 	if (!d_hits || !d_rows || !out || !out->d_rgba) return fail(ctx, MRT_ERR_INVALID, "null hits / rows / output");
 	if (const char *why = mrt::light_list_invalid(lights, n_lights, env, p.count)) return fail(ctx, MRT_ERR_INVALID, why);
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (p.count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	BEGIN_PASS(ctx, p.count);
 	mrt::LightParams s;
 	std::memset(&s, 0, sizeof(s));
 	s.records = d_hits; s.rows = d_rows; s.mask = d_mask; s.out = out->d_rgba;
 	mrt::fill_light_params(lights, n_lights, env, s);
-	if (ctx->pano_resident && env) { // (without an environment no kernel reads the panorama)
-		const mrt::PanoramaParams pano = {ctx->pano_texels.ptr, ctx->pano_width, ctx->pano_height, ctx->pano_energy, 0u};
-		HIP_TRY(ctx, mrt::launch_light_panorama_surfaces(p, s, pano, src, ctx->stream));
-	} else HIP_TRY(ctx, mrt::launch_light_surfaces(p, s, src, ctx->stream));
+	const mrt::PanoramaParams pano = panorama_params(ctx); // (without an environment no kernel reads the panorama)
+	HIP_TRY(ctx, mrt::launch_light_surfaces(p, s, ctx->pano_resident && env ? &pano : nullptr, src, ctx->stream));
 	return finish_call(ctx, flags);
 }
 

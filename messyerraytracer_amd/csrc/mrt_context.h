@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"
 #include "launch_policy.h"
+#include "texture.h"
+#include "panorama.h"
 
 namespace mrt {
 // ---- kernels.hip: the walks
@@ -34,23 +36,17 @@ hipError_t launch_morton_keys(const void *rays, uint32_t in_fmt, uint64_t count,
 hipError_t launch_origin_dir_keys(const void *rays, uint32_t in_fmt, uint64_t count, const float lo[3], const float hi[3],
 		uint32_t *keys, uint32_t *index, hipStream_t stream);
 // ---- shade_kernels.hip: the passes over hit records
-// shading surfaces (surface_kernel.h): src = a SurfaceSrc; the rows of shade data given as device arrays (any of the three may be null)
-hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream);
-// the same with a texture set resident (surface_tex_kernel.h; texture.h)
-struct TextureParams;
-hipError_t launch_resolve_textured_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams &t, int src, hipStream_t stream);
-// direct light on resolved surfaces (light_kernel.h): src = a SurfaceSrc
+// src = a SurfaceSrc; t (texture.h) / pano (panorama.h) null: no texture set / no panorama resident
+// shading surfaces (surface_kernel.h); the rows of shade data given as device arrays (any of the three may be null)
+hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams *t, int src, hipStream_t stream);
+// direct light on resolved surfaces (light_kernel.h)
 struct LightParams;
-hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int src, hipStream_t stream);
-// the path tracer's per-pixel state (path_kernel.h): src = a SurfaceSrc; white = Hable's white value for tone-map mode 2
+hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams *pano, int src, hipStream_t stream);
+// the path tracer's per-pixel state (path_kernel.h); white = Hable's white value for tone-map mode 2
 struct PathParams;
 hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream);
-hipError_t launch_path_step(const TraceParams &p, const PathParams &s, int src, hipStream_t stream);
+hipError_t launch_path_step(const TraceParams &p, const PathParams &s, const PanoramaParams *pano, int src, hipStream_t stream);
 hipError_t launch_path_finish(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba, hipStream_t stream);
-// the lighting and the path step with a panorama resident (light_panorama_kernel.h, path_kernel.h; panorama.h)
-struct PanoramaParams;
-hipError_t launch_light_panorama_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams &pano, int src, hipStream_t stream);
-hipError_t launch_path_panorama_step(const TraceParams &p, const PathParams &s, const PanoramaParams &pano, int src, hipStream_t stream);
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream);
 // the renderer's channels (channel_kernel.h): src = a SurfaceSrc, t all zero with no texture set resident; the lit frame's last pass
 // and the 8-bit image (path_frame_kernel.h)
@@ -213,12 +209,43 @@ inline int record_params(const void *d_rays, uint64_t count, uint32_t flags, mrt
 	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
 	return host ? mrt::SURF_HOST : mrt::SURF_RAY32;
 }
+// The opening of such a call after its own checks (returns from the call like HIP_TRY): a pending dispatch is refused, no records is
+// MRT_OK, else the device is selected.
+#define BEGIN_PASS(ctx, count)                                                                             \
+	do {                                                                                                   \
+		if ((ctx)->pending) return fail((ctx), MRT_ERR_PENDING, "collect the pending dispatch first");     \
+		if ((count) == 0) return MRT_OK;                                                                   \
+		HIP_TRY((ctx), hipSetDevice((ctx)->device));                                                       \
+	} while (0)
 // ... and the end of such a call, its pass queued: back at once for MRT_FLAG_ASYNC, else when the stream is done
 inline int finish_call(mrt_ctx *ctx, uint32_t flags)
 {
 	if (flags & MRT_FLAG_ASYNC) return MRT_OK;
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return MRT_OK;
+}
+// What the context holds resident, as the kernels' parameter blocks take it: the shade data into the fields SurfaceParams and
+// ChannelParams share, the texture set (all zero with none resident: no binding applies) and the panorama.
+template <class S>
+inline void shade_data_params(const mrt_ctx *ctx, S &s)
+{
+	s.shade_rows = ctx->shade_rows.ptr; s.materials = ctx->shade_materials.ptr;
+	s.n_tris = ctx->shade_n_tris; s.n_materials = ctx->shade_n_materials; s.present = ctx->shade_present;
+}
+inline mrt::TextureParams texture_params(const mrt_ctx *ctx)
+{
+	mrt::TextureParams t;
+	std::memset(&t, 0, sizeof(t));
+	if (ctx->tex_resident) {
+		t.texels = ctx->tex_texels.ptr; t.table = ctx->tex_table.ptr; t.bindings = ctx->tex_bindings.ptr;
+		t.tangents = ctx->tex_n_tangent_tris ? ctx->tex_tangents.ptr : nullptr;
+		t.n_bindings = ctx->tex_n_bindings; t.n_tangent_tris = ctx->tex_n_tangent_tris;
+	}
+	return t;
+}
+inline mrt::PanoramaParams panorama_params(const mrt_ctx *ctx)
+{
+	return {ctx->pano_texels.ptr, ctx->pano_width, ctx->pano_height, ctx->pano_energy, 0u};
 }
 // schedule.hip: before the launch of a scheduled cast (fills p's schedule fields), after it (ev[4] recorded)
 int schedule_grid(mrt_ctx *ctx, const mrt::CastPlan &c, mrt::TraceParams &p);

@@ -1,6 +1,6 @@
 // panorama.h -- the resident equirectangular panorama of a context (mrt_upload_panorama): the descriptor's checks
 // (host/panorama_data.cpp), what the panorama kernels take besides their own blocks, and the sampler as include/mrt_hip.h states it --
-// atan2_def, acos_def, the direction's (u, v), the four taps and their weights -- one definition for the kernels (light_panorama_kernel.h,
+// atan2_def, acos_def, the direction's (u, v), the four taps and their weights -- one definition for the kernels (light_kernel.h,
 // path_kernel.h) and the host, so that both hold the same bits.  Host-only code may include this without HIP.
 #pragma once
 #include <cstdint>

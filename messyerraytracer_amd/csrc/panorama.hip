@@ -1,5 +1,5 @@
 // panorama.hip — the panorama a context holds (include/mrt_hip.h: mrt_upload_panorama, mrt_clear_panorama).  The descriptor's checks
-// and the scan of a host image are host/panorama_data.cpp; the kernels that sample it are light_panorama_kernel.h and path_kernel.h
+// and the scan of a host image are host/panorama_data.cpp; the kernels that sample it are light_kernel.h and path_kernel.h
 // (shade_kernels.hip), launched by lighting.hip and path.hip while a panorama is resident.
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"

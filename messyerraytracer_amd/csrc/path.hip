@@ -13,17 +13,13 @@ namespace {
 int step(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, const mrt_surface64 *d_rows, uint32_t pixel0,
 		const mrt_path_step_desc *desc, uint32_t flags)
 {
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (p.count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	BEGIN_PASS(ctx, p.count);
 	mrt::PathParams s;
 	std::memset(&s, 0, sizeof(s));
 	s.records = d_hits; s.rows = d_rows;
 	mrt::fill_path_params(desc, pixel0, s);
-	if (ctx->pano_resident) {
-		const mrt::PanoramaParams pano = {ctx->pano_texels.ptr, ctx->pano_width, ctx->pano_height, ctx->pano_energy, 0u};
-		HIP_TRY(ctx, mrt::launch_path_panorama_step(p, s, pano, src, ctx->stream));
-	} else HIP_TRY(ctx, mrt::launch_path_step(p, s, src, ctx->stream));
+	const mrt::PanoramaParams pano = panorama_params(ctx);
+	HIP_TRY(ctx, mrt::launch_path_step(p, s, ctx->pano_resident ? &pano : nullptr, src, ctx->stream));
 	return finish_call(ctx, flags);
 }
 
@@ -35,9 +31,7 @@ int mrt_path_init(mrt_ctx *ctx, mrt_path_state *d_state, uint64_t count, uint32_
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	if (const char *why = mrt::path_frame_invalid(d_state, nullptr, false, flags, 0u)) return fail(ctx, MRT_ERR_INVALID, why);
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	BEGIN_PASS(ctx, count);
 	HIP_TRY(ctx, mrt::launch_path_init(d_state, count, ctx->stream));
 	return finish_call(ctx, flags);
 }
@@ -68,9 +62,7 @@ int mrt_path_finish(mrt_ctx *ctx, const mrt_path_state *d_state, uint64_t count,
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	if (const char *why = mrt::path_frame_invalid(d_state, d_rgba, true, flags, tonemap_mode)) return fail(ctx, MRT_ERR_INVALID, why);
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	BEGIN_PASS(ctx, count);
 	HIP_TRY(ctx, mrt::launch_path_finish(d_state, count, tonemap_mode, mrt::hable_partial(11.2f), d_rgba, ctx->stream));
 	return finish_call(ctx, flags);
 }

@@ -25,36 +25,24 @@ namespace mrt {
 #include "surface_tex_kernel.h"
 #include "surface_kernel.h"
 #include "light_kernel.h"
-#include "light_panorama_kernel.h"
 #include "path_kernel.h"
 #include "channel_kernel.h"
 
-// ---- launch wrappers (called from surface.hip, lighting.hip and path.hip); src = a SurfaceSrc ------------------------------------
-hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, int src, hipStream_t stream)
+// ---- launch wrappers (called from surface.hip, lighting.hip and path.hip); src = a SurfaceSrc; t / pano null: none resident --------
+hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams *t, int src, hipStream_t stream)
 {
-	return launch_surface_pass([](auto SRC) { return resolve_surfaces_kernel<SRC>; }, src, p, stream, s);
+	if (t == nullptr) return launch_surface_pass([](auto SRC) { return resolve_surfaces_kernel<SRC>; }, src, p, stream, s);
+	return launch_surface_pass([](auto SRC) { return resolve_textured_surfaces_kernel<SRC>; }, src, p, stream, s, *t);
 }
-// the same with a texture set resident (surface_tex_kernel.h)
-hipError_t launch_resolve_textured_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams &t, int src, hipStream_t stream)
+hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams *pano, int src, hipStream_t stream)
 {
-	return launch_surface_pass([](auto SRC) { return resolve_textured_surfaces_kernel<SRC>; }, src, p, stream, s, t);
+	if (pano == nullptr) return launch_surface_pass([](auto SRC) { return light_surfaces_kernel<SRC>; }, src, p, stream, s);
+	return launch_surface_pass([](auto SRC) { return light_panorama_surfaces_kernel<SRC>; }, src, p, stream, s, *pano);
 }
-hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, int src, hipStream_t stream)
+hipError_t launch_path_step(const TraceParams &p, const PathParams &s, const PanoramaParams *pano, int src, hipStream_t stream)
 {
-	return launch_surface_pass([](auto SRC) { return light_surfaces_kernel<SRC>; }, src, p, stream, s);
-}
-hipError_t launch_path_step(const TraceParams &p, const PathParams &s, int src, hipStream_t stream)
-{
-	return launch_surface_pass([](auto SRC) { return path_step_kernel<SRC>; }, src, p, stream, s);
-}
-// the two with a panorama resident (light_panorama_kernel.h, path_kernel.h)
-hipError_t launch_light_panorama_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams &pano, int src, hipStream_t stream)
-{
-	return launch_surface_pass([](auto SRC) { return light_panorama_surfaces_kernel<SRC>; }, src, p, stream, s, pano);
-}
-hipError_t launch_path_panorama_step(const TraceParams &p, const PathParams &s, const PanoramaParams &pano, int src, hipStream_t stream)
-{
-	return launch_surface_pass([](auto SRC) { return path_step_panorama_kernel<SRC>; }, src, p, stream, s, pano);
+	if (pano == nullptr) return launch_surface_pass([](auto SRC) { return path_step_kernel<SRC>; }, src, p, stream, s);
+	return launch_surface_pass([](auto SRC) { return path_step_panorama_kernel<SRC>; }, src, p, stream, s, *pano);
 }
 hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream)
 {

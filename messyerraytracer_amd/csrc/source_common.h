@@ -177,3 +177,44 @@ __device__ __forceinline__ void onb_direction(const Surface &sf, float rr, float
 	vx = (tx * x + bx * y) + nx * z; vy = (ty * x + by * y) + ny * z; vz = (tz * x + bz * y) + nz * z;
 	normalize3(vx, vy, vz);
 }
+
+// PathTrace::sample_bounce's draw (bounce_kernel.h states the operations) at a surface whose normal faces the incoming ray: the lobe,
+// the direction v, n . v (<= 0: below the surface, an invalid sample), and what the renderer's weights need besides -- the specular
+// probability sp, a2 = roughness^4 and, of the specular lobe, the half vector h and vh (a diffuse sample: h = v, vh = 0).  state
+// enters as the generator's state of the first draw and leaves as that of the third: the next draw (the roulette's) follows from it.
+struct BounceSample { bool specular; float vx, vy, vz, ndl, hx, hy, hz, vh, sp, a2; };
+__device__ __forceinline__ BounceSample sample_bounce(const Surface &sf, float metallic, float roughness, uint32_t &state)
+{
+	BounceSample b;
+	const float m = fminf(fmaxf(metallic, 0.0f), 1.0f), ro = fminf(fmaxf(roughness, 0.04f), 1.0f);
+	b.sp = m + ((1.0f - m) * (1.0f - ro)) * 0.5f;
+	b.sp = fmaxf(fminf(b.sp, 0.95f), 0.05f);
+	const float u0 = pcg_float(state);
+	state = state * kPcgMul + kPcgInc;
+	const float u1 = pcg_float(state);
+	state = state * kPcgMul + kPcgInc;
+	const float u2 = pcg_float(state);
+	b.specular = u0 < b.sp;
+	const float a = ro * ro, a2 = a * a;
+	b.a2 = a2;
+	// the local direction before the basis: the half vector's (specular) or the ray's (diffuse)
+	float rr, z;
+	if (b.specular) {
+		z = __builtin_sqrtf((1.0f - u1) / ((1.0f + (a2 - 1.0f) * u1) + 1e-7f));
+		rr = __builtin_sqrtf(fmaxf(0.0f, 1.0f - z * z));
+	} else {
+		rr = __builtin_sqrtf(u1); z = __builtin_sqrtf(fmaxf(0.0f, 1.0f - u1));
+	}
+	onb_direction(sf, rr, z, u2, b.vx, b.vy, b.vz);
+	b.hx = b.vx; b.hy = b.vy; b.hz = b.vz; b.vh = 0.0f;
+	if (b.specular) { // v is the half vector: the view direction reflected about it
+		float wx = -sf.dx, wy = -sf.dy, wz = -sf.dz;
+		normalize3(wx, wy, wz);
+		b.vh = fmaxf((wx * b.vx + wy * b.vy) + wz * b.vz, 0.0f);
+		const float k = 2.0f * b.vh;
+		b.vx = b.vx * k - wx; b.vy = b.vy * k - wy; b.vz = b.vz * k - wz;
+		normalize3(b.vx, b.vy, b.vz);
+	}
+	b.ndl = (sf.nx * b.vx + sf.ny * b.vy) + sf.nz * b.vz;
+	return b;
+}

@@ -1,7 +1,7 @@
 // surface.hip — the shade data a context holds and the resolve of hit records to shading surfaces (include/mrt_hip.h:
 // mrt_upload_shade_data, mrt_clear_shade_data, mrt_resolve_surfaces, mrt_resolve_grid_surfaces).  The descriptor's checks and the
-// packing of host arrays are host/shade_data.cpp; the kernels are surface_kernel.h and, with a texture set resident (texture.hip),
-// surface_tex_kernel.h (shade_kernels.hip).
+// packing of host arrays are host/shade_data.cpp; the kernels are surface_kernel.h (shade_kernels.hip), one of them for a context
+// with a texture set resident (texture.hip).
 #include <cstring>
 #include <vector>
 #include <hip/hip_runtime.h>
@@ -24,23 +24,14 @@ int resolve(mrt_ctx *ctx, int src, mrt::TraceParams &p, const void *d_hits, cons
 	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, "unknown flag for a surface resolve");
 	if (!d_hits || !out) return fail(ctx, MRT_ERR_INVALID, "null hits / outputs");
 	if (!out->d_rows && !out->d_bounce_surface && !out->d_out_hits) return fail(ctx, MRT_ERR_INVALID, "no output asked for");
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
-	if (p.count == 0) return MRT_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	BEGIN_PASS(ctx, p.count);
 	mrt::SurfaceParams s;
 	std::memset(&s, 0, sizeof(s));
 	s.records = d_hits;
-	s.shade_rows = ctx->shade_rows.ptr; s.materials = ctx->shade_materials.ptr;
-	s.n_tris = ctx->shade_n_tris; s.n_materials = ctx->shade_n_materials; s.present = ctx->shade_present;
+	shade_data_params(ctx, s);
 	s.out_rows = out->d_rows; s.out_bounce = out->d_bounce_surface; s.out_hits = out->d_out_hits;
-	if (ctx->tex_resident) { // (texture.hip) extract_surface in full: surface_tex_kernel.h
-		mrt::TextureParams t;
-		std::memset(&t, 0, sizeof(t));
-		t.texels = ctx->tex_texels.ptr; t.table = ctx->tex_table.ptr; t.bindings = ctx->tex_bindings.ptr;
-		t.tangents = ctx->tex_n_tangent_tris ? ctx->tex_tangents.ptr : nullptr;
-		t.n_bindings = ctx->tex_n_bindings; t.n_tangent_tris = ctx->tex_n_tangent_tris;
-		HIP_TRY(ctx, mrt::launch_resolve_textured_surfaces(p, s, t, src, ctx->stream));
-	} else HIP_TRY(ctx, mrt::launch_resolve_surfaces(p, s, src, ctx->stream));
+	const mrt::TextureParams t = texture_params(ctx); // (texture.hip) resident: extract_surface in full
+	HIP_TRY(ctx, mrt::launch_resolve_surfaces(p, s, ctx->tex_resident ? &t : nullptr, src, ctx->stream));
 	return finish_call(ctx, flags);
 }
 

@@ -23,8 +23,9 @@
 //        P = (T * ts.x + B * ts.y) + N * ts.z; l2(P) < 1e-8f ? N : P / sqrt(l2)
 //        n_dot_v from the result, which is the row's normal and d_out_hits' normal
 //   albedo texture: bound, b.albedo_texture != none, uv_ok: albedo.c *= sample.c (no sRGB step)
-// (The row gather, uv, the smooth normal, the binding and the normal map's lines are surface_tex_steps.inc, which channel_kernel.h
-// includes too.)  Misses and ids out of range as surface_kernel.h; where no binding applies the outputs equal resolve_surfaces_kernel's byte for byte.
+// Here: the sampler and perturb_normal.  The kernel, resolve_textured_surfaces_kernel, is surface_kernel.h's resolve_record with TEX set,
+// next to the steps it shares with the plain resolve and the channels.  Misses and ids out of range as surface_kernel.h; where no
+// binding applies the outputs equal resolve_surfaces_kernel's byte for byte.
 // Every texel address lies inside the pool: u - floorf(u) of a finite u is in [0, 1], so fx is in [-0.5, width - 0.5] (width <= 16384:
 // exact), x0 in -1 .. width - 1, and after the wrap x0 and x1 are in 0 .. width - 1; texture indices and sizes were checked at upload.
 #pragma once
@@ -65,82 +66,32 @@ __device__ __forceinline__ void sample_bilinear(const TextureParams &t, uint32_t
 	b = lerp1(lerp1(b00, b10, sx), lerp1(b01, b11, sx), sy);
 }
 
-template <int SRC>
-__global__ __launch_bounds__(MRT_WG) void resolve_textured_surfaces_kernel(const TraceParams p, const SurfaceParams s, const TextureParams t)
+// perturb_normal where a binding's normal map applies: n is the smooth normal on entry; (u, v, w) the barycentrics, (uvx, uvy) the UV
+__device__ __forceinline__ void perturb_normal(const TextureParams &t, uint32_t normal_tex, float normal_scale, uint32_t prim, bool uv_ok,
+		float u, float v, float w, float uvx, float uvy, float &nx, float &ny, float &nz)
 {
-	constexpr bool HOST = SRC == SURF_HOST;
-	const uint64_t i = (uint64_t)blockIdx.x * MRT_WG + threadIdx.x;
-	if (i >= p.count) return;
-	Surface sf = {};
-	const bool hit = record_surface<HOST, SRC == SURF_GRID>(p, s.records, i, sf);
-	const float *h = reinterpret_cast<const float *>(s.records) + i * 11u;                   // HOST
-	const float4 *q = reinterpret_cast<const float4 *>(s.records) + i * 2u;                  // otherwise
-	float4 ra = {}, rb = {};
-	float u, v; uint32_t prim;
-	if (HOST) { u = h[7]; v = h[8]; prim = reinterpret_cast<const uint32_t *>(h)[9]; }
-	else { ra = q[0]; rb = q[1]; prim = __float_as_uint(ra.y); u = ra.z; v = ra.w; }
-
-	float4 o0 = {0.0f, 0.0f, 0.0f, 0.0f}, o1 = o0, o2 = o0, o3 = {0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)};
-	float metallic = 0.0f, roughness = 0.5f; // (a miss's bounce pair)
-	float nx = sf.nx, ny = sf.ny, nz = sf.nz;
-	if (hit) {
-		// the row, uv, the smooth normal, the binding and perturb_normal: surface_tex_steps.inc, shared with channel_kernel.h
-#define MRT_TEX_STEP 1
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
-		const float w = (1.0f - u) - v;
-#define MRT_TEX_STEP 2
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
-#define MRT_TEX_STEP 3
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
-#define MRT_TEX_STEP 4
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
-#define MRT_TEX_STEP 5
-#include "surface_tex_steps.inc"
-#undef MRT_TEX_STEP
-		float vx = -sf.dx, vy = -sf.dy, vz = -sf.dz;
-		normalize3(vx, vy, vz);
-		const float ndv = (nx * vx + ny * vy) + nz * vz;
-		o0.x = nx; o0.y = ny; o0.z = nz; o0.w = ndv < 0.001f ? 0.001f : ndv;
-		o1.x = 0.75f; o1.y = 0.75f; o1.z = 0.75f; o1.w = 0.0f;
-		o2.w = 0.5f; o3.z = 0.5f;
-		if (material) {
-			const float4 *m = reinterpret_cast<const float4 *>(s.materials) + (size_t)id * 3u;
-			const float4 m0 = m[0], m1 = m[1], m2 = m[2]; // {albedo, metallic | roughness, specular, emission rg | emission b, energy, flags, -}
-			o1 = m0;
-			o2.w = m1.x < 0.04f ? 0.04f : m1.x;
-			o3.z = m1.y;
-			if (albedo_tex != MRT_NO_TEXTURE && uv_ok) {
-				float cr, cg, cb;
-				sample_bilinear(t, albedo_tex, o3.x, o3.y, cr, cg, cb);
-				o1.x = o1.x * cr; o1.y = o1.y * cg; o1.z = o1.z * cb;
-			}
-			if (m2.y > 0.0f) { o2.x = m1.z * m2.y; o2.y = m1.w * m2.y; o2.z = m2.x * m2.y; }
-			o3.w = __uint_as_float(id);
-		}
-		metallic = o1.w; roughness = o2.w;
-	}
-	if (s.out_rows != nullptr) {
-		float4 *o = reinterpret_cast<float4 *>(s.out_rows) + i * 4u;
-		o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3;
-	}
-	if (s.out_bounce != nullptr) reinterpret_cast<float2 *>(s.out_bounce)[i] = make_float2(metallic, roughness);
-	if (s.out_hits != nullptr) {
-		if (HOST) {
-			float *d = reinterpret_cast<float *>(s.out_hits) + i * 11u;
-			float r[11];
-#pragma unroll
-			for (int k = 0; k < 11; k++) r[k] = h[k];
-			if (hit) { r[4] = nx; r[5] = ny; r[6] = nz; }
-#pragma unroll
-			for (int k = 0; k < 11; k++) d[k] = r[k];
-		} else {
-			float4 *d = reinterpret_cast<float4 *>(s.out_hits) + i * 2u;
-			if (hit) { rb.x = nx; rb.y = ny; rb.z = nz; }
-			d[0] = ra; d[1] = rb;
-		}
-	}
+	if (!(normal_tex != MRT_NO_TEXTURE && t.tangents != nullptr && prim < t.n_tangent_tris && uv_ok)) return;
+	const float4 *tr = reinterpret_cast<const float4 *>(t.tangents) + (size_t)prim * 3u;
+	const float4 a0 = tr[0], a1 = tr[1], a2 = tr[2]; // {t0 xyz, t1.x | t1 yz, t2 xy | t2.z, sign0, sign1, sign2}
+	if (!(a2.y != 0.0f || a2.z != 0.0f || a2.w != 0.0f)) return;
+	float tx = (a0.x * w + a0.w * u) + a1.z * v;
+	float ty = (a0.y * w + a1.x * u) + a1.w * v;
+	float tz = (a0.z * w + a1.y * u) + a2.x * v;
+	const float tl2 = (tx * tx + ty * ty) + tz * tz;
+	if (tl2 < 1e-8f) { tx = 1.0f; ty = 0.0f; tz = 0.0f; }
+	else { const float l = sqrtf(tl2); tx = tx / l; ty = ty / l; tz = tz / l; }
+	const float bsign = ((a2.y * w + a2.z * u) + a2.w * v) >= 0.0f ? 1.0f : -1.0f;
+	const float k = (nx * tx + ny * ty) + nz * tz;
+	tx = tx - nx * k; ty = ty - ny * k; tz = tz - nz * k;
+	normalize3(tx, ty, tz);
+	const float bx = (ny * tz - nz * ty) * bsign, by = (nz * tx - nx * tz) * bsign, bz = (nx * ty - ny * tx) * bsign;
+	float cr, cg, cb;
+	sample_bilinear(t, normal_tex, uvx, uvy, cr, cg, cb);
+	float sx = cr * 2.0f - 1.0f, sy = cg * 2.0f - 1.0f;
+	const float sz = cb * 2.0f - 1.0f;
+	sx = sx * normal_scale; sy = sy * normal_scale;
+	const float px = (tx * sx + bx * sy) + nx * sz, py = (ty * sx + by * sy) + ny * sz, pz = (tz * sx + bz * sy) + nz * sz;
+	const float pl2 = (px * px + py * py) + pz * pz;
+	if (!(pl2 < 1e-8f)) { const float l = sqrtf(pl2); nx = px / l; ny = py / l; nz = pz / l; }
 }
+

@@ -1,5 +1,5 @@
 // texture.h -- the resident texture set of a context (mrt_upload_textures): the descriptor's checks, the layout of the pooled texel
-// buffer and its descriptor table (host/texture_data.cpp), and what the textured resolve takes (surface_tex_kernel.h).  Host-only code
+// buffer and its descriptor table (host/texture_data.cpp), and what the textured resolve takes (surface_kernel.h).  Host-only code
 // may include this without HIP.
 #pragma once
 #include <cstdint>

@@ -1,5 +1,5 @@
 // texture.hip — the texture set a context holds (include/mrt_hip.h: mrt_upload_textures, mrt_clear_textures).  The descriptor's
-// checks and the pool's layout are host/texture_data.cpp; the resolve that samples the set is surface_tex_kernel.h (shade_kernels.hip),
+// checks and the pool's layout are host/texture_data.cpp; the resolve that samples the set is surface_kernel.h with surface_tex_kernel.h (shade_kernels.hip),
 // launched by surface.hip while a set is resident.
 #include <vector>
 #include <hip/hip_runtime.h>
