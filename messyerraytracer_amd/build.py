@@ -50,6 +50,9 @@ DRIVERS = {
     "lane_map_test": (["host/lane_map_test.cpp"], LANE + ["-O2"], False),  # lane_map.h
     "lane_map_test_san": (["host/lane_map_test.cpp"], LANE + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
                                                               "-fno-sanitize-recover=undefined"], False),
+    "lane_map_fast_test": (["host/lane_map_fast_test.cpp"], LANE + ["-O2"], False),  # lane_map.h: the short map of whole-tile pairs
+    "lane_map_fast_test_san": (["host/lane_map_fast_test.cpp"], LANE + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                                                                        "-fno-sanitize-recover=undefined"], False),
 }
 
 
@@ -184,6 +187,11 @@ def build_build_rules_test(force: bool = False, sanitize: bool = False) -> str:
 def build_lane_map_test(force: bool = False, sanitize: bool = False) -> str:
     """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
     return build_driver("lane_map_test_san" if sanitize else "lane_map_test", force)
+
+
+def build_lane_map_fast_test(force: bool = False, sanitize: bool = False) -> str:
+    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
+    return build_driver("lane_map_fast_test_san" if sanitize else "lane_map_fast_test", force)
 
 
 if __name__ == "__main__":

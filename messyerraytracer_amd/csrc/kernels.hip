@@ -100,6 +100,17 @@ hipError_t launch_trace(const TraceParams &p_in, bool any_hit, bool count, hipSt
 	TraceParams p = p_in;
 	p.tile_group = l.tile_group;
 	const TraceVariant &v = l.v;
+	p.rows_fast = kFastNo;
+	if (v.kernel == TraceKernel::PACKET_ROWS) { // whole-tile pairs take the short map (lane_map.h)
+		FastLaunch f;
+		f.packets = v.packets; f.counting = v.count; f.lane_map = p.lane_map;
+		f.k = p.tile_w_log2; f.order = p.tile_order; f.quarter_all = p.quarter_all;
+		f.sched = p.tile_sched != nullptr; f.perm = p.perm != nullptr; f.tile_cost = p.tile_cost != nullptr;
+		f.ray32_in = p.in_fmt == IN_RAY32; f.hit32_out = p.out_fmt == OUT_HIT32;
+		f.auto_grid = p.auto_grid != nullptr;
+		f.skip = p.skip_flag == nullptr ? 0 : (p.auto_grid != nullptr && p.skip_flag == p.auto_grid + 3 ? 1 : 2);
+		p.rows_fast = fast_launch(f);
+	}
 	const Bool a{v.any_hit}, c{v.count};
 	const auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(l.blocks), dim3(l.threads), l.lds, stream, p); };
 	switch (v.kernel) {

@@ -175,6 +175,58 @@ MRT_LM_HD bool tile_lane(const TileGrid &g, const WaveTile &w, uint32_t l, uint6
 	return true;
 }
 
+// ---- whole-tile pairs: the launches whose map needs none of the above -------------------------------------------------------------
+// A wave of two groups (the 128-ray walk) that casts whole 8x8 tiles in row-major pairs, reads 32-byte rays and writes 32-byte
+// records takes a short form of the map (packet_rows_kernel.h): one 32-bit division per wave, two shifts and two adds per lane, no
+// validity flags (every lane has a ray), group B = A's right-hand neighbour.  The test is in two parts.  fast_launch: what the host
+// knows of a launch (launch_trace asks it once and leaves the answer in TraceParams::rows_fast); fast_grid: the grid's size, which
+// a MAP_AUTO launch learns on the device.  csrc/host/lane_map_fast_test.cpp holds both to a listed expectation and the short map to
+// wave_tile + wave_tile_next + tile_lane.
+struct FastLaunch {
+	uint32_t packets;            // groups per wave
+	bool counting;               // a counting build
+	uint32_t lane_map;           // LaneMap (mrt_internal.h): 0 linear, 1 tiled, 2 the grid is found on the device
+	uint32_t k, order, quarter_all;
+	bool sched, perm, tile_cost; // the launch has a tile schedule / a sort permutation / tile-cost notes (the pointer is set)
+	bool ray32_in, hit32_out;    // 32-byte rays in, 32-byte records out
+	bool auto_grid;              // the device's grid words are there (the pointer is set)
+	int skip;                    // the launch's skip word: 0 none, 1 word 3 of the grid words, 2 anywhere else
+};
+// 0: the general map.  Else how the kernel gets the grid and the skip word: 1 = the launch's own grid, no skip word; 2 = the device's
+// four words {width, rows, tiles_x, skip word}; 3 = the device's first three, no skip word.
+constexpr uint32_t kFastNo = 0u, kFastOwnGrid = 1u, kFastAutoSkip = 2u, kFastAuto = 3u;
+MRT_LM_HD uint32_t fast_launch(const FastLaunch &f)
+{
+	if (f.packets != 2u || f.counting || f.k != 3u || f.order != 0u || f.quarter_all != 0u) return kFastNo;
+	if (f.sched || f.perm || f.tile_cost || !f.ray32_in || !f.hit32_out) return kFastNo;
+	if (f.lane_map == 1u) return f.skip == 0 ? kFastOwnGrid : kFastNo;
+	if (f.lane_map == 2u && f.auto_grid) return f.skip == 1 ? kFastAutoSkip : (f.skip == 0 ? kFastAuto : kFastNo);
+	return kFastNo;
+}
+// The grid's part: whole tiles in pairs on every tile row (no clipped tile, no wave without a group B, no pair across two tile rows),
+// tiles_x what the width says, and rays -- so tiles too -- below 2^32.  width 0 = no grid was found.
+MRT_LM_HD bool fast_grid(uint32_t grid_w, uint32_t rows, uint32_t tiles_x)
+{
+	return grid_w != 0u && rows != 0u && (grid_w & 15u) == 0u && (rows & 7u) == 0u && tiles_x == grid_w >> 3 && (((uint64_t)grid_w * rows) >> 32) == 0u;
+}
+// Wave `pair` of such a launch (its groups are 2 pair and 2 pair + 1): group A's tile; false = past the grid's last pair.
+MRT_LM_HD bool fast_wave_tile(uint32_t grid_w, uint32_t rows, uint32_t pair, uint32_t &tx, uint32_t &ty)
+{
+	const uint32_t pairs_x = grid_w >> 4;
+	ty = pair / pairs_x;
+	tx = (pair - ty * pairs_x) << 1;
+	return ty < rows >> 3;
+}
+// What such a wave keeps of its tiles: the ray of tile A's first pixel ...
+MRT_LM_HD uint32_t fast_tile_ray(uint32_t grid_w, uint32_t tx, uint32_t ty) { return (ty << 3) * grid_w + (tx << 3); }
+// ... from which lane l's ray in group A follows; in group B it is 8 more.
+MRT_LM_HD uint32_t fast_lane_ray(uint32_t grid_w, uint32_t tile_ray, uint32_t l) { return tile_ray + (l >> 3) * grid_w + (l & 7u); }
+// Lane l's pixel in group A (rays made from a camera need it); in group B px is 8 more.
+MRT_LM_HD void fast_lane_pixel(uint32_t tx, uint32_t ty, uint32_t l, uint32_t &px, uint32_t &py)
+{
+	px = (tx << 3) + (l & 7u); py = (ty << 3) + (l >> 3);
+}
+
 // The linear map: lane l of group `group` takes entry group * 64 + l, or with sparse_lanes = n (rays in lanes 0 .. n - 1 only)
 // entry group * n + l.  false = no entry.
 MRT_LM_HD bool linear_lane(uint64_t group, uint32_t l, uint32_t sparse_lanes, uint64_t count, uint64_t &entry)

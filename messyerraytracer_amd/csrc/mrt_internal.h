@@ -161,6 +161,7 @@ struct TraceParams {
 	uint32_t n_nodes;          // rows in nodes (the hand-written node loop addresses them with a 32-bit byte offset)
 	uint32_t count_mode;       // COUNT variants: mrt_options.count_visits (1: visit counters, 2: only the sampled clock of the rows kernel)
 	uint32_t extra_lds;        // experiments: dynamic LDS bytes added per workgroup of the packet kernels (occupancy sweeps)
+	uint32_t rows_fast;        // trace_packet_rows_kernel<.., 2>: lane_map.h fast_launch of this launch (set by launch_trace)
 	mrt_camera cam;
 };
 

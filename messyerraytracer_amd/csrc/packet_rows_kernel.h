@@ -385,6 +385,26 @@ struct PacketRegs {
 	"global_load_dword v60, v55, %[rows]\n" /* v60 is never read (vmcnt drained at the very end) */
 #endif
 
+// The push of the shared walk: the far child's two masks (s[50:51], s[58:59]) and its ref (s53) go to v50..v54 for the two
+// ds_writes.  gfx950 moves a scalar pair in one v_mov_b64: three vector instructions where five single moves stood, the same bits
+// stored (-DMRT_ROWS_PUSH64=0: the single moves, for A/B builds).
+#ifndef MRT_ROWS_PUSH64
+#define MRT_ROWS_PUSH64 1
+#endif
+#if MRT_ROWS_PUSH64
+#define MRT_ROWSW_PUSH_MOVES                                                                                          \
+	"v_mov_b64 v[50:51], s[50:51]\n"                                                                                \
+	"v_mov_b64 v[52:53], s[58:59]\n"                                                                                \
+	"v_mov_b32 v54, s53\n"
+#else
+#define MRT_ROWSW_PUSH_MOVES                                                                                          \
+	"v_mov_b32 v50, s50\n"                                                                                          \
+	"v_mov_b32 v51, s51\n"                                                                                          \
+	"v_mov_b32 v52, s58\n"                                                                                          \
+	"v_mov_b32 v53, s59\n"                                                                                          \
+	"v_mov_b32 v54, s53\n"
+#endif
+
 // In: cur (group A's operand) = a row to visit, the groups' own masks.  Out: cur = 0x7FFFFFFF.
 // Stack entries are 32 bytes: {group A's mask, group B's mask, ref, -}; the sentinel entry has ref 0x7FFFFFFF.
 #define MRT_ROWS_LOOPW(CNT_N, CNT_T, CNT_P, ANYA, ANYB, ANYDONE, BX, BY, BZ)                                                 \
@@ -414,11 +434,7 @@ struct PacketRegs {
 		"s_cselect_b64 s[58:59], s[42:43], s[40:41]\n"                                                              \
 		"s_cselect_b64 s[60:61], s[36:37], s[38:39]\n"        /* the near child's */                                \
 		"s_cselect_b64 s[62:63], s[40:41], s[42:43]\n"                                                              \
-		"v_mov_b32 v50, s50\n"                                                                                      \
-		"v_mov_b32 v51, s51\n"                                                                                      \
-		"v_mov_b32 v52, s58\n"                                                                                      \
-		"v_mov_b32 v53, s59\n"                                                                                      \
-		"v_mov_b32 v54, s53\n"                                                                                      \
+		MRT_ROWSW_PUSH_MOVES                                                                                        \
 		"ds_write_b128 %[spA], v[50:53]\n"                                                                          \
 		"ds_write_b32 %[spA], v54 offset:16\n"                                                                      \
 		"v_add_u32 %[spA], 32, %[spA]\n"                                                                            \
@@ -603,11 +619,7 @@ struct PacketRegs {
 		"s_cselect_b64 s[60:61], s[36:37], s[38:39]\n"        /* the near child's */                                \
 		"s_cselect_b64 s[62:63], s[40:41], s[42:43]\n"                                                              \
 		"s_cselect_b64 s[66:67], 0, -1\n"                     /* the near child's vector copy: v60 (left) / v61 */  \
-		"v_mov_b32 v50, s50\n"                                                                                      \
-		"v_mov_b32 v51, s51\n"                                                                                      \
-		"v_mov_b32 v52, s58\n"                                                                                      \
-		"v_mov_b32 v53, s59\n"                                                                                      \
-		"v_mov_b32 v54, s53\n"                                                                                      \
+		MRT_ROWSW_PUSH_MOVES                                                                                        \
 		"ds_write_b128 %[spA], v[50:53]\n"                                                                          \
 		"ds_write_b32 %[spA], v54 offset:16\n"                                                                      \
 		"v_add_u32 %[spA], 32, %[spA]\n"                                                                            \
@@ -693,6 +705,9 @@ __device__ __forceinline__ void rows_walk_one(const float4 *rows, uint32_t qmask
 {
 	const float eps = 1e-8f, vneg = -FLT_MAX;
 	uint32_t ev = 0u;
+	// (the counters go into the block as scalars: constants where nothing is counted, else told to be uniform as on the way out)
+	if (!COUNT) { cnt_n = 0u; cnt_t = 0u; cnt_w = 0u; sp_max = 0u; }
+	else { cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t); cnt_w = __builtin_amdgcn_readfirstlane(cnt_w); sp_max = __builtin_amdgcn_readfirstlane(sp_max); }
 #define MRT_W1(O, BX, BY, BZ)                                                                                         \
 	if (OCT == O) {                                                                                                 \
 		if (COUNT) { if (ANY_HIT) MRT_ROWS_LOOP1(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWS_T_PRE, MRT_ROWS_T_POST, MRT_ROWS_ANYHIT("A", "4"), BX, BY, BZ); \
@@ -711,6 +726,8 @@ template <int OCT, bool ANY_HIT, bool COUNT>
 __device__ __forceinline__ void rows_walk_wide(const float4 *rows, uint32_t qmask, PacketRegs &a, PacketRegs &b, uint32_t &cnt_n, uint32_t &cnt_t, uint32_t &sp_max)
 {
 	const float eps = 1e-8f, vneg = -FLT_MAX;
+	if (!COUNT) { cnt_n = 0u; cnt_t = 0u; sp_max = 0u; }
+	else { cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t); sp_max = __builtin_amdgcn_readfirstlane(sp_max); }
 #define MRT_WW(O, BX, BY, BZ)                                                                                         \
 	if (OCT == O) {                                                                                                 \
 		if (COUNT) { if (ANY_HIT) MRT_ROWS_LOOPW(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE, BX, BY, BZ); \
@@ -729,6 +746,8 @@ template <int OCT, bool ANY_HIT, bool COUNT>
 __device__ __forceinline__ void rows_walk_cull(const float4 *rows, uint32_t qmask, PacketRegs &a, PacketRegs &b, const CullRegs &cull, uint32_t &cnt_n, uint32_t &cnt_t, uint32_t &sp_max)
 {
 	const float eps = 1e-8f, vneg = -FLT_MAX;
+	if (!COUNT) { cnt_n = 0u; cnt_t = 0u; sp_max = 0u; }
+	else { cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t); sp_max = __builtin_amdgcn_readfirstlane(sp_max); }
 #define MRT_WC(O, BX, BY, BZ)                                                                                         \
 	if (OCT == O) {                                                                                                 \
 		if (COUNT) { if (ANY_HIT) MRT_ROWS_LOOPC(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE, BX, BY, BZ); \
@@ -823,11 +842,11 @@ __device__ __forceinline__ void rows_init(PacketRegs &s, const RayRegs &r, bool 
 }
 
 // wave-uniform octant of a packet's reciprocal directions over the lanes that take part (8 = mixed)
-__device__ __forceinline__ int rows_octant(const RayRegs &r, bool part, unsigned long long &part_mask)
+// (s.ix = safe_inv(r.dx), ..., as rows_init left them: the reciprocals are not worked out a second time)
+__device__ __forceinline__ int rows_octant(const PacketRegs &s, bool part, unsigned long long &part_mask)
 {
 	part_mask = __ballot(part);
-	const unsigned long long sx = __ballot(part && safe_inv(r.dx) < 0.0f), sy = __ballot(part && safe_inv(r.dy) < 0.0f),
-			sz = __ballot(part && safe_inv(r.dz) < 0.0f);
+	const unsigned long long sx = __ballot(part && s.ix < 0.0f), sy = __ballot(part && s.iy < 0.0f), sz = __ballot(part && s.iz < 0.0f);
 	const bool uniform = (sx == 0ull || sx == part_mask) && (sy == 0ull || sy == part_mask) && (sz == 0ull || sz == part_mask);
 	return uniform ? ((sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0)) : 8;
 }
@@ -860,6 +879,71 @@ __device__ __forceinline__ void finish_row_ray(const TraceParams &p, const float
 	store_hit<STREAM>(p, ray_idx, r, best_t, prim, best_u, best_v, nx, ny, nz, layers, best_slot);
 }
 
+// ---- whole-tile pairs (lane_map.h fast_launch): 32-byte rays in, 32-byte records out, nothing to decide per launch -----------
+template <bool STREAM>
+__device__ __forceinline__ void load_ray32(const float4 *q, RayRegs &r)
+{
+	const float4 a = STREAM ? stream_load4(q) : q[0], b = STREAM ? stream_load4(q + 1) : q[1];
+	r.ox = a.x; r.oy = a.y; r.oz = a.z; r.t_max = a.w;
+	r.dx = b.x; r.dy = b.y; r.dz = b.z; r.t_min = b.w;
+}
+// the record of finish_row_ray + store_hit for OUT_HIT32
+__device__ __forceinline__ void row_record32(const float4 *rows, float best_t, float best_u, float best_v, uint32_t best_row, uint32_t best_id, float4 &a, float4 &b)
+{
+	a.x = best_t; a.y = __int_as_float(-1); a.z = best_u; a.w = best_v;
+	b.x = 0.0f; b.y = 0.0f; b.z = 0.0f; b.w = __uint_as_float(0u);
+	if (best_row != 0xFFFFFFFFu) {
+		const float4 *row = rows + (size_t)best_row * 4u;
+		a.y = __uint_as_float(best_id);
+		const float4 nn = row[3];
+		b.x = nn.x; b.y = nn.y; b.z = nn.z;
+		b.w = reinterpret_cast<const float *>(row)[7];
+	}
+}
+struct RowsWave;
+template <bool STREAM> __device__ __forceinline__ void rows_fast_records(const RowsWave &w, const PacketRegs &A, const PacketRegs &B);
+// The kernel's arguments (its first one lies at the start of the argument block) through an address the compiler cannot tie to its
+// first reading of them: what is read through it is read here and now.  Holds only while TraceParams is the kernel's FIRST argument
+// (offset 0 of the argument block): trace_packet_rows_kernel takes it alone; an argument put in front of it breaks this.
+__device__ __forceinline__ const __attribute__((address_space(4))) TraceParams *rows_args_again()
+{
+	const __attribute__((address_space(4))) TraceParams *q =
+			(const __attribute__((address_space(4))) TraceParams *)__builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(q));
+	return q;
+}
+
+// the wave-uniform words a wave keeps across its walks, for its records: whole-tile pairs the last two, else the others
+struct RowsWave {
+	uint32_t block_s, wave_s, tile_ax, tile_ay, tile_bx, tile_by, tile_code;
+	uint32_t fast_ray, fast_w; // whole-tile pairs: the ray of tile A's first pixel, the row width
+};
+typedef __attribute__((address_space(3))) uint32_t *RowsStack; // a packet's stack in the LDS
+// whole-tile pairs read the device's four grid words {width, rows, tiles_x, skip word} as one 16-byte load
+static_assert((kAutoGridOff * sizeof(unsigned long long)) % 16u == 0u && (kDetectScratchOff - kAutoGridOff) * sizeof(unsigned long long) >= 16u,
+		"the grid words of detect_grid_kernel: 16-byte aligned, four of them");
+// whole-tile pairs: both records, from the two scalars, the lane, and the kernel's arguments read again
+template <bool STREAM>
+__device__ __forceinline__ void rows_fast_records(const RowsWave &w, const PacketRegs &A, const PacketRegs &B)
+{
+	const TraceParams &p2 = *(const TraceParams *)rows_args_again();
+	const uint32_t lane2 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+	float4 *out = reinterpret_cast<float4 *>(p2.hits) + (size_t)fast_lane_ray(w.fast_w, w.fast_ray, lane2) * 2u;
+	const float4 *rows2 = reinterpret_cast<const float4 *>(p2.row_array);
+	// both records first, then the four stores in a row: a store between the two rows' loads made the wave wait for its own stores
+	// to come back (loads and stores share one counter), which a cast of short walks pays for with its bandwidth
+	float4 aa, ab, ba, bb;
+	row_record32(rows2, A.bt, A.bu, A.bv, A.bs, A.bi, aa, ab);
+	row_record32(rows2, B.bt, B.bu, B.bv, B.bs, B.bi, ba, bb);
+	if (STREAM) { stream_store4(out, aa); stream_store4(out + 1, ab); stream_store4(out + 16, ba); stream_store4(out + 17, bb); }
+	else { out[0] = aa; out[1] = ab; out[16] = ba; out[17] = bb; }
+}
+// The second half of trace_packet_rows_kernel: the walks of the wave's packets and their records (defined below the kernel).
+// FAST: whole-tile pairs, of which it does the paired walk alone; false = the wave's packets do not share an octant, nothing is done.
+template <bool ANY_HIT, bool COUNT, int PACKETS, int WG, bool CULL, bool FAST>
+__device__ __forceinline__ bool rows_walks_and_records(const TraceParams &p, RowsStack lds_a, RowsStack lds_b, uint32_t lane,
+		RayRegs &ra, RayRegs &rb, bool valid_a, bool valid_b, const RowsWave &w);
+
 #ifndef MRT_ROWS_WPE
 #define MRT_ROWS_WPE 8
 #endif
@@ -873,7 +957,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS_WPE
 {
 	// per wave and packet: 16-byte stack entries {ref, -, lane mask}; entry 0 holds the sentinel
 	__shared__ __attribute__((aligned(16))) uint32_t wave_stack[WG / MRT_WAVE][PACKETS][(MRT_PACKET_STACK + 1) * 4];
-	if (skip_launch(p)) return;
 	// Rays are read and records written once per launch: in the one-wave workgroups api.hip picks for scenes whose rows the caches can
 	// hold (up to 256 MB) they stream past those rows (non-temporal: C3 1.89 -> 1.73 ms); beyond, the rows fit no cache either way (C5
 	// measured the same with and without), and the 256-thread culling form spilled registers with the streaming loads.
@@ -885,55 +968,101 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS_WPE
 	}
 	const uint32_t wave = threadIdx.x / MRT_WAVE, lane = threadIdx.x & (MRT_WAVE - 1);
 	const uint32_t wave_s = __builtin_amdgcn_readfirstlane(wave), block_s = block; // (scalars: for the epilogue)
-	const uint64_t group_a = ((uint64_t)block_s * (WG / MRT_WAVE) + wave_s) * PACKETS; // the wave's first group of 64 rays
-	// The wave's tiles, once, on the scalar unit (lane_map.h): the second group's follows from the first's.  They stay in scalar
-	// registers across the walk, for the epilogue: tile_a / tile_b = column | row of a tile, tile_code = the two pieces.
-	TileGrid tg;
-	const bool tiled = tile_grid(p, tg);
-	WaveTile ta = {0u, 0u, kPieceNone}, tb = ta;
-	if (tiled) {
-		ta = wave_tile(tg, group_a);
-		if (PACKETS == 2) tb = wave_tile_next(tg, ta, group_a);
-	}
-	const uint32_t tile_ax = __builtin_amdgcn_readfirstlane(ta.tx), tile_ay = __builtin_amdgcn_readfirstlane(ta.ty);
-	const uint32_t tile_bx = __builtin_amdgcn_readfirstlane(tb.tx), tile_by = __builtin_amdgcn_readfirstlane(tb.ty);
-	const uint32_t tile_code = __builtin_amdgcn_readfirstlane((ta.code & 0xFFu) | (tb.code & 0xFFu) << 8 | (tiled ? 1u << 16 : 0u));
-	uint64_t idx = 0; uint32_t px = 0, py = 0;
-	const bool valid_a = tiled ? tile_lane(tg, ta, lane, idx, px, py) : linear_ray(p, group_a, lane, idx, px, py);
 	// a lane without a ray in a packet walks along with an empty interval
 	RayRegs ra = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f}, rb = ra;
-	if (valid_a) load_ray<STREAM>(p, idx, px, py, ra);
-	bool valid_b = false;
-	if (PACKETS == 2) {
-		valid_b = tiled ? tile_lane(tg, tb, lane, idx, px, py) : linear_ray(p, group_a + 1u, lane, idx, px, py);
-		if (valid_b) load_ray<STREAM>(p, idx, px, py, rb);
+	bool valid_a = false, valid_b = false;
+	uint32_t tile_ax = 0u, tile_ay = 0u, tile_bx = 0u, tile_by = 0u, tile_code = 0u;
+	// Whole-tile pairs (lane_map.h fast_launch, asked by launch_trace; the grid's part here, where a width found on the device is
+	// known): one division for the wave, two shifts and two adds for the lane, 32-bit up to the address, both rays always there.
+	// The grid words and the skip word of a MAP_AUTO launch are one load.  Across the walk stay two scalars: the ray of tile A's
+	// first pixel and the row width (the lane's index in a vector register of its own made the compiler spill to scratch).  The
+	// paired walk and the records of such a wave are a copy of their own of the code below (rows_walks_and_records<.., true>): one
+	// copy for both would make this path carry the other's words across the walk.
+	if (PACKETS == 2 && !COUNT && p.rows_fast != kFastNo) {
+		const uint32_t how = p.rows_fast;
+		uint32_t gw = p.grid_w, n_rows = p.rows, tiles_x = p.tiles_x;
+		if (how != kFastOwnGrid) {
+			// (the four words detect_grid_kernel writes, 16-byte aligned: the static_assert on kAutoGridOff above the kernel)
+			const uint4 found = *reinterpret_cast<const uint4 *>(p.auto_grid);
+			if ((how == kFastAutoSkip) & (found.w == p.skip_when)) return;
+			gw = found.x; n_rows = found.y; tiles_x = found.z;
+		}
+		if (fast_grid(gw, n_rows, tiles_x)) {
+			uint32_t tx = 0u, ty = 0u;
+			if (!fast_wave_tile(gw, n_rows, block_s * (WG / MRT_WAVE) + wave_s, tx, ty)) return; // past the last pair
+			const RowsWave w = {0u, 0u, 0u, 0u, 0u, 0u, 0u, fast_tile_ray(gw, tx, ty), gw};
+			const float4 *q = reinterpret_cast<const float4 *>(p.rays) + (size_t)fast_lane_ray(gw, w.fast_ray, lane) * 2u;
+			load_ray32<STREAM>(q, ra);
+			load_ray32<STREAM>(q + 16, rb); // (group B: the ray 8 on)
+			if (rows_walks_and_records<ANY_HIT, COUNT, PACKETS, WG, CULL, true>(p, (RowsStack)wave_stack[wave_s][0], (RowsStack)wave_stack[wave_s][PACKETS - 1], lane, ra, rb, true, true, w))
+				return;
+			// the two tiles do not share an octant: on with the general code, as the two whole tiles of the general map they are
+			valid_a = valid_b = true;
+			tile_ax = tx; tile_ay = ty; tile_bx = tx + 1u; tile_by = ty; tile_code = kPieceTile | kPieceTile << 8 | 1u << 16;
+		}
 	}
-	if (__ballot(valid_a || valid_b) == 0ull) return; // nothing for this wave (otherwise every lane stays in)
+	// Every other launch: the wave's tiles, once, on the scalar unit (lane_map.h): the second group's follows from the first's.  They
+	// stay in scalar registers across the walk, for the epilogue: tile_a / tile_b = column | row of a tile, tile_code = the two pieces.
+	// (The kernel's arguments are read again from here on: what this code needs of them -- most of them, some kept across the walks in
+	// spill lanes -- is loaded here, not in the code every wave runs.)
+	const TraceParams &pg = *(const TraceParams *)rows_args_again();
+	if (tile_code == 0u) {
+		if (skip_launch(pg)) return;
+		const uint64_t group_a = ((uint64_t)block_s * (WG / MRT_WAVE) + wave_s) * PACKETS; // the wave's first group of 64 rays
+		TileGrid tg;
+		const bool tiled = tile_grid(pg, tg);
+		WaveTile ta = {0u, 0u, kPieceNone}, tb = ta;
+		if (tiled) {
+			ta = wave_tile(tg, group_a);
+			if (PACKETS == 2) tb = wave_tile_next(tg, ta, group_a);
+		}
+		tile_ax = __builtin_amdgcn_readfirstlane(ta.tx); tile_ay = __builtin_amdgcn_readfirstlane(ta.ty);
+		tile_bx = __builtin_amdgcn_readfirstlane(tb.tx); tile_by = __builtin_amdgcn_readfirstlane(tb.ty);
+		tile_code = __builtin_amdgcn_readfirstlane((ta.code & 0xFFu) | (tb.code & 0xFFu) << 8 | (tiled ? 1u << 16 : 0u));
+		uint64_t idx = 0; uint32_t px = 0, py = 0;
+		valid_a = tiled ? tile_lane(tg, ta, lane, idx, px, py) : linear_ray(pg, group_a, lane, idx, px, py);
+		if (valid_a) load_ray<STREAM>(pg, idx, px, py, ra);
+		if (PACKETS == 2) {
+			valid_b = tiled ? tile_lane(tg, tb, lane, idx, px, py) : linear_ray(pg, group_a + 1u, lane, idx, px, py);
+			if (valid_b) load_ray<STREAM>(pg, idx, px, py, rb);
+		}
+		if (__ballot(valid_a || valid_b) == 0ull) return; // nothing for this wave (otherwise every lane stays in)
+		// the wave's start time waits in memory, not in registers (none to spare in the walk): in the cost array itself
+		// (note_tile_start / note_tile_cost)
+		if (pg.tile_cost != nullptr && lane == 0u) note_tile_start(pg, group_a << 6);
+	}
+	const RowsWave w = {block_s, wave_s, tile_ax, tile_ay, tile_bx, tile_by, tile_code, 0u, 0u};
+	rows_walks_and_records<ANY_HIT, COUNT, PACKETS, WG, CULL, false>(pg, (RowsStack)wave_stack[wave][0], (RowsStack)wave_stack[wave][PACKETS - 1], lane, ra, rb, valid_a, valid_b, w);
+}
 
+template <bool ANY_HIT, bool COUNT, int PACKETS, int WG, bool CULL, bool FAST>
+__device__ __forceinline__ bool rows_walks_and_records(const TraceParams &p, RowsStack lds_a, RowsStack lds_b, uint32_t lane,
+		RayRegs &ra, RayRegs &rb, bool valid_a, bool valid_b, const RowsWave &w)
+{
+	constexpr bool STREAM = WG == MRT_WAVE;
+	uint32_t *stack_a = (uint32_t *)lds_a, *stack_b = (uint32_t *)lds_b;
+	const uint32_t block_s = w.block_s, wave_s = w.wave_s, tile_ax = w.tile_ax, tile_ay = w.tile_ay, tile_bx = w.tile_bx, tile_by = w.tile_by, tile_code = w.tile_code;
 	const float4 *rows = reinterpret_cast<const float4 *>(p.row_array);
-	uint32_t *stack_a = wave_stack[wave][0], *stack_b = wave_stack[wave][PACKETS - 1];
 	// sentinels (volatile: the asm blocks have no "memory" clobber; they touch only read-only scene data and this stack)
-	*(volatile uint32_t *)&stack_a[0] = kSentinel;
-	if (PACKETS == 2) *(volatile uint32_t *)&stack_b[0] = kSentinel;
+	*(volatile __attribute__((address_space(3))) uint32_t *)&lds_a[0] = kSentinel;
+	if (PACKETS == 2) *(volatile __attribute__((address_space(3))) uint32_t *)&lds_b[0] = kSentinel;
 	PacketRegs A, B;
-	rows_init(A, ra, valid_a, (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(stack_a + 4));
-	rows_init(B, rb, valid_b, (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(stack_b + 4));
+	rows_init(A, ra, valid_a, (uint32_t)(uintptr_t)(lds_a + 4));
+	rows_init(B, rb, valid_b, (uint32_t)(uintptr_t)(lds_b + 4));
 
 	unsigned long long part_a = 0ull, part_b = 0ull;
-	const int oct_a = rows_octant(ra, valid_a, part_a);
-	const int oct_b = PACKETS == 2 ? rows_octant(rb, valid_b, part_b) : 8;
+	const int oct_a = rows_octant(A, valid_a, part_a);
+	const int oct_b = PACKETS == 2 ? rows_octant(B, valid_b, part_b) : 8;
 	uint32_t cnt_n = 0u, cnt_t = 0u; // COUNT: node rows / triangle rows fetched by this wave
 	uint32_t cnt_w = 0u;             // COUNT, one-packet loop: shader cycles between issuing a row fetch and having it
 	uint32_t sp_wide = 0u, sp_one = 0u; // COUNT: highest stack pointers seen (LDS byte addresses) by the 128-ray / the one-packet walk
-	// the wave's start time waits in memory, not in registers (none to spare in the walk): in the cost array itself
-	// (note_tile_start / note_tile_cost), and for the counting builds in the unused words of the stack's sentinel entry
-	if (p.tile_cost != nullptr && lane == 0u) note_tile_start(p, group_a << 6);
-	if (COUNT) *(volatile unsigned long long *)&stack_a[2] = __builtin_amdgcn_s_memtime();
+	// (the counting builds' start time waits in memory too: in the unused words of the stack's sentinel entry)
+	if (COUNT) *(volatile __attribute__((address_space(3))) unsigned long long *)&lds_a[2] = __builtin_amdgcn_s_memtime();
 	bool done_a = part_a == 0ull, done_b = part_b == 0ull;
 	if (PACKETS == 2 && !done_a && !done_b && oct_a == oct_b && oct_a != 8) {
 		// one walk for both groups: 32-byte stack entries over the wave's whole stack area, sentinel at its bottom;
 		// at the root every lane that takes part owns the row
-		*(volatile uint32_t *)&stack_a[4] = kSentinel;
+		*(volatile __attribute__((address_space(3))) uint32_t *)&lds_a[4] = kSentinel;
 		A.sp += 16u; // (= stack base + 32)
 		A.mask = part_a; B.mask = part_b;
 		if (CULL) {
@@ -947,28 +1076,31 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS_WPE
 #undef MRT_RW2
 		}
 		done_a = done_b = true;
+		if (FAST) { rows_fast_records<STREAM>(w, A, B); return true; }
 	}
+	if (FAST) return false; // (tiles on an image axis, mixed directions in a tile: the general code below takes the wave on)
 	// packets that could not be paired (different octants: tiles on an image axis; a single packet): one at a time
 #define MRT_RW1(O, S) case O: rows_walk_one<O, ANY_HIT, COUNT>(rows, p.query_mask, S, cnt_n, cnt_t, cnt_w, sp_one); break;
 	if (!done_a && oct_a != 8) { switch (oct_a) { MRT_RW1(0, A) MRT_RW1(1, A) MRT_RW1(2, A) MRT_RW1(3, A) MRT_RW1(4, A) MRT_RW1(5, A) MRT_RW1(6, A) MRT_RW1(7, A) } done_a = true; }
 	if (PACKETS == 2 && !done_b && oct_b != 8) { switch (oct_b) { MRT_RW1(0, B) MRT_RW1(1, B) MRT_RW1(2, B) MRT_RW1(3, B) MRT_RW1(4, B) MRT_RW1(5, B) MRT_RW1(6, B) MRT_RW1(7, B) } done_b = true; }
 #undef MRT_RW1
+	const TraceParams &p2 = p;
 	// best hit as the other kernels keep it: leaf-order slot = row - number of node rows
-	uint32_t slot_a = A.bs == 0xFFFFFFFFu ? 0xFFFFFFFFu : A.bs - p.n_nodes, slot_b = B.bs == 0xFFFFFFFFu ? 0xFFFFFFFFu : B.bs - p.n_nodes;
+	uint32_t slot_a = A.bs == 0xFFFFFFFFu ? 0xFFFFFFFFu : A.bs - p2.n_nodes, slot_b = B.bs == 0xFFFFFFFFu ? 0xFFFFFFFFu : B.bs - p2.n_nodes;
 	// mixed directions inside a packet: the generic compiler-scheduled walk over nodes + triangle arrays
 	if (!done_a) {
 		uint32_t nn = 0, nt = 0, nd = 0;
 		A.bt = ra.t_max;
-		packet_traverse<8, ANY_HIT, COUNT>(p, ra, stack_a, A.bt, A.bu, A.bv, slot_a, nn, nt, nd, 0u, 0u, nullptr, !valid_a);
+		packet_traverse<8, ANY_HIT, COUNT>(p2, ra, stack_a, A.bt, A.bu, A.bv, slot_a, nn, nt, nd, 0u, 0u, nullptr, !valid_a);
 		if (COUNT) { cnt_n += __builtin_amdgcn_readfirstlane(nn); cnt_t += __builtin_amdgcn_readfirstlane(nt); }
-		rows_hit_of_slot(rows, p.n_nodes, slot_a, A);
+		rows_hit_of_slot(rows, p2.n_nodes, slot_a, A);
 	}
 	if (PACKETS == 2 && !done_b) {
 		uint32_t nn = 0, nt = 0, nd = 0;
 		B.bt = rb.t_max;
-		packet_traverse<8, ANY_HIT, COUNT>(p, rb, stack_b, B.bt, B.bu, B.bv, slot_b, nn, nt, nd, 0u, 0u, nullptr, !valid_b);
+		packet_traverse<8, ANY_HIT, COUNT>(p2, rb, stack_b, B.bt, B.bu, B.bv, slot_b, nn, nt, nd, 0u, 0u, nullptr, !valid_b);
 		if (COUNT) { cnt_n += __builtin_amdgcn_readfirstlane(nn); cnt_t += __builtin_amdgcn_readfirstlane(nt); }
-		rows_hit_of_slot(rows, p.n_nodes, slot_b, B);
+		rows_hit_of_slot(rows, p2.n_nodes, slot_b, B);
 	}
 
 	// The rays' indices again, from the wave's tiles (scalars) and the lane (the exec-mask count): no index, pixel or validity
@@ -979,30 +1111,31 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS_WPE
 		const uint64_t h_a = ((uint64_t)block_s * (WG / MRT_WAVE) + wave_s) * PACKETS;
 		const bool tiled2 = (tile_code >> 16 & 1u) != 0u;
 		TileGrid tg2;
-		(void)tile_grid(p, tg2); // (of which the lane's part reads the clip rectangle and the tile's shape)
+		(void)tile_grid(p2, tg2); // (of which the lane's part reads the clip rectangle and the tile's shape)
 		const WaveTile ua = {tile_ax, tile_ay, tile_code & 0xFFu}, ub = {tile_bx, tile_by, tile_code >> 8 & 0xFFu};
 		uint64_t idx2 = 0; uint32_t px2 = 0, py2 = 0;
-		if (tiled2 ? tile_lane(tg2, ua, lane2, idx2, px2, py2) : linear_ray(p, h_a, lane2, idx2, px2, py2))
-			finish_row_ray<STREAM>(p, rows, idx2, ra, A.bt, A.bu, A.bv, A.bs, A.bi, slot_a);
-		if (PACKETS == 2 && (tiled2 ? tile_lane(tg2, ub, lane2, idx2, px2, py2) : linear_ray(p, h_a + 1u, lane2, idx2, px2, py2)))
-			finish_row_ray<STREAM>(p, rows, idx2, rb, B.bt, B.bu, B.bv, B.bs, B.bi, slot_b);
-		if (p.tile_cost != nullptr && lane2 == 0u) note_tile_cost(p, h_a << 6);
+		if (tiled2 ? tile_lane(tg2, ua, lane2, idx2, px2, py2) : linear_ray(p2, h_a, lane2, idx2, px2, py2))
+			finish_row_ray<STREAM>(p2, rows, idx2, ra, A.bt, A.bu, A.bv, A.bs, A.bi, slot_a);
+		if (PACKETS == 2 && (tiled2 ? tile_lane(tg2, ub, lane2, idx2, px2, py2) : linear_ray(p2, h_a + 1u, lane2, idx2, px2, py2)))
+			finish_row_ray<STREAM>(p2, rows, idx2, rb, B.bt, B.bu, B.bv, B.bs, B.bi, slot_b);
+		if (p2.tile_cost != nullptr && lane2 == 0u) note_tile_cost(p2, h_a << 6);
 	}
-	const unsigned long long t_start = COUNT ? *(volatile unsigned long long *)&stack_a[2] : 0ull;
-	if (COUNT && lane == 0u && (p.count_mode != 2u || (blockIdx.x & 15u) == 0u)) { // the wave's clock: cycles in the row-fetch waits of the one-packet loop, cycles in all
-		atomicAdd(&p.counters[kCntFetchWaitCycles], (unsigned long long)cnt_w);
-		atomicAdd(&p.counters[kCntWaveCycles], __builtin_amdgcn_s_memtime() - t_start);
-		atomicAdd(&p.counters[kCntWaves], 1ull);
+	const unsigned long long t_start = COUNT ? *(volatile __attribute__((address_space(3))) unsigned long long *)&lds_a[2] : 0ull;
+	if (COUNT && lane == 0u && (p2.count_mode != 2u || (blockIdx.x & 15u) == 0u)) { // the wave's clock: cycles in the row-fetch waits of the one-packet loop, cycles in all
+		atomicAdd(&p2.counters[kCntFetchWaitCycles], (unsigned long long)cnt_w);
+		atomicAdd(&p2.counters[kCntWaveCycles], __builtin_amdgcn_s_memtime() - t_start);
+		atomicAdd(&p2.counters[kCntWaves], 1ull);
 	}
-	if (COUNT && p.count_mode != 2u) { // the stack's high-water mark, in entries (the bound is the uploaded BVH's depth, <= 64: api.hip)
-		const uint32_t base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)stack_a;
+	if (COUNT && p2.count_mode != 2u) { // the stack's high-water mark, in entries (the bound is the uploaded BVH's depth, <= 64: api.hip)
+		const uint32_t base = (uint32_t)(uintptr_t)lds_a;
 		const uint32_t e_wide = sp_wide > base ? (sp_wide - base) / 32u : 0u, e_one = sp_one > base ? ((sp_one - base) % 1040u) / 16u : 0u;
-		atomicMax(&p.counters[kCntMaxStack], (unsigned long long)(e_wide > e_one ? e_wide : e_one));
+		atomicMax(&p2.counters[kCntMaxStack], (unsigned long long)(e_wide > e_one ? e_wide : e_one));
 	}
-	if (COUNT && p.count_mode != 2u) { // (count_visits = 2: the clock only, sampled, so that the counting itself does not load the memory system)
+	if (COUNT && p2.count_mode != 2u) { // (count_visits = 2: the clock only, sampled, so that the counting itself does not load the memory system)
 		// per-ray words: every step of the wave is charged to every ray of the wave (both packets): an upper bound
 		// per packet; the fetch words (kCntWaveNodeFetch / kCntWaveTriFetch) are exact
-		if (valid_a) packet_count(p, cnt_n, cnt_t, 0u, slot_a != 0xFFFFFFFFu, part_a | part_b);
-		if (PACKETS == 2 && valid_b) { atomicAdd(&p.counters[kCntRays], 1ull); if (slot_b != 0xFFFFFFFFu) atomicAdd(&p.counters[kCntHits], 1ull); }
+		if (valid_a) packet_count(p2, cnt_n, cnt_t, 0u, slot_a != 0xFFFFFFFFu, part_a | part_b);
+		if (PACKETS == 2 && valid_b) { atomicAdd(&p2.counters[kCntRays], 1ull); if (slot_b != 0xFFFFFFFFu) atomicAdd(&p2.counters[kCntHits], 1ull); }
 	}
+	return true;
 }
