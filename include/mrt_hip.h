@@ -982,7 +982,8 @@ int mrt_light_grid_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w
  * and the direct light mrt_light_surfaces wrote with env == NULL.  Per bounce a renderer queues
  *   cast -> resolve (d_rows, d_bounce_surface, d_out_hits) -> shadows -> light with env = NULL -> step -> bounce cast with d_select
  * and reads back four bytes (d_active_count); after the last bounce, mrt_path_finish.  With a panorama resident
- * (mrt_upload_panorama, below) the sky of a miss is a sample of it.  The average over sample_index frames stays with the renderer. */
+ * (mrt_upload_panorama, below) the sky of a miss is a sample of it.  The average over sample_index frames is
+ * mrt_accumulate (MRT_ACCUM_SRC_PATH_STATE, in place of mrt_path_finish), below. */
 
 /* PathState without its generator (the stream is a function of pixel, frame and bounce: mrt_cast_bounce); 32 bytes */
 typedef struct mrt_path_state {
@@ -1112,8 +1113,8 @@ int mrt_clear_panorama(mrt_ctx *ctx);
  *   acos_def(c), c in [-1, 1] = (float)core(sqrt((1.0 - c) * (1.0 + c)), c) with c as a double: acos_def(1) = +0,
  *     acos_def(-1) = (float)pi.
  *   Both are within 1 fp32 ulp of the correctly rounded function.
- * Not taken: prefiltered or importance-sampled IBL, mipmaps, RGBE or half-float images, the running average over sample_index,
- * and a panorama per member of an mrt_group (a group's contexts take uploads one by one, mrt_group_context). */
+ * Not taken: prefiltered or importance-sampled IBL, mipmaps, RGBE or half-float images (the running average over
+ * sample_index is mrt_accumulate, below), and a panorama per member of an mrt_group (a group's contexts take uploads one by one, mrt_group_context). */
 
 /* ---- the renderer's AOV channels and its 8-bit image: the ten channels of RayImage besides COLOR as ShadePass's per-channel
  * functions write them (src/modules/graphics/shade_pass.h:337-395, :732-884; the enum is ray_image.h:43-56), the last two lines of
@@ -1181,6 +1182,85 @@ int mrt_finish_color(mrt_ctx *ctx, const float *d_lit_rgba, uint64_t count, uint
  * Not taken: RayImage's other image formats, resizing, and COLOR inside mrt_shade_channels (it needs the lights and the shadow
  * masks: the lighting calls). */
 int mrt_image_to_rgba8(mrt_ctx *ctx, const float *d_rgba, uint64_t count, uint8_t *d_rgba8, uint32_t flags);
+
+/* ---- progressive frames: the temporal accumulation of RayRenderer (src/modules/graphics/ray_renderer.cpp) -- the camera-motion
+ * reset (:441-469), the Halton(2,3) sub-pixel jitter (:474-504), the running mean over accum_count_ frames (:799-835) and the byte
+ * conversion of the mean (:847-858).  Three host rules that need no context and no device, and one per-pixel device pass that takes
+ * the float frame (or, fused, the lit frame or the path state) to the mean and its displayable bytes.  A frame of a renderer is
+ *   mrt_accum_begin_frame -> camera.jitter_x / jitter_y, frame = sample_index -> the frame's casts and passes
+ *   -> mrt_accum_end_frame -> accumulate ? mrt_accumulate(n_prior) : mrt_image_to_rgba8 / mrt_finish_color / mrt_path_finish.
+ *
+ * mrt_halton_jitter: jitter = {halton2(sample_index + 1), halton3(sample_index + 1)}, the two lambdas of :480-501 -- fp32, one
+ * operation at a time, the loop on the integer i = sample_index + 1:
+ *   halton2: f = 1, r = 0; while (i > 0) { f = f * 0.5f; r = r + f * (float)(i & 1); i >>= 1; }
+ *   halton3: f = 1, r = 0; while (i > 0) { f = f * INV3; r = r + f * (float)(i % 3); i /= 3; }, INV3 = 1.0f / 3.0f one float constant.
+ * The pair goes into mrt_camera.jitter_x / jitter_y as it is (generate_rays_tile_jittered takes the values unchanged; 0.5 is only the
+ * no-jitter default).  MRT_ERR_INVALID for a null pointer, then for sample_index > 0x7ffffffe (the reference's index is an int). */
+int mrt_halton_jitter(uint32_t sample_index, float jitter[2]);
+
+typedef struct mrt_accum_state {           /* 96 bytes */
+	uint32_t struct_size;                  /* sizeof(mrt_accum_state) */
+	/* settings, the caller's: set_aa_enabled / set_aa_max_samples (:66-75).  The setter's clamp max_samples > 1 ? max_samples : 1
+	 * is applied where the value is read, so any int may stand here. */
+	uint32_t aa_enabled;                   /* 0: off; anything else: on */
+	int32_t max_samples;
+	/* persistent words, zero before the first frame and then left to the two calls */
+	uint32_t count;                        /* accum_count_: frames in the mean */
+	uint64_t pixels;                       /* the accumulation buffer's size in pixels */
+	float prev_origin[3];                  /* prev_cam_origin_ */
+	float prev_basis[9];                   /* prev_cam_basis_, row-major as mrt_camera_perspective takes it */
+	/* outputs of mrt_accum_begin_frame */
+	float jitter_x, jitter_y;              /* for mrt_camera.jitter_x / jitter_y */
+	uint32_t sample_index;                 /* for mrt_bounce.frame and mrt_path_step_desc.frame of a path-traced frame (:177) */
+	/* outputs of mrt_accum_end_frame */
+	uint32_t accumulate;                   /* 1: show the mean (mrt_accumulate with n_prior); 0: show the raw frame */
+	uint32_t n_prior;                      /* frames in the mean before this one */
+	uint32_t reserved;                     /* not read */
+} mrt_accum_state;
+/* The start of a frame (:444-469 and the branch at :474).  origin, basis: the camera's, as mrt_camera_perspective takes them; column
+ * c of a basis is {basis[c], basis[3 + c], basis[6 + c]}.  length_squared(v) = (v.x * v.x + v.y * v.y) + v.z * v.z, fp32, summed left
+ * to right, of the component-wise difference new - previous.
+ *   aa_enabled == 0: count = 0.
+ *   otherwise: moved = length_squared(origin - prev_origin) > POS_EPS * POS_EPS, POS_EPS = 1e-4f; only when not moved, over columns
+ *     0, 1, 2 until one says so: rotated = length_squared(column - previous column) > ROT_EPS * ROT_EPS, ROT_EPS = 1e-3f (both
+ *     thresholds float products); moved or rotated: count = 0.
+ *   A NaN in the pose compares false, as in the reference: a pose that is NaN, or that follows one, resets nothing.
+ *   prev_origin and prev_basis are overwritten in every case; then sample_index = count, and
+ *   aa_enabled and count < max(max_samples, 1): {jitter_x, jitter_y} = mrt_halton_jitter(count); otherwise {0.5, 0.5}.
+ * MRT_ERR_INVALID for a null pointer, then for a struct_size that is not sizeof(mrt_accum_state); nothing is written then. */
+int mrt_accum_begin_frame(mrt_accum_state *st, const float origin[3], const float basis[9]);
+/* The end of a frame, before it is shown (the bookkeeping of :804-835).  pixels = width * height of the frame.
+ *   aa_enabled and count < max(max_samples, 1): pixels != st->pixels (the resolution changed): st->pixels = pixels, count = 0;
+ *     n_prior = count; accumulate = 1; count = count + 1.
+ *   otherwise accumulate = 0 and n_prior = 0: the frame shown is the raw one, through mrt_image_to_rgba8,
+ *     mrt_finish_color or mrt_path_finish as before.  That includes the reference's behaviour once max_samples is reached: with the
+ *     camera at rest it then shows the un-averaged, un-jittered frame again (begin_frame gave {0.5, 0.5}), not the converged mean; a
+ *     renderer that wants to hold the mean keeps showing its own d_rgba8.
+ * MRT_ERR_INVALID as for mrt_accum_begin_frame. */
+int mrt_accum_end_frame(mrt_accum_state *st, uint64_t pixels);
+
+/* The running mean on the device.  Sample s of pixel i, four floats:
+ *   MRT_ACCUM_SRC_RGBA        d_source = 4 floats per pixel; s = those, bits as they are.
+ *   MRT_ACCUM_SRC_LIT         d_source = 4 floats per pixel as mrt_light_surfaces / mrt_light_grid_surfaces wrote them with an
+ *                             environment; s = what mrt_finish_color writes to d_rgba for it with tonemap_mode.
+ *   MRT_ACCUM_SRC_PATH_STATE  d_source = mrt_path_state per pixel; s = what mrt_path_finish writes for it with tonemap_mode.
+ * The two fused kinds call the device functions of those passes (hp(11.2f) once per call on the host), so a frame's tail is one
+ * launch and one pass over the pixels.  acc = d_accum[4i .. 4i + 3]:
+ *   n_prior == 0: acc = s (the reference's memcpy: for RGBA every bit of the source, a NaN's payload and -0 included).
+ *   otherwise, inv = 1.0f / (float)(int)(n_prior + 1) once per call on the host, and per component, alpha included, three separately
+ *     rounded fp32 operations: d = s - acc; p = d * inv; acc = acc + p   (:824-827).
+ *   d_rgba8 (optional, 4 bytes per pixel) = to_rgba8 of the four floats of acc just written (:850-857: std::max(0.0f, x) and
+ *     std::min(255.0f, y) select exactly as to_rgba8 states, a NaN becomes 0).
+ * Per pixel: one 16-byte load of the source (PATH_STATE: the second 16 bytes of the state), one 16-byte load of the accumulator when
+ * n_prior != 0, one 16-byte store of it, one 4-byte store of the bytes.  d_source is only read.  Flags: MRT_FLAG_ASYNC.
+ * count == 0: MRT_OK, nothing written.  The call touches neither the scene, the tuner, the tile schedule nor mrt_stats.
+ * MRT_ERR_INVALID before any device work, in this order: a null context, d_source or d_accum; an unknown flag; an unknown
+ * source_kind; tonemap_mode > 4 for LIT and PATH_STATE (not looked at for RGBA); n_prior > 0x7ffffffe; d_accum == d_source;
+ * count * 32 overflowing.  Then MRT_ERR_PENDING while a dispatch is pending.
+ * Not taken: variance estimates, reprojection of the mean when the camera moves, and the reflection effect's GLSL denoisers. */
+enum { MRT_ACCUM_SRC_RGBA = 0, MRT_ACCUM_SRC_LIT = 1, MRT_ACCUM_SRC_PATH_STATE = 2 };
+int mrt_accumulate(mrt_ctx *ctx, uint32_t source_kind, const void *d_source, uint64_t count, uint32_t tonemap_mode,
+		uint32_t n_prior, float *d_accum, uint8_t *d_rgba8, uint32_t flags);
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to
  * tokens written by a cast with MRT_FLAG_TOKEN_OUT: mrt_hit32 records (mrt_host_hit44 with

@@ -36,6 +36,7 @@ SYMBOLS = [
     "mrt_upload_textures", "mrt_clear_textures",
     "mrt_upload_panorama", "mrt_clear_panorama",
     "mrt_shade_channels", "mrt_shade_grid_channels", "mrt_finish_color", "mrt_image_to_rgba8",
+    "mrt_halton_jitter", "mrt_accum_begin_frame", "mrt_accum_end_frame", "mrt_accumulate",
     "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
     "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
@@ -119,6 +120,17 @@ class ChannelOut(C.Structure):
                 ("d_rgba", C.c_void_p * CHANNEL_COUNT), ("d_rgba8", C.c_void_p * CHANNEL_COUNT)]
 
 
+class AccumState(C.Structure):
+    """mrt_accum_state"""
+    _fields_ = [("struct_size", C.c_uint32), ("aa_enabled", C.c_uint32), ("max_samples", C.c_int32), ("count", C.c_uint32),
+                ("pixels", C.c_uint64), ("prev_origin", C.c_float * 3), ("prev_basis", C.c_float * 9),
+                ("jitter_x", C.c_float), ("jitter_y", C.c_float), ("sample_index", C.c_uint32), ("accumulate", C.c_uint32),
+                ("n_prior", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ACCUM_SRC_RGBA, ACCUM_SRC_LIT, ACCUM_SRC_PATH_STATE = 0, 1, 2
+
+
 class LightOut(C.Structure):
     """mrt_light_out"""
     _fields_ = [("d_rgba", C.c_void_p)]
@@ -136,6 +148,7 @@ TEXTURES_ON_DEVICE = 1
 TEXEL_RGBA8, TEXEL_RGBA32F = 0, 1
 PANORAMA_ON_DEVICE = 1
 PANORAMA_MAX_DIM = 16384
+STRUCT_ACCUM_STATE = 26   # mrt_struct_size index (25: not a struct)
 STRUCT_CHANNEL_OUT = 24   # mrt_struct_size index (23: not a struct)
 STRUCT_PANORAMA = 22   # mrt_struct_size index (21: not a struct)
 STRUCT_TEXTURE, STRUCT_MATERIAL_TEXTURES, STRUCT_TEXTURE_SET = 18, 19, 20   # mrt_struct_size indices (17: not a struct)
@@ -286,6 +299,10 @@ def load():
                                           C.POINTER(ChannelOut), C.c_uint32]
     L.mrt_finish_color.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
     L.mrt_image_to_rgba8.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
+    L.mrt_halton_jitter.argtypes = [C.c_uint32, C.POINTER(C.c_float)]
+    L.mrt_accum_begin_frame.argtypes = [C.POINTER(AccumState), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.mrt_accum_end_frame.argtypes = [C.POINTER(AccumState), C.c_uint64]
+    L.mrt_accumulate.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
     L.mrt_cast_tiled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mrt_expand_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
     L.mrt_expand_grid_tokens.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -485,6 +502,40 @@ def kernel_available(kernel_id: int) -> bool:
 
 def kernel_name(kernel_id: int) -> str:
     return load().mrt_kernel_name(kernel_id).decode()
+
+
+def halton_jitter(sample_index):
+    """mrt_halton_jitter: (jitter_x, jitter_y) of frame sample_index of a progressive render"""
+    j = (C.c_float * 2)()
+    rc = load().mrt_halton_jitter(sample_index, j)
+    if rc:
+        raise MrtError(rc, "mrt_halton_jitter")
+    return np.float32(j[0]), np.float32(j[1])
+
+
+def accum_state(aa_enabled=True, max_samples=256) -> AccumState:
+    """A fresh mrt_accum_state: the two settings, every persistent word zero"""
+    st = AccumState()
+    st.struct_size, st.aa_enabled, st.max_samples = C.sizeof(AccumState), int(bool(aa_enabled)), max_samples
+    return st
+
+
+def accum_begin_frame(st, origin, basis):
+    """mrt_accum_begin_frame: the motion reset, then st.sample_index and st.jitter_x / jitter_y of the frame (basis: 3x3 row-major)"""
+    o = (C.c_float * 3)(*np.asarray(origin, dtype=np.float32).reshape(3))
+    b = (C.c_float * 9)(*np.asarray(basis, dtype=np.float32).reshape(9))
+    rc = load().mrt_accum_begin_frame(C.byref(st), o, b)
+    if rc:
+        raise MrtError(rc, "mrt_accum_begin_frame")
+    return st
+
+
+def accum_end_frame(st, pixels):
+    """mrt_accum_end_frame: st.accumulate and st.n_prior of the frame of `pixels` pixels just rendered"""
+    rc = load().mrt_accum_end_frame(C.byref(st), pixels)
+    if rc:
+        raise MrtError(rc, "mrt_accum_end_frame")
+    return st
 
 
 def camera_look(origin, forward, grid_w, grid_h, fov_degrees) -> Camera:
@@ -981,6 +1032,13 @@ class Context:
     def image_to_rgba8(self, d_rgba, count, d_rgba8, flags=0):
         """The 8-bit image of a float plane: 4 bytes per record."""
         self._chk(self.L.mrt_image_to_rgba8(self.h, _ptr(d_rgba), count, _ptr(d_rgba8), flags))
+
+    def accumulate(self, source_kind, d_source, count, d_accum, n_prior, d_rgba8=None, tonemap_mode=0, flags=0):
+        """One frame into the running mean of a progressive render: d_accum (4 floats per pixel) takes the sample when n_prior == 0, else
+        acc + (s - acc) * (1 / (n_prior + 1)); d_rgba8 (optional) the mean's 8-bit image.  source_kind: ACCUM_SRC_RGBA (4 floats per
+        pixel as they are), ACCUM_SRC_LIT (a lit frame, finished as finish_color would) or ACCUM_SRC_PATH_STATE (T.PATH_STATE entries,
+        finished as path_finish would)."""
+        self._chk(self.L.mrt_accumulate(self.h, source_kind, _ptr(d_source), count, tonemap_mode, n_prior, _ptr(d_accum), _optr(d_rgba8), flags))
 
     def expand_tokens(self, d_rays, d_tokens, d_hits, count, flags=0, stream=None):
         """Device pointers; enqueued on `stream` (raw hipStream_t) or the context's stream, not waited for."""

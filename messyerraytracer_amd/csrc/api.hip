@@ -167,6 +167,7 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 20: return (uint32_t)sizeof(mrt_texture_set);
 		case 22: return (uint32_t)sizeof(mrt_panorama); // (21: not a struct)
 		case 24: return (uint32_t)sizeof(mrt_channel_out); // (23: not a struct)
+		case 26: return (uint32_t)sizeof(mrt_accum_state); // (25: not a struct)
 		default: return 0u;
 	}
 }

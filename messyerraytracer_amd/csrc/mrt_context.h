@@ -53,6 +53,9 @@ hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, co
 hipError_t launch_shade_channels(const TraceParams &p, const ChannelParams &c, const TextureParams &t, int src, hipStream_t stream);
 hipError_t launch_finish_color(const float *lit, uint64_t count, uint32_t mode, float white, float *rgba, uint8_t *rgba8, hipStream_t stream);
 hipError_t launch_image_to_rgba8(const float *rgba, uint64_t count, uint8_t *rgba8, hipStream_t stream);
+// the running mean of progressive frames (accum_kernel.h): kind = an MRT_ACCUM_SRC_*, first: n_prior == 0, inv = 1 / (n_prior + 1)
+hipError_t launch_accumulate(int kind, bool first, const void *source, uint64_t count, uint32_t mode, float white, float inv, float *accum,
+		uint8_t *rgba8, hipStream_t stream);
 // ---- device_build.hip
 hipError_t grow_arena(BuildArena *arena, size_t need, hipStream_t stream); // hipErrorOutOfMemory: no allocation, the arena is empty
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);

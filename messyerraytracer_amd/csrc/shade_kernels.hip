@@ -1,6 +1,6 @@
 // shade_kernels.hip — gfx950 kernels of the shading passes over hit records: the resolve to shading surfaces (plain and textured), the
 // direct light and the path tracer's per-pixel state (the lighting and the step also with a resident panorama), the renderer's
-// channels with the two image passes, and the packing of shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
+// channels with the two image passes, the running mean of progressive frames, and the packing of shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
 // source_common.h with the walks of kernels.hip, and are compiled apart from them.  The arithmetic is the canonical form of DESIGN.md
 // ("Arithmetic"), as in kernels.hip.
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@
 #include "path.h"
 #include "panorama.h"
 #include "channels.h"
+#include "accum.h"
 #include "lane_map.h"
 
 namespace mrt {
@@ -22,6 +23,7 @@ namespace mrt {
 #include "source_common.h"
 
 #include "path_frame_kernel.h"
+#include "accum_kernel.h"
 #include "surface_tex_kernel.h"
 #include "surface_kernel.h"
 #include "light_kernel.h"
@@ -64,6 +66,15 @@ hipError_t launch_finish_color(const float *lit, uint64_t count, uint32_t mode, 
 hipError_t launch_image_to_rgba8(const float *rgba, uint64_t count, uint8_t *rgba8, hipStream_t stream)
 {
 	return launch_per_entry<true>(image_to_rgba8_kernel, count, stream, rgba, count, rgba8);
+}
+// the running mean of progressive frames (accum_kernel.h), called from accum.hip; kind = an MRT_ACCUM_SRC_*, first: n_prior == 0
+hipError_t launch_accumulate(int kind, bool first, const void *source, uint64_t count, uint32_t mode, float white, float inv, float *accum,
+		uint8_t *rgba8, hipStream_t stream)
+{
+	hipError_t e = count ? hipErrorInvalidValue : hipSuccess;
+	dispatch([&](auto KIND, auto FIRST) { e = launch_per_entry<true>(accumulate_kernel<KIND, FIRST>, count, stream, source, count, mode, white, inv, accum, rgba8); },
+			Among<(int)MRT_ACCUM_SRC_RGBA, (int)MRT_ACCUM_SRC_LIT, (int)MRT_ACCUM_SRC_PATH_STATE>{kind}, Among<false, true>{first});
+	return e;
 }
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream)
 {
