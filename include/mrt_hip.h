@@ -273,8 +273,8 @@ uint32_t mrt_version(void);
 /* sizeof() of the boundary's structs as this library was compiled, for bindings in other languages to check
  * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light, 6 mrt_material,
  * 7 mrt_shade_data, 8 mrt_surface64, 9 mrt_surface_out, 11 mrt_shade_light, 12 mrt_environment, 13 mrt_light_out,
- * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set, 22 mrt_panorama
- * (0 for anything else). */
+ * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set, 22 mrt_panorama,
+ * 24 mrt_channel_out, 26 mrt_accum_state, 28 mrt_denoise_params (0 for anything else). */
 uint32_t mrt_struct_size(uint32_t which);
 /* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream). */
 int mrt_set_stream(mrt_ctx *ctx, void *hip_stream);
@@ -1257,10 +1257,108 @@ int mrt_accum_end_frame(mrt_accum_state *st, uint64_t pixels);
  * MRT_ERR_INVALID before any device work, in this order: a null context, d_source or d_accum; an unknown flag; an unknown
  * source_kind; tonemap_mode > 4 for LIT and PATH_STATE (not looked at for RGBA); n_prior > 0x7ffffffe; d_accum == d_source;
  * count * 32 overflowing.  Then MRT_ERR_PENDING while a dispatch is pending.
- * Not taken: variance estimates, reprojection of the mean when the camera moves, and the reflection effect's GLSL denoisers. */
+ * Not taken: variance estimates and reprojection of the mean when the camera moves.  (The reflection effect's denoisers: below.) */
 enum { MRT_ACCUM_SRC_RGBA = 0, MRT_ACCUM_SRC_LIT = 1, MRT_ACCUM_SRC_PATH_STATE = 2 };
 int mrt_accumulate(mrt_ctx *ctx, uint32_t source_kind, const void *d_source, uint64_t count, uint32_t tonemap_mode,
 		uint32_t n_prior, float *d_accum, uint8_t *d_rgba8, uint32_t flags);
+/* ---- the reflection effect's image passes: RTReflectionEffect (src/modules/graphics/rt_reflection_effect.cpp:255-435) after its
+ * trace -- the cross-bilateral spatial filter (src/gpu/shaders/rt_denoise_spatial.comp.glsl), the exponential history with rejection
+ * (rt_denoise_temporal.comp.glsl) and the Fresnel- and roughness-weighted blend into the colour buffer (rt_composite.comp.glsl).  The
+ * ray itself is mrt_cast_reflections / mrt_cast_grid_reflections; its records are resolved and lit like any others.  GLSL's exp, pow,
+ * normalize and half-float images are pinned by no standard, so every pass is stated here as fp32 operations in a fixed order, one
+ * rounding each, nothing contracted: every output is reproducible on the CPU bit for bit (messyerraytracer_amd/denoise.py).
+ *
+ * Images: device arrays, row-major, pixel (x, y) at index y * W + x.  Reflection, history, colour: 4 floats {r, g, b, a} per pixel;
+ * depth: 1 float per pixel; normal and roughness: 4 floats per pixel.  fp32 throughout: the reference's rgba16f storage is not taken.
+ * Sampling: the shaders sample at texel centres with UVs clamped to [0, 1], which is a texel fetch with clamp-to-edge: the tap at
+ * (x + dx, y + dy) reads texel (clamp(x + dx, 0, W - 1), clamp(y + dy, 0, H - 1)).  No UV arithmetic enters.
+ * max(a, b) = a < b ? b : a; min(a, b) = b < a ? b : a; clamp(x, lo, hi) = min(max(x, lo), hi): a NaN first argument is kept.
+ * normalize(x, y, z): len = sqrtf((x * x + y * y) + z * z); x / len, y / len, z / len (a zero vector gives NaNs).
+ *
+ * Normals, mrt_denoise_params.normal_kind, of a guide texel {gx, gy, gz, gw}:
+ *   MRT_NORMAL_OCTAHEDRAL (Godot's normal-roughness buffer): octahedral_decode (:40-46): fx = gx * 2 - 1, fy = gy * 2 - 1 (two
+ *     operations each); z = (1 - |fx|) - |fy|; t = clamp(-z, 0, 1); nx = fx + (fx >= 0 ? -t : t), ny = fy + (fy >= 0 ? -t : t), nz = z;
+ *     then normalize.  roughness = gz.
+ *   MRT_NORMAL_WORLD: n = {gx, gy, gz} as given, nothing normalised; roughness = gw (what mrt_reflection_guides writes).
+ *
+ * expn_def(float y), the passes' exp, defined for y <= 0 by fp64 arithmetic alone: the reduction, polynomial and scaling of pow01's
+ * second half (above), on Y = (double)y: Y < -104: 0.  Y > 89: +infinity.  n = (Y * INV_LN2 + RND) - RND; r = (Y - n * LN2_HI) -
+ * n * LN2_LO; p = Horner in r over 1 / k!, k = 13 .. 0, pow01's literals; the result (float)(p * 2^n), 2^n made from n's integer bits.
+ * -0.0f and +0.0f give 1.  A positive argument goes through the same arithmetic (its exp, rounded once; above 89 infinity); a NaN
+ * is returned as it is before any arithmetic, because the integer conversion of n is not defined for it.  Within 1 fp32 ulp of the
+ * correctly rounded exp on [-110, 0] (tests/test_denoise_cpu.py).
+ * pow01 is used as it stands.  For a base b a few ulps above 1 (the dot of two normalised vectors can be one) it has no select: the
+ * logarithm is a small positive number and the result is b^e computed like any other, slightly above 1 (b = 1 + 2^-22, e = 128:
+ * 1.0000305f).  A NaN base is returned as it is.
+ *
+ * Spatial pass (:52-124), per pixel; c = the centre texel, its normal decoded:
+ *   c.a <= 0: {0, 0, 0, 0}.  Then depth(c) >= 1: {0, 0, 0, 0}.
+ *   radius = clamp(kernel_radius, 1, 4) (integers).  Taps dy = -radius .. radius outer, dx = -radius .. radius inner, both ascending;
+ *   s = the tap's texel; s.a <= 0: skipped.  Otherwise
+ *     dd = |depth(c) - depth(s)|; w_depth = expn_def(-((dd * dd) * depth_sigma));
+ *     dot = (n(c).x * n(s).x + n(c).y * n(s).y) + n(c).z * n(s).z; w_normal = pow01(max(dot, 0), normal_sigma);
+ *     dr, dg, db = c.rgb - s.rgb; w_color = expn_def(-(((dr * dr + dg * dg) + db * db) * color_sigma));
+ *     w_spatial = expn_def(-((float)(dx * dx + dy * dy) / (2.0f * (float)(radius * radius) + 0.001f))), once per call on the host;
+ *     weight = ((w_depth * w_normal) * w_color) * w_spatial;
+ *     sum.k = sum.k + s.k * weight for k = r, g, b, a; weight_sum = weight_sum + weight.
+ *   weight_sum > 0.001f: sum.k / weight_sum per component; else c's four floats.
+ * Temporal pass (:40-83), per pixel, in this order:
+ *   1. has_history == 0 (the shader's frame_count == 0): the current pixel; the history is not read.
+ *   2. cur.a <= 0: history.k * 0.9f.   3. history.a <= 0: the current pixel.
+ *   4. rej = |cur.a - history.a| < depth_threshold ? 0 : 1; alpha = blend * (1 - rej) + rej; om = 1 - alpha;
+ *      out.k = history.k * om + cur.k * alpha.
+ *   As in the shader the two alphas are compared, not depths: the depth it samples is never used, so the call takes none.
+ *   d_out may be d_history (a pixel reads only its own history): that replaces the effect's texture_copy.
+ * Composite (:61-109), per pixel (x, y): untouched for refl.a <= 0.001f or depth >= 1.  Otherwise
+ *   u = ((float)x + 0.5f) / (float)W, v likewise with y and H; d = normalize(u * 2 - 1, v * 2 - 1, -1);
+ *   w.r = (M[0][r] * d.x + M[1][r] * d.y) + M[2][r] * d.z with M[c][r] = inv_view[4 c + r] (columns, as GLSL and Godot store a mat4;
+ *   only the 3x3 is read); w = normalize(w);
+ *   NdotV = max((n.x * -w.x + n.y * -w.y) + n.z * -w.z, 0.001f); s = clamp(1 - NdotV, 0, 1); s2 = s * s; s4 = s2 * s2; s5 = s4 * s;
+ *   fresnel = f0 + (1 - f0) * s5 (the lighting kernel's Schlick has no clamp and three channels: not that one);
+ *   t = clamp(roughness / roughness_threshold, 0, 1); rw = 1 - (t * t) * (3 - 2 * t);
+ *   blend = clamp(((fresnel * rw) * refl.a) * intensity, 0, 1); rgb.k = colour.k * (1 - blend) + refl.k * blend; alpha is kept.
+ *
+ * The calls are ordered on the context's stream, take MRT_FLAG_ASYNC, and touch neither the scene, the tuner, the tile schedule nor
+ * mrt_stats.  W == 0 or H == 0: MRT_OK, nothing written.  MRT_ERR_INVALID before any device work, in this order: a null context; a
+ * null params; a null image, each in the order of the call's arguments (d_denoised is optional); struct_size not
+ * sizeof(mrt_denoise_params); an unknown flag; an unknown normal_kind; a non-finite parameter (the three sigmas, blend_factor,
+ * depth_threshold, roughness_threshold, intensity, f0, the sixteen of inv_view, in this order); W * H * 32 overflowing; an output
+ * that is an image read across pixels (d_out == d_reflection in the spatial call; d_history, d_color or d_denoised equal to
+ * d_reflection, d_depth or d_normal_roughness in the fused call).  Then MRT_ERR_PENDING while a dispatch is pending. */
+enum { MRT_NORMAL_OCTAHEDRAL = 0, MRT_NORMAL_WORLD = 1 };
+typedef struct mrt_denoise_params {        /* 112 bytes; the defaults of rt_reflection_effect.h:43-53 in brackets */
+	uint32_t struct_size;                  /* sizeof(mrt_denoise_params) */
+	uint32_t normal_kind;                  /* MRT_NORMAL_* */
+	uint32_t has_history;                  /* 0: the first frame */
+	int32_t kernel_radius;                 /* [2] */
+	float depth_sigma, normal_sigma, color_sigma;   /* [1, 128, 4] */
+	float blend_factor;                    /* [0.1] the current frame's share */
+	float depth_threshold;                 /* [0.1] */
+	float roughness_threshold;             /* [0.3] */
+	float intensity;                       /* [1] */
+	float f0;                              /* [0.04] */
+	float inv_view[16];                    /* camera to world, column-major */
+} mrt_denoise_params;
+int mrt_denoise_spatial(mrt_ctx *ctx, const mrt_denoise_params *params, uint32_t W, uint32_t H, const float *d_reflection,
+		const float *d_depth, const float *d_normal_roughness, float *d_out, uint32_t flags);
+int mrt_denoise_temporal(mrt_ctx *ctx, const mrt_denoise_params *params, uint32_t W, uint32_t H, const float *d_current,
+		const float *d_history, float *d_out, uint32_t flags);
+int mrt_composite_reflections(mrt_ctx *ctx, const mrt_denoise_params *params, uint32_t W, uint32_t H, const float *d_reflection,
+		const float *d_depth, const float *d_normal_roughness, float *d_color, uint32_t flags);
+/* The three in one launch: d_history = temporal(spatial(d_reflection), d_history) in place, d_color composited with the new history
+ * in place; the filtered pixel never leaves registers unless d_denoised (optional, 4 floats per pixel) asks for it.  Bit-identical to
+ * mrt_denoise_spatial -> mrt_denoise_temporal(d_out = d_history) -> mrt_composite_reflections(d_reflection = d_history), and free of
+ * hazards: only the raw reflection and the guides are read across pixels, and nothing read across pixels is written. */
+int mrt_resolve_reflections(mrt_ctx *ctx, const mrt_denoise_params *params, uint32_t W, uint32_t H, const float *d_reflection,
+		const float *d_depth, const float *d_normal_roughness, float *d_history, float *d_color, float *d_denoised, uint32_t flags);
+/* The guides of this project's own pipeline: record i of d_hits (the primary cast's mrt_hit32) and row i of d_rows (its
+ * mrt_surface64): d_depth[i] = 1.0f for a miss (prim_id == -1), else min(t * inv_depth_range, 1); d_normal_roughness[4 i ..] =
+ * {row.normal, row.roughness}, for MRT_NORMAL_WORLD (a miss's row is all zero).  Flags: MRT_FLAG_ASYNC.  count == 0: MRT_OK.
+ * MRT_ERR_INVALID in this order: a null context, d_hits, d_rows, d_depth, d_normal_roughness; an unknown flag; a non-finite
+ * inv_depth_range; count * 64 overflowing.  Then MRT_ERR_PENDING. */
+int mrt_reflection_guides(mrt_ctx *ctx, const mrt_hit32 *d_hits, const mrt_surface64 *d_rows, uint64_t count, float inv_depth_range,
+		float *d_depth, float *d_normal_roughness, uint32_t flags);
+
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to
  * tokens written by a cast with MRT_FLAG_TOKEN_OUT: mrt_hit32 records (mrt_host_hit44 with

@@ -56,6 +56,14 @@ hipError_t launch_image_to_rgba8(const float *rgba, uint64_t count, uint8_t *rgb
 // the running mean of progressive frames (accum_kernel.h): kind = an MRT_ACCUM_SRC_*, first: n_prior == 0, inv = 1 / (n_prior + 1)
 hipError_t launch_accumulate(int kind, bool first, const void *source, uint64_t count, uint32_t mode, float white, float inv, float *accum,
 		uint8_t *rgba8, hipStream_t stream);
+// the reflection effect's image passes (denoise_kernel.h): fused = spatial, temporal and composite in one launch (out optional)
+namespace dn { struct DenoiseArgs; }
+hipError_t launch_denoise(bool fused, const dn::DenoiseArgs &a, const float *reflection, const float *depth, const float *guide, float *history,
+		float *color, float *out, hipStream_t stream);
+hipError_t launch_denoise_temporal(const dn::DenoiseArgs &a, const float *current, const float *history, float *out, hipStream_t stream);
+hipError_t launch_composite(const dn::DenoiseArgs &a, const float *reflection, const float *depth, const float *guide, float *color, hipStream_t stream);
+hipError_t launch_reflection_guides(const mrt_hit32 *hits, const mrt_surface64 *rows, uint64_t count, float inv_depth_range, float *depth,
+		float *guide, hipStream_t stream);
 // ---- device_build.hip
 hipError_t grow_arena(BuildArena *arena, size_t need, hipStream_t stream); // hipErrorOutOfMemory: no allocation, the arena is empty
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);

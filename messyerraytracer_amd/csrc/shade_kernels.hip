@@ -1,6 +1,6 @@
 // shade_kernels.hip — gfx950 kernels of the shading passes over hit records: the resolve to shading surfaces (plain and textured), the
 // direct light and the path tracer's per-pixel state (the lighting and the step also with a resident panorama), the renderer's
-// channels with the two image passes, the running mean of progressive frames, and the packing of shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
+// channels with the two image passes, the running mean of progressive frames, the reflection effect's image passes, and the packing of shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
 // source_common.h with the walks of kernels.hip, and are compiled apart from them.  The arithmetic is the canonical form of DESIGN.md
 // ("Arithmetic"), as in kernels.hip.
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "panorama.h"
 #include "channels.h"
 #include "accum.h"
+#include "denoise.h"
 #include "lane_map.h"
 
 namespace mrt {
@@ -24,6 +25,7 @@ namespace mrt {
 
 #include "path_frame_kernel.h"
 #include "accum_kernel.h"
+#include "denoise_kernel.h"
 #include "surface_tex_kernel.h"
 #include "surface_kernel.h"
 #include "light_kernel.h"
@@ -75,6 +77,36 @@ hipError_t launch_accumulate(int kind, bool first, const void *source, uint64_t 
 	dispatch([&](auto KIND, auto FIRST) { e = launch_per_entry<true>(accumulate_kernel<KIND, FIRST>, count, stream, source, count, mode, white, inv, accum, rgba8); },
 			Among<(int)MRT_ACCUM_SRC_RGBA, (int)MRT_ACCUM_SRC_LIT, (int)MRT_ACCUM_SRC_PATH_STATE>{kind}, Among<false, true>{first});
 	return e;
+}
+// the reflection effect's image passes (denoise_kernel.h), called from denoise.hip
+hipError_t launch_denoise(bool fused, const dn::DenoiseArgs &a, const float *reflection, const float *depth, const float *guide, float *history,
+		float *color, float *out, hipStream_t stream)
+{
+	const uint64_t tiles_x = ((uint64_t)a.w + DN_TILE - 1) / DN_TILE, tiles = tiles_x * (((uint64_t)a.h + DN_TILE - 1) / DN_TILE);
+	if (tiles == 0) return hipSuccess;
+	if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	const auto *r = reinterpret_cast<const dn::Px4 *>(reflection), *g = reinterpret_cast<const dn::Px4 *>(guide);
+	auto *h = reinterpret_cast<dn::Px4 *>(history), *c = reinterpret_cast<dn::Px4 *>(color), *o = reinterpret_cast<dn::Px4 *>(out);
+	if (fused) hipLaunchKernelGGL(denoise_kernel<true>, dim3((uint32_t)tiles), dim3(DN_TILE * DN_TILE), 0, stream, a, (uint32_t)tiles_x, r, depth, g, h, c, o);
+	else hipLaunchKernelGGL(denoise_kernel<false>, dim3((uint32_t)tiles), dim3(DN_TILE * DN_TILE), 0, stream, a, (uint32_t)tiles_x, r, depth, g, h, c, o);
+	return hipGetLastError();
+}
+hipError_t launch_denoise_temporal(const dn::DenoiseArgs &a, const float *current, const float *history, float *out, hipStream_t stream)
+{
+	const uint64_t count = (uint64_t)a.w * a.h;
+	return launch_per_entry<true>(temporal_kernel, count, stream, a, count, reinterpret_cast<const dn::Px4 *>(current),
+			reinterpret_cast<const dn::Px4 *>(history), reinterpret_cast<dn::Px4 *>(out));
+}
+hipError_t launch_composite(const dn::DenoiseArgs &a, const float *reflection, const float *depth, const float *guide, float *color, hipStream_t stream)
+{
+	const uint64_t count = (uint64_t)a.w * a.h;
+	return launch_per_entry<true>(composite_kernel, count, stream, a, count, reinterpret_cast<const dn::Px4 *>(reflection), depth,
+			reinterpret_cast<const dn::Px4 *>(guide), reinterpret_cast<dn::Px4 *>(color));
+}
+hipError_t launch_reflection_guides(const mrt_hit32 *hits, const mrt_surface64 *rows, uint64_t count, float inv_depth_range, float *depth,
+		float *guide, hipStream_t stream)
+{
+	return launch_per_entry<true>(guides_kernel, count, stream, hits, rows, count, inv_depth_range, depth, reinterpret_cast<dn::Px4 *>(guide));
 }
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream)
 {
