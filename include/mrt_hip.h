@@ -144,7 +144,7 @@ typedef struct mrt_stats {
 	uint64_t tri_tests;          /* filled only when options.count_visits != 0 */
 	uint64_t bvh_nodes_visited;  /* idem: wide-node (internal) visits          */
 	uint64_t hits;               /* idem                                        */
-	float last_trace_ms;         /* hipEvent time of the trace kernel(s)        */
+	float last_trace_ms;         /* hipEvent time of the trace kernel(s); this and the three times below: 0 after an ASYNC cast */
 	float last_sort_ms;          /* key+sort+gather kernels (0 if coherent)     */
 	float last_h2d_ms, last_d2h_ms;
 	uint32_t last_kernel_launches;
@@ -190,7 +190,9 @@ enum {
 	                                      uint32_t[2 * count].                                                */
 	MRT_FLAG_ASYNC          = 1u << 7  /* mrt_cast / mrt_cast_grid with device-resident rays and hits: queue the
 	                                      work on the context's stream and return without waiting (no timing
-	                                      stats).  Order later work on that stream, or mrt_synchronize().
+	                                      stats, no kernel named).  Inputs are read and outputs complete in
+	                                      stream order (mrt_set_stream): order later work on that stream, or
+	                                      mrt_synchronize().
 	                                      Lets a frame loop keep the device busy while the host queues the
 	                                      exchange of the previous frame (sharded.py).                        */
 };
@@ -276,7 +278,19 @@ uint32_t mrt_version(void);
  * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set, 22 mrt_panorama,
  * 24 mrt_channel_out, 26 mrt_accum_state, 28 mrt_denoise_params (0 for anything else). */
 uint32_t mrt_struct_size(uint32_t which);
-/* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream). */
+/* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream): from here on it is "the context's stream".
+ * What a caller that shares its stream may rely on (tests/test_caller_stream_gpu.py holds every entry point to it):
+ *   - every device call of the library is ordered on that stream.  A call reads its device inputs in stream order (what the caller
+ *     queued on the stream before the call has been written), and its device outputs are complete in stream order (for what the
+ *     caller queues on the stream after it), with no wait on the host: a whole frame of MRT_FLAG_ASYNC calls and the caller's own
+ *     copies between them is one queue.  Several contexts may share one stream, each reading what the other wrote.
+ *   - a call with MRT_FLAG_ASYNC returns without waiting for the stream once its work buffers have their size (the first call of a
+ *     size, and the first cast of a grid under a tile schedule, may allocate and wait); so does mrt_expand_tokens.  The calls that
+ *     change what is resident -- mrt_build_scene_device, mrt_refit_scene, mrt_refit_two_level_scene, mrt_update_instances_device,
+ *     mrt_upload_shade_data, mrt_upload_textures, mrt_upload_panorama -- wait for the stream: they return after everything queued
+ *     before them, their own work done; an ASYNC call queued before one of them sees the old state, the next call the new.
+ *   - mrt_set_stream itself waits for the stream it leaves, so work queued there is complete when it returns, and the old stream
+ *     may be destroyed once the context has left it.  MRT_ERR_PENDING with a dispatch pending (mrt_submit): the stream is unchanged. */
 int mrt_set_stream(mrt_ctx *ctx, void *hip_stream);
 int mrt_synchronize(mrt_ctx *ctx);
 
@@ -1383,6 +1397,15 @@ int mrt_get_stats(mrt_ctx *ctx, mrt_stats *out);
  * reference counterpart (the reference prints its pipeline choice, gpu_ray_caster.cpp:654-671); bench.py uses it to
  * accept committed counter passes only for the very kernel a run used. */
 const char *mrt_last_kernel_variant(mrt_ctx *ctx);
+/* How this context has used the tile schedule of grid casts, counted on the host as casts are queued (no device work, no wait; no
+ * reference counterpart): out[0] = casts planned under the schedule, out[1] = those of them launched in a measured order (a
+ * finished sort was found when the cast was queued; else the plain order), out[2] = sorts of a measuring frame's costs queued on
+ * the schedule's side stream.  For tests and tools: which of these a cast took changes its launch order only, never a record. */
+int mrt_schedule_counts(mrt_ctx *ctx, uint64_t out[3]);
+/* Debug: the order in which the last sorted mrt_cast of `count` rays walked them (out[k] = the ray walked k-th: the radix sort's
+ * permutation of 0 .. count - 1 by the rays' sort keys), copied on the context's stream; waits for it.  MRT_ERR_INVALID when no sorted cast
+ * of at least `count` rays has run.  Reads only.  The order decides no record; tests hold it to the cast it belongs to. */
+int mrt_debug_sort_order(mrt_ctx *ctx, uint32_t *out, uint64_t count);
 /* 1 if this build contains the kernel.  MRT_KERNEL_PACKET_QUAD (the four-wide packet walk: held to the oracle, not faster
  * than the default) is compiled only into builds made with MRT_WITH_QUAD=1 (messyerraytracer_amd/build.py); mrt_create
  * with it returns MRT_ERR_UNSUPPORTED otherwise. */

@@ -161,6 +161,18 @@ def build_driver(name: str, force: bool = False) -> str:
     return exe
 
 
+STREAM_GATE = os.path.join(HERE, "libmrt_stream_gate.so")
+STREAM_GATE_SRC = os.path.join(HERE, "test_support", "stream_gate.cpp")  # (in the package: build() needs nothing of tests/)
+
+
+def build_stream_gate(force: bool = False) -> str:
+    """The tests' own caller of the HIP runtime (test_support/stream_gate.cpp: a stream, a timed gate and copies on it; no
+    kernel), linked against the runtime the library links.  The package never loads it."""
+    if force or _stale(STREAM_GATE, [STREAM_GATE_SRC]):
+        _run([_hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", STREAM_GATE_SRC, "-o", STREAM_GATE, "-pthread"], "stream gate build")
+    return STREAM_GATE
+
+
 def _driver(name: str):
     def build(force: bool = False) -> str:
         return build_driver(name, force)

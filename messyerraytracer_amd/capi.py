@@ -41,7 +41,7 @@ SYMBOLS = [
     "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
     "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
-    "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
+    "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_schedule_counts", "mrt_debug_sort_order", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
     "mrt_group_create", "mrt_group_destroy", "mrt_group_size", "mrt_group_context", "mrt_group_last_error", "mrt_group_row_block",
     "mrt_group_upload_scene", "mrt_group_upload_two_level_scene", "mrt_group_cast_grid",
 ]
@@ -311,6 +311,8 @@ def load():
                                          C.c_void_p, C.c_void_p, C.c_void_p]
     L.mrt_morton_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.mrt_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
+    L.mrt_schedule_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mrt_debug_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.mrt_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
     L.mrt_device_free.argtypes = [C.c_void_p, C.c_void_p]
     L.mrt_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -1058,6 +1060,18 @@ class Context:
         s = Stats()
         self._chk(self.L.mrt_get_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in Stats._fields_}
+
+    def schedule_counts(self) -> dict:
+        """mrt_schedule_counts: casts planned under the tile schedule, those launched in a measured order, sorts queued"""
+        c = (C.c_uint64 * 3)()
+        self._chk(self.L.mrt_schedule_counts(self.h, c))
+        return dict(scheduled=int(c[0]), ordered=int(c[1]), sorts=int(c[2]))
+
+    def debug_sort_order(self, count) -> np.ndarray:
+        """mrt_debug_sort_order: the order in which the last sorted cast of `count` rays walked them"""
+        out = np.zeros(count, dtype=np.uint32)
+        self._chk(self.L.mrt_debug_sort_order(self.h, _np(out), count))
+        return out
 
     def _token_array(self, count):
         """host array for `count` hit tokens: uint32[count] (flat scene) or uint32[count, 2] (two-level: {triangle, instance})"""

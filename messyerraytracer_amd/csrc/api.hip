@@ -371,7 +371,10 @@ int mrt_build_scene_device(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris,
 	if (n_tris < 2) {
 		// a one-triangle scene has no radix tree: the host path wraps the root leaf (scene_prep.cpp)
 		mrt_tri64 t;
-		if (on_device) HIP_TRY(ctx, hipMemcpy(&t, tris, sizeof(t), hipMemcpyDeviceToHost)); else t = tris[0];
+		if (on_device) { // read in stream order: the caller's work on the context's stream may still be writing the triangle
+			HIP_TRY(ctx, hipMemcpyAsync(&t, tris, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		} else t = tris[0];
 		float verts[12] = { t.v0[0], t.v0[1], t.v0[2], 0.0f, t.v0[0] + t.edge1[0], t.v0[1] + t.edge1[1], t.v0[2] + t.edge1[2], 0.0f,
 			t.v0[0] + t.edge2[0], t.v0[1] + t.edge2[1], t.v0[2] + t.edge2[2], 0.0f };
 		mrt_bvh_node32 nodes[2]; uint32_t prim = 0, used = 0;
@@ -757,6 +760,23 @@ int mrt_get_stats(mrt_ctx *ctx, mrt_stats *out)
 {
 	if (!ctx || !out) return MRT_ERR_INVALID;
 	*out = ctx->stats;
+	return MRT_OK;
+}
+
+int mrt_schedule_counts(mrt_ctx *ctx, uint64_t out[3])
+{
+	if (!ctx || !out) return MRT_ERR_INVALID;
+	for (int k = 0; k < 3; k++) out[k] = ctx->sched_counts[k];
+	return MRT_OK;
+}
+
+int mrt_debug_sort_order(mrt_ctx *ctx, uint32_t *out, uint64_t count)
+{
+	if (!ctx || !out) return MRT_ERR_INVALID;
+	if (!ctx->idx_out.ptr || count == 0 || count > ctx->idx_out.cap / 4) return fail(ctx, MRT_ERR_INVALID, "no sorted cast of that many rays");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(out, ctx->idx_out.ptr, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return MRT_OK;
 }
 

@@ -68,6 +68,17 @@ void note_queued(mrt_ctx *ctx, uint32_t kernel)
 	std::snprintf(ctx->queued_variant, sizeof(ctx->queued_variant), "%s", mrt::last_trace_variant());
 }
 
+// The end of an ASYNC cast: no kernel is named (mrt_stats.last_kernel, mrt_last_kernel_variant) -- which one does the work of a
+// batch declared coherent is known only once the stream has been waited for -- and there is no timing: the four times are 0, not
+// those of an earlier blocking cast.
+int queued_async(mrt_ctx *ctx)
+{
+	ctx->stats.last_trace_ms = ctx->stats.last_sort_ms = ctx->stats.last_h2d_ms = ctx->stats.last_d2h_ms = 0.0f;
+	ctx->stats.last_kernel = 0;
+	ctx->last_variant[0] = '\0';
+	return MRT_OK;
+}
+
 // A cast whose rays are made in the kernel launches its source family's instantiation of the same lane kernels: the family's launcher
 // (mrt::launch_source<S>), its parameters (an S) and which of its three sources.  launch_planned and launch_lane pass it through.
 struct SourceLaunch {
@@ -307,7 +318,7 @@ int run_source_cast(mrt_ctx *ctx, mrt::Entry entry, int src, int mode, mrt::Trac
 	const SourceLaunch sl{&mrt::launch_source<S>, &s, src};
 	int rc = launch_planned(ctx, c, r, p, &sl);
 	if (rc) return rc;
-	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
+	if (flags & MRT_FLAG_ASYNC) return queued_async(ctx);
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->stats.last_h2d_ms = ctx->stats.last_sort_ms = ctx->stats.last_d2h_ms = 0.0f;
 	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
@@ -494,7 +505,7 @@ int mrt_cast(mrt_ctx *ctx, const void *rays, void *hits, uint64_t count, uint32_
 	}
 	int rc = enqueue_cast(ctx, mrt::ENTRY_CAST, rays, hits_dev ? hits : nullptr, count, query_mask, mode, flags, &d_hits);
 	if (rc) return rc;
-	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; } // queued on the context's stream; no timing
+	if (flags & MRT_FLAG_ASYNC) return queued_async(ctx); // queued on the context's stream; no timing
 	if (!hits_dev) {
 		HIP_TRY(ctx, hipMemcpyAsync(hits, d_hits, count * hit_stride(ctx, flags, mode), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
@@ -561,7 +572,7 @@ int mrt_cast_grid(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t
 	p.out_fmt = out_format(ctx, flags, mode);
 	const mrt::CastRequest r{mrt::ENTRY_GRID, p.count, flags, mode, grid_w, grid_h, y0, p.rows};
 	if ((rc = launch_planned(ctx, plan(ctx, r), r, p))) return rc;
-	if (flags & MRT_FLAG_ASYNC) { ctx->stats.last_kernel = 0; return MRT_OK; }
+	if (flags & MRT_FLAG_ASYNC) return queued_async(ctx);
 	if (!hits_dev) {
 		HIP_TRY(ctx, hipMemcpyAsync(hits, d_hits, p.count * hs, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));

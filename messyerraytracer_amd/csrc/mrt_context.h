@@ -140,6 +140,7 @@ struct mrt_ctx {
 	// per grid and cast mode, for the last few of them (mrt::GridStates): how it is cast, and its tile schedule in sched[same index]
 	mrt::GridStates grids;
 	TileSchedule sched[mrt::GridStates::kCount];
+	uint64_t sched_counts[3] = {0, 0, 0}; // mrt_schedule_counts: casts under the schedule, those launched in a measured order, sorts queued
 	char queued_variant[96] = "", queued_alt_variant[96] = "", last_variant[96] = ""; // instantiation names (mrt_last_kernel_variant)
 	uint32_t queued_kernel = 0, queued_alt_kernel = 0; bool queued_detect = false; // what the last cast put on the stream
 	// host-array pipeline (cast_host_pipelined): copy streams and per-chunk events, created on first use

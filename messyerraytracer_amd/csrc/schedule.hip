@@ -124,6 +124,8 @@ int schedule_grid(mrt_ctx *ctx, const mrt::CastPlan &c, mrt::TraceParams &p)
 	p.tile_sched = order; p.sched_hdr = hdr; p.n_slots_max = order ? s.n_slots_max : 0u;
 	p.tile_cost = s.measuring ? (uint32_t *)s.cost[cur].ptr : nullptr;
 	p.tile_unit = unit; p.n_units = n_units;
+	ctx->sched_counts[0]++;
+	if (order) ctx->sched_counts[1]++;
 	return MRT_OK;
 }
 
@@ -150,6 +152,7 @@ int schedule_sort(mrt_ctx *ctx)
 	HIP_TRY(ctx, hipEventRecord(s.ready[cur], s.side));
 	s.have_order[cur] = true;
 	s.gen++;
+	ctx->sched_counts[2]++;
 	if (ctx->knobs.dump) { // diagnosis: what the schedule was made of (tools/bench_resolutions.py with MRT_SCHED_DUMP=1)
 		std::vector<uint32_t> c(s.n_units);
 		uint32_t hdr[3] = {0, 0, 0};

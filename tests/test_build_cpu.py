@@ -55,11 +55,26 @@ def test_compile_pool_is_not_sized_by_the_cpu_count(monkeypatch):
     assert "cpu_count" not in inspect.getsource(build)
 
 
+def test_stream_gate_is_the_tests_alone():
+    """messyerraytracer_amd/test_support/stream_gate.cpp holds no kernel and lies outside tests/ (build() must not need that
+    directory); nothing of the package but build.py (which compiles it) names it, nor bench.py."""
+    with open(build.STREAM_GATE_SRC) as f:
+        src = f.read()
+    assert "__global__" not in src and "hipLaunchKernelGGL" not in src and "<<<" not in src
+    assert os.path.dirname(build.STREAM_GATE) == build.HERE
+    assert os.path.dirname(build.STREAM_GATE_SRC) == os.path.join(build.HERE, "test_support")
+    root = os.path.dirname(build.HERE)
+    for path in glob.glob(os.path.join(build.HERE, "*.py")) + [os.path.join(root, "bench.py")]:
+        if os.path.basename(path) != "build.py":
+            with open(path) as f:
+                assert "stream_gate" not in f.read(), path
+
+
 def test_public_build_names():
     for name in ("build_lib", "build_host_test", "build_host_cpu_test", "build_host_tlas_test", "build_policy_test",
                  "build_shadow_policy_test", "build_reflection_policy_test", "build_hemisphere_policy_test", "build_bounce_policy_test",
                  "build_instance_math_test", "build_build_rules_test", "build_shade_data_test", "build_light_data_test", "build_path_data_test",
-                 "build_texture_data_test", "build_lane_map_test"):
+                 "build_texture_data_test", "build_lane_map_test", "build_stream_gate"):
         f = getattr(build, name)
         params = inspect.signature(f).parameters
         assert "force" in params and params["force"].default is False, name

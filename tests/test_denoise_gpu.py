@@ -302,6 +302,23 @@ ROOM_ORIGIN, ROOM_FWD, ROOM_FOV = (0.0, 3.0, 4.6), (0.0, -0.35, -1.0), 70.0
 FAR = F(1e30)
 
 
+def reflected_frame(rays, hits, reflection_hits, shade, lights, env, inv_range, p, hist, mask=None):
+    """One reflected frame of the W x H grid in numpy from the primary rays and their records: the rows, the lit frame (mask: the primary shadow mask
+    [lights, n] or None), the reflection rays, reflection_hits(rrays) -> their records, their rows and lit frame, the guides, and
+    Dn.resolve with the history `hist` (None on the first frame).  Returns a dict of every stage."""
+    hit = hits["prim_id"] != -1
+    rows = expected(rays, hits, shade)[0]
+    lit = Lg.shade_linear(rows, hit, hit_point(rays, hits), rays["direction"], lights, mask, env)[0]
+    rrays = R.reflection_rays(rays["direction"], hit_point(rays, hits), hits["normal"], hit, FAR)[0]
+    rhits = reflection_hits(rrays)
+    rhit = rhits["prim_id"] != -1
+    rrows = expected(rrays, rhits, shade)[0]
+    rlit = Lg.shade_linear(rrows, rhit, hit_point(rrays, rhits), rrays["direction"], lights, None, env)[0]
+    depth, guide = Dn.guides(hits, rows, inv_range)
+    _, new_hist, color = Dn.resolve(p, rlit.reshape(H, W, 4), depth.reshape(H, W), guide.reshape(H, W, 4), hist, lit.reshape(H, W, 4))
+    return dict(hit=hit, rows=rows, lit=lit, rrays=rrays, rhits=rhits, rrows=rrows, rlit=rlit, depth=depth, guide=guide, hist=new_hist, color=color)
+
+
 def test_guides_and_a_reflected_frame_end_to_end(built):
     """6, 7. synth.room() at 64 x 48: primary cast -> resolve -> light -> reflection cast -> resolve -> light -> mrt_reflection_guides
     -> mrt_resolve_reflections, all on the device, two frames, against the same chain in numpy on the device's records.  The primary cast
@@ -333,26 +350,19 @@ def test_guides_and_a_reflected_frame_end_to_end(built):
             p = Dn.params(normal_kind=Dn.NORMAL_WORLD, has_history=frame > 0, roughness_threshold=0.9, intensity=2.0)
             color, refl = d_lit.read().copy(), d_rlit.read().copy()
             Dn.resolve_reflections(ctx, p, W, H, d_rlit.p, d_depth.p, d_guide.p, d_hist.p, d_lit.p)
-            # the same chain in numpy
+            # the same chain in numpy, on the device's records
             hits = dev.get(d_hits, n, T.HIT32)
-            hit = hits["prim_id"] != -1
+            want = reflected_frame(rays, hits, lambda rrays: dev.get(d_rhits, n, T.HIT32), shade, lights, env, inv_range, p, want_hist)
+            hit, lit, depth, guide = want["hit"], want["lit"], want["depth"], want["guide"]
             assert hit.any() and (~hit).any()                                              # misses included
-            rows = expected(rays, hits, shade)[0]
-            same(dev.get(d_rows, n, T.SURFACE64), rows)
-            lit = Lg.shade_linear(rows, hit, hit_point(rays, hits), rays["direction"], lights, None, env)[0]
+            same(dev.get(d_rows, n, T.SURFACE64), want["rows"])
             np.testing.assert_array_equal(words(color.reshape(-1, 4)), words(lit))
-            rrays = R.reflection_rays(rays["direction"], hit_point(rays, hits), hits["normal"], hit, FAR)[0]
-            same(dev.get(d_rrays, n, T.RAY32), rrays)
-            rhits = dev.get(d_rhits, n, T.HIT32)
-            rhit = rhits["prim_id"] != -1
-            rrows = expected(rrays, rhits, shade)[0]
-            rlit = Lg.shade_linear(rrows, rhit, hit_point(rrays, rhits), rrays["direction"], lights, None, env)[0]
-            np.testing.assert_array_equal(words(refl.reshape(-1, 4)), words(rlit))
-            depth, guide = Dn.guides(hits, rows, inv_range)
+            same(dev.get(d_rrays, n, T.RAY32), want["rrays"])
+            np.testing.assert_array_equal(words(refl.reshape(-1, 4)), words(want["rlit"]))
             np.testing.assert_array_equal(words(d_depth.read().reshape(-1)), words(depth))
             np.testing.assert_array_equal(words(d_guide.read().reshape(-1, 4)), words(guide))
             assert (depth[~hit] == 1).all() and (depth[hit] < 1).any() and (guide[~hit] == 0).all()
-            _, want_hist, want_color = Dn.resolve(p, rlit.reshape(H, W, 4), depth.reshape(H, W), guide.reshape(H, W, 4), want_hist, lit.reshape(H, W, 4))
+            want_hist, want_color = want["hist"], want["color"]
             same_floats(d_hist.read(), want_hist, f"frame {frame} history")
             same_floats(d_lit.read(), want_color, f"frame {frame} colour")
             assert (words(want_color) != words(lit.reshape(H, W, 4))).any()                 # reflections were blended in
