@@ -276,7 +276,7 @@ uint32_t mrt_version(void);
  * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light, 6 mrt_material,
  * 7 mrt_shade_data, 8 mrt_surface64, 9 mrt_surface_out, 11 mrt_shade_light, 12 mrt_environment, 13 mrt_light_out,
  * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set, 22 mrt_panorama,
- * 24 mrt_channel_out, 26 mrt_accum_state, 28 mrt_denoise_params (0 for anything else). */
+ * 24 mrt_channel_out, 26 mrt_accum_state, 28 mrt_denoise_params, 30 mrt_gbuffer (0 for anything else). */
 uint32_t mrt_struct_size(uint32_t which);
 /* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream): from here on it is "the context's stream".
  * What a caller that shares its stream may rely on (tests/test_caller_stream_gpu.py holds every entry point to it):
@@ -1372,6 +1372,70 @@ int mrt_resolve_reflections(mrt_ctx *ctx, const mrt_denoise_params *params, uint
  * inv_depth_range; count * 64 overflowing.  Then MRT_ERR_PENDING. */
 int mrt_reflection_guides(mrt_ctx *ctx, const mrt_hit32 *d_hits, const mrt_surface64 *d_rows, uint64_t count, float inv_depth_range,
 		float *d_depth, float *d_normal_roughness, uint32_t flags);
+/* ---- the reflection effect's first pass from a rasteriser's G-buffer: RTReflectionEffect pass 1
+ * (src/gpu/shaders/rt_reflections.comp.glsl:276-332) as it runs inside a rasterised frame.  A host that rasterises has no hit records
+ * and no primary rays; it has a depth buffer and a normal-roughness buffer.  mrt_cast_gbuffer_reflections makes the reflection ray of
+ * every pixel from those two in the trace kernel and traces it closest-hit; mrt_reflection_image turns the rays' records into the
+ * RGBA reflection image whose alpha is the confidence that mrt_denoise_*, mrt_composite_reflections and mrt_resolve_reflections key on.
+ * GLSL pins the rounding of mat4 * vec4, normalize, reflect and texture nowhere, so the pass is stated here as fp32 operations in a
+ * fixed order, one rounding each, nothing contracted (messyerraytracer_amd/gbuffer.py restates it in numpy, bit for bit).
+ *
+ * Whole frames only: W x H pixels, pixel (x, y) at texel i = y * W + x of both images; count = W * H.  fp32 images as the denoise
+ * calls take them (a packed depth or a 10-bit normal buffer is the host's to convert); depth in [0, 1] with 1 = far, as the shader
+ * expects it (no reverse-Z).  The shader samples at texel centres, uv = (pixel + 0.5) / size: a texel fetch, no UV arithmetic enters the
+ * reads.  normalize, max and the two normal kinds are those of the denoise passes above (decode_guide: n and roughness of a texel).
+ *
+ * The ray of pixel (x, y), with depth = d_depth[i] and (n, roughness) = decode_guide(normal_kind, d_normal_roughness[4 i ..]):
+ *   No ray if !(depth < 1.0f): sky.  (The shader's depth >= 1, except that a NaN depth is sky here too.  The normal texel of a sky
+ *   pixel is not looked at.)  No ray if !(roughness <= roughness_threshold) (a NaN roughness: no ray).
+ *   u = ((float)x + 0.5f) / (float)W, v likewise with y and H (the composite's expression); cx = u * 2 - 1, cy = v * 2 - 1.
+ *   q.r = ((P[0][r] * cx + P[1][r] * cy) + P[2][r] * depth) + P[3][r], r = 0 .. 3, with P[c][r] = inv_projection[4 c + r] (columns,
+ *   as GLSL and Godot store a mat4).  view = (q.0 / q.3, q.1 / q.3, q.2 / q.3): three divisions, no reciprocal.
+ *   world.r = ((V[0][r] * view.x + V[1][r] * view.y) + V[2][r] * view.z) + V[3][r], r = 0 .. 2, with V[c][r] = inv_view[4 c + r]; row 3
+ *   of inv_view is not read.  cam = (V[3][0], V[3][1], V[3][2]).  d = normalize(world - cam).
+ *   k = 2 * ((n.x * d.x + n.y * d.y) + n.z * d.z); dir = d - k * n per component (GLSL reflect; not renormalised).
+ *   org = world + n * 0.01f, t_min = 0, t_max = max_distance.
+ *   The normal is NOT turned towards the viewer: the shader does not turn it, and a rasteriser's normals face the camera.  This
+ *   differs from mrt_cast_reflections, which faces a record's geometric normal against the incoming ray because a cast can hit a back
+ *   face (there the unturned offset would start the ray behind the surface).
+ *   No ray either if any of the six floats of org and dir is not finite (a singular inv_projection gives q.3 = 0; a zero octahedral
+ *   texel decodes to NaNs).  The shader has no such test; it keeps garbage out of the walk.
+ * A pixel without a ray gets what mrt_cast_reflections gives a record without one: the placeholder Ray(0, (0,1,0), 0, 0) in
+ * d_out_rays and its record (t = 0, prim_id = -1) in d_out_hits; it never walks the tree.
+ * d_out_hits / d_out_rays (optional) are mrt_cast's layouts: with them the frame goes on through mrt_resolve_surfaces,
+ * mrt_cast_shadows, mrt_light_surfaces or a second mrt_cast_reflections unchanged.
+ * Flags: MRT_FLAG_ASYNC.  The checks come in the order of every record-driven cast: MRT_ERR_INVALID for a null context; an unknown
+ * flag; then, in this order, a null descriptor, d_depth, d_normal_roughness or d_out_hits; struct_size not sizeof(mrt_gbuffer); an
+ * unknown normal_kind; a non-finite entry of inv_projection, then of inv_view; roughness_threshold, then max_distance, not finite or
+ * not > 0; W * H * 32 overflowing.  Then MRT_ERR_NO_SCENE, MRT_ERR_PENDING.  After those W == 0 or H == 0 is MRT_OK with nothing written.
+ * The kernel is chosen as for mrt_cast_reflections of W * H records (the plain lane kernel below 2^16 pixels, the persistent ones
+ * from there); mrt_last_kernel_variant names it "trace_gbuffer_lane_kernel<13>", "trace_gbuffer_persistent_kernel<13, 8, false>", ...
+ *
+ * The image (:321-331), pixel i with the ray's record h = d_hits[i]:
+ *   h.prim_id == -1 (a miss, and every pixel without a ray): {0, 0, 0, 0}; the G-buffer is not looked at.
+ *   Otherwise d and roughness as above, recomputed from the G-buffer (no sky, roughness or finiteness test: the record says there was
+ *   a ray); conf = 1 - roughness / roughness_threshold;
+ *   without d_lit: ndotl = max((h.n.x * -d.x + h.n.y * -d.y) + h.n.z * -d.z, 0); grey = 0.5f + 0.5f * ndotl; {grey, grey, grey, conf}
+ *   (the shader calls it a placeholder "to be enhanced with material data");
+ *   with d_lit (4 floats per record, what mrt_light_surfaces writes for the reflection records): {lit.r, lit.g, lit.b, conf}.
+ * Ordered on the context's stream like the denoise calls; touches neither the scene, the tuner, the tile schedule nor mrt_stats.
+ * W == 0 or H == 0: MRT_OK, nothing written.  MRT_ERR_INVALID before any device work, in this order: a null context, descriptor,
+ * d_hits or d_reflection; an unknown flag; then the descriptor's checks as above from d_depth on.  Then MRT_ERR_PENDING.
+ * Not taken: row bands, packed input formats, the shader's unused frame_count jitter. */
+typedef struct mrt_gbuffer {               /* 160 bytes */
+	uint32_t struct_size;                  /* sizeof(mrt_gbuffer) */
+	uint32_t normal_kind;                  /* MRT_NORMAL_* */
+	float inv_projection[16];              /* clip to camera, column-major; clip z = depth */
+	float inv_view[16];                    /* camera to world, column-major */
+	float roughness_threshold;             /* finite, > 0 (rt_reflection_effect.h: 0.3) */
+	float max_distance;                    /* finite, > 0: t_max of every ray */
+	const float *d_depth;                  /* W * H */
+	const float *d_normal_roughness;       /* W * H * 4 */
+} mrt_gbuffer;
+int mrt_cast_gbuffer_reflections(mrt_ctx *ctx, const mrt_gbuffer *gbuffer, uint32_t W, uint32_t H, mrt_hit32 *d_out_hits,
+		mrt_ray32 *d_out_rays, uint32_t query_mask, uint32_t flags);
+int mrt_reflection_image(mrt_ctx *ctx, const mrt_gbuffer *gbuffer, uint32_t W, uint32_t H, const mrt_hit32 *d_hits, const float *d_lit,
+		float *d_reflection, uint32_t flags);
 
 /* ---- hit tokens -> hit records (no reference counterpart: the reference is single-device).
  * The packed->Intersection readback conversion of gpu_ray_caster.cpp:442-456 applied to

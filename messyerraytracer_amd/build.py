@@ -15,7 +15,7 @@ OBJ = os.path.join(HERE, "_obj")  # object files, their dependency files and the
 # passes over hit records, prep_kernels.hip = what prepares a scene or a cast; an edit to one is compiled apart from the others.
 SOURCES = ["kernels.hip", "shade_kernels.hip", "prep_kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip",
            "device_build.hip", "refit.hip", "tlas_device.hip", "surface.hip", "texture.hip", "lighting.hip", "path.hip", "panorama.hip", "channels.hip", "accum.hip", "denoise.hip",
-           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/accum_data.cpp", "host/denoise_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
+           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/accum_data.cpp", "host/denoise_data.cpp", "host/gbuffer_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
 # implicitly (-ffp-contract=off), so every result is unchanged.
@@ -37,6 +37,7 @@ DRIVERS = {
     "reflection_policy_test": (["host/reflection_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
     "hemisphere_policy_test": (["host/hemisphere_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
     "bounce_policy_test": (["host/bounce_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
+    "gbuffer_policy_test": (["host/gbuffer_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
     "instance_math_test": (["host/instance_math_test.cpp"], CPU, False),  # instance_math.h, shared by the host path and the device TLAS build
     "build_rules_test": (["host/build_rules_test.cpp"], CPU, False),  # build_rules.h, shared by the host and the device scene builders
     "build_rules_test_san": (["host/build_rules_test.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
@@ -52,6 +53,9 @@ DRIVERS = {
                                                                                          "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
     "denoise_data_test": (["host/denoise_data_test.cpp", "host/denoise_data.cpp"], CPU, False),  # denoise.h, shared with the kernels
     "denoise_data_test_san": (["host/denoise_data_test.cpp", "host/denoise_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
+                                                                                             "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
+    "gbuffer_data_test": (["host/gbuffer_data_test.cpp", "host/gbuffer_data.cpp"], CPU, False),  # gbuffer.h, shared with the kernels
+    "gbuffer_data_test_san": (["host/gbuffer_data_test.cpp", "host/gbuffer_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
                                                                                              "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
     "lane_map_test": (["host/lane_map_test.cpp"], LANE + ["-O2"], False),  # lane_map.h
     "lane_map_test_san": (["host/lane_map_test.cpp"], LANE + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
@@ -188,6 +192,7 @@ build_shadow_policy_test = _driver("shadow_policy_test")
 build_reflection_policy_test = _driver("reflection_policy_test")
 build_hemisphere_policy_test = _driver("hemisphere_policy_test")
 build_bounce_policy_test = _driver("bounce_policy_test")
+build_gbuffer_policy_test = _driver("gbuffer_policy_test")
 build_instance_math_test = _driver("instance_math_test")
 build_shade_data_test = _driver("shade_data_test")
 build_light_data_test = _driver("light_data_test")
@@ -210,6 +215,11 @@ def build_accum_data_test(force: bool = False, sanitize: bool = False) -> str:
 def build_denoise_data_test(force: bool = False, sanitize: bool = False) -> str:
     """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
     return build_driver("denoise_data_test_san" if sanitize else "denoise_data_test", force)
+
+
+def build_gbuffer_data_test(force: bool = False, sanitize: bool = False) -> str:
+    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
+    return build_driver("gbuffer_data_test_san" if sanitize else "gbuffer_data_test", force)
 
 
 def build_lane_map_test(force: bool = False, sanitize: bool = False) -> str:

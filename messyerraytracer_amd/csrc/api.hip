@@ -169,6 +169,7 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 24: return (uint32_t)sizeof(mrt_channel_out); // (23: not a struct)
 		case 26: return (uint32_t)sizeof(mrt_accum_state); // (25: not a struct)
 		case 28: return (uint32_t)sizeof(mrt_denoise_params); // (27: not a struct)
+		case 30: return (uint32_t)sizeof(mrt_gbuffer); // (29: not a struct)
 		default: return 0u;
 	}
 }

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "mrt_context.h"
+#include "gbuffer.h"
 
 namespace {
 
@@ -707,6 +708,23 @@ int mrt_cast_grid_bounce(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, u
 	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the entries; the kernel regenerates the incoming ray from p.cam itself)
 	return cast_bounce(ctx, mrt::ENTRY_GRID_BOUNCE, mrt::SRC_BOUNCE_GRID, p, d_hits, p.count, y0 * grid_w, desc, d_out_hits, d_out_rays,
 			query_mask, flags);
+}
+
+// Reflection rays from a rasteriser's G-buffer (gbuffer_kernel.h): a whole frame, count = W * H; the checks in the family's order.
+int mrt_cast_gbuffer_reflections(mrt_ctx *ctx, const mrt_gbuffer *gbuffer, uint32_t W, uint32_t H, mrt_hit32 *d_out_hits,
+		mrt_ray32 *d_out_rays, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (int rc = source_cast_check(ctx, false, flags, "unknown flag for a G-buffer reflection cast",
+			[&] { return mrt::gb::cast_invalid(gbuffer, W, H, d_out_hits); })) return rc;
+	mrt::TraceParams p;
+	base_params(ctx, p);
+	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the pixels; no ray is read)
+	mrt::GBufferParams s;
+	mrt::gb::fill_params(gbuffer, W, H, d_out_rays, s);
+	p.hits = d_out_hits; p.count = (uint64_t)W * H; p.query_mask = query_mask;
+	p.out_fmt = mrt::OUT_HIT32;
+	return run_source_cast(ctx, mrt::ENTRY_GBUFFER_REFLECTION, mrt::SRC_GBUFFER, MRT_MODE_NEAREST, p, s, flags);
 }
 
 } // extern "C"

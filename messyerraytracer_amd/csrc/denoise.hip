@@ -1,10 +1,12 @@
 // denoise.hip — the reflection effect's image passes on the device (include/mrt_hip.h: mrt_denoise_spatial, mrt_denoise_temporal,
-// mrt_composite_reflections, mrt_resolve_reflections, mrt_reflection_guides).  The refusals, the clamped radius and the w_spatial
-// table are host/denoise_data.cpp and denoise.h; the kernels are denoise_kernel.h (shade_kernels.hip).  Like the other image passes,
+// mrt_composite_reflections, mrt_resolve_reflections, mrt_reflection_guides, and mrt_reflection_image of a G-buffer cast).  The
+// refusals, the clamped radius and the w_spatial table are host/denoise_data.cpp and denoise.h (the image's: host/gbuffer_data.cpp and
+// gbuffer.h); the kernels are denoise_kernel.h and gbuffer_image_kernel.h (shade_kernels.hip).  Like the other image passes,
 // a call waits or queues on the context's stream, writes nothing to mrt_stats and reads no scene, tuner or schedule state.
 #include <hip/hip_runtime.h>
 #include "mrt_context.h"
 #include "denoise.h"
+#include "gbuffer.h"
 
 namespace {
 
@@ -63,6 +65,18 @@ int mrt_reflection_guides(mrt_ctx *ctx, const mrt_hit32 *d_hits, const mrt_surfa
 		return fail(ctx, MRT_ERR_INVALID, why);
 	BEGIN_PASS(ctx, count);
 	HIP_TRY(ctx, mrt::launch_reflection_guides(d_hits, d_rows, count, inv_depth_range, d_depth, d_normal_roughness, ctx->stream));
+	return finish_call(ctx, flags);
+}
+
+int mrt_reflection_image(mrt_ctx *ctx, const mrt_gbuffer *gbuffer, uint32_t W, uint32_t H, const mrt_hit32 *d_hits, const float *d_lit,
+		float *d_reflection, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	if (const char *why = mrt::gb::image_invalid(gbuffer, W, H, d_hits, d_reflection, flags)) return fail(ctx, MRT_ERR_INVALID, why);
+	BEGIN_PASS(ctx, (uint64_t)W * H);
+	mrt::GBufferParams s;
+	mrt::gb::fill_params(gbuffer, W, H, nullptr, s);
+	HIP_TRY(ctx, mrt::launch_reflection_image(s, d_hits, d_lit, d_reflection, ctx->stream));
 	return finish_call(ctx, flags);
 }
 

@@ -19,6 +19,7 @@
 #include "mrt_internal.h"
 #include "launch_policy.h"
 #include "lane_map.h"
+#include "gbuffer.h"
 
 namespace mrt {
 
@@ -30,6 +31,7 @@ namespace mrt {
 #include "reflection_kernel.h"
 #include "hemisphere_kernel.h"
 #include "bounce_kernel.h"
+#include "gbuffer_kernel.h"
 
 // ---- the traversal kernel: one lane = one ray -------------------------------------
 // LDS: per-lane stack, entry d of lane l at dword d*64 + l of the wave's region
@@ -52,8 +54,8 @@ __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 #include "two_level_kernel.h"
 
 // ---- record-driven casts (source_common.h): the lane kernels a non-coherent batch can get, with a ray source -------------------
-// S = the source family's parameters (its own kernel argument: ShadowParams and HemiParams are large, and a union of the four would
-// grow every family's argument block), SRC one of its three sources, ANY_HIT a mode its source_entry accepts.  The bodies are the
+// S = the source family's parameters (its own kernel argument: ShadowParams and HemiParams are large, and a union of the five would
+// grow every family's argument block), SRC one of its sources, ANY_HIT a mode its source_entry accepts.  The bodies are the
 // ones of trace_lane_kernel, trace_two_level_kernel and trace_lane_persistent_kernel, included with SRC set.
 template <class S, int SRC, bool ANY_HIT>
 __global__ __launch_bounds__(MRT_WG) void trace_source_lane_kernel(const TraceParams p, const S s)
@@ -195,5 +197,6 @@ template hipError_t launch_source<ShadowParams>(const TraceParams &, const void 
 template hipError_t launch_source<ReflectParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<HemiParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<BounceParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+template hipError_t launch_source<GBufferParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 
 } // namespace mrt

@@ -180,7 +180,8 @@ void tune_record(GridTune &t, float trace_ms)
 // Record-driven casts (shadow, reflection, hemisphere, bounce: record_cast_entry): count rays made in the kernel from resident hit records
 // -- pixels * lights any-hit shadow rays, one closest-hit mirror or bounce ray per record, pixels * samples hemisphere rays in either
 // mode -- in entry order (which already groups nearby origins, though hemisphere and bounce rays are far less coherent than the
-// others).  One plan for all of them, since neither the family nor the mode enters it:
+// others).  A G-buffer reflection cast (ENTRY_GBUFFER_REFLECTION: one mirror ray per pixel from depth and normal buffers, in pixel order)
+// is the same kind of batch.  One plan for all of them, since neither the family nor the mode enters it:
 //   - never sorted: the rays never exist in memory, so there is nothing to sort; no detection and no tiling;
 //   - the lane kernels as for any incoherent batch: the plain one below 2^16 rays (small batches on emptier waves), the persistent ones
 //     from 2^16 (8-, 4- or 2-wide, two-level scenes their own);

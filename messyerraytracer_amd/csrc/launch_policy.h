@@ -52,11 +52,14 @@ struct SceneFacts {
 // unsorted, non-coherent closest-hit batch).  ENTRY_HEMISPHERE / ENTRY_GRID_HEMISPHERE: mrt_cast_hemisphere / mrt_cast_grid_hemisphere,
 // count = pixels * samples (cosine-weighted hemisphere rays made in the kernel: an unsorted, non-coherent batch in either mode).
 // ENTRY_BOUNCE / ENTRY_GRID_BOUNCE: mrt_cast_bounce / mrt_cast_grid_bounce, count = records (the path tracer's bounce rays made in the
-// kernel: an unsorted, non-coherent closest-hit batch)
+// kernel: an unsorted, non-coherent closest-hit batch).  ENTRY_GBUFFER_REFLECTION: mrt_cast_gbuffer_reflections, count = pixels of the
+// frame (mirror rays made in the kernel from a rasteriser's depth and normal buffers: the plan of a reflection cast of as many rays)
 enum Entry : uint32_t { ENTRY_CAST, ENTRY_SUBMIT, ENTRY_CHUNK, ENTRY_GRID, ENTRY_TILED, ENTRY_SHADOW, ENTRY_GRID_SHADOW,
-	ENTRY_REFLECTION, ENTRY_GRID_REFLECTION, ENTRY_HEMISPHERE, ENTRY_GRID_HEMISPHERE, ENTRY_BOUNCE, ENTRY_GRID_BOUNCE };
+	ENTRY_REFLECTION, ENTRY_GRID_REFLECTION, ENTRY_HEMISPHERE, ENTRY_GRID_HEMISPHERE, ENTRY_BOUNCE, ENTRY_GRID_BOUNCE,
+	ENTRY_GBUFFER_REFLECTION };
 inline bool ray_entry(Entry e) { return e <= ENTRY_CHUNK; } // rays from an array, through enqueue_cast
-inline bool record_cast_entry(Entry e) { return e >= ENTRY_SHADOW && e <= ENTRY_GRID_BOUNCE; } // rays made in the kernel from hit records
+// rays made in the kernel, from hit records or (the last) from a G-buffer
+inline bool record_cast_entry(Entry e) { return e >= ENTRY_SHADOW && e <= ENTRY_GBUFFER_REFLECTION; }
 
 struct CastRequest {
 	Entry entry = ENTRY_CAST;

@@ -18,7 +18,7 @@ bool quad_kernel_built();
 hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream);
 // record-driven casts (source_common.h): S = the family's parameter struct (instantiated in kernels.hip for ShadowParams, ReflectParams,
-// HemiParams and BounceParams), params = an S, src = one of SourceFamily<S>'s sources, any_hit = a mode the family has; blocks != 0: the
+// HemiParams, BounceParams and GBufferParams), params = an S, src = one of SourceFamily<S>'s sources, any_hit = a mode the family has; blocks != 0: the
 // persistent kernel (next_ray .. leaf_wait as launch_trace_persistent)
 template <class S>
 hipError_t launch_source(const TraceParams &p, const void *params, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
@@ -64,6 +64,8 @@ hipError_t launch_denoise_temporal(const dn::DenoiseArgs &a, const float *curren
 hipError_t launch_composite(const dn::DenoiseArgs &a, const float *reflection, const float *depth, const float *guide, float *color, hipStream_t stream);
 hipError_t launch_reflection_guides(const mrt_hit32 *hits, const mrt_surface64 *rows, uint64_t count, float inv_depth_range, float *depth,
 		float *guide, hipStream_t stream);
+// the reflection image of a G-buffer cast (gbuffer_image_kernel.h): s = the frame and its G-buffer (out_rays and max_distance unused)
+hipError_t launch_reflection_image(const GBufferParams &s, const mrt_hit32 *hits, const float *lit, float *out, hipStream_t stream);
 // ---- device_build.hip
 hipError_t grow_arena(BuildArena *arena, size_t need, hipStream_t stream); // hipErrorOutOfMemory: no allocation, the arena is empty
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);

@@ -172,11 +172,13 @@ struct TraceParams {
 enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, SRC_SHADOW_GRID = 3,
 	SRC_REFLECT_RAY32 = 4, SRC_REFLECT_HOST = 5, SRC_REFLECT_GRID = 6,
 	SRC_HEMI_RAY32 = 7, SRC_HEMI_HOST = 8, SRC_HEMI_GRID = 9,
-	SRC_BOUNCE_RAY32 = 10, SRC_BOUNCE_HOST = 11, SRC_BOUNCE_GRID = 12 };
+	SRC_BOUNCE_RAY32 = 10, SRC_BOUNCE_HOST = 11, SRC_BOUNCE_GRID = 12,
+	SRC_GBUFFER = 13 };
 constexpr bool shadow_source(int src) { return src >= SRC_SHADOW_RAY32 && src <= SRC_SHADOW_GRID; }
 constexpr bool reflection_source(int src) { return src >= SRC_REFLECT_RAY32 && src <= SRC_REFLECT_GRID; }
 constexpr bool hemisphere_source(int src) { return src >= SRC_HEMI_RAY32 && src <= SRC_HEMI_GRID; }
 constexpr bool bounce_source(int src) { return src >= SRC_BOUNCE_RAY32 && src <= SRC_BOUNCE_GRID; }
+constexpr bool gbuffer_source(int src) { return src == SRC_GBUFFER; }
 // the result of an entry is one byte (1 = no occluder, or no ray): every shadow cast, and a hemisphere cast in any-hit mode
 constexpr bool lit_output(int src, bool any_hit) { return shadow_source(src) || (hemisphere_source(src) && any_hit); }
 enum ShadowKind : uint32_t { SHADOW_OFF = 0, SHADOW_DIRECTIONAL = 1, SHADOW_POINT = 2 }; // OFF: cast_shadows == 0 (lit)
@@ -228,6 +230,19 @@ struct BounceParams {
 	HemiJump jump;             // (A, C) of draw first_draw
 };
 
+// ---- reflection rays from a rasteriser's G-buffer (gbuffer_kernel.h, gbuffer.h): one closest-hit ray per pixel of a whole frame -----
+// Entry i of a G-buffer cast is pixel (i % w, i / w); TraceParams::count = w * h, hits = the output records (OUT_HIT32); rays is not
+// read.  The matrices are part of the kernel argument: uniform, read with constant indices before the walk (scalar loads).
+struct GBufferParams {
+	const float *depth;        // w * h
+	const void *guide;         // w * h normal-roughness texels, 4 floats each
+	void *out_rays;            // optional: the rays made, mrt_ray32
+	uint32_t w, h, normal_kind; // MRT_NORMAL_*
+	float roughness_threshold;
+	float max_distance;        // t_max of every ray
+	float inv_projection[16], inv_view[16]; // column-major, as mrt_gbuffer gives them
+};
+
 // ---- shading surfaces (surface_kernel.h): one mrt_surface64 row per hit record, nothing walked ---------------------------------
 // Record i of a resolve is entry i; TraceParams::count = records, rays = the incoming rays as for reflections (or the grid).  The
 // resident shade data (shade_data.h): n_tris rows of 64 bytes, n_materials rows of 48; an absent per-triangle array is a bit not set
@@ -261,7 +276,8 @@ constexpr uint32_t CHANNELS_ROW = (1u << MRT_CHANNEL_NORMAL) | (1u << MRT_CHANNE
 constexpr uint32_t CHANNELS_MATERIAL = (1u << MRT_CHANNEL_NORMAL) | (1u << MRT_CHANNEL_ALBEDO);
 
 // What the one launcher and the one set of kernels need to know of a source family, by its parameter struct: its three sources
-// (RaySrc values: they are printed in mrt_last_kernel_variant), the modes it has (a family with one does not print it) and its name.
+// (RaySrc values: they are printed in mrt_last_kernel_variant; a family with one source names it three times), the modes it has (a
+// family with one does not print it) and its name.
 template <class S> struct SourceFamily;
 template <> struct SourceFamily<ShadowParams> {
 	static constexpr int ray32 = SRC_SHADOW_RAY32, host = SRC_SHADOW_HOST44, grid = SRC_SHADOW_GRID;
@@ -282,6 +298,11 @@ template <> struct SourceFamily<BounceParams> {
 	static constexpr int ray32 = SRC_BOUNCE_RAY32, host = SRC_BOUNCE_HOST, grid = SRC_BOUNCE_GRID;
 	static constexpr bool any_hit = false, nearest = true;
 	static constexpr const char *name = "bounce";
+};
+template <> struct SourceFamily<GBufferParams> {
+	static constexpr int ray32 = SRC_GBUFFER, host = SRC_GBUFFER, grid = SRC_GBUFFER;
+	static constexpr bool any_hit = false, nearest = true;
+	static constexpr const char *name = "gbuffer";
 };
 
 // host-side preparation (scene_prep.cpp)

@@ -15,6 +15,7 @@
 #include "channels.h"
 #include "accum.h"
 #include "denoise.h"
+#include "gbuffer.h"
 #include "lane_map.h"
 
 namespace mrt {
@@ -31,6 +32,7 @@ namespace mrt {
 #include "light_kernel.h"
 #include "path_kernel.h"
 #include "channel_kernel.h"
+#include "gbuffer_image_kernel.h"
 
 // ---- launch wrappers (called from surface.hip, lighting.hip and path.hip); src = a SurfaceSrc; t / pano null: none resident --------
 hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams *t, int src, hipStream_t stream)
@@ -107,6 +109,13 @@ hipError_t launch_reflection_guides(const mrt_hit32 *hits, const mrt_surface64 *
 		float *guide, hipStream_t stream)
 {
 	return launch_per_entry<true>(guides_kernel, count, stream, hits, rows, count, inv_depth_range, depth, reinterpret_cast<dn::Px4 *>(guide));
+}
+// the reflection image of a G-buffer cast (gbuffer_image_kernel.h), called from denoise.hip; lit may be null
+hipError_t launch_reflection_image(const GBufferParams &s, const mrt_hit32 *hits, const float *lit, float *out, hipStream_t stream)
+{
+	const uint64_t count = (uint64_t)s.w * s.h;
+	return launch_per_entry<true>(reflection_image_kernel, count, stream, s, count, hits, reinterpret_cast<const dn::Px4 *>(lit),
+			reinterpret_cast<dn::Px4 *>(out));
 }
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream)
 {

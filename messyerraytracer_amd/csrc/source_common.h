@@ -1,9 +1,9 @@
-// source_common.h — what every record-driven ray source shares (shadow_kernel.h, reflection_kernel.h, hemisphere_kernel.h,
-// bounce_kernel.h).  Included by kernels.hip (inside namespace mrt, after device_common.h, before the four family headers) and, for
-// record_surface, by shade_kernels.hip.
+// source_common.h — what every ray source shares (shadow_kernel.h, reflection_kernel.h, hemisphere_kernel.h, bounce_kernel.h, and
+// gbuffer_kernel.h, whose entries are pixels of a G-buffer, not records).  Included by kernels.hip (inside namespace mrt, after
+// device_common.h, before the family headers) and, for record_surface, by shade_kernels.hip.
 //
-// A source family is a parameter struct (mrt_internal.h: ShadowParams, ReflectParams, HemiParams, BounceParams; SourceFamily<S> names
-// its three sources and its modes) plus one overload of
+// A source family is a parameter struct (mrt_internal.h: ShadowParams, ReflectParams, HemiParams, BounceParams, GBufferParams;
+// SourceFamily<S> names its sources and its modes) plus one overload of
 //   template <int SRC, bool ANY_HIT> bool source_entry(const TraceParams &p, const S &s, uint64_t g, RayRegs &r)
 // which makes the ray of entry g (true: r is a ray to walk) or stores the result of an entry without a ray (false: the lit byte, or
 // the placeholder's record; nothing walks).  The lane kernels, persistent or not, and the two-level kernels take (S, SRC, ANY_HIT) as
