@@ -119,8 +119,8 @@
 #endif
 #define MRT_QUAD_CLOBBERS MRT_ROWS_CLOBBERS, "s68", "s69", "s70", "s71", "v61", "v62", "m0"
 
-// counting builds: the stack's high-water mark (s39 is free during a push)
-#define MRT_QUAD_CNT_P "v_readfirstlane_b32 s39, %[spA]\n s_max_u32 %[cntp], %[cntp], s39\n"
+// counting builds: the stack's high-water mark (s39 is free during a push; the s_nop: MRT_ROWS_CNT_P, packet_rows_kernel.h)
+#define MRT_QUAD_CNT_P "s_nop 0\n v_readfirstlane_b32 s39, %[spA]\n s_max_u32 %[cntp], %[cntp], s39\n"
 
 // push {group A's mask, group B's mask, ref, -} = s[40:41], s[42:43], s38
 #define MRT_Q_PUSH(CNT_P)                                                                                             \

@@ -689,7 +689,10 @@ struct CullRegs {
 #define MRT_ROWS_T_PRE "s_memtime s[64:65]\n s_waitcnt lgkmcnt(0)\n"
 #define MRT_ROWS_T_POST "s_memtime s[66:67]\n s_waitcnt lgkmcnt(0)\n s_sub_u32 s64, s66, s64\n s_add_u32 %[cntw], %[cntw], s64\n"
 #define MRT_ROWS_CNT_N "s_add_u32 %[cntn], %[cntn], 1\n"
-#define MRT_ROWS_CNT_P "v_readfirstlane_b32 s52, %[spA]\n s_max_u32 %[cntp], %[cntp], s52\n" /* counting builds: the stack's high-water mark */
+// counting builds: the stack's high-water mark.  It follows the push's v_add_u32 of sp directly, and a VGPR written by the VALU needs one
+// wait state before v_readfirstlane reads it (nothing pads the inside of an asm string): without the s_nop some waves read the
+// pointer from before the push and the mark came out one entry low (tests/test_deep_trees_gpu.py)
+#define MRT_ROWS_CNT_P "s_nop 0\n v_readfirstlane_b32 s52, %[spA]\n s_max_u32 %[cntp], %[cntp], s52\n"
 #define MRT_ROWS_CNT_T "s_add_u32 %[cntt], %[cntt], 1\n"
 
 // wave-uniform operands come back from an asm block as SGPRs; this tells the compiler they still are
