@@ -41,6 +41,47 @@
 // s[40:41] / s[42:43] (group B), s[44:45] (any lane hit left), s[46:47] (left-is-nearer flags),
 // s[50:51] / s[58:59] (the pushed child's masks)
 // v50..v59 temporaries, v60 the never-read destination of the far-child prefetches.
+//
+// ---- the pop that fetches first (round 6; -DMRT_ROWS_POPFETCH=1, NOT the default) ----------------------------------
+// Measured (profiles/r19_pop_fetch.json): 1.6 % fewer wave cycles, about 1 % of C3's kernel time in each of two
+// sessions, less than the builds' own spread: the gate for a gain fails, so the default build keeps the pop that reads its entry
+// first and is the same machine code as before.  The form, for whoever measures it again:
+// top (s68, the first scalar above the fixed ones; the kernel has 72) shadows ONE field of the stack, which stays in the LDS entry
+// for entry and byte for byte as it was.  Invariant inside each walk block: top == the ref field of the entry at sp - entry size.
+// Every block is entered with an empty stack (only the sentinel below sp: rows_walks_and_records sets sp so), so top starts as
+// 0x7FFFFFFF; a push copies the far ref (s53) into it: one scalar instruction.  A pop runs in this order:
+//   1. cur = top; top == 0x7FFFFFFF -> leave the walk: the sentinel is never read from the LDS;
+//   2. s_lshl / s_load_dwordx16 of row top into s[20:35]: the fetch is in flight from here.  Every path into a pop has finished
+//      with the row registers (the leaf path tests RA_FLAGS before it branches, the miss path has made its masks);
+//   3. the LDS reads: the masks of the entry popped and the ref word of the entry below it, the new top (it always exists: the
+//      sentinel lies at the bottom).  DS offsets are unsigned, so the lower entry's address goes to a temporary, both reads use
+//      positive offsets from it, then sp is set;
+//   4. ONE s_waitcnt lgkmcnt(0): scalar loads and LDS reads share the counter, scalar loads return out of order, and the child
+//      prefetches into s64 / s65 may still be on their way (the triangle test writes those registers): only 0 is safe, and it
+//      covers the row, the entry and the prefetches;
+//   5. v_readfirstlane of the mask words and of the new top (LDS results, behind the wait: no VALU write precedes them), and on at
+//      the label BEHIND the loop head's own fetch and wait.
+// So the LDS round trip and the hand-overs to the scalar unit run under the row fetch's latency instead of in front of it.  The
+// any-hit early finish leaves with entries still on the stack, as before (top is dead from there).  The four-wide walk keeps the
+// old pop: its loop head issues a second load by the row's kind, and it is an experiment kept for the record.
+#ifndef MRT_ROWS_POPFETCH
+#define MRT_ROWS_POPFETCH 0
+#endif
+#define RA_TOP "s68"
+#if MRT_ROWS_POPFETCH
+#define MRT_ROWS_TOP_CLOBBER "s68",
+#define MRT_ROWS_TOP_EMPTY "s_mov_b32 s68, 0x7fffffff\n"   /* on entry to a block: the stack is empty, its top is the sentinel */
+#define MRT_ROWS_TOP_PUSHED "s_mov_b32 s68, s53\n"         /* the entry being pushed (far ref s53) is the stack's top */
+#define MRT_ROWS_HAVE "L_have_%=:\n"                       /* behind the loop head's fetch: the row is in s[20:35] */
+// (the pop at the sentinel waits for nothing: no prefetch may land in s64 / s65 once the compiler owns them again)
+#define MRT_ROWS_EXIT_WAIT "s_waitcnt vmcnt(0) lgkmcnt(0)\n"
+#else
+#define MRT_ROWS_TOP_CLOBBER
+#define MRT_ROWS_TOP_EMPTY ""
+#define MRT_ROWS_TOP_PUSHED ""
+#define MRT_ROWS_HAVE ""
+#define MRT_ROWS_EXIT_WAIT "s_waitcnt vmcnt(0)\n"
+#endif
 #define RA_LMINX "s20"
 #define RA_LMINY "s21"
 #define RA_LMINZ "s22"
@@ -122,6 +163,7 @@
 	"s_cselect_b32 s53, " RS##_RREF ", " RS##_LREF "\n"                  /* far  */                                  \
 	"s_cselect_b32 " MRT_OP("cur", P) ", " RS##_LREF ", " RS##_RREF "\n" /* near */                                  \
 	"s_cselect_b64 s[58:59], s[54:55], vcc\n"        /* lanes that hit the far child  */                           \
+	MRT_ROWS_TOP_PUSHED \
 	"s_cselect_b64 " RS##_MASK ", vcc, s[54:55]\n"    /* lanes that hit the near child */                           \
 	"v_mov_b32 v51, s53\n"                                                                                          \
 	"v_mov_b32 v52, s58\n"                                                                                          \
@@ -268,26 +310,56 @@
 	MRT_ROWS_TRI_STEP(P, RS, POPBIT, CNT_T, ANYHIT_CODE)                                                             \
 	"L_" P "done_%=:\n"
 
-// pop of packet P (slow path): the entry {ref, -, mask} into V0..V3, then cur and the mask register
-#define MRT_ROWS_POP_ISSUE(P, POPBITNO, V0123)                                                                      \
-	"s_bitcmp1_b32 %[ev], " POPBITNO "\n"                                                                           \
-	"s_cbranch_scc0 L_" P "pi_%=\n"                                                                                 \
-	"v_add_u32 " MRT_OP("sp", P) ", -16, " MRT_OP("sp", P) "\n"                                                     \
-	"ds_read_b128 " V0123 ", " MRT_OP("sp", P) "\n"                                                                 \
-	"L_" P "pi_%=:\n"
-#define MRT_ROWS_POP_TAKE(P, RS, POPBITNO, V0, V2, V3)                                                               \
-	"s_bitcmp1_b32 %[ev], " POPBITNO "\n"                                                                           \
-	"s_cbranch_scc0 L_" P "pt_%=\n"                                                                                 \
-	"v_readfirstlane_b32 " MRT_OP("cur", P) ", " V0 "\n"                                                            \
-	"v_readfirstlane_b32 " RS##_MASKLO ", " V2 "\n"                                                                  \
-	"v_readfirstlane_b32 " RS##_MASKHI ", " V3 "\n"                                                                  \
-	"L_" P "pt_%=:\n"
+// The pop of the one-packet loop (16-byte entries {ref, -, mask}), entered with an event in %[ev]: the pop bit (bit 0), or the any-hit
+// finish (cur is the sentinel already).  Falls out at the end of the walk; else goes on at L_loop, or (fetching first) at L_have.
+#if MRT_ROWS_POPFETCH
+// "the pop" above: cur = top, out at the sentinel, the fetch of row top (T_PRE / T_POST: the counting builds' clock), the popped
+// entry's mask into v[52:53] and the ref of the entry below it into v50 under it, one wait, three hand-overs
+#define MRT_ROWS_POP1(T_PRE, T_POST)                                                                                \
+	"s_bitcmp1_b32 %[ev], 0\n"                                                                                      \
+	"s_mov_b32 %[ev], 0\n"                                                                                          \
+	"s_cbranch_scc0 L_exit_%=\n"                                                                                    \
+	"s_mov_b32 %[curA], " RA_TOP "\n"                                                                               \
+	"s_cmp_eq_u32 " RA_TOP ", 0x7fffffff\n"                                                                         \
+	"s_cbranch_scc1 L_exit_%=\n"                                                                                    \
+	"s_lshl_b32 s52, " RA_TOP ", 6\n"                                                                               \
+	T_PRE                                                                                                           \
+	"s_load_dwordx16 s[20:35], %[rows], s52\n"                                                                      \
+	"v_add_u32 v50, -32, %[spA]\n"                           /* the entry below the one popped */                  \
+	"ds_read_b64 v[52:53], v50 offset:24\n"                                                                         \
+	"ds_read_b32 v50, v50\n"                                                                                        \
+	"v_add_u32 %[spA], -16, %[spA]\n"                                                                               \
+	"s_waitcnt lgkmcnt(0)\n"                                                                                        \
+	T_POST                                                                                                          \
+	"v_readfirstlane_b32 s60, v52\n"                                                                                \
+	"v_readfirstlane_b32 s61, v53\n"                                                                                \
+	"v_readfirstlane_b32 " RA_TOP ", v50\n"                                                                         \
+	"s_branch L_have_%=\n"                                                                                          \
+	"L_exit_%=:\n"
+#else
+#define MRT_ROWS_POP1(T_PRE, T_POST)                                                                                \
+	"s_bitcmp1_b32 %[ev], 0\n"                                                                                      \
+	"s_cbranch_scc0 L_Api_%=\n"                                                                                     \
+	"v_add_u32 %[spA], -16, %[spA]\n"                                                                               \
+	"ds_read_b128 v[50:53], %[spA]\n"                                                                               \
+	"L_Api_%=:\n"                                                                                                   \
+	"s_waitcnt lgkmcnt(0)\n"                                                                                        \
+	"s_bitcmp1_b32 %[ev], 0\n"                                                                                      \
+	"s_cbranch_scc0 L_Apt_%=\n"                                                                                     \
+	"v_readfirstlane_b32 %[curA], v50\n"                                                                            \
+	"v_readfirstlane_b32 s60, v52\n"                                                                                \
+	"v_readfirstlane_b32 s61, v53\n"                                                                                \
+	"L_Apt_%=:\n"                                                                                                   \
+	"s_mov_b32 %[ev], 0\n"                                                                                          \
+	"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                            \
+	"s_cbranch_scc1 L_loop_%=\n"
+#endif
 
 #define MRT_ROWS_CLOBBERS                                                                                             \
 	"vcc", "scc", "s20", "s21", "s22", "s23", "s24", "s25", "s26", "s27", "s28", "s29", "s30", "s31", "s32", "s33", \
 	"s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", \
 	"s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", \
-	"s66", "s67", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60"
+	"s66", "s67", MRT_ROWS_TOP_CLOBBER "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60"
 
 // operands of one packet (S = its PacketRegs)
 #define MRT_ROWS_OUT(P, S)                                                                                            \
@@ -315,21 +387,18 @@ struct PacketRegs {
 #define MRT_ROWS_LOOP1(CNT_N, CNT_T, CNT_P, T_PRE, T_POST, ANYHIT_CODE, BX, BY, BZ)                                          \
 	asm volatile(                                                                                                   \
 		"s_mov_b64 s[60:61], %[maskA]\n"                                                                            \
+		MRT_ROWS_TOP_EMPTY \
 		"L_loop_%=:\n"                                                                                              \
 		"s_lshl_b32 s52, %[curA], 6\n"                                                                              \
 		T_PRE                                                                                                       \
 		"s_load_dwordx16 s[20:35], %[rows], s52\n"                                                                  \
 		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
 		T_POST                                                                                                      \
+		MRT_ROWS_HAVE \
 		MRT_ROWS_STEP("A", RA, "1", CNT_N, CNT_T, CNT_P, ANYHIT_CODE, BX, BY, BZ)                                   \
 		"s_cmp_eq_u32 %[ev], 0\n"                                                                                   \
 		"s_cbranch_scc1 L_loop_%=\n"                                                                                \
-		MRT_ROWS_POP_ISSUE("A", "0", "v[50:53]")                                                                    \
-		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
-		MRT_ROWS_POP_TAKE("A", RA, "0", "v50", "v52", "v53")                                                        \
-		"s_mov_b32 %[ev], 0\n"                                                                                      \
-		"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                        \
-		"s_cbranch_scc1 L_loop_%=\n"                                                                                \
+		MRT_ROWS_POP1(T_PRE, T_POST)                                                                                \
 		"s_waitcnt vmcnt(0)\n"               /* no prefetch may land in v60 once the compiler owns it again */     \
 		"s_mov_b64 %[maskA], s[60:61]\n"                                                                            \
 		: MRT_ROWS_OUT(A, a), [ev] "+s"(ev), [cntn] "+s"(cnt_n), [cntt] "+s"(cnt_t), [cntw] "+s"(cnt_w), [cntp] "+s"(sp_max) \
@@ -405,16 +474,57 @@ struct PacketRegs {
 	"v_mov_b32 v54, s53\n"
 #endif
 
+// The pop of the shared walks (32-byte entries {group A's mask, group B's mask, ref, -}): leaves through L_exit at the sentinel.
+// WITH_FETCH: what the culling loop issues beside the popped row's scalar fetch (the vector copy of the row); RELOAD: the label the
+// pop that reads its entry first goes on at (the loop head, or the culling loop's request for that copy in front of it).
+#if MRT_ROWS_POPFETCH
+// "the pop" above: goes on at L_have with the popped row in s[20:35], its masks in s[60:63], cur = its ref, top = the ref of the entry below
+#define MRT_ROWSW_POP(WITH_FETCH, RELOAD)                                                                             \
+	"s_mov_b32 %[curA], " RA_TOP "\n"                                                                               \
+	"s_cmp_eq_u32 " RA_TOP ", 0x7fffffff\n"                                                                         \
+	"s_cbranch_scc1 L_exit_%=\n"                                                                                    \
+	"s_lshl_b32 s52, " RA_TOP ", 6\n"                                                                               \
+	"s_load_dwordx16 s[20:35], %[rows], s52\n"                                                                      \
+	WITH_FETCH                                                                                                      \
+	"v_add_u32 v54, -64, %[spA]\n"                            /* the entry below the one popped */                  \
+	"ds_read_b128 v[50:53], v54 offset:32\n"                                                                        \
+	"ds_read_b32 v54, v54 offset:16\n"                                                                              \
+	"v_add_u32 %[spA], -32, %[spA]\n"                                                                               \
+	"s_waitcnt lgkmcnt(0)\n"                                                                                        \
+	"v_readfirstlane_b32 s60, v50\n"                                                                                \
+	"v_readfirstlane_b32 s61, v51\n"                                                                                \
+	"v_readfirstlane_b32 s62, v52\n"                                                                                \
+	"v_readfirstlane_b32 s63, v53\n"                                                                                \
+	"v_readfirstlane_b32 " RA_TOP ", v54\n"                                                                         \
+	"s_branch L_have_%=\n"
+#else
+#define MRT_ROWSW_POP(WITH_FETCH, RELOAD)                                                                             \
+	"v_add_u32 %[spA], -32, %[spA]\n"                                                                               \
+	"ds_read_b128 v[50:53], %[spA]\n"                                                                               \
+	"ds_read_b32 v54, %[spA] offset:16\n"                                                                           \
+	"s_waitcnt lgkmcnt(0)\n"                                                                                        \
+	"v_readfirstlane_b32 %[curA], v54\n"                                                                            \
+	"v_readfirstlane_b32 s60, v50\n"                                                                                \
+	"v_readfirstlane_b32 s61, v51\n"                                                                                \
+	"v_readfirstlane_b32 s62, v52\n"                                                                                \
+	"v_readfirstlane_b32 s63, v53\n"                                                                                \
+	"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                            \
+	"s_cbranch_scc1 " RELOAD "\n"                                                                                   \
+	"s_branch L_exit_%=\n"
+#endif
+
 // In: cur (group A's operand) = a row to visit, the groups' own masks.  Out: cur = 0x7FFFFFFF.
 // Stack entries are 32 bytes: {group A's mask, group B's mask, ref, -}; the sentinel entry has ref 0x7FFFFFFF.
 #define MRT_ROWS_LOOPW(CNT_N, CNT_T, CNT_P, ANYA, ANYB, ANYDONE, BX, BY, BZ)                                                 \
 	asm volatile(                                                                                                   \
 		"s_mov_b64 s[60:61], %[maskA]\n"                                                                            \
 		"s_mov_b64 s[62:63], %[maskB]\n"                                                                            \
+		MRT_ROWS_TOP_EMPTY \
 		"L_loop_%=:\n"                                                                                              \
 		"s_lshl_b32 s52, %[curA], 6\n"                                                                              \
 		"s_load_dwordx16 s[20:35], %[rows], s52\n"                                                                  \
 		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
+		MRT_ROWS_HAVE \
 		"s_bitcmp1_b32 %[curA], 31\n"                                                                               \
 		"s_cbranch_scc1 L_tri_%=\n"                                                                                 \
 		CNT_N                                                                                                       \
@@ -434,6 +544,7 @@ struct PacketRegs {
 		"s_cselect_b64 s[58:59], s[42:43], s[40:41]\n"                                                              \
 		"s_cselect_b64 s[60:61], s[36:37], s[38:39]\n"        /* the near child's */                                \
 		"s_cselect_b64 s[62:63], s[40:41], s[42:43]\n"                                                              \
+		MRT_ROWS_TOP_PUSHED \
 		MRT_ROWSW_PUSH_MOVES                                                                                        \
 		"ds_write_b128 %[spA], v[50:53]\n"                                                                          \
 		"ds_write_b32 %[spA], v54 offset:16\n"                                                                      \
@@ -467,22 +578,11 @@ struct PacketRegs {
 		"s_add_u32 %[curA], %[curA], 1\n"                                                                           \
 		"s_branch L_loop_%=\n"                                                                                      \
 		"L_pop_%=:\n"                                                                                               \
-		"v_add_u32 %[spA], -32, %[spA]\n"                                                                           \
-		"ds_read_b128 v[50:53], %[spA]\n"                                                                           \
-		"ds_read_b32 v54, %[spA] offset:16\n"                                                                       \
-		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
-		"v_readfirstlane_b32 %[curA], v54\n"                                                                        \
-		"v_readfirstlane_b32 s60, v50\n"                                                                            \
-		"v_readfirstlane_b32 s61, v51\n"                                                                            \
-		"v_readfirstlane_b32 s62, v52\n"                                                                            \
-		"v_readfirstlane_b32 s63, v53\n"                                                                            \
-		"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                        \
-		"s_cbranch_scc1 L_loop_%=\n"                                                                                \
-		"s_branch L_exit_%=\n"                                                                                      \
+		MRT_ROWSW_POP("", "L_loop_%=")                                                                              \
 		MRT_ROWSW_GROUP_SKIP("A", "s[36:37]", "s[38:39]")                                                           \
 		MRT_ROWSW_GROUP_SKIP("B", "s[40:41]", "s[42:43]")                                                           \
 		"L_exit_%=:\n"                                                                                              \
-		"s_waitcnt vmcnt(0)\n"               /* no prefetch may land in v60 once the compiler owns it again */     \
+		MRT_ROWS_EXIT_WAIT                   /* no prefetch or copy may land in v60 / v61 once the compiler owns them again */ \
 		"s_mov_b64 %[maskA], s[60:61]\n"                                                                            \
 		"s_mov_b64 %[maskB], s[62:63]\n"                                                                            \
 		: MRT_ROWS_OUT(A, a), [limB] "+v"(b.lim), [btB] "+v"(b.bt), [buB] "+v"(b.bu), [bvB] "+v"(b.bv),             \
@@ -581,6 +681,7 @@ struct PacketRegs {
 	asm volatile(                                                                                                   \
 		"s_mov_b64 s[60:61], %[maskA]\n"                                                                            \
 		"s_mov_b64 s[62:63], %[maskB]\n"                                                                            \
+		MRT_ROWS_TOP_EMPTY \
 		"L_vload_%=:\n"                           /* the current row's vector copy is not on its way yet */          \
 		MRT_ROWSC_VLOAD("v60", "%[curA]")                                                                           \
 		"s_mov_b64 s[66:67], 0\n"                                                                                   \
@@ -588,6 +689,7 @@ struct PacketRegs {
 		"s_lshl_b32 s52, %[curA], 6\n"                                                                              \
 		"s_load_dwordx16 s[20:35], %[rows], s52\n"                                                                  \
 		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
+		MRT_ROWS_HAVE \
 		"s_bitcmp1_b32 %[curA], 31\n"                                                                               \
 		"s_cbranch_scc1 L_tri_%=\n"                                                                                 \
 		CNT_N                                                                                                       \
@@ -619,6 +721,7 @@ struct PacketRegs {
 		"s_cselect_b64 s[60:61], s[36:37], s[38:39]\n"        /* the near child's */                                \
 		"s_cselect_b64 s[62:63], s[40:41], s[42:43]\n"                                                              \
 		"s_cselect_b64 s[66:67], 0, -1\n"                     /* the near child's vector copy: v60 (left) / v61 */  \
+		MRT_ROWS_TOP_PUSHED \
 		MRT_ROWSW_PUSH_MOVES                                                                                        \
 		"ds_write_b128 %[spA], v[50:53]\n"                                                                          \
 		"ds_write_b32 %[spA], v54 offset:16\n"                                                                      \
@@ -652,23 +755,12 @@ struct PacketRegs {
 		"s_cbranch_scc1 L_pop_%=\n"                                                                                 \
 		"s_add_u32 %[curA], %[curA], 1\n"                                                                           \
 		"s_branch L_loop_%=\n"                                                                                      \
-		"L_pop_%=:\n"                                                                                               \
-		"v_add_u32 %[spA], -32, %[spA]\n"                                                                           \
-		"ds_read_b128 v[50:53], %[spA]\n"                                                                           \
-		"ds_read_b32 v54, %[spA] offset:16\n"                                                                       \
-		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
-		"v_readfirstlane_b32 %[curA], v54\n"                                                                        \
-		"v_readfirstlane_b32 s60, v50\n"                                                                            \
-		"v_readfirstlane_b32 s61, v51\n"                                                                            \
-		"v_readfirstlane_b32 s62, v52\n"                                                                            \
-		"v_readfirstlane_b32 s63, v53\n"                                                                            \
-		"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                        \
-		"s_cbranch_scc1 L_vload_%=\n"                                                                               \
-		"s_branch L_exit_%=\n"                                                                                      \
+		"L_pop_%=:\n"                             /* the popped row's vector copy goes out beside its scalar fetch */ \
+		MRT_ROWSW_POP(MRT_ROWSC_VLOAD("v60", RA_TOP) "s_mov_b64 s[66:67], 0\n", "L_vload_%=")                       \
 		MRT_ROWSC_CHILD_OOL(L, "s[36:37]", "s[40:41]")                                                              \
 		MRT_ROWSC_CHILD_OOL(R, "s[38:39]", "s[42:43]")                                                              \
 		"L_exit_%=:\n"                                                                                              \
-		"s_waitcnt vmcnt(0)\n"               /* no copy may land in v60 / v61 once the compiler owns them again */  \
+		MRT_ROWS_EXIT_WAIT                   /* no prefetch or copy may land in v60 / v61 once the compiler owns them again */ \
 		"s_mov_b64 %[maskA], s[60:61]\n"                                                                            \
 		"s_mov_b64 %[maskB], s[62:63]\n"                                                                            \
 		: MRT_ROWS_OUT(A, a), [limB] "+v"(b.lim), [btB] "+v"(b.bt), [buB] "+v"(b.bu), [bvB] "+v"(b.bv),             \
@@ -685,7 +777,8 @@ struct CullRegs {
 };
 
 // counting builds of the one-packet loop also clock the row fetch: shader cycles from before the s_load to after
-// its s_waitcnt (two s_memtime reads included), summed per wave in %[cntw]
+// its s_waitcnt (two s_memtime reads included), summed per wave in %[cntw].  At a pop the same pair brackets the popped row's
+// fetch AND the stack entry's LDS reads issued under it (one wait for both): the longer of the two, which is the fetch.
 #define MRT_ROWS_T_PRE "s_memtime s[64:65]\n s_waitcnt lgkmcnt(0)\n"
 #define MRT_ROWS_T_POST "s_memtime s[66:67]\n s_waitcnt lgkmcnt(0)\n s_sub_u32 s64, s66, s64\n s_add_u32 %[cntw], %[cntw], s64\n"
 #define MRT_ROWS_CNT_N "s_add_u32 %[cntn], %[cntn], 1\n"
