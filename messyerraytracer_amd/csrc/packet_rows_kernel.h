@@ -513,6 +513,147 @@ struct PacketRegs {
 	"s_branch L_exit_%=\n"
 #endif
 
+// ---- the packed node step (round 7; -DMRT_ROWS_PKSLAB=1, NOT the default) ------------------------------------------------------
+// Measured (profiles/r20_packed_slab.json): 16 % fewer vector instructions per wave at C3 (9 618 -> 8 067) and
+// the kernel 6 % SLOWER (1.66 -> 1.76 ms, well outside both builds' spread): in this walk a v_pk_fma_f32 costs more than the two
+// v_fma_f32 it stands for.  So the default build keeps the two single-group tests and is the same machine code as before.  The form,
+// for whoever measures it again:
+// On a row that BOTH groups own, MRT_ROWS_SLAB multiplies the same twelve plane scalars first into group A's six registers and then
+// into group B's: 24 v_fma_f32.  v_pk_fma_f32 does an {A, B} pair in one instruction (the same IEEE fma per component: the same
+// bits), so such a row costs 12 packed fmas + 2 x 10 (four clamps, max3 / min3 twice, four compares) = 32 vector instructions
+// where 44 stood.  For that the six hot values of the two groups stand side by side in aligned register pairs,
+//   ix v[12:13]  iy v[14:15]  iz v[16:17]  nrx v[18:19]  nry v[20:21]  nrz v[22:23]      (low half group A, high half group B),
+// which the operands of MRT_ROWS_LOOPW are pinned to (MRT_ROWSW_IN_A / _B); every single-group test still names its half through
+// its operand (%[ixA] is v12), so MRT_ROWS_SLAB and the triangle test are the text they were.  (Where the pairs stand was chosen
+// by compiling: at v[38:49] the headline's general code spilled 12 bytes to scratch, at v[12:23] every instantiation has the
+// parent's registers, scratch and occupancy.)  A plane scalar is read from its aligned pair of s[20:35], op_sel / op_sel_hi
+// choosing the half for both components: one SGPR source per instruction.
+// Temporaries: v50..v60 as they stand (five pairs and v60; a box's six products are never all live at once: the left box's far z
+// and the right box's products take the registers its near planes have left); no instruction reads its predecessor's result.
+// It ends as the single tests do: group B (the group tested last) leaves tl in v50 and tr in v56 for the near / far decision, the
+// masks are in s[36:43].  A row only one group owns takes MRT_ROWSW_GROUP_SLAB, out of line.
+// The culling loop (MRT_ROWS_LOOPC) keeps its one-box tests in either build: v61 / v62 hold its row copies there, and a culled box
+// leaves a step with one box for two groups, half of what a packed step pairs up.
+#ifndef MRT_ROWS_PKSLAB
+#define MRT_ROWS_PKSLAB 0
+#endif
+// a plane's aligned scalar pair and the half it is
+#define RA_LMINX_PK "s[20:21]", "0"
+#define RA_LMINY_PK "s[20:21]", "1"
+#define RA_LMINZ_PK "s[22:23]", "0"
+#define RA_LMAXX_PK "s[24:25]", "0"
+#define RA_LMAXY_PK "s[24:25]", "1"
+#define RA_LMAXZ_PK "s[26:27]", "0"
+#define RA_RMINX_PK "s[28:29]", "0"
+#define RA_RMINY_PK "s[28:29]", "1"
+#define RA_RMINZ_PK "s[30:31]", "0"
+#define RA_RMAXX_PK "s[32:33]", "0"
+#define RA_RMAXY_PK "s[32:33]", "1"
+#define RA_RMAXZ_PK "s[34:35]", "0"
+#define MRT_NEARPK_0(RS, AX, SIDE) RS##_##SIDE##MIN##AX##_PK
+#define MRT_NEARPK_1(RS, AX, SIDE) RS##_##SIDE##MAX##AX##_PK
+#define MRT_FARPK_0(RS, AX, SIDE) RS##_##SIDE##MAX##AX##_PK
+#define MRT_FARPK_1(RS, AX, SIDE) RS##_##SIDE##MIN##AX##_PK
+#ifndef MRT_PK_V0
+#define MRT_PK_V0 12
+#define MRT_PK_V1 13
+#define MRT_PK_V2 14
+#define MRT_PK_V3 15
+#define MRT_PK_V4 16
+#define MRT_PK_V5 17
+#define MRT_PK_V6 18
+#define MRT_PK_V7 19
+#define MRT_PK_V8 20
+#define MRT_PK_V9 21
+#define MRT_PK_V10 22
+#define MRT_PK_V11 23
+#endif
+#define MRT_STR2(X) #X
+#define MRT_STR(X) MRT_STR2(X)
+#define MRT_PK_PAIR(LO, HI) "v[" MRT_STR(LO) ":" MRT_STR(HI) "]"
+#define MRT_PK_PIN(N) "{v" MRT_STR(N) "}"
+#define MRT_PK_IX MRT_PK_PAIR(MRT_PK_V0, MRT_PK_V1)
+#define MRT_PK_IY MRT_PK_PAIR(MRT_PK_V2, MRT_PK_V3)
+#define MRT_PK_IZ MRT_PK_PAIR(MRT_PK_V4, MRT_PK_V5)
+#define MRT_PK_NRX MRT_PK_PAIR(MRT_PK_V6, MRT_PK_V7)
+#define MRT_PK_NRY MRT_PK_PAIR(MRT_PK_V8, MRT_PK_V9)
+#define MRT_PK_NRZ MRT_PK_PAIR(MRT_PK_V10, MRT_PK_V11)
+// DST = {plane * inv + nr of group A, of group B}
+#define MRT_PKFMA2(DST, PAIR, HALF, INV, NR)                                                                          \
+	"v_pk_fma_f32 " DST ", " PAIR ", " INV ", " NR " op_sel:[" HALF ",0,0] op_sel_hi:[" HALF ",1,1]\n"
+#define MRT_PKFMA(DST, PLANE, INV, NR) MRT_PKFMA2(DST, PLANE, INV, NR)
+#define MRT_ROWSW_PKSLAB(BX, BY, BZ)                                                                                  \
+	MRT_PKFMA("v[50:51]", MRT_NEARPK_##BX(RA, X, L), MRT_PK_IX, MRT_PK_NRX)                                        \
+	MRT_PKFMA("v[52:53]", MRT_NEARPK_##BY(RA, Y, L), MRT_PK_IY, MRT_PK_NRY)                                        \
+	MRT_PKFMA("v[54:55]", MRT_NEARPK_##BZ(RA, Z, L), MRT_PK_IZ, MRT_PK_NRZ)                                        \
+	MRT_PKFMA("v[56:57]", MRT_FARPK_##BX(RA, X, L), MRT_PK_IX, MRT_PK_NRX)                                         \
+	MRT_PKFMA("v[58:59]", MRT_FARPK_##BY(RA, Y, L), MRT_PK_IY, MRT_PK_NRY)                                         \
+	"v_max_f32 v54, v54, %[tminA]\n"                                                                               \
+	"v_max_f32 v55, v55, %[tminB]\n"                                                                               \
+	"v_max3_f32 v60, v50, v52, v54\n"        /* v60 = tl of group A  */                                            \
+	"v_max3_f32 v50, v51, v53, v55\n"        /* v50 = tl of group B (stays) */                                     \
+	MRT_PKFMA("v[52:53]", MRT_FARPK_##BZ(RA, Z, L), MRT_PK_IZ, MRT_PK_NRZ)                                         \
+	MRT_PKFMA("v[54:55]", MRT_NEARPK_##BX(RA, X, R), MRT_PK_IX, MRT_PK_NRX)                                        \
+	"v_min_f32 v52, v52, %[limA]\n"                                                                                \
+	"v_min_f32 v53, v53, %[limB]\n"                                                                                \
+	"v_min3_f32 v56, v56, v58, v52\n"        /* v56 = tlx of group A */                                            \
+	"v_min3_f32 v57, v57, v59, v53\n"        /* v57 = tlx of group B */                                            \
+	MRT_PKFMA("v[52:53]", MRT_NEARPK_##BY(RA, Y, R), MRT_PK_IY, MRT_PK_NRY)                                        \
+	MRT_PKFMA("v[58:59]", MRT_NEARPK_##BZ(RA, Z, R), MRT_PK_IZ, MRT_PK_NRZ)                                        \
+	"v_cmp_le_f32_e64 s[36:37], v60, v56\n"  /* group A's lanes that hit the left child */                         \
+	"v_cmp_le_f32_e64 s[40:41], v50, v57\n"  /* group B's */                                                       \
+	"v_max_f32 v58, v58, %[tminA]\n"                                                                               \
+	"v_max_f32 v59, v59, %[tminB]\n"                                                                               \
+	"v_max3_f32 v60, v54, v52, v58\n"        /* v60 = tr of group A  */                                            \
+	"v_max3_f32 v56, v55, v53, v59\n"        /* v56 = tr of group B (stays) */                                     \
+	MRT_PKFMA("v[52:53]", MRT_FARPK_##BX(RA, X, R), MRT_PK_IX, MRT_PK_NRX)                                         \
+	MRT_PKFMA("v[54:55]", MRT_FARPK_##BZ(RA, Z, R), MRT_PK_IZ, MRT_PK_NRZ)                                         \
+	MRT_PKFMA("v[58:59]", MRT_FARPK_##BY(RA, Y, R), MRT_PK_IY, MRT_PK_NRY)                                         \
+	"v_min_f32 v54, v54, %[limA]\n"                                                                                \
+	"v_min_f32 v55, v55, %[limB]\n"                                                                                \
+	"v_min3_f32 v52, v52, v58, v54\n"        /* v52 = trx of group A */                                            \
+	"v_min3_f32 v53, v53, v59, v55\n"        /* v53 = trx of group B */                                            \
+	"v_cmp_le_f32_e64 s[38:39], v60, v52\n"  /* group A's lanes that hit the right child */                        \
+	"v_cmp_le_f32_e64 s[42:43], v56, v53\n"  /* group B's */
+#if MRT_ROWS_PKSLAB && !MRT_ROWS_KPREFETCH
+#error "MRT_ROWS_PKSLAB keeps a product in v60, where the far-child prefetch of MRT_ROWS_KPREFETCH=0 lands"
+#endif
+#if MRT_ROWS_PKSLAB
+// both groups' tests at a node row, and what of them stands out of line (behind the pop)
+#define MRT_ROWSW_SLABS(BX, BY, BZ)                                                                                   \
+	"s_cmp_eq_u64 s[60:61], 0\n"                                                                                    \
+	"s_cbranch_scc1 L_Askip_%=\n"             /* group B alone: on at L_Asdone, group B's own test */                \
+	"s_cmp_eq_u64 s[62:63], 0\n"                                                                                    \
+	"s_cbranch_scc1 L_single_%=\n"            /* group A alone */                                                    \
+	MRT_ROWSW_PKSLAB(BX, BY, BZ)                                                                                    \
+	"L_slabbed_%=:\n"
+#define MRT_ROWSW_SLABS_OOL(BX, BY, BZ)                                                                               \
+	"L_single_%=:\n"                                                                                                \
+	MRT_ROWSW_GROUP_SLAB("A", "s[60:61]", "s[36:37]", "s[38:39]", BX, BY, BZ)                                       \
+	MRT_ROWSW_GROUP_SLAB("B", "s[62:63]", "s[40:41]", "s[42:43]", BX, BY, BZ)                                       \
+	"s_branch L_slabbed_%=\n"                                                                                       \
+	MRT_ROWSW_GROUP_SKIP("A", "s[36:37]", "s[38:39]")                                                               \
+	MRT_ROWSW_GROUP_SKIP("B", "s[40:41]", "s[42:43]")
+// the operands of MRT_ROWS_IN with the six hot ones pinned to their halves of the pairs above
+#define MRT_ROWSW_IN_A(S)                                                                                             \
+	[oxA] "v"(S.ox), [oyA] "v"(S.oy), [ozA] "v"(S.oz), [dxA] "v"(S.dx), [dyA] "v"(S.dy), [dzA] "v"(S.dz),            \
+	[tminA] "v"(S.tmin), [ixA] MRT_PK_PIN(MRT_PK_V0)(S.ix), [iyA] MRT_PK_PIN(MRT_PK_V2)(S.iy), [izA] MRT_PK_PIN(MRT_PK_V4)(S.iz), [nrxA] MRT_PK_PIN(MRT_PK_V6)(S.nrx),      \
+	[nryA] MRT_PK_PIN(MRT_PK_V8)(S.nry), [nrzA] MRT_PK_PIN(MRT_PK_V10)(S.nrz)
+#define MRT_ROWSW_IN_B(S)                                                                                             \
+	[oxB] "v"(S.ox), [oyB] "v"(S.oy), [ozB] "v"(S.oz), [dxB] "v"(S.dx), [dyB] "v"(S.dy), [dzB] "v"(S.dz),            \
+	[tminB] "v"(S.tmin), [ixB] MRT_PK_PIN(MRT_PK_V1)(S.ix), [iyB] MRT_PK_PIN(MRT_PK_V3)(S.iy), [izB] MRT_PK_PIN(MRT_PK_V5)(S.iz), [nrxB] MRT_PK_PIN(MRT_PK_V7)(S.nrx),      \
+	[nryB] MRT_PK_PIN(MRT_PK_V9)(S.nry), [nrzB] MRT_PK_PIN(MRT_PK_V11)(S.nrz)
+#else
+#define MRT_ROWSW_SLABS(BX, BY, BZ)                                                                                   \
+	MRT_ROWSW_GROUP_SLAB("A", "s[60:61]", "s[36:37]", "s[38:39]", BX, BY, BZ)                                       \
+	MRT_ROWSW_GROUP_SLAB("B", "s[62:63]", "s[40:41]", "s[42:43]", BX, BY, BZ)
+#define MRT_ROWSW_SLABS_OOL(BX, BY, BZ)                                                                               \
+	MRT_ROWSW_GROUP_SKIP("A", "s[36:37]", "s[38:39]")                                                               \
+	MRT_ROWSW_GROUP_SKIP("B", "s[40:41]", "s[42:43]")
+#define MRT_ROWSW_IN_A(S) MRT_ROWS_IN(A, S)
+#define MRT_ROWSW_IN_B(S) MRT_ROWS_IN(B, S)
+#endif
+
 // In: cur (group A's operand) = a row to visit, the groups' own masks.  Out: cur = 0x7FFFFFFF.
 // Stack entries are 32 bytes: {group A's mask, group B's mask, ref, -}; the sentinel entry has ref 0x7FFFFFFF.
 #define MRT_ROWS_LOOPW(CNT_N, CNT_T, CNT_P, ANYA, ANYB, ANYDONE, BX, BY, BZ)                                                 \
@@ -529,8 +670,7 @@ struct PacketRegs {
 		"s_cbranch_scc1 L_tri_%=\n"                                                                                 \
 		CNT_N                                                                                                       \
 		MRT_ROWSW_KPREFETCH                                                                                         \
-		MRT_ROWSW_GROUP_SLAB("A", "s[60:61]", "s[36:37]", "s[38:39]", BX, BY, BZ)                                   \
-		MRT_ROWSW_GROUP_SLAB("B", "s[62:63]", "s[40:41]", "s[42:43]", BX, BY, BZ)                                   \
+		MRT_ROWSW_SLABS(BX, BY, BZ)                                                                                 \
 		"s_or_b64 s[44:45], s[36:37], s[40:41]\n"    /* any lane of the 128 hit the left child?  */                 \
 		"s_cbranch_scc0 L_lmiss_%=\n"                                                                               \
 		"s_or_b64 vcc, s[38:39], s[42:43]\n"         /* ... the right child? */                                     \
@@ -579,15 +719,14 @@ struct PacketRegs {
 		"s_branch L_loop_%=\n"                                                                                      \
 		"L_pop_%=:\n"                                                                                               \
 		MRT_ROWSW_POP("", "L_loop_%=")                                                                              \
-		MRT_ROWSW_GROUP_SKIP("A", "s[36:37]", "s[38:39]")                                                           \
-		MRT_ROWSW_GROUP_SKIP("B", "s[40:41]", "s[42:43]")                                                           \
+		MRT_ROWSW_SLABS_OOL(BX, BY, BZ)                                                                             \
 		"L_exit_%=:\n"                                                                                              \
 		MRT_ROWS_EXIT_WAIT                   /* no prefetch or copy may land in v60 / v61 once the compiler owns them again */ \
 		"s_mov_b64 %[maskA], s[60:61]\n"                                                                            \
 		"s_mov_b64 %[maskB], s[62:63]\n"                                                                            \
 		: MRT_ROWS_OUT(A, a), [limB] "+v"(b.lim), [btB] "+v"(b.bt), [buB] "+v"(b.bu), [bvB] "+v"(b.bv),             \
 		  [bsB] "+v"(b.bs), [biB] "+v"(b.bi), [maskB] "+s"(b.mask), [cntn] "+s"(cnt_n), [cntt] "+s"(cnt_t), [cntp] "+s"(sp_max) \
-		: MRT_ROWS_IN(A, a), MRT_ROWS_IN(B, b), [rows] "s"(rows), [qmask] "s"(qmask), [eps] "s"(eps), [vneg] "v"(vneg) \
+		: MRT_ROWSW_IN_A(a), MRT_ROWSW_IN_B(b), [rows] "s"(rows), [qmask] "s"(qmask), [eps] "s"(eps), [vneg] "v"(vneg) \
 		: MRT_ROWS_CLOBBERS)
 
 
