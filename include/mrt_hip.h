@@ -1470,9 +1470,10 @@ int mrt_schedule_counts(mrt_ctx *ctx, uint64_t out[3]);
  * permutation of 0 .. count - 1 by the rays' sort keys), copied on the context's stream; waits for it.  MRT_ERR_INVALID when no sorted cast
  * of at least `count` rays has run.  Reads only.  The order decides no record; tests hold it to the cast it belongs to. */
 int mrt_debug_sort_order(mrt_ctx *ctx, uint32_t *out, uint64_t count);
-/* 1 if this build contains the kernel.  MRT_KERNEL_PACKET_QUAD (the four-wide packet walk: held to the oracle, not faster
- * than the default) is compiled only into builds made with MRT_WITH_QUAD=1 (messyerraytracer_amd/build.py); mrt_create
- * with it returns MRT_ERR_UNSUPPORTED otherwise. */
+/* 1 if this build contains the kernel.  MRT_KERNEL_PACKET_QUAD (the four-wide packet walk: not faster than the default) is
+ * compiled only into builds made with MRT_WITH_QUAD=1 (messyerraytracer_amd/build.py), and only in such a build do the tests
+ * that hold it to the oracle run: the default suite checks no more of it than that it compiles.  mrt_create with it returns
+ * MRT_ERR_UNSUPPORTED otherwise. */
 int mrt_kernel_available(uint32_t kernel);
 int mrt_device_alloc(mrt_ctx *ctx, size_t bytes, void **d_ptr);
 int mrt_device_free(mrt_ctx *ctx, void *d_ptr);

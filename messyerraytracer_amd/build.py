@@ -99,7 +99,9 @@ def _deps(dfile: str):
 
 def define_set(env) -> list:
     """The -D flags that decide what is built.  MRT_WITH_QUAD=1 also compiles the four-wide packet walk (packet_quad_kernel.h: an
-    experiment kept for the record, held to the oracle by the packet tests, slower than the default on every measured config);
+    experiment kept for the record, slower than the default on every measured config; the packet tests hold it to the oracle only
+    in such a build and skip its cases in any other, where tests/test_define_sets_cpu.py holds it to compiling: from 7a50a6c
+    until that test came it did not);
     MRT_EXTRA_DEFINES: A/B builds of the tools (e.g. -DMRT_ASM_KPF=0)."""
     return sorted((["-DMRT_WITH_QUAD"] if env.get("MRT_WITH_QUAD") == "1" else []) + env.get("MRT_EXTRA_DEFINES", "").split())
 

@@ -1,6 +1,7 @@
 // packet_quad_kernel.h — the 128-ray shared packet walk of packet_rows_kernel.h over FOUR-wide node rows, with the
 // instruction stream cut to what gfx950 issues cheaply.  Included by kernels.hip (inside namespace mrt, after
-// packet_rows_kernel.h, whose triangle test and operand macros it reuses).
+// packet_rows_kernel.h, of which it takes the leaf section, the pop that reads its entry first, the exit, the output operands and
+// the ladder of walk forms).  Only in builds made with -DMRT_WITH_QUAD; tests/test_define_sets_cpu.py holds it to compiling.
 //
 // What the second half of round 2 measured (tools/ubench/issue_cost.hip, ubench/pk_fma_issue.hip, ubench/row_fetch.hip; counters of
 // trace_packet_rows_kernel<2> in profiles/r02d_*), at 8 waves per SIMD:
@@ -121,6 +122,7 @@
 
 // counting builds: the stack's high-water mark (s39 is free during a push; the s_nop: MRT_ROWS_CNT_P, packet_rows_kernel.h)
 #define MRT_QUAD_CNT_P "s_nop 0\n v_readfirstlane_b32 s39, %[spA]\n s_max_u32 %[cntp], %[cntp], s39\n"
+#define MRT_QUAD_COUNTING MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_QUAD_CNT_P, MRT_ROWS_T_PRE, MRT_ROWS_T_POST
 
 // push {group A's mask, group B's mask, ref, -} = s[40:41], s[42:43], s38
 #define MRT_Q_PUSH(CNT_P)                                                                                             \
@@ -182,34 +184,10 @@
 		"s_movrels_b64 s[68:69], s[52:53]\n"                                                                        \
 		"s_movrels_b64 s[70:71], s[60:61]\n"                                                                        \
 		"s_branch L_loop_%=\n"                                                                                      \
-		"L_tri_%=:\n"                                                                                               \
-		CNT_T                                                                                                       \
-		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
-		T_POST                                                                                                      \
-		"s_cmp_eq_u64 s[68:69], 0\n"                                                                                \
-		"s_cbranch_scc1 L_Atnext_%=\n"                                                                              \
-		MRT_ROWS_TRI_TEST("A", RA, "s[68:69]", "%[curA]", ANYA)                                                     \
-		"s_cmp_eq_u64 s[70:71], 0\n"                                                                                \
-		"s_cbranch_scc1 L_Btnext_%=\n"                                                                              \
-		MRT_ROWS_TRI_TEST("B", RA, "s[70:71]", "%[curA]", ANYB)                                                     \
-		ANYDONE                                                                                                     \
-		"s_bitcmp1_b32 " RA_FLAGS ", 0\n"        /* the last triangle of its leaf? */                               \
-		"s_cbranch_scc1 L_pop_%=\n"                                                                                 \
-		"s_add_u32 %[curA], %[curA], 1\n"                                                                           \
-		"s_branch L_loop_%=\n"                                                                                      \
+		/* the leaf section of the two-wide walks, behind the wait for the row (the loop head did not wait) */      \
+		MRT_ROWSW_LEAF("s[68:69]", "s[70:71]", "s_waitcnt lgkmcnt(0)\n" T_POST, CNT_T, ANYA, ANYB, ANYDONE)         \
 		"L_pop_%=:\n"                                                                                               \
-		"v_add_u32 %[spA], -32, %[spA]\n"                                                                           \
-		"ds_read_b128 v[50:53], %[spA]\n"                                                                           \
-		"ds_read_b32 v54, %[spA] offset:16\n"                                                                       \
-		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
-		"v_readfirstlane_b32 %[curA], v54\n"                                                                        \
-		"v_readfirstlane_b32 s68, v50\n"                                                                            \
-		"v_readfirstlane_b32 s69, v51\n"                                                                            \
-		"v_readfirstlane_b32 s70, v52\n"                                                                            \
-		"v_readfirstlane_b32 s71, v53\n"                                                                            \
-		"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                        \
-		"s_cbranch_scc1 L_loop_%=\n"                                                                                \
-		"s_branch L_exit_%=\n"                                                                                      \
+		MRT_ROWSW_POP_READ("s68", "s69", "s70", "s71", "L_loop_%=")                                                 \
 		/* ---- out of line: a group whose rays have all left this subtree ---- */                                  \
 		"L_onlyA_%=:\n"                                                                                             \
 		"s_waitcnt lgkmcnt(0)\n"                                                                                    \
@@ -269,12 +247,8 @@
 		"s_mov_b64 s[68:69], s[28:29]\n"                                                                            \
 		"s_mov_b64 s[70:71], s[30:31]\n"                                                                            \
 		"s_branch L_loop_%=\n"                                                                                      \
-		"L_exit_%=:\n"                                                                                              \
-		"s_waitcnt vmcnt(0)\n"               /* no prefetch may land in v62 once the compiler owns it again */     \
-		"s_mov_b64 %[maskA], s[68:69]\n"                                                                            \
-		"s_mov_b64 %[maskB], s[70:71]\n"                                                                            \
-		: MRT_QUAD_OUT(A, a), [limB] "+v"(b.lim), [btB] "+v"(b.bt), [buB] "+v"(b.bu), [bvB] "+v"(b.bv),             \
-		  [bsB] "+v"(b.bs), [biB] "+v"(b.bi), [maskB] "+s"(b.mask), [cntn] "+s"(cnt_n), [cntt] "+s"(cnt_t), [cntp] "+s"(sp_max), [cntw] "+s"(cnt_w) \
+		MRT_ROWSW_EXIT("s_waitcnt vmcnt(0)\n", "s[68:69]", "s[70:71]")   /* (the prefetches into v62) */            \
+		: MRT_ROWSW_OUT, [cntw] "+s"(cnt_w)                                                                         \
 		: MRT_QUAD_IN(A, a), MRT_QUAD_IN(B, b), [rows] "s"(rows), [qmask] "s"(qmask), [eps] "s"(eps), [vneg] "v"(vneg) \
 		: MRT_QUAD_CLOBBERS)
 
@@ -289,9 +263,7 @@ struct QuadRegs {
 	uint32_t cur;                         // wave-uniform: the row to visit next (bit 31: a triangle), 0x7FFFFFFF = finished
 	unsigned long long mask;              // wave-uniform: the lanes that own the current row
 };
-#define MRT_QUAD_OUT(P, S)                                                                                            \
-	[cur##P] "+s"(S.cur), [sp##P] "+v"(S.sp), [lim##P] "+v"(S.lim), [bt##P] "+v"(S.bt), [bu##P] "+v"(S.bu),         \
-	[bv##P] "+v"(S.bv), [bs##P] "+v"(S.bs), [bi##P] "+v"(S.bi), [mask##P] "+s"(S.mask)
+// (the output operands are MRT_ROWSW_OUT: QuadRegs names those fields as PacketRegs does)
 #define MRT_QUAD_IN(P, S)                                                                                             \
 	[ox##P] "v"(S.ox), [oy##P] "v"(S.oy), [oz##P] "v"(S.oz), [dx##P] "v"(S.dx), [dy##P] "v"(S.dy), [dz##P] "v"(S.dz), \
 	[tmin##P] "v"(S.tmin), [p0##P] "v"(S.p0), [p1##P] "v"(S.p1), [p2##P] "v"(S.p2)
@@ -312,30 +284,33 @@ __device__ __forceinline__ void quad_init(QuadRegs &s, const RayRegs &r, bool ta
 	s.sp = sp; s.cur = 0u; s.mask = 0ull;
 }
 
+// wave-uniform octant of a packet's reciprocal directions over the lanes that take part (8 = mixed); QuadRegs keeps the
+// reciprocals in pairs, so this reads the ray (rows_octant reads a PacketRegs)
+__device__ __forceinline__ int quad_octant(const RayRegs &r, bool part, unsigned long long &part_mask)
+{
+	part_mask = __ballot(part);
+	const unsigned long long sx = __ballot(part && safe_inv(r.dx) < 0.0f), sy = __ballot(part && safe_inv(r.dy) < 0.0f),
+			sz = __ballot(part && safe_inv(r.dz) < 0.0f);
+	const bool uniform = (sx == 0ull || sx == part_mask) && (sy == 0ull || sy == part_mask) && (sz == 0ull || sz == part_mask);
+	return uniform ? ((sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0)) : 8;
+}
+
 template <int OCT, bool ANY_HIT, bool COUNT>
 __device__ __forceinline__ void quad_walk(const float4 *rows, uint32_t qmask, QuadRegs &a, QuadRegs &b, uint32_t &cnt_n, uint32_t &cnt_t, uint32_t &cnt_w, uint32_t &sp_max)
 {
 	const float eps = 1e-8f, vneg = -FLT_MAX;
-#define MRT_QW(O, BX, BY, BZ)                                                                                         \
-	if (OCT == O) {                                                                                                 \
-		if (COUNT) { if (ANY_HIT) MRT_QUAD_LOOP(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_QUAD_CNT_P, MRT_ROWS_T_PRE, MRT_ROWS_T_POST, MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE, BX, BY, BZ); \
-			else MRT_QUAD_LOOP(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_QUAD_CNT_P, MRT_ROWS_T_PRE, MRT_ROWS_T_POST, MRT_ROWS_NEAREST("A"), MRT_ROWS_NEAREST("B"), "", BX, BY, BZ); } \
-		else { if (ANY_HIT) MRT_QUAD_LOOP("", "", "", "", "", MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE, BX, BY, BZ); \
-			else MRT_QUAD_LOOP("", "", "", "", "", MRT_ROWS_NEAREST("A"), MRT_ROWS_NEAREST("B"), "", BX, BY, BZ); }         \
-	}
-	MRT_QW(0, 0, 0, 0) MRT_QW(1, 1, 0, 0) MRT_QW(2, 0, 1, 0) MRT_QW(3, 1, 1, 0) MRT_QW(4, 0, 0, 1) MRT_QW(5, 1, 0, 1) MRT_QW(6, 0, 1, 1) MRT_QW(7, 1, 1, 1)
-#undef MRT_QW
-	a.cur = __builtin_amdgcn_readfirstlane(a.cur);
-	cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t); cnt_w = __builtin_amdgcn_readfirstlane(cnt_w);
-	sp_max = __builtin_amdgcn_readfirstlane(sp_max);
+	// (the loop's hit arguments are those of the two-wide 128-ray loops, its plain counting arguments five empty ones)
+#define MRT_ROW(O, BX, BY, BZ) MRT_WALK_FORMS(MRT_QUAD_LOOP, MRT_QUAD_COUNTING, MRT_ROWS1_PLAIN, MRT_ROWSW_ANY, MRT_ROWSW_NEAREST, O, BX, BY, BZ)
+	MRT_OCTANTS(MRT_ROW)
+#undef MRT_ROW
+	MRT_UNIFORM(a.cur);
+	MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(cnt_w); MRT_UNIFORM(sp_max);
 }
 
 template <bool ANY_HIT, bool COUNT>
 __device__ __forceinline__ void quad_walk_oct(int oct, const float4 *rows, uint32_t qmask, QuadRegs &a, QuadRegs &b, uint32_t &cnt_n, uint32_t &cnt_t, uint32_t &cnt_w, uint32_t &sp_max)
 {
-#define MRT_QO(O) case O: quad_walk<O, ANY_HIT, COUNT>(rows, qmask, a, b, cnt_n, cnt_t, cnt_w, sp_max); break;
-	switch (oct) { MRT_QO(0) MRT_QO(1) MRT_QO(2) MRT_QO(3) MRT_QO(4) MRT_QO(5) MRT_QO(6) MRT_QO(7) }
-#undef MRT_QO
+	MRT_OCT_SWITCH(oct, quad_walk, rows, qmask, a, b, cnt_n, cnt_t, cnt_w, sp_max)
 }
 
 // Two packets (neighbouring tiles of the launch order) per wave.  Packets of one octant share one walk; a packet
@@ -373,7 +348,7 @@ __global__ __launch_bounds__(MRT_WG) __attribute__((amdgpu_waves_per_eu(MRT_ROWS
 	quad_init(B, rb, valid_b, sp0);
 
 	unsigned long long part_a = 0ull, part_b = 0ull;
-	const int oct_a = rows_octant(ra, valid_a, part_a), oct_b = rows_octant(rb, valid_b, part_b);
+	const int oct_a = quad_octant(ra, valid_a, part_a), oct_b = quad_octant(rb, valid_b, part_b);
 	uint32_t cnt_n = 0u, cnt_t = 0u, sp_max = 0u; // COUNT: node rows / triangle rows fetched by this wave, highest stack pointer
 	uint32_t cnt_w = 0u;                          // COUNT: shader cycles between issuing a row fetch and having it
 	const unsigned long long t_start = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;

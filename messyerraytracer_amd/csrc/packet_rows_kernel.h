@@ -36,52 +36,18 @@
 //   node row:     lmin.xyz lref | lmax.xyz rref | rmin.xyz - | rmax.xyz -
 //   triangle row: v0.xyz id | e1.xyz layers | e2.xyz flags | normal (unused here)
 // own masks (the lanes whose own ray hit the current row's box): group A s[60:61], group B s[62:63]
-// scratch: s52 (byte offset), s53 (far ref); lane-mask pairs of the triangle test s[54:55] (accepting lanes),
-// s[56:57], s[58:59], s[64:65], s[66:67]; of the 128-ray node step s[36:37] / s[38:39] (group A hit left / right),
-// s[40:41] / s[42:43] (group B), s[44:45] (any lane hit left), s[46:47] (left-is-nearer flags),
-// s[50:51] / s[58:59] (the pushed child's masks)
-// v50..v59 temporaries, v60 the never-read destination of the far-child prefetches.
-//
-// ---- the pop that fetches first (round 6; -DMRT_ROWS_POPFETCH=1, NOT the default) ----------------------------------
-// Measured (DESIGN 4.1b round 6, profiles/r19_pop_fetch.json): 1.6 % fewer wave cycles, about 1 % of C3's kernel time in each of two
-// sessions, less than the builds' own spread: the gate for a gain fails, so the default build keeps the pop that reads its entry
-// first and is the same machine code as before.  The form, for whoever measures it again:
-// top (s68, the first scalar above the fixed ones; the kernel has 72) shadows ONE field of the stack, which stays in the LDS entry
-// for entry and byte for byte as it was.  Invariant inside each walk block: top == the ref field of the entry at sp - entry size.
-// Every block is entered with an empty stack (only the sentinel below sp: rows_walks_and_records sets sp so), so top starts as
-// 0x7FFFFFFF; a push copies the far ref (s53) into it: one scalar instruction.  A pop runs in this order:
-//   1. cur = top; top == 0x7FFFFFFF -> leave the walk: the sentinel is never read from the LDS;
-//   2. s_lshl / s_load_dwordx16 of row top into s[20:35]: the fetch is in flight from here.  Every path into a pop has finished
-//      with the row registers (the leaf path tests RA_FLAGS before it branches, the miss path has made its masks);
-//   3. the LDS reads: the masks of the entry popped and the ref word of the entry below it, the new top (it always exists: the
-//      sentinel lies at the bottom).  DS offsets are unsigned, so the lower entry's address goes to a temporary, both reads use
-//      positive offsets from it, then sp is set;
-//   4. ONE s_waitcnt lgkmcnt(0): scalar loads and LDS reads share the counter, scalar loads return out of order, and the child
-//      prefetches into s64 / s65 may still be on their way (the triangle test writes those registers): only 0 is safe, and it
-//      covers the row, the entry and the prefetches;
-//   5. v_readfirstlane of the mask words and of the new top (LDS results, behind the wait: no VALU write precedes them), and on at
-//      the label BEHIND the loop head's own fetch and wait.
-// So the LDS round trip and the hand-overs to the scalar unit run under the row fetch's latency instead of in front of it.  The
-// any-hit early finish leaves with entries still on the stack, as before (top is dead from there).  The four-wide walk keeps the
-// old pop: its loop head issues a second load by the row's kind, and it is an experiment kept for the record.
-#ifndef MRT_ROWS_POPFETCH
-#define MRT_ROWS_POPFETCH 0
-#endif
-#define RA_TOP "s68"
-#if MRT_ROWS_POPFETCH
-#define MRT_ROWS_TOP_CLOBBER "s68",
-#define MRT_ROWS_TOP_EMPTY "s_mov_b32 s68, 0x7fffffff\n"   /* on entry to a block: the stack is empty, its top is the sentinel */
-#define MRT_ROWS_TOP_PUSHED "s_mov_b32 s68, s53\n"         /* the entry being pushed (far ref s53) is the stack's top */
-#define MRT_ROWS_HAVE "L_have_%=:\n"                       /* behind the loop head's fetch: the row is in s[20:35] */
-// (the pop at the sentinel waits for nothing: no prefetch may land in s64 / s65 once the compiler owns them again)
-#define MRT_ROWS_EXIT_WAIT "s_waitcnt vmcnt(0) lgkmcnt(0)\n"
-#else
-#define MRT_ROWS_TOP_CLOBBER
-#define MRT_ROWS_TOP_EMPTY ""
-#define MRT_ROWS_TOP_PUSHED ""
-#define MRT_ROWS_HAVE ""
-#define MRT_ROWS_EXIT_WAIT "s_waitcnt vmcnt(0)\n"
-#endif
+// scratch: s52 (byte offset; the counting builds' copy of sp), s53 (far ref); lane-mask pairs of the triangle test s[54:55]
+// (accepting lanes), s[56:57], s[58:59], s[64:65], s[66:67]; of the 128-ray node step s[36:37] / s[38:39] (group A hit left /
+// right), s[40:41] / s[42:43] (group B), s[44:45] (any lane hit left; the culling loop's cull word), s[46:47] (left-is-nearer
+// flags), s48 / s49 (byte offsets of the child prefetches; s48 the cull bits of one child), s[50:51] / s[58:59] (the pushed
+// child's masks).  s64 / s65 are also the never-read destinations of the 128-ray walk's child prefetches, s[64:67] the counting
+// builds' clock, s[66:67] in the culling loop "the current row's copy is the one in v61".  s68: the stack's top, in
+// MRT_ROWS_POPFETCH builds only (the kernel has 72 scalars below the compiler's).
+// v50..v59 temporaries; v60 the never-read destination of the one-packet loop's far-child prefetch, a product of the packed node
+// step (MRT_ROWS_PKSLAB), in the culling loop the vector copy of the left child's (or the popped) row; v61 the right child's
+// copy and v62 the address of a copy's request, both in the culling loop only.
+// The four-wide loop (packet_quad_kernel.h) reads a 128-byte row into s[20:51] and keeps its own masks in s[68:71]: its register
+// comment is in that file.
 #define RA_LMINX "s20"
 #define RA_LMINY "s21"
 #define RA_LMINZ "s22"
@@ -310,8 +276,72 @@
 	MRT_ROWS_TRI_STEP(P, RS, POPBIT, CNT_T, ANYHIT_CODE)                                                             \
 	"L_" P "done_%=:\n"
 
-// The pop of the one-packet loop (16-byte entries {ref, -, mask}), entered with an event in %[ev]: the pop bit (bit 0), or the any-hit
-// finish (cur is the sentinel already).  Falls out at the end of the walk; else goes on at L_loop, or (fetching first) at L_have.
+// ---- the pops; the pop that fetches first (round 6; -DMRT_ROWS_POPFETCH=1, NOT the default) ------------------------------------
+// Everything that switch changes stands in this section: the words the loops take from it (MRT_ROWS_TOP_*, MRT_ROWS_HAVE,
+// MRT_ROWS_EXIT_WAIT) and both forms of both pops.
+// Measured (DESIGN 4.1b round 6, profiles/r19_pop_fetch.json): 1.6 % fewer wave cycles, about 1 % of C3's kernel time in each of two
+// sessions, less than the builds' own spread: the gate for a gain fails, so the default build keeps the pop that reads its entry
+// first and is the same machine code as before.  The form, for whoever measures it again:
+// top (s68, the first scalar above the fixed ones; the kernel has 72) shadows ONE field of the stack, which stays in the LDS entry
+// for entry and byte for byte as it was.  Invariant inside each walk block: top == the ref field of the entry at sp - entry size.
+// Every block is entered with an empty stack (only the sentinel below sp: rows_walks_and_records sets sp so), so top starts as
+// 0x7FFFFFFF; a push copies the far ref (s53) into it: one scalar instruction.  A pop runs in this order:
+//   1. cur = top; top == 0x7FFFFFFF -> leave the walk: the sentinel is never read from the LDS;
+//   2. s_lshl / s_load_dwordx16 of row top into s[20:35]: the fetch is in flight from here.  Every path into a pop has finished
+//      with the row registers (the leaf path tests RA_FLAGS before it branches, the miss path has made its masks);
+//   3. the LDS reads: the masks of the entry popped and the ref word of the entry below it, the new top (it always exists: the
+//      sentinel lies at the bottom).  DS offsets are unsigned, so the lower entry's address goes to a temporary, both reads use
+//      positive offsets from it, then sp is set;
+//   4. ONE s_waitcnt lgkmcnt(0): scalar loads and LDS reads share the counter, scalar loads return out of order, and the child
+//      prefetches into s64 / s65 may still be on their way (the triangle test writes those registers): only 0 is safe, and it
+//      covers the row, the entry and the prefetches;
+//   5. v_readfirstlane of the mask words and of the new top (LDS results, behind the wait: no VALU write precedes them), and on at
+//      the label BEHIND the loop head's own fetch and wait.
+// So the LDS round trip and the hand-overs to the scalar unit run under the row fetch's latency instead of in front of it.  The
+// any-hit early finish leaves with entries still on the stack, as before (top is dead from there).  The four-wide walk keeps the
+// old pop (MRT_ROWSW_POP_READ) in either build: its loop head issues a second load by the row's kind, and it is an experiment kept
+// for the record.
+#ifndef MRT_ROWS_POPFETCH
+#define MRT_ROWS_POPFETCH 0
+#endif
+#define RA_TOP "s68"
+#if MRT_ROWS_POPFETCH
+#define MRT_ROWS_TOP_CLOBBER "s68",
+#define MRT_ROWS_TOP_EMPTY "s_mov_b32 s68, 0x7fffffff\n"   /* on entry to a block: the stack is empty, its top is the sentinel */
+#define MRT_ROWS_TOP_PUSHED "s_mov_b32 s68, s53\n"         /* the entry being pushed (far ref s53) is the stack's top */
+#define MRT_ROWS_HAVE "L_have_%=:\n"                       /* behind the loop head's fetch: the row is in s[20:35] */
+// (the pop at the sentinel waits for nothing: no prefetch may land in s64 / s65 once the compiler owns them again)
+#define MRT_ROWS_EXIT_WAIT "s_waitcnt vmcnt(0) lgkmcnt(0)\n"
+#else
+#define MRT_ROWS_TOP_CLOBBER
+#define MRT_ROWS_TOP_EMPTY ""
+#define MRT_ROWS_TOP_PUSHED ""
+#define MRT_ROWS_HAVE ""
+#define MRT_ROWS_EXIT_WAIT "s_waitcnt vmcnt(0)\n"
+#endif
+
+// The pop of the shared walks (32-byte entries {group A's mask, group B's mask, ref, -}) that reads its entry first: the own masks
+// into M0..M3, on at RELOAD, or out through L_exit at the sentinel
+#define MRT_ROWSW_POP_READ(M0, M1, M2, M3, RELOAD)                                                                    \
+	"v_add_u32 %[spA], -32, %[spA]\n"                                                                               \
+	"ds_read_b128 v[50:53], %[spA]\n"                                                                               \
+	"ds_read_b32 v54, %[spA] offset:16\n"                                                                           \
+	"s_waitcnt lgkmcnt(0)\n"                                                                                        \
+	"v_readfirstlane_b32 %[curA], v54\n"                                                                            \
+	"v_readfirstlane_b32 " M0 ", v50\n"                                                                             \
+	"v_readfirstlane_b32 " M1 ", v51\n"                                                                             \
+	"v_readfirstlane_b32 " M2 ", v52\n"                                                                             \
+	"v_readfirstlane_b32 " M3 ", v53\n"                                                                             \
+	"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                            \
+	"s_cbranch_scc1 " RELOAD "\n"                                                                                   \
+	"s_branch L_exit_%=\n"
+
+// MRT_ROWS_POP1: the pop of the one-packet loop (16-byte entries {ref, -, mask}), entered with an event in %[ev]: the pop bit (bit 0),
+// or the any-hit finish (cur is the sentinel already).  Falls out at the end of the walk; else goes on at L_loop, or (fetching first)
+// at L_have.
+// MRT_ROWSW_POP: the pop of the two 128-ray loops: leaves through L_exit at the sentinel.  WITH_FETCH: what the culling loop issues
+// beside the popped row's scalar fetch (the vector copy of the row); RELOAD: the label the pop that reads its entry first goes on at
+// (the loop head, or the culling loop's request for that copy in front of it).
 #if MRT_ROWS_POPFETCH
 // "the pop" above: cur = top, out at the sentinel, the fetch of row top (T_PRE / T_POST: the counting builds' clock), the popped
 // entry's mask into v[52:53] and the ref of the entry below it into v50 under it, one wait, three hand-overs
@@ -336,8 +366,27 @@
 	"v_readfirstlane_b32 " RA_TOP ", v50\n"                                                                         \
 	"s_branch L_have_%=\n"                                                                                          \
 	"L_exit_%=:\n"
+// "the pop" above: goes on at L_have with the popped row in s[20:35], its masks in s[60:63], cur = its ref, top = the ref of the entry below
+#define MRT_ROWSW_POP(WITH_FETCH, RELOAD)                                                                             \
+	"s_mov_b32 %[curA], " RA_TOP "\n"                                                                               \
+	"s_cmp_eq_u32 " RA_TOP ", 0x7fffffff\n"                                                                         \
+	"s_cbranch_scc1 L_exit_%=\n"                                                                                    \
+	"s_lshl_b32 s52, " RA_TOP ", 6\n"                                                                               \
+	"s_load_dwordx16 s[20:35], %[rows], s52\n"                                                                      \
+	WITH_FETCH                                                                                                      \
+	"v_add_u32 v54, -64, %[spA]\n"                            /* the entry below the one popped */                  \
+	"ds_read_b128 v[50:53], v54 offset:32\n"                                                                        \
+	"ds_read_b32 v54, v54 offset:16\n"                                                                              \
+	"v_add_u32 %[spA], -32, %[spA]\n"                                                                               \
+	"s_waitcnt lgkmcnt(0)\n"                                                                                        \
+	"v_readfirstlane_b32 s60, v50\n"                                                                                \
+	"v_readfirstlane_b32 s61, v51\n"                                                                                \
+	"v_readfirstlane_b32 s62, v52\n"                                                                                \
+	"v_readfirstlane_b32 s63, v53\n"                                                                                \
+	"v_readfirstlane_b32 " RA_TOP ", v54\n"                                                                         \
+	"s_branch L_have_%=\n"
 #else
-#define MRT_ROWS_POP1(T_PRE, T_POST)                                                                                \
+#define MRT_ROWS_POP1(T_PRE, T_POST)                                                                              \
 	"s_bitcmp1_b32 %[ev], 0\n"                                                                                      \
 	"s_cbranch_scc0 L_Api_%=\n"                                                                                     \
 	"v_add_u32 %[spA], -16, %[spA]\n"                                                                               \
@@ -353,6 +402,7 @@
 	"s_mov_b32 %[ev], 0\n"                                                                                          \
 	"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                            \
 	"s_cbranch_scc1 L_loop_%=\n"
+#define MRT_ROWSW_POP(WITH_FETCH, RELOAD) MRT_ROWSW_POP_READ("s60", "s61", "s62", "s63", RELOAD)
 #endif
 
 #define MRT_ROWS_CLOBBERS                                                                                             \
@@ -436,82 +486,89 @@ struct PacketRegs {
 // Both child rows are pulled into the scalar cache as soon as the node's own row has arrived, before the slab tests:
 // the row fetch of the next step (whichever child it visits) then finds its line there instead of waiting for the L2
 // (two one-dword scalar loads into the triangle test's temporaries s64 / s65, which nothing reads; they are long back
-// when the next step waits on lgkmcnt).  The far-child vector prefetch of round 1 is the alternative (MRT_ROWS_KPREFETCH=0).
-#ifndef MRT_ROWS_KPREFETCH
-#define MRT_ROWS_KPREFETCH 1
-#endif
-#if MRT_ROWS_KPREFETCH
+// when the next step waits on lgkmcnt).  (The far-child vector prefetch of round 1 that this replaced, and the same two loads
+// tried inside the culling loop, are measured in DESIGN 4.1c / 4.1d and profiles/r03_kprefetch_pmc.txt.)
 #define MRT_ROWSW_KPREFETCH                                                                                           \
 	"s_lshl_b32 s48, " RA_LREF ", 6\n"                                                                               \
 	"s_lshl_b32 s49, " RA_RREF ", 6\n"                                                                               \
 	"s_load_dword s64, %[rows], s48\n"                                                                              \
 	"s_load_dword s65, %[rows], s49\n"
-#define MRT_ROWSW_FARPREFETCH ""
-#else
-#define MRT_ROWSW_KPREFETCH ""
-#define MRT_ROWSW_FARPREFETCH                                                                                         \
-	"v_lshlrev_b32 v55, 6, v54\n"           /* pull the pushed row towards the L2 now */                            \
-	"global_load_dword v60, v55, %[rows]\n" /* v60 is never read (vmcnt drained at the very end) */
-#endif
 
-// The push of the shared walk: the far child's two masks (s[50:51], s[58:59]) and its ref (s53) go to v50..v54 for the two
-// ds_writes.  gfx950 moves a scalar pair in one v_mov_b64: three vector instructions where five single moves stood, the same bits
-// stored (-DMRT_ROWS_PUSH64=0: the single moves, for A/B builds).
-#ifndef MRT_ROWS_PUSH64
-#define MRT_ROWS_PUSH64 1
-#endif
-#if MRT_ROWS_PUSH64
-#define MRT_ROWSW_PUSH_MOVES                                                                                          \
+// ---- the steps the two 128-ray loops share, and the four-wide loop where it does the same ---------------------------------------
+// The near / far decision from the groups' hit masks (s[36:43]; tl / tr of the group tested last in v50 / v56) and the push of the
+// far child: the next row's ref into cur, its own masks into s[60:63], then on at L_loop; no child hit: L_pop.  The far child's two
+// masks (s[50:51], s[58:59]) and its ref (s53) go to v50..v54 for the two ds_writes (gfx950 moves a scalar pair in one v_mov_b64).
+// COPY_NEAR / COPY_L / COPY_R: the culling loop's note of which vector copy the next row has, where both children / the left one /
+// the right one was hit.
+#define MRT_ROWSW_DECIDE(CNT_P, COPY_NEAR, COPY_L, COPY_R)                                                            \
+	"s_or_b64 s[44:45], s[36:37], s[40:41]\n"    /* any lane of the 128 hit the left child?  */                     \
+	"s_cbranch_scc0 L_lmiss_%=\n"                                                                                   \
+	"s_or_b64 vcc, s[38:39], s[42:43]\n"         /* ... the right child? */                                         \
+	"s_cbranch_scc0 L_onlyl_%=\n"                                                                                   \
+	/* both: lane 0 of the group tested last (its tl, tr are still in v50, v56) decides which is nearer */          \
+	"v_cmp_lt_f32_e64 s[46:47], v50, v56\n"      /* (order = speed only) */                                         \
+	"s_bitcmp1_b32 s46, 0\n"                                                                                        \
+	"s_cselect_b32 s53, " RA_RREF ", " RA_LREF "\n"       /* far  */                                                \
+	"s_cselect_b32 %[curA], " RA_LREF ", " RA_RREF "\n"   /* near */                                                \
+	"s_cselect_b64 s[50:51], s[38:39], s[36:37]\n"        /* the far child's masks: group A, group B */             \
+	"s_cselect_b64 s[58:59], s[42:43], s[40:41]\n"                                                                  \
+	"s_cselect_b64 s[60:61], s[36:37], s[38:39]\n"        /* the near child's */                                    \
+	"s_cselect_b64 s[62:63], s[40:41], s[42:43]\n"                                                                  \
+	COPY_NEAR                                                                                                       \
+	MRT_ROWS_TOP_PUSHED                                                                                             \
 	"v_mov_b64 v[50:51], s[50:51]\n"                                                                                \
 	"v_mov_b64 v[52:53], s[58:59]\n"                                                                                \
-	"v_mov_b32 v54, s53\n"
-#else
-#define MRT_ROWSW_PUSH_MOVES                                                                                          \
-	"v_mov_b32 v50, s50\n"                                                                                          \
-	"v_mov_b32 v51, s51\n"                                                                                          \
-	"v_mov_b32 v52, s58\n"                                                                                          \
-	"v_mov_b32 v53, s59\n"                                                                                          \
-	"v_mov_b32 v54, s53\n"
-#endif
+	"v_mov_b32 v54, s53\n"                                                                                          \
+	"ds_write_b128 %[spA], v[50:53]\n"                                                                              \
+	"ds_write_b32 %[spA], v54 offset:16\n"                                                                          \
+	"v_add_u32 %[spA], 32, %[spA]\n"                                                                                \
+	CNT_P                                                                                                           \
+	"s_branch L_loop_%=\n"                                                                                          \
+	"L_onlyl_%=:\n"                                                                                                 \
+	"s_mov_b32 %[curA], " RA_LREF "\n"                                                                              \
+	"s_mov_b64 s[60:61], s[36:37]\n"                                                                                \
+	"s_mov_b64 s[62:63], s[40:41]\n"                                                                                \
+	COPY_L                                                                                                          \
+	"s_branch L_loop_%=\n"                                                                                          \
+	"L_lmiss_%=:\n"                                                                                                 \
+	"s_or_b64 vcc, s[38:39], s[42:43]\n"                                                                            \
+	"s_cbranch_scc0 L_pop_%=\n"                                                                                     \
+	"s_mov_b32 %[curA], " RA_RREF "\n"                                                                              \
+	"s_mov_b64 s[60:61], s[38:39]\n"                                                                                \
+	"s_mov_b64 s[62:63], s[42:43]\n"                                                                                \
+	COPY_R                                                                                                          \
+	"s_branch L_loop_%=\n"
 
-// The pop of the shared walks (32-byte entries {group A's mask, group B's mask, ref, -}): leaves through L_exit at the sentinel.
-// WITH_FETCH: what the culling loop issues beside the popped row's scalar fetch (the vector copy of the row); RELOAD: the label the
-// pop that reads its entry first goes on at (the loop head, or the culling loop's request for that copy in front of it).
-#if MRT_ROWS_POPFETCH
-// "the pop" above: goes on at L_have with the popped row in s[20:35], its masks in s[60:63], cur = its ref, top = the ref of the entry below
-#define MRT_ROWSW_POP(WITH_FETCH, RELOAD)                                                                             \
-	"s_mov_b32 %[curA], " RA_TOP "\n"                                                                               \
-	"s_cmp_eq_u32 " RA_TOP ", 0x7fffffff\n"                                                                         \
-	"s_cbranch_scc1 L_exit_%=\n"                                                                                    \
-	"s_lshl_b32 s52, " RA_TOP ", 6\n"                                                                               \
-	"s_load_dwordx16 s[20:35], %[rows], s52\n"                                                                      \
-	WITH_FETCH                                                                                                      \
-	"v_add_u32 v54, -64, %[spA]\n"                            /* the entry below the one popped */                  \
-	"ds_read_b128 v[50:53], v54 offset:32\n"                                                                        \
-	"ds_read_b32 v54, v54 offset:16\n"                                                                              \
-	"v_add_u32 %[spA], -32, %[spA]\n"                                                                               \
-	"s_waitcnt lgkmcnt(0)\n"                                                                                        \
-	"v_readfirstlane_b32 s60, v50\n"                                                                                \
-	"v_readfirstlane_b32 s61, v51\n"                                                                                \
-	"v_readfirstlane_b32 s62, v52\n"                                                                                \
-	"v_readfirstlane_b32 s63, v53\n"                                                                                \
-	"v_readfirstlane_b32 " RA_TOP ", v54\n"                                                                         \
-	"s_branch L_have_%=\n"
-#else
-#define MRT_ROWSW_POP(WITH_FETCH, RELOAD)                                                                             \
-	"v_add_u32 %[spA], -32, %[spA]\n"                                                                               \
-	"ds_read_b128 v[50:53], %[spA]\n"                                                                               \
-	"ds_read_b32 v54, %[spA] offset:16\n"                                                                           \
-	"s_waitcnt lgkmcnt(0)\n"                                                                                        \
-	"v_readfirstlane_b32 %[curA], v54\n"                                                                            \
-	"v_readfirstlane_b32 s60, v50\n"                                                                                \
-	"v_readfirstlane_b32 s61, v51\n"                                                                                \
-	"v_readfirstlane_b32 s62, v52\n"                                                                                \
-	"v_readfirstlane_b32 s63, v53\n"                                                                                \
-	"s_cmp_lg_u32 %[curA], 0x7fffffff\n"                                                                            \
-	"s_cbranch_scc1 " RELOAD "\n"                                                                                   \
-	"s_branch L_exit_%=\n"
-#endif
+// The leaf section: the triangle row in s[20:35] against each group that has a lane owning it (OWN_A / OWN_B), then the leaf's next
+// triangle (on at L_loop) or, after its last one, the pop (L_pop).  ARRIVED: what a loop that comes here with the row
+// still on its way puts first.
+#define MRT_ROWSW_LEAF(OWN_A, OWN_B, ARRIVED, CNT_T, ANYA, ANYB, ANYDONE)                                             \
+	"L_tri_%=:\n"                                                                                                   \
+	CNT_T                                                                                                           \
+	ARRIVED                                                                                                         \
+	"s_cmp_eq_u64 " OWN_A ", 0\n"                                                                                   \
+	"s_cbranch_scc1 L_Atnext_%=\n"                                                                                  \
+	MRT_ROWS_TRI_TEST("A", RA, OWN_A, "%[curA]", ANYA)                                                              \
+	"s_cmp_eq_u64 " OWN_B ", 0\n"                                                                                   \
+	"s_cbranch_scc1 L_Btnext_%=\n"                                                                                  \
+	MRT_ROWS_TRI_TEST("B", RA, OWN_B, "%[curA]", ANYB)                                                              \
+	ANYDONE                                                                                                         \
+	"s_bitcmp1_b32 " RA_FLAGS ", 0\n"        /* the last triangle of its leaf? */                                   \
+	"s_cbranch_scc1 L_pop_%=\n"                                                                                     \
+	"s_add_u32 %[curA], %[curA], 1\n"                                                                               \
+	"s_branch L_loop_%=\n"
+
+// The exit: WAIT (nothing in flight may land in a register once the compiler owns it again), the own masks back to their operands
+#define MRT_ROWSW_EXIT(WAIT, OWN_A, OWN_B)                                                                            \
+	"L_exit_%=:\n"                                                                                                  \
+	WAIT                                                                                                            \
+	"s_mov_b64 %[maskA], " OWN_A "\n"                                                                               \
+	"s_mov_b64 %[maskB], " OWN_B "\n"
+
+// what a paired walk hands back: group A's packet whole, of group B's what is not shared, the counters
+#define MRT_ROWSW_OUT                                                                                                 \
+	MRT_ROWS_OUT(A, a), [limB] "+v"(b.lim), [btB] "+v"(b.bt), [buB] "+v"(b.bu), [bvB] "+v"(b.bv),                   \
+	[bsB] "+v"(b.bs), [biB] "+v"(b.bi), [maskB] "+s"(b.mask), [cntn] "+s"(cnt_n), [cntt] "+s"(cnt_t), [cntp] "+s"(sp_max)
 
 // ---- the packed node step (round 7; -DMRT_ROWS_PKSLAB=1, NOT the default) ------------------------------------------------------
 // Measured (profiles/r20_packed_slab.json): 16 % fewer vector instructions per wave at C3 (9 618 -> 8 067) and
@@ -615,9 +672,6 @@ struct PacketRegs {
 	"v_min3_f32 v53, v53, v59, v55\n"        /* v53 = trx of group B */                                            \
 	"v_cmp_le_f32_e64 s[38:39], v60, v52\n"  /* group A's lanes that hit the right child */                        \
 	"v_cmp_le_f32_e64 s[42:43], v56, v53\n"  /* group B's */
-#if MRT_ROWS_PKSLAB && !MRT_ROWS_KPREFETCH
-#error "MRT_ROWS_PKSLAB keeps a product in v60, where the far-child prefetch of MRT_ROWS_KPREFETCH=0 lands"
-#endif
 #if MRT_ROWS_PKSLAB
 // both groups' tests at a node row, and what of them stands out of line (behind the pop)
 #define MRT_ROWSW_SLABS(BX, BY, BZ)                                                                                   \
@@ -671,64 +725,15 @@ struct PacketRegs {
 		CNT_N                                                                                                       \
 		MRT_ROWSW_KPREFETCH                                                                                         \
 		MRT_ROWSW_SLABS(BX, BY, BZ)                                                                                 \
-		"s_or_b64 s[44:45], s[36:37], s[40:41]\n"    /* any lane of the 128 hit the left child?  */                 \
-		"s_cbranch_scc0 L_lmiss_%=\n"                                                                               \
-		"s_or_b64 vcc, s[38:39], s[42:43]\n"         /* ... the right child? */                                     \
-		"s_cbranch_scc0 L_onlyl_%=\n"                                                                               \
-		/* both: lane 0 of the group tested last (its tl, tr are still in v50, v56) decides which is nearer */      \
-		"v_cmp_lt_f32_e64 s[46:47], v50, v56\n"      /* (order = speed only) */                                     \
-		"s_bitcmp1_b32 s46, 0\n"                                                                                    \
-		"s_cselect_b32 s53, " RA_RREF ", " RA_LREF "\n"       /* far  */                                            \
-		"s_cselect_b32 %[curA], " RA_LREF ", " RA_RREF "\n"   /* near */                                            \
-		"s_cselect_b64 s[50:51], s[38:39], s[36:37]\n"        /* the far child's masks: group A, group B */         \
-		"s_cselect_b64 s[58:59], s[42:43], s[40:41]\n"                                                              \
-		"s_cselect_b64 s[60:61], s[36:37], s[38:39]\n"        /* the near child's */                                \
-		"s_cselect_b64 s[62:63], s[40:41], s[42:43]\n"                                                              \
-		MRT_ROWS_TOP_PUSHED \
-		MRT_ROWSW_PUSH_MOVES                                                                                        \
-		"ds_write_b128 %[spA], v[50:53]\n"                                                                          \
-		"ds_write_b32 %[spA], v54 offset:16\n"                                                                      \
-		"v_add_u32 %[spA], 32, %[spA]\n"                                                                            \
-		CNT_P                                                                                                       \
-		MRT_ROWSW_FARPREFETCH                                                                                       \
-		"s_branch L_loop_%=\n"                                                                                      \
-		"L_onlyl_%=:\n"                                                                                             \
-		"s_mov_b32 %[curA], " RA_LREF "\n"                                                                          \
-		"s_mov_b64 s[60:61], s[36:37]\n"                                                                            \
-		"s_mov_b64 s[62:63], s[40:41]\n"                                                                            \
-		"s_branch L_loop_%=\n"                                                                                      \
-		"L_lmiss_%=:\n"                                                                                             \
-		"s_or_b64 vcc, s[38:39], s[42:43]\n"                                                                        \
-		"s_cbranch_scc0 L_pop_%=\n"                                                                                 \
-		"s_mov_b32 %[curA], " RA_RREF "\n"                                                                          \
-		"s_mov_b64 s[60:61], s[38:39]\n"                                                                            \
-		"s_mov_b64 s[62:63], s[42:43]\n"                                                                            \
-		"s_branch L_loop_%=\n"                                                                                      \
-		"L_tri_%=:\n"                                                                                               \
-		CNT_T                                                                                                       \
-		"s_cmp_eq_u64 s[60:61], 0\n"                                                                                \
-		"s_cbranch_scc1 L_Atnext_%=\n"                                                                              \
-		MRT_ROWS_TRI_TEST("A", RA, "s[60:61]", "%[curA]", ANYA)                                                     \
-		"s_cmp_eq_u64 s[62:63], 0\n"                                                                                \
-		"s_cbranch_scc1 L_Btnext_%=\n"                                                                              \
-		MRT_ROWS_TRI_TEST("B", RA, "s[62:63]", "%[curA]", ANYB)                                                     \
-		ANYDONE                                                                                                     \
-		"s_bitcmp1_b32 " RA_FLAGS ", 0\n"        /* the last triangle of its leaf? */                               \
-		"s_cbranch_scc1 L_pop_%=\n"                                                                                 \
-		"s_add_u32 %[curA], %[curA], 1\n"                                                                           \
-		"s_branch L_loop_%=\n"                                                                                      \
+		MRT_ROWSW_DECIDE(CNT_P, "", "", "")                                                                         \
+		MRT_ROWSW_LEAF("s[60:61]", "s[62:63]", "", CNT_T, ANYA, ANYB, ANYDONE)                                      \
 		"L_pop_%=:\n"                                                                                               \
 		MRT_ROWSW_POP("", "L_loop_%=")                                                                              \
 		MRT_ROWSW_SLABS_OOL(BX, BY, BZ)                                                                             \
-		"L_exit_%=:\n"                                                                                              \
-		MRT_ROWS_EXIT_WAIT                   /* no prefetch or copy may land in v60 / v61 once the compiler owns them again */ \
-		"s_mov_b64 %[maskA], s[60:61]\n"                                                                            \
-		"s_mov_b64 %[maskB], s[62:63]\n"                                                                            \
-		: MRT_ROWS_OUT(A, a), [limB] "+v"(b.lim), [btB] "+v"(b.bt), [buB] "+v"(b.bu), [bvB] "+v"(b.bv),             \
-		  [bsB] "+v"(b.bs), [biB] "+v"(b.bi), [maskB] "+s"(b.mask), [cntn] "+s"(cnt_n), [cntt] "+s"(cnt_t), [cntp] "+s"(sp_max) \
+		MRT_ROWSW_EXIT(MRT_ROWS_EXIT_WAIT, "s[60:61]", "s[62:63]")                                                  \
+		: MRT_ROWSW_OUT                                                                                             \
 		: MRT_ROWSW_IN_A(a), MRT_ROWSW_IN_B(b), [rows] "s"(rows), [qmask] "s"(qmask), [eps] "s"(eps), [vneg] "v"(vneg) \
 		: MRT_ROWS_CLOBBERS)
-
 
 // ---- the 128-ray walk with packet-level frustum culling ---------------------------------------------------------
 // The ownership model (tools/sim_ownership.py, profiles/r03_ownership_sim_c3.json): of the (group, child box) slab
@@ -801,19 +806,7 @@ struct PacketRegs {
 	"v_lshl_add_u32 v62, " REF ", 6, %[cvo]\n"                                                                      \
 	"global_load_dword " VDST ", v62, %[rows]\n"
 
-// (optional, -DMRT_ROWSC_KPF=1: also the scalar-cache prefetch of MRT_ROWS_LOOPW; the vector copies already pull both rows to the L2)
-#ifndef MRT_ROWSC_KPF
-#define MRT_ROWSC_KPF 0
-#endif
-#if MRT_ROWSC_KPF
-#define MRT_ROWSC_KPREFETCH                                                                                           \
-	"s_lshl_b32 s46, " RA_LREF ", 6\n"                                                                               \
-	"s_lshl_b32 s47, " RA_RREF ", 6\n"                                                                               \
-	"s_load_dword s64, %[rows], s46\n"                                                                              \
-	"s_load_dword s65, %[rows], s47\n"
-#else
-#define MRT_ROWSC_KPREFETCH ""
-#endif
+// (No scalar-cache prefetch of the children here: the vector copies already pull both rows to the L2.)
 // In: cur (group A's operand) = a row to visit, the groups' own masks, the lane's cull constants.  Out: cur = 0x7FFFFFFF.
 // Stack entries as in MRT_ROWS_LOOPW.
 #define MRT_ROWS_LOOPC(CNT_N, CNT_T, CNT_P, ANYA, ANYB, ANYDONE, BX, BY, BZ)                                          \
@@ -842,68 +835,18 @@ struct PacketRegs {
 		"s_nop 1\n"                                                                                                 \
 		"v_add_f32_dpp v59, v58, v58 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"                           \
 		"v_cmp_lt_f32_e64 s[44:45], v59, %[ccc]\n" /* bit 16 r + 7: the left box is outside plane r; 16 r + 15: the right one */ \
-		MRT_ROWSC_KPREFETCH                                                                                         \
 		"s_or_b32 s44, s44, s45\n"                                                                                  \
 		MRT_ROWSC_CHILD(L, "v50", "0x00800080", "s[36:37]", "s[40:41]", BX, BY, BZ)                                 \
 		MRT_ROWSC_CHILD(R, "v56", "0x80008000", "s[38:39]", "s[42:43]", BX, BY, BZ)                                 \
-		"s_or_b64 s[44:45], s[36:37], s[40:41]\n"    /* any lane of the 128 hit the left child?  */                 \
-		"s_cbranch_scc0 L_lmiss_%=\n"                                                                               \
-		"s_or_b64 vcc, s[38:39], s[42:43]\n"         /* ... the right child? */                                     \
-		"s_cbranch_scc0 L_onlyl_%=\n"                                                                               \
-		/* both: lane 0 of the group tested last (its tl, tr are still in v50, v56) decides which is nearer */      \
-		"v_cmp_lt_f32_e64 s[46:47], v50, v56\n"      /* (order = speed only) */                                     \
-		"s_bitcmp1_b32 s46, 0\n"                                                                                    \
-		"s_cselect_b32 s53, " RA_RREF ", " RA_LREF "\n"       /* far  */                                            \
-		"s_cselect_b32 %[curA], " RA_LREF ", " RA_RREF "\n"   /* near */                                            \
-		"s_cselect_b64 s[50:51], s[38:39], s[36:37]\n"        /* the far child's masks: group A, group B */         \
-		"s_cselect_b64 s[58:59], s[42:43], s[40:41]\n"                                                              \
-		"s_cselect_b64 s[60:61], s[36:37], s[38:39]\n"        /* the near child's */                                \
-		"s_cselect_b64 s[62:63], s[40:41], s[42:43]\n"                                                              \
-		"s_cselect_b64 s[66:67], 0, -1\n"                     /* the near child's vector copy: v60 (left) / v61 */  \
-		MRT_ROWS_TOP_PUSHED \
-		MRT_ROWSW_PUSH_MOVES                                                                                        \
-		"ds_write_b128 %[spA], v[50:53]\n"                                                                          \
-		"ds_write_b32 %[spA], v54 offset:16\n"                                                                      \
-		"v_add_u32 %[spA], 32, %[spA]\n"                                                                            \
-		CNT_P                                                                                                       \
-		"s_branch L_loop_%=\n"                                                                                      \
-		"L_onlyl_%=:\n"                                                                                             \
-		"s_mov_b32 %[curA], " RA_LREF "\n"                                                                          \
-		"s_mov_b64 s[60:61], s[36:37]\n"                                                                            \
-		"s_mov_b64 s[62:63], s[40:41]\n"                                                                            \
-		"s_mov_b64 s[66:67], 0\n"                                                                                   \
-		"s_branch L_loop_%=\n"                                                                                      \
-		"L_lmiss_%=:\n"                                                                                             \
-		"s_or_b64 vcc, s[38:39], s[42:43]\n"                                                                        \
-		"s_cbranch_scc0 L_pop_%=\n"                                                                                 \
-		"s_mov_b32 %[curA], " RA_RREF "\n"                                                                          \
-		"s_mov_b64 s[60:61], s[38:39]\n"                                                                            \
-		"s_mov_b64 s[62:63], s[42:43]\n"                                                                            \
-		"s_mov_b64 s[66:67], -1\n"                                                                                  \
-		"s_branch L_loop_%=\n"                                                                                      \
-		"L_tri_%=:\n"                                                                                               \
-		CNT_T                                                                                                       \
-		"s_cmp_eq_u64 s[60:61], 0\n"                                                                                \
-		"s_cbranch_scc1 L_Atnext_%=\n"                                                                              \
-		MRT_ROWS_TRI_TEST("A", RA, "s[60:61]", "%[curA]", ANYA)                                                     \
-		"s_cmp_eq_u64 s[62:63], 0\n"                                                                                \
-		"s_cbranch_scc1 L_Btnext_%=\n"                                                                              \
-		MRT_ROWS_TRI_TEST("B", RA, "s[62:63]", "%[curA]", ANYB)                                                     \
-		ANYDONE                                                                                                     \
-		"s_bitcmp1_b32 " RA_FLAGS ", 0\n"        /* the last triangle of its leaf? */                               \
-		"s_cbranch_scc1 L_pop_%=\n"                                                                                 \
-		"s_add_u32 %[curA], %[curA], 1\n"                                                                           \
-		"s_branch L_loop_%=\n"                                                                                      \
+		/* the next row's vector copy: both children hit: the near one's, v60 (left) / v61; one child: its own */   \
+		MRT_ROWSW_DECIDE(CNT_P, "s_cselect_b64 s[66:67], 0, -1\n", "s_mov_b64 s[66:67], 0\n", "s_mov_b64 s[66:67], -1\n") \
+		MRT_ROWSW_LEAF("s[60:61]", "s[62:63]", "", CNT_T, ANYA, ANYB, ANYDONE)                                      \
 		"L_pop_%=:\n"                             /* the popped row's vector copy goes out beside its scalar fetch */ \
 		MRT_ROWSW_POP(MRT_ROWSC_VLOAD("v60", RA_TOP) "s_mov_b64 s[66:67], 0\n", "L_vload_%=")                       \
 		MRT_ROWSC_CHILD_OOL(L, "s[36:37]", "s[40:41]")                                                              \
 		MRT_ROWSC_CHILD_OOL(R, "s[38:39]", "s[42:43]")                                                              \
-		"L_exit_%=:\n"                                                                                              \
-		MRT_ROWS_EXIT_WAIT                   /* no prefetch or copy may land in v60 / v61 once the compiler owns them again */ \
-		"s_mov_b64 %[maskA], s[60:61]\n"                                                                            \
-		"s_mov_b64 %[maskB], s[62:63]\n"                                                                            \
-		: MRT_ROWS_OUT(A, a), [limB] "+v"(b.lim), [btB] "+v"(b.bt), [buB] "+v"(b.bu), [bvB] "+v"(b.bv),             \
-		  [bsB] "+v"(b.bs), [biB] "+v"(b.bi), [maskB] "+s"(b.mask), [cntn] "+s"(cnt_n), [cntt] "+s"(cnt_t), [cntp] "+s"(sp_max) \
+		MRT_ROWSW_EXIT(MRT_ROWS_EXIT_WAIT, "s[60:61]", "s[62:63]")                                                  \
+		: MRT_ROWSW_OUT                                                                                             \
 		: MRT_ROWS_IN(A, a), MRT_ROWS_IN(B, b), [rows] "s"(rows), [qmask] "s"(qmask),                                \
 		  [eps] "s"(eps), [vneg] "v"(vneg), [cw] "v"(cull.w), [ccc] "v"(cull.cc), [cvo] "v"(cull.voff)               \
 		: MRT_ROWS_CLOBBERS, "v61", "v62")
@@ -927,7 +870,33 @@ struct CullRegs {
 #define MRT_ROWS_CNT_P "s_nop 0\n v_readfirstlane_b32 s52, %[spA]\n s_max_u32 %[cntp], %[cntp], s52\n"
 #define MRT_ROWS_CNT_T "s_add_u32 %[cntt], %[cntt], 1\n"
 
-// wave-uniform operands come back from an asm block as SGPRs; this tells the compiler they still are
+// ---- the forms of a walk ----------------------------------------------------------------------------------------------------------
+// A walk function holds 8 octants x (counting or not) x (any hit or nearest) asm blocks, of which a template instantiation keeps one.
+// The eight octants: ROW(octant, sign bit of x, of y, of z)
+#define MRT_OCTANTS(ROW) ROW(0, 0, 0, 0) ROW(1, 1, 0, 0) ROW(2, 0, 1, 0) ROW(3, 1, 1, 0) ROW(4, 0, 0, 1) ROW(5, 1, 0, 1) ROW(6, 0, 1, 1) ROW(7, 1, 1, 1)
+// The four forms of octant O: LOOP(counting arguments, hit arguments, BX, BY, BZ) with COUNTING or PLAIN, ANY or NEAREST: the
+// argument lists of that loop, as below
+#define MRT_WALK_FORMS(LOOP, COUNTING, PLAIN, ANY, NEAREST, O, BX, BY, BZ)                                            \
+	if (OCT == O) {                                                                                                 \
+		if (COUNT) { if (ANY_HIT) LOOP(COUNTING, ANY, BX, BY, BZ); else LOOP(COUNTING, NEAREST, BX, BY, BZ); }      \
+		else { if (ANY_HIT) LOOP(PLAIN, ANY, BX, BY, BZ); else LOOP(PLAIN, NEAREST, BX, BY, BZ); }                  \
+	}
+#define MRT_ROWS1_COUNTING MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWS_T_PRE, MRT_ROWS_T_POST
+#define MRT_ROWS1_PLAIN "", "", "", "", ""
+#define MRT_ROWS1_ANY MRT_ROWS_ANYHIT("A", "4")
+#define MRT_ROWS1_NEAREST MRT_ROWS_NEAREST("A")
+#define MRT_ROWSW_COUNTING MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P
+#define MRT_ROWSW_PLAIN "", "", ""
+#define MRT_ROWSW_ANY MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE
+#define MRT_ROWSW_NEAREST MRT_ROWS_NEAREST("A"), MRT_ROWS_NEAREST("B"), ""
+// the eight cases of a switch on a wave-uniform octant: WALK<octant, ANY_HIT, COUNT>(arguments)
+#define MRT_OCT_CASE(O, WALK, ...) case O: WALK<O, ANY_HIT, COUNT>(__VA_ARGS__); break;
+#define MRT_OCT_SWITCH(OCT, WALK, ...)                                                                                \
+	switch (OCT) { MRT_OCT_CASE(0, WALK, __VA_ARGS__) MRT_OCT_CASE(1, WALK, __VA_ARGS__) MRT_OCT_CASE(2, WALK, __VA_ARGS__) MRT_OCT_CASE(3, WALK, __VA_ARGS__) \
+		MRT_OCT_CASE(4, WALK, __VA_ARGS__) MRT_OCT_CASE(5, WALK, __VA_ARGS__) MRT_OCT_CASE(6, WALK, __VA_ARGS__) MRT_OCT_CASE(7, WALK, __VA_ARGS__) }
+
+// wave-uniform operands come back from an asm block as SGPRs; this tells the compiler they still are (MRT_UNIFORM: one counter)
+#define MRT_UNIFORM(X) X = __builtin_amdgcn_readfirstlane(X)
 __device__ __forceinline__ void rows_uniform(PacketRegs &s)
 {
 	s.cur = __builtin_amdgcn_readfirstlane(s.cur);
@@ -942,19 +911,12 @@ __device__ __forceinline__ void rows_walk_one(const float4 *rows, uint32_t qmask
 	uint32_t ev = 0u;
 	// (the counters go into the block as scalars: constants where nothing is counted, else told to be uniform as on the way out)
 	if (!COUNT) { cnt_n = 0u; cnt_t = 0u; cnt_w = 0u; sp_max = 0u; }
-	else { cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t); cnt_w = __builtin_amdgcn_readfirstlane(cnt_w); sp_max = __builtin_amdgcn_readfirstlane(sp_max); }
-#define MRT_W1(O, BX, BY, BZ)                                                                                         \
-	if (OCT == O) {                                                                                                 \
-		if (COUNT) { if (ANY_HIT) MRT_ROWS_LOOP1(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWS_T_PRE, MRT_ROWS_T_POST, MRT_ROWS_ANYHIT("A", "4"), BX, BY, BZ); \
-			else MRT_ROWS_LOOP1(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWS_T_PRE, MRT_ROWS_T_POST, MRT_ROWS_NEAREST("A"), BX, BY, BZ); } \
-		else { if (ANY_HIT) MRT_ROWS_LOOP1("", "", "", "", "", MRT_ROWS_ANYHIT("A", "4"), BX, BY, BZ);              \
-			else MRT_ROWS_LOOP1("", "", "", "", "", MRT_ROWS_NEAREST("A"), BX, BY, BZ); }                           \
-	}
-	MRT_W1(0, 0, 0, 0) MRT_W1(1, 1, 0, 0) MRT_W1(2, 0, 1, 0) MRT_W1(3, 1, 1, 0) MRT_W1(4, 0, 0, 1) MRT_W1(5, 1, 0, 1) MRT_W1(6, 0, 1, 1) MRT_W1(7, 1, 1, 1)
-#undef MRT_W1
+	else { MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(cnt_w); MRT_UNIFORM(sp_max); }
+#define MRT_ROW(O, BX, BY, BZ) MRT_WALK_FORMS(MRT_ROWS_LOOP1, MRT_ROWS1_COUNTING, MRT_ROWS1_PLAIN, MRT_ROWS1_ANY, MRT_ROWS1_NEAREST, O, BX, BY, BZ)
+	MRT_OCTANTS(MRT_ROW)
+#undef MRT_ROW
 	rows_uniform(a);
-	cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t); cnt_w = __builtin_amdgcn_readfirstlane(cnt_w);
-	sp_max = __builtin_amdgcn_readfirstlane(sp_max);
+	MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(cnt_w); MRT_UNIFORM(sp_max);
 }
 
 template <int OCT, bool ANY_HIT, bool COUNT>
@@ -962,19 +924,12 @@ __device__ __forceinline__ void rows_walk_wide(const float4 *rows, uint32_t qmas
 {
 	const float eps = 1e-8f, vneg = -FLT_MAX;
 	if (!COUNT) { cnt_n = 0u; cnt_t = 0u; sp_max = 0u; }
-	else { cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t); sp_max = __builtin_amdgcn_readfirstlane(sp_max); }
-#define MRT_WW(O, BX, BY, BZ)                                                                                         \
-	if (OCT == O) {                                                                                                 \
-		if (COUNT) { if (ANY_HIT) MRT_ROWS_LOOPW(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE, BX, BY, BZ); \
-			else MRT_ROWS_LOOPW(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWS_NEAREST("A"), MRT_ROWS_NEAREST("B"), "", BX, BY, BZ); } \
-		else { if (ANY_HIT) MRT_ROWS_LOOPW("", "", "", MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE, BX, BY, BZ); \
-			else MRT_ROWS_LOOPW("", "", "", MRT_ROWS_NEAREST("A"), MRT_ROWS_NEAREST("B"), "", BX, BY, BZ); }        \
-	}
-	MRT_WW(0, 0, 0, 0) MRT_WW(1, 1, 0, 0) MRT_WW(2, 0, 1, 0) MRT_WW(3, 1, 1, 0) MRT_WW(4, 0, 0, 1) MRT_WW(5, 1, 0, 1) MRT_WW(6, 0, 1, 1) MRT_WW(7, 1, 1, 1)
-#undef MRT_WW
+	else { MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(sp_max); }
+#define MRT_ROW(O, BX, BY, BZ) MRT_WALK_FORMS(MRT_ROWS_LOOPW, MRT_ROWSW_COUNTING, MRT_ROWSW_PLAIN, MRT_ROWSW_ANY, MRT_ROWSW_NEAREST, O, BX, BY, BZ)
+	MRT_OCTANTS(MRT_ROW)
+#undef MRT_ROW
 	rows_uniform(a);
-	cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t);
-	sp_max = __builtin_amdgcn_readfirstlane(sp_max);
+	MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(sp_max);
 }
 
 template <int OCT, bool ANY_HIT, bool COUNT>
@@ -982,19 +937,12 @@ __device__ __forceinline__ void rows_walk_cull(const float4 *rows, uint32_t qmas
 {
 	const float eps = 1e-8f, vneg = -FLT_MAX;
 	if (!COUNT) { cnt_n = 0u; cnt_t = 0u; sp_max = 0u; }
-	else { cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t); sp_max = __builtin_amdgcn_readfirstlane(sp_max); }
-#define MRT_WC(O, BX, BY, BZ)                                                                                         \
-	if (OCT == O) {                                                                                                 \
-		if (COUNT) { if (ANY_HIT) MRT_ROWS_LOOPC(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE, BX, BY, BZ); \
-			else MRT_ROWS_LOOPC(MRT_ROWS_CNT_N, MRT_ROWS_CNT_T, MRT_ROWS_CNT_P, MRT_ROWS_NEAREST("A"), MRT_ROWS_NEAREST("B"), "", BX, BY, BZ); } \
-		else { if (ANY_HIT) MRT_ROWS_LOOPC("", "", "", MRT_ROWSW_ANYHIT("A"), MRT_ROWSW_ANYHIT("B"), MRT_ROWSW_ANYDONE, BX, BY, BZ); \
-			else MRT_ROWS_LOOPC("", "", "", MRT_ROWS_NEAREST("A"), MRT_ROWS_NEAREST("B"), "", BX, BY, BZ); }        \
-	}
-	MRT_WC(0, 0, 0, 0) MRT_WC(1, 1, 0, 0) MRT_WC(2, 0, 1, 0) MRT_WC(3, 1, 1, 0) MRT_WC(4, 0, 0, 1) MRT_WC(5, 1, 0, 1) MRT_WC(6, 0, 1, 1) MRT_WC(7, 1, 1, 1)
-#undef MRT_WC
+	else { MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(sp_max); }
+#define MRT_ROW(O, BX, BY, BZ) MRT_WALK_FORMS(MRT_ROWS_LOOPC, MRT_ROWSW_COUNTING, MRT_ROWSW_PLAIN, MRT_ROWSW_ANY, MRT_ROWSW_NEAREST, O, BX, BY, BZ)
+	MRT_OCTANTS(MRT_ROW)
+#undef MRT_ROW
 	rows_uniform(a);
-	cnt_n = __builtin_amdgcn_readfirstlane(cnt_n); cnt_t = __builtin_amdgcn_readfirstlane(cnt_t);
-	sp_max = __builtin_amdgcn_readfirstlane(sp_max);
+	MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(sp_max);
 }
 
 // The packet's culling pyramid.  Culling is on only if every ray of the two tiles starts at one point (bit for bit),
@@ -1302,23 +1250,17 @@ __device__ __forceinline__ bool rows_walks_and_records(const TraceParams &p, Row
 		A.mask = part_a; B.mask = part_b;
 		if (CULL) {
 			const CullRegs cull = cull_setup(ra, rb, valid_a, valid_b, part_a, part_b, p.scene_abs_max, lane);
-#define MRT_RWC(O) case O: rows_walk_cull<O, ANY_HIT, COUNT>(rows, p.query_mask, A, B, cull, cnt_n, cnt_t, sp_wide); break;
-			switch (oct_a) { MRT_RWC(0) MRT_RWC(1) MRT_RWC(2) MRT_RWC(3) MRT_RWC(4) MRT_RWC(5) MRT_RWC(6) MRT_RWC(7) }
-#undef MRT_RWC
+			MRT_OCT_SWITCH(oct_a, rows_walk_cull, rows, p.query_mask, A, B, cull, cnt_n, cnt_t, sp_wide)
 		} else {
-#define MRT_RW2(O) case O: rows_walk_wide<O, ANY_HIT, COUNT>(rows, p.query_mask, A, B, cnt_n, cnt_t, sp_wide); break;
-		switch (oct_a) { MRT_RW2(0) MRT_RW2(1) MRT_RW2(2) MRT_RW2(3) MRT_RW2(4) MRT_RW2(5) MRT_RW2(6) MRT_RW2(7) }
-#undef MRT_RW2
+			MRT_OCT_SWITCH(oct_a, rows_walk_wide, rows, p.query_mask, A, B, cnt_n, cnt_t, sp_wide)
 		}
 		done_a = done_b = true;
 		if (FAST) { rows_fast_records<STREAM>(w, A, B); return true; }
 	}
 	if (FAST) return false; // (tiles on an image axis, mixed directions in a tile: the general code below takes the wave on)
 	// packets that could not be paired (different octants: tiles on an image axis; a single packet): one at a time
-#define MRT_RW1(O, S) case O: rows_walk_one<O, ANY_HIT, COUNT>(rows, p.query_mask, S, cnt_n, cnt_t, cnt_w, sp_one); break;
-	if (!done_a && oct_a != 8) { switch (oct_a) { MRT_RW1(0, A) MRT_RW1(1, A) MRT_RW1(2, A) MRT_RW1(3, A) MRT_RW1(4, A) MRT_RW1(5, A) MRT_RW1(6, A) MRT_RW1(7, A) } done_a = true; }
-	if (PACKETS == 2 && !done_b && oct_b != 8) { switch (oct_b) { MRT_RW1(0, B) MRT_RW1(1, B) MRT_RW1(2, B) MRT_RW1(3, B) MRT_RW1(4, B) MRT_RW1(5, B) MRT_RW1(6, B) MRT_RW1(7, B) } done_b = true; }
-#undef MRT_RW1
+	if (!done_a && oct_a != 8) { MRT_OCT_SWITCH(oct_a, rows_walk_one, rows, p.query_mask, A, cnt_n, cnt_t, cnt_w, sp_one) done_a = true; }
+	if (PACKETS == 2 && !done_b && oct_b != 8) { MRT_OCT_SWITCH(oct_b, rows_walk_one, rows, p.query_mask, B, cnt_n, cnt_t, cnt_w, sp_one) done_b = true; }
 	const TraceParams &p2 = p;
 	// best hit as the other kernels keep it: leaf-order slot = row - number of node rows
 	uint32_t slot_a = A.bs == 0xFFFFFFFFu ? 0xFFFFFFFFu : A.bs - p2.n_nodes, slot_b = B.bs == 0xFFFFFFFFu ? 0xFFFFFFFFu : B.bs - p2.n_nodes;
