@@ -276,7 +276,7 @@ uint32_t mrt_version(void);
  * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light, 6 mrt_material,
  * 7 mrt_shade_data, 8 mrt_surface64, 9 mrt_surface_out, 11 mrt_shade_light, 12 mrt_environment, 13 mrt_light_out,
  * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set, 22 mrt_panorama,
- * 24 mrt_channel_out, 26 mrt_accum_state, 28 mrt_denoise_params, 30 mrt_gbuffer (0 for anything else). */
+ * 24 mrt_channel_out, 26 mrt_accum_state, 28 mrt_denoise_params, 30 mrt_gbuffer, 32 mrt_svgf_params (0 for anything else). */
 uint32_t mrt_struct_size(uint32_t which);
 /* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream): from here on it is "the context's stream".
  * What a caller that shares its stream may rely on (tests/test_caller_stream_gpu.py holds every entry point to it):
@@ -1271,7 +1271,8 @@ int mrt_accum_end_frame(mrt_accum_state *st, uint64_t pixels);
  * MRT_ERR_INVALID before any device work, in this order: a null context, d_source or d_accum; an unknown flag; an unknown
  * source_kind; tonemap_mode > 4 for LIT and PATH_STATE (not looked at for RGBA); n_prior > 0x7ffffffe; d_accum == d_source;
  * count * 32 overflowing.  Then MRT_ERR_PENDING while a dispatch is pending.
- * Not taken: variance estimates and reprojection of the mean when the camera moves.  (The reflection effect's denoisers: below.) */
+ * The mean itself is not reprojected when the camera moves and carries no variance: that is the SVGF chain's work (mrt_svgf_*,
+ * below), which a renderer runs in place of this call.  (The reflection effect's denoisers: below.) */
 enum { MRT_ACCUM_SRC_RGBA = 0, MRT_ACCUM_SRC_LIT = 1, MRT_ACCUM_SRC_PATH_STATE = 2 };
 int mrt_accumulate(mrt_ctx *ctx, uint32_t source_kind, const void *d_source, uint64_t count, uint32_t tonemap_mode,
 		uint32_t n_prior, float *d_accum, uint8_t *d_rgba8, uint32_t flags);
@@ -1372,6 +1373,123 @@ int mrt_resolve_reflections(mrt_ctx *ctx, const mrt_denoise_params *params, uint
  * inv_depth_range; count * 64 overflowing.  Then MRT_ERR_PENDING. */
 int mrt_reflection_guides(mrt_ctx *ctx, const mrt_hit32 *d_hits, const mrt_surface64 *d_rows, uint64_t count, float inv_depth_range,
 		float *d_depth, float *d_normal_roughness, uint32_t flags);
+/* ---- a path-traced frame denoised on the device: an SVGF pass chain (spatiotemporal variance-guided filtering: temporal
+ * accumulation with reprojection and disocclusion detection, a variance estimate, an a-trous wavelet filter with edge-stopping on
+ * normal, depth and luminance, guided by albedo, normal and depth).  The reference has no such code (its roadmap names it); the
+ * definition is this project's, stated like the passes above: fp32 operations in a fixed order, one rounding each, nothing contracted,
+ * reproducible on the CPU bit for bit (messyerraytracer_amd/svgf.py).  A frame of a renderer is
+ *   the casts and passes of a path-traced frame -> mrt_svgf_guides -> mrt_svgf_frame (= temporal -> variance -> a-trous x iterations
+ *   -> modulate), and the caller swaps its two sets of history images.
+ * No pass traces a ray.  A renderer chooses per frame between this chain and the running mean of mrt_accumulate; neither feeds the other.
+ *
+ * Images: device arrays, row-major, pixel (x, y) at index y * W + x, 4 floats per pixel:
+ *   illum         {r, g, b, variance}   the radiance divided by the albedo, and the variance of its luminance
+ *   moments       {m1, m2, history_length, 0}   history_length an integer-valued float
+ *   normal_depth  {n.x, n.y, n.z, t}    t <= 0 marks a miss
+ *   position      {p.x, p.y, p.z, 0}
+ *   albedo        {r, g, b, 1}
+ * a . b = (a.x * b.x + a.y * b.y) + a.z * b.z.  lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b.  max_of(a, b) = a < b ? b : a
+ * and min_of(a, b) = b < a ? b : a (a NaN first argument is kept), expn_def and pow01 as above.  Sums are written in the order they
+ * are added: s = s + v * w means one product, one sum.
+ *
+ * 1. mrt_svgf_guides, per record i (a stream, array form; a host with a grid passes the rays of mrt_generate_grid).  The radiance is
+ *    d_source in one of mrt_accumulate's two linear kinds: MRT_ACCUM_SRC_RGBA (4 floats per pixel, the fourth not read) or
+ *    MRT_ACCUM_SRC_PATH_STATE (mrt_path_state, of which only the second 16 bytes are read); no tone mapping.
+ *    A miss (prim_id == -1): illum = {radiance, 0}; albedo = {1, 1, 1, 1}; normal_depth and position all zero.
+ *    A hit: a.c = max_of(row.albedo.c, 0.001f); illum = {radiance.c / a.c, 0}; albedo = {a, 1}; normal_depth = {row.normal, t};
+ *    position.c = origin.c + direction.c * t (one product, one sum), position.w = 0.
+ *
+ * 2. mrt_svgf_temporal, per pixel; cur, nd, p = this frame's illum, normal_depth, position; l = lum(cur).
+ *    nd.t <= 0: illum = {cur.rgb, 0}, moments = {0, 0, 0, 0}.
+ *    History, only with has_history != 0 (otherwise the previous images and the camera are not read and may be null).  The camera is
+ *    the previous frame's, MRT_CAMERA_PERSPECTIVE:
+ *      e = p - origin; cx = e . right; cy = e . up; cz = e . fwd; none unless cz < 0.  w = -cz;
+ *      u = (cx / w) / half_w; v = (cy / w) / half_h;
+ *      fx = ((u + 1.0f) * 0.5f) * (float)W - jitter_x; fy = ((1.0f - v) * 0.5f) * (float)H - jitter_y
+ *      (the inverse of generate_ray_jittered: a pixel's sample stands at x + jitter_x);
+ *      none unless fx >= -1 and fx < (float)W and fy >= -1 and fy < (float)H, tested on the floats (a NaN fails).
+ *      x0 = floorf(fx), ax = fx - x0, bx = 1 - ax; likewise y.  Taps (x0 + i, y0 + j) in the order (0,0), (1,0), (0,1), (1,1) with
+ *      weights bx * by, ax * by, bx * ay, ax * ay.  A tap counts only if it lies inside the image (no clamping), then
+ *      prev_normal_depth.t > 0, then n . n_prev >= normal_threshold, then with d = p - p_prev: d . d <= bound * bound,
+ *      bound = position_threshold * nd.t (each test fails for a NaN).  For a counted tap: sum.k = sum.k + prev.k * weight for
+ *      k = r, g, b, m1, m2; weight_sum = weight_sum + weight; N_prev = the first counted tap's history_length, after that
+ *      min_of(N_prev, the tap's) -- a minimum, not an interpolation, so that it stays an exact integer.
+ *      History exists iff weight_sum > 0.01f; then hist.k = sum.k / weight_sum.
+ *    With history: N = min_of(N_prev + 1.0f, max_history); inv = 1.0f / N; alpha = max_of(color_alpha, inv);
+ *      alpha_m = max_of(moments_alpha, inv); om = 1 - alpha; rgb.k = hist.k * om + cur.k * alpha; omm = 1 - alpha_m;
+ *      m1 = hist.m1 * omm + l * alpha_m; m2 = hist.m2 * omm + (l * l) * alpha_m; variance = max_of(m2 - m1 * m1, 0);
+ *      moments = {m1, m2, N, 0}.
+ *    Without: illum = {cur.rgb, 0}; moments = {l, l * l, 1, 0}.
+ *    d_out_illum may be d_illum (a pixel reads only its own).  No output may be a previous-frame image: those are read across pixels.
+ *
+ * 3. mrt_svgf_variance: the spatial estimate for young pixels.  out = in for nd.t <= 0, then for history_length >= 4.  Otherwise taps
+ *    dy = -3 .. 3 outer, dx = -3 .. 3 inner, both ascending.  The centre has weight 1.  Any other tap s is skipped if it lies outside
+ *    the image, then if its t <= 0, then if dot = n_c . n_s <= 0; else
+ *      ez = |n_c . (p_s - p_c)| / (sigma_plane * t_c); weight = expn_def(-ez) * pow01(dot, sigma_n);
+ *    s1 = s1 + m1_s * weight; s2 = s2 + m2_s * weight; weight_sum = weight_sum + weight.  m1 = s1 / weight_sum, m2 likewise;
+ *    variance = max_of(m2 - m1 * m1, 0) * (4.0f / history_length); rgb unchanged.
+ *
+ * 4. mrt_svgf_atrous: one iteration, step in {1, 2, 4, 8, 16}.  A centre with t <= 0 is copied.  var_c: taps dy = -1 .. 1 outer,
+ *    dx inner, at stride 1, g = 1/4 (centre), 1/8 (edge), 1/16 (corner); taps outside the image are skipped (no other test);
+ *    sv = sv + variance_s * g; sg = sg + g; var_c = sv / sg.  denom = sigma_l * sqrtf(var_c) + 1e-4f.
+ *    Taps j = -2 .. 2 outer, i = -2 .. 2 inner at (x + i * step, y + j * step); h = {1/16, 1/4, 3/8, 1/4, 1/16}.  The centre has
+ *    weight h[2] * h[2] and no exponent.  Any other tap is skipped as in pass 3; else
+ *      el = |lum(c) - lum(s)| / denom; weight = ((h[i] * h[j]) * expn_def(-(ez + el))) * pow01(dot, sigma_n)
+ *    (one exponential serves the plane and the luminance terms).  sum.k = sum.k + s.k * weight for r, g, b;
+ *    sv = sv + variance_s * (weight * weight); ws = ws + weight.  rgb.k = sum.k / ws; variance = sv / (ws * ws).
+ *
+ * 5. mrt_svgf_modulate: c = illum.c * albedo.c, then tone mapping and gamma exactly as mrt_path_finish applies them (the same device
+ *    functions); alpha 1; d_rgba8 (optional) = to_rgba8 of the four floats.  d_rgba may be d_illum.
+ *
+ * 6. mrt_svgf_frame: host sequencing only, word for word what the separate calls give:
+ *    temporal(d_illum, previous frame) -> (d_scratch_a, d_next_moments); variance(d_scratch_a) -> d_scratch_b;
+ *    a-trous step 1 (d_scratch_b) -> d_next_illum: the filtered illumination fed back as the next frame's history; then, for
+ *    iterations > 1, steps 2, 4, .. from d_next_illum into d_scratch_a, then alternating d_scratch_b, d_scratch_a; modulate(the last
+ *    output, d_albedo) -> d_rgba, d_rgba8.  The next frame's history is d_next_illum, d_next_moments and this frame's normal_depth
+ *    and position.
+ *
+ * The calls are ordered on the context's stream, take MRT_FLAG_ASYNC, and touch neither the scene, the tuner, the tile schedule nor
+ * mrt_stats.  W == 0 or H == 0 (count == 0): MRT_OK, nothing written.  MRT_ERR_INVALID before any device work, in this order:
+ *   the five calls with params: a null context; a null params; a null image, each in the order of the call's arguments (d_rgba8 is
+ *   optional; with has_history == 0 the previous images are not looked at); struct_size not sizeof(mrt_svgf_params); an unknown flag;
+ *   temporal and frame with has_history != 0: a null prev_cam, then a kind that is not MRT_CAMERA_PERSPECTIVE; a-trous: a step not in
+ *   {1, 2, 4, 8, 16}; frame: iterations not in 1 .. 5; modulate and frame: tonemap_mode > 4; a non-finite float of params (in the
+ *   struct's order); max_history < 1; a threshold or sigma that is not > 0 (normal_threshold, position_threshold, sigma_l, sigma_n,
+ *   sigma_plane, in this order); W * H * 32 overflowing; an output that is an image read across pixels (temporal: an output equal
+ *   to a previous-frame image, or the two outputs equal; variance and a-trous: d_out equal to an input; frame: any written image
+ *   equal to any read image or to another written image).
+ *   mrt_svgf_guides: a null context, d_rays, d_hits, d_rows, d_source, d_illum, d_albedo, d_normal_depth, d_position; an unknown
+ *   flag; a source_kind that is neither MRT_ACCUM_SRC_RGBA nor MRT_ACCUM_SRC_PATH_STATE; count * 64 overflowing; two outputs equal.
+ * Then MRT_ERR_PENDING while a dispatch is pending.
+ * Not taken: motion vectors (reprojection assumes static world positions: geometry that moved restarts its history through the
+ * position test), orthographic reprojection, SVGF's 3x3 fallback search, half-float images. */
+typedef struct mrt_svgf_params {           /* 48 bytes; defaults in brackets */
+	uint32_t struct_size;                  /* sizeof(mrt_svgf_params) */
+	uint32_t has_history;                  /* 0: the first frame */
+	uint32_t iterations;                   /* [5] a-trous passes of mrt_svgf_frame, 1 .. 5 */
+	uint32_t tonemap_mode;                 /* 0 .. 4, as mrt_path_finish */
+	float color_alpha, moments_alpha;      /* [0.2, 0.2] the current frame's least share */
+	float max_history;                     /* [32] */
+	float normal_threshold;                /* [0.95] */
+	float position_threshold;              /* [0.05] a fraction of the pixel's depth */
+	float sigma_l, sigma_n, sigma_plane;   /* [4, 128, 0.01] */
+} mrt_svgf_params;
+int mrt_svgf_guides(mrt_ctx *ctx, const mrt_ray32 *d_rays, const mrt_hit32 *d_hits, const mrt_surface64 *d_rows, uint32_t source_kind,
+		const void *d_source, uint64_t count, float *d_illum, float *d_albedo, float *d_normal_depth, float *d_position, uint32_t flags);
+int mrt_svgf_temporal(mrt_ctx *ctx, const mrt_svgf_params *params, uint32_t W, uint32_t H, const float *d_illum,
+		const float *d_normal_depth, const float *d_position, const mrt_camera *prev_cam, const float *d_prev_illum,
+		const float *d_prev_moments, const float *d_prev_normal_depth, const float *d_prev_position, float *d_out_illum,
+		float *d_out_moments, uint32_t flags);
+int mrt_svgf_variance(mrt_ctx *ctx, const mrt_svgf_params *params, uint32_t W, uint32_t H, const float *d_illum, const float *d_moments,
+		const float *d_normal_depth, const float *d_position, float *d_out, uint32_t flags);
+int mrt_svgf_atrous(mrt_ctx *ctx, const mrt_svgf_params *params, uint32_t W, uint32_t H, uint32_t step, const float *d_illum,
+		const float *d_normal_depth, const float *d_position, float *d_out, uint32_t flags);
+int mrt_svgf_modulate(mrt_ctx *ctx, const mrt_svgf_params *params, uint32_t W, uint32_t H, const float *d_illum, const float *d_albedo,
+		float *d_rgba, uint8_t *d_rgba8, uint32_t flags);
+int mrt_svgf_frame(mrt_ctx *ctx, const mrt_svgf_params *params, uint32_t W, uint32_t H, const float *d_illum, const float *d_albedo,
+		const float *d_normal_depth, const float *d_position, const mrt_camera *prev_cam, const float *d_prev_illum,
+		const float *d_prev_moments, const float *d_prev_normal_depth, const float *d_prev_position, float *d_next_illum,
+		float *d_next_moments, float *d_scratch_a, float *d_scratch_b, float *d_rgba, uint8_t *d_rgba8, uint32_t flags);
 /* ---- the reflection effect's first pass from a rasteriser's G-buffer: RTReflectionEffect pass 1
  * (src/gpu/shaders/rt_reflections.comp.glsl:276-332) as it runs inside a rasterised frame.  A host that rasterises has no hit records
  * and no primary rays; it has a depth buffer and a normal-roughness buffer.  mrt_cast_gbuffer_reflections makes the reflection ray of

@@ -38,6 +38,7 @@ SYMBOLS = [
     "mrt_shade_channels", "mrt_shade_grid_channels", "mrt_finish_color", "mrt_image_to_rgba8",
     "mrt_halton_jitter", "mrt_accum_begin_frame", "mrt_accum_end_frame", "mrt_accumulate",
     "mrt_denoise_spatial", "mrt_denoise_temporal", "mrt_composite_reflections", "mrt_resolve_reflections", "mrt_reflection_guides",
+    "mrt_svgf_guides", "mrt_svgf_temporal", "mrt_svgf_variance", "mrt_svgf_atrous", "mrt_svgf_modulate", "mrt_svgf_frame",
     "mrt_cast_gbuffer_reflections", "mrt_reflection_image",
     "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
     "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
@@ -150,6 +151,7 @@ TEXTURES_ON_DEVICE = 1
 TEXEL_RGBA8, TEXEL_RGBA32F = 0, 1
 PANORAMA_ON_DEVICE = 1
 PANORAMA_MAX_DIM = 16384
+STRUCT_SVGF_PARAMS = 32   # mrt_struct_size index (31: not a struct); the struct and the calls: svgf.py
 STRUCT_GBUFFER = 30   # mrt_struct_size index (29: not a struct); the struct and the calls: gbuffer.py
 STRUCT_DENOISE_PARAMS = 28   # mrt_struct_size index (27: not a struct); the struct and the calls: denoise.py
 STRUCT_ACCUM_STATE = 26   # mrt_struct_size index (25: not a struct)

@@ -66,6 +66,15 @@ hipError_t launch_reflection_guides(const mrt_hit32 *hits, const mrt_surface64 *
 		float *guide, hipStream_t stream);
 // the reflection image of a G-buffer cast (gbuffer_image_kernel.h): s = the frame and its G-buffer (out_rays and max_distance unused)
 hipError_t launch_reflection_image(const GBufferParams &s, const mrt_hit32 *hits, const float *lit, float *out, hipStream_t stream);
+// the SVGF pass chain (svgf_kernel.h); kind = MRT_ACCUM_SRC_RGBA or _PATH_STATE; spatial: atrous ? pass 4 at a.step : pass 3
+namespace sv { struct SvgfArgs; }
+hipError_t launch_svgf_guides(int kind, const mrt_ray32 *rays, const mrt_hit32 *hits, const mrt_surface64 *rows, const void *source, uint64_t count,
+		float *illum, float *albedo, float *normal_depth, float *position, hipStream_t stream);
+hipError_t launch_svgf_temporal(const sv::SvgfArgs &a, const float *illum, const float *normal_depth, const float *position, const float *prev_illum,
+		const float *prev_moments, const float *prev_normal_depth, const float *prev_position, float *out_illum, float *out_moments, hipStream_t stream);
+hipError_t launch_svgf_spatial(bool atrous, const sv::SvgfArgs &a, const float *illum, const float *moments, const float *normal_depth,
+		const float *position, float *out, hipStream_t stream);
+hipError_t launch_svgf_modulate(const sv::SvgfArgs &a, const float *illum, const float *albedo, float *rgba, uint8_t *rgba8, hipStream_t stream);
 // ---- device_build.hip
 hipError_t grow_arena(BuildArena *arena, size_t need, hipStream_t stream); // hipErrorOutOfMemory: no allocation, the arena is empty
 hipError_t launch_collapse4(const DevNode *nodes, uint32_t n_nodes, Dev4Node *nodes4, hipStream_t stream);

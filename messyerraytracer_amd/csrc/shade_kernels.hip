@@ -1,6 +1,6 @@
 // shade_kernels.hip — gfx950 kernels of the shading passes over hit records: the resolve to shading surfaces (plain and textured), the
 // direct light and the path tracer's per-pixel state (the lighting and the step also with a resident panorama), the renderer's
-// channels with the two image passes, the running mean of progressive frames, the reflection effect's image passes, and the packing of shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
+// channels with the two image passes, the running mean of progressive frames, the reflection effect's image passes, the SVGF pass chain, and the packing of shade rows.  None of them walks a scene; they share the ray and record helpers of device_common.h and record_surface of
 // source_common.h with the walks of kernels.hip, and are compiled apart from them.  The arithmetic is the canonical form of DESIGN.md
 // ("Arithmetic"), as in kernels.hip.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include "channels.h"
 #include "accum.h"
 #include "denoise.h"
+#include "svgf.h"
 #include "gbuffer.h"
 #include "lane_map.h"
 
@@ -27,6 +28,7 @@ namespace mrt {
 #include "path_frame_kernel.h"
 #include "accum_kernel.h"
 #include "denoise_kernel.h"
+#include "svgf_kernel.h"
 #include "surface_tex_kernel.h"
 #include "surface_kernel.h"
 #include "light_kernel.h"
@@ -116,6 +118,48 @@ hipError_t launch_reflection_image(const GBufferParams &s, const mrt_hit32 *hits
 	const uint64_t count = (uint64_t)s.w * s.h;
 	return launch_per_entry<true>(reflection_image_kernel, count, stream, s, count, hits, reinterpret_cast<const dn::Px4 *>(lit),
 			reinterpret_cast<dn::Px4 *>(out));
+}
+// the SVGF pass chain (svgf_kernel.h), called from svgf.hip
+hipError_t launch_svgf_guides(int kind, const mrt_ray32 *rays, const mrt_hit32 *hits, const mrt_surface64 *rows, const void *source, uint64_t count,
+		float *illum, float *albedo, float *normal_depth, float *position, hipStream_t stream)
+{
+	hipError_t e = count ? hipErrorInvalidValue : hipSuccess;
+	dispatch([&](auto KIND) { e = launch_per_entry<true>(svgf_guides_kernel<KIND>, count, stream, rays, hits, rows, source, count, reinterpret_cast<sv::Px4 *>(illum),
+				reinterpret_cast<sv::Px4 *>(albedo), reinterpret_cast<sv::Px4 *>(normal_depth), reinterpret_cast<sv::Px4 *>(position)); },
+			Among<(int)MRT_ACCUM_SRC_RGBA, (int)MRT_ACCUM_SRC_PATH_STATE>{kind});
+	return e;
+}
+static sv::Images svgf_images(const sv::SvgfArgs &a, const float *illum, const float *moments, const float *normal_depth, const float *position)
+{
+	return sv::Images{reinterpret_cast<const sv::Px4 *>(illum), reinterpret_cast<const sv::Px4 *>(moments), reinterpret_cast<const sv::Px4 *>(normal_depth),
+			reinterpret_cast<const sv::Px4 *>(position), a.w, a.h};
+}
+hipError_t launch_svgf_temporal(const sv::SvgfArgs &a, const float *illum, const float *normal_depth, const float *position, const float *prev_illum,
+		const float *prev_moments, const float *prev_normal_depth, const float *prev_position, float *out_illum, float *out_moments, hipStream_t stream)
+{
+	const uint64_t count = (uint64_t)a.w * a.h;
+	return launch_per_entry<true>(svgf_temporal_kernel, count, stream, a, count, reinterpret_cast<const sv::Px4 *>(illum),
+			reinterpret_cast<const sv::Px4 *>(normal_depth), reinterpret_cast<const sv::Px4 *>(position),
+			svgf_images(a, prev_illum, prev_moments, prev_normal_depth, prev_position), reinterpret_cast<sv::Px4 *>(out_illum),
+			reinterpret_cast<sv::Px4 *>(out_moments));
+}
+hipError_t launch_svgf_spatial(bool atrous, const sv::SvgfArgs &a, const float *illum, const float *moments, const float *normal_depth,
+		const float *position, float *out, hipStream_t stream)
+{
+	const uint64_t tiles_x = ((uint64_t)a.w + SV_TILE - 1) / SV_TILE, tiles = tiles_x * (((uint64_t)a.h + SV_TILE - 1) / SV_TILE);
+	if (tiles == 0) return hipSuccess;
+	if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	const sv::Images im = svgf_images(a, illum, moments, normal_depth, position);
+	auto *o = reinterpret_cast<sv::Px4 *>(out);
+	if (atrous) hipLaunchKernelGGL(svgf_spatial_kernel<true>, dim3((uint32_t)tiles), dim3(SV_TILE * SV_TILE), 0, stream, a, (uint32_t)tiles_x, im, o);
+	else hipLaunchKernelGGL(svgf_spatial_kernel<false>, dim3((uint32_t)tiles), dim3(SV_TILE * SV_TILE), 0, stream, a, (uint32_t)tiles_x, im, o);
+	return hipGetLastError();
+}
+hipError_t launch_svgf_modulate(const sv::SvgfArgs &a, const float *illum, const float *albedo, float *rgba, uint8_t *rgba8, hipStream_t stream)
+{
+	const uint64_t count = (uint64_t)a.w * a.h;
+	return launch_per_entry<true>(svgf_modulate_kernel, count, stream, a, count, reinterpret_cast<const sv::Px4 *>(illum),
+			reinterpret_cast<const sv::Px4 *>(albedo), rgba, rgba8);
 }
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream)
 {
