@@ -1073,6 +1073,72 @@ int mrt_path_grid_step(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uin
 int mrt_path_finish(mrt_ctx *ctx, const mrt_path_state *d_state, uint64_t count, uint32_t tonemap_mode, float *d_rgba,
 		uint32_t flags);
 
+/* ---- next-event estimation with one light per record: the light sampling of the reference's GPU path tracer
+ * (src/gpu/shaders/pt_shade.comp.glsl steps 6 and 1, gpu_path_tracer.cpp:334-336, :757).  Each record draws one light uniformly from
+ * its own PCG32 stream, traces one shadow ray to it, evaluates that light alone and scales the result by the number of lights: an
+ * unbiased estimator of the sum mrt_cast_shadows + mrt_light_surfaces compute, at one any-hit ray per record instead of n_lights.
+ * The reference draws its light first in stream order; these calls do not, and no call here reproduces the reference's GLSL stream.
+ * What is kept is the estimator: a uniform choice, the weight n_lights, one ray.  Per bounce a renderer queues
+ *   cast -> resolve -> selected shadows with select_draw = MRT_PATH_SELECT_DRAW(bounce) -> selected light with env = NULL -> step ->
+ *   bounce cast. */
+#define MRT_LIGHT_NONE 0xFFu                              /* the light byte of a record that selected no light */
+/* The draw of a pixel's stream that selects bounce b's light.  The draws mrt_cast_bounce and mrt_path_step take end at
+ * 3 * 32 + max(0, 32 - 2) + 3 = 129, so draws from 256 up collide with none of them. */
+#define MRT_PATH_SELECT_DRAW(bounce) (256u + (bounce))
+typedef struct mrt_light_select {                         /* 24 bytes */
+	uint32_t frame;            /* enters the seed, as mrt_bounce.frame; <= MRT_PATH_MAX_FRAME                         */
+	uint32_t select_draw;      /* the draw of the pixel's stream that selects the light                               */
+	const uint8_t *d_select;   /* optional device pointer, one byte per record: 0 = the record selects no light       */
+	uint8_t *d_out_light;      /* device pointer, one byte per record: the light selected, or MRT_LIGHT_NONE          */
+} mrt_light_select;
+/* One shadow ray per record, to the light the record selects.  d_rays, d_hits, lights, query_mask as for mrt_cast_shadows; d_mask one
+ * byte per record.  Per record i:
+ *   a miss, or d_select given and d_select[i] == 0: d_out_light[i] = MRT_LIGHT_NONE, d_mask[i] = 1, no ray.
+ *   otherwise k = out % n_lights in uint32 (the reference's pcg32_next(rng) % light_count), out = the output word of draw number
+ *     select_draw of the PCG32 stream of mrt_cast_hemisphere, with mrt_cast_bounce's seed and pixel_index rule (seed = pixel_index *
+ *     1009 + frame * 6529 + 7; array form: the record's index; grid form: y * grid_w + x of the whole grid, so a row band selects what
+ *     the whole frame selects).  d_out_light[i] = k.
+ *   The ray is that of mrt_cast_shadows for the pair (i, light k), operation for operation: org = p + n * 1e-3 with the record's normal
+ *     as given (not faced), t_min = 0; DIRECTIONAL: dir = direction as given, t_max = 1000; POINT / SPOT: to = position - org, dist =
+ *     sqrt((to.x*to.x + to.y*to.y) + to.z*to.z), dir = to / dist per component, t_max = dist.  cast_shadows == 0, or dist < 1e-6f: no
+ *     ray, d_mask[i] = 1.  Otherwise d_mask[i] = 1 - occluded (any-hit under query_mask).
+ * So d_mask[i] == M[d_out_light[i] * count + i] for the mask M mrt_cast_shadows writes for the same arguments.  `lights` and desc are
+ * host pointers, the rest device pointers.  Flags: MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC.  n_lights == 0: MRT_OK, nothing written, as
+ * mrt_cast_shadows; count == 0: MRT_OK.  MRT_ERR_INVALID, before any device work and in this order, for: a null required pointer
+ * (rays, hits, desc, mask, d_out_light, lights with n_lights > 0); an unknown flag; n_lights > MRT_MAX_LIGHTS; an unknown light type;
+ * frame > MRT_PATH_MAX_FRAME.  Then MRT_ERR_NO_SCENE, then MRT_ERR_PENDING while a dispatch is pending.  Flat and two-level scenes. */
+int mrt_cast_selected_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const mrt_light_select *desc,
+		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_hits as it wrote them, mrt_hit32; d_select, d_out_light and
+ * d_mask indexed by the record within the band): the primary rays are regenerated in the kernel.  count = grid_w * (y1 - y0).
+ * Flags: MRT_FLAG_ASYNC. */
+int mrt_cast_grid_selected_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const mrt_hit32 *d_hits, const mrt_light_select *desc, const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask,
+		uint32_t query_mask, uint32_t flags);
+
+/* Lights every record with the one light it selected.  Every argument as for mrt_light_surfaces, except: d_light (required, device),
+ * one byte per record, what mrt_cast_selected_shadows wrote to d_out_light; d_mask (optional, device; null: lit) one byte per record,
+ * what it wrote to d_mask.  For a hit, with k = d_light[i]:
+ *   k >= n_lights (MRT_LIGHT_NONE is), or d_mask given and d_mask[i] == 0: rgb = 0.
+ *   otherwise rgb.c = 0 + term_k.c, where term_k is exactly the addend mrt_light_surfaces adds for light k (its L, atten, ndl, h, D, G,
+ *     F and the sum's last line, operation for operation), or nothing where mrt_light_surfaces skips light k: dist < 1e-6f || dist >
+ *     range, atten < 1e-6f, ndl <= 0.
+ *   then rgb.c = rgb.c * (float)n_lights.
+ * env == NULL and env given behave exactly as in mrt_light_surfaces: the sky of a miss, and the ambient term and the emission of a hit
+ * added after the scaling; a panorama resident is sampled as there.  With env == NULL the output is what mrt_path_step takes as
+ * d_direct.  cos_outer is computed per call on the host for all lights, as there.  With n_lights == 1 and a d_light of zeros the output
+ * equals mrt_light_surfaces' word for word.  No scene is required and nothing is walked.  Flags: MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC.
+ * count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID and MRT_ERR_PENDING as mrt_light_surfaces, d_light among the required
+ * pointers. */
+int mrt_light_selected_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_hits, const mrt_surface64 *d_rows, uint64_t count,
+		const mrt_shade_light *lights, uint32_t n_lights, const uint8_t *d_light, const uint8_t *d_mask, const mrt_environment *env,
+		const mrt_light_out *out, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_rows, d_light, d_mask and the output indexed by the record
+ * within the band).  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_light_grid_selected_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const void *d_hits, const mrt_surface64 *d_rows, const mrt_shade_light *lights, uint32_t n_lights, const uint8_t *d_light,
+		const uint8_t *d_mask, const mrt_environment *env, const mrt_light_out *out, uint32_t flags);
+
 /* ---- resident panorama: the panorama half of ShadePass::EnvironmentData (panorama_data, _width, _height, _energy), the
  * equirectangular RGBAF32 image of a PanoramaSkyMaterial that ray_renderer.cpp:676-703 binds, held on the device, so that the
  * lighting calls and the path steps run sky_color's and shade_material's panorama branches (shade_pass.h:164-257, :684-711)

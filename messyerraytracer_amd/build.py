@@ -15,7 +15,7 @@ OBJ = os.path.join(HERE, "_obj")  # object files, their dependency files and the
 # passes over hit records, prep_kernels.hip = what prepares a scene or a cast; an edit to one is compiled apart from the others.
 SOURCES = ["kernels.hip", "shade_kernels.hip", "prep_kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip",
            "device_build.hip", "refit.hip", "tlas_device.hip", "surface.hip", "texture.hip", "lighting.hip", "path.hip", "panorama.hip", "channels.hip", "accum.hip", "denoise.hip", "svgf.hip",
-           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/accum_data.cpp", "host/denoise_data.cpp", "host/svgf_data.cpp", "host/gbuffer_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
+           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/accum_data.cpp", "host/denoise_data.cpp", "host/svgf_data.cpp", "host/gbuffer_data.cpp", "host/selected_shadow_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
 # implicitly (-ffp-contract=off), so every result is unchanged.
@@ -60,6 +60,9 @@ DRIVERS = {
     "gbuffer_data_test": (["host/gbuffer_data_test.cpp", "host/gbuffer_data.cpp"], CPU, False),  # gbuffer.h, shared with the kernels
     "gbuffer_data_test_san": (["host/gbuffer_data_test.cpp", "host/gbuffer_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
                                                                                              "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
+    "selected_shadow_data_test": (["host/selected_shadow_data_test.cpp", "host/selected_shadow_data.cpp"], CPU, False),  # selected_shadow.h
+    "selected_shadow_data_test_san": (["host/selected_shadow_data_test.cpp", "host/selected_shadow_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
+                                                                                                             "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
     "lane_map_test": (["host/lane_map_test.cpp"], LANE + ["-O2"], False),  # lane_map.h
     "lane_map_test_san": (["host/lane_map_test.cpp"], LANE + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
                                                               "-fno-sanitize-recover=undefined"], False),
@@ -230,6 +233,11 @@ def build_svgf_data_test(force: bool = False, sanitize: bool = False) -> str:
 def build_gbuffer_data_test(force: bool = False, sanitize: bool = False) -> str:
     """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
     return build_driver("gbuffer_data_test_san" if sanitize else "gbuffer_data_test", force)
+
+
+def build_selected_shadow_data_test(force: bool = False, sanitize: bool = False) -> str:
+    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
+    return build_driver("selected_shadow_data_test_san" if sanitize else "selected_shadow_data_test", force)
 
 
 def build_lane_map_test(force: bool = False, sanitize: bool = False) -> str:

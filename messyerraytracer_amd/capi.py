@@ -41,6 +41,7 @@ SYMBOLS = [
     "mrt_svgf_guides", "mrt_svgf_temporal", "mrt_svgf_variance", "mrt_svgf_atrous", "mrt_svgf_modulate", "mrt_svgf_frame",
     "mrt_cast_gbuffer_reflections", "mrt_reflection_image",
     "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
+    "mrt_cast_selected_shadows", "mrt_cast_grid_selected_shadows", "mrt_light_selected_surfaces", "mrt_light_grid_selected_surfaces",
     "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
     "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_schedule_counts", "mrt_debug_sort_order", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
@@ -83,6 +84,11 @@ class Bounce(C.Structure):
 
 
 LOBE_NONE, LOBE_DIFFUSE, LOBE_SPECULAR = 0, 1, 2
+
+
+class LightSelect(C.Structure):
+    """mrt_light_select (types.LIGHT_SELECT)"""
+    _fields_ = [("frame", C.c_uint32), ("select_draw", C.c_uint32), ("d_select", C.c_void_p), ("d_out_light", C.c_void_p)]
 
 
 class ShadeData(C.Structure):
@@ -151,6 +157,7 @@ TEXTURES_ON_DEVICE = 1
 TEXEL_RGBA8, TEXEL_RGBA32F = 0, 1
 PANORAMA_ON_DEVICE = 1
 PANORAMA_MAX_DIM = 16384
+STRUCT_LIGHT_SELECT = 34   # mrt_struct_size index (33: not a struct)
 STRUCT_SVGF_PARAMS = 32   # mrt_struct_size index (31: not a struct); the struct and the calls: svgf.py
 STRUCT_GBUFFER = 30   # mrt_struct_size index (29: not a struct); the struct and the calls: gbuffer.py
 STRUCT_DENOISE_PARAMS = 28   # mrt_struct_size index (27: not a struct); the struct and the calls: denoise.py
@@ -295,6 +302,15 @@ def load():
                                      C.c_void_p, C.POINTER(LightOut), C.c_uint32]
     L.mrt_light_grid_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(LightOut), C.c_uint32]
+    L.mrt_cast_selected_shadows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(LightSelect), C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_uint32, C.c_uint32]
+    L.mrt_cast_grid_selected_shadows.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.POINTER(LightSelect), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.mrt_light_selected_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(LightOut), C.c_uint32]
+    L.mrt_light_grid_selected_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LightOut),
+                                                   C.c_uint32]
     L.mrt_path_init.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
     L.mrt_path_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PathStepDesc), C.c_uint32]
     L.mrt_path_grid_step.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -357,6 +373,11 @@ def bounce_desc(frame, first_draw, t_max, metallic=0.0, roughness=0.5, d_select=
     """mrt_bounce from its fields (d_select, d_surface, d_out_lobe: device pointers / tensors or None)"""
     v = [None if x is None else _ptr(x).value for x in (d_select, d_surface, d_out_lobe)]
     return Bounce(frame, first_draw, t_max, metallic, roughness, v[0], v[1], v[2])
+
+
+def light_select_desc(frame, select_draw, d_out_light, d_select=None):
+    """mrt_light_select from its fields (d_out_light, d_select: device pointers / tensors; d_select or None)"""
+    return LightSelect(frame, select_draw, None if d_select is None else _ptr(d_select).value, _ptr(d_out_light).value)
 
 
 def surface_out(d_rows=None, d_bounce_surface=None, d_out_hits=None):
@@ -821,6 +842,26 @@ class Context:
         self._chk(self.L.mrt_cast_grid_shadows(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), lp, lights.shape[0],
                                                _ptr(d_mask), query_mask, flags))
 
+    def cast_selected_shadows(self, d_rays, d_hits, count, lights, d_mask, d_out_light, frame=0, select_draw=256, d_select=None,
+                              query_mask=0xFFFFFFFF, flags=0):
+        """One shadow ray per record, to the light the record draws uniformly from its own stream (draw select_draw; the path tracer:
+        types.path_select_draw(bounce)).  d_rays / d_hits / lights as for cast_shadows; d_mask and d_out_light one byte per record: 1 lit
+        / 0 shadowed, and the light selected or types.LIGHT_NONE; d_select: optional byte per record (0 = selects no light)."""
+        lights, lp = self._lights(lights)
+        desc = light_select_desc(frame, select_draw, d_out_light, d_select)
+        self._chk(self.L.mrt_cast_selected_shadows(self.h, _ptr(d_rays), _ptr(d_hits), count, C.byref(desc), lp, lights.shape[0],
+                                                   _ptr(d_mask), query_mask, flags))
+
+    def cast_grid_selected_shadows(self, cam, grid_w, grid_h, d_hits, lights, d_mask, d_out_light, frame=0, select_draw=256, d_select=None,
+                                   y0=0, y1=None, query_mask=0xFFFFFFFF, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (d_hits: its mrt_hit32 records on the device; the bytes indexed by the
+        record within the band); the random stream of a pixel is seeded from its index in the whole grid."""
+        y1 = grid_h if y1 is None else y1
+        lights, lp = self._lights(lights)
+        desc = light_select_desc(frame, select_draw, d_out_light, d_select)
+        self._chk(self.L.mrt_cast_grid_selected_shadows(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(desc), lp,
+                                                        lights.shape[0], _ptr(d_mask), query_mask, flags))
+
     def cast_reflections(self, d_rays, d_hits, count, d_out_hits, max_distance, d_select=None, d_out_rays=None,
                          query_mask=0xFFFFFFFF, flags=0):
         """Mirror-reflection rays for the hit records of a cast, traced closest-hit (device pointers / tensors: mrt_ray32 + mrt_hit32,
@@ -984,6 +1025,24 @@ class Context:
         out = LightOut(_ptr(d_rgba).value)
         self._chk(self.L.mrt_light_grid_surfaces(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _ptr(d_rows), lp,
                                                  lights.shape[0], _optr(d_mask), ep, C.byref(out), flags))
+
+    def light_selected_surfaces(self, d_rays, d_hits, d_rows, count, lights, d_light, d_rgba, d_mask=None, env=None, flags=0):
+        """Direct light of the one light each record selected, scaled by the number of lights: light_surfaces' arguments, with d_light
+        one byte per record (cast_selected_shadows' d_out_light) and d_mask one byte per record (its d_mask) or None.  With env=None
+        d_rgba is what path_step takes as d_direct."""
+        lights, lp, env, ep = self._shade_lights(lights, env)
+        out = LightOut(_ptr(d_rgba).value)
+        self._chk(self.L.mrt_light_selected_surfaces(self.h, _ptr(d_rays), _ptr(d_hits), _ptr(d_rows), count, lp, lights.shape[0],
+                                                     _ptr(d_light), _optr(d_mask), ep, C.byref(out), flags))
+
+    def light_grid_selected_surfaces(self, cam, grid_w, grid_h, d_hits, d_rows, lights, d_light, d_rgba, d_mask=None, env=None, y0=0, y1=None,
+                                     flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (every per-record array indexed by the record within the band)."""
+        y1 = grid_h if y1 is None else y1
+        lights, lp, env, ep = self._shade_lights(lights, env)
+        out = LightOut(_ptr(d_rgba).value)
+        self._chk(self.L.mrt_light_grid_selected_surfaces(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _ptr(d_rows), lp,
+                                                          lights.shape[0], _ptr(d_light), _optr(d_mask), ep, C.byref(out), flags))
 
     def path_init(self, d_state, count, flags=0):
         """Every T.PATH_STATE entry to throughput 1, active, radiance 0."""

@@ -171,6 +171,7 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 28: return (uint32_t)sizeof(mrt_denoise_params); // (27: not a struct)
 		case 30: return (uint32_t)sizeof(mrt_gbuffer); // (29: not a struct)
 		case 32: return (uint32_t)sizeof(mrt_svgf_params); // (31: not a struct)
+		case 34: return (uint32_t)sizeof(mrt_light_select); // (33: not a struct)
 		default: return 0u;
 	}
 }

@@ -11,6 +11,7 @@
 #include <rocprim/rocprim.hpp>
 #include "mrt_context.h"
 #include "gbuffer.h"
+#include "selected_shadow.h"
 
 namespace {
 
@@ -333,14 +334,7 @@ const char *shadow_invalid(const void *d_hits, uint64_t count, const mrt_light *
 	if (n_lights && count > ~0ull / n_lights) return "count * n_lights overflows";
 	std::memset(&s, 0, sizeof(s));
 	s.records = d_hits; s.pixels = count;
-	for (uint32_t l = 0; l < n_lights; l++) {
-		const mrt_light &L = lights[l];
-		if (L.type > MRT_LIGHT_SPOT) return "unknown light type";
-		mrt::ShadowLight &d = s.light[l];
-		d.kind = !L.cast_shadows ? mrt::SHADOW_OFF : (L.type == MRT_LIGHT_DIRECTIONAL ? mrt::SHADOW_DIRECTIONAL : mrt::SHADOW_POINT);
-		const float *v = L.type == MRT_LIGHT_DIRECTIONAL ? L.direction : L.position;
-		d.v[0] = v[0]; d.v[1] = v[1]; d.v[2] = v[2];
-	}
+	if (const char *why = mrt::sel::fill_shadow_lights(lights, n_lights, s.light)) return why;
 	return nullptr;
 }
 
@@ -353,6 +347,24 @@ int cast_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, c
 	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_SHADOW, flags, "unknown flag for a shadow cast",
 			[&] { return shadow_invalid(d_hits, count, lights, n_lights, d_mask, s); })) return rc;
 	p.hits = d_mask; p.count = count * n_lights; p.query_mask = query_mask;
+	p.out_fmt = mrt::OUT_BOOL8;
+	return run_source_cast(ctx, entry, src, MRT_MODE_ANY_HIT, p, s, flags);
+}
+
+// The selected-shadow casts (mrt_cast_selected_shadows, mrt_cast_grid_selected_shadows): p holds the scene, the grid (grid source) and
+// the primary rays (SRC_SELSHADOW_RAY32; the grid form passes any non-null d_rays); count = records, pixel0 = the pixel index of
+// record 0.  The checks in the header's order (selected_shadow.h), not source_cast_check's: the pointers come before the flags.
+int cast_selected_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_rays, const void *d_hits, uint64_t count,
+		uint32_t pixel0, const mrt_light_select *desc, const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	if (const char *why = mrt::sel::cast_invalid(entry == mrt::ENTRY_SELECTED_SHADOW, d_rays, d_hits, desc, lights, n_lights, d_mask, flags))
+		return fail(ctx, MRT_ERR_INVALID, why);
+	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
+	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (n_lights == 0) return MRT_OK; // (nothing to select from: nothing written, as a shadow cast without lights)
+	mrt::SelectShadowParams s;
+	mrt::sel::fill_params(d_hits, desc, lights, n_lights, pixel0, s);
+	p.hits = d_mask; p.count = count; p.query_mask = query_mask;
 	p.out_fmt = mrt::OUT_BOOL8;
 	return run_source_cast(ctx, entry, src, MRT_MODE_ANY_HIT, p, s, flags);
 }
@@ -388,22 +400,10 @@ const char *hemisphere_invalid(const mrt_hemisphere *desc, const void *d_hits, u
 	return nullptr;
 }
 
-// (A, C) with: PCG32 state before draw k = A * state0 + C, modulo 2^32, by squaring: the step (a, c) applied twice is (a * a, a * c + c).
-// Once per call on the host, so that the kernel has no loop over draws.
-mrt::HemiJump pcg_jump(uint32_t first_draw)
-{
-	uint32_t A = 1u, C = 0u, a = mrt::kPcgMul, c = mrt::kPcgInc;
-	for (uint32_t k = first_draw; k != 0u; k >>= 1) {
-		if (k & 1u) { A = a * A; C = a * C + c; }
-		c = a * c + c; a = a * a;
-	}
-	return mrt::HemiJump{A, C};
-}
-
 // The jump of the first draw of every sample (k = first_draw + 2 * sample): one pass over the draws.
 void hemisphere_jumps(uint32_t first_draw, uint32_t n_samples, mrt::HemiJump *out)
 {
-	mrt::HemiJump j = pcg_jump(first_draw);
+	mrt::HemiJump j = mrt::pcg_jump(first_draw);
 	for (uint32_t s = 0; s < n_samples; s++) {
 		out[s] = j;
 		for (int k = 0; k < 2; k++) { j.a = mrt::kPcgMul * j.a; j.c = mrt::kPcgMul * j.c + mrt::kPcgInc; }
@@ -453,7 +453,7 @@ int cast_bounce(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, co
 	s.records = d_hits; s.select = desc->d_select; s.surface = desc->d_surface; s.out_rays = d_out_rays; s.out_lobe = desc->d_out_lobe;
 	s.t_max = desc->t_max; s.metallic = desc->metallic; s.roughness = desc->roughness;
 	s.seed_add = pixel0 * 1009u + desc->frame * 6529u + 7u;
-	s.jump = pcg_jump(desc->first_draw);
+	s.jump = mrt::pcg_jump(desc->first_draw);
 	p.hits = d_out_hits; p.count = count; p.query_mask = query_mask;
 	p.out_fmt = src == mrt::SRC_BOUNCE_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32;
 	return run_source_cast(ctx, entry, src, MRT_MODE_NEAREST, p, s, flags);
@@ -629,6 +629,30 @@ int mrt_cast_grid_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, 
 	if (rc) return rc;
 	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the pairs; the kernel regenerates the primary ray from p.cam itself)
 	return cast_shadows(ctx, mrt::ENTRY_GRID_SHADOW, mrt::SRC_SHADOW_GRID, p, d_hits, p.count, lights, n_lights, d_mask, query_mask, flags);
+}
+
+int mrt_cast_selected_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const mrt_light_select *desc,
+		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	mrt::TraceParams p;
+	base_params(ctx, p);
+	p.rays = d_rays; // (SRC_SELSHADOW_HOST44: not read, the record has the position)
+	const int src = (flags & MRT_FLAG_HOST_LAYOUT) ? mrt::SRC_SELSHADOW_HOST44 : mrt::SRC_SELSHADOW_RAY32;
+	return cast_selected_shadows(ctx, mrt::ENTRY_SELECTED_SHADOW, src, p, d_rays, d_hits, count, 0u, desc, lights, n_lights, d_mask, query_mask, flags);
+}
+
+int mrt_cast_grid_selected_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const mrt_hit32 *d_hits, const mrt_light_select *desc, const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask,
+		uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	mrt::TraceParams p;
+	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
+	if (rc) return rc;
+	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the records; the kernel regenerates the primary ray from p.cam itself)
+	return cast_selected_shadows(ctx, mrt::ENTRY_GRID_SELECTED_SHADOW, mrt::SRC_SELSHADOW_GRID, p, cam, d_hits, p.count, y0 * grid_w, desc, lights,
+			n_lights, d_mask, query_mask, flags);
 }
 
 int mrt_cast_reflections(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const uint8_t *d_select,

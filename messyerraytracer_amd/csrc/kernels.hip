@@ -28,6 +28,7 @@ namespace mrt {
 
 #include "source_common.h"
 #include "shadow_kernel.h"
+#include "selected_shadow_kernel.h"
 #include "reflection_kernel.h"
 #include "hemisphere_kernel.h"
 #include "bounce_kernel.h"
@@ -168,7 +169,7 @@ hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *nex
 
 // Record-driven casts: p.kernel is the lane kernel the plan chose (launch_policy.cpp plan_source); p.count = entries.  persistent:
 // blocks != 0 (as launch_trace_persistent), else the plain kernel with p.sparse_lanes (resolve_source).  src = one of the family's
-// three sources; any_hit = a mode the family has (shadows any-hit, reflections and bounces closest-hit, hemispheres either: the other
+// three sources; any_hit = a mode the family has (shadows, selected or not, any-hit, reflections and bounces closest-hit, hemispheres either: the other
 // instantiations do not compile, source_entry).  Anything else is hipErrorInvalidValue.
 template <class S>
 hipError_t launch_source(const TraceParams &p, const void *params, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
@@ -194,6 +195,7 @@ hipError_t launch_source(const TraceParams &p, const void *params, int src, bool
 	return hipGetLastError();
 }
 template hipError_t launch_source<ShadowParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+template hipError_t launch_source<SelectShadowParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<ReflectParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<HemiParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<BounceParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);

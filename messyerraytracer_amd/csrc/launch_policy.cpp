@@ -177,8 +177,8 @@ void tune_record(GridTune &t, float trace_ms)
 	t.armed = false;
 }
 
-// Record-driven casts (shadow, reflection, hemisphere, bounce: record_cast_entry): count rays made in the kernel from resident hit records
-// -- pixels * lights any-hit shadow rays, one closest-hit mirror or bounce ray per record, pixels * samples hemisphere rays in either
+// Record-driven casts (shadow, selected shadow, reflection, hemisphere, bounce: record_cast_entry): count rays made in the kernel from resident hit records
+// -- pixels * lights any-hit shadow rays or one per record to a drawn light, one closest-hit mirror or bounce ray per record, pixels * samples hemisphere rays in either
 // mode -- in entry order (which already groups nearby origins, though hemisphere and bounce rays are far less coherent than the
 // others).  A G-buffer reflection cast (ENTRY_GBUFFER_REFLECTION: one mirror ray per pixel from depth and normal buffers, in pixel order)
 // is the same kind of batch.  One plan for all of them, since neither the family nor the mode enters it:

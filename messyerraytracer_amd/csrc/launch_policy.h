@@ -53,13 +53,15 @@ struct SceneFacts {
 // count = pixels * samples (cosine-weighted hemisphere rays made in the kernel: an unsorted, non-coherent batch in either mode).
 // ENTRY_BOUNCE / ENTRY_GRID_BOUNCE: mrt_cast_bounce / mrt_cast_grid_bounce, count = records (the path tracer's bounce rays made in the
 // kernel: an unsorted, non-coherent closest-hit batch).  ENTRY_GBUFFER_REFLECTION: mrt_cast_gbuffer_reflections, count = pixels of the
-// frame (mirror rays made in the kernel from a rasteriser's depth and normal buffers: the plan of a reflection cast of as many rays)
+// frame (mirror rays made in the kernel from a rasteriser's depth and normal buffers: the plan of a reflection cast of as many rays).
+// ENTRY_SELECTED_SHADOW / ENTRY_GRID_SELECTED_SHADOW: mrt_cast_selected_shadows / mrt_cast_grid_selected_shadows, count = records (one
+// shadow ray per record to the light it draws: an unsorted any-hit batch, less coherent than a shadow cast's since neighbours differ in light)
 enum Entry : uint32_t { ENTRY_CAST, ENTRY_SUBMIT, ENTRY_CHUNK, ENTRY_GRID, ENTRY_TILED, ENTRY_SHADOW, ENTRY_GRID_SHADOW,
 	ENTRY_REFLECTION, ENTRY_GRID_REFLECTION, ENTRY_HEMISPHERE, ENTRY_GRID_HEMISPHERE, ENTRY_BOUNCE, ENTRY_GRID_BOUNCE,
-	ENTRY_GBUFFER_REFLECTION };
+	ENTRY_GBUFFER_REFLECTION, ENTRY_SELECTED_SHADOW, ENTRY_GRID_SELECTED_SHADOW };
 inline bool ray_entry(Entry e) { return e <= ENTRY_CHUNK; } // rays from an array, through enqueue_cast
-// rays made in the kernel, from hit records or (the last) from a G-buffer
-inline bool record_cast_entry(Entry e) { return e >= ENTRY_SHADOW && e <= ENTRY_GBUFFER_REFLECTION; }
+// rays made in the kernel, from hit records or (ENTRY_GBUFFER_REFLECTION) from a G-buffer
+inline bool record_cast_entry(Entry e) { return e >= ENTRY_SHADOW && e <= ENTRY_GRID_SELECTED_SHADOW; }
 
 struct CastRequest {
 	Entry entry = ENTRY_CAST;

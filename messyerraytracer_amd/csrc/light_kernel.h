@@ -1,4 +1,5 @@
-// light_kernel.h — direct light on resolved surfaces (mrt_light_surfaces / mrt_light_grid_surfaces), plain and with a panorama resident
+// light_kernel.h — direct light on resolved surfaces (mrt_light_surfaces / mrt_light_grid_surfaces; mrt_light_selected_surfaces /
+// mrt_light_grid_selected_surfaces: one light per record, drawn by mrt_cast_selected_shadows), plain and with a panorama resident
 // (mrt_upload_panorama), and the shading formulas the path step shares with it.  Included by shade_kernels.hip (inside namespace mrt,
 // after source_common.h; lighting.h holds LightParams and pow01, panorama.h PanoramaParams and the sampler's arithmetic).
 //
@@ -91,12 +92,59 @@ __device__ __forceinline__ void panorama_sky(const PanoramaParams &pano, float d
 	b = pano_blend(p00.z, p10.z, p01.z, p11.z, t) * pano.energy;
 }
 
-// ---- the light of record i: PANO = a panorama is resident (pano is read only then) ------------------------------------------------
-template <int SRC, bool PANO>
+// What every light's term reads of a hit: the position, the row's normal and n . v, the view direction, the surface's F0 and diffuse
+// albedo, a2 = roughness^4 and g1(n . v).
+struct LitPoint { float px, py, pz, nx, ny, nz, ndv, vx, vy, vz, a2, g1v; float f0[3], df[3]; };
+
+// One light's pass through cook_torrance_multi_light's loop at a hit (include/mrt_hip.h): rgb.c = rgb.c + the addend of light K, the one
+// text of it for the loop over all lights and for the one selected light (which enters with rgb = 0).  Nothing is added where the light
+// is skipped -- out of range, attenuated away, behind the surface, or lit() == false, which is asked after ndl and before the specular
+// terms (the all-lights loop reads its mask byte there).
+template <class Lit>
+__device__ __forceinline__ void add_light_term(const KernelLight &K, const LitPoint &q, Lit lit, float &cr, float &cg, float &cb)
+{
+	constexpr float PI = 3.14159265358979323846f;
+	float lx, ly, lz, atten = 1.0f;
+	if (K.type == MRT_LIGHT_DIRECTIONAL) { lx = K.direction[0]; ly = K.direction[1]; lz = K.direction[2]; }
+	else {
+		const float tx = K.position[0] - q.px, ty = K.position[1] - q.py, tz = K.position[2] - q.pz;
+		const float dist = __builtin_sqrtf((tx * tx + ty * ty) + tz * tz);
+		if (dist < 1e-6f || dist > K.range) return;
+		lx = tx / dist; ly = ty / dist; lz = tz / dist;
+		const float ratio = dist / K.range;
+		atten = pow01(max0(1.0f - ratio * ratio), K.attenuation);
+		if (K.type == MRT_LIGHT_SPOT) {
+			const float cos_angle = (lx * K.direction[0] + ly * K.direction[1]) + lz * K.direction[2];
+			float spot = 0.0f;
+			if (!(cos_angle <= K.cos_outer)) spot = pow01(max0((cos_angle - K.cos_outer) / K.one_minus_cos_outer), K.spot_attenuation);
+			atten = atten * spot;
+		}
+	}
+	if (atten < 1e-6f) return;
+	const float ndl = (q.nx * lx + q.ny * ly) + q.nz * lz;
+	if (ndl <= 0.0f) return;
+	if (!lit()) return;
+	float hx = q.vx + lx, hy = q.vy + ly, hz = q.vz + lz;
+	normalize3(hx, hy, hz);
+	const float n_dot_h = max0((q.nx * hx + q.ny * hy) + q.nz * hz), v_dot_h = max0((q.vx * hx + q.vy * hy) + q.vz * hz);
+	const float den = (n_dot_h * n_dot_h) * (q.a2 - 1.0f) + 1.0f;
+	const float d_term = q.a2 / ((PI * den) * den + 1e-7f);
+	const float g_term = q.g1v * smith_g1(ndl, q.a2);
+	float f[3];
+	schlick(q.f0, v_dot_h, f);
+	const float spec_scale = (d_term * g_term) / ((4.0f * q.ndv) * ndl + 1e-7f);
+	const float diff_scale = 1.0f / PI;
+	cr = cr + ((((q.df[0] * (1.0f - f[0])) * diff_scale + f[0] * spec_scale) * (K.color[0] * atten)) * ndl);
+	cg = cg + ((((q.df[1] * (1.0f - f[1])) * diff_scale + f[1] * spec_scale) * (K.color[1] * atten)) * ndl);
+	cb = cb + ((((q.df[2] * (1.0f - f[2])) * diff_scale + f[2] * spec_scale) * (K.color[2] * atten)) * ndl);
+}
+
+// ---- the light of record i: PANO = a panorama is resident (pano is read only then); SELECTED = the record's one light, s.selected[i],
+// scaled by the number of lights (mrt_light_selected_surfaces), instead of the loop over all of them -------------------------------------
+template <int SRC, bool PANO, bool SELECTED>
 __device__ __forceinline__ void light_record(const TraceParams &p, const LightParams &s, const PanoramaParams &pano)
 {
 	constexpr bool HOST = SRC == SURF_HOST, GRID = SRC == SURF_GRID;
-	constexpr float PI = 3.14159265358979323846f;
 	const uint64_t i = (uint64_t)blockIdx.x * MRT_WG + threadIdx.x;
 	if (i >= p.count) return;
 	Surface sf = {};
@@ -115,49 +163,26 @@ __device__ __forceinline__ void light_record(const TraceParams &p, const LightPa
 	if (hit) {
 		const float4 *row = reinterpret_cast<const float4 *>(s.rows) + i * 4u;
 		const float4 r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3]; // {n, n_dot_v | albedo, metallic | emission, roughness | uv, specular, material}
-		const float nx = r0.x, ny = r0.y, nz = r0.z, ndv = r0.w, rough = r2.w;
-		float vx = -sf.dx, vy = -sf.dy, vz = -sf.dz;
-		normalize3(vx, vy, vz);
-		float f0[3], df[3];
-		f0_diffuse(r1, r3.z, f0, df);
-		const float a = rough * rough, a2 = a * a;
-		const float g1v = smith_g1(ndv, a2);
-		const float diff_scale = 1.0f / PI;
+		const float ny = r0.y, rough = r2.w;
+		LitPoint q;
+		q.px = sf.px; q.py = sf.py; q.pz = sf.pz;
+		q.nx = r0.x; q.ny = r0.y; q.nz = r0.z; q.ndv = r0.w;
+		q.vx = -sf.dx; q.vy = -sf.dy; q.vz = -sf.dz;
+		normalize3(q.vx, q.vy, q.vz);
+		f0_diffuse(r1, r3.z, q.f0, q.df);
+		const float (&df)[3] = q.df;
+		const float a = rough * rough;
+		q.a2 = a * a;
+		q.g1v = smith_g1(q.ndv, q.a2);
 		float cr = 0.0f, cg = 0.0f, cb = 0.0f;
-		for (uint32_t l = 0; l < s.n_lights; l++) {
-			const KernelLight &K = s.light[l];
-			float lx, ly, lz, atten = 1.0f;
-			if (K.type == MRT_LIGHT_DIRECTIONAL) { lx = K.direction[0]; ly = K.direction[1]; lz = K.direction[2]; }
-			else {
-				const float tx = K.position[0] - sf.px, ty = K.position[1] - sf.py, tz = K.position[2] - sf.pz;
-				const float dist = __builtin_sqrtf((tx * tx + ty * ty) + tz * tz);
-				if (dist < 1e-6f || dist > K.range) continue;
-				lx = tx / dist; ly = ty / dist; lz = tz / dist;
-				const float ratio = dist / K.range;
-				atten = pow01(max0(1.0f - ratio * ratio), K.attenuation);
-				if (K.type == MRT_LIGHT_SPOT) {
-					const float cos_angle = (lx * K.direction[0] + ly * K.direction[1]) + lz * K.direction[2];
-					float spot = 0.0f;
-					if (!(cos_angle <= K.cos_outer)) spot = pow01(max0((cos_angle - K.cos_outer) / K.one_minus_cos_outer), K.spot_attenuation);
-					atten = atten * spot;
-				}
-			}
-			if (atten < 1e-6f) continue;
-			const float ndl = (nx * lx + ny * ly) + nz * lz;
-			if (ndl <= 0.0f) continue;
-			if (s.mask != nullptr && s.mask[(uint64_t)l * p.count + i] == 0) continue;
-			float hx = vx + lx, hy = vy + ly, hz = vz + lz;
-			normalize3(hx, hy, hz);
-			const float n_dot_h = max0((nx * hx + ny * hy) + nz * hz), v_dot_h = max0((vx * hx + vy * hy) + vz * hz);
-			const float den = (n_dot_h * n_dot_h) * (a2 - 1.0f) + 1.0f;
-			const float d_term = a2 / ((PI * den) * den + 1e-7f);
-			const float g_term = g1v * smith_g1(ndl, a2);
-			float f[3];
-			schlick(f0, v_dot_h, f);
-			const float spec_scale = (d_term * g_term) / ((4.0f * ndv) * ndl + 1e-7f);
-			cr = cr + ((((df[0] * (1.0f - f[0])) * diff_scale + f[0] * spec_scale) * (K.color[0] * atten)) * ndl);
-			cg = cg + ((((df[1] * (1.0f - f[1])) * diff_scale + f[1] * spec_scale) * (K.color[1] * atten)) * ndl);
-			cb = cb + ((((df[2] * (1.0f - f[2])) * diff_scale + f[2] * spec_scale) * (K.color[2] * atten)) * ndl);
+		if constexpr (SELECTED) { // the light is indexed per lane: its 16 words are read from the kernel argument where it lies
+			const uint32_t k = s.selected[i];
+			if (k < s.n_lights && !(s.mask != nullptr && s.mask[i] == 0)) add_light_term(s.light[k], q, [] { return true; }, cr, cg, cb);
+			const float n = (float)s.n_lights;
+			cr = cr * n; cg = cg * n; cb = cb * n;
+		} else {
+			for (uint32_t l = 0; l < s.n_lights; l++)
+				add_light_term(s.light[l], q, [&] { return !(s.mask != nullptr && s.mask[(uint64_t)l * p.count + i] == 0); }, cr, cg, cb);
 		}
 		if (s.has_env != 0u) {
 			if constexpr (!PANO) { // the ambient factor: the gradient between ground and zenith by the normal's y
@@ -186,11 +211,23 @@ __device__ __forceinline__ void light_record(const TraceParams &p, const LightPa
 template <int SRC>
 __global__ __launch_bounds__(MRT_WG) void light_surfaces_kernel(const TraceParams p, const LightParams s)
 {
-	light_record<SRC, false>(p, s, PanoramaParams{});
+	light_record<SRC, false, false>(p, s, PanoramaParams{});
 }
 
 template <int SRC>
 __global__ __launch_bounds__(MRT_WG) void light_panorama_surfaces_kernel(const TraceParams p, const LightParams s, const PanoramaParams pano)
 {
-	light_record<SRC, true>(p, s, pano);
+	light_record<SRC, true, false>(p, s, pano);
+}
+
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void light_selected_surfaces_kernel(const TraceParams p, const LightParams s)
+{
+	light_record<SRC, false, true>(p, s, PanoramaParams{});
+}
+
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void light_selected_panorama_surfaces_kernel(const TraceParams p, const LightParams s, const PanoramaParams pano)
+{
+	light_record<SRC, true, true>(p, s, pano);
 }

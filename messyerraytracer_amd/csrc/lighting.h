@@ -1,4 +1,4 @@
-// lighting.h -- direct light on resolved surfaces (mrt_light_surfaces, mrt_light_grid_surfaces): the kernel's argument block, pow01 as
+// lighting.h -- direct light on resolved surfaces (mrt_light_surfaces, mrt_light_grid_surfaces and their selected forms): the kernel's argument block, pow01 as
 // include/mrt_hip.h defines it (one definition for the kernel, light_kernel.h, and the host, so that both hold the same bits), and the
 // checks of the light list and the environment (host/light_data.cpp).  Host-only code may include this without HIP.
 #pragma once
@@ -31,7 +31,8 @@ static_assert(sizeof(KernelLight) == 64, "KernelLight is 16 words");
 struct LightParams {
 	const void *records;       // mrt_hit32 (SURF_RAY32, SURF_GRID) or mrt_host_hit44 (SURF_HOST)
 	const void *rows;          // mrt_surface64 per record
-	const uint8_t *mask;       // optional: [light * count + record], 0 = shadowed
+	const uint8_t *mask;       // optional: [light * count + record], 0 = shadowed (the selected calls: [record])
+	const uint8_t *selected;   // the selected calls only: the one light of each record (>= n_lights: none)
 	void *out;                 // float4 per record
 	uint32_t n_lights, has_env;
 	float zenith[3], horizon[3], ground[3], ambient[3], ambient_energy;

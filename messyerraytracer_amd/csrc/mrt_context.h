@@ -17,7 +17,7 @@ const char *last_trace_variant();
 bool quad_kernel_built();
 hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream);
-// record-driven casts (source_common.h): S = the family's parameter struct (instantiated in kernels.hip for ShadowParams, ReflectParams,
+// record-driven casts (source_common.h): S = the family's parameter struct (instantiated in kernels.hip for ShadowParams, SelectShadowParams, ReflectParams,
 // HemiParams, BounceParams and GBufferParams), params = an S, src = one of SourceFamily<S>'s sources, any_hit = a mode the family has; blocks != 0: the
 // persistent kernel (next_ray .. leaf_wait as launch_trace_persistent)
 template <class S>
@@ -39,7 +39,7 @@ hipError_t launch_origin_dir_keys(const void *rays, uint32_t in_fmt, uint64_t co
 // src = a SurfaceSrc; t (texture.h) / pano (panorama.h) null: no texture set / no panorama resident
 // shading surfaces (surface_kernel.h); the rows of shade data given as device arrays (any of the three may be null)
 hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s, const TextureParams *t, int src, hipStream_t stream);
-// direct light on resolved surfaces (light_kernel.h)
+// direct light on resolved surfaces (light_kernel.h): over all lights, or with s.selected given the one light of each record
 struct LightParams;
 hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams *pano, int src, hipStream_t stream);
 // the path tracer's per-pixel state (path_kernel.h); white = Hable's white value for tone-map mode 2

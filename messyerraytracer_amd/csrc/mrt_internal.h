@@ -173,14 +173,16 @@ enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, S
 	SRC_REFLECT_RAY32 = 4, SRC_REFLECT_HOST = 5, SRC_REFLECT_GRID = 6,
 	SRC_HEMI_RAY32 = 7, SRC_HEMI_HOST = 8, SRC_HEMI_GRID = 9,
 	SRC_BOUNCE_RAY32 = 10, SRC_BOUNCE_HOST = 11, SRC_BOUNCE_GRID = 12,
-	SRC_GBUFFER = 13 };
+	SRC_GBUFFER = 13,
+	SRC_SELSHADOW_RAY32 = 14, SRC_SELSHADOW_HOST44 = 15, SRC_SELSHADOW_GRID = 16 };
 constexpr bool shadow_source(int src) { return src >= SRC_SHADOW_RAY32 && src <= SRC_SHADOW_GRID; }
 constexpr bool reflection_source(int src) { return src >= SRC_REFLECT_RAY32 && src <= SRC_REFLECT_GRID; }
 constexpr bool hemisphere_source(int src) { return src >= SRC_HEMI_RAY32 && src <= SRC_HEMI_GRID; }
 constexpr bool bounce_source(int src) { return src >= SRC_BOUNCE_RAY32 && src <= SRC_BOUNCE_GRID; }
 constexpr bool gbuffer_source(int src) { return src == SRC_GBUFFER; }
-// the result of an entry is one byte (1 = no occluder, or no ray): every shadow cast, and a hemisphere cast in any-hit mode
-constexpr bool lit_output(int src, bool any_hit) { return shadow_source(src) || (hemisphere_source(src) && any_hit); }
+constexpr bool selected_shadow_source(int src) { return src >= SRC_SELSHADOW_RAY32 && src <= SRC_SELSHADOW_GRID; }
+// the result of an entry is one byte (1 = no occluder, or no ray): every shadow cast, selected or not, and a hemisphere cast in any-hit mode
+constexpr bool lit_output(int src, bool any_hit) { return shadow_source(src) || selected_shadow_source(src) || (hemisphere_source(src) && any_hit); }
 enum ShadowKind : uint32_t { SHADOW_OFF = 0, SHADOW_DIRECTIONAL = 1, SHADOW_POINT = 2 }; // OFF: cast_shadows == 0 (lit)
 struct ShadowLight { uint32_t kind; float v[3]; }; // DIRECTIONAL: direction towards the light; POINT (point and spot): position
 struct ShadowParams {
@@ -205,6 +207,17 @@ struct ReflectParams {
 // before a sample's first draw is jump[sample].a * state0 + jump[sample].c (hemisphere_jumps, cast.hip).
 constexpr uint32_t kPcgMul = 747796405u, kPcgInc = 2891336453u; // the reference's PCG32 (path_state.h): state' = state * mul + inc
 struct HemiJump { uint32_t a, c; };
+// (A, C) with: PCG32 state before draw k = A * state0 + C, modulo 2^32, by squaring: the step (a, c) applied twice is (a * a, a * c + c).
+// Once per call on the host, so that the kernel has no loop over draws.
+inline HemiJump pcg_jump(uint32_t first_draw)
+{
+	uint32_t A = 1u, C = 0u, a = kPcgMul, c = kPcgInc;
+	for (uint32_t k = first_draw; k != 0u; k >>= 1) {
+		if (k & 1u) { A = a * A; C = a * C + c; }
+		c = a * c + c; a = a * a;
+	}
+	return HemiJump{A, C};
+}
 struct HemiParams {
 	const void *records;       // mrt_hit32 (SRC_HEMI_RAY32, SRC_HEMI_GRID) or mrt_host_hit44 (SRC_HEMI_HOST)
 	const uint8_t *select;     // optional: 0 = no ray for this pixel
@@ -217,7 +230,7 @@ struct HemiParams {
 
 // ---- the path tracer's bounce (bounce_kernel.h): one closest-hit ray per hit record, lobe chosen and sampled in the kernel ---------
 // Entry i of a bounce cast is record i; TraceParams::count = records, hits = the output records, rays = the incoming rays as for
-// reflections.  The generator's state before the lobe draw is jump.a * state0 + jump.c (pcg_jump, cast.hip).
+// reflections.  The generator's state before the lobe draw is jump.a * state0 + jump.c (pcg_jump).
 struct BounceParams {
 	const void *records;       // mrt_hit32 (SRC_BOUNCE_RAY32, SRC_BOUNCE_GRID) or mrt_host_hit44 (SRC_BOUNCE_HOST)
 	const uint8_t *select;     // optional: 0 = no ray for this record
@@ -228,6 +241,19 @@ struct BounceParams {
 	float t_max;               // t_max of every ray
 	float metallic, roughness; // as the descriptor gave them (clamped in the kernel like a record's pair)
 	HemiJump jump;             // (A, C) of draw first_draw
+};
+
+// ---- one shadow ray per record, to the light the record draws (selected_shadow_kernel.h; selected_shadow.h fills this) ---------------
+// Entry i of a selected-shadow cast is record i; TraceParams::count = records, hits = the lit mask (one byte per record), rays = the
+// primary rays (SRC_SELSHADOW_RAY32).  The generator's state before the selecting draw is jump.a * state0 + jump.c, as for a bounce.
+struct SelectShadowParams {
+	const void *records;       // mrt_hit32 (SRC_SELSHADOW_RAY32, SRC_SELSHADOW_GRID) or mrt_host_hit44 (SRC_SELSHADOW_HOST44)
+	const uint8_t *select;     // optional: 0 = the record selects no light
+	uint8_t *out_light;        // the light selected per record, or MRT_LIGHT_NONE
+	uint32_t seed_add;         // frame * 6529 + 7 (+ y0 * grid_w * 1009 for a row band): seed = record * 1009 + seed_add
+	HemiJump jump;             // (A, C) of draw select_draw
+	uint32_t n_lights;         // >= 1
+	ShadowLight light[MRT_MAX_LIGHTS];
 };
 
 // ---- reflection rays from a rasteriser's G-buffer (gbuffer_kernel.h, gbuffer.h): one closest-hit ray per pixel of a whole frame -----
@@ -303,6 +329,11 @@ template <> struct SourceFamily<GBufferParams> {
 	static constexpr int ray32 = SRC_GBUFFER, host = SRC_GBUFFER, grid = SRC_GBUFFER;
 	static constexpr bool any_hit = false, nearest = true;
 	static constexpr const char *name = "gbuffer";
+};
+template <> struct SourceFamily<SelectShadowParams> {
+	static constexpr int ray32 = SRC_SELSHADOW_RAY32, host = SRC_SELSHADOW_HOST44, grid = SRC_SELSHADOW_GRID;
+	static constexpr bool any_hit = true, nearest = false;
+	static constexpr const char *name = "selected_shadow";
 };
 
 // host-side preparation (scene_prep.cpp)

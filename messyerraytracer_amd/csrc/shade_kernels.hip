@@ -44,6 +44,10 @@ hipError_t launch_resolve_surfaces(const TraceParams &p, const SurfaceParams &s,
 }
 hipError_t launch_light_surfaces(const TraceParams &p, const LightParams &s, const PanoramaParams *pano, int src, hipStream_t stream)
 {
+	if (s.selected != nullptr) { // one light per record (mrt_light_selected_surfaces)
+		if (pano == nullptr) return launch_surface_pass([](auto SRC) { return light_selected_surfaces_kernel<SRC>; }, src, p, stream, s);
+		return launch_surface_pass([](auto SRC) { return light_selected_panorama_surfaces_kernel<SRC>; }, src, p, stream, s, *pano);
+	}
 	if (pano == nullptr) return launch_surface_pass([](auto SRC) { return light_surfaces_kernel<SRC>; }, src, p, stream, s);
 	return launch_surface_pass([](auto SRC) { return light_panorama_surfaces_kernel<SRC>; }, src, p, stream, s, *pano);
 }

@@ -1,8 +1,8 @@
-// source_common.h — what every ray source shares (shadow_kernel.h, reflection_kernel.h, hemisphere_kernel.h, bounce_kernel.h, and
-// gbuffer_kernel.h, whose entries are pixels of a G-buffer, not records).  Included by kernels.hip (inside namespace mrt, after
+// source_common.h — what every ray source shares (shadow_kernel.h, selected_shadow_kernel.h, reflection_kernel.h, hemisphere_kernel.h,
+// bounce_kernel.h, and gbuffer_kernel.h, whose entries are pixels of a G-buffer, not records).  Included by kernels.hip (inside namespace mrt, after
 // device_common.h, before the family headers) and, for record_surface, by shade_kernels.hip.
 //
-// A source family is a parameter struct (mrt_internal.h: ShadowParams, ReflectParams, HemiParams, BounceParams, GBufferParams;
+// A source family is a parameter struct (mrt_internal.h: ShadowParams, SelectShadowParams, ReflectParams, HemiParams, BounceParams, GBufferParams;
 // SourceFamily<S> names its sources and its modes) plus one overload of
 //   template <int SRC, bool ANY_HIT> bool source_entry(const TraceParams &p, const S &s, uint64_t g, RayRegs &r)
 // which makes the ray of entry g (true: r is a ray to walk) or stores the result of an entry without a ray (false: the lit byte, or
@@ -116,6 +116,14 @@ __device__ __forceinline__ bool record_surface(const TraceParams &p, const void 
 	return hit;
 }
 
+// record i is a hit: record_surface's test alone (prim_id of either layout), for a source that has something to store for a miss
+template <bool HOST>
+__device__ __forceinline__ bool record_is_hit(const void *records, uint64_t i)
+{
+	if (HOST) return reinterpret_cast<const uint32_t *>(records)[i * 11u + 9u] != 0xFFFFFFFFu;
+	return __float_as_int((reinterpret_cast<const float4 *>(records) + i * 2u)[0].y) != -1;
+}
+
 // Faces the normal against the incoming ray: n = -n if c = ((nx*dx + ny*dy) + nz*dz) > 0.  Returns the faced n's dot product with d
 // (the same sum negated, exactly).
 __device__ __forceinline__ float face_normal(Surface &sf)
@@ -125,11 +133,17 @@ __device__ __forceinline__ float face_normal(Surface &sf)
 	return c;
 }
 
-// PCG32::next's output permutation of a state, as PCG32::next_float scales it
-__device__ __forceinline__ float pcg_float(uint32_t state)
+// PCG32::next's output permutation of a state
+__device__ __forceinline__ uint32_t pcg_word(uint32_t state)
 {
 	const uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
-	return (float)((word >> 22u) ^ word) * 2.3283064e-10f; // 2^-32; 0xFFFFFF80 and above round to 2^32: 1.0
+	return (word >> 22u) ^ word;
+}
+
+// ... as PCG32::next_float scales it
+__device__ __forceinline__ float pcg_float(uint32_t state)
+{
+	return (float)pcg_word(state) * 2.3283064e-10f; // 2^-32; 0xFFFFFF80 and above round to 2^32: 1.0
 }
 
 // cos and sin of 2 pi u for u in [0, 1]: the quadrant k = rint(4u) (ties to even), f = 4u - k in [-1/2, 1/2] (both exact),

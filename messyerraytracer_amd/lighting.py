@@ -219,6 +219,27 @@ def sky_gradient(d, env):
     return np.where(up[:, None], hi, lo).astype(F)
 
 
+def add_environment(rgb, r, env, panorama=None):
+    """shade_material's two terms after the lights, added in place to rgb [N, 3] of the hit rows r: the ambient term (the gradient
+    between ground and zenith by the normal's y, or the panorama's sample of the normal), then the emission"""
+    with np.errstate(all="ignore"):
+        zen, gnd, amb = (np.asarray(env[k], dtype=F) for k in ("sky_zenith", "sky_ground", "ambient"))
+        blend = r["normal"][:, 1] * F(0.5) + F(0.5)
+        one_m = F(1) - r["metallic"]
+        sampled = None if panorama is None else Pn.sky_panorama(panorama[0], panorama[1], r["normal"])
+        for c in range(3):
+            a = gnd[c] + (zen[c] - gnd[c]) * blend if sampled is None else sampled[:, c]
+            diff = r["albedo"][:, c] * one_m
+            rgb[:, c] = rgb[:, c] + ((diff * a) * amb[c]) * F(env["ambient_energy"])
+            rgb[:, c] = rgb[:, c] + r["emission"][:, c]
+    return rgb
+
+
+def miss_sky(miss_d, env, panorama=None):
+    """what a lighting call with an environment writes for a miss: the analytic gradient, or the panorama's sample, of d as given"""
+    return sky_gradient(miss_d, env) if panorama is None else Pn.sky_panorama(panorama[0], panorama[1], miss_d)
+
+
 def shade_linear(rows, hit, p, d, lights, mask=None, env=None, cos_outer=None, panorama=None):
     """mrt_light_surfaces for N records: rows as mrt_resolve_surfaces wrote them, hit [N] bool, p [N, 3] positions (used for hits),
     d [N, 3] incoming directions, mask [n_lights, N] or None, env one T.ENVIRONMENT row or None, panorama (pixels [H, W, 4], energy)
@@ -232,18 +253,8 @@ def shade_linear(rows, hit, p, d, lights, mask=None, env=None, cos_outer=None, p
     rgb, n_pow = direct_light(r, np.asarray(p, dtype=F)[idx], np.asarray(d, dtype=F)[idx], lights,
                               None if mask is None else np.asarray(mask).reshape(-1, N)[:, idx], cos_outer)
     if env is not None:
-        with np.errstate(all="ignore"):
-            zen, gnd, amb = (np.asarray(env[k], dtype=F) for k in ("sky_zenith", "sky_ground", "ambient"))
-            blend = r["normal"][:, 1] * F(0.5) + F(0.5)
-            one_m = F(1) - r["metallic"]
-            sampled = None if panorama is None else Pn.sky_panorama(panorama[0], panorama[1], r["normal"])
-            for c in range(3):
-                a = gnd[c] + (zen[c] - gnd[c]) * blend if sampled is None else sampled[:, c]
-                diff = r["albedo"][:, c] * one_m
-                rgb[:, c] = rgb[:, c] + ((diff * a) * amb[c]) * F(env["ambient_energy"])
-                rgb[:, c] = rgb[:, c] + r["emission"][:, c]
-        miss_d = np.asarray(d, dtype=F)[~hit]
-        out[~hit, :3] = sky_gradient(miss_d, env) if panorama is None else Pn.sky_panorama(panorama[0], panorama[1], miss_d)
+        rgb = add_environment(rgb, r, env, panorama)
+        out[~hit, :3] = miss_sky(np.asarray(d, dtype=F)[~hit], env, panorama)
     out[idx, :3] = rgb
     out[idx, 3] = 1
     return out, n_pow

@@ -55,6 +55,16 @@ PATH_STATE = np.dtype([("throughput", "<f4", 3), ("active", "<u4"), ("radiance",
 PATH_MAX_FRAME, PATH_MAX_BOUNCES = 999999, 32
 assert PATH_STATE.itemsize == 32
 
+# next-event estimation with one light per record (mrt_cast_selected_shadows, mrt_light_selected_surfaces)
+LIGHT_SELECT = np.dtype([("frame", "<u4"), ("select_draw", "<u4"), ("d_select", "<u8"), ("d_out_light", "<u8")])  # mrt_light_select
+LIGHT_NONE = 0xFF
+assert LIGHT_SELECT.itemsize == 24
+
+
+def path_select_draw(bounce):
+    """MRT_PATH_SELECT_DRAW: the draw of a pixel's stream that selects bounce b's light"""
+    return 256 + int(bounce)
+
 # rows of the device layouts (csrc/mrt_internal.h), as mrt_debug_snapshot and the host preparations return them
 TRI_HOT = np.dtype([("v0", "<f4", 3), ("id", "<u4"), ("e1", "<f4", 3), ("layers", "<u4"), ("e2", "<f4", 3), ("flags", "<u4")])
 TRI_COLD = np.dtype([("normal", "<f4", 3), ("pad", "<u4")])
