@@ -15,7 +15,7 @@ OBJ = os.path.join(HERE, "_obj")  # object files, their dependency files and the
 # passes over hit records, prep_kernels.hip = what prepares a scene or a cast; an edit to one is compiled apart from the others.
 SOURCES = ["kernels.hip", "shade_kernels.hip", "prep_kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip",
            "device_build.hip", "refit.hip", "tlas_device.hip", "surface.hip", "texture.hip", "lighting.hip", "path.hip", "panorama.hip", "channels.hip", "accum.hip", "denoise.hip", "svgf.hip",
-           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/accum_data.cpp", "host/denoise_data.cpp", "host/svgf_data.cpp", "host/gbuffer_data.cpp", "host/selected_shadow_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
+           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/accum_data.cpp", "host/denoise_data.cpp", "host/svgf_data.cpp", "host/gbuffer_data.cpp", "host/source_cast_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
 # implicitly (-ffp-contract=off), so every result is unchanged.
@@ -24,24 +24,29 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 
 # The C++ test drivers: name -> (sources under csrc, flags, whether it links the library).  MIRROR: the host mirrors over the C-ABI;
 # POLICY: launch_policy.cpp alone; CPU: headers or host/*.cpp compiled for the CPU alone.  The last two need no device and no library.
+# A new driver is one row here (and a second one by _twin if it is to run under the sanitizers too): build_<name> below, build() of
+# __graft_entry__.py and .gitignore follow from it.
 MIRROR = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall"]
 POLICY = ["-O2", "-std=c++17", "-Wall"]
 CPU = ["-x", "c++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall"]
-LANE = ["-x", "c++", "-std=c++17", "-Wall"]
+LANE = ["-x", "c++", "-O2", "-std=c++17", "-Wall"]
+SANITIZE = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+
+
+def _twin(row):
+    """The row of a driver's sanitized twin, <name>_san: the same sources under AddressSanitizer and UndefinedBehaviorSanitizer."""
+    srcs, flags, links = row
+    return srcs, [f for f in flags if f != "-O2"] + SANITIZE, links
+
+
 DRIVERS = {
     "host_mirror_test": (["host/host_mirror_test.cpp"], MIRROR, True),  # GPURayCaster / RayDispatcher
     "host_cpu_test": (["host/host_cpu_test.cpp"], MIRROR, True),        # RayTracerServer over the router's CPU backend
     "host_tlas_test": (["host/host_tlas_test.cpp"], MIRROR, True),      # the router with a TLAS set, CPU and device backend
     "launch_policy_test": (["host/launch_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
-    "shadow_policy_test": (["host/shadow_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
-    "reflection_policy_test": (["host/reflection_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
-    "hemisphere_policy_test": (["host/hemisphere_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
-    "bounce_policy_test": (["host/bounce_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
-    "gbuffer_policy_test": (["host/gbuffer_policy_test.cpp", "launch_policy.cpp"], POLICY, False),
+    "record_policy_test": (["host/record_policy_test.cpp", "launch_policy.cpp"], POLICY, False),  # the six record-driven families: <exe> [family]
     "instance_math_test": (["host/instance_math_test.cpp"], CPU, False),  # instance_math.h, shared by the host path and the device TLAS build
     "build_rules_test": (["host/build_rules_test.cpp"], CPU, False),  # build_rules.h, shared by the host and the device scene builders
-    "build_rules_test_san": (["host/build_rules_test.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
-                                                               "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
     "shade_data_test": (["host/shade_data_test.cpp", "host/shade_data.cpp"], CPU, False),
     "light_data_test": (["host/light_data_test.cpp", "host/light_data.cpp"], CPU, False),
     "path_data_test": (["host/path_data_test.cpp", "host/path_data.cpp"], CPU, False),
@@ -49,27 +54,16 @@ DRIVERS = {
     "panorama_data_test": (["host/panorama_data_test.cpp", "host/panorama_data.cpp"], CPU, False),  # panorama.h, shared with the kernels
     "channel_data_test": (["host/channel_data_test.cpp", "host/channel_data.cpp"], CPU, False),  # channels.h, shared with the kernels
     "accum_data_test": (["host/accum_data_test.cpp", "host/accum_data.cpp"], CPU, False),  # accum.h, shared with the kernels
-    "accum_data_test_san": (["host/accum_data_test.cpp", "host/accum_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
-                                                                                         "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
     "denoise_data_test": (["host/denoise_data_test.cpp", "host/denoise_data.cpp"], CPU, False),  # denoise.h, shared with the kernels
-    "denoise_data_test_san": (["host/denoise_data_test.cpp", "host/denoise_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
-                                                                                             "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
     "svgf_data_test": (["host/svgf_data_test.cpp", "host/svgf_data.cpp"], CPU, False),  # svgf.h, shared with the kernels
-    "svgf_data_test_san": (["host/svgf_data_test.cpp", "host/svgf_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
-                                                                                       "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
     "gbuffer_data_test": (["host/gbuffer_data_test.cpp", "host/gbuffer_data.cpp"], CPU, False),  # gbuffer.h, shared with the kernels
-    "gbuffer_data_test_san": (["host/gbuffer_data_test.cpp", "host/gbuffer_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
-                                                                                             "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
-    "selected_shadow_data_test": (["host/selected_shadow_data_test.cpp", "host/selected_shadow_data.cpp"], CPU, False),  # selected_shadow.h
-    "selected_shadow_data_test_san": (["host/selected_shadow_data_test.cpp", "host/selected_shadow_data.cpp"], CPU[:2] + ["-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-ffp-contract=off", "-Wall",
-                                                                                                             "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], False),
-    "lane_map_test": (["host/lane_map_test.cpp"], LANE + ["-O2"], False),  # lane_map.h
-    "lane_map_test_san": (["host/lane_map_test.cpp"], LANE + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                                                              "-fno-sanitize-recover=undefined"], False),
-    "lane_map_fast_test": (["host/lane_map_fast_test.cpp"], LANE + ["-O2"], False),  # lane_map.h: the short map of whole-tile pairs
-    "lane_map_fast_test_san": (["host/lane_map_fast_test.cpp"], LANE + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                                                                        "-fno-sanitize-recover=undefined"], False),
+    "source_cast_data_test": (["host/source_cast_data_test.cpp", "host/source_cast_data.cpp"], CPU, False),  # source_cast.h
+    "lane_map_test": (["host/lane_map_test.cpp"], LANE, False),  # lane_map.h
+    "lane_map_fast_test": (["host/lane_map_fast_test.cpp"], LANE, False),  # lane_map.h: the short map of whole-tile pairs
 }
+for _name in ("build_rules_test", "accum_data_test", "denoise_data_test", "svgf_data_test", "gbuffer_data_test", "source_cast_data_test",
+              "lane_map_test", "lane_map_fast_test"):
+    DRIVERS[_name + "_san"] = _twin(DRIVERS[_name])
 
 
 def _hipcc() -> str:
@@ -185,73 +179,35 @@ def build_stream_gate(force: bool = False) -> str:
     return STREAM_GATE
 
 
+def build_drivers(force: bool = False) -> list:
+    """Every driver but the sanitized twins (a test that runs one builds it)."""
+    return [build_driver(name, force) for name in DRIVERS if not name.endswith("_san")]
+
+
 def _driver(name: str):
-    def build(force: bool = False) -> str:
-        return build_driver(name, force)
-    build.__doc__ = "C++ test driver " + name + " (DRIVERS)."
+    """build_<name>(force=False), and sanitize=False exactly where DRIVERS has the row's twin."""
+    if name + "_san" in DRIVERS:
+        def build(force: bool = False, sanitize: bool = False) -> str:
+            return build_driver(name + "_san" if sanitize else name, force)
+        build.__doc__ = "C++ test driver " + name + " (DRIVERS); sanitize = its twin under AddressSanitizer and UndefinedBehaviorSanitizer."
+    else:
+        def build(force: bool = False) -> str:
+            return build_driver(name, force)
+        build.__doc__ = "C++ test driver " + name + " (DRIVERS)."
     return build
 
 
-build_host_test = _driver("host_mirror_test")
-build_host_cpu_test = _driver("host_cpu_test")
-build_host_tlas_test = _driver("host_tlas_test")
-build_policy_test = _driver("launch_policy_test")
-build_shadow_policy_test = _driver("shadow_policy_test")
-build_reflection_policy_test = _driver("reflection_policy_test")
-build_hemisphere_policy_test = _driver("hemisphere_policy_test")
-build_bounce_policy_test = _driver("bounce_policy_test")
-build_gbuffer_policy_test = _driver("gbuffer_policy_test")
-build_instance_math_test = _driver("instance_math_test")
-build_shade_data_test = _driver("shade_data_test")
-build_light_data_test = _driver("light_data_test")
-build_path_data_test = _driver("path_data_test")
-build_texture_data_test = _driver("texture_data_test")
-build_panorama_data_test = _driver("panorama_data_test")
-build_channel_data_test = _driver("channel_data_test")
-
-
-def build_build_rules_test(force: bool = False, sanitize: bool = False) -> str:
-    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
-    return build_driver("build_rules_test_san" if sanitize else "build_rules_test", force)
-
-
-def build_accum_data_test(force: bool = False, sanitize: bool = False) -> str:
-    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
-    return build_driver("accum_data_test_san" if sanitize else "accum_data_test", force)
-
-
-def build_denoise_data_test(force: bool = False, sanitize: bool = False) -> str:
-    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
-    return build_driver("denoise_data_test_san" if sanitize else "denoise_data_test", force)
-
-
-def build_svgf_data_test(force: bool = False, sanitize: bool = False) -> str:
-    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
-    return build_driver("svgf_data_test_san" if sanitize else "svgf_data_test", force)
-
-
-def build_gbuffer_data_test(force: bool = False, sanitize: bool = False) -> str:
-    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
-    return build_driver("gbuffer_data_test_san" if sanitize else "gbuffer_data_test", force)
-
-
-def build_selected_shadow_data_test(force: bool = False, sanitize: bool = False) -> str:
-    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
-    return build_driver("selected_shadow_data_test_san" if sanitize else "selected_shadow_data_test", force)
-
-
-def build_lane_map_test(force: bool = False, sanitize: bool = False) -> str:
-    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
-    return build_driver("lane_map_test_san" if sanitize else "lane_map_test", force)
-
-
-def build_lane_map_fast_test(force: bool = False, sanitize: bool = False) -> str:
-    """sanitize = a second binary under AddressSanitizer and UndefinedBehaviorSanitizer."""
-    return build_driver("lane_map_fast_test_san" if sanitize else "lane_map_fast_test", force)
+for _name in DRIVERS:
+    if not _name.endswith("_san"):
+        globals()["build_" + _name] = _driver(_name)
+# callables whose name is not their row's
+build_host_test = build_host_mirror_test  # noqa: F821
+build_policy_test = build_launch_policy_test  # noqa: F821
+# (one driver for every family now: run it with the family's name)
+build_shadow_policy_test = build_reflection_policy_test = build_hemisphere_policy_test = build_bounce_policy_test = build_record_policy_test  # noqa: F821
+build_gbuffer_policy_test = build_record_policy_test  # noqa: F821
 
 
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
-    for name in DRIVERS:
-        if not name.endswith("_san"):
-            print(build_driver(name, force=True))
+    print("\n".join(build_drivers(force=True)))

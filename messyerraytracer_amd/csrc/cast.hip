@@ -1,6 +1,7 @@
 // cast.hip — the casts of the C-ABI: mrt_cast / mrt_submit / mrt_collect (rays from arrays), mrt_cast_grid (rays made in the
-// kernel), mrt_cast_tiled.  launch_policy.cpp plans every cast (which kernel, how launched); launch_planned runs the plan.
-#include <cfloat>
+// kernel), mrt_cast_tiled, and the record-driven casts (rays made in the kernel from resident records: their entry points; what they
+// refuse and how their arguments are filled is source_cast.h's).  launch_policy.cpp plans every cast (which kernel, how launched);
+// launch_planned runs the plan.
 #include <cstdio>
 #include <cstring>
 #include <atomic>
@@ -11,7 +12,7 @@
 #include <rocprim/rocprim.hpp>
 #include "mrt_context.h"
 #include "gbuffer.h"
-#include "selected_shadow.h"
+#include "source_cast.h"
 
 namespace {
 
@@ -292,17 +293,33 @@ int cast_host_pipelined(mrt_ctx *ctx, const void *rays, void *hits, uint64_t cou
 	return finish_timing(ctx, false, launches >= 2, false);
 }
 
-// What every record-driven cast checks before it touches the device, in this order: its flags (HOST_LAYOUT for the entry that takes
-// arrays, ASYNC), then invalid() (what the family's own checks of its arguments find, or null; the arguments are not looked at before the
-// flags are known), the scene, a pending dispatch.  MRT_OK: go on (an empty cast is OK only after all of those: run_source_cast).
-template <class Invalid>
-int source_cast_check(mrt_ctx *ctx, bool array_entry, uint32_t flags, const char *unknown_flag, Invalid invalid)
+// What every record-driven cast checks before it touches the device, after its entry point's opening (array_params, grid_source_params):
+// why (what the family's *_invalid finds of the arguments and the flags, or null: source_cast.h, whose table has the order), the scene, a
+// pending dispatch.  MRT_OK: go on (an empty cast is OK only after all of those: run_source_cast).
+int source_cast_check(mrt_ctx *ctx, const char *why)
 {
-	const uint32_t known = (array_entry ? MRT_FLAG_HOST_LAYOUT : 0u) | MRT_FLAG_ASYNC;
-	if (flags & ~known) return fail(ctx, MRT_ERR_INVALID, unknown_flag);
-	if (const char *why = invalid()) return fail(ctx, MRT_ERR_INVALID, why);
+	if (why) return fail(ctx, MRT_ERR_INVALID, why);
 	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
 	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	return MRT_OK;
+}
+
+// The opening of an array form: the scene and the incoming rays.  host_rays: they are mrt_host_ray60 and the source reads them (a
+// shadow source does not: the record has the position).  A null d_rays is the family's first refusal.
+void array_params(mrt_ctx *ctx, const void *d_rays, bool host_rays, mrt::TraceParams &p)
+{
+	base_params(ctx, p);
+	p.rays = d_rays;
+	p.in_fmt = host_rays ? mrt::IN_HOST60 : mrt::IN_RAY32;
+}
+
+// The opening of a grid form: grid_params' refusals, then the lanes linear over the entries (the kernel regenerates the primary or
+// incoming ray of an entry from p.cam itself).  p.count = the records of the band.
+int grid_source_params(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1, mrt::TraceParams &p)
+{
+	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
+	if (rc) return rc;
+	p.in_fmt = mrt::IN_RAY32;
 	return MRT_OK;
 }
 
@@ -326,137 +343,68 @@ int run_source_cast(mrt_ctx *ctx, mrt::Entry entry, int src, int mode, mrt::Trac
 	return finish_timing(ctx, false, false, false); // (no tune_record: the grid tuner times primary casts only)
 }
 
-// The checks of a shadow cast's arguments that need no context (lights and nulls: before the scene), filling s as they go.
-const char *shadow_invalid(const void *d_hits, uint64_t count, const mrt_light *lights, uint32_t n_lights, const uint8_t *d_mask, mrt::ShadowParams &s)
+// Runs a family's batch (source_cast.h): out = its output, one b.out_fmt record per entry.
+template <class S>
+int cast_batch(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const mrt::sc::Batch &b, void *out, uint32_t query_mask,
+		const S &s, uint32_t flags)
 {
-	if (n_lights > MRT_MAX_LIGHTS) return "more than MRT_MAX_LIGHTS lights";
-	if (!d_hits || !d_mask || (n_lights && !lights)) return "null hits / lights / mask";
-	if (n_lights && count > ~0ull / n_lights) return "count * n_lights overflows";
-	std::memset(&s, 0, sizeof(s));
-	s.records = d_hits; s.pixels = count;
-	if (const char *why = mrt::sel::fill_shadow_lights(lights, n_lights, s.light)) return why;
-	return nullptr;
+	p.hits = out; p.count = b.count; p.query_mask = query_mask;
+	p.out_fmt = b.out_fmt;
+	return run_source_cast(ctx, entry, src, b.mode, p, s, flags);
 }
 
-// The shadow casts (mrt_cast_shadows, mrt_cast_grid_shadows) after their own checks: p holds the scene, the grid (grid source) and
-// the primary rays (SRC_SHADOW_RAY32); count = records.
+// The families' casts, array and grid form (ENTRY_X / ENTRY_GRID_X): p comes from the form's opening and holds the scene, the grid (grid
+// source) and the primary or incoming rays (array sources); count = records, pixel0 = the pixel index of record 0.
+
 int cast_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
 		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
 {
+	if (int rc = source_cast_check(ctx, mrt::sc::shadow_invalid(entry == mrt::ENTRY_SHADOW, p.rays, d_hits, count, lights, n_lights, d_mask, flags)))
+		return rc;
 	mrt::ShadowParams s;
-	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_SHADOW, flags, "unknown flag for a shadow cast",
-			[&] { return shadow_invalid(d_hits, count, lights, n_lights, d_mask, s); })) return rc;
-	p.hits = d_mask; p.count = count * n_lights; p.query_mask = query_mask;
-	p.out_fmt = mrt::OUT_BOOL8;
-	return run_source_cast(ctx, entry, src, MRT_MODE_ANY_HIT, p, s, flags);
+	mrt::sc::fill_shadow(d_hits, count, lights, n_lights, s);
+	return cast_batch(ctx, entry, src, p, mrt::sc::shadow_batch(src, count, n_lights), d_mask, query_mask, s, flags);
 }
 
-// The selected-shadow casts (mrt_cast_selected_shadows, mrt_cast_grid_selected_shadows): p holds the scene, the grid (grid source) and
-// the primary rays (SRC_SELSHADOW_RAY32; the grid form passes any non-null d_rays); count = records, pixel0 = the pixel index of
-// record 0.  The checks in the header's order (selected_shadow.h), not source_cast_check's: the pointers come before the flags.
+// (d_rays: the grid form passes any non-null pointer; the family checks it before its other pointers)
 int cast_selected_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_rays, const void *d_hits, uint64_t count,
 		uint32_t pixel0, const mrt_light_select *desc, const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
 {
-	if (const char *why = mrt::sel::cast_invalid(entry == mrt::ENTRY_SELECTED_SHADOW, d_rays, d_hits, desc, lights, n_lights, d_mask, flags))
-		return fail(ctx, MRT_ERR_INVALID, why);
-	if (!ctx->scene) return fail(ctx, MRT_ERR_NO_SCENE, "no scene uploaded");
-	if (ctx->pending) return fail(ctx, MRT_ERR_PENDING, "collect the pending dispatch first");
+	if (int rc = source_cast_check(ctx, mrt::sc::selected_shadow_invalid(entry == mrt::ENTRY_SELECTED_SHADOW, d_rays, d_hits, desc, lights,
+			n_lights, d_mask, flags))) return rc;
 	if (n_lights == 0) return MRT_OK; // (nothing to select from: nothing written, as a shadow cast without lights)
 	mrt::SelectShadowParams s;
-	mrt::sel::fill_params(d_hits, desc, lights, n_lights, pixel0, s);
-	p.hits = d_mask; p.count = count; p.query_mask = query_mask;
-	p.out_fmt = mrt::OUT_BOOL8;
-	return run_source_cast(ctx, entry, src, MRT_MODE_ANY_HIT, p, s, flags);
+	mrt::sc::fill_selected_shadow(d_hits, desc, lights, n_lights, pixel0, s);
+	return cast_batch(ctx, entry, src, p, mrt::sc::selected_shadow_batch(src, count), d_mask, query_mask, s, flags);
 }
 
-// The reflection casts (mrt_cast_reflections, mrt_cast_grid_reflections) after their own checks: p holds the scene, the grid (grid
-// source) and the incoming rays (SRC_REFLECT_RAY32, SRC_REFLECT_HOST); count = records.
 int cast_reflections(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
 		const uint8_t *d_select, float max_distance, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
 {
-	const auto invalid = [&]() -> const char * {
-		if (!d_hits || !d_out_hits) return "null hits / output hits";
-		if (!(max_distance > 0.0f && max_distance <= FLT_MAX)) return "max_distance must be finite and > 0";
-		return nullptr;
-	};
-	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_REFLECTION, flags, "unknown flag for a reflection cast", invalid)) return rc;
+	if (int rc = source_cast_check(ctx, mrt::sc::reflection_invalid(entry == mrt::ENTRY_REFLECTION, p.rays, d_hits, max_distance, d_out_hits, flags)))
+		return rc;
 	mrt::ReflectParams s;
-	s.records = d_hits; s.select = d_select; s.out_rays = d_out_rays; s.max_distance = max_distance;
-	p.hits = d_out_hits; p.count = count; p.query_mask = query_mask;
-	p.out_fmt = src == mrt::SRC_REFLECT_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32;
-	return run_source_cast(ctx, entry, src, MRT_MODE_NEAREST, p, s, flags);
+	mrt::sc::fill_reflection(d_hits, d_select, max_distance, d_out_rays, s);
+	return cast_batch(ctx, entry, src, p, mrt::sc::reflection_batch(src, count), d_out_hits, query_mask, s, flags);
 }
 
-// The checks of a hemisphere descriptor and its outputs that need no context: what the entry points refuse before anything else.
-const char *hemisphere_invalid(const mrt_hemisphere *desc, const void *d_hits, uint64_t count, const void *d_out, const void *d_out_rays, int mode)
-{
-	if (!desc) return "null descriptor";
-	if (desc->n_samples < 1u || desc->n_samples > MRT_MAX_HEMISPHERE_SAMPLES) return "n_samples outside 1 .. MRT_MAX_HEMISPHERE_SAMPLES";
-	if (!(desc->t_max > 1e-4f && desc->t_max <= FLT_MAX)) return "t_max must be finite and > 1e-4 (t_min)";
-	if (mode != MRT_MODE_NEAREST && mode != MRT_MODE_ANY_HIT) return "unknown mode";
-	if (mode == MRT_MODE_ANY_HIT && d_out_rays) return "any-hit writes no rays: d_out_rays must be null";
-	if (!d_hits || !d_out) return "null hits / output";
-	if (count > ~0ull / desc->n_samples) return "count * n_samples overflows";
-	return nullptr;
-}
-
-// The jump of the first draw of every sample (k = first_draw + 2 * sample): one pass over the draws.
-void hemisphere_jumps(uint32_t first_draw, uint32_t n_samples, mrt::HemiJump *out)
-{
-	mrt::HemiJump j = mrt::pcg_jump(first_draw);
-	for (uint32_t s = 0; s < n_samples; s++) {
-		out[s] = j;
-		for (int k = 0; k < 2; k++) { j.a = mrt::kPcgMul * j.a; j.c = mrt::kPcgMul * j.c + mrt::kPcgInc; }
-	}
-}
-
-// The hemisphere casts (mrt_cast_hemisphere, mrt_cast_grid_hemisphere) after their own checks: p holds the scene, the grid (grid
-// source) and the incoming rays (SRC_HEMI_RAY32, SRC_HEMI_HOST); count = records, pixel0 = the pixel index of record 0.
 int cast_hemisphere(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count, uint32_t pixel0,
 		const mrt_hemisphere *desc, void *d_out, void *d_out_rays, uint32_t query_mask, int mode, uint32_t flags)
 {
-	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_HEMISPHERE, flags, "unknown flag for a hemisphere cast",
-			[&] { return hemisphere_invalid(desc, d_hits, count, d_out, d_out_rays, mode); })) return rc;
-	const bool any = mode == MRT_MODE_ANY_HIT;
+	if (int rc = source_cast_check(ctx, mrt::sc::hemisphere_invalid(entry == mrt::ENTRY_HEMISPHERE, p.rays, d_hits, count, desc, d_out, d_out_rays,
+			mode, flags))) return rc;
 	mrt::HemiParams s;
-	std::memset(&s, 0, sizeof(s));
-	s.records = d_hits; s.select = desc->d_select; s.out_rays = d_out_rays; s.pixels = count; s.t_max = desc->t_max;
-	s.seed_add = pixel0 * 1009u + desc->frame * 6529u + 7u;
-	hemisphere_jumps(desc->first_draw, desc->n_samples, s.jump);
-	p.hits = d_out; p.count = count * desc->n_samples; p.query_mask = query_mask;
-	p.out_fmt = any ? mrt::OUT_BOOL8 : (src == mrt::SRC_HEMI_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32);
-	return run_source_cast(ctx, entry, src, mode, p, s, flags);
+	mrt::sc::fill_hemisphere(d_hits, count, pixel0, desc, d_out_rays, s);
+	return cast_batch(ctx, entry, src, p, mrt::sc::hemisphere_batch(src, count, desc->n_samples, mode), d_out, query_mask, s, flags);
 }
 
-// The checks of a bounce descriptor and its outputs that need no context: what the entry points refuse before anything else.
-const char *bounce_invalid(const mrt_bounce *desc, const void *d_hits, const void *d_out_hits)
-{
-	if (!desc) return "null descriptor";
-	if (!(desc->t_max > 1e-4f && desc->t_max <= FLT_MAX)) return "t_max must be finite and > 1e-4 (t_min)";
-	if (!desc->d_surface) { // (the comparisons are false for a NaN)
-		if (!(desc->metallic >= 0.0f && desc->metallic <= 1.0f)) return "metallic must be in [0, 1]";
-		if (!(desc->roughness >= 0.0f && desc->roughness <= 1.0f)) return "roughness must be in [0, 1]";
-	}
-	if (!d_hits || !d_out_hits) return "null hits / output";
-	return nullptr;
-}
-
-// The bounce casts (mrt_cast_bounce, mrt_cast_grid_bounce) after their own checks: p holds the scene, the grid (grid source) and the
-// incoming rays (SRC_BOUNCE_RAY32, SRC_BOUNCE_HOST); count = records, pixel0 = the pixel index of record 0.
 int cast_bounce(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count, uint32_t pixel0,
 		const mrt_bounce *desc, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
 {
-	if (int rc = source_cast_check(ctx, entry == mrt::ENTRY_BOUNCE, flags, "unknown flag for a bounce cast",
-			[&] { return bounce_invalid(desc, d_hits, d_out_hits); })) return rc;
+	if (int rc = source_cast_check(ctx, mrt::sc::bounce_invalid(entry == mrt::ENTRY_BOUNCE, p.rays, d_hits, desc, d_out_hits, flags))) return rc;
 	mrt::BounceParams s;
-	std::memset(&s, 0, sizeof(s));
-	s.records = d_hits; s.select = desc->d_select; s.surface = desc->d_surface; s.out_rays = d_out_rays; s.out_lobe = desc->d_out_lobe;
-	s.t_max = desc->t_max; s.metallic = desc->metallic; s.roughness = desc->roughness;
-	s.seed_add = pixel0 * 1009u + desc->frame * 6529u + 7u;
-	s.jump = mrt::pcg_jump(desc->first_draw);
-	p.hits = d_out_hits; p.count = count; p.query_mask = query_mask;
-	p.out_fmt = src == mrt::SRC_BOUNCE_HOST ? mrt::OUT_HOST44 : mrt::OUT_HIT32;
-	return run_source_cast(ctx, entry, src, MRT_MODE_NEAREST, p, s, flags);
+	mrt::sc::fill_bounce(d_hits, pixel0, desc, d_out_rays, s);
+	return cast_batch(ctx, entry, src, p, mrt::sc::bounce_batch(src, count), d_out_hits, query_mask, s, flags);
 }
 
 } // namespace
@@ -608,14 +556,14 @@ int mrt_cast_tiled(mrt_ctx *ctx, const mrt_ray32 *d_rays, mrt_hit32 *d_hits,
 	return finish_timing(ctx, false, false, false);
 }
 
+// ---- the record-driven casts: each entry point is its form's opening (array_params / grid_source_params), its source and its family --------
+
 int mrt_cast_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count,
 		const mrt_light *lights, uint32_t n_lights, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
 {
 	if (!ctx) return MRT_ERR_INVALID;
-	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
 	mrt::TraceParams p;
-	base_params(ctx, p);
-	p.rays = d_rays; // (SRC_SHADOW_HOST44: not read, the record has the position)
+	array_params(ctx, d_rays, false, p);
 	const int src = (flags & MRT_FLAG_HOST_LAYOUT) ? mrt::SRC_SHADOW_HOST44 : mrt::SRC_SHADOW_RAY32;
 	return cast_shadows(ctx, mrt::ENTRY_SHADOW, src, p, d_hits, count, lights, n_lights, d_mask, query_mask, flags);
 }
@@ -625,9 +573,7 @@ int mrt_cast_grid_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, 
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	mrt::TraceParams p;
-	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
-	if (rc) return rc;
-	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the pairs; the kernel regenerates the primary ray from p.cam itself)
+	if (int rc = grid_source_params(ctx, cam, grid_w, grid_h, y0, y1, p)) return rc;
 	return cast_shadows(ctx, mrt::ENTRY_GRID_SHADOW, mrt::SRC_SHADOW_GRID, p, d_hits, p.count, lights, n_lights, d_mask, query_mask, flags);
 }
 
@@ -636,8 +582,7 @@ int mrt_cast_selected_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hi
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	mrt::TraceParams p;
-	base_params(ctx, p);
-	p.rays = d_rays; // (SRC_SELSHADOW_HOST44: not read, the record has the position)
+	array_params(ctx, d_rays, false, p);
 	const int src = (flags & MRT_FLAG_HOST_LAYOUT) ? mrt::SRC_SELSHADOW_HOST44 : mrt::SRC_SELSHADOW_RAY32;
 	return cast_selected_shadows(ctx, mrt::ENTRY_SELECTED_SHADOW, src, p, d_rays, d_hits, count, 0u, desc, lights, n_lights, d_mask, query_mask, flags);
 }
@@ -648,9 +593,7 @@ int mrt_cast_grid_selected_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	mrt::TraceParams p;
-	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
-	if (rc) return rc;
-	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the records; the kernel regenerates the primary ray from p.cam itself)
+	if (int rc = grid_source_params(ctx, cam, grid_w, grid_h, y0, y1, p)) return rc;
 	return cast_selected_shadows(ctx, mrt::ENTRY_GRID_SELECTED_SHADOW, mrt::SRC_SELSHADOW_GRID, p, cam, d_hits, p.count, y0 * grid_w, desc, lights,
 			n_lights, d_mask, query_mask, flags);
 }
@@ -659,12 +602,9 @@ int mrt_cast_reflections(mrt_ctx *ctx, const void *d_rays, const void *d_hits, u
 		float max_distance, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
 {
 	if (!ctx) return MRT_ERR_INVALID;
-	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
-	mrt::TraceParams p;
-	base_params(ctx, p);
-	p.rays = d_rays; // (read for every source: the incoming direction)
 	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
-	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
+	mrt::TraceParams p;
+	array_params(ctx, d_rays, host, p);
 	return cast_reflections(ctx, mrt::ENTRY_REFLECTION, host ? mrt::SRC_REFLECT_HOST : mrt::SRC_REFLECT_RAY32, p, d_hits, count,
 			d_select, max_distance, d_out_hits, d_out_rays, query_mask, flags);
 }
@@ -675,9 +615,7 @@ int mrt_cast_grid_reflections(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	mrt::TraceParams p;
-	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
-	if (rc) return rc;
-	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the records; the kernel regenerates the incoming ray from p.cam itself)
+	if (int rc = grid_source_params(ctx, cam, grid_w, grid_h, y0, y1, p)) return rc;
 	return cast_reflections(ctx, mrt::ENTRY_GRID_REFLECTION, mrt::SRC_REFLECT_GRID, p, d_hits, p.count, d_select, max_distance,
 			d_out_hits, d_out_rays, query_mask, flags);
 }
@@ -686,12 +624,9 @@ int mrt_cast_hemisphere(mrt_ctx *ctx, const void *d_rays, const void *d_hits, ui
 		void *d_out, void *d_out_rays, uint32_t query_mask, int mode, uint32_t flags)
 {
 	if (!ctx) return MRT_ERR_INVALID;
-	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
-	mrt::TraceParams p;
-	base_params(ctx, p);
-	p.rays = d_rays; // (read for every source: the incoming direction)
 	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
-	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
+	mrt::TraceParams p;
+	array_params(ctx, d_rays, host, p);
 	return cast_hemisphere(ctx, mrt::ENTRY_HEMISPHERE, host ? mrt::SRC_HEMI_HOST : mrt::SRC_HEMI_RAY32, p, d_hits, count, 0u, desc,
 			d_out, d_out_rays, query_mask, mode, flags);
 }
@@ -701,9 +636,7 @@ int mrt_cast_grid_hemisphere(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	mrt::TraceParams p;
-	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
-	if (rc) return rc;
-	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the entries; the kernel regenerates the incoming ray from p.cam itself)
+	if (int rc = grid_source_params(ctx, cam, grid_w, grid_h, y0, y1, p)) return rc;
 	return cast_hemisphere(ctx, mrt::ENTRY_GRID_HEMISPHERE, mrt::SRC_HEMI_GRID, p, d_hits, p.count, y0 * grid_w, desc, d_out, d_out_rays,
 			query_mask, mode, flags);
 }
@@ -712,12 +645,9 @@ int mrt_cast_bounce(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64
 		void *d_out_rays, uint32_t query_mask, uint32_t flags)
 {
 	if (!ctx) return MRT_ERR_INVALID;
-	if (!d_rays) return fail(ctx, MRT_ERR_INVALID, "null rays");
-	mrt::TraceParams p;
-	base_params(ctx, p);
-	p.rays = d_rays; // (read for every source: the incoming direction)
 	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
-	p.in_fmt = host ? mrt::IN_HOST60 : mrt::IN_RAY32;
+	mrt::TraceParams p;
+	array_params(ctx, d_rays, host, p);
 	return cast_bounce(ctx, mrt::ENTRY_BOUNCE, host ? mrt::SRC_BOUNCE_HOST : mrt::SRC_BOUNCE_RAY32, p, d_hits, count, 0u, desc, d_out_hits,
 			d_out_rays, query_mask, flags);
 }
@@ -727,28 +657,26 @@ int mrt_cast_grid_bounce(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, u
 {
 	if (!ctx) return MRT_ERR_INVALID;
 	mrt::TraceParams p;
-	int rc = grid_params(ctx, cam, grid_w, grid_h, y0, y1, p);
-	if (rc) return rc;
-	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the entries; the kernel regenerates the incoming ray from p.cam itself)
+	if (int rc = grid_source_params(ctx, cam, grid_w, grid_h, y0, y1, p)) return rc;
 	return cast_bounce(ctx, mrt::ENTRY_GRID_BOUNCE, mrt::SRC_BOUNCE_GRID, p, d_hits, p.count, y0 * grid_w, desc, d_out_hits, d_out_rays,
 			query_mask, flags);
 }
 
-// Reflection rays from a rasteriser's G-buffer (gbuffer_kernel.h): a whole frame, count = W * H; the checks in the family's order.
+// Reflection rays from a rasteriser's G-buffer (gbuffer_kernel.h): a whole frame, count = W * H; no ray is read (the lanes are linear
+// over the pixels).  The family's pair is gbuffer.h's.
 int mrt_cast_gbuffer_reflections(mrt_ctx *ctx, const mrt_gbuffer *gbuffer, uint32_t W, uint32_t H, mrt_hit32 *d_out_hits,
 		mrt_ray32 *d_out_rays, uint32_t query_mask, uint32_t flags)
 {
 	if (!ctx) return MRT_ERR_INVALID;
-	if (int rc = source_cast_check(ctx, false, flags, "unknown flag for a G-buffer reflection cast",
-			[&] { return mrt::gb::cast_invalid(gbuffer, W, H, d_out_hits); })) return rc;
+	if (int rc = source_cast_check(ctx, mrt::sc::unknown_flag(false, flags) ? "unknown flag for a G-buffer reflection cast"
+			: mrt::gb::cast_invalid(gbuffer, W, H, d_out_hits))) return rc;
 	mrt::TraceParams p;
 	base_params(ctx, p);
-	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the pixels; no ray is read)
+	p.in_fmt = mrt::IN_RAY32; // (the lanes are linear over the pixels)
 	mrt::GBufferParams s;
 	mrt::gb::fill_params(gbuffer, W, H, d_out_rays, s);
-	p.hits = d_out_hits; p.count = (uint64_t)W * H; p.query_mask = query_mask;
-	p.out_fmt = mrt::OUT_HIT32;
-	return run_source_cast(ctx, mrt::ENTRY_GBUFFER_REFLECTION, mrt::SRC_GBUFFER, MRT_MODE_NEAREST, p, s, flags);
+	return cast_batch(ctx, mrt::ENTRY_GBUFFER_REFLECTION, mrt::SRC_GBUFFER, p, mrt::sc::batch(mrt::SRC_GBUFFER, MRT_MODE_NEAREST, (uint64_t)W * H),
+			d_out_hits, query_mask, s, flags);
 }
 
 } // extern "C"

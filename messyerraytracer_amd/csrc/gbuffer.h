@@ -91,7 +91,7 @@ inline void fill_params(const mrt_gbuffer *g, uint32_t w, uint32_t h, void *out_
 }
 
 // host/gbuffer_data.cpp (no device, no library): what the two calls refuse before any device work, or null, in the order
-// include/mrt_hip.h lists (the cast's flags are checked before, with every record-driven cast's: source_cast_check).
+// include/mrt_hip.h lists (the cast's flags are checked before, as every record-driven cast's: source_cast.h unknown_flag).
 const char *cast_invalid(const mrt_gbuffer *g, uint32_t w, uint32_t h, const void *d_out_hits);
 const char *image_invalid(const mrt_gbuffer *g, uint32_t w, uint32_t h, const void *d_hits, const void *d_reflection, uint32_t flags);
 

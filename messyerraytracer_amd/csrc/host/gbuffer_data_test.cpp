@@ -50,7 +50,7 @@ void refusals()
 	expect(sizeof(mrt_gbuffer) == 160, "mrt_gbuffer is 160 bytes");
 	const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
 	const uint32_t BIG = 0xffffffffu;
-	for (int call = 0; call < 2; call++) { // 0: the cast (its flags are source_cast_check's), 1: the image
+	for (int call = 0; call < 2; call++) { // 0: the cast (its flags are checked in cast.hip), 1: the image
 		const std::string c = call ? "image: " : "cast: ";
 		mrt_gbuffer bad = defaults();
 		bad.d_depth = nullptr; bad.d_normal_roughness = nullptr; bad.struct_size = 159u; bad.normal_kind = 2u;

@@ -2,6 +2,7 @@
 // include/mrt_hip.h lists, the generator's jump to a bounce's first draw and the kernel's copy of a descriptor (path.h).  No device and
 // no HIP call, so that csrc/host/path_data_test.cpp drives it alone.
 #include "../path.h"
+#include "../source_cast.h"
 
 #include <cmath>
 
@@ -48,7 +49,7 @@ void fill_path_params(const mrt_path_step_desc *desc, uint32_t pixel0, PathParam
 	s.direct = desc->d_direct; s.state = desc->d_state;
 	s.out_select = desc->d_out_select; s.out_lobe = desc->d_out_lobe; s.active_count = desc->d_active_count;
 	s.bounce = desc->bounce; s.max_bounces = desc->max_bounces;
-	s.seed_add = pixel0 * 1009u + desc->frame * 6529u + 7u;
+	s.seed_add = sc::seed_add(pixel0, desc->frame); // the seed rule of every record-driven cast
 	path_jump(path_first_draw(desc->bounce), s.jump_a, s.jump_c);
 	const mrt_environment *env = desc->env;
 	for (int k = 0; k < 3; k++) {

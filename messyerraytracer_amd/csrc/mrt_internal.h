@@ -204,7 +204,7 @@ struct ReflectParams {
 // ---- cosine-weighted hemisphere rays (hemisphere_kernel.h): n_samples rays per hit record of a cast ----------------------------
 // Entry g of a hemisphere cast is the pair (sample g / pixels, pixel g % pixels); TraceParams::count = pixels * n_samples, hits = one
 // byte per entry (any-hit) or one record per entry (closest-hit), rays = the incoming rays as for reflections.  The generator's state
-// before a sample's first draw is jump[sample].a * state0 + jump[sample].c (hemisphere_jumps, cast.hip).
+// before a sample's first draw is jump[sample].a * state0 + jump[sample].c (hemisphere_jumps, source_cast.h).
 constexpr uint32_t kPcgMul = 747796405u, kPcgInc = 2891336453u; // the reference's PCG32 (path_state.h): state' = state * mul + inc
 struct HemiJump { uint32_t a, c; };
 // (A, C) with: PCG32 state before draw k = A * state0 + C, modulo 2^32, by squaring: the step (a, c) applied twice is (a * a, a * c + c).
@@ -243,7 +243,7 @@ struct BounceParams {
 	HemiJump jump;             // (A, C) of draw first_draw
 };
 
-// ---- one shadow ray per record, to the light the record draws (selected_shadow_kernel.h; selected_shadow.h fills this) ---------------
+// ---- one shadow ray per record, to the light the record draws (selected_shadow_kernel.h; source_cast.h fills this) ------------------
 // Entry i of a selected-shadow cast is record i; TraceParams::count = records, hits = the lit mask (one byte per record), rays = the
 // primary rays (SRC_SELSHADOW_RAY32).  The generator's state before the selecting draw is jump.a * state0 + jump.c, as for a bounce.
 struct SelectShadowParams {

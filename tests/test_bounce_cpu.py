@@ -1,6 +1,6 @@
 """Bounce casts without a device: the library exports mrt_cast_bounce / mrt_cast_grid_bounce and the calls reject a null context and
 bad arguments before any device work; the launch policy plans them as reflection casts that never touch the primary grid's state
-(csrc/host/bounce_policy_test.cpp); the numpy restatement of the sampler (messyerraytracer_amd/bounce.py, what the GPU tests hold the
+(csrc/host/record_policy_test.cpp); the numpy restatement of the sampler (messyerraytracer_amd/bounce.py, what the GPU tests hold the
 kernels to byte for byte) against values recorded from the reference's own sample_bounce, ggx_sample_half and PCG32
 (tests/golden/bounce_reference.npz); the diffuse lobe against hemisphere.py; the jump constants."""
 import ctypes as C
@@ -65,8 +65,8 @@ def test_null_context_and_bad_arguments_are_invalid():
 
 
 def test_bounce_policy_driver():
-    exe = mbuild.build_bounce_policy_test()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = mbuild.build_record_policy_test()
+    r = subprocess.run([exe, "bounce"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout and " checks hold " in r.stdout, r.stdout
 

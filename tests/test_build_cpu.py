@@ -71,15 +71,21 @@ def test_stream_gate_is_the_tests_alone():
 
 
 def test_public_build_names():
-    for name in ("build_lib", "build_host_test", "build_host_cpu_test", "build_host_tlas_test", "build_policy_test",
-                 "build_shadow_policy_test", "build_reflection_policy_test", "build_hemisphere_policy_test", "build_bounce_policy_test",
+    rows = ["build_" + name for name in build.DRIVERS if not name.endswith("_san")]
+    assert set(rows) >= {"build_record_policy_test", "build_source_cast_data_test", "build_gbuffer_data_test", "build_lane_map_fast_test"}
+    for name in ["build_lib", "build_drivers", "build_host_test", "build_host_cpu_test", "build_host_tlas_test", "build_policy_test",
+                 "build_shadow_policy_test", "build_reflection_policy_test", "build_hemisphere_policy_test", "build_bounce_policy_test", "build_gbuffer_policy_test",
                  "build_instance_math_test", "build_build_rules_test", "build_shade_data_test", "build_light_data_test", "build_path_data_test",
-                 "build_texture_data_test", "build_lane_map_test", "build_stream_gate"):
+                 "build_texture_data_test", "build_lane_map_test", "build_stream_gate"] + rows:
         f = getattr(build, name)
         params = inspect.signature(f).parameters
         assert "force" in params and params["force"].default is False, name
     assert inspect.signature(build.build_lane_map_test).parameters["sanitize"].default is False
     assert inspect.signature(build.build_build_rules_test).parameters["sanitize"].default is False
+    for name in rows:  # sanitize exactly where the row has a sanitized twin
+        params = inspect.signature(getattr(build, name)).parameters
+        assert ("sanitize" in params) == (name[len("build_"):] + "_san" in build.DRIVERS), name
+        assert "sanitize" not in params or params["sanitize"].default is False, name
     lib = inspect.signature(build.build_lib).parameters
     assert [lib[k].default for k in ("verbose", "lib", "obj_dir", "defines")] == [False, None, None, None]
     assert build.LIB == os.path.join(build.HERE, "libmrt_hip.so")

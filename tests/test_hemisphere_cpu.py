@@ -1,6 +1,6 @@
 """Hemisphere casts without a device: the library exports mrt_cast_hemisphere / mrt_cast_grid_hemisphere and the calls reject a null
 context and bad arguments before any device work; the launch policy plans them as unsorted non-coherent batches that never touch the
-primary grid's state (csrc/host/hemisphere_policy_test.cpp); the numpy restatement of the sampler (messyerraytracer_amd/hemisphere.py,
+primary grid's state (csrc/host/record_policy_test.cpp); the numpy restatement of the sampler (messyerraytracer_amd/hemisphere.py,
 what the GPU tests hold the kernels to byte for byte) against values recorded from the reference's own PCG32 and
 cosine_hemisphere_sample (tests/golden/hemisphere_reference.npz), and the accuracy condition on its sincos pair."""
 import ctypes as C
@@ -61,8 +61,8 @@ def test_null_context_and_bad_arguments_are_invalid():
 
 
 def test_hemisphere_policy_driver():
-    exe = mbuild.build_hemisphere_policy_test()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = mbuild.build_record_policy_test()
+    r = subprocess.run([exe, "hemisphere"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout and " checks hold " in r.stdout, r.stdout
 

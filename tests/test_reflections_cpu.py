@@ -1,6 +1,6 @@
 """Reflection casts without a device: the library exports mrt_cast_reflections / mrt_cast_grid_reflections, the calls reject a null
 context and bad arguments before any device work, and the launch policy plans reflection casts as unsorted non-coherent closest-hit
-batches that never touch the primary grid's state (csrc/host/reflection_policy_test.cpp, launch_policy.cpp alone); the numpy
+batches that never touch the primary grid's state (csrc/host/record_policy_test.cpp, launch_policy.cpp alone); the numpy
 restatement of the formula (messyerraytracer_amd/reflection.py, what the GPU tests hold the kernels to byte for byte) against float64
 within a derived bound, and its exact properties."""
 import ctypes as C
@@ -45,8 +45,8 @@ def test_bad_arguments_without_a_context_are_invalid():
 
 
 def test_reflection_policy_driver():
-    exe = mbuild.build_reflection_policy_test()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = mbuild.build_record_policy_test()
+    r = subprocess.run([exe, "reflection"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout and " checks hold " in r.stdout, r.stdout
 

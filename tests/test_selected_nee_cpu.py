@@ -1,5 +1,5 @@
 """Next-event estimation with one light per record, without a device: the numpy restatement (messyerraytracer_amd/nee.py, what the GPU
-tests hold the kernels to byte for byte) and the host side of the casts (csrc/host/selected_shadow_data_test.cpp).  Fixed inputs, so
+tests hold the kernels to byte for byte) and the plans of the casts (csrc/host/record_policy_test.cpp; their host side: tests/test_source_cast_cpu.py).  Fixed inputs, so
 every check is deterministic.
 
 The two statistical checks state their bound before they look: 5 standard deviations of the exact distribution, which a correct
@@ -206,12 +206,8 @@ def test_the_selection_is_uniform(n_lights):
     assert (np.abs(counts - n * q) <= 5 * sigma).all()
 
 
-@pytest.mark.parametrize("sanitize", [False, True])
-def test_selected_shadow_data_driver(sanitize):
-    """The host side of the casts -- the refusals in the header's order, the jump, the seed of a row band, the light kinds -- as a
-    program of its own, with and without the sanitizers; never loaded into this process."""
-    exe = mbuild.build_selected_shadow_data_test(sanitize=sanitize)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+def test_selected_shadow_policy_driver():
+    exe = mbuild.build_record_policy_test()
+    r = subprocess.run([exe, "selected_shadow"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout and " checks hold " in r.stdout, r.stdout
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr

@@ -1,6 +1,6 @@
 """Shadow casts without a device: the library exports mrt_cast_shadows / mrt_cast_grid_shadows, mrt_light is the 32-byte struct the
 binding declares, the calls reject bad arguments before any device work, and the launch policy plans shadow casts as unsorted
-non-coherent any-hit batches that never touch the primary grid's state (csrc/host/shadow_policy_test.cpp, launch_policy.cpp alone);
+non-coherent any-hit batches that never touch the primary grid's state (csrc/host/record_policy_test.cpp, launch_policy.cpp alone);
 the numpy restatement of the formula (messyerraytracer_amd/shadow.py, what the GPU tests hold the kernels to byte for byte) against
 rays recorded from the reference's own text (tests/golden/shadow_reference.npz), three deliberately wrong variants the
 recording must tell apart, the host-layout ray against Ray::_precompute (tests/golden/ray_reference.npz), and the oracle on every
@@ -42,8 +42,8 @@ def test_null_context_is_invalid():
 
 
 def test_shadow_policy_driver():
-    exe = mbuild.build_shadow_policy_test()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = mbuild.build_record_policy_test()
+    r = subprocess.run([exe, "shadow"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout and " checks hold " in r.stdout, r.stdout
 
