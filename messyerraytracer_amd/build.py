@@ -47,6 +47,7 @@ DRIVERS = {
     "record_policy_test": (["host/record_policy_test.cpp", "launch_policy.cpp"], POLICY, False),  # the six record-driven families: <exe> [family]
     "instance_math_test": (["host/instance_math_test.cpp"], CPU, False),  # instance_math.h, shared by the host path and the device TLAS build
     "build_rules_test": (["host/build_rules_test.cpp"], CPU, False),  # build_rules.h, shared by the host and the device scene builders
+    "walk_steps_test": (["host/walk_steps_test.cpp"], CPU, False),  # walk_steps.h (the token expansion, the host walkers) against oracle/mrt_oracle.c
     "shade_data_test": (["host/shade_data_test.cpp", "host/shade_data.cpp"], CPU, False),
     "light_data_test": (["host/light_data_test.cpp", "host/light_data.cpp"], CPU, False),
     "path_data_test": (["host/path_data_test.cpp", "host/path_data.cpp"], CPU, False),
@@ -61,7 +62,7 @@ DRIVERS = {
     "lane_map_test": (["host/lane_map_test.cpp"], LANE, False),  # lane_map.h
     "lane_map_fast_test": (["host/lane_map_fast_test.cpp"], LANE, False),  # lane_map.h: the short map of whole-tile pairs
 }
-for _name in ("build_rules_test", "accum_data_test", "denoise_data_test", "svgf_data_test", "gbuffer_data_test", "source_cast_data_test",
+for _name in ("build_rules_test", "walk_steps_test", "accum_data_test", "denoise_data_test", "svgf_data_test", "gbuffer_data_test", "source_cast_data_test",
               "lane_map_test", "lane_map_fast_test"):
     DRIVERS[_name + "_san"] = _twin(DRIVERS[_name])
 
@@ -161,7 +162,7 @@ def build_driver(name: str, force: bool = False) -> str:
     """One row of DRIVERS, rebuilt when a source, any header of csrc or (if it links it) the library is newer."""
     srcs, flags, links = DRIVERS[name]
     srcs, exe = [os.path.join(CSRC, s) for s in srcs], os.path.join(HERE, name)
-    headers = [h for pat in ("*.h", "*.inc", "host/*.h", "host/*.hpp", "../../include/*.h") for h in glob.glob(os.path.join(CSRC, pat))]
+    headers = [h for pat in ("*.h", "*.inc", "host/*.h", "host/*.hpp", "../../include/*.h", "../../oracle/mrt_oracle.[ch]") for h in glob.glob(os.path.join(CSRC, pat))]
     if force or _stale(exe, srcs + headers + ([LIB] if links else [])):
         _run([_hipcc()] + flags + srcs + ["-o", exe] + (["-L" + HERE, "-lmrt_hip", "-Wl,-rpath," + HERE, "-pthread"] if links else []), name + " build")
     return exe

@@ -1,27 +1,17 @@
-// device_common.h — what every kernel unit shares (kernels.hip, shade_kernels.hip, prep_kernels.hip): the canonical arithmetic, the
+// device_common.h — what every kernel unit shares (kernels.hip, shade_kernels.hip, prep_kernels.hip): the
 // lane -> ray map's glue, the camera's rays, and the load of a ray and the store of a record.  Included inside namespace mrt, after
-// mrt_internal.h and lane_map.h.  Every function is __forceinline__, so a unit gets the same code whichever unit it is.
+// mrt_internal.h, lane_map.h and walk_steps.h (the canonical arithmetic).  Every function is __forceinline__, so a unit gets the same code whichever unit it is.
 #pragma once
 
 #define MRT_WG 256
 #define MRT_WAVE 64
 
-// ---- canonical arithmetic ------------------------------------------------------
-__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz)
-{
-	return fma_(ax, bx, fma_(ay, by, az * bz));
-}
-// safe_inv_direction, bvh_traverse.comp.glsl:137-145 == Ray::_precompute, src/core/ray.h:78-89
-__device__ __forceinline__ float safe_inv(float d)
-{
-	const float eps = 1e-9f;
-	const float big = 1.0f / eps;
-	return __builtin_fabsf(d) > eps ? 1.0f / d : (d >= 0.0f ? big : -big);
-}
+// ---- canonical arithmetic: walk_steps.h (fma_, dot3, safe_inv and the steps of a walk), which the unit includes before namespace mrt ----
 
 struct RayRegs {
 	float ox, oy, oz, dx, dy, dz, t_min, t_max;
+	__device__ __forceinline__ V3 o() const { return {ox, oy, oz}; }
+	__device__ __forceinline__ V3 d() const { return {dx, dy, dz}; }
 };
 
 // Two launches are queued for a batch declared coherent: the packet kernel and, behind it, the

@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 #include "host_types.hpp"
+#include "../walk_steps.h"
 #include "../../../include/mrt_hip.h"
 
 namespace mrt {
@@ -135,10 +136,8 @@ public:
 		Intersection out; // a miss record as the default constructor leaves it (Intersection::set_miss, intersection.h:45-52)
 		if (stats) stats->rays_cast++;
 		if (n_tris_ == 0 || ray.t_min >= ray.t_max) return out; // degenerate rays are misses (glsl:214-222)
-		const float ox = ray.origin.x, oy = ray.origin.y, oz = ray.origin.z;
-		const float dx = ray.direction.x, dy = ray.direction.y, dz = ray.direction.z;
-		const float ix = safe_inv(dx), iy = safe_inv(dy), iz = safe_inv(dz);
-		const float nrx = -(ox * ix), nry = -(oy * iy), nrz = -(oz * iz);
+		const Vector3 &o = ray.origin, &d = ray.direction;
+		const RayInv inv = ray_inverse(o, d);
 		float best_t = ray.t_max, best_u = 0.0f, best_v = 0.0f;
 		uint32_t best_tri = UINT32_MAX, best_id = UINT32_MAX;
 		uint32_t stack[128];
@@ -149,7 +148,7 @@ public:
 		if (nodes_[0].tri_count > 0) {
 			float tn;
 			if (stats) stats->bvh_nodes_visited++;
-			if (!slab(nodes_[0], ix, iy, iz, nrx, nry, nrz, ray.t_min, best_t, tn)) return out;
+			if (!slab(nodes_[0], inv, ray.t_min, best_t, tn)) return out;
 		}
 		for (;;) {
 			const mrt_bvh_node32 &n = nodes_[cur];
@@ -159,24 +158,8 @@ public:
 					const Triangle &t = tris_[ti];
 					if ((t.layers & query_mask) == 0u) continue;
 					if (stats) stats->tri_tests++;
-					// ray_triangle, glsl:105-131 == Triangle::intersect, src/core/triangle.h:56-105
-					const float pvx = std::fmaf(dy, t.edge2.z, -(dz * t.edge2.y));
-					const float pvy = std::fmaf(dz, t.edge2.x, -(dx * t.edge2.z));
-					const float pvz = std::fmaf(dx, t.edge2.y, -(dy * t.edge2.x));
-					const float det = dot3(t.edge1.x, t.edge1.y, t.edge1.z, pvx, pvy, pvz);
-					if (std::fabs(det) < 1e-8f) continue;
-					const float inv_det = 1.0f / det;
-					const float tvx = ox - t.v0.x, tvy = oy - t.v0.y, tvz = oz - t.v0.z;
-					const float u = dot3(tvx, tvy, tvz, pvx, pvy, pvz) * inv_det;
-					if (u < 0.0f || u > 1.0f) continue;
-					const float qvx = std::fmaf(tvy, t.edge1.z, -(tvz * t.edge1.y));
-					const float qvy = std::fmaf(tvz, t.edge1.x, -(tvx * t.edge1.z));
-					const float qvz = std::fmaf(tvx, t.edge1.y, -(tvy * t.edge1.x));
-					const float v = dot3(dx, dy, dz, qvx, qvy, qvz) * inv_det;
-					if (v < 0.0f || u + v > 1.0f) continue;
-					const float tt = dot3(t.edge2.x, t.edge2.y, t.edge2.z, qvx, qvy, qvz) * inv_det;
-					// glsl:124 accepts t_min <= t < best_t; an exact tie goes to the lower triangle id
-					if (!(tt < ray.t_min) && (tt < best_t || (tt == best_t && best_tri != UINT32_MAX && t.id < best_id))) {
+					float tt, u, v;
+					if (tri_hit(o, d, t.v0, t.edge1, t.edge2, tt, u, v) && closer_hit(tt, t.id, ray.t_min, best_t, best_tri, best_id)) {
 						best_t = tt; best_u = u; best_v = v; best_tri = ti; best_id = t.id;
 						if (any_hit) goto done;
 					}
@@ -188,8 +171,8 @@ public:
 			if (stats) stats->bvh_nodes_visited++;
 			const uint32_t l = n.left_first, r = l + 1u;
 			float tl, tr;
-			const bool hl = slab(nodes_[l], ix, iy, iz, nrx, nry, nrz, ray.t_min, best_t, tl);
-			const bool hr = slab(nodes_[r], ix, iy, iz, nrx, nry, nrz, ray.t_min, best_t, tr);
+			const bool hl = slab(nodes_[l], inv, ray.t_min, best_t, tl);
+			const bool hr = slab(nodes_[r], inv, ray.t_min, best_t, tr);
 			if (hl && hr) { // near child first, far child pushed (glsl:290-305)
 				const bool left_near = tl < tr;
 				if (sp < 128) stack[sp++] = left_near ? r : l;
@@ -202,7 +185,7 @@ public:
 		if (best_tri != UINT32_MAX) { // packed -> Intersection, gpu_ray_caster.cpp:442-456
 			const Triangle &t = tris_[best_tri];
 			out.t = best_t;
-			out.position = Vector3(ox + dx * best_t, oy + dy * best_t, oz + dz * best_t);
+			out.position = Vector3(o.x + d.x * best_t, o.y + d.y * best_t, o.z + d.z * best_t);
 			out.normal = t.normal; out.u = best_u; out.v = best_v; out.prim_id = t.id; out.hit_layers = t.layers;
 			if (stats) stats->hits++;
 		}
@@ -212,21 +195,9 @@ public:
 private:
 	const Triangle *tris_; const mrt_bvh_node32 *nodes_; const uint32_t *prim_idx_; uint32_t n_tris_;
 
-	static float safe_inv(float d) // safe_inv_direction, glsl:137-145 == Ray::_precompute, src/core/ray.h:78-89
+	static bool slab(const mrt_bvh_node32 &b, const RayInv &inv, float t_min, float best_t, float &tnear)
 	{
-		const float eps = 1e-9f, big = 1.0f / eps;
-		return std::fabs(d) > eps ? 1.0f / d : (d >= 0.0f ? big : -big);
-	}
-	static float dot3(float ax, float ay, float az, float bx, float by, float bz) { return std::fmaf(ax, bx, std::fmaf(ay, by, az * bz)); }
-	// ray_aabb, glsl:84-99, clamped to [t_min, best_t]
-	static bool slab(const mrt_bvh_node32 &b, float ix, float iy, float iz, float nrx, float nry, float nrz, float t_min, float best_t, float &tnear)
-	{
-		const float x0 = std::fmaf(b.aabb_min[0], ix, nrx), x1 = std::fmaf(b.aabb_max[0], ix, nrx);
-		const float y0 = std::fmaf(b.aabb_min[1], iy, nry), y1 = std::fmaf(b.aabb_max[1], iy, nry);
-		const float z0 = std::fmaf(b.aabb_min[2], iz, nrz), z1 = std::fmaf(b.aabb_max[2], iz, nrz);
-		tnear = std::fmax(std::fmax(std::fmin(x0, x1), std::fmin(y0, y1)), std::fmax(std::fmin(z0, z1), t_min));
-		const float tfar = std::fmin(std::fmin(std::fmax(x0, x1), std::fmax(y0, y1)), std::fmin(std::fmax(z0, z1), best_t));
-		return tnear <= tfar;
+		return slab_box(V3{ b.aabb_min[0], b.aabb_min[1], b.aabb_min[2] }, V3{ b.aabb_max[0], b.aabb_max[1], b.aabb_max[2] }, inv, t_min, best_t, tnear);
 	}
 };
 
@@ -248,10 +219,9 @@ public:
 		if (stats) stats->rays_cast++;
 		if (a_.n_instances == 0 || ray.t_min >= ray.t_max) return out;
 		constexpr uint32_t kEnd = 0x7FFFFFFFu, kBack = 0x7FFFFFFEu, kLeaf = 0x80000000u; // sentinel, "back to the world ray", leaf flag
-		const float wox = ray.origin.x, woy = ray.origin.y, woz = ray.origin.z, wdx = ray.direction.x, wdy = ray.direction.y, wdz = ray.direction.z;
-		float ox = wox, oy = woy, oz = woz, dx = wdx, dy = wdy, dz = wdz;          // the ray being walked
-		float ix = safe_inv(dx), iy = safe_inv(dy), iz = safe_inv(dz);
-		float nrx = -(ox * ix), nry = -(oy * iy), nrz = -(oz * iz);
+		const V3 wo = { ray.origin.x, ray.origin.y, ray.origin.z }, wd = { ray.direction.x, ray.direction.y, ray.direction.z }; // the world ray
+		V3 o = wo, d = wd;          // the ray being walked
+		RayInv inv = ray_inverse(o, d);
 		float best_t = ray.t_max, best_u = 0.0f, best_v = 0.0f;
 		uint32_t best_slot = UINT32_MAX, best_id = UINT32_MAX, best_inst = 0u;
 		std::vector<uint32_t> stack(a_.depth + 8u);
@@ -263,9 +233,8 @@ public:
 			if (cur < kBack) { // an inner node of the TLAS or of a BLAS
 				if (stats) stats->bvh_nodes_visited++;
 				const mrt_bvh_node_wide64 &n = a_.nodes[cur];
-				float tl, tr;
-				const bool hl = slab(n.left_min, n.left_max, ix, iy, iz, nrx, nry, nrz, ray.t_min, best_t, tl);
-				const bool hr = slab(n.right_min, n.right_max, ix, iy, iz, nrx, nry, nrz, ray.t_min, best_t, tr);
+				bool hl, hr; float tl, tr;
+				slab_pair(box3(n.left_min), box3(n.left_max), box3(n.right_min), box3(n.right_max), inv, ray.t_min, best_t, hl, tl, hr, tr);
 				if (hl && hr) {
 					const bool left_near = tl < tr;
 					cur = left_near ? n.left_idx : n.right_idx;
@@ -276,9 +245,8 @@ public:
 				continue;
 			}
 			if (cur == kBack) { // the BLAS is done: back to the world ray
-				ox = wox; oy = woy; oz = woz; dx = wdx; dy = wdy; dz = wdz;
-				ix = safe_inv(dx); iy = safe_inv(dy); iz = safe_inv(dz);
-				nrx = -(ox * ix); nry = -(oy * iy); nrz = -(oz * iz);
+				o = wo; d = wd;
+				inv = ray_inverse(o, d);
 				in_blas = false;
 				cur = stack[--sp];
 				continue;
@@ -291,14 +259,8 @@ public:
 				std::memcpy(&flags, row + 24, sizeof(flags));
 				if ((flags & 1u) == 0u && sp < stack.size()) stack[sp++] = kLeaf | (slot0 + 1u); // the rest of the leaf
 				if ((meta[3] & query_mask) != 0u) {
-					ox = std::fmaf(row[0], wox, std::fmaf(row[1], woy, std::fmaf(row[2], woz, row[3])));
-					oy = std::fmaf(row[4], wox, std::fmaf(row[5], woy, std::fmaf(row[6], woz, row[7])));
-					oz = std::fmaf(row[8], wox, std::fmaf(row[9], woy, std::fmaf(row[10], woz, row[11])));
-					dx = std::fmaf(row[0], wdx, std::fmaf(row[1], wdy, row[2] * wdz));
-					dy = std::fmaf(row[4], wdx, std::fmaf(row[5], wdy, row[6] * wdz));
-					dz = std::fmaf(row[8], wdx, std::fmaf(row[9], wdy, row[10] * wdz));
-					ix = safe_inv(dx); iy = safe_inv(dy); iz = safe_inv(dz);
-					nrx = -(ox * ix); nry = -(oy * iy); nrz = -(oz * iz);
+					to_instance_space(V4{ row[0], row[1], row[2], row[3] }, V4{ row[4], row[5], row[6], row[7] }, V4{ row[8], row[9], row[10], row[11] }, wo, wd, o, d);
+					inv = ray_inverse(o, d);
 					if (sp < stack.size()) stack[sp++] = kBack;
 					in_blas = true; cur_inst = slot0; id_base = meta[2];
 					cur = meta[1];
@@ -314,28 +276,11 @@ public:
 				std::memcpy(&local_id, q + 3, 4); std::memcpy(&tflags, q + 11, 4);
 				last = (tflags & 1u) != 0u;
 				if (stats) stats->tri_tests++;
-				const float pvx = std::fmaf(dy, q[10], -(dz * q[9]));
-				const float pvy = std::fmaf(dz, q[8], -(dx * q[10]));
-				const float pvz = std::fmaf(dx, q[9], -(dy * q[8]));
-				const float det = dot3(q[4], q[5], q[6], pvx, pvy, pvz);
-				if (!(std::fabs(det) < 1e-8f)) {
-					const float inv_det = 1.0f / det;
-					const float tvx = ox - q[0], tvy = oy - q[1], tvz = oz - q[2];
-					const float u = dot3(tvx, tvy, tvz, pvx, pvy, pvz) * inv_det;
-					if (!(u < 0.0f || u > 1.0f)) {
-						const float qvx = std::fmaf(tvy, q[6], -(tvz * q[5]));
-						const float qvy = std::fmaf(tvz, q[4], -(tvx * q[6]));
-						const float qvz = std::fmaf(tvx, q[5], -(tvy * q[4]));
-						const float v = dot3(dx, dy, dz, qvx, qvy, qvz) * inv_det;
-						if (!(v < 0.0f || u + v > 1.0f)) {
-							const float t = dot3(q[8], q[9], q[10], qvx, qvy, qvz) * inv_det;
-							const uint32_t id = id_base + local_id;
-							if (!(t < ray.t_min) && (t < best_t || (t == best_t && best_slot != UINT32_MAX && id < best_id))) {
-								best_t = t; best_u = u; best_v = v; best_slot = slot; best_id = id; best_inst = cur_inst;
-								if (any_hit) last = true;
-							}
-						}
-					}
+				float t, u, v;
+				const uint32_t id = id_base + local_id;
+				if (tri_hit(o, d, V3{ q[0], q[1], q[2] }, V3{ q[4], q[5], q[6] }, V3{ q[8], q[9], q[10] }, t, u, v) && closer_hit(t, id, ray.t_min, best_t, best_slot, best_id)) {
+					best_t = t; best_u = u; best_v = v; best_slot = slot; best_id = id; best_inst = cur_inst;
+					if (any_hit) last = true;
 				}
 				slot++;
 			} while (!last);
@@ -353,7 +298,7 @@ public:
 			if (l2 == 0.0f) { nx = ny = nz = 0.0f; }
 			else { const float l = std::sqrt(l2); nx /= l; ny /= l; nz /= l; }
 			out.t = best_t;
-			out.position = Vector3(wox + wdx * best_t, woy + wdy * best_t, woz + wdz * best_t);
+			out.position = Vector3(wo.x + wd.x * best_t, wo.y + wd.y * best_t, wo.z + wd.z * best_t);
 			out.normal = Vector3(nx, ny, nz); out.u = best_u; out.v = best_v; out.prim_id = best_id; out.hit_layers = layers;
 			if (stats) stats->hits++;
 		}
@@ -362,21 +307,7 @@ public:
 
 private:
 	mrt_two_level_arrays a_;
-	static float safe_inv(float d)
-	{
-		const float eps = 1e-9f, big = 1.0f / eps;
-		return std::fabs(d) > eps ? 1.0f / d : (d >= 0.0f ? big : -big);
-	}
-	static float dot3(float ax, float ay, float az, float bx, float by, float bz) { return std::fmaf(ax, bx, std::fmaf(ay, by, az * bz)); }
-	static bool slab(const float mn[3], const float mx[3], float ix, float iy, float iz, float nrx, float nry, float nrz, float t_min, float best_t, float &tnear)
-	{
-		const float x0 = std::fmaf(mn[0], ix, nrx), x1 = std::fmaf(mx[0], ix, nrx);
-		const float y0 = std::fmaf(mn[1], iy, nry), y1 = std::fmaf(mx[1], iy, nry);
-		const float z0 = std::fmaf(mn[2], iz, nrz), z1 = std::fmaf(mx[2], iz, nrz);
-		tnear = std::fmax(std::fmax(std::fmin(x0, x1), std::fmin(y0, y1)), std::fmax(std::fmin(z0, z1), t_min));
-		const float tfar = std::fmin(std::fmin(std::fmax(x0, x1), std::fmax(y0, y1)), std::fmin(std::fmax(z0, z1), best_t));
-		return tnear <= tfar;
-	}
+	static V3 box3(const float c[3]) { return { c[0], c[1], c[2] }; }
 };
 
 } // namespace mrt

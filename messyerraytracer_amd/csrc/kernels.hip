@@ -19,6 +19,7 @@
 #include "mrt_internal.h"
 #include "launch_policy.h"
 #include "lane_map.h"
+#include "walk_steps.h"
 #include "gbuffer.h"
 
 namespace mrt {
@@ -34,16 +35,10 @@ namespace mrt {
 #include "bounce_kernel.h"
 #include "gbuffer_kernel.h"
 
-// ---- the traversal kernel: one lane = one ray -------------------------------------
-// LDS: per-lane stack, entry d of lane l at dword d*64 + l of the wave's region
-// (conflict-free: the 64 lanes of a push/pop hit 64 consecutive dwords).
+// ---- the traversal kernel: one lane = one ray (lane_walk.h) -------------------------------------
+#include "lane_walk.h"
 template <bool ANY_HIT, bool COUNT>
-__global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
-{
-	constexpr int SRC = SRC_CAST;
-	const NoSource s{};
-#include "lane_walk.inc" // (in scope: the names its first lines check)
-}
+__global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p) { lane_walk<SRC_CAST, ANY_HIT, COUNT>(p, NoSource{}); }
 
 #include "lane_persistent_kernel.h"
 #include "packet_kernel.h"
@@ -56,24 +51,17 @@ __global__ __launch_bounds__(MRT_WG) void trace_lane_kernel(const TraceParams p)
 
 // ---- record-driven casts (source_common.h): the lane kernels a non-coherent batch can get, with a ray source -------------------
 // S = the source family's parameters (its own kernel argument: ShadowParams and HemiParams are large, and a union of the five would
-// grow every family's argument block), SRC one of its sources, ANY_HIT a mode its source_entry accepts.  The bodies are the
-// ones of trace_lane_kernel, trace_two_level_kernel and trace_lane_persistent_kernel, included with SRC set.
+// grow every family's argument block), SRC one of its sources, ANY_HIT a mode its source_entry accepts.  The walks are the
+// ones of trace_lane_kernel, trace_two_level_kernel and trace_lane_persistent_kernel, called with SRC set.
 template <class S, int SRC, bool ANY_HIT>
-__global__ __launch_bounds__(MRT_WG) void trace_source_lane_kernel(const TraceParams p, const S s)
-{
-	constexpr bool COUNT = false;
-#include "lane_walk.inc" // (in scope: the names its first lines check)
-}
+__global__ __launch_bounds__(MRT_WG) void trace_source_lane_kernel(const TraceParams p, const S s) { lane_walk<SRC, ANY_HIT, false>(p, s); }
 template <class S, int SRC, bool ANY_HIT>
-__global__ __launch_bounds__(MRT_WG) void trace_source_two_level_kernel(const TraceParams p, const S s)
-{
-#include "two_level_walk.inc" // (in scope: the names its first lines check)
-}
+__global__ __launch_bounds__(MRT_WG) void trace_source_two_level_kernel(const TraceParams p, const S s) { two_level_walk<SRC, ANY_HIT>(p, s); }
 template <class S, int SRC, bool ANY_HIT, int WIDTH, bool TL>
 __global__ __launch_bounds__(MRT_WG) MRT_PERSIST_ATTR void trace_source_persistent_kernel(const TraceParams p, const PersistParams q, const S s)
 {
 	constexpr bool COUNT = false;
-#include "persistent_walk.inc" // (in scope: the names its first lines check)
+#include "persistent_walk.inc" // (in scope: the names its first lines check; kept as a textual body: DESIGN.md 4.2a)
 }
 
 // ---- launch wrappers (called from api.hip / cast.hip) -------------------------------------------

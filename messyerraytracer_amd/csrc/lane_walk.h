@@ -1,11 +1,16 @@
-// lane_walk.inc -- the body of trace_lane_kernel and trace_source_lane_kernel (kernels.hip), included inside each: the kernel that
-// existed before the ray sources keeps the very code it had (a walk inlined from a function compiles differently).  In scope: p
-// (TraceParams), s (the parameters of the kernel's source family, source_common.h; NoSource in a SRC_CAST kernel), ANY_HIT, COUNT, SRC
-// (SRC_CAST: the batch's rays, load_ray; else the family's source_entry makes the ray of an entry or stores its result).
-	// the contract with the including kernel, checked here rather than deep in the walk
-	static_assert(std::is_same<decltype(p), const TraceParams>::value && (SRC == SRC_CAST) == std::is_same<decltype(s), const NoSource>::value,
-			"lane_walk.inc: p (const TraceParams) and s (the source family's parameters; const NoSource for SRC_CAST) in scope");
-	static_assert(SRC == SRC_CAST || !COUNT, "lane_walk.inc: no ray source counts (source_entry checks the family's modes)");
+// lane_walk.h -- the walk of trace_lane_kernel and trace_source_lane_kernel (kernels.hip): one lane = one ray, a per-lane stack in LDS
+// (entry d of lane l at dword d*64 + l of the wave's region: the 64 lanes of a push or a pop hit 64 consecutive dwords).  Included by
+// kernels.hip inside namespace mrt, after source_common.h.  The arithmetic is the canonical form, written out here: called from
+// walk_steps.h the same steps measured 1 to 4 % slower.
+// p = the cast, s = the parameters of the kernel's source family (source_common.h; NoSource in a SRC_CAST kernel).  SRC_CAST: the
+// batch's rays (load_ray); else the family's source_entry makes the ray of an entry or stores its result.
+#pragma once
+
+template <int SRC, bool ANY_HIT, bool COUNT, class S>
+__device__ __forceinline__ void lane_walk(const TraceParams &p, const S &s)
+{
+	static_assert((SRC == SRC_CAST) == std::is_same<S, NoSource>::value, "lane_walk: s is NoSource exactly for SRC_CAST");
+	static_assert(SRC == SRC_CAST || !COUNT, "lane_walk: no ray source counts (source_entry checks the family's modes)");
 	extern __shared__ uint32_t lds_stack[];
 	if (skip_launch(p)) return;
 	uint32_t block = blockIdx.x;
@@ -121,3 +126,4 @@
 		atomicAdd(&p.counters[kCntWaveNodeFetch], (unsigned long long)n_nodes);
 		atomicAdd(&p.counters[kCntWaveTriFetch], (unsigned long long)n_tris);
 	}
+}

@@ -1,5 +1,5 @@
 // persistent_walk.inc -- the body of trace_lane_persistent_kernel (lane_persistent_kernel.h) and trace_source_persistent_kernel
-// (kernels.hip), included inside each (see lane_walk.inc).  In scope: p, q, s, ANY_HIT, WIDTH, TL, COUNT, SRC (a ray source: an entry
+// (kernels.hip), included inside each.  In scope: p, q, s, ANY_HIT, WIDTH, TL, COUNT, SRC (a ray source: an entry
 // without a ray writes its result when it is handed out, and the lane takes the next entry at once).
 	// the contract with the including kernel, checked here rather than deep in the walk
 	static_assert(std::is_same<decltype(p), const TraceParams>::value && std::is_same<decltype(q), const PersistParams>::value &&

@@ -7,6 +7,7 @@
 #include <type_traits>
 #include "mrt_internal.h"
 #include "lane_map.h"
+#include "walk_steps.h"
 
 namespace mrt {
 
@@ -102,7 +103,7 @@ hipError_t launch_grid_rays(const TraceParams &p, mrt_ray32 *out, hipStream_t st
 // ---- hit tokens -> full hit records (mrt_expand_tokens) -----------------------------------
 // A token names the winning triangle of a ray (leaf-order slot, 0xFFFFFFFF = miss).  Everything
 // else in the record is a function of (ray, triangle): t, u, v come out of one Moller-Trumbore
-// evaluation written exactly as in the traversal kernels, so the rebuilt record is the record
+// evaluation, the walks' form without its rejections (walk_steps.h tri_tuv), so the rebuilt record is the record
 // the trace would have stored, bit for bit.  This is what lets a multi-GPU gather move 4 bytes
 // per ray over xGMI instead of 32 (sharded.py): the root rebuilds the records from its own copy
 // of the scene and the sender's camera.
@@ -121,26 +122,16 @@ __global__ __launch_bounds__(MRT_WG) void expand_tokens_kernel(const TraceParams
 	}
 	const float4 *t3 = reinterpret_cast<const float4 *>(p.tri_hot) + (size_t)slot * 3u;
 	const float4 q0 = t3[0], q1 = t3[1], q2 = t3[2];
-	const float pvx = fma_(r.dy, q2.z, -(r.dz * q2.y));
-	const float pvy = fma_(r.dz, q2.x, -(r.dx * q2.z));
-	const float pvz = fma_(r.dx, q2.y, -(r.dy * q2.x));
-	const float det = dot3(q1.x, q1.y, q1.z, pvx, pvy, pvz);
-	const float inv_det = 1.0f / det;
-	const float tvx = r.ox - q0.x, tvy = r.oy - q0.y, tvz = r.oz - q0.z;
-	const float u = dot3(tvx, tvy, tvz, pvx, pvy, pvz) * inv_det;
-	const float qvx = fma_(tvy, q1.z, -(tvz * q1.y));
-	const float qvy = fma_(tvz, q1.x, -(tvx * q1.z));
-	const float qvz = fma_(tvx, q1.y, -(tvy * q1.x));
-	const float v = dot3(r.dx, r.dy, r.dz, qvx, qvy, qvz) * inv_det;
-	const float t = dot3(q2.x, q2.y, q2.z, qvx, qvy, qvz) * inv_det;
+	float t, u, v;
+	tri_tuv(r.o(), r.d(), q0, q1, q2, t, u, v);
 	const float4 nn = reinterpret_cast<const float4 *>(p.tri_cold)[slot];
 	store_hit(p, g, r, t, (int32_t)__float_as_uint(q0.w), u, v, nn.x, nn.y, nn.z, __float_as_uint(q1.w), slot);
 }
 
 // The same for a two-level scene: a token is {triangle slot in the mesh arrays, DevInstance row}.  The ray goes to the
-// instance's mesh space with the kernels' own sequence (trace_two_level_kernel: o' = M o + t, d' = M d, every fused
-// operation an explicit fma), Moller-Trumbore runs there, and finish_two_level_ray writes the record: flat id = the
-// instance's id base + the mesh-local id, the instance's layer mask, normalize(basis * n), position on the world ray.
+// instance's mesh space as in the walks (walk_steps.h to_instance_space), Moller-Trumbore runs there, and
+// finish_two_level_ray writes the record: flat id = the instance's id base + the mesh-local id, the instance's layer mask,
+// normalize(basis * n), position on the world ray.
 __global__ __launch_bounds__(MRT_WG) void expand_two_level_tokens_kernel(const TraceParams p, const uint2 *tokens)
 {
 	const uint64_t g = (uint64_t)blockIdx.x * MRT_WG + threadIdx.x;
@@ -157,26 +148,12 @@ __global__ __launch_bounds__(MRT_WG) void expand_two_level_tokens_kernel(const T
 	}
 	const float4 *row = reinterpret_cast<const float4 *>(p.instances) + (size_t)inst * 8u;
 	const float4 m0 = row[0], m1 = row[1], m2 = row[2], meta = row[5];
-	const float ox = fma_(m0.x, r.ox, fma_(m0.y, r.oy, fma_(m0.z, r.oz, m0.w)));
-	const float oy = fma_(m1.x, r.ox, fma_(m1.y, r.oy, fma_(m1.z, r.oz, m1.w)));
-	const float oz = fma_(m2.x, r.ox, fma_(m2.y, r.oy, fma_(m2.z, r.oz, m2.w)));
-	const float dx = fma_(m0.x, r.dx, fma_(m0.y, r.dy, m0.z * r.dz));
-	const float dy = fma_(m1.x, r.dx, fma_(m1.y, r.dy, m1.z * r.dz));
-	const float dz = fma_(m2.x, r.dx, fma_(m2.y, r.dy, m2.z * r.dz));
+	V3 o, d;
+	to_instance_space(m0, m1, m2, r.o(), r.d(), o, d);
 	const float4 *t3 = reinterpret_cast<const float4 *>(p.tri_hot) + (size_t)slot * 3u;
 	const float4 q0 = t3[0], q1 = t3[1], q2 = t3[2];
-	const float pvx = fma_(dy, q2.z, -(dz * q2.y));
-	const float pvy = fma_(dz, q2.x, -(dx * q2.z));
-	const float pvz = fma_(dx, q2.y, -(dy * q2.x));
-	const float det = dot3(q1.x, q1.y, q1.z, pvx, pvy, pvz);
-	const float inv_det = 1.0f / det;
-	const float tvx = ox - q0.x, tvy = oy - q0.y, tvz = oz - q0.z;
-	const float u = dot3(tvx, tvy, tvz, pvx, pvy, pvz) * inv_det;
-	const float qvx = fma_(tvy, q1.z, -(tvz * q1.y));
-	const float qvy = fma_(tvz, q1.x, -(tvx * q1.z));
-	const float qvz = fma_(tvx, q1.y, -(tvy * q1.x));
-	const float v = dot3(dx, dy, dz, qvx, qvy, qvz) * inv_det;
-	const float t = dot3(q2.x, q2.y, q2.z, qvx, qvy, qvz) * inv_det;
+	float t, u, v;
+	tri_tuv(o, d, q0, q1, q2, t, u, v);
 	finish_two_level_ray(p, g, r, t, u, v, slot, __float_as_uint(meta.z) + __float_as_uint(q0.w), inst);
 }
 

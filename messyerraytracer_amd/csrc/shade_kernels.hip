@@ -18,6 +18,7 @@
 #include "svgf.h"
 #include "gbuffer.h"
 #include "lane_map.h"
+#include "walk_steps.h"
 
 namespace mrt {
 

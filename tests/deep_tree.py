@@ -141,7 +141,7 @@ SENT = 0x7FFFFFFF   # the sentinel ref; refs below it are inner nodes, refs abov
 
 
 def _inv(d):
-    """safe_inv (device_common.h): 1 / d, or +-1e9 for a component within 1e-9 of zero"""
+    """safe_inv (csrc/walk_steps.h): 1 / d, or +-1e9 for a component within 1e-9 of zero"""
     d = np.asarray(d, dtype=np.float32)
     big = np.float32(1.0) / np.float32(1e-9)
     with np.errstate(divide="ignore"):
@@ -165,7 +165,7 @@ def children8(nodes8, decode8):
 
 
 def high_water(children, ray, slot_t, sentinel=1, query_mask=0xFFFFFFFF):
-    """The push rule of the walks over one ray (lane_walk.inc:54-63 two-wide; persistent_walk.inc four- and eight-wide): of the
+    """The push rule of the walks over one ray (two-wide: lane_walk.h, two_level_kernel.h and persistent_walk.inc of csrc; four- and eight-wide: persistent_walk.inc): of the
     children whose box the ray's interval [t_min, best_t] meets, the nearest is entered and the others are pushed, farthest first; a
     leaf is tested (slot_t(slot, ray, query_mask) -> (t or None, last in leaf), best_t shrinks) and the next entry popped.  Returns the
     most entries the stack held: `sentinel` = 1 counts the bottom entry the plain kernels keep, 0 the persistent ones' empty bottom.

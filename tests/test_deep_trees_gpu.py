@@ -199,7 +199,7 @@ def test_every_form_walks_the_chain_to_its_bottom(built, poison, form, n, overri
 
 # ---- counting builds: the high-water mark itself -----------------------------------------------------------------------------------
 def records_high_water(variant):
-    """the instantiations that write kCntMaxStack: the plain lane kernel (lane_walk.inc) and the row walks (packet_rows_kernel.h);
+    """the instantiations that write kCntMaxStack: the plain lane kernel (lane_walk.h) and the row walks (packet_rows_kernel.h);
     the C++ packet kernel, the 64-ray asm walk and the persistent kernels keep no such mark"""
     return variant.startswith("trace_lane_kernel<") or variant.startswith("trace_packet_rows_kernel<")
 
