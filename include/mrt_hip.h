@@ -276,7 +276,8 @@ uint32_t mrt_version(void);
  * their own declarations against: 0 mrt_options, 1 mrt_camera, 2 mrt_stats, 3 mrt_instance, 4 mrt_light, 6 mrt_material,
  * 7 mrt_shade_data, 8 mrt_surface64, 9 mrt_surface_out, 11 mrt_shade_light, 12 mrt_environment, 13 mrt_light_out,
  * 15 mrt_path_state, 16 mrt_path_step_desc, 18 mrt_texture, 19 mrt_material_textures, 20 mrt_texture_set, 22 mrt_panorama,
- * 24 mrt_channel_out, 26 mrt_accum_state, 28 mrt_denoise_params, 30 mrt_gbuffer, 32 mrt_svgf_params (0 for anything else). */
+ * 24 mrt_channel_out, 26 mrt_accum_state, 28 mrt_denoise_params, 30 mrt_gbuffer, 32 mrt_svgf_params, 34 mrt_light_select,
+ * 36 mrt_emitter_select, 38 mrt_emitter64 (0 for anything else). */
 uint32_t mrt_struct_size(uint32_t which);
 /* Launch on this HIP stream (hipStream_t as void*; 0 = the context's own stream): from here on it is "the context's stream".
  * What a caller that shares its stream may rely on (tests/test_caller_stream_gpu.py holds every entry point to it):
@@ -1138,6 +1139,124 @@ int mrt_light_selected_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_
 int mrt_light_grid_selected_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
 		const void *d_hits, const mrt_surface64 *d_rows, const mrt_shade_light *lights, uint32_t n_lights, const uint8_t *d_light,
 		const uint8_t *d_mask, const mrt_environment *env, const mrt_light_out *out, uint32_t flags);
+
+/* ---- emissive triangles as light sources: a resident emitter table, one shadow ray per record to a sampled point of a sampled
+ * emitter, that point's diffuse term, and a path step that does not count the same emission twice.
+ * mrt_path_step adds t * emission where a bounce ray happens to hit an emissive triangle and nothing samples those triangles: the
+ * chance that a cosine-distributed ray finds a lamp is the lamp's projected solid angle over pi.  The bounce splits the BRDF integral
+ * into a diffuse lobe (drawn with probability 1 - sp, weighted diff.c / (1 - sp): it estimates the integral of (diff / pi) *
+ * max(n . w, 0) * L dw) and a specular lobe.  Emitter sampling takes over the diffuse lobe's share of the emitted light and only that,
+ * so no pdf is carried between calls: mrt_light_emitter_surfaces adds the diffuse term of one sampled emitter point, and
+ * mrt_path_step_emitters drops t * emission on a hit that a diffuse-lobe ray reached (that light was counted at the previous vertex)
+ * and keeps it at bounce 0 and after a specular-lobe ray.  The loop estimates, without bias, the integral the loop over mrt_path_step
+ * converges to.  Multiple importance sampling of rough specular lobes is not done; mrt_path_state.reserved is the place for a pdf.
+ * Per bounce a renderer queues
+ *   cast -> resolve -> (selected shadows -> selected light, with analytic lights) -> emitter shadows -> emitter light with
+ *   MRT_EMITTER_ACCUMULATE into the same d_direct -> mrt_path_step_emitters with d_prev_lobe = the lobe bytes of the step before ->
+ *   bounce cast.
+ * At bounce == max_bounces the emitter shadows and the emitter light are left out (d_direct holds the analytic lights' term alone, or
+ * zeros): the light that sample stands for is the emission a bounce ray would find at bounce max_bounces + 1, which neither loop
+ * reaches, and with it the loop would estimate one more bounce of emitted light than mrt_path_step's does.
+ *
+ * The table.  tris: the world-space triangles the scene came from, n_tris of them (host array; device array with
+ * MRT_BUILD_TRIS_ON_DEVICE; for instanced and two-level scenes the output of mrt_flatten_instances).  The material of a triangle is
+ * material_ids[tri.id] of the resident shade data (mrt_upload_shade_data).  The table is the context's, as the shade data is: it
+ * survives scene uploads, is stale once geometry or materials move, and the caller rebuilds it.  Built on the device.  Per triangle,
+ * plain fp32, one operation at a time:
+ *   Le.c = emission.c * emission_energy if material ids are resident, tri.id < the shade data's n_tris, the id < n_materials and
+ *     emission_energy > 0 (the resolve's rule); otherwise 0
+ *   c = edge1 x edge2: c.x = e1.y*e2.z - e1.z*e2.y, c.y = e1.z*e2.x - e1.x*e2.z, c.z = e1.x*e2.y - e1.y*e2.x;
+ *   area = 0.5f * sqrt((c.x*c.x + c.y*c.y) + c.z*c.z)
+ *   w = area * ((0.2126f*Le.r + 0.7152f*Le.g) + 0.0722f*Le.b); the triangle is an emitter iff w is finite and > 0.
+ * The emitters keep their input order.  Their weights are integers, so that the table does not depend on the order of any sum:
+ *   w_max = the largest w; Q = 2^(31 - ceil_log2(n_emit)); q0 = max(1, (uint32)((w / w_max) * (float)Q)); T0 = the sum of q0 (exact,
+ *   uint64); q = (uint64(q0) << 31) / T0 >= 1; total = the sum of q, in (2^31 - n_emit, 2^31].
+ * Row k (64 bytes, mrt_emitter64) = {v0, q | edge1, tri.id | edge2, area | Le, material id}; cdf[k] = q_0 + ... + q_k (uint32).
+ * Selection from a 32-bit word: target = word >> 1; target >= total: no emitter (probability below 2^-11; the record contributes 0);
+ * otherwise k = the first entry with cdf[k] > target, so that the probability of k is exactly q_k / 2^31. */
+#define MRT_MAX_EMITTERS (1u << 20)
+#define MRT_EMITTER_NONE 0xFFFFFFFFu                      /* the emitter word of a record without an emitter */
+/* The first of the three draws of a pixel's stream that bounce b's emitter sample takes: clear of the bounce's draws (<= 129) and of
+ * the light-selecting draws (256 .. 288). */
+#define MRT_PATH_EMITTER_DRAW(bounce) (512u + 4u * (bounce))
+typedef struct mrt_emitter64 {
+	float v0[3];    uint32_t q;
+	float edge1[3]; uint32_t prim_id;
+	float edge2[3]; float area;
+	float radiance[3]; uint32_t material;
+} mrt_emitter64;
+/* Builds the table and replaces the resident one.  Blocks until done.  flags: 0 or MRT_BUILD_TRIS_ON_DEVICE.  n_tris == 0, no shade
+ * data resident or no emissive triangle: the table has 0 emitters (MRT_OK).  MRT_ERR_INVALID for a null context, null tris with n_tris >
+ * 0 or an unknown flag; MRT_ERR_PENDING while a dispatch is pending; MRT_ERR_UNSUPPORTED for more than MRT_MAX_EMITTERS emitters: the
+ * resident table is then unchanged. */
+int mrt_build_emitters(mrt_ctx *ctx, const mrt_tri64 *tris, uint32_t n_tris, uint32_t flags);
+/* Drops the table: 0 emitters. */
+int mrt_clear_emitters(mrt_ctx *ctx);
+/* The number of emitters and the sum of their q.  Either pointer may be null. */
+int mrt_emitter_info(const mrt_ctx *ctx, uint32_t *n_emitters, uint32_t *total);
+/* Debug download of the resident table (the tests): up to `capacity` rows and cdf words to host memory; either pointer may be null. */
+int mrt_emitter_table(mrt_ctx *ctx, mrt_emitter64 *rows, uint32_t *cdf, uint32_t capacity);
+
+typedef struct mrt_emitter_select {                       /* 24 bytes */
+	uint32_t frame;            /* enters the seed, as mrt_bounce.frame; <= MRT_PATH_MAX_FRAME                         */
+	uint32_t draw;             /* the first of the three draws: MRT_PATH_EMITTER_DRAW(bounce)                         */
+	const uint8_t *d_select;   /* optional device pointer, one byte per record: 0 = the record samples no emitter     */
+	uint32_t *d_out_emitter;   /* device pointer, one word per record: the emitter sampled, or MRT_EMITTER_NONE       */
+} mrt_emitter_select;
+/* One shadow ray per record, to a point of the emitter the record samples.  d_rays, d_hits, query_mask as for mrt_cast_bounce (the
+ * incoming rays are read: the normal is faced); d_mask one byte per record.  Per record i, plain fp32 in this order:
+ *   a miss, d_select given and d_select[i] == 0, or an empty table: d_out_emitter[i] = MRT_EMITTER_NONE, d_mask[i] = 1, no ray.
+ *   The stream is mrt_cast_bounce's (seed = pixel_index * 1009 + frame * 6529 + 7; array form: the record's index; grid form:
+ *     y * grid_w + x of the whole grid, so a row band draws what the whole frame draws).  The output word of draw `draw` selects k as
+ *     above (no emitter: as a miss); d_out_emitter[i] = k.  u1, u2 = the floats of draws draw + 1 and draw + 2.
+ *   su = sqrt(u1), a = su * (1 - u2), b = su * u2, y = (v0 + edge1 * a) + edge2 * b per component (row k).
+ *   p, d of the record as mrt_cast_bounce takes them; n = the record's normal, n = -n if ((n.x*d.x + n.y*d.y) + n.z*d.z) > 0.
+ *   org = p + n * 1e-3, to = y - org, dist2 = (to.x*to.x + to.y*to.y) + to.z*to.z, dist = sqrt(dist2), dir = to / dist per component.
+ *   ng = normalized(edge1 x edge2) (the cross product as above; normalized() as for the lighting calls).
+ *   No ray and d_mask[i] = 1 when dist < 1e-6f, or ndl = (n.x*dir.x + n.y*dir.y) + n.z*dir.z <= 0, or cy = |(ng.x*dir.x + ng.y*dir.y)
+ *     + ng.z*dir.z| < 1e-6f, asked in this order.
+ *   Otherwise the ray {org, dir, t_min = 0, t_max = dist * 0.999f} (the emitter does not shadow itself) and d_mask[i] = 1 - occluded
+ *     (any-hit under query_mask).
+ * desc is a host pointer, the rest device pointers.  The CDF is searched in device memory: up to 20 dependent loads per record.
+ * Flags: MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC.  count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID, before any device work and in
+ * this order, for: a null required pointer (rays, hits, desc, mask, d_out_emitter); an unknown flag; frame > MRT_PATH_MAX_FRAME.  Then
+ * MRT_ERR_NO_SCENE, then MRT_ERR_PENDING while a dispatch is pending.  Flat and two-level scenes. */
+int mrt_cast_emitter_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const mrt_emitter_select *desc,
+		uint8_t *d_mask, uint32_t query_mask, uint32_t flags);
+/* The same for rows [y0,y1) of a camera grid cast by mrt_cast_grid (d_hits as it wrote them, mrt_hit32; the per-record arrays indexed
+ * by the record within the band): the primary rays are regenerated in the kernel.  count = grid_w * (y1 - y0).  Flags: MRT_FLAG_ASYNC. */
+int mrt_cast_grid_emitter_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const mrt_hit32 *d_hits, const mrt_emitter_select *desc, uint8_t *d_mask, uint32_t query_mask, uint32_t flags);
+
+#define MRT_EMITTER_ACCUMULATE 1u
+/* The diffuse term of the emitter point every record sampled.  d_rays, d_hits, d_rows, out as for mrt_light_selected_surfaces; desc
+ * as given to mrt_cast_emitter_shadows for the same records (d_select is not read, d_out_emitter is: the cast's words), d_mask
+ * (optional, device; null: lit) what the cast wrote.  The call derives y, dir, dist2, ndl, cy and the three refusals again from the
+ * draws and row d_out_emitter[i], operation for operation as stated there.  For a hit:
+ *   term = 0 where the word is MRT_EMITTER_NONE or >= the table's count, where the cast had no ray, or where d_mask[i] == 0; otherwise
+ *   geom = (ndl * cy) / dist2, wgt = area * (2147483648.0f / (float)q), diff.c = albedo.c * (1 - metallic) from row i,
+ *   term.c = ((diff.c * 0.31830988618f) * Le.c) * (geom * wgt).   There is no clamp: the estimator stays unbiased.
+ *   accumulate == 0: rgba = {0 + term.r, 0 + term.g, 0 + term.b, 1}.  accumulate == MRT_EMITTER_ACCUMULATE: rgb.c = out.c + term.c with
+ *   out as it stands (what mrt_light_selected_surfaces wrote with env == NULL); the fourth float is kept.
+ * A miss writes four zeros, or with MRT_EMITTER_ACCUMULATE keeps what is there.  No environment is taken.  The output is what
+ * mrt_path_step_emitters takes as d_direct.  No scene is required and nothing is walked.  Flags: MRT_FLAG_HOST_LAYOUT, MRT_FLAG_ASYNC.
+ * count == 0: MRT_OK, nothing written.  MRT_ERR_INVALID, in this order, for: a null required pointer (rays, hits, rows, desc,
+ * d_out_emitter, out and its d_rgba); an unknown flag; accumulate > 1; frame > MRT_PATH_MAX_FRAME.  Then MRT_ERR_PENDING. */
+int mrt_light_emitter_surfaces(mrt_ctx *ctx, const void *d_rays, const void *d_hits, const mrt_surface64 *d_rows, uint64_t count,
+		const mrt_emitter_select *desc, const uint8_t *d_mask, uint32_t accumulate, const mrt_light_out *out, uint32_t flags);
+int mrt_light_grid_emitter_surfaces(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const void *d_hits, const mrt_surface64 *d_rows, const mrt_emitter_select *desc, const uint8_t *d_mask, uint32_t accumulate,
+		const mrt_light_out *out, uint32_t flags);
+
+/* mrt_path_step / mrt_path_grid_step with one difference: on a hit with bounce >= 1 the line r.c = r.c + t.c * emission.c runs only
+ * if d_prev_lobe[i] == MRT_LOBE_SPECULAR (at bounce 0 it always runs).  d_prev_lobe: device, one byte per record, the lobe bytes the
+ * step of the bounce before wrote; it may be null only at bounce 0, and it may be the array desc->d_out_lobe points to (each entry is
+ * read before it is written).  Every other line, flag and refusal is mrt_path_step's; a null d_prev_lobe with bounce >= 1 is refused
+ * after them (MRT_ERR_INVALID). */
+int mrt_path_step_emitters(mrt_ctx *ctx, const void *d_rays, const void *d_hits, const mrt_surface64 *d_rows, uint64_t count,
+		const mrt_path_step_desc *desc, const uint8_t *d_prev_lobe, uint32_t flags);
+int mrt_path_grid_step_emitters(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const void *d_hits, const mrt_surface64 *d_rows, const mrt_path_step_desc *desc, const uint8_t *d_prev_lobe, uint32_t flags);
 
 /* ---- resident panorama: the panorama half of ShadePass::EnvironmentData (panorama_data, _width, _height, _energy), the
  * equirectangular RGBAF32 image of a PanoramaSkyMaterial that ray_renderer.cpp:676-703 binds, held on the device, so that the

@@ -14,8 +14,8 @@ OBJ = os.path.join(HERE, "_obj")  # object files, their dependency files and the
 # The library's translation units.  The kernels are three of them: kernels.hip = the walks, shade_kernels.hip = the
 # passes over hit records, prep_kernels.hip = what prepares a scene or a cast; an edit to one is compiled apart from the others.
 SOURCES = ["kernels.hip", "shade_kernels.hip", "prep_kernels.hip", "api.hip", "cast.hip", "schedule.hip", "launch_policy.cpp", "group.hip",
-           "device_build.hip", "refit.hip", "tlas_device.hip", "surface.hip", "texture.hip", "lighting.hip", "path.hip", "panorama.hip", "channels.hip", "accum.hip", "denoise.hip", "svgf.hip",
-           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/accum_data.cpp", "host/denoise_data.cpp", "host/svgf_data.cpp", "host/gbuffer_data.cpp", "host/source_cast_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
+           "device_build.hip", "refit.hip", "tlas_device.hip", "surface.hip", "texture.hip", "lighting.hip", "path.hip", "panorama.hip", "channels.hip", "accum.hip", "denoise.hip", "svgf.hip", "emitters.hip",
+           "host/shade_data.cpp", "host/texture_data.cpp", "host/light_data.cpp", "host/path_data.cpp", "host/panorama_data.cpp", "host/channel_data.cpp", "host/accum_data.cpp", "host/denoise_data.cpp", "host/svgf_data.cpp", "host/gbuffer_data.cpp", "host/source_cast_data.cpp", "host/emitter_data.cpp", "host/scene_prep.cpp", "host/bvh_builder.cpp", "host/two_level_prep.cpp"]
 # -Xarch_host -mfma: explicit fmaf() calls of the host code (the 8-wide collapse verifies every quantised
 # box with the kernel's own fma) become one instruction instead of a libm call; nothing is contracted
 # implicitly (-ffp-contract=off), so every result is unchanged.
@@ -59,10 +59,12 @@ DRIVERS = {
     "svgf_data_test": (["host/svgf_data_test.cpp", "host/svgf_data.cpp"], CPU, False),  # svgf.h, shared with the kernels
     "gbuffer_data_test": (["host/gbuffer_data_test.cpp", "host/gbuffer_data.cpp"], CPU, False),  # gbuffer.h, shared with the kernels
     "source_cast_data_test": (["host/source_cast_data_test.cpp", "host/source_cast_data.cpp"], CPU, False),  # source_cast.h
+    "emitter_data_test": (["host/emitter_data_test.cpp", "host/emitter_data.cpp", "host/path_data.cpp"], CPU, False),  # emitters.h
+    "emitter_policy_test": (["host/emitter_policy_test.cpp", "launch_policy.cpp"], POLICY, False),  # the emitter-shadow entries against the selected-shadow entries
     "lane_map_test": (["host/lane_map_test.cpp"], LANE, False),  # lane_map.h
     "lane_map_fast_test": (["host/lane_map_fast_test.cpp"], LANE, False),  # lane_map.h: the short map of whole-tile pairs
 }
-for _name in ("build_rules_test", "walk_steps_test", "accum_data_test", "denoise_data_test", "svgf_data_test", "gbuffer_data_test", "source_cast_data_test",
+for _name in ("build_rules_test", "walk_steps_test", "accum_data_test", "denoise_data_test", "svgf_data_test", "gbuffer_data_test", "source_cast_data_test", "emitter_data_test",
               "lane_map_test", "lane_map_fast_test"):
     DRIVERS[_name + "_san"] = _twin(DRIVERS[_name])
 

@@ -42,6 +42,8 @@ SYMBOLS = [
     "mrt_cast_gbuffer_reflections", "mrt_reflection_image",
     "mrt_shadow_lights", "mrt_light_surfaces", "mrt_light_grid_surfaces",
     "mrt_cast_selected_shadows", "mrt_cast_grid_selected_shadows", "mrt_light_selected_surfaces", "mrt_light_grid_selected_surfaces",
+    "mrt_build_emitters", "mrt_clear_emitters", "mrt_emitter_info", "mrt_emitter_table", "mrt_cast_emitter_shadows", "mrt_cast_grid_emitter_shadows",
+    "mrt_light_emitter_surfaces", "mrt_light_grid_emitter_surfaces", "mrt_path_step_emitters", "mrt_path_grid_step_emitters",
     "mrt_path_init", "mrt_path_step", "mrt_path_grid_step", "mrt_path_finish", "mrt_expand_tokens",
     "mrt_expand_grid_tokens", "mrt_token_bytes", "mrt_morton_keys",
     "mrt_kernel_name", "mrt_struct_size", "mrt_get_stats", "mrt_last_kernel_variant", "mrt_schedule_counts", "mrt_debug_sort_order", "mrt_kernel_available", "mrt_device_alloc", "mrt_device_free", "mrt_memcpy_h2d", "mrt_memcpy_d2h",
@@ -89,6 +91,14 @@ LOBE_NONE, LOBE_DIFFUSE, LOBE_SPECULAR = 0, 1, 2
 class LightSelect(C.Structure):
     """mrt_light_select (types.LIGHT_SELECT)"""
     _fields_ = [("frame", C.c_uint32), ("select_draw", C.c_uint32), ("d_select", C.c_void_p), ("d_out_light", C.c_void_p)]
+
+
+class EmitterSelect(C.Structure):
+    """mrt_emitter_select (types.EMITTER_SELECT)"""
+    _fields_ = [("frame", C.c_uint32), ("draw", C.c_uint32), ("d_select", C.c_void_p), ("d_out_emitter", C.c_void_p)]
+
+
+EMITTER_ACCUMULATE = 1
 
 
 class ShadeData(C.Structure):
@@ -158,6 +168,7 @@ TEXEL_RGBA8, TEXEL_RGBA32F = 0, 1
 PANORAMA_ON_DEVICE = 1
 PANORAMA_MAX_DIM = 16384
 STRUCT_LIGHT_SELECT = 34   # mrt_struct_size index (33: not a struct)
+STRUCT_EMITTER_SELECT, STRUCT_EMITTER64 = 36, 38   # mrt_struct_size indices (35, 37: not structs)
 STRUCT_SVGF_PARAMS = 32   # mrt_struct_size index (31: not a struct); the struct and the calls: svgf.py
 STRUCT_GBUFFER = 30   # mrt_struct_size index (29: not a struct); the struct and the calls: gbuffer.py
 STRUCT_DENOISE_PARAMS = 28   # mrt_struct_size index (27: not a struct); the struct and the calls: denoise.py
@@ -311,6 +322,22 @@ def load():
     L.mrt_light_grid_selected_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LightOut),
                                                    C.c_uint32]
+    L.mrt_build_emitters.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.mrt_clear_emitters.argtypes = [C.c_void_p]
+    L.mrt_emitter_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.mrt_emitter_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.mrt_cast_emitter_shadows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(EmitterSelect), C.c_void_p, C.c_uint32,
+                                           C.c_uint32]
+    L.mrt_cast_grid_emitter_shadows.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                C.POINTER(EmitterSelect), C.c_void_p, C.c_uint32, C.c_uint32]
+    L.mrt_light_emitter_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(EmitterSelect), C.c_void_p,
+                                             C.c_uint32, C.POINTER(LightOut), C.c_uint32]
+    L.mrt_light_grid_emitter_surfaces.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(EmitterSelect), C.c_void_p, C.c_uint32, C.POINTER(LightOut), C.c_uint32]
+    L.mrt_path_step_emitters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PathStepDesc), C.c_void_p,
+                                         C.c_uint32]
+    L.mrt_path_grid_step_emitters.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.POINTER(PathStepDesc), C.c_void_p, C.c_uint32]
     L.mrt_path_init.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
     L.mrt_path_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PathStepDesc), C.c_uint32]
     L.mrt_path_grid_step.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -378,6 +405,11 @@ def bounce_desc(frame, first_draw, t_max, metallic=0.0, roughness=0.5, d_select=
 def light_select_desc(frame, select_draw, d_out_light, d_select=None):
     """mrt_light_select from its fields (d_out_light, d_select: device pointers / tensors; d_select or None)"""
     return LightSelect(frame, select_draw, None if d_select is None else _ptr(d_select).value, _ptr(d_out_light).value)
+
+
+def emitter_select_desc(frame, draw, d_out_emitter, d_select=None):
+    """mrt_emitter_select from its fields (d_out_emitter, d_select: device pointers / tensors; d_select or None)"""
+    return EmitterSelect(frame, draw, None if d_select is None else _ptr(d_select).value, _ptr(d_out_emitter).value)
 
 
 def surface_out(d_rows=None, d_bounce_surface=None, d_out_hits=None):
@@ -1043,6 +1075,78 @@ class Context:
         out = LightOut(_ptr(d_rgba).value)
         self._chk(self.L.mrt_light_grid_selected_surfaces(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _ptr(d_rows), lp,
                                                           lights.shape[0], _ptr(d_light), _optr(d_mask), ep, C.byref(out), flags))
+
+    def build_emitters(self, tris, n_tris=None, on_device=False):
+        """Builds the resident emitter table from the scene's world-space triangles (T.TRI64 rows on the host, or a device pointer with
+        on_device and n_tris) and the resident shade data; returns (number of emitters, sum of their integer weights)."""
+        if isinstance(tris, np.ndarray):
+            tris = np.ascontiguousarray(tris, dtype=T.TRI64)
+            n_tris = tris.shape[0]
+        self._chk(self.L.mrt_build_emitters(self.h, _ptr(tris) if n_tris else None, n_tris, BUILD_TRIS_ON_DEVICE if on_device else 0))
+        return self.emitter_info()
+
+    def clear_emitters(self):
+        self._chk(self.L.mrt_clear_emitters(self.h))
+
+    def emitter_info(self):
+        n, total = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self.L.mrt_emitter_info(self.h, C.byref(n), C.byref(total)))
+        return n.value, total.value
+
+    def emitter_table(self):
+        """The resident table: (rows [n] T.EMITTER64, cdf [n] uint32)."""
+        n = self.emitter_info()[0]
+        rows, cdf = np.zeros(n, T.EMITTER64), np.zeros(n, np.uint32)
+        self._chk(self.L.mrt_emitter_table(self.h, _np(rows), _np(cdf), n))
+        return rows, cdf
+
+    def cast_emitter_shadows(self, d_rays, d_hits, count, d_mask, d_out_emitter, frame=0, draw=512, d_select=None, query_mask=0xFFFFFFFF,
+                             flags=0):
+        """One shadow ray per record, to a point of the emitter the record samples from the resident table (draws draw .. draw + 2 of its
+        stream; the path tracer: types.path_emitter_draw(bounce)).  d_mask one byte per record: 1 lit / 0 shadowed; d_out_emitter one
+        uint32 per record: the emitter or types.EMITTER_NONE; d_select: optional byte per record (0 = samples no emitter)."""
+        desc = emitter_select_desc(frame, draw, d_out_emitter, d_select)
+        self._chk(self.L.mrt_cast_emitter_shadows(self.h, _ptr(d_rays), _ptr(d_hits), count, C.byref(desc), _ptr(d_mask), query_mask, flags))
+
+    def cast_grid_emitter_shadows(self, cam, grid_w, grid_h, d_hits, d_mask, d_out_emitter, frame=0, draw=512, d_select=None, y0=0, y1=None,
+                                  query_mask=0xFFFFFFFF, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid; the stream of a pixel is seeded from its index in the whole grid."""
+        y1 = grid_h if y1 is None else y1
+        desc = emitter_select_desc(frame, draw, d_out_emitter, d_select)
+        self._chk(self.L.mrt_cast_grid_emitter_shadows(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), C.byref(desc), _ptr(d_mask),
+                                                       query_mask, flags))
+
+    def light_emitter_surfaces(self, d_rays, d_hits, d_rows, count, d_emitter, d_rgba, d_mask=None, frame=0, draw=512, accumulate=False, flags=0):
+        """The diffuse term of the emitter point each record sampled (d_emitter, d_mask: what cast_emitter_shadows wrote with the same
+        frame and draw).  accumulate: added to what d_rgba holds, else written."""
+        desc = emitter_select_desc(frame, draw, d_emitter)
+        out = LightOut(_ptr(d_rgba).value)
+        self._chk(self.L.mrt_light_emitter_surfaces(self.h, _ptr(d_rays), _ptr(d_hits), _ptr(d_rows), count, C.byref(desc), _optr(d_mask),
+                                                    EMITTER_ACCUMULATE if accumulate else 0, C.byref(out), flags))
+
+    def light_grid_emitter_surfaces(self, cam, grid_w, grid_h, d_hits, d_rows, d_emitter, d_rgba, d_mask=None, frame=0, draw=512,
+                                    accumulate=False, y0=0, y1=None, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (every per-record array indexed by the record within the band)."""
+        y1 = grid_h if y1 is None else y1
+        desc = emitter_select_desc(frame, draw, d_emitter)
+        out = LightOut(_ptr(d_rgba).value)
+        self._chk(self.L.mrt_light_grid_emitter_surfaces(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _ptr(d_rows), C.byref(desc),
+                                                         _optr(d_mask), EMITTER_ACCUMULATE if accumulate else 0, C.byref(out), flags))
+
+    def path_step_emitters(self, d_rays, d_hits, d_rows, count, d_direct, d_state, env, d_out_select, d_prev_lobe, frame=0, bounce=0,
+                           max_bounces=4, d_out_lobe=None, d_active_count=None, flags=0):
+        """path_step for a loop that samples emitters: from bounce 1 on the emission of a hit is added only where d_prev_lobe (the lobe
+        bytes of the step before; None at bounce 0; may be d_out_lobe) says the ray came from the specular lobe."""
+        desc, env = self._path_desc(frame, bounce, max_bounces, d_direct, d_state, env, d_out_select, d_out_lobe, d_active_count)
+        self._chk(self.L.mrt_path_step_emitters(self.h, _ptr(d_rays), _ptr(d_hits), _ptr(d_rows), count, C.byref(desc), _optr(d_prev_lobe), flags))
+
+    def path_grid_step_emitters(self, cam, grid_w, grid_h, d_hits, d_rows, d_direct, d_state, env, d_out_select, d_prev_lobe, frame=0, bounce=0,
+                                max_bounces=4, d_out_lobe=None, d_active_count=None, y0=0, y1=None, flags=0):
+        """The same for rows [y0, y1) of a grid cast by cast_grid (every per-record array indexed by the record within the band)."""
+        y1 = grid_h if y1 is None else y1
+        desc, env = self._path_desc(frame, bounce, max_bounces, d_direct, d_state, env, d_out_select, d_out_lobe, d_active_count)
+        self._chk(self.L.mrt_path_grid_step_emitters(self.h, C.byref(cam), grid_w, grid_h, y0, y1, _ptr(d_hits), _ptr(d_rows), C.byref(desc),
+                                                     _optr(d_prev_lobe), flags))
 
     def path_init(self, d_state, count, flags=0):
         """Every T.PATH_STATE entry to throughput 1, active, radiance 0."""

@@ -172,6 +172,8 @@ uint32_t mrt_struct_size(uint32_t which)
 		case 30: return (uint32_t)sizeof(mrt_gbuffer); // (29: not a struct)
 		case 32: return (uint32_t)sizeof(mrt_svgf_params); // (31: not a struct)
 		case 34: return (uint32_t)sizeof(mrt_light_select); // (33: not a struct)
+		case 36: return (uint32_t)sizeof(mrt_emitter_select); // (35: not a struct)
+		case 38: return (uint32_t)sizeof(mrt_emitter64); // (37: not a struct)
 		default: return 0u;
 	}
 }
@@ -276,6 +278,7 @@ void mrt_destroy(mrt_ctx *ctx)
 	release(ctx->shade_rows); release(ctx->shade_materials);
 	release(ctx->tex_texels); release(ctx->tex_table); release(ctx->tex_bindings); release(ctx->tex_tangents);
 	release(ctx->pano_texels);
+	release(ctx->emit_rows); release(ctx->emit_cdf); release(ctx->emit_in); release(ctx->emit_work);
 	for (auto &sc : ctx->sched) {
 		if (sc.side) { (void)hipStreamSynchronize(sc.side); (void)hipStreamDestroy(sc.side); }
 		if (sc.traced) (void)hipEventDestroy(sc.traced);

@@ -13,6 +13,7 @@
 #include "mrt_context.h"
 #include "gbuffer.h"
 #include "source_cast.h"
+#include "emitters.h"
 
 namespace {
 
@@ -378,6 +379,16 @@ int cast_selected_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TracePar
 	return cast_batch(ctx, entry, src, p, mrt::sc::selected_shadow_batch(src, count), d_mask, query_mask, s, flags);
 }
 
+// (an empty table: every record gets MRT_EMITTER_NONE and a lit byte, in the kernel, so that the outputs are always written)
+int cast_emitter_shadows(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_rays, const void *d_hits, uint64_t count,
+		uint32_t pixel0, const mrt_emitter_select *desc, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	if (int rc = source_cast_check(ctx, mrt::em::shadow_invalid(entry == mrt::ENTRY_EMITTER_SHADOW, d_rays, d_hits, desc, d_mask, flags))) return rc;
+	mrt::EmitterShadowParams s;
+	mrt::em::fill_shadow(d_hits, desc, emitter_table(ctx), pixel0, s);
+	return cast_batch(ctx, entry, src, p, mrt::sc::batch(src, MRT_MODE_ANY_HIT, count), d_mask, query_mask, s, flags);
+}
+
 int cast_reflections(mrt_ctx *ctx, mrt::Entry entry, int src, mrt::TraceParams &p, const void *d_hits, uint64_t count,
 		const uint8_t *d_select, float max_distance, void *d_out_hits, void *d_out_rays, uint32_t query_mask, uint32_t flags)
 {
@@ -596,6 +607,27 @@ int mrt_cast_grid_selected_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t
 	if (int rc = grid_source_params(ctx, cam, grid_w, grid_h, y0, y1, p)) return rc;
 	return cast_selected_shadows(ctx, mrt::ENTRY_GRID_SELECTED_SHADOW, mrt::SRC_SELSHADOW_GRID, p, cam, d_hits, p.count, y0 * grid_w, desc, lights,
 			n_lights, d_mask, query_mask, flags);
+}
+
+int mrt_cast_emitter_shadows(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const mrt_emitter_select *desc,
+		uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	const bool host = (flags & MRT_FLAG_HOST_LAYOUT) != 0;
+	mrt::TraceParams p;
+	array_params(ctx, d_rays, host, p); // (the incoming rays are read: the normal is faced)
+	return cast_emitter_shadows(ctx, mrt::ENTRY_EMITTER_SHADOW, host ? mrt::SRC_EMITSHADOW_HOST44 : mrt::SRC_EMITSHADOW_RAY32, p, d_rays, d_hits,
+			count, 0u, desc, d_mask, query_mask, flags);
+}
+
+int mrt_cast_grid_emitter_shadows(mrt_ctx *ctx, const mrt_camera *cam, uint32_t grid_w, uint32_t grid_h, uint32_t y0, uint32_t y1,
+		const mrt_hit32 *d_hits, const mrt_emitter_select *desc, uint8_t *d_mask, uint32_t query_mask, uint32_t flags)
+{
+	if (!ctx) return MRT_ERR_INVALID;
+	mrt::TraceParams p;
+	if (int rc = grid_source_params(ctx, cam, grid_w, grid_h, y0, y1, p)) return rc;
+	return cast_emitter_shadows(ctx, mrt::ENTRY_GRID_EMITTER_SHADOW, mrt::SRC_EMITSHADOW_GRID, p, cam, d_hits, p.count, y0 * grid_w, desc, d_mask,
+			query_mask, flags);
 }
 
 int mrt_cast_reflections(mrt_ctx *ctx, const void *d_rays, const void *d_hits, uint64_t count, const uint8_t *d_select,

@@ -34,6 +34,8 @@ namespace mrt {
 #include "hemisphere_kernel.h"
 #include "bounce_kernel.h"
 #include "gbuffer_kernel.h"
+#include "emitter_sample_kernel.h"
+#include "emitter_shadow_kernel.h"
 
 // ---- the traversal kernel: one lane = one ray (lane_walk.h) -------------------------------------
 #include "lane_walk.h"
@@ -157,7 +159,7 @@ hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *nex
 
 // Record-driven casts: p.kernel is the lane kernel the plan chose (launch_policy.cpp plan_source); p.count = entries.  persistent:
 // blocks != 0 (as launch_trace_persistent), else the plain kernel with p.sparse_lanes (resolve_source).  src = one of the family's
-// three sources; any_hit = a mode the family has (shadows, selected or not, any-hit, reflections and bounces closest-hit, hemispheres either: the other
+// three sources; any_hit = a mode the family has (shadows, selected, to an emitter or neither, any-hit, reflections and bounces closest-hit, hemispheres either: the other
 // instantiations do not compile, source_entry).  Anything else is hipErrorInvalidValue.
 template <class S>
 hipError_t launch_source(const TraceParams &p, const void *params, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
@@ -188,5 +190,6 @@ template hipError_t launch_source<ReflectParams>(const TraceParams &, const void
 template hipError_t launch_source<HemiParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<BounceParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 template hipError_t launch_source<GBufferParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+template hipError_t launch_source<EmitterShadowParams>(const TraceParams &, const void *, int, bool, unsigned long long *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 
 } // namespace mrt

@@ -56,12 +56,14 @@ struct SceneFacts {
 // frame (mirror rays made in the kernel from a rasteriser's depth and normal buffers: the plan of a reflection cast of as many rays).
 // ENTRY_SELECTED_SHADOW / ENTRY_GRID_SELECTED_SHADOW: mrt_cast_selected_shadows / mrt_cast_grid_selected_shadows, count = records (one
 // shadow ray per record to the light it draws: an unsorted any-hit batch, less coherent than a shadow cast's since neighbours differ in light)
+// ENTRY_EMITTER_SHADOW / ENTRY_GRID_EMITTER_SHADOW: mrt_cast_emitter_shadows / mrt_cast_grid_emitter_shadows, count = records (one shadow
+// ray per record to a sampled point of a sampled emissive triangle: the same kind of batch, neighbours differing in emitter and point)
 enum Entry : uint32_t { ENTRY_CAST, ENTRY_SUBMIT, ENTRY_CHUNK, ENTRY_GRID, ENTRY_TILED, ENTRY_SHADOW, ENTRY_GRID_SHADOW,
 	ENTRY_REFLECTION, ENTRY_GRID_REFLECTION, ENTRY_HEMISPHERE, ENTRY_GRID_HEMISPHERE, ENTRY_BOUNCE, ENTRY_GRID_BOUNCE,
-	ENTRY_GBUFFER_REFLECTION, ENTRY_SELECTED_SHADOW, ENTRY_GRID_SELECTED_SHADOW };
+	ENTRY_GBUFFER_REFLECTION, ENTRY_SELECTED_SHADOW, ENTRY_GRID_SELECTED_SHADOW, ENTRY_EMITTER_SHADOW, ENTRY_GRID_EMITTER_SHADOW };
 inline bool ray_entry(Entry e) { return e <= ENTRY_CHUNK; } // rays from an array, through enqueue_cast
 // rays made in the kernel, from hit records or (ENTRY_GBUFFER_REFLECTION) from a G-buffer
-inline bool record_cast_entry(Entry e) { return e >= ENTRY_SHADOW && e <= ENTRY_GRID_SELECTED_SHADOW; }
+inline bool record_cast_entry(Entry e) { return e >= ENTRY_SHADOW && e <= ENTRY_GRID_EMITTER_SHADOW; }
 
 struct CastRequest {
 	Entry entry = ENTRY_CAST;

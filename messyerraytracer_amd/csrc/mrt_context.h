@@ -18,7 +18,7 @@ bool quad_kernel_built();
 hipError_t launch_trace_persistent(const TraceParams &p, unsigned long long *next_ray, uint32_t *overflow,
 		uint32_t lds_depth, uint32_t refill, uint32_t leaf_wait, uint32_t blocks, bool any_hit, bool count, hipStream_t stream);
 // record-driven casts (source_common.h): S = the family's parameter struct (instantiated in kernels.hip for ShadowParams, SelectShadowParams, ReflectParams,
-// HemiParams, BounceParams and GBufferParams), params = an S, src = one of SourceFamily<S>'s sources, any_hit = a mode the family has; blocks != 0: the
+// HemiParams, BounceParams, GBufferParams and EmitterShadowParams), params = an S, src = one of SourceFamily<S>'s sources, any_hit = a mode the family has; blocks != 0: the
 // persistent kernel (next_ray .. leaf_wait as launch_trace_persistent)
 template <class S>
 hipError_t launch_source(const TraceParams &p, const void *params, int src, bool any_hit, unsigned long long *next_ray, uint32_t *overflow,
@@ -47,6 +47,11 @@ struct PathParams;
 hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream);
 hipError_t launch_path_step(const TraceParams &p, const PathParams &s, const PanoramaParams *pano, int src, hipStream_t stream);
 hipError_t launch_path_finish(const mrt_path_state *state, uint64_t count, uint32_t mode, float white, float *rgba, hipStream_t stream);
+// emissive triangles as light sources: the step that leaves out emission a diffuse-lobe ray found (path_kernel.h) and the sampled
+// point's diffuse term (emitter_light_kernel.h)
+struct EmitterLightParams;
+hipError_t launch_path_step_emitters(const TraceParams &p, const PathParams &s, const PanoramaParams *pano, const uint8_t *prev_lobe, int src, hipStream_t stream);
+hipError_t launch_light_emitter_surfaces(const TraceParams &p, const EmitterLightParams &s, int src, hipStream_t stream);
 hipError_t launch_pack_shade_rows(const uint32_t *ids, const float *normals9, const float *uvs6, uint32_t n_tris, void *rows, hipStream_t stream);
 // the renderer's channels (channel_kernel.h): src = a SurfaceSrc, t all zero with no texture set resident; the lit frame's last pass
 // and the 8-bit image (path_frame_kernel.h)
@@ -175,6 +180,9 @@ struct mrt_ctx {
 	uint32_t pano_width = 0, pano_height = 0;
 	float pano_energy = 0.0f;
 	bool pano_resident = false;
+	// emitter table (emitters.hip): the context's, like the shade data; emit_n rows and CDF words, emit_total = the last CDF word
+	DevBuf emit_rows, emit_cdf, emit_in, emit_work;
+	uint32_t emit_n = 0, emit_total = 0;
 };
 
 #define HIP_TRY(ctx, call)                                                                          \
@@ -265,6 +273,10 @@ inline mrt::TextureParams texture_params(const mrt_ctx *ctx)
 		t.n_bindings = ctx->tex_n_bindings; t.n_tangent_tris = ctx->tex_n_tangent_tris;
 	}
 	return t;
+}
+inline mrt::EmitterTable emitter_table(const mrt_ctx *ctx)
+{
+	return {ctx->emit_n ? ctx->emit_rows.ptr : nullptr, ctx->emit_n ? (const uint32_t *)ctx->emit_cdf.ptr : nullptr, ctx->emit_n, ctx->emit_total};
 }
 inline mrt::PanoramaParams panorama_params(const mrt_ctx *ctx)
 {

@@ -174,15 +174,20 @@ enum RaySrc : int { SRC_CAST = 0, SRC_SHADOW_RAY32 = 1, SRC_SHADOW_HOST44 = 2, S
 	SRC_HEMI_RAY32 = 7, SRC_HEMI_HOST = 8, SRC_HEMI_GRID = 9,
 	SRC_BOUNCE_RAY32 = 10, SRC_BOUNCE_HOST = 11, SRC_BOUNCE_GRID = 12,
 	SRC_GBUFFER = 13,
-	SRC_SELSHADOW_RAY32 = 14, SRC_SELSHADOW_HOST44 = 15, SRC_SELSHADOW_GRID = 16 };
+	SRC_SELSHADOW_RAY32 = 14, SRC_SELSHADOW_HOST44 = 15, SRC_SELSHADOW_GRID = 16,
+	SRC_EMITSHADOW_RAY32 = 17, SRC_EMITSHADOW_HOST44 = 18, SRC_EMITSHADOW_GRID = 19 };
 constexpr bool shadow_source(int src) { return src >= SRC_SHADOW_RAY32 && src <= SRC_SHADOW_GRID; }
 constexpr bool reflection_source(int src) { return src >= SRC_REFLECT_RAY32 && src <= SRC_REFLECT_GRID; }
 constexpr bool hemisphere_source(int src) { return src >= SRC_HEMI_RAY32 && src <= SRC_HEMI_GRID; }
 constexpr bool bounce_source(int src) { return src >= SRC_BOUNCE_RAY32 && src <= SRC_BOUNCE_GRID; }
 constexpr bool gbuffer_source(int src) { return src == SRC_GBUFFER; }
 constexpr bool selected_shadow_source(int src) { return src >= SRC_SELSHADOW_RAY32 && src <= SRC_SELSHADOW_GRID; }
-// the result of an entry is one byte (1 = no occluder, or no ray): every shadow cast, selected or not, and a hemisphere cast in any-hit mode
-constexpr bool lit_output(int src, bool any_hit) { return shadow_source(src) || selected_shadow_source(src) || (hemisphere_source(src) && any_hit); }
+constexpr bool emitter_shadow_source(int src) { return src >= SRC_EMITSHADOW_RAY32 && src <= SRC_EMITSHADOW_GRID; }
+// the result of an entry is one byte (1 = no occluder, or no ray): every shadow cast, selected, to an emitter or neither, and a hemisphere cast in any-hit mode
+constexpr bool lit_output(int src, bool any_hit)
+{
+	return shadow_source(src) || selected_shadow_source(src) || emitter_shadow_source(src) || (hemisphere_source(src) && any_hit);
+}
 enum ShadowKind : uint32_t { SHADOW_OFF = 0, SHADOW_DIRECTIONAL = 1, SHADOW_POINT = 2 }; // OFF: cast_shadows == 0 (lit)
 struct ShadowLight { uint32_t kind; float v[3]; }; // DIRECTIONAL: direction towards the light; POINT (point and spot): position
 struct ShadowParams {
@@ -254,6 +259,26 @@ struct SelectShadowParams {
 	HemiJump jump;             // (A, C) of draw select_draw
 	uint32_t n_lights;         // >= 1
 	ShadowLight light[MRT_MAX_LIGHTS];
+};
+
+// ---- one shadow ray per record, to a sampled point of a sampled emissive triangle (emitter_shadow_kernel.h; emitters.h fills this) ------
+// The resident emitter table (emitters.hip): n rows of 64 bytes {v0, q | edge1, prim id | edge2, area | Le, material} and the inclusive
+// uint32 CDF of q, both in device memory; total = cdf[n - 1] (0 with n == 0).
+struct EmitterTable {
+	const void *rows;
+	const uint32_t *cdf;
+	uint32_t n, total;
+};
+// Entry i of an emitter-shadow cast is record i; TraceParams::count = records, hits = the lit mask (one byte per record), rays = the
+// incoming rays as for a bounce (the normal is faced).  The generator's state before the selecting draw is jump.a * state0 + jump.c;
+// the two floats of the point are the next two draws.
+struct EmitterShadowParams {
+	const void *records;       // mrt_hit32 (SRC_EMITSHADOW_RAY32, SRC_EMITSHADOW_GRID) or mrt_host_hit44 (SRC_EMITSHADOW_HOST44)
+	const uint8_t *select;     // optional: 0 = the record samples no emitter
+	uint32_t *out_emitter;     // the emitter sampled per record, or MRT_EMITTER_NONE
+	EmitterTable table;
+	uint32_t seed_add;         // frame * 6529 + 7 (+ y0 * grid_w * 1009 for a row band): seed = record * 1009 + seed_add
+	HemiJump jump;             // (A, C) of draw `draw`
 };
 
 // ---- reflection rays from a rasteriser's G-buffer (gbuffer_kernel.h, gbuffer.h): one closest-hit ray per pixel of a whole frame -----
@@ -334,6 +359,12 @@ template <> struct SourceFamily<SelectShadowParams> {
 	static constexpr int ray32 = SRC_SELSHADOW_RAY32, host = SRC_SELSHADOW_HOST44, grid = SRC_SELSHADOW_GRID;
 	static constexpr bool any_hit = true, nearest = false;
 	static constexpr const char *name = "selected_shadow";
+};
+
+template <> struct SourceFamily<EmitterShadowParams> {
+	static constexpr int ray32 = SRC_EMITSHADOW_RAY32, host = SRC_EMITSHADOW_HOST44, grid = SRC_EMITSHADOW_GRID;
+	static constexpr bool any_hit = true, nearest = false;
+	static constexpr const char *name = "emitter_shadow";
 };
 
 // host-side preparation (scene_prep.cpp)

@@ -1,4 +1,5 @@
-// path_kernel.h — the path tracer's per-pixel state (mrt_path_step / mrt_path_grid_step; the two small kernels of mrt_path_init and
+// path_kernel.h — the path tracer's per-pixel state (mrt_path_step / mrt_path_grid_step, and mrt_path_step_emitters / its grid form;
+// the two small kernels of mrt_path_init and
 // mrt_path_finish are path_frame_kernel.h).  Included by shade_kernels.hip (inside namespace mrt, after light_kernel.h; path.h holds PathParams).
 //
 // The rest of CPUPathTracer's loop body (src/modules/graphics/cpu_path_tracer.h:110-194) around the links already resident: the
@@ -14,8 +15,11 @@
 // the ambient line of bounce 0 is the same line either way, as in the reference.  The panorama is a kernel argument of its own.
 #pragma once
 
-template <int SRC, bool PANO>
-__device__ __forceinline__ void path_step_record(const TraceParams &p, const PathParams &s, const PanoramaParams &pano)
+// EMIT (mrt_path_step_emitters): emitter sampling has already counted, at the previous vertex, the emission a diffuse-lobe ray finds --
+// from bounce 1 on the emission line runs only where prev_lobe[i] is MRT_LOBE_SPECULAR.  prev_lobe may be s.out_lobe: the entry is read
+// here, before the end of the step writes it.
+template <int SRC, bool PANO, bool EMIT = false>
+__device__ __forceinline__ void path_step_record(const TraceParams &p, const PathParams &s, const PanoramaParams &pano, const uint8_t *prev_lobe = nullptr)
 {
 	constexpr bool HOST = SRC == SURF_HOST, GRID = SRC == SURF_GRID;
 	const uint64_t i = (uint64_t)blockIdx.x * MRT_WG + threadIdx.x;
@@ -42,7 +46,9 @@ __device__ __forceinline__ void path_step_record(const TraceParams &p, const Pat
 				const float ndv = r0.w;
 				float f0[3], df[3];
 				f0_diffuse(r1, r3.z, f0, df);
-				rr = rr + tr * r2.x; rg = rg + tg * r2.y; rb = rb + tb * r2.z;
+				bool emits = true;
+				if constexpr (EMIT) emits = s.bounce == 0u || prev_lobe[i] == MRT_LOBE_SPECULAR;
+				if (emits) { rr = rr + tr * r2.x; rg = rg + tg * r2.y; rb = rb + tb * r2.z; }
 				rr = rr + tr * dl.x; rg = rg + tg * dl.y; rb = rb + tb * dl.z;
 				if (s.bounce == 0u) {
 					rr = rr + ((tr * df[0]) * s.ambient[0]) * s.ambient_energy;
@@ -105,4 +111,17 @@ template <int SRC>
 __global__ __launch_bounds__(MRT_WG) void path_step_panorama_kernel(const TraceParams p, const PathParams s, const PanoramaParams pano)
 {
 	path_step_record<SRC, true>(p, s, pano);
+}
+
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void path_step_emitters_kernel(const TraceParams p, const PathParams s, const uint8_t *prev_lobe)
+{
+	path_step_record<SRC, false, true>(p, s, PanoramaParams{}, prev_lobe);
+}
+
+template <int SRC>
+__global__ __launch_bounds__(MRT_WG) void path_step_emitters_panorama_kernel(const TraceParams p, const PathParams s, const PanoramaParams pano,
+		const uint8_t *prev_lobe)
+{
+	path_step_record<SRC, true, true>(p, s, pano, prev_lobe);
 }

@@ -16,6 +16,7 @@
 #include "accum.h"
 #include "denoise.h"
 #include "svgf.h"
+#include "emitters.h"
 #include "gbuffer.h"
 #include "lane_map.h"
 #include "walk_steps.h"
@@ -33,6 +34,8 @@ namespace mrt {
 #include "surface_tex_kernel.h"
 #include "surface_kernel.h"
 #include "light_kernel.h"
+#include "emitter_sample_kernel.h"
+#include "emitter_light_kernel.h"
 #include "path_kernel.h"
 #include "channel_kernel.h"
 #include "gbuffer_image_kernel.h"
@@ -56,6 +59,17 @@ hipError_t launch_path_step(const TraceParams &p, const PathParams &s, const Pan
 {
 	if (pano == nullptr) return launch_surface_pass([](auto SRC) { return path_step_kernel<SRC>; }, src, p, stream, s);
 	return launch_surface_pass([](auto SRC) { return path_step_panorama_kernel<SRC>; }, src, p, stream, s, *pano);
+}
+// mrt_path_step_emitters: prev_lobe may be null at bounce 0 alone (the kernel reads it from bounce 1 on)
+hipError_t launch_path_step_emitters(const TraceParams &p, const PathParams &s, const PanoramaParams *pano, const uint8_t *prev_lobe, int src, hipStream_t stream)
+{
+	if (pano == nullptr) return launch_surface_pass([](auto SRC) { return path_step_emitters_kernel<SRC>; }, src, p, stream, s, prev_lobe);
+	return launch_surface_pass([](auto SRC) { return path_step_emitters_panorama_kernel<SRC>; }, src, p, stream, s, *pano, prev_lobe);
+}
+// the diffuse term of a sampled emitter point (emitter_light_kernel.h), called from emitters.hip
+hipError_t launch_light_emitter_surfaces(const TraceParams &p, const EmitterLightParams &s, int src, hipStream_t stream)
+{
+	return launch_surface_pass([](auto SRC) { return light_emitter_surfaces_kernel<SRC>; }, src, p, stream, s);
 }
 hipError_t launch_path_init(mrt_path_state *state, uint64_t count, hipStream_t stream)
 {

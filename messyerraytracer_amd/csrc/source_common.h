@@ -1,8 +1,8 @@
 // source_common.h — what every ray source shares (shadow_kernel.h, selected_shadow_kernel.h, reflection_kernel.h, hemisphere_kernel.h,
-// bounce_kernel.h, and gbuffer_kernel.h, whose entries are pixels of a G-buffer, not records).  Included by kernels.hip (inside namespace mrt, after
+// bounce_kernel.h, emitter_shadow_kernel.h, and gbuffer_kernel.h, whose entries are pixels of a G-buffer, not records).  Included by kernels.hip (inside namespace mrt, after
 // device_common.h, before the family headers) and, for record_surface, by shade_kernels.hip.
 //
-// A source family is a parameter struct (mrt_internal.h: ShadowParams, SelectShadowParams, ReflectParams, HemiParams, BounceParams, GBufferParams;
+// A source family is a parameter struct (mrt_internal.h: ShadowParams, SelectShadowParams, ReflectParams, HemiParams, BounceParams, GBufferParams, EmitterShadowParams;
 // SourceFamily<S> names its sources and its modes) plus one overload of
 //   template <int SRC, bool ANY_HIT> bool source_entry(const TraceParams &p, const S &s, uint64_t g, RayRegs &r)
 // which makes the ray of entry g (true: r is a ray to walk) or stores the result of an entry without a ray (false: the lit byte, or

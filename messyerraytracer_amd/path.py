@@ -123,13 +123,14 @@ def roulette(t):
     return np.where(SURVIVAL_CAP < mx, SURVIVAL_CAP, mx).astype(F)
 
 
-def path_step(state, rows, hit, nrm, in_dirs, direct, env, pixel_index, frame, bounce, max_bounces, info=None, panorama=None):
+def path_step(state, rows, hit, nrm, in_dirs, direct, env, pixel_index, frame, bounce, max_bounces, info=None, panorama=None, emits=None):
     """mrt_path_step for N records: state [N] T.PATH_STATE (not modified), rows as mrt_resolve_surfaces wrote them, hit [N] bool, nrm
     [N, 3] the records' normals, in_dirs [N, 3] the incoming directions as given, direct [N, >= 3] what mrt_light_surfaces wrote with
     env == NULL, env one T.ENVIRONMENT row, pixel_index [N].  Returns (state', select [N] uint8, lobe [N] uint8, active count).  info: an
     optional dict that receives what happened to each entry, [N] bool each: missed, invalid (a sample below the surface), killed and
     survived (roulette), stopped (the last bounce).  panorama: (pixels [H, W, 4], energy) as resident (mrt_upload_panorama) or None -- the
-    sky of a miss is then its sample."""
+    sky of a miss is then its sample.  emits: [N] bool or None -- mrt_path_step_emitters' rule, the emission line runs only where it is set
+    (None: everywhere, mrt_path_step)."""
     N = state.shape[0]
     st = state.copy()
     hit = np.asarray(hit, dtype=bool)
@@ -151,7 +152,10 @@ def path_step(state, rows, hit, nrm, in_dirs, direct, env, pixel_index, frame, b
             rw = rows[idx]
             tt, rr = t[idx], r[idx]
             f0, diff = surface_terms(rw)
-            rr = rr + tt * rw["emission"]
+            if emits is None:
+                rr = rr + tt * rw["emission"]
+            else:
+                rr = np.where(np.asarray(emits, dtype=bool)[idx][:, None], rr + tt * rw["emission"], rr).astype(F)
             rr = rr + tt * np.asarray(direct, dtype=F)[idx, :3]
             if bounce == 0:
                 amb = np.asarray(env["ambient"], dtype=F)

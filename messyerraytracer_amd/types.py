@@ -65,6 +65,21 @@ def path_select_draw(bounce):
     """MRT_PATH_SELECT_DRAW: the draw of a pixel's stream that selects bounce b's light"""
     return 256 + int(bounce)
 
+
+# emissive triangles as light sources (mrt_build_emitters, mrt_cast_emitter_shadows, mrt_light_emitter_surfaces)
+EMITTER_SELECT = np.dtype([("frame", "<u4"), ("draw", "<u4"), ("d_select", "<u8"), ("d_out_emitter", "<u8")])  # mrt_emitter_select
+EMITTER64 = np.dtype([("v0", "<f4", 3), ("q", "<u4"), ("edge1", "<f4", 3), ("prim_id", "<u4"), ("edge2", "<f4", 3), ("area", "<f4"),
+                      ("radiance", "<f4", 3), ("material", "<u4")])  # mrt_emitter64
+EMITTER_NONE = 0xFFFFFFFF
+MAX_EMITTERS = 1 << 20
+assert EMITTER_SELECT.itemsize == 24 and EMITTER64.itemsize == 64
+
+
+def path_emitter_draw(bounce):
+    """MRT_PATH_EMITTER_DRAW: the first of the three draws of a pixel's stream that bounce b's emitter sample takes"""
+    return 512 + 4 * int(bounce)
+
+
 # rows of the device layouts (csrc/mrt_internal.h), as mrt_debug_snapshot and the host preparations return them
 TRI_HOT = np.dtype([("v0", "<f4", 3), ("id", "<u4"), ("e1", "<f4", 3), ("layers", "<u4"), ("e2", "<f4", 3), ("flags", "<u4")])
 TRI_COLD = np.dtype([("normal", "<f4", 3), ("pad", "<u4")])
