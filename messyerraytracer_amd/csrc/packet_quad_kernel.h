@@ -185,7 +185,7 @@
 		"s_movrels_b64 s[70:71], s[60:61]\n"                                                                        \
 		"s_branch L_loop_%=\n"                                                                                      \
 		/* the leaf section of the two-wide walks, behind the wait for the row (the loop head did not wait) */      \
-		MRT_ROWSW_LEAF("s[68:69]", "s[70:71]", "s_waitcnt lgkmcnt(0)\n" T_POST, CNT_T, ANYA, ANYB, ANYDONE)         \
+		MRT_ROWSW_LEAF("s[68:69]", "s[70:71]", "s_waitcnt lgkmcnt(0)\n" T_POST, CNT_T, ANYA, ANYB, ANYDONE, "", "", "") \
 		"L_pop_%=:\n"                                                                                               \
 		MRT_ROWSW_POP_READ("s68", "s69", "s70", "s71", "L_loop_%=")                                                 \
 		/* ---- out of line: a group whose rays have all left this subtree ---- */                                  \

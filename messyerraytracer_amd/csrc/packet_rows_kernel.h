@@ -42,7 +42,8 @@
 // flags), s48 / s49 (byte offsets of the child prefetches; s48 the cull bits of one child), s[50:51] / s[58:59] (the pushed
 // child's masks).  s64 / s65 are also the never-read destinations of the 128-ray walk's child prefetches, s[64:67] the counting
 // builds' clock, s[66:67] in the culling loop "the current row's copy is the one in v61".  s68: the stack's top, in
-// MRT_ROWS_POPFETCH builds only (the kernel has 72 scalars below the compiler's).
+// MRT_ROWS_POPFETCH builds only (the kernel has 72 scalars below the compiler's).  s[70:71]: the EXEC the paired walk's general code was
+// entered with, in MRT_ROWS_OWNEXEC builds only.
 // v50..v59 temporaries; v60 the never-read destination of the one-packet loop's far-child prefetch, a product of the packed node
 // step (MRT_ROWS_PKSLAB), in the culling loop the vector copy of the left child's (or the popped) row; v61 the right child's
 // copy and v62 the address of a copy's request, both in the culling loop only.
@@ -455,12 +456,59 @@ struct PacketRegs {
 		: MRT_ROWS_IN(A, a), [rows] "s"(rows), [qmask] "s"(qmask), [eps] "s"(eps), [vneg] "v"(vneg)                 \
 		: MRT_ROWS_CLOBBERS)
 
+// ---- owner-narrowed EXEC in the paired walk (round 8; -DMRT_ROWS_OWNEXEC=1, NOT the default) -----------------------------------
+// Everything that switch changes stands in this section: the words MRT_ROWS_LOOPW takes from it.  Switch off, they are empty and
+// the build is the parent's machine code.
+// What it does: a group's box test and its triangle test run with EXEC = the lanes of the group that own the row, where the
+// parent runs them on all 64.  The parent is correct without any masking (a lane that missed an ancestor's box cannot pass a
+// child's: the planes are monotone, and lim is -FLT_MAX for a lane that takes no part), so the masks that come out are the same
+// bits: a v_cmp_e64 under a narrowed EXEC writes 0 for the lanes that are off, which is what those lanes produce today.
+//   * node step: EXEC = the group's own mask OR lane 0, in front of MRT_ROWS_SLAB and its two v_cmp.  Lane 0 keeps v50 / v56 (tl /
+//     tr of the group tested last) current in the lane MRT_ROWSW_DECIDE reads, so the near / far order and every counter of the
+//     counting builds stay the parent's.  Lane 0 takes part only if it was in the EXEC the block was entered with;
+//   * triangle test: EXEC = the group's own mask: the v_div_scale / v_div_fmas VCC chain, the v_cndmask updates and the any-hit
+//     code run on owners only;
+//   * EXEC is the entry EXEC again, one s_mov_b64 per step, before anything that is not a per-lane test: MRT_ROWSW_DECIDE (its
+//     v_add_u32 on sp must run on every lane), the pops and their v_readfirstlane, the any-hit finish (MRT_ROWSW_ANYDONE compares
+//     every lane's lim), the counting macros, the exit.  The child prefetches are scalar and stand in front of the tests.
+// The two copies of the walk take different words, because the kernel has no scalar register to spare (with four more fixed ones
+// the compiler spilled scalars to lanes on the whole-tile path):
+//   * whole-tile fast path (rows_walk_wide_whole): entered with EXEC all ones, so lane 0 is the constant 1 and the constant -1
+//     restores: one scalar instruction per group tested, one per step, no register;
+//   * general code (rows_walk_wide): the entry EXEC is kept in s[70:71] (the last pair below the compiler's registers; s68 is the
+//     stack's top in MRT_ROWS_POPFETCH builds), and an s_and_b64 with it follows the OR with lane 0: two per group tested.
+// gfx950 wait states after a scalar write of EXEC: a VALU instruction that only executes under it needs none (the hardware
+// interlocks), nor does v_readfirstlane after the restoring s_mov_b64; a DPP instruction needs five wait states, and the paired walk
+// has none (the culling loop has its DPP sums, one reason it would pay more for this).  A lane mask written by v_cmp_e64 under a
+// narrowed EXEC goes to the scalar ALU as before.
+// The culling loop (MRT_ROWS_LOOPC), the one-packet loop (MRT_ROWS_LOOP1) and the four-wide walk keep the parent's text in either build.
+#ifndef MRT_ROWS_OWNEXEC
+#define MRT_ROWS_OWNEXEC 0
+#endif
+// the words of a copy of the walk: on entry, behind the OR with lane 0, the restore, and the name of its clobbers
+#if MRT_ROWS_OWNEXEC
+#define MRT_ROWS_OWN_WHOLE "", "", "s_mov_b64 exec, -1\n", WHOLE
+#define MRT_ROWS_OWN_ANYEXEC "s_mov_b64 s[70:71], exec\n", "s_and_b64 exec, exec, s[70:71]\n", "s_mov_b64 exec, s[70:71]\n", ANYEXEC
+#define MRT_ROWS_OWN_CLOBBER_WHOLE
+#define MRT_ROWS_OWN_CLOBBER_ANYEXEC "s70", "s71",
+#define MRT_ROWS_OWN_NODE(OWN, KEEP) "s_or_b64 exec, " OWN ", 1\n" KEEP
+#define MRT_ROWS_OWN_LEAF(OWN) "s_mov_b64 exec, " OWN "\n"
+#else
+#define MRT_ROWS_OWN_WHOLE "", "", "", WHOLE
+#define MRT_ROWS_OWN_ANYEXEC "", "", "", ANYEXEC
+#define MRT_ROWS_OWN_CLOBBER_WHOLE
+#define MRT_ROWS_OWN_CLOBBER_ANYEXEC
+#define MRT_ROWS_OWN_NODE(OWN, KEEP) ""
+#define MRT_ROWS_OWN_LEAF(OWN) ""
+#endif
+
 // ---- the 128-ray packet: groups A and B (two rays per lane) share one walk --------------------------------------
 // One group's slab test at a node row, skipped (no child hit) when no lane of the group owns the node.
 // LM / RM: the group's lanes that hit the left / right child.  v50 / v56 keep tl / tr of the last group tested.
-#define MRT_ROWSW_GROUP_SLAB(P, OWN, LM, RM, BX, BY, BZ)                                                              \
+#define MRT_ROWSW_GROUP_SLAB(P, OWN, LM, RM, BX, BY, BZ, NARROW)                                                           \
 	"s_cmp_eq_u64 " OWN ", 0\n"                                                                                     \
 	"s_cbranch_scc1 L_" P "skip_%=\n"         /* (out of line: the common path falls through) */                    \
+	NARROW                                                                                                          \
 	MRT_ROWS_SLAB(P, RA, BX, BY, BZ)                                                                                \
 	"v_cmp_le_f32_e64 " LM ", v50, v53\n"                                                                           \
 	"v_cmp_le_f32_e64 " RM ", v56, v52\n"                                                                           \
@@ -541,17 +589,20 @@ struct PacketRegs {
 
 // The leaf section: the triangle row in s[20:35] against each group that has a lane owning it (OWN_A / OWN_B), then the leaf's next
 // triangle (on at L_loop) or, after its last one, the pop (L_pop).  ARRIVED: what a loop that comes here with the row
-// still on its way puts first.
-#define MRT_ROWSW_LEAF(OWN_A, OWN_B, ARRIVED, CNT_T, ANYA, ANYB, ANYDONE)                                             \
+// still on its way puts first.  NARROW_A / NARROW_B / RESTORE: the words of MRT_ROWS_OWNEXEC in the loop that takes them, else "".
+#define MRT_ROWSW_LEAF(OWN_A, OWN_B, ARRIVED, CNT_T, ANYA, ANYB, ANYDONE, NARROW_A, NARROW_B, RESTORE)                 \
 	"L_tri_%=:\n"                                                                                                   \
 	CNT_T                                                                                                           \
 	ARRIVED                                                                                                         \
 	"s_cmp_eq_u64 " OWN_A ", 0\n"                                                                                   \
 	"s_cbranch_scc1 L_Atnext_%=\n"                                                                                  \
+	NARROW_A                                                                                                        \
 	MRT_ROWS_TRI_TEST("A", RA, OWN_A, "%[curA]", ANYA)                                                              \
 	"s_cmp_eq_u64 " OWN_B ", 0\n"                                                                                   \
 	"s_cbranch_scc1 L_Btnext_%=\n"                                                                                  \
+	NARROW_B                                                                                                        \
 	MRT_ROWS_TRI_TEST("B", RA, OWN_B, "%[curA]", ANYB)                                                              \
+	RESTORE                                                                                                         \
 	ANYDONE                                                                                                         \
 	"s_bitcmp1_b32 " RA_FLAGS ", 0\n"        /* the last triangle of its leaf? */                                   \
 	"s_cbranch_scc1 L_pop_%=\n"                                                                                     \
@@ -674,17 +725,17 @@ struct PacketRegs {
 	"v_cmp_le_f32_e64 s[42:43], v56, v53\n"  /* group B's */
 #if MRT_ROWS_PKSLAB
 // both groups' tests at a node row, and what of them stands out of line (behind the pop)
-#define MRT_ROWSW_SLABS(BX, BY, BZ)                                                                                   \
+#define MRT_ROWSW_SLABS(BX, BY, BZ, KEEP)                                                                              \
 	"s_cmp_eq_u64 s[60:61], 0\n"                                                                                    \
 	"s_cbranch_scc1 L_Askip_%=\n"             /* group B alone: on at L_Asdone, group B's own test */                \
 	"s_cmp_eq_u64 s[62:63], 0\n"                                                                                    \
 	"s_cbranch_scc1 L_single_%=\n"            /* group A alone */                                                    \
 	MRT_ROWSW_PKSLAB(BX, BY, BZ)                                                                                    \
 	"L_slabbed_%=:\n"
-#define MRT_ROWSW_SLABS_OOL(BX, BY, BZ)                                                                               \
+#define MRT_ROWSW_SLABS_OOL(BX, BY, BZ, KEEP)                                                                          \
 	"L_single_%=:\n"                                                                                                \
-	MRT_ROWSW_GROUP_SLAB("A", "s[60:61]", "s[36:37]", "s[38:39]", BX, BY, BZ)                                       \
-	MRT_ROWSW_GROUP_SLAB("B", "s[62:63]", "s[40:41]", "s[42:43]", BX, BY, BZ)                                       \
+	MRT_ROWSW_GROUP_SLAB("A", "s[60:61]", "s[36:37]", "s[38:39]", BX, BY, BZ, MRT_ROWS_OWN_NODE("s[60:61]", KEEP))  \
+	MRT_ROWSW_GROUP_SLAB("B", "s[62:63]", "s[40:41]", "s[42:43]", BX, BY, BZ, MRT_ROWS_OWN_NODE("s[62:63]", KEEP))  \
 	"s_branch L_slabbed_%=\n"                                                                                       \
 	MRT_ROWSW_GROUP_SKIP("A", "s[36:37]", "s[38:39]")                                                               \
 	MRT_ROWSW_GROUP_SKIP("B", "s[40:41]", "s[42:43]")
@@ -698,10 +749,10 @@ struct PacketRegs {
 	[tminB] "v"(S.tmin), [ixB] MRT_PK_PIN(MRT_PK_V1)(S.ix), [iyB] MRT_PK_PIN(MRT_PK_V3)(S.iy), [izB] MRT_PK_PIN(MRT_PK_V5)(S.iz), [nrxB] MRT_PK_PIN(MRT_PK_V7)(S.nrx),      \
 	[nryB] MRT_PK_PIN(MRT_PK_V9)(S.nry), [nrzB] MRT_PK_PIN(MRT_PK_V11)(S.nrz)
 #else
-#define MRT_ROWSW_SLABS(BX, BY, BZ)                                                                                   \
-	MRT_ROWSW_GROUP_SLAB("A", "s[60:61]", "s[36:37]", "s[38:39]", BX, BY, BZ)                                       \
-	MRT_ROWSW_GROUP_SLAB("B", "s[62:63]", "s[40:41]", "s[42:43]", BX, BY, BZ)
-#define MRT_ROWSW_SLABS_OOL(BX, BY, BZ)                                                                               \
+#define MRT_ROWSW_SLABS(BX, BY, BZ, KEEP)                                                                              \
+	MRT_ROWSW_GROUP_SLAB("A", "s[60:61]", "s[36:37]", "s[38:39]", BX, BY, BZ, MRT_ROWS_OWN_NODE("s[60:61]", KEEP))  \
+	MRT_ROWSW_GROUP_SLAB("B", "s[62:63]", "s[40:41]", "s[42:43]", BX, BY, BZ, MRT_ROWS_OWN_NODE("s[62:63]", KEEP))
+#define MRT_ROWSW_SLABS_OOL(BX, BY, BZ, KEEP)                                                                          \
 	MRT_ROWSW_GROUP_SKIP("A", "s[36:37]", "s[38:39]")                                                               \
 	MRT_ROWSW_GROUP_SKIP("B", "s[40:41]", "s[42:43]")
 #define MRT_ROWSW_IN_A(S) MRT_ROWS_IN(A, S)
@@ -710,11 +761,13 @@ struct PacketRegs {
 
 // In: cur (group A's operand) = a row to visit, the groups' own masks.  Out: cur = 0x7FFFFFFF.
 // Stack entries are 32 bytes: {group A's mask, group B's mask, ref, -}; the sentinel entry has ref 0x7FFFFFFF.
-#define MRT_ROWS_LOOPW(CNT_N, CNT_T, CNT_P, ANYA, ANYB, ANYDONE, BX, BY, BZ)                                                 \
+// (OWN_ENTER, OWN_KEEP, OWN_RESTORE, OWN_WHICH: the words of MRT_ROWS_OWNEXEC for this copy of the walk)
+#define MRT_ROWS_LOOPW_X(CNT_N, CNT_T, CNT_P, ANYA, ANYB, ANYDONE, BX, BY, BZ, OWN_ENTER, OWN_KEEP, OWN_RESTORE, OWN_WHICH)  \
 	asm volatile(                                                                                                   \
 		"s_mov_b64 s[60:61], %[maskA]\n"                                                                            \
 		"s_mov_b64 s[62:63], %[maskB]\n"                                                                            \
 		MRT_ROWS_TOP_EMPTY \
+		OWN_ENTER \
 		"L_loop_%=:\n"                                                                                              \
 		"s_lshl_b32 s52, %[curA], 6\n"                                                                              \
 		"s_load_dwordx16 s[20:35], %[rows], s52\n"                                                                  \
@@ -724,16 +777,22 @@ struct PacketRegs {
 		"s_cbranch_scc1 L_tri_%=\n"                                                                                 \
 		CNT_N                                                                                                       \
 		MRT_ROWSW_KPREFETCH                                                                                         \
-		MRT_ROWSW_SLABS(BX, BY, BZ)                                                                                 \
+		MRT_ROWSW_SLABS(BX, BY, BZ, OWN_KEEP)                                                                       \
+		OWN_RESTORE                                                                                                 \
 		MRT_ROWSW_DECIDE(CNT_P, "", "", "")                                                                         \
-		MRT_ROWSW_LEAF("s[60:61]", "s[62:63]", "", CNT_T, ANYA, ANYB, ANYDONE)                                      \
+		MRT_ROWSW_LEAF("s[60:61]", "s[62:63]", "", CNT_T, ANYA, ANYB, ANYDONE,                                      \
+				MRT_ROWS_OWN_LEAF("s[60:61]"), MRT_ROWS_OWN_LEAF("s[62:63]"), OWN_RESTORE)                              \
 		"L_pop_%=:\n"                                                                                               \
 		MRT_ROWSW_POP("", "L_loop_%=")                                                                              \
-		MRT_ROWSW_SLABS_OOL(BX, BY, BZ)                                                                             \
+		MRT_ROWSW_SLABS_OOL(BX, BY, BZ, OWN_KEEP)                                                                   \
 		MRT_ROWSW_EXIT(MRT_ROWS_EXIT_WAIT, "s[60:61]", "s[62:63]")                                                  \
 		: MRT_ROWSW_OUT                                                                                             \
 		: MRT_ROWSW_IN_A(a), MRT_ROWSW_IN_B(b), [rows] "s"(rows), [qmask] "s"(qmask), [eps] "s"(eps), [vneg] "v"(vneg) \
-		: MRT_ROWS_CLOBBERS)
+		: MRT_ROWS_OWN_CLOBBER_##OWN_WHICH MRT_ROWS_CLOBBERS)
+// the two copies: the general code, and the whole-tile fast path (entered with EXEC all ones)
+#define MRT_ROWS_LOOPW_ARGS(...) MRT_ROWS_LOOPW_X(__VA_ARGS__)
+#define MRT_ROWS_LOOPW(...) MRT_ROWS_LOOPW_ARGS(__VA_ARGS__, MRT_ROWS_OWN_ANYEXEC)
+#define MRT_ROWS_LOOPW_WHOLE(...) MRT_ROWS_LOOPW_ARGS(__VA_ARGS__, MRT_ROWS_OWN_WHOLE)
 
 // ---- the 128-ray walk with packet-level frustum culling ---------------------------------------------------------
 // The ownership model (tools/sim_ownership.py, profiles/r03_ownership_sim_c3.json): of the (group, child box) slab
@@ -840,7 +899,7 @@ struct PacketRegs {
 		MRT_ROWSC_CHILD(R, "v56", "0x80008000", "s[38:39]", "s[42:43]", BX, BY, BZ)                                 \
 		/* the next row's vector copy: both children hit: the near one's, v60 (left) / v61; one child: its own */   \
 		MRT_ROWSW_DECIDE(CNT_P, "s_cselect_b64 s[66:67], 0, -1\n", "s_mov_b64 s[66:67], 0\n", "s_mov_b64 s[66:67], -1\n") \
-		MRT_ROWSW_LEAF("s[60:61]", "s[62:63]", "", CNT_T, ANYA, ANYB, ANYDONE)                                      \
+		MRT_ROWSW_LEAF("s[60:61]", "s[62:63]", "", CNT_T, ANYA, ANYB, ANYDONE, "", "", "")                          \
 		"L_pop_%=:\n"                             /* the popped row's vector copy goes out beside its scalar fetch */ \
 		MRT_ROWSW_POP(MRT_ROWSC_VLOAD("v60", RA_TOP) "s_mov_b64 s[66:67], 0\n", "L_vload_%=")                       \
 		MRT_ROWSC_CHILD_OOL(L, "s[36:37]", "s[40:41]")                                                              \
@@ -930,6 +989,24 @@ __device__ __forceinline__ void rows_walk_wide(const float4 *rows, uint32_t qmas
 #undef MRT_ROW
 	rows_uniform(a);
 	MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(sp_max);
+}
+
+// the same walk for a wave that is entered with EXEC all ones (whole-tile pairs): it differs in the words of MRT_ROWS_OWNEXEC alone
+template <int OCT, bool ANY_HIT, bool COUNT>
+__device__ __forceinline__ void rows_walk_wide_whole(const float4 *rows, uint32_t qmask, PacketRegs &a, PacketRegs &b, uint32_t &cnt_n, uint32_t &cnt_t, uint32_t &sp_max)
+{
+#if MRT_ROWS_OWNEXEC
+	const float eps = 1e-8f, vneg = -FLT_MAX;
+	if (!COUNT) { cnt_n = 0u; cnt_t = 0u; sp_max = 0u; }
+	else { MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(sp_max); }
+#define MRT_ROW(O, BX, BY, BZ) MRT_WALK_FORMS(MRT_ROWS_LOOPW_WHOLE, MRT_ROWSW_COUNTING, MRT_ROWSW_PLAIN, MRT_ROWSW_ANY, MRT_ROWSW_NEAREST, O, BX, BY, BZ)
+	MRT_OCTANTS(MRT_ROW)
+#undef MRT_ROW
+	rows_uniform(a);
+	MRT_UNIFORM(cnt_n); MRT_UNIFORM(cnt_t); MRT_UNIFORM(sp_max);
+#else
+	rows_walk_wide<OCT, ANY_HIT, COUNT>(rows, qmask, a, b, cnt_n, cnt_t, sp_max);
+#endif
 }
 
 template <int OCT, bool ANY_HIT, bool COUNT>
@@ -1252,7 +1329,8 @@ __device__ __forceinline__ bool rows_walks_and_records(const TraceParams &p, Row
 			const CullRegs cull = cull_setup(ra, rb, valid_a, valid_b, part_a, part_b, p.scene_abs_max, lane);
 			MRT_OCT_SWITCH(oct_a, rows_walk_cull, rows, p.query_mask, A, B, cull, cnt_n, cnt_t, sp_wide)
 		} else {
-			MRT_OCT_SWITCH(oct_a, rows_walk_wide, rows, p.query_mask, A, B, cnt_n, cnt_t, sp_wide)
+			if (FAST) { MRT_OCT_SWITCH(oct_a, rows_walk_wide_whole, rows, p.query_mask, A, B, cnt_n, cnt_t, sp_wide) }
+			else { MRT_OCT_SWITCH(oct_a, rows_walk_wide, rows, p.query_mask, A, B, cnt_n, cnt_t, sp_wide) }
 		}
 		done_a = done_b = true;
 		if (FAST) { rows_fast_records<STREAM>(w, A, B); return true; }
